@@ -8,12 +8,17 @@ Pioneer-arm envs IN TOTAL.  At N=1 they all live on one GPU; at N>1 the env axis
 contiguous blocks over the ranks (65 536 / N per GPU, global env ids, no data-path collective — envs
 are independent), so scaling is "strong" and `value` = 65 536 x K / (max over ranks of the wall time).
 
-Timed region: after W warm-up steps, blocks of EXACTLY K steps are enqueued back to back (`repeats` of them, until the series
-lasts >= 60 ms) between barrier + torch.cuda.synchronize() on both sides; `ms_per_step` = max-over-ranks wall time of the series /
-(repeats x K), and HIP events recorded on the launch stream between consecutive blocks give the median block (the roofline's
-duration) and the spread.  `--split 2 --graph 1` steps the batch as TWO handles of n/2 envs (global env ids: the same
-trajectories bit for bit, tests/test_gpu_parity.py) whose launches are independent, each block replayed from a hipGraph; by
-default that form is the `split_streams` leg and the headline is one eager pnr_step launch per step.
+Timed region: after W warm-up steps, EXACTLY K steps are enqueued back to back between barrier + torch.cuda.synchronize() on
+both sides; `ms_per_step` = max-over-ranks wall time / K.  `--split 2 --graph 1` steps the batch as TWO handles of n/2 envs
+(global env ids: the same trajectories bit for bit, tests/test_gpu_parity.py) whose launches are independent, the K steps
+replayed from a hipGraph captured before the timed region; by default that form is the `split_streams` leg and the headline is
+one eager pnr_step launch per step.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, `--dump-outputs DIR` (what the timed path
+computed in its last step: obs / reward / done / truncated of the whole env axis as DIR/<name>.npy in float32, above 64 MB a
+fixed seeded sample of env rows with their ids as env_index.npy) and the line.  `--full` adds the rest: the roofline (HIP events
+on the launch stream between `repeats` back-to-back K-step blocks, until that series lasts >= 60 ms, give the median block and
+the spread), the extra legs below, `cpu_baseline` and `build`.
 
 Launch: `python bench.py --gpus N --steps K --warmup W`.  With N > 1 and no torchrun environment the
 script starts its own N ranks (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -21,7 +26,7 @@ script starts its own N ranks (`python -m torch.distributed.run --nnodes=1 --npr
 relays rank 0's line; started under torch.distributed.run it is one of the ranks.  Rank 0 prints ONE
 JSON line.
 
-Extra legs in the same line, never part of `value`: "fused_rollout" (pnr_rollout, T steps per launch),
+Extra legs in the same line with `--full`, never part of `value`: "fused_rollout" (pnr_rollout, T steps per launch),
 "large_batch" (262 144 envs per launch), "weak_scaling" at N>1 (65 536 envs PER GPU), "dynamics_randomized"
 (BASELINE config[4]), "ppo_loop_f32" (config[2] at N=1: 16 384 envs; config[3] at N>1: 65 536 envs in total,
 the full rollout+learn loop on SURVEY 8(d)'s contract: T = 32, 4 epochs of 32 768-sample minibatches,
@@ -53,6 +58,7 @@ HBM_PEAK_GBPS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MIN_SERIES_S = 0.06        # the timed K-step block is repeated back to back until the series is at least this long ...
 MIN_REPEATS = 5            # ... and at least this often; `ms_per_step` = series wall time / (repeats x K)
 MAX_REPEATS = 20000
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all; a larger env axis is written as a fixed seeded sample of rows
 DYN_PACKED_FRAC = 361.0 / 977.0                 # v_pk_*_f32 share of the dynamics sub-step loop's VALU instructions (tools/isa_loop_mix.py)
 DYN_COUNTERS = "r05_e_dyn_sq_counters.json"      # tools/dyn_counters_summary.py (VALU instructions per launch of the dynamics kernel)
 
@@ -104,6 +110,11 @@ def parse_args(argv=None):
                     help="N = 1: also report BASELINE config[3] whole on ONE GPU (65 536 envs, T = 32, 32 768-sample minibatches) at both "
                          "precisions as \"ppo_loop_65536\": the first point of SURVEY 8(d)'s 1/2/4/8 table")
     ap.add_argument("--ppo-timeout", type=float, default=300.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the roofline's block series, the extra legs (the options above), "
+                         "cpu_baseline and the build check; a plain run times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -273,6 +284,10 @@ def run_rank(args):
     if args.gpus != world:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
         return 2
+    if args.steps < 1 or args.steps % max(1, args.fused):
+        print(f"bench.py: --steps {args.steps} must be a positive multiple of --fused {args.fused} (the timed steps are exactly --steps)",
+              file=sys.stderr)
+        return 2
     if os.environ.get("PNR_BENCH_DRYRUN") == "1":
         return dry_run(args, rank, world)
 
@@ -368,9 +383,17 @@ def run_rank(args):
                 "source": "VALU wave-instructions per 65 536-env launch from " + src + "; duration = this run's HIP events; peak = one "
                           "wave64 VALU instruction per 2 cycles per SIMD at 2.4 GHz; one wave per SIMD can issue one per 4"}
 
+    def timed_steps(block, K):
+        """The headline's timed region: EXACTLY K steps, barrier + synchronize on both sides, wall time = max over ranks."""
+        barrier()
+        t0 = time.perf_counter()
+        block(K)
+        barrier()
+        return max_over_ranks(time.perf_counter() - t0)
+
     def timed_series(block, K):
-        """The contract's timed region: EXACTLY K steps per block, barrier + synchronize on both sides of the series, wall
-        time = max over ranks.  A K-step block is short (20 steps = 0.2 ms), so the block is repeated back to back —
+        """The extra legs' timed region and the headline's roofline (--full): EXACTLY K steps per block, barrier + synchronize
+        on both sides of the series, wall time = max over ranks.  A K-step block is short (20 steps = 0.2 ms), so the block is repeated back to back —
         `repeats` times, until the series lasts MIN_SERIES_S — with a HIP event on the launch stream between consecutive
         blocks: `ms_per_step` = series wall time / (repeats x K), and the per-block event times give the median block
         (the roofline's duration) and the spread.  Returns a dict."""
@@ -414,6 +437,7 @@ def run_rank(args):
             e0 = self.envs[0]
             self.lib = e0.lib
             fm_o, fm_a = e0.feature_major_obs, e0.feature_major_act
+            self.feature_major_obs = fm_o
             n_act = max(n_act, Tl)
             ring = max(ring, Tl)
             ring -= ring % Tl
@@ -476,17 +500,29 @@ def run_rank(args):
             if not self.graph:
                 self._fork_launch_join(K, stream)
                 return
-            gr = self._graphs.get(K)
-            if gr is None:
-                torch.cuda.synchronize(dev)
-                gr = torch.cuda.CUDAGraph()
-                cap = torch.cuda.Stream(dev)
-                with torch.cuda.stream(cap):
-                    gr.capture_begin()
-                    self._fork_launch_join(K, torch.cuda.current_stream(dev))
-                    gr.capture_end()
-                self._graphs[K] = gr
-            gr.replay()
+            self.prepare(K)
+            self._graphs[K].replay()
+
+        def prepare(self, K):
+            """graph=1: capture the K-step block's hipGraph now (capturing launches nothing), so that a timed block is a replay only."""
+            if not self.graph or K in self._graphs:
+                return
+            torch.cuda.synchronize(dev)
+            gr = torch.cuda.CUDAGraph()
+            cap = torch.cuda.Stream(dev)
+            with torch.cuda.stream(cap):
+                gr.capture_begin()
+                self._fork_launch_join(K, torch.cuda.current_stream(dev))
+                gr.capture_end()
+            self._graphs[K] = gr
+
+        def last_step_outputs(self, K):
+            """Host copies of what the last step of the latest K-step block wrote (the ring slice it filled): the arrays a caller of
+            pnr_step / pnr_rollout receives, observations in the leg's layout ([envs, 137], or [137, envs] feature-major)."""
+            sl = ((K // self.T - 1) % (self.ring // self.T)) * self.T + self.T - 1
+            torch.cuda.synchronize(dev)
+            return {"obs": self.obs[sl].cpu().numpy(), "reward": self.rew[sl].cpu().numpy(),
+                    "done": self.done[sl].float().cpu().numpy(), "truncated": self.trunc[sl].float().cpu().numpy()}
 
         def close(self):
             self._graphs.clear()
@@ -500,15 +536,87 @@ def run_rank(args):
             leg.block(W)
         return timed_series(leg.block, K), K, W
 
+    def dump_outputs(arrays, feature_major_obs):
+        """--dump-outputs DIR: this rank's last-step arrays joined with the other ranks' along the global env axis (rank order) and
+        written by rank 0 as DIR/<name>.npy in float32.  Above DUMP_MAX_BYTES in all, a fixed seeded sample of env rows is written,
+        with their global env ids as env_index.npy (float64)."""
+        import numpy as np
+        out_dir = args.dump_outputs
+        os.makedirs(out_dir, exist_ok=True)
+        axis = {k: 1 if (k == "obs" and feature_major_obs) else 0 for k in arrays}
+        if world > 1:
+            part = lambda k, r: os.path.join(out_dir, f".{k}.rank{r}.npy")
+            for k, a in arrays.items():
+                np.save(part(k, rank), a)
+            dist.barrier()
+            if rank == 0:
+                arrays = {k: np.concatenate([np.load(part(k, r)) for r in range(world)], axis=axis[k]) for k in arrays}
+                for k in arrays:
+                    for r in range(world):
+                        os.remove(part(k, r))
+        if rank == 0:
+            index = os.path.join(out_dir, "env_index.npy")
+            if os.path.exists(index):
+                os.remove(index)
+            bytes_per_env = sum(a.size // a.shape[axis[k]] for k, a in arrays.items()) * 4
+            if total_envs * bytes_per_env > DUMP_MAX_BYTES:
+                keep = DUMP_MAX_BYTES // (bytes_per_env + 8)
+                rows = np.sort(np.random.default_rng(0).choice(total_envs, size=keep, replace=False))
+                arrays = {k: np.take(a, rows, axis=axis[k]) for k, a in arrays.items()}
+                np.save(index, rows.astype(np.float64))
+            for k, a in arrays.items():
+                np.save(os.path.join(out_dir, k + ".npy"), a.astype(np.float32))
+        if world > 1:
+            dist.barrier()
+
     split = args.split
     if split < 0:
         split = 1
     use_graph = args.graph if args.graph >= 0 else 0
     simc = SimulationConfig(gravity=args.gravity)
+    K, W = args.steps, args.warmup - args.warmup % T
     main_leg = StepLeg(n, env_start, parts=split, graph=use_graph, Tl=T, ring=args.ring, sim=simc, mode=args.mode, randomize=args.randomize)
-    ts, K, W = run_leg(main_leg, args.steps, args.warmup)
-    elapsed, repeats = ts["block_s"], ts["repeats"]
-    value = float(total_envs) * K / elapsed
+    if W > 0:
+        main_leg.block(W)
+    main_leg.prepare(K)
+    wall = timed_steps(main_leg.block, K)
+    value = float(total_envs) * K / wall
+    if args.dump_outputs:
+        dump_outputs(main_leg.last_step_outputs(K), main_leg.feature_major_obs)
+
+    def headline():
+        """The line of a plain run: the headline figure and the configuration it was measured on."""
+        variant = ("one pnr_step launch per step" if T == 1 else f"one pnr_rollout launch per {T} steps") if split == 1 else \
+            (f"{split} handles of {n // split} envs (contiguous blocks, global env ids), their pnr_step launches independent of each other")
+        variant += "; the timed steps are one hipGraph replay" if use_graph else "; eager launches"
+        return {
+            "metric": "env-steps/sec", "value": value, "unit": "env-steps/s",
+            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": wall / K * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{total_envs} Pioneer-arm envs in total ({n} per GPU on {world} GPU(s)), physics-only step "
+                                   f"(integrate+FK+reward+TimeLimit(500)+auto-reset+obs[137]), random actions U(-a_max,a_max) resident in HBM",
+                       "envs_per_gpu": n, "total_envs": total_envs, "mode": args.mode,
+                       "randomize": bool(args.randomize), "gravity": args.gravity,
+                       "obs_layout": args.obs_layout, "action_layout": args.action_layout,
+                       "steps_per_launch": T, "variant": variant, "handles_per_gpu": split, "hip_graph": bool(use_graph),
+                       "obs_ring_slices": main_leg.ring, "parallelism": f"env-shard x{world}",
+                       "timed_region": f"exactly {K} steps after {W} warm-up steps, between barrier + synchronize; "
+                                       "ms_per_step = wall / steps"},
+        }
+
+    if not args.full:
+        main_leg.close()
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
+
+    # --full: the roofline's figures come from the same K-step block repeated back to back (HIP events between the blocks)
+    ts = timed_series(main_leg.block, K)
+    repeats = ts["repeats"]
     single = None
     if split > 1 or use_graph:
         # the same batch as ONE eager launch per step: the form whose kernel duration rocprofv3 can check directly
@@ -719,25 +827,13 @@ def run_rank(args):
         achieved = algo_bytes / (step_ms * 1e-3) / 1e9
         traffic, traffic_source = looked_up("pmc_traffic.json", [f"{args.mode}:{args.obs_layout}:{n}:{T}", "hbm_bytes_per_launch"])
         kname = "pnr::step_kernel" if args.mode == "kinematic" else "pnr::dyn_step_kernel"
-        variant = ("one pnr_step launch per step" if T == 1 else f"one pnr_rollout launch per {T} steps") if split == 1 else \
-            (f"{split} handles of {n // split} envs (contiguous blocks, global env ids), their pnr_step launches independent of each other")
-        variant += "; each timed block is one hipGraph replay" if use_graph else "; eager launches"
-        out = {
-            "metric": "env-steps/sec", "value": value, "unit": "env-steps/s",
-            "n_gpus": world, "steps": K, "warmup": W, "repeats": repeats, "ms_per_step": elapsed / K * 1e3,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{total_envs} Pioneer-arm envs in total ({n} per GPU on {world} GPU(s)), physics-only step "
-                                   f"(integrate+FK+reward+TimeLimit(500)+auto-reset+obs[137]), random actions U(-a_max,a_max) resident in HBM",
-                       "envs_per_gpu": n, "total_envs": total_envs, "mode": args.mode,
-                       "randomize": bool(args.randomize), "gravity": args.gravity,
-                       "obs_layout": args.obs_layout, "action_layout": args.action_layout,
-                       "steps_per_launch": T, "variant": variant, "handles_per_gpu": split, "hip_graph": bool(use_graph),
-                       "obs_ring_slices": main_leg.ring, "parallelism": f"env-shard x{world}",
-                       "timed_region": f"{repeats} back-to-back blocks of exactly {K} steps between barrier + synchronize; "
-                                       "ms_per_step = wall / (repeats x steps)",
-                       "series_wall_s": ts["wall_s"], "block_event_ms_median": ts["block_ev_ms"],
-                       "block_event_ms_p10_p90": ts["block_ev_ms_p10_p90"], "block_event_spread_p10_p90": ts["block_ev_spread"]},
+        out = headline()
+        out["config"].update({
+            "roofline_series": f"after the timed steps, {repeats} back-to-back blocks of exactly {K} steps between barrier + synchronize, "
+                               "HIP events between the blocks",
+            "series_repeats": repeats, "series_wall_s": ts["wall_s"], "block_event_ms_median": ts["block_ev_ms"],
+            "block_event_ms_p10_p90": ts["block_ev_ms_p10_p90"], "block_event_spread_p10_p90": ts["block_ev_spread"]})
+        out.update({
             "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBPS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
                          "traffic_source": traffic_source,
@@ -748,7 +844,7 @@ def run_rank(args):
                                    + ("; the step's launches overlap, so avg_launch_ms is the time per STEP (all its launches) and the kernel "
                                       "durations of a rocprofv3 trace (which serialises dispatches) do not add up to it: `single_launch` is the "
                                       "same batch as one launch per step, whose duration the trace shows" if split > 1 else "")},
-        }
+        })
         if single:
             out["roofline"]["single_launch"] = single
         if split_leg:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Extract the kinematic chain DATA of the reference's URDF into urdf_chain.json.
 
-Run in the build container (the reference tree is not on the GPU box):
-    python tests/golden/make_urdf_chain.py [/root/reference]
+Run where a checkout of the reference project is at hand:
+    python tests/golden/make_urdf_chain.py REFERENCE_ROOT | FILE.urdf
 Only numbers and names are copied (joint order, types, parents, origins, axes,
 limits, link masses / inertias, collision count); no reference source text.
 """
@@ -11,8 +11,10 @@ import os
 import sys
 import xml.etree.ElementTree as ET
 
-REF = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
-URDF = os.path.join(REF, "pioneer/envs/pioneer/assets/pioneer_knm_6dof.urdf")
+if len(sys.argv) != 2:
+    sys.exit(__doc__)
+REF = sys.argv[1]
+URDF = REF if REF.endswith(".urdf") else os.path.join(REF, "pioneer/envs/pioneer/assets/pioneer_knm_6dof.urdf")
 
 
 def floats(text, default):

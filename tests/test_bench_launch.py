@@ -49,6 +49,13 @@ def test_world_size_mismatch_is_an_error():
     assert res.returncode == 2
 
 
+def test_steps_must_be_a_whole_number_of_launches():
+    """--steps is exactly the number of timed steps: a count no whole number of launches makes is refused, not rounded."""
+    for extra in (["--steps", "0"], ["--fused", "32", "--steps", "40"]):
+        res = _run(extra)
+        assert res.returncode == 2 and "--steps" in res.stderr, (extra, res.returncode, res.stderr[-2000:])
+
+
 def test_a_failing_rank_fails_the_launcher():
     # rank 1 dies before the first barrier: the child's non-zero exit code must come back, with no result line
     res = _run(["--gpus", "2", "--steps", "10"], env_extra={"PNR_BENCH_DRYRUN_FAIL_RANK": "1"})

@@ -10,7 +10,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "64", "--warmup", "8", "--large-envs", "0", "--dynamic-leg", "0", "--fused-leg", "0",
+SMALL = ["--full", "--steps", "64", "--warmup", "8", "--large-envs", "0", "--dynamic-leg", "0", "--fused-leg", "0",
          "--ppo-iters", "1", "--ppo-envs", "2048", "--ppo-minibatch", "8192", "--ppo-large-minibatch", "0"]
 
 
@@ -29,7 +29,7 @@ def test_single_gpu_line_has_the_contract_fields():
     r, _ = _bench(SMALL + ["--cpu-seconds", "1"])
     assert r["metric"] == "env-steps/sec" and r["n_gpus"] == 1 and r["steps"] == 64 and r["warmup"] == 8
     assert r["scaling"] == "strong" and r["config"]["total_envs"] == 65536 and r["config"]["envs_per_gpu"] == 65536
-    assert r["repeats"] >= 5                       # a 64-step block is far below 60 ms: many back-to-back blocks
+    assert r["config"]["series_repeats"] >= 5      # a 64-step block is far below 60 ms: many back-to-back blocks for the roofline
     assert abs(r["value"] - 65536 * 64 / (r["ms_per_step"] * 64e-3)) < 1e-6 * r["value"]
     assert r["config"]["handles_per_gpu"] == 1 and not r["config"]["hip_graph"]
     assert r["split_streams"]["handles_per_gpu"] == 2 and 0.05 < r["split_streams"]["frac"] < 1.0
@@ -54,10 +54,32 @@ def test_single_gpu_line_has_the_contract_fields():
     assert b["binary_is_this_tree"] and b["binary"] == b["tree"] and len(b["env_kernel_sources_sha16"]) == 16
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """Without --full the line is the headline over exactly --steps timed steps, and --dump-outputs writes the last timed step's
+    obs / reward / done / truncated for the whole env axis; the same arguments give the same arrays run after run."""
+    import numpy as np
+    names = ("obs", "reward", "done", "truncated")
+    dumps = []
+    for i in range(2):
+        r, _ = _bench(["--steps", "48", "--warmup", "8", "--dump-outputs", str(tmp_path / str(i))])
+        assert r["metric"] == "env-steps/sec" and r["steps"] == 48 and r["warmup"] == 8 and r["dtype"] == "f32" and r["higher_is_better"]
+        assert abs(r["value"] - 65536 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+        assert not {"roofline", "cpu_baseline", "build", "split_streams", "fused_rollout", "large_batch", "dynamics_randomized",
+                    "ppo_loop_f32", "ppo_loop"} & set(r)
+        dumps.append({k: np.load(tmp_path / str(i) / f"{k}.npy") for k in names})
+    a = dumps[0]
+    assert a["obs"].shape == (65536, 137) and all(a[k].shape == (65536,) for k in names[1:])
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert set(np.unique(a["done"])) <= {0.0, 1.0} and not a["truncated"].any()      # 56 steps: no episode reaches its 500-step limit
+    assert np.abs(a["obs"]).max() > 0
+    for k in names:
+        assert np.array_equal(a[k], dumps[1][k]), k
+
+
 def test_config3_anchor_and_dynamics_lane_roofline_are_in_the_line():
     """`ppo_loop_65536` (config[3] whole on one GPU, both precisions, each with its roofline), and the dynamics leg's
     second roofline figure in fp32 lane-operations."""
-    r, _ = _bench(["--steps", "64", "--warmup", "8", "--large-envs", "0", "--fused-leg", "0", "--split-leg", "0", "--ppo-iters", "3",
+    r, _ = _bench(["--full", "--steps", "64", "--warmup", "8", "--large-envs", "0", "--fused-leg", "0", "--split-leg", "0", "--ppo-iters", "3",
                    "--ppo-f32", "0", "--ppo-large-minibatch", "0", "--no-cpu-baseline"])
     a = r["ppo_loop_65536"]
     for prec in ("f32", "bf16"):

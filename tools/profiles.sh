@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; RND=${1:-r04}; TAG=${2:-x}; shift 2 || true
 WHAT="${*:-main dyn dyntraffic ppo learner}"
 O=$R/gpurun_out/$RND; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-MAIN="$R/bench.py --steps 2000 --warmup 100 --fused-leg 0 --large-envs 0 --dynamic-leg 0 --split-leg 0 --ppo-iters 0 --no-cpu-baseline"
+MAIN="$R/bench.py --full --steps 2000 --warmup 100 --fused-leg 0 --large-envs 0 --dynamic-leg 0 --split-leg 0 --ppo-iters 0 --no-cpu-baseline"
 DYN="$R/bench.py --mode dynamic --randomize --gravity 9.81 --warmup 20 --no-cpu-baseline --ppo-iters 0 --large-envs 0"
 prof() { # name, rocprof args..., -- program args
   name=$1; shift
