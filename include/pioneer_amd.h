@@ -67,11 +67,23 @@ enum pnr_layout {
     PNR_FEATURE_MAJOR = 1  /* [F][num_envs] — feature planes (first Linear as W . X^T)      */
 };
 
-/* The reference's motor forms (Joint.control_position / control_velocity, bullet_scene.py:123-155). */
+/* The reference's motor forms (Joint.control_position / control_velocity, bullet_scene.py:123-155).  0 and 1 are the engine's PD
+ * torque law (pnr_config.control_mode and pnr_set_joint_motor); 2 and 3 are Bullet's velocity-level constraint motor, accepted by
+ * pnr_set_joint_motor only (pnr_create rejects them: the step's law is the PD law). */
 enum pnr_control {
     PNR_CONTROL_POSITION = 0, /* POSITION_CONTROL: positionGain pd_kp, velocityGain pd_kd, force torque_limit, maxVelocity */
-    PNR_CONTROL_VELOCITY = 1  /* VELOCITY_CONTROL: the motor tracks the commanded velocity only (gain pd_kd, force torque_limit) */
+    PNR_CONTROL_VELOCITY = 1, /* VELOCITY_CONTROL: the motor tracks the commanded velocity only (gain pd_kd, force torque_limit) */
+    PNR_CONTROL_POSITION_CONSTRAINT = 2, /* Bullet's POSITION_CONTROL motor: a constraint on the joint velocity (pnr_set_joint_motor) */
+    PNR_CONTROL_VELOCITY_CONSTRAINT = 3  /* Bullet's VELOCITY_CONTROL motor: a constraint on the joint velocity (pnr_set_joint_motor) */
 };
+
+/* Bullet's values for the arguments of a constraint motor (PNR_CONTROL_*_CONSTRAINT) that the caller leaves out (NaN).  RECALLED
+ * from pybullet's setJointMotorControl2 and btMultiBodyJointMotor, NOT verified against Bullet. */
+#define PNR_BULLET_POSITION_GAIN 0.1        /* positionGain (recalled, not verified) */
+#define PNR_BULLET_VELOCITY_GAIN 1.0        /* velocityGain (recalled, not verified) */
+#define PNR_BULLET_TARGET_VELOCITY 0.0      /* targetVelocity (recalled, not verified) */
+#define PNR_BULLET_MAX_FORCE 100000.0       /* force: pybullet's setJointMotorControl2 default (recalled, not verified) */
+#define PNR_BULLET_MAX_VELOCITY 0.0         /* maxVelocity: none (pybullet's -1; recalled, not verified) */
 
 enum pnr_mode {
     PNR_MODE_KINEMATIC = 0, /* the reference's live semantics ("parity mode")   */
@@ -260,14 +272,23 @@ int pnr_world_step(pnr_handle h, float* joint_state, void* stream);
 
 /*
  * Joint.control_position / Joint.control_velocity (bullet_scene.py:123-155 -> setJointMotorControl2) for joint `joint`
- * (0..5, URDF order) of every env of a dynamics-mode handle: control_mode PNR_CONTROL_POSITION (targetPosition,
- * targetVelocity, positionGain, velocityGain, force, maxVelocity) or PNR_CONTROL_VELOCITY (targetVelocity, force).  An
- * optional argument the caller leaves out is passed as NaN and takes the handle's configured value (pd_kp, pd_kd,
- * torque_limit, max_velocity; targetVelocity: 0).  The motor is the engine's one law,
- *   tau = clip(Kp (r* - q) + kd (clamp(v* + c (r* - q), +-maxVelocity) - qd), +-force)
- * (pnr_config.control_mode's folding, per joint), honoured by pnr_world_step; pnr_step keeps driving every joint from the
- * env's own command state (the reference's act() teleports the joints each step, pioneer_knm_env.py:148).  Host-side and
- * synchronous: takes effect with the next pnr_world_step.  Parity unpinned (Bullet's motor is a velocity-level constraint).
+ * (0..5, URDF order) of every env of a dynamics-mode handle, honoured by pnr_world_step; pnr_step keeps driving every joint from
+ * the env's own command state (the reference's act() teleports the joints each step, pioneer_knm_env.py:148).  Host-side and
+ * synchronous: takes effect with the next pnr_world_step.  Parity unpinned.  Two laws:
+ *
+ * PD torque (PNR_CONTROL_POSITION: targetPosition, targetVelocity, positionGain, velocityGain, force, maxVelocity;
+ * PNR_CONTROL_VELOCITY: targetVelocity, force).  An optional argument left out (NaN) takes the handle's configured value (pd_kp,
+ * pd_kd, torque_limit, max_velocity; targetVelocity: 0).  The engine's one law (pnr_config.control_mode's folding, per joint):
+ *   tau = clip(Kp (r* - q) + kd (clamp(v* + c (r* - q), +-maxVelocity) - qd), +-force);   force <= 0: no cap.
+ *
+ * Bullet's constraint motor (PNR_CONTROL_POSITION_CONSTRAINT: targetPosition required; PNR_CONTROL_VELOCITY_CONSTRAINT:
+ * targetVelocity required).  Each sub-step of length h = timestep, the joint's torque is the one that brings its velocity to
+ *   VELOCITY: rhs = v*        POSITION: rhs = clamp(Kp (r* - q) / h + qd + Kd (v* - qd), +-maxVelocity)  (maxVelocity > 0)
+ * at the end of the sub-step, limited to |tau| <= force, solved jointly with the other constraint joints over the coupled chain
+ * (gravity, contacts, damping, friction and the PD joints' torques all included).  Arguments left out (NaN) take Bullet's values
+ * (PNR_BULLET_*), not the handle's.  force = 0 means NO motor: the joint is free (PD law: force <= 0 means no cap).
+ * PNR_ERR_INVALID, with the motor left as it was, for a NaN or inf required target, an inf targetVelocity, a negative force or a
+ * negative or non-finite gain.
  */
 int pnr_set_joint_motor(pnr_handle h, int32_t joint, int32_t control_mode, double target_position, double target_velocity,
                         double position_gain, double velocity_gain, double max_force, double max_velocity);

@@ -37,7 +37,8 @@ DYN_STATE_WORDS = 36
 PNR_OK = 0
 ENV_MAJOR, FEATURE_MAJOR = 0, 1
 MODE_KINEMATIC, MODE_DYNAMIC = 0, 1
-CONTROL_POSITION, CONTROL_VELOCITY = 0, 1
+CONTROL_POSITION, CONTROL_VELOCITY = 0, 1                                   # the engine's PD torque law
+CONTROL_POSITION_CONSTRAINT, CONTROL_VELOCITY_CONSTRAINT = 2, 3             # Bullet's constraint motor (set_joint_motor only)
 
 
 class PnrError(RuntimeError):

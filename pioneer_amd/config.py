@@ -125,6 +125,17 @@ class EngineConfig:
     pd_inertia_scaled: bool = False
     # further static bodies (up to 8): planes of any normal, oriented boxes, spheres — see SceneBody
     scene: Tuple[SceneBody, ...] = ()
+    # the law behind the facade's Joint.control_position / control_velocity (world.step() only; the step's law is the PD law
+    # above either way): "pd" = that PD torque law with this config's gains for omitted arguments; "constraint" = Bullet's
+    # velocity-level constraint motor with Bullet's defaults (pnr_set_joint_motor).  Python-side only: not part of pnr_config.
+    joint_motor: str = "pd"
+
+    def __post_init__(self):
+        if self.joint_motor not in _JOINT_MOTORS:
+            raise ValueError(f"joint_motor must be one of {sorted(_JOINT_MOTORS)}, not {self.joint_motor!r}")
+
+
+_JOINT_MOTORS = ("pd", "constraint")
 
 
 _LAYOUTS = {"env_major": _lib.ENV_MAJOR, "feature_major": _lib.FEATURE_MAJOR}

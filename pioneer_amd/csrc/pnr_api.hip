@@ -232,7 +232,7 @@ static void fill_base(pnr_handle h)
             JointMotorTable& W = h->motors;
             W.kp[i] = c.teleport ? 0.f : D.kp_eff; W.kd[i] = c.teleport ? 0.f : (float)c.pd_kd; W.cpos[i] = D.c_pos; W.vcap[i] = D.v_cap;
             W.tcap[i] = c.torque_limit > 0 ? (float)c.torque_limit : INFINITY;
-            W.r_ref[i] = 0.f; W.v_ref[i] = 0.f; W.from_cmd[i] = 1;
+            W.r_ref[i] = 0.f; W.v_ref[i] = 0.f; W.from_cmd[i] = 1; W.kind[i] = kMotorPD;
         }
     }
     D.link_contacts = c.link_contacts ? 1 : 0;
@@ -498,12 +498,47 @@ static int launch_step(pnr_handle h, int T, const float* actions, float* obs, fl
     return PNR_OK;
 }
 
+// PNR_CONTROL_*_CONSTRAINT (the header's second law): everything is checked before the table is touched
+static int set_constraint_motor(pnr_handle h, int joint, bool position, double target_position, double target_velocity,
+                                double position_gain, double velocity_gain, double max_force, double max_velocity)
+{
+    const auto pick = [](double given, double dflt) { return given == given ? given : dflt; };
+    if (position ? !std::isfinite(target_position) : !std::isfinite(target_velocity))
+        return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: the %s target must be finite", position ? "position" : "velocity");
+    const double vt = pick(target_velocity, PNR_BULLET_TARGET_VELOCITY);
+    const double kp = pick(position_gain, PNR_BULLET_POSITION_GAIN), kd = pick(velocity_gain, PNR_BULLET_VELOCITY_GAIN);
+    const double fmax = pick(max_force, PNR_BULLET_MAX_FORCE), vmax = pick(max_velocity, PNR_BULLET_MAX_VELOCITY);
+    if (!std::isfinite(vt)) return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: targetVelocity must be finite");
+    if (!std::isfinite(kp) || !std::isfinite(kd) || kp < 0 || kd < 0)
+        return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: gains must be finite and >= 0 (%g, %g)", kp, kd);
+    if (!(fmax >= 0)) return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: force must be >= 0 (%g)", fmax);
+    JointMotorTable& W = h->motors;
+    W.from_cmd[joint] = 0;
+    W.cpos[joint] = 0.f;
+    if (fmax == 0) {                      // Bullet: no motor, the joint is free (as the PD law with zero gains and no cap)
+        W.kind[joint] = kMotorPD;
+        W.kp[joint] = 0.f; W.kd[joint] = 0.f; W.vcap[joint] = INFINITY; W.tcap[joint] = INFINITY;
+        W.r_ref[joint] = 0.f; W.v_ref[joint] = 0.f;
+        return PNR_OK;
+    }
+    W.kind[joint] = position ? kMotorPositionConstraint : kMotorVelocityConstraint;
+    W.kp[joint] = (float)kp; W.kd[joint] = (float)kd;
+    W.vcap[joint] = (position && vmax > 0) ? (float)vmax : INFINITY;
+    W.tcap[joint] = (float)fmax;
+    W.r_ref[joint] = position ? (float)target_position : 0.f;
+    W.v_ref[joint] = (float)vt;
+    return PNR_OK;
+}
+
 int pnr_set_joint_motor(pnr_handle h, int joint, int control_mode, double target_position, double target_velocity,
                         double position_gain, double velocity_gain, double max_force, double max_velocity)
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (h->cfg.mode != PNR_MODE_DYNAMIC) return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: motors exist in dynamics mode only");
     if (joint < 0 || joint >= kDof) return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: joint %d out of [0, 6)", joint);
+    if (control_mode == PNR_CONTROL_POSITION_CONSTRAINT || control_mode == PNR_CONTROL_VELOCITY_CONSTRAINT)
+        return set_constraint_motor(h, joint, control_mode == PNR_CONTROL_POSITION_CONSTRAINT, target_position, target_velocity,
+                                    position_gain, velocity_gain, max_force, max_velocity);
     if (control_mode != PNR_CONTROL_POSITION && control_mode != PNR_CONTROL_VELOCITY)
         return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: control_mode %d", control_mode);
     const pnr_config& c = h->cfg;
@@ -523,6 +558,7 @@ int pnr_set_joint_motor(pnr_handle h, int joint, int control_mode, double target
     W.r_ref[joint] = velocity ? 0.f : (float)target_position;
     W.v_ref[joint] = (float)pick(target_velocity, 0.0);
     W.from_cmd[joint] = 0;
+    W.kind[joint] = kMotorPD;
     return PNR_OK;
 }
 
@@ -543,10 +579,17 @@ int pnr_world_step(pnr_handle h, float* joint_state, void* stream)
     const DynParams& D = h->dbase;
     const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
     const bool ct = D.has_ground || D.has_box || D.n_scene > 0;
+    bool cm = false;                      // a constraint motor anywhere: the instantiation with motor_constraints
+    for (int i = 0; i < kDof; ++i) cm = cm || h->motors.kind[i] != kMotorPD;
     // (always the instantiation that reads the per-env link scales: without randomisation they are stored as 1)
-#define PNR_WORLD_LAUNCH(C) hipLaunchKernelGGL((dyn_world_kernel<true, C>), grid, dim3(kWave), 0, st, h->state, h->dyn, (long long)h->n, D, h->motors)
-    if (D.inertia_scaled) { if (ct) PNR_WORLD_LAUNCH(3); else PNR_WORLD_LAUNCH(2); }
-    else { if (ct) PNR_WORLD_LAUNCH(1); else PNR_WORLD_LAUNCH(0); }
+#define PNR_WORLD_LAUNCH(C, M) hipLaunchKernelGGL((dyn_world_kernel<true, C, M>), grid, dim3(kWave), 0, st, h->state, h->dyn, (long long)h->n, D, h->motors)
+    if (cm) {
+        if (D.inertia_scaled) { if (ct) PNR_WORLD_LAUNCH(3, true); else PNR_WORLD_LAUNCH(2, true); }
+        else { if (ct) PNR_WORLD_LAUNCH(1, true); else PNR_WORLD_LAUNCH(0, true); }
+    } else {
+        if (D.inertia_scaled) { if (ct) PNR_WORLD_LAUNCH(3, false); else PNR_WORLD_LAUNCH(2, false); }
+        else { if (ct) PNR_WORLD_LAUNCH(1, false); else PNR_WORLD_LAUNCH(0, false); }
+    }
 #undef PNR_WORLD_LAUNCH
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;

@@ -62,10 +62,14 @@ struct DynParams {
 // pnr_world_step (World.step, bullet_scene.py:273-275): the motor of every joint as Joint.control_position / control_velocity
 // left it (bullet_scene.py:123-155), in the terms of the one motor law above — the same for every env of the handle.  A joint
 // nobody commanded keeps the handle's own motor (DynParams), tracking the env's command state r, v (from_cmd).
+// kind != kMotorPD: Bullet's velocity-level constraint motor instead (PNR_CONTROL_*_CONSTRAINT, motor_constraints below); its
+// entries are then kp = positionGain, kd = velocityGain, vcap = maxVelocity (+inf: none), tcap = force (> 0), r_ref, v_ref.
+enum : int { kMotorPD = 0, kMotorPositionConstraint = 1, kMotorVelocityConstraint = 2 };
 struct JointMotorTable {
     float kp[kDof], kd[kDof], cpos[kDof], vcap[kDof], tcap[kDof];   // kp_eff, kd, c_pos, v_cap, torque cap (+inf: none) per joint
     float r_ref[kDof], v_ref[kDof];                                  // targetPosition / targetVelocity
     int from_cmd[kDof];                                              // 1: targets = the env's own r, v (no per-joint command)
+    int kind[kDof];                                                  // kMotorPD | kMotor*Constraint
 };
 
 constexpr float kFrictionEps = 0.05f;   // smooth sign(qd) = qd / sqrt(qd^2 + eps^2)
@@ -319,6 +323,35 @@ __device__ __forceinline__ M3 mul_rx(const M3& m)
     return {-1.f * tt.r0, -1.f * tt.r1, -1.f * tt.r2};
 }
 
+// IP += X^T Ia X: body J's (articulated or composite) inertia, in J's frame, rotated into the parent's orientation and shifted
+// to the parent's origin:  C_p = C', B_p = B' + rx C', A_p = A' - P - P^T - (rx C') rx  with P = B' rx
+template <int J>
+__device__ __forceinline__ void fold_inertia(const SIp& Ia, float cJ, float sJ, SIp& IP)
+{
+    constexpr int AXJ = (int)kJoints[J].axis;
+    const SIp I1 = rot_inertia<AXJ>(Ia, cJ, sJ);
+    const M3 C1 = unpackC(I1), B1 = unpackB(I1);
+    const M3 T = rx_mul<J>(C1);
+    const M3 Pm = mul_rx<J>(B1);
+    const M3 Q = mul_rx<J>(T);
+    static_for<3>([&](auto i_) {
+        constexpr int i = decltype(i_)::value;
+        IP.bd[i] += I1.bd[i] + mc<i, i>(T);
+        static_for<3>([&](auto j_) {
+            constexpr int j = decltype(j_)::value;
+            if constexpr (j >= i) {
+                IP.ac[SIDX<i, j>] += I1.ac[SIDX<i, j>];
+                IP.ac[SIDX<i, j>].x -= mc<i, j>(Pm) + mc<j, i>(Pm) + mc<i, j>(Q);
+            }
+            if constexpr (j > i) {
+                IP.bo[OIDX<i, j>] += I1.bo[OIDX<i, j>];
+                IP.bo[OIDX<i, j>].x += mc<i, j>(T);
+                IP.bo[OIDX<i, j>].y += mc<j, i>(T);
+            }
+        });
+    });
+}
+
 struct DynBody {   // what pass 3 needs from pass 2
     P3 U;          // (Ua_i, Ul_i)
     float D, u;
@@ -397,30 +430,8 @@ __device__ __forceinline__ void aba_inward(const SIp& IA, const P3& pA, const P3
         });
         pr<i>(pa) = acc;
     });
-    // rotate into the parent's orientation, then shift to the parent's origin:
-    //   C_p = C', B_p = B' + rx C', A_p = A' - P - P^T - (rx C') rx  with P = B' rx
+    fold_inertia<J>(Ia, cJ, sJ, IP);
     constexpr int AXJ = (int)kJoints[J].axis;
-    const SIp I1 = rot_inertia<AXJ>(Ia, cJ, sJ);
-    const M3 C1 = unpackC(I1), B1 = unpackB(I1);
-    const M3 T = rx_mul<J>(C1);
-    const M3 Pm = mul_rx<J>(B1);
-    const M3 Q = mul_rx<J>(T);
-    static_for<3>([&](auto i_) {
-        constexpr int i = decltype(i_)::value;
-        IP.bd[i] += I1.bd[i] + mc<i, i>(T);
-        static_for<3>([&](auto j_) {
-            constexpr int j = decltype(j_)::value;
-            if constexpr (j >= i) {
-                IP.ac[SIDX<i, j>] += I1.ac[SIDX<i, j>];
-                IP.ac[SIDX<i, j>].x -= mc<i, j>(Pm) + mc<j, i>(Pm) + mc<i, j>(Q);
-            }
-            if constexpr (j > i) {
-                IP.bo[OIDX<i, j>] += I1.bo[OIDX<i, j>];
-                IP.bo[OIDX<i, j>].x += mc<i, j>(T);
-                IP.bo[OIDX<i, j>].y += mc<j, i>(T);
-            }
-        });
-    });
     const P3 p1 = rotp<AXJ>(pa, cJ, sJ);
     const V3 rxf = cross_r<J>(lin(p1));
     pP = pP + p1;
@@ -655,6 +666,150 @@ __device__ __forceinline__ void aba(const DynParams& D, const DynModel& M, const
 }
 
 // ---------------------------------------------------------------------------------
+// Bullet's joint motor (btMultiBodyJointMotor, pybullet's setJointMotorControl2): a velocity-level constraint per motorised
+// joint, solved per sub-step of length h over the coupled chain (pnr_set_joint_motor's PNR_CONTROL_*_CONSTRAINT).  With S the
+// constraint joints, qdd_free the ABA with tau_S = 0 and M the joint-space mass matrix, tau_S solves the boxed problem
+//   qd+ = qd + h (qdd_free + M^-1 tau),   per i in S: qd+_i = rhs_i with |tau_i| < F_i, or tau_i = +-F_i with qd+_i short of
+//   rhs_i on that side.
+// Active-set solve in the unknowns dv = qd+ - (qd + h qdd_free) and tau, with M dv = h tau (tau = 0 off S): a FREE joint has
+// its dv known (rhs - b), every other joint its tau (0, or +-F when clamped).  The known dv are moved to the right-hand side,
+// which leaves an SPD system G dv = r (M's block over the unknown dv, identity rows for the known ones), factored by a 6x6
+// Cholesky with compile-time indices — the per-lane free / clamped pattern only selects entries, so nothing is indexed at run
+// time.  Each pass clamps the free joints whose torque exceeds F and frees the clamped ones whose velocity passed rhs; at most
+// kMotorPasses passes (the last one's solve stands if the pattern still changed).
+// ---------------------------------------------------------------------------------
+constexpr int kMotorPasses = 2 * kDof;
+
+// packed lower triangle of a symmetric 6x6
+template <int I, int J> constexpr int TRI = I >= J ? I * (I + 1) / 2 + J : J * (J + 1) / 2 + I;
+constexpr int kTri = kDof * (kDof + 1) / 2;
+
+// the force transform of joint J: body J's frame -> its parent's (as pass 2 of the ABA carries the bias force)
+template <int J>
+__device__ __forceinline__ P3 force_to_parent(const P3& f, float c, float s)
+{
+    constexpr int AXJ = (int)kJoints[J].axis;
+    P3 p = rotp<AXJ>(f, c, s);
+    const V3 rxf = cross_r<J>(lin(p));
+    p.x.x += rxf.x; p.y.x += rxf.y; p.z.x += rxf.z;
+    return p;
+}
+
+// H = M(q) by the composite-rigid-body algorithm on the ABA's own rigid-body inertias and joint transforms
+__device__ __forceinline__ void mass_matrix(const DynModel& M, const float (&c)[kDof], const float (&s)[kDof], float (&H)[kTri])
+{
+    const P3 v0 = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+    SIp IC; P3 unused;
+    rigid_body<kDof - 1>(M, v0, IC, unused);
+    static_for<kDof>([&](auto t_) {
+        constexpr int i = kDof - 1 - decltype(t_)::value;
+        constexpr int k = (int)kJoints[i].axis;
+        P3 F;                                                         // IC_i S_i: (A_jk, B_kj), as U in aba_inward
+        static_for<3>([&](auto j_) {
+            constexpr int j = decltype(j_)::value;
+            pr<j>(F) = (f2){IC.ac[SIDX<j, k>].x, bget<k, j>(IC)};
+        });
+        H[TRI<i, i>] = pc<k>(F).x;
+        static_for<i>([&](auto u_) {                                  // up the chain: H_{i, j-1} = S_{j-1}^T X^T ... F
+            constexpr int j = i - decltype(u_)::value;
+            F = force_to_parent<j>(F, c[j], s[j]);
+            H[TRI<i, j - 1>] = pc<(int)kJoints[j - 1].axis>(F).x;
+        });
+        if constexpr (i > 0) {
+            SIp IP;
+            rigid_body<i - 1>(M, v0, IP, unused);
+            fold_inertia<i>(IC, c[i], s[i], IP);
+            IC = IP;
+        }
+    });
+}
+
+// x = G^-1 r for an SPD G (packed lower triangle, overwritten by its Cholesky factor)
+__device__ __forceinline__ void chol_solve6(float (&G)[kTri], const float (&r)[kDof], float (&x)[kDof])
+{
+    float inv[kDof];                                                  // 1 / L_jj
+    static_for<kDof>([&](auto j_) {
+        constexpr int j = decltype(j_)::value;
+        float d = G[TRI<j, j>];
+        static_for<j>([&](auto k_) { constexpr int k = decltype(k_)::value; d -= G[TRI<j, k>] * G[TRI<j, k>]; });
+        inv[j] = __builtin_amdgcn_rsqf(d);
+        static_for<kDof - 1 - j>([&](auto o_) {
+            constexpr int i = j + 1 + decltype(o_)::value;
+            float a = G[TRI<i, j>];
+            static_for<j>([&](auto k_) { constexpr int k = decltype(k_)::value; a -= G[TRI<i, k>] * G[TRI<j, k>]; });
+            G[TRI<i, j>] = a * inv[j];
+        });
+    });
+    float y[kDof];
+    static_for<kDof>([&](auto i_) {                                   // L y = r
+        constexpr int i = decltype(i_)::value;
+        float a = r[i];
+        static_for<i>([&](auto k_) { constexpr int k = decltype(k_)::value; a -= G[TRI<i, k>] * y[k]; });
+        y[i] = a * inv[i];
+    });
+    static_for<kDof>([&](auto t_) {                                   // L^T x = y
+        constexpr int i = kDof - 1 - decltype(t_)::value;
+        float a = y[i];
+        static_for<kDof - 1 - i>([&](auto o_) { constexpr int k = i + 1 + decltype(o_)::value; a -= G[TRI<k, i>] * x[k]; });
+        x[i] = a * inv[i];
+    });
+}
+
+// qdd: in qdd_free (the constraint joints' motor torque 0), out qdd_free + M^-1 tau_S.  q, qd: the sub-step's start.
+__device__ __forceinline__ void motor_constraints(const DynParams& D, const DynModel& M, const float (&c)[kDof], const float (&s)[kDof],
+                                                  const float (&q)[kDof], const float (&qd)[kDof], const JointMotorTable& W,
+                                                  float inv_h, float (&qdd)[kDof])
+{
+    float H[kTri];
+    mass_matrix(M, c, s, H);
+    const float h = D.dt_sub;
+    float d[kDof], rhs[kDof], b[kDof], tcl[kDof];                    // dv of a free joint, its target, the free velocity, clamped tau
+    bool in_s[kDof], fr[kDof];                                        // in S (wave-uniform), free (per lane)
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) {
+        in_s[i] = W.kind[i] != kMotorPD;
+        const float vp = W.kp[i] * (W.r_ref[i] - q[i]) * inv_h + qd[i] + W.kd[i] * (W.v_ref[i] - qd[i]);
+        rhs[i] = W.kind[i] == kMotorVelocityConstraint ? W.v_ref[i] : fminf(fmaxf(vp, -W.vcap[i]), W.vcap[i]);
+        b[i] = qd[i] + h * qdd[i];
+        d[i] = rhs[i] - b[i];
+        fr[i] = in_s[i];
+        tcl[i] = 0.f;
+    }
+    float dv[kDof];
+    for (int pass = 0;; ++pass) {
+        float G[kTri], r[kDof];
+        static_for<kDof>([&](auto i_) {
+            constexpr int i = decltype(i_)::value;
+            float acc = h * tcl[i];
+            static_for<kDof>([&](auto j_) {
+                constexpr int j = decltype(j_)::value;
+                if constexpr (j <= i) G[TRI<i, j>] = (fr[i] || fr[j]) ? (i == j ? 1.f : 0.f) : H[TRI<i, j>];
+                acc -= fr[j] ? H[TRI<i, j>] * d[j] : 0.f;
+            });
+            r[i] = fr[i] ? d[i] : acc;
+        });
+        chol_solve6(G, r, dv);
+        bool changed = false;
+        static_for<kDof>([&](auto i_) {
+            constexpr int i = decltype(i_)::value;
+            if (in_s[i]) {
+                float ht = 0.f;                                       // h tau_i = (M dv)_i
+                static_for<kDof>([&](auto j_) { constexpr int j = decltype(j_)::value; ht += H[TRI<i, j>] * dv[j]; });
+                const float vn = b[i] + dv[i];
+                if (fr[i]) {
+                    if (fabsf(ht) > h * W.tcap[i]) { fr[i] = false; tcl[i] = ht > 0.f ? W.tcap[i] : -W.tcap[i]; changed = true; }
+                } else if (tcl[i] > 0.f ? vn > rhs[i] : vn < rhs[i]) {
+                    fr[i] = true; changed = true;
+                }
+            }
+        });
+        if (!changed || pass == kMotorPasses - 1) break;
+    }
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) qdd[i] += dv[i] * inv_h;
+}
+
+// ---------------------------------------------------------------------------------
 // Phase A of a dynamics step for ONE env in this lane: kinematic command integration (the
 // parity-mode integrator) + nsub sub-steps of ABA + PD.  In: the env's two state records as they
 // lie in HBM (k0/k1/k2[p], see load_state_raw).  Out: the records with a, v, r updated, and the
@@ -751,7 +906,9 @@ __device__ __forceinline__ void dyn_lane_load(const DynLead& in, long long base,
 constexpr int kDynStageWords = 33;
 
 // WORLD (pnr_world_step): the sub-steps alone — no command integration, no teleport — with the per-joint motor table W.
-template <int PHYS, bool WORLD = false>
+// CMOTOR (WORLD only): W holds constraint motors as well; their joints get no torque of the table's law, and motor_constraints
+// adds their boxed solve to each sub-step's accelerations.
+template <int PHYS, bool WORLD = false, bool CMOTOR = false>
 __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, float (&a)[kDof], float (&v)[kDof],
                                          float (&r)[kDof], float (&q)[kDof], float (&qd)[kDof], const float (&sc)[kNumLinks],
                                          const float (&fric_)[kDof], const float (&damp_)[kDof], const float (&act)[kDof],
@@ -800,6 +957,7 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
     f2 cs[kDof];
 #pragma unroll
     for (int i = 0; i < kDof; ++i) { float sn, cn; sincos_bounded(q[i], sn, cn); cs[i] = (f2){cn, sn}; }
+    [[maybe_unused]] const float inv_h = CMOTOR ? 1.0f / D.dt_sub : 0.f;
     for (int k = 0; k < D.nsub; ++k) {
         float tau[kDof], qdd[kDof], ades[kDof];
 #if PNR_DYN_LDS_MODEL
@@ -824,6 +982,9 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
                 tq = W->kp[i] * dq + W->kd[i] * (v_ask - qd[i]);
                 if constexpr ((PHYS & 2) != 0) { ades[i] = tq; tq = 0.f; }
                 else { ades[i] = 0.f; tq = fminf(fmaxf(tq, -W->tcap[i]), W->tcap[i]); }
+                if constexpr (CMOTOR) {
+                    if (W->kind[i] != kMotorPD) { ades[i] = 0.f; tq = 0.f; }
+                }
             } else {
             const float dq = r[i] - q[i];
             const float v_ask = fminf(fmaxf(v[i] + cpos * dq, -vcap), vcap);
@@ -843,6 +1004,7 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
 #pragma unroll
             for (int i = 0; i < kDof; ++i) tc[i] = WORLD ? W->tcap[i] : tcap;
             aba<PHYS>(D, M, c, s, qd, tau, ades, tc, qdd);
+            if constexpr (CMOTOR) motor_constraints(D, M, c, s, q, qd, *W, inv_h, qdd);
         }
 #pragma unroll
         for (int i = 0; i < kDof; ++i) {   // semi-implicit Euler + inelastic joint limits (selects, no branches)

@@ -684,9 +684,10 @@ __global__ __launch_bounds__(kWave) void reset_kernel(const KParams P, const Dyn
 // ---------------------------------------------------------------------------------
 // World.step (bullet_scene.py:273-275), pnr_world_step: frame_skip sub-steps of the simulator and NOTHING else — no command
 // integration, reward, TimeLimit, reset or observation.  One env per lane (the phase-A shape of dyn_step_kernel); the joints'
-// motors are the per-joint table W (Joint.control_position / control_velocity, bullet_scene.py:123-155).
+// motors are the per-joint table W (Joint.control_position / control_velocity, bullet_scene.py:123-155).  CMOTOR: the table holds
+// at least one of Bullet's constraint motors (motor_constraints, pnr_dyn.h); launched only then.
 // ---------------------------------------------------------------------------------
-template <bool RAND, int PHYS>
+template <bool RAND, int PHYS, bool CMOTOR = false>
 __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
                                                           const DynParams D, const JointMotorTable W)
 {
@@ -710,7 +711,7 @@ __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restri
 #pragma unroll
     for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(12 + l) * n + e] : 1.0f;
     const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
-    dyn_core<PHYS, true>(lead, D, a, v, r, q, qd, sc, fric, damp, act, nullptr, &W);
+    dyn_core<PHYS, true, CMOTOR>(lead, D, a, v, r, q, qd, sc, fric, damp, act, nullptr, &W);
 #pragma unroll
     for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(6 + i) * n + e] = qd[i]; }
 }

@@ -14,8 +14,10 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   kinematic mode — a [1, 12] device buffer of this Scene (q | q̇), set to (r, 0) by every ``env.step`` / ``reset_world`` — what act()
   leaves in Bullet — and advanced by ``world.step()``.  ``env.step(a)`` followed by ``env.world.step()`` therefore changes nothing.
 * ``control_position / control_velocity`` (bullet_scene.py:123-155): dynamics mode: the joint's motor for ``world.step()``
-  (``pnr_set_joint_motor``: the engine's one motor law with this joint's targets, gains, force and maxVelocity; an argument left
-  ``None`` takes the EngineConfig's value).  Kinematic mode has no motors (the engine says so).
+  (``pnr_set_joint_motor``).  ``EngineConfig.joint_motor == "pd"``: the engine's PD motor law with this joint's targets, gains,
+  force and maxVelocity; an argument left ``None`` takes the EngineConfig's value.  ``"constraint"``: Bullet's velocity-level
+  constraint motor; an argument left ``None`` takes Bullet's value, and ``max_force=0`` leaves the joint free.  Kinematic mode
+  has no motors (the engine says so).
 * bodies: ``create_body_box / plane / sphere`` with ``mass == 0``.  The reference's arm has no ``<collision>`` shapes, so there a
   created body never touches it: in kinematic mode a body is a record (``items_by_name``), as inert as in the reference.  In dynamics
   mode a body with a collision shape becomes a static scene body of the engine (``EngineConfig.scene``; the handle is rebuilt with the
@@ -99,14 +101,19 @@ class Joint:
         self._env._vec.set_joint_motor(*args)
         self._env._motor_cmds[self.index] = args                  # re-applied when the engine handle is rebuilt (a body created later)
 
+    def _constraint(self) -> bool:
+        return self._env._vec.engine_config.joint_motor == "constraint"
+
     def control_position(self, position: float, velocity: Optional[float] = None, max_velocity: Optional[float] = None,
                          max_force: Optional[float] = None, position_gain: Optional[float] = None, velocity_gain: Optional[float] = None):
         """setJointMotorControl2(POSITION_CONTROL, ...) (bullet_scene.py:123-142) for ``world.step()``."""
-        self._set_motor(_lib.CONTROL_POSITION, position, velocity, position_gain, velocity_gain, max_force, max_velocity)
+        mode = _lib.CONTROL_POSITION_CONSTRAINT if self._constraint() else _lib.CONTROL_POSITION
+        self._set_motor(mode, position, velocity, position_gain, velocity_gain, max_force, max_velocity)
 
     def control_velocity(self, velocity: float, max_force: Optional[float] = None):
         """setJointMotorControl2(VELOCITY_CONTROL, ...) (bullet_scene.py:144-155) for ``world.step()``."""
-        self._set_motor(_lib.CONTROL_VELOCITY, None, velocity, None, None, max_force, None)
+        mode = _lib.CONTROL_VELOCITY_CONSTRAINT if self._constraint() else _lib.CONTROL_VELOCITY
+        self._set_motor(mode, None, velocity, None, None, max_force, None)
 
 
 class Scene:

@@ -201,8 +201,10 @@ class PioneerVectorEnv:
 
     def set_joint_motor(self, joint, control_mode, target_position=float("nan"), target_velocity=float("nan"), position_gain=float("nan"),
                         velocity_gain=float("nan"), max_force=float("nan"), max_velocity=float("nan")):
-        """Joint.control_position / control_velocity (bullet_scene.py:123-155; pnr_set_joint_motor) for ``joint`` of every env; NaN = the
-        EngineConfig's value.  Honoured by ``world_step``."""
+        """Joint.control_position / control_velocity (bullet_scene.py:123-155; pnr_set_joint_motor) for ``joint`` of every env.
+        ``control_mode``: ``_lib.CONTROL_POSITION`` / ``CONTROL_VELOCITY`` (the PD torque law; NaN = the EngineConfig's value) or
+        ``_lib.CONTROL_POSITION_CONSTRAINT`` / ``CONTROL_VELOCITY_CONSTRAINT`` (Bullet's constraint motor; NaN = Bullet's value,
+        ``max_force`` 0 = no motor).  Honoured by ``world_step``."""
         self._check_handle()
         self._chk(self.lib.pnr_set_joint_motor(self._h, int(joint), int(control_mode), float(target_position), float(target_velocity),
                                                float(position_gain), float(velocity_gain), float(max_force), float(max_velocity)))
