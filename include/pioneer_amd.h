@@ -42,7 +42,7 @@ extern "C" {
  *      (before `stream`), pnr_mlp_step gained `planes`; pnr_create waits for its zero fill (Conventions)
  *   5  new entry points pnr_world_step, pnr_set_joint_motor, pnr_build_fingerprint; `planes` == 2 now means two SCALED FP16 planes
  *      (was: two bf16 planes) in every pnr_mlp_* call; pnr_mlp_train_step checks every argument before its first launch and
- *      accepts g_head == NULL with w3_partials */
+ *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -51,6 +51,8 @@ extern "C" {
 #define PNR_INFO_DIM 4     /* r_pot, r_step, r_done, dist (numeric subset of   */
                            /* the info dict, pioneer_knm_env.py:167-179)      */
 #define PNR_DYN_STATE_WORDS 36 /* dynamics mode: q[6] qd[6] + 24 params       */
+#define PNR_NUM_LINKS 11       /* pnr_get_link_states: links per env (URDF joint order) */
+#define PNR_LINK_STATE_DIM 13  /* floats per link record                      */
 
 enum pnr_status {
     PNR_OK = 0,
@@ -306,6 +308,28 @@ int pnr_set_state(pnr_handle h, const uint32_t* words_in, void* stream);
  * kinematic mode. */
 int pnr_get_dyn_state(pnr_handle h, float* words_out, void* stream);
 int pnr_set_dyn_state(pnr_handle h, const float* words_in, void* stream);
+
+/*
+ * Item.pose() / Item.velocity() of every link item (bullet_scene.py:53-67 -> getLinkState(computeLinkVelocity=1,
+ * computeForwardKinematics=1)) for every env, in one launch: the world pose and velocity of each URDF link.
+ *   out          [num_envs][PNR_NUM_LINKS][PNR_LINK_STATE_DIM] float32, row-major, 16-byte aligned; nothing past
+ *                num_envs * 143 floats is written.  Record of link k:
+ *                  [0:3]   world position of the link frame              (LinkState.link_world_position)
+ *                  [3:7]   world orientation, quaternion (x, y, z, w), unit norm, w >= 0   (link_world_orientation)
+ *                  [7:10]  world linear velocity of the link frame origin (world_link_linear_velocity)
+ *                  [10:13] world angular velocity                         (world_link_angular_velocity)
+ *                Link k is Bullet's link_index = the URDF joint order: robot:base, rotator1, hinge1, arm1, arm2,
+ *                rotator2, hinge2, arm3, rotator3, effector, pointer.  Link 0 (robot:base) is static: identity at the
+ *                origin, zero velocity.  Every link's inertial origin is its link frame origin and every fixed joint
+ *                has rpy 0, so the link frame is Bullet's COM frame and its velocity the COM velocity.
+ *   joint_state  [num_envs][12] float32 (q[6] | qd[6], the pnr_world_step layout), 16-byte aligned, read only: pure
+ *                kinematics of the given joints, either mode.  NULL: the handle's own joints — dynamics mode the
+ *                simulated q, qd (pnr_get_dyn_state words 0-11); kinematic mode the env's r and v (pnr_get_state
+ *                words 12-17 and 6-11; PNR_ERR_INVALID before the first pnr_reset or pnr_set_state).
+ * Any finite joint value is accepted (full-range sin/cos); non-finite input gives non-finite records, unchecked.
+ * float32 arithmetic.  Parity unpinned (Bullet's own link states are not reproduced bit for bit).
+ */
+int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void* stream);
 
 /* Diagnostic: the engine's float32 sin/cos (the np.sin/np.cos replacement used
  * for obs entries, pioneer_knm_env.py:195-203) over a device array x[n].

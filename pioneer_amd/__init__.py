@@ -8,11 +8,12 @@ package is the host-side mirror of the reference's Python interface.
 from .config import (EngineConfig, PioneerKinematicConfig, RenderConfig, SceneBody, SimulationConfig,  # noqa: F401
                      scene_box, scene_plane, scene_sphere)
 from ._lib import PnrError, build_library, load_library  # noqa: F401
+from .model import LINK_NAMES  # noqa: F401
 
 __all__ = ["EngineConfig", "PioneerKinematicConfig", "RenderConfig", "SimulationConfig", "SceneBody", "scene_box", "scene_plane",
            "scene_sphere",
            "PioneerVectorEnv", "PioneerKinematicEnv", "TimeLimit", "make_env", "make_vector_env", "PioneerRLlibVectorEnv",
-           "PnrError", "build_library", "load_library"]
+           "PnrError", "build_library", "load_library", "LINK_NAMES"]
 
 
 def __getattr__(name):

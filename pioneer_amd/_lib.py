@@ -33,6 +33,8 @@ OBS_DIM = 137
 STATE_WORDS = 24
 INFO_DIM = 4
 DYN_STATE_WORDS = 36
+NUM_LINKS = 11          # pnr_get_link_states: link records per env (Bullet's link_index order, model.LINKS[1:])
+LINK_STATE_DIM = 13     # position[3], quaternion x y z w [4], linear velocity[3], angular velocity[3]
 
 PNR_OK = 0
 ENV_MAJOR, FEATURE_MAJOR = 0, 1
@@ -139,6 +141,7 @@ SIGNATURES = {
     "pnr_set_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_get_dyn_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_dyn_state": (C.c_int, [_VP, _VP, _VP]),
+    "pnr_get_link_states": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_diag_sincos": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, _VP]),
     "pnr_ppo_loss": (C.c_int, [C.c_int64] + [_VP] * 12 + [C.c_float] * 3 + [_VP] * 3 + [C.c_int64, _VP, _VP]),
     "pnr_mlp_pack_elems": (C.c_int64, []),
@@ -169,7 +172,7 @@ SIGNATURES = {
 
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 UNITS = {
-    "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h"],
+    "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_links.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_sampler.h"],
 }
 SOURCES = sorted({f for deps in UNITS.values() for f in deps})      # every file a unit includes: what _stale() watches

@@ -38,6 +38,7 @@
 #include "pnr_device.h"
 #include "pnr_dyn.h"
 #include "pnr_env_kernels.h"
+#include "pnr_links.h"
 
 // =====================================================================================
 // host side
@@ -678,6 +679,25 @@ int pnr_set_dyn_state(pnr_handle h, const float* words_in, void* stream)
     if (h->kin_set) h->ready = true;
     const size_t bytes = sizeof(float) * PNR_DYN_STATE_WORDS * (size_t)h->n;
     HIP_TRY(h, hipMemcpyAsync(h->dyn, words_in, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PNR_OK;
+}
+
+int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!out) return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: null out");
+    if (reinterpret_cast<uintptr_t>(out) & 15u) return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: out must be 16-byte aligned");
+    if (joint_state && (reinterpret_cast<uintptr_t>(joint_state) & 15u))
+        return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: joint_state must be 16-byte aligned");
+    if (!joint_state && !h->dyn && !h->ready)
+        return fail(h, PNR_ERR_INVALID, "pnr_get_link_states before the first pnr_reset (or pnr_set_state)");
+    DeviceGuard g(h->device);
+    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave)), block(kWave);
+    hipStream_t st = (hipStream_t)stream;
+    if (joint_state) hipLaunchKernelGGL(link_state_kernel<kLinkSrcBuffer>, grid, block, 0, st, joint_state, nullptr, out, (long long)h->n);
+    else if (h->dyn) hipLaunchKernelGGL(link_state_kernel<kLinkSrcDyn>, grid, block, 0, st, h->dyn, nullptr, out, (long long)h->n);
+    else hipLaunchKernelGGL(link_state_kernel<kLinkSrcKin>, grid, block, 0, st, nullptr, h->state, out, (long long)h->n);
+    HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }
 

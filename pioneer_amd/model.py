@@ -24,6 +24,9 @@ LINKS: List[str] = ["world", "robot:base", "robot:rotator1", "robot:hinge1", "ro
                     "robot:rotator2", "robot:hinge2", "robot:arm3", "robot:rotator3", "robot:effector",
                     "robot:pointer"]
 
+# the links of pnr_get_link_states / PioneerVectorEnv.link_states, record k = link k: Bullet's link_index (URDF joint order)
+LINK_NAMES: Tuple[str, ...] = tuple(LINKS[1:])
+
 JOINTS: List[JointDef] = [
     JointDef("world_to_base", "fixed", "world", "robot:base"),
     JointDef("robot:base_to_rotator1", "revolute", "robot:base", "robot:rotator1", (0, 0, 0), (0, 0, 1), 3.1416),

@@ -26,17 +26,49 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   mode: the articulated-body sub-steps (gravity, contacts with the scene's bodies, limits, every joint's motor) and nothing else —
   no command integration, reward or observation.  Kinematic mode: each joint carries on at the velocity it was reset with
   (q += q̇ × step_time, stopped at its limit): what Bullet does without gravity, motor torque and collision shapes.
+* links: ``scene.links`` / ``scene.links_by_name`` hold one item per URDF link, as load_scene makes one per joint
+  (bullet_env.py:114-126), and ``joint.item`` is the joint's child link, as in the reference.  ``pose()`` / ``velocity()`` of a
+  link are one engine launch each (``pnr_get_link_states``) for the one env: dynamics mode on the simulated joints; kinematic
+  mode on the simulator's joints above (so after ``env.step`` every link's velocity is 0, and ``reset_state(p, v)`` gives the
+  links downstream of that joint the velocity v moves them with, as in Bullet).  ``reset_pose`` on a link asserts, as the
+  reference's does.  Deviation: link items are NOT in ``scene.items_by_name`` (which holds the created bodies and the target
+  only); the reference's ``items_by_name['robot:pointer']`` is ``links_by_name['robot:pointer']`` here.
+* ``Item.pose()`` is a ``Pose`` (``.xyz``, ``.rpy``), still a 2-tuple (position, orientation); ``Item.velocity()`` a ``Velocity``
+  (linear, angular), zero for created bodies and the target (they are static).
 Build-defined behaviour where the reference delegates to Bullet: parity unpinned, like the rest of the Bullet boundary.
 """
 import dataclasses
 import math
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib, model
 from .config import scene_box, scene_plane, scene_sphere
+
+
+class Pose(NamedTuple):
+    """bullet_scene.py:11-30: a world position and an orientation quaternion (x, y, z, w)."""
+    position: Tuple[float, float, float]
+    orientation: Tuple[float, float, float, float]
+
+    @property
+    def xyz(self) -> Tuple[float, float, float]:
+        return self.position
+
+    @property
+    def rpy(self) -> Tuple[float, float, float]:
+        return Scene.quat2rpy(self.orientation)
+
+
+class Velocity(NamedTuple):
+    """bullet_scene.py:33-36: world linear and angular velocity."""
+    linear: Tuple[float, float, float]
+    angular: Tuple[float, float, float]
+
+
+_ZERO3 = (0.0, 0.0, 0.0)
 
 
 class Item:
@@ -46,16 +78,48 @@ class Item:
         self.name, self.shape, self.collision, self.size = name, shape, bool(collision), tuple(size)
         self._position, self._orientation = tuple(map(float, position)), tuple(map(float, orientation))
 
-    def pose(self):
-        return self._position, self._orientation
+    def pose(self) -> Pose:
+        return Pose(self._position, self._orientation)
+
+    def velocity(self) -> Velocity:
+        return Velocity(_ZERO3, _ZERO3)                      # created bodies are static (mass 0), the target is a marker
 
     def __repr__(self) -> str:
         return f"Item(name={self.name}, shape={self.shape}, position={self._position}, collision={self.collision})"
 
 
+class LinkItem(Item):
+    """A link item of load_scene (bullet_env.py:114-126): Item with a link_index, its pose and velocity from getLinkState
+    (bullet_scene.py:53-67), here one pnr_get_link_states launch."""
+
+    def __init__(self, scene: "Scene", name: str, link_index: int):
+        super().__init__(name, "link", _ZERO3, (0.0, 0.0, 0.0, 1.0), False, ())
+        self._scene, self.link_index = scene, link_index
+
+    def _record(self) -> np.ndarray:
+        vec = self._scene._env._vec
+        js = None if vec.engine_config.mode == "dynamic" else self._scene._bullet
+        return vec.link_states(js)[0, self.link_index].double().cpu().numpy()
+
+    def pose(self) -> Pose:
+        r = self._record()
+        return Pose(tuple(map(float, r[0:3])), tuple(map(float, r[3:7])))
+
+    def velocity(self) -> Velocity:
+        r = self._record()
+        return Velocity(tuple(map(float, r[7:10])), tuple(map(float, r[10:13])))
+
+    def reset_pose(self, position, orientation):
+        raise AssertionError("Position can be reset only for base items: to control linked items use joint methods")   # :69-71
+
+    def __repr__(self) -> str:
+        return f"Item(name={self.name}, link_index={self.link_index})"
+
+
 class Joint:
     def __init__(self, env, index: int, jd: model.JointDef):
         self._env, self.index, self.name = env, index, jd.name
+        self.item: Optional[Item] = None                                       # the child link, set by Scene
         self.joint_type = jd.type
         lo, hi = env.joint_limits()
         self.lower_limit, self.upper_limit = float(lo[index]), float(hi[index])      # the float32 limits the env uses (:56)
@@ -121,8 +185,13 @@ class Scene:
         self._env = env
         self.items: List[Item] = []
         self.items_by_name: Dict[str, Item] = {}
+        # one item per URDF link (Bullet's link_index order); kept out of items_by_name (module docstring)
+        self.links: List[LinkItem] = [LinkItem(self, name, k) for k, name in enumerate(model.LINK_NAMES)]
+        self.links_by_name: Dict[str, LinkItem] = {li.name: li for li in self.links}
         self.joints: List[Joint] = [Joint(env, i, jd) for i, jd in enumerate(model.revolute_joints())]
         self.joints_by_name: Dict[str, Joint] = {j.name: j for j in self.joints}
+        for j, jd in zip(self.joints, model.revolute_joints()):
+            j.item = self.links_by_name[jd.child]                              # the joint's child link (bullet_env.py:120-126)
         # kinematic mode: the simulator's joints (q | qd) as act() leaves them in Bullet; see the module docstring
         self._bullet = torch.zeros((1, 12), dtype=torch.float32, device=env._vec.device)
 

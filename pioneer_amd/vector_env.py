@@ -209,6 +209,22 @@ class PioneerVectorEnv:
         self._chk(self.lib.pnr_set_joint_motor(self._h, int(joint), int(control_mode), float(target_position), float(target_velocity),
                                                float(position_gain), float(velocity_gain), float(max_force), float(max_velocity)))
 
+    def link_states(self, joint_state=None, out=None):
+        """Item.pose() / Item.velocity() of every link of every env (bullet_scene.py:53-67; pnr_get_link_states), one launch:
+        float32 ``[N, 11, 13]`` on the env's device, link k = ``LINK_NAMES[k]``; per link position[3], quaternion (x, y, z, w)
+        with w >= 0 [4], linear velocity of the link frame origin [3], angular velocity [3], all in the world frame.
+        ``joint_state`` (optional, ``[N, 12]`` = q | qd, only read): the kinematics of those joints; None = the handle's own
+        (dynamics mode: the simulated q, qd; kinematic mode: the env's r, v)."""
+        self._check_handle()
+        n = self.num_envs
+        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        shape = (n, _lib.NUM_LINKS, _lib.LINK_STATE_DIM)
+        res = self._new(shape) if out is None else self._in(out, shape, torch.float32, "out")
+        if out is not None:
+            assert res.data_ptr() == out.data_ptr(), "out is written in place: it must already be a contiguous float32 device tensor"
+        self._chk(self.lib.pnr_get_link_states(self._h, _ptr(js), _ptr(res), self._stream()))
+        return res
+
     def observe(self, out=None):
         """observe() without stepping (pioneer_knm_env.py:184-211)."""
         self._check_handle()

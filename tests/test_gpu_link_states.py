@@ -1,0 +1,182 @@
+"""GPU tests of pnr_get_link_states (PioneerVectorEnv.link_states, link items of env.scene): every record against the
+independent float64 reference of tests/link_kinematics_ref.py, for each joint-state source (the kinematic env's r, v; a
+caller's buffer in either mode; a dynamics handle's simulated joints), and the façade's Item.pose() / velocity()."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import link_kinematics_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+ROW = 11 * 13
+LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416], dtype=np.float32)
+
+
+def check_records(rec, q, qd):
+    """rec: engine records [N, 11, 13]; q, qd: the float32 joints they were computed from [N, 6]."""
+    rec = np.asarray(rec, dtype=np.float64)
+    want = ref.link_states(np.asarray(q, dtype=np.float64), np.asarray(qd, dtype=np.float64))
+    assert rec.shape == want.shape and np.isfinite(rec).all()
+    # positions: the existing forward-kinematics bound
+    assert np.abs(rec[..., 0:3] - want[..., 0:3]).max() <= 3e-5
+    # quaternions: canonical (w >= 0), unit, per component.  Where the reference's w is within the bound of 0 the canonical
+    # sign is not determined by float32 arithmetic: there either sign is the same rotation
+    quat, wq = rec[..., 3:7], want[..., 3:7]
+    assert (quat[..., 3] >= 0).all()
+    assert np.abs(np.linalg.norm(quat, axis=-1) - 1.0).max() <= 1e-6
+    err = np.abs(quat - wq).max(axis=-1)
+    near0 = np.abs(wq[..., 3]) <= 2e-6
+    err = np.where(near0, np.minimum(err, np.abs(quat + wq).max(axis=-1)), err)
+    assert err.max() <= 2e-6, f"quaternion error {err.max():.3g}"
+    # velocities, relative to the size of each link's reference vector
+    for lo, tol in ((7, 2e-5), (10, 2e-6)):
+        got, exp = rec[..., lo:lo + 3], want[..., lo:lo + 3]
+        bound = tol * (1.0 + np.linalg.norm(exp, axis=-1))
+        assert (np.abs(got - exp).max(axis=-1) <= bound).all(), f"velocity [{lo}:{lo + 3}] error {np.abs(got - exp).max():.3g}"
+
+
+def kin_joints(env):
+    f = env.get_state().view(torch.float32).cpu().numpy()
+    return f[12:18].T.copy(), f[6:12].T.copy()
+
+
+def dyn_joints(env):
+    d = env.get_dyn_state().cpu().numpy()
+    return d[0:6].T.copy(), d[6:12].T.copy()
+
+
+@pytest.mark.parametrize("n", [1, 37, 64, 1000, 65536])
+def test_kinematic_handle_links_follow_the_env_state(n):
+    from pioneer_amd import PioneerVectorEnv
+    env = PioneerVectorEnv(n, device="cuda:0", seed=3 + n)
+    env.reset()
+    g = torch.Generator(device="cpu").manual_seed(n)
+    amax = torch.from_numpy(env.a_max)
+    for _ in range(4):
+        env.vector_step(((torch.rand(n, 6, generator=g) * 2 - 1) * amax).cuda())
+    rec = env.link_states()
+    assert rec.shape == (n, 11, 13) and rec.dtype == torch.float32 and rec.device == env.device
+    q, qd = kin_joints(env)
+    if n >= 37:
+        assert np.abs(qd).max() > 0.1                                               # the joints are moving
+    rec_np = rec.cpu().numpy()
+    check_records(rec_np, q, qd)
+    obs = env.observe().cpu().numpy()
+    assert np.abs(rec_np[:, 10, 0:3] - obs[:, 126:129]).max() <= 6e-5               # the pointer is the observation's
+    # the raw call writes exactly N x 143 floats: the rest of an oversized buffer keeps its sentinel
+    big = torch.full((n * ROW + 1000,), -7.25, dtype=torch.float32, device=env.device)
+    assert env.lib.pnr_get_link_states(env._h, None, C.c_void_p(big.data_ptr()), env._stream()) == 0
+    torch.cuda.synchronize()
+    big = big.cpu()
+    assert torch.equal(big[:n * ROW], torch.from_numpy(rec_np).reshape(-1))
+    assert (big[n * ROW:] == -7.25).all()
+    env.close()
+
+
+@pytest.mark.parametrize("mode", ["kinematic", "dynamic"])
+@pytest.mark.parametrize("n", [37, 1000])
+def test_explicit_joint_state_beyond_the_limits(mode, n):
+    from pioneer_amd import EngineConfig, PioneerVectorEnv
+    env = PioneerVectorEnv(n, device="cuda:0", seed=11, engine_config=EngineConfig(mode=mode))
+    rng = np.random.default_rng(n)
+    q = rng.uniform(-2.5, 2.5, size=(n, 6)).astype(np.float32) * LIMITS
+    qd = rng.uniform(-10.0, 10.0, size=(n, 6)).astype(np.float32)
+    js = torch.from_numpy(np.concatenate([q, qd], axis=1)).cuda()
+    keep = js.clone()
+    rec = env.link_states(js)                                                        # no reset needed: pure kinematics
+    check_records(rec.cpu().numpy(), q, qd)
+    assert torch.equal(js, keep)                                                     # only read
+    # non-finite input: non-finite records, no error
+    js[0, 2] = float("nan")
+    bad = env.link_states(js).cpu().numpy()
+    assert not np.isfinite(bad[0, 4:]).all() and np.isfinite(bad[1:]).all()
+    # misaligned buffers and a kinematic handle without state are refused
+    from pioneer_amd import PnrError
+    raw = torch.zeros(n * ROW + 4, dtype=torch.float32, device=env.device)
+    assert env.lib.pnr_get_link_states(env._h, C.c_void_p(js.data_ptr()), C.c_void_p(raw.data_ptr() + 4), env._stream()) == -1
+    assert env.lib.pnr_get_link_states(env._h, C.c_void_p(js.data_ptr() + 4), C.c_void_p(raw.data_ptr()), env._stream()) == -1
+    assert env.lib.pnr_get_link_states(env._h, None, None, env._stream()) == -1
+    if mode == "kinematic":
+        with pytest.raises(PnrError, match="before the first pnr_reset"):
+            env.link_states()
+    env.close()
+
+
+def test_dynamics_handle_links_follow_the_simulated_joints():
+    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig, scene_box, scene_plane
+    n = 1000
+    eng = EngineConfig(mode="dynamic", link_contacts=True,
+                       scene=(scene_plane((0.0, 0.0, 1.0), (0.0, 0.0, -2.0)), scene_box((0.5, 0.5, 5.0), (10.0, 5.0, 0.0))))
+    env = PioneerVectorEnv(n, device="cuda:0", seed=5, simulation_config=SimulationConfig(gravity=9.81), engine_config=eng)
+    env.reset()
+    d = env.get_dyn_state()
+    rng = np.random.default_rng(7)
+    d[0:6] = torch.from_numpy((rng.uniform(-0.9, 0.9, size=(n, 6)).astype(np.float32) * LIMITS).T.copy()).cuda()
+    d[6:12] = torch.from_numpy(rng.uniform(-2.0, 2.0, size=(6, n)).astype(np.float32)).cuda()
+    env.set_dyn_state(d)
+    for _ in range(10):
+        env.world_step()
+    rec = env.link_states().cpu().numpy()
+    q, qd = dyn_joints(env)
+    assert np.isfinite(q).all() and np.abs(qd).max() > 0.1
+    check_records(rec, q, qd)
+    env.close()
+
+
+def test_scene_link_items():
+    from pioneer_amd import EngineConfig, PioneerKinematicEnv
+    from pioneer_amd.scene import Pose, Velocity
+    env = PioneerKinematicEnv()
+    names_before = set(env.scene.items_by_name)
+    links = env.scene.links_by_name
+    assert [li.name for li in env.scene.links] == ["robot:base", "robot:rotator1", "robot:hinge1", "robot:arm1", "robot:arm2",
+                                                   "robot:rotator2", "robot:hinge2", "robot:arm3", "robot:rotator3",
+                                                   "robot:effector", "robot:pointer"]
+    pose = links["robot:pointer"].pose()
+    assert isinstance(pose, Pose) and np.abs(np.array(pose.xyz) - env.observe()[126:129]).max() <= 6e-5
+    pos, orn = pose
+    assert len(orn) == 4 and len(pose.rpy) == 3
+    # joint.item is the joint's child link
+    assert [j.item.name for j in env.scene.joints] == ["robot:rotator1", "robot:arm1", "robot:arm2", "robot:rotator2",
+                                                       "robot:arm3", "robot:rotator3"]
+    assert all(j.item is links[j.item.name] for j in env.scene.joints)
+    # resetJointState with a velocity: the links downstream of the joint move, the ones upstream do not
+    j = env.scene.joints_by_name["robot:hinge1_to_arm1"]
+    j.reset_state(0.25, velocity=1.0)
+    b = env.scene._bullet.cpu().numpy()
+    want = ref.link_states(b[:, 0:6].astype(np.float64), b[:, 6:12].astype(np.float64))[0]
+    for k, li in enumerate(env.scene.links):
+        vel = li.velocity()
+        assert isinstance(vel, Velocity)
+        if k < 3:
+            assert vel.linear == (0.0, 0.0, 0.0) and vel.angular == (0.0, 0.0, 0.0), li.name
+        else:
+            assert np.abs(np.array(vel.linear) - want[k, 7:10]).max() <= 2e-5 * (1 + np.linalg.norm(want[k, 7:10]))
+            assert np.abs(np.array(vel.angular) - want[k, 10:13]).max() <= 2e-6 * (1 + np.linalg.norm(want[k, 10:13]))
+            assert np.linalg.norm(vel.angular) > 0.5, li.name
+    assert np.abs(np.array(links["robot:arm1"].pose().xyz) - want[3, 0:3]).max() <= 3e-5
+    # act() teleports the joints with velocity 0: after env.step every link is at rest
+    env.step(env.a_max * 0.3)
+    for li in env.scene.links:
+        vel = li.velocity()
+        assert vel.linear == (0.0, 0.0, 0.0) and vel.angular == (0.0, 0.0, 0.0), li.name
+    assert np.abs(np.array(links["robot:pointer"].pose().xyz) - env.observe()[126:129]).max() <= 6e-5
+    with pytest.raises(AssertionError):
+        links["robot:arm2"].reset_pose((0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0))
+    assert set(env.scene.items_by_name) == names_before == {"target"}
+    assert env.scene.items_by_name["target"].velocity() == Velocity((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
+    env.close()
+    # dynamics mode: the simulated joints
+    dyn = PioneerKinematicEnv(engine_config=EngineConfig(mode="dynamic"))
+    dyn.scene.joints_by_name["robot:arm1_to_arm2"].reset_state(0.4, velocity=-0.7)
+    q, qd = dyn_joints(dyn._vec)
+    want = ref.link_states(q.astype(np.float64), qd.astype(np.float64))[0]
+    for k, li in enumerate(dyn.scene.links):
+        p, vel = li.pose(), li.velocity()
+        assert np.abs(np.array(p.xyz) - want[k, 0:3]).max() <= 3e-5
+        assert np.abs(np.array(vel.linear) - want[k, 7:10]).max() <= 2e-5 * (1 + np.linalg.norm(want[k, 7:10]))
+        assert np.abs(np.array(vel.angular) - want[k, 10:13]).max() <= 2e-6 * (1 + np.linalg.norm(want[k, 10:13]))
+    dyn.close()
