@@ -42,7 +42,7 @@ extern "C" {
  *      (before `stream`), pnr_mlp_step gained `planes`; pnr_create waits for its zero fill (Conventions)
  *   5  new entry points pnr_world_step, pnr_set_joint_motor, pnr_build_fingerprint; `planes` == 2 now means two SCALED FP16 planes
  *      (was: two bf16 planes) in every pnr_mlp_* call; pnr_mlp_train_step checks every argument before its first launch and
- *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states */
+ *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -330,6 +330,58 @@ int pnr_set_dyn_state(pnr_handle h, const float* words_in, void* stream);
  * float32 arithmetic.  Parity unpinned (Bullet's own link states are not reproduced bit for bit).
  */
 int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void* stream);
+
+/*
+ * render('rgb_array') for every env in one launch (bullet_env.py:156-185 -> getCameraImage): one camera shared by all envs,
+ * each env's scene drawn by ray casting against analytic shapes.
+ *   Scene of env k: the URDF's 14 <visual> shapes (boxes, cylinders, the pointer's sphere; their <material> colours) posed by
+ *   the env's joints; the target, a sphere of pnr_config.target_radius at the env's target (pnr_get_state words 18-20); the
+ *   caller's n_bodies static bodies, shared by all envs (planes are infinite).
+ *   joint_state: as pnr_get_link_states ([num_envs][12] q | qd, 16-byte aligned, read only; NULL = the handle's own joints:
+ *   dynamics mode the simulated q, kinematic mode the env's r).
+ *   Camera: view is world -> eye, row-major 4x4 (render.view_matrix): the eye looks along -z with +y up; its 3x3 part must be
+ *   orthonormal (to 1e-5) and its last row is ignored.  Pixel (x, y), row 0 at the top, is the ray through
+ *   ndc (2(x + 0.5)/W - 1, 1 - 2(y + 0.5)/H) under the vertical-fov_y perspective of aspect W/H (render.project).
+ *   Hit rule: per primitive, the entering and the leaving intersection are both candidates; a candidate counts if its eye depth
+ *   lies in (near_clip, far_clip); the nearest opaque candidate wins.  The target is the one translucent surface: if it is
+ *   nearer than the opaque hit, colour = a c_target + (1 - a) c_behind (a = target_rgba[3], blended before quantisation) and
+ *   seg / depth report the target.  Body alpha is ignored (bodies are opaque).
+ *   Shading: c = clamp(rgb (ambient + diffuse max(0, n . l)), 0, 1), n the unit normal turned to face the viewer, l the unit
+ *   light_direction; byte = floor(255 c + 0.5).  Background colour where nothing is hit.
+ *   Outputs (each may be NULL, not all three; each 16-byte aligned; nothing past its last byte is written):
+ *     rgb   [num_envs][height][width][3] uint8 (the reference's np.array(rgb_pixels)[:, :, :3] per env)
+ *     depth [num_envs][height][width] float32: eye depth along the view axis (render.project's depth), +inf where nothing is hit
+ *     seg   [num_envs][height][width] uint8: enum pnr_seg
+ * PNR_ERR_INVALID, no output touched, for: a null handle or params, a wrong struct_size, width or height outside 1..4096, fov_y
+ * outside (0, 180), a near or far clip that is not finite and > 0, near_clip >= far_clip, a non-finite view or one whose 3x3 part
+ * is not orthonormal, a non-finite or zero light_direction, non-finite ambient or diffuse, n_bodies outside 0..PNR_MAX_SCENE, a
+ * bad shape or non-finite / degenerate body data (as pnr_config.scene), misaligned pointers, all outputs NULL, more than 2^31 - 1
+ * tiles of 256 to 1 024 pixels, and a call before the first pnr_reset or pnr_set_state (the target comes from the state).
+ * float32 arithmetic.  Parity unpinned: Bullet's TinyRenderer / OpenGL pixels are not reproduced (no shadows, textures or
+ * anti-aliasing; the shading rule above is the engine's own).
+ */
+enum pnr_seg {
+    PNR_SEG_BACKGROUND = 0,
+    PNR_SEG_LINK0 = 1,       /* + link_index: the URDF link of the visual (2 .. 11: robot:rotator1 .. robot:pointer) */
+    PNR_SEG_TARGET = 12,
+    PNR_SEG_BODY0 = 13       /* + body index (13 .. 20) */
+};
+typedef struct pnr_render_params {
+    uint32_t struct_size;              /* sizeof(pnr_render_params) */
+    int32_t  width, height;            /* 1 .. 4096 each */
+    int32_t  n_bodies;                 /* 0 .. PNR_MAX_SCENE */
+    double   view[16];                 /* world -> eye, row-major 4x4 (render.view_matrix): eye looks along -z, +y up */
+    double   fov_y, near_clip, far_clip;   /* RenderConfig.projection_fov (degrees), projection_near / far */
+    double   light_direction[3];       /* towards the light, world frame (need not be unit) */
+    double   ambient, diffuse;
+    float    background[3];            /* rgb in [0, 1] */
+    float    target_rgba[4];           /* PioneerKinematicConfig.target_rgba */
+    int32_t  reserved;
+    pnr_scene_body bodies[PNR_MAX_SCENE];  /* shape, position, orientation, size as in pnr_config.scene */
+    float    body_rgba[PNR_MAX_SCENE][4];  /* rgb used, alpha ignored */
+} pnr_render_params;
+int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* p, uint8_t* rgb, float* depth, uint8_t* seg,
+               void* stream);
 
 /* Diagnostic: the engine's float32 sin/cos (the np.sin/np.cos replacement used
  * for obs entries, pioneer_knm_env.py:195-203) over a device array x[n].

@@ -58,6 +58,21 @@ class PnrSceneBody(C.Structure):
                 ("size", C.c_double * 3)]
 
 
+# pnr_render's segmentation labels (enum pnr_seg): background, 1 + URDF link index, the target, 13 + static body index
+SEG_BACKGROUND, SEG_LINK0, SEG_TARGET, SEG_BODY0 = 0, 1, 12, 13
+
+
+class PnrRenderParams(C.Structure):
+    """pnr_render_params of include/pioneer_amd.h (pnr_render's camera, shading and static bodies)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("n_bodies", C.c_int32),
+        ("view", C.c_double * 16), ("fov_y", C.c_double), ("near_clip", C.c_double), ("far_clip", C.c_double),
+        ("light_direction", C.c_double * 3), ("ambient", C.c_double), ("diffuse", C.c_double),
+        ("background", C.c_float * 3), ("target_rgba", C.c_float * 4), ("reserved", C.c_int32),
+        ("bodies", PnrSceneBody * MAX_SCENE), ("body_rgba", (C.c_float * 4) * MAX_SCENE),
+    ]
+
+
 class PnrConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
@@ -142,6 +157,7 @@ SIGNATURES = {
     "pnr_get_dyn_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_dyn_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_get_link_states": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
     "pnr_diag_sincos": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, _VP]),
     "pnr_ppo_loss": (C.c_int, [C.c_int64] + [_VP] * 12 + [C.c_float] * 3 + [_VP] * 3 + [C.c_int64, _VP, _VP]),
     "pnr_mlp_pack_elems": (C.c_int64, []),
@@ -172,7 +188,8 @@ SIGNATURES = {
 
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 UNITS = {
-    "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_links.h"],
+    "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_links.h",
+                    "pnr_render.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_sampler.h"],
 }
 SOURCES = sorted({f for deps in UNITS.values() for f in deps})      # every file a unit includes: what _stale() watches

@@ -129,13 +129,19 @@ class EngineConfig:
     # above either way): "pd" = that PD torque law with this config's gains for omitted arguments; "constraint" = Bullet's
     # velocity-level constraint motor with Bullet's defaults (pnr_set_joint_motor).  Python-side only: not part of pnr_config.
     joint_motor: str = "pd"
+    # what the facade's render("rgb_array") draws: "host" = the stick figure of render.py; "engine" = the URDF's visual shapes,
+    # the target and the scene's bodies, one pnr_render launch (PioneerVectorEnv.render_frames).  Python-side only.
+    renderer: str = "host"
 
     def __post_init__(self):
         if self.joint_motor not in _JOINT_MOTORS:
             raise ValueError(f"joint_motor must be one of {sorted(_JOINT_MOTORS)}, not {self.joint_motor!r}")
+        if self.renderer not in _RENDERERS:
+            raise ValueError(f"renderer must be one of {sorted(_RENDERERS)}, not {self.renderer!r}")
 
 
 _JOINT_MOTORS = ("pd", "constraint")
+_RENDERERS = ("host", "engine")
 
 
 _LAYOUTS = {"env_major": _lib.ENV_MAJOR, "feature_major": _lib.FEATURE_MAJOR}

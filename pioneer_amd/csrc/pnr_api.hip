@@ -39,6 +39,7 @@
 #include "pnr_dyn.h"
 #include "pnr_env_kernels.h"
 #include "pnr_links.h"
+#include "pnr_render.h"
 
 // =====================================================================================
 // host side
@@ -697,6 +698,158 @@ int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void
     if (joint_state) hipLaunchKernelGGL(link_state_kernel<kLinkSrcBuffer>, grid, block, 0, st, joint_state, nullptr, out, (long long)h->n);
     else if (h->dyn) hipLaunchKernelGGL(link_state_kernel<kLinkSrcDyn>, grid, block, 0, st, h->dyn, nullptr, out, (long long)h->n);
     else hipLaunchKernelGGL(link_state_kernel<kLinkSrcKin>, grid, block, 0, st, nullptr, h->state, out, (long long)h->n);
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+}  // extern "C"
+
+static bool finite_all(const double* v, int k)
+{
+    for (int i = 0; i < k; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// pnr_render's checks of its params (nothing launched, nothing written on failure) and the kernel's constants built from them
+static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& P)
+{
+    if (p->struct_size != sizeof(pnr_render_params))
+        return fail(h, PNR_ERR_INVALID, "pnr_render: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_render_params));
+    if (p->width < 1 || p->width > 4096 || p->height < 1 || p->height > 4096)
+        return fail(h, PNR_ERR_INVALID, "pnr_render: image size %d x %d outside 1..4096", p->width, p->height);
+    if (!(p->fov_y > 0 && p->fov_y < 180)) return fail(h, PNR_ERR_INVALID, "pnr_render: fov_y must lie in (0, 180) degrees");
+    if (!(std::isfinite(p->near_clip) && std::isfinite(p->far_clip) && p->near_clip > 0 && p->far_clip > 0))
+        return fail(h, PNR_ERR_INVALID, "pnr_render: near_clip and far_clip must be finite and > 0");
+    if (!(p->near_clip < p->far_clip)) return fail(h, PNR_ERR_INVALID, "pnr_render: near_clip must be < far_clip");
+    if (!finite_all(p->view, 16)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite view matrix");
+    const double* V = p->view;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            const double d = V[4 * a] * V[4 * b] + V[4 * a + 1] * V[4 * b + 1] + V[4 * a + 2] * V[4 * b + 2];
+            if (!(std::fabs(d - (a == b ? 1.0 : 0.0)) <= 1e-5))
+                return fail(h, PNR_ERR_INVALID, "pnr_render: the view matrix's rotation is not orthonormal");
+        }
+    if (!finite_all(p->light_direction, 3)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite light_direction");
+    const double ll = std::sqrt(p->light_direction[0] * p->light_direction[0] + p->light_direction[1] * p->light_direction[1] +
+                                p->light_direction[2] * p->light_direction[2]);
+    if (!(ll > 0)) return fail(h, PNR_ERR_INVALID, "pnr_render: zero light_direction");
+    if (!std::isfinite(p->ambient) || !std::isfinite(p->diffuse)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite ambient or diffuse");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->background[k])) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite background");
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(p->target_rgba[k])) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite target_rgba");
+    if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
+        return fail(h, PNR_ERR_INVALID, "pnr_render: n_bodies %d outside 0..%d", p->n_bodies, PNR_MAX_SCENE);
+    for (int b = 0; b < p->n_bodies; ++b) {
+        const pnr_scene_body& S = p->bodies[b];
+        if (S.shape != PNR_SHAPE_PLANE && S.shape != PNR_SHAPE_BOX && S.shape != PNR_SHAPE_SPHERE)
+            return fail(h, PNR_ERR_INVALID, "pnr_render: body %d: bad shape %d", b, S.shape);
+        bool ok = finite_all(S.position, 3) && finite_all(S.orientation, 4) && finite_all(S.size, 3);
+        for (int k = 0; k < 4; ++k) ok = ok && std::isfinite(p->body_rgba[b][k]);
+        if (!ok) return fail(h, PNR_ERR_INVALID, "pnr_render: body %d: non-finite data", b);
+        const double qn = S.orientation[0] * S.orientation[0] + S.orientation[1] * S.orientation[1] +
+                          S.orientation[2] * S.orientation[2] + S.orientation[3] * S.orientation[3];
+        const double sn = S.size[0] * S.size[0] + S.size[1] * S.size[1] + S.size[2] * S.size[2];
+        if (!(qn > 0) || (S.shape == PNR_SHAPE_PLANE && !(sn > 0)) ||
+            (S.shape == PNR_SHAPE_BOX && !(S.size[0] > 0 && S.size[1] > 0 && S.size[2] > 0)) ||
+            (S.shape == PNR_SHAPE_SPHERE && !(S.size[0] > 0)))
+            return fail(h, PNR_ERR_INVALID, "pnr_render: body %d: zero quaternion, normal or size", b);
+    }
+
+    memset(&P, 0, sizeof(P));
+    // the eye axes are the rows of the view rotation; the eye sits at -R^T t
+    double eye[3];
+    for (int k = 0; k < 3; ++k) eye[k] = -(V[k] * V[3] + V[4 + k] * V[7] + V[8 + k] * V[11]);
+    for (int k = 0; k < 3; ++k) {
+        P.eye[k] = (float)eye[k];
+        P.right[k] = (float)V[k]; P.up[k] = (float)V[4 + k]; P.back[k] = (float)V[8 + k];
+        P.light[k] = (float)(p->light_direction[k] / ll);
+        P.bg[k] = p->background[k];
+        P.target_rgb[k] = p->target_rgba[k];
+    }
+    const double tan_half = std::tan(0.5 * p->fov_y * M_PI / 180.0);
+    P.sy = (float)tan_half;
+    P.sx = (float)(tan_half * (double)p->width / (double)p->height);
+    P.near_clip = (float)p->near_clip; P.far_clip = (float)p->far_clip;
+    P.ambient = (float)p->ambient; P.diffuse = (float)p->diffuse;
+    P.target_alpha = p->target_rgba[3];
+    P.target_radius = (float)h->cfg.target_radius;
+    P.W = p->width; P.H = p->height; P.HW = p->width * p->height;
+    // pixels per lane: 4 (1 024-pixel tiles) unless that leaves fewer than ~4 096 workgroups (one env at 1280 x 800: 4 000 of 256)
+    const long long total = h->n * (long long)P.HW;
+    P.ppl = total >= 4096LL * 1024 ? 4 : (total >= 4096LL * 512 ? 2 : 1);
+    const int tile_px = kRenderThreads * P.ppl;
+    P.tiles = (P.HW + tile_px - 1) / tile_px;
+    if (h->n * (long long)P.tiles > 0x7fffffffLL)
+        return fail(h, PNR_ERR_INVALID, "pnr_render: %lld envs x %d tiles exceed one launch", h->n, P.tiles);
+    // the static bodies, in world space once for all envs
+    P.n_static = p->n_bodies;
+    for (int b = 0; b < p->n_bodies; ++b) {
+        const pnr_scene_body& S = p->bodies[b];
+        RenderPrim& Q = P.bodies[b];
+        const double qn = std::sqrt(S.orientation[0] * S.orientation[0] + S.orientation[1] * S.orientation[1] +
+                                    S.orientation[2] * S.orientation[2] + S.orientation[3] * S.orientation[3]);
+        const double x = S.orientation[0] / qn, y = S.orientation[1] / qn, z = S.orientation[2] / qn, w = S.orientation[3] / qn;
+        const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                             2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                             2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+        const double e[3] = {eye[0] - S.position[0], eye[1] - S.position[1], eye[2] - S.position[2]};
+        double rt[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {e[0], e[1], e[2]}, bound = 0;
+        if (S.shape == PNR_SHAPE_BOX) {
+            for (int i = 0; i < 3; ++i)
+                for (int k = 0; k < 3; ++k) rt[3 * i + k] = R[3 * k + i];
+            for (int i = 0; i < 3; ++i) { o[i] = rt[3 * i] * e[0] + rt[3 * i + 1] * e[1] + rt[3 * i + 2] * e[2]; Q.h[i] = (float)S.size[i]; }
+            bound = std::sqrt(S.size[0] * S.size[0] + S.size[1] * S.size[1] + S.size[2] * S.size[2]);
+            Q.shape = kVisBox;
+        } else if (S.shape == PNR_SHAPE_SPHERE) {
+            for (int i = 0; i < 3; ++i) Q.h[i] = (float)S.size[0];
+            bound = S.size[0];
+            Q.shape = kVisSphere;
+        } else {                                     // unit world normal R n / |n| as the frame's z row
+            const double nl = std::sqrt(S.size[0] * S.size[0] + S.size[1] * S.size[1] + S.size[2] * S.size[2]);
+            for (int k = 0; k < 6; ++k) rt[k] = 0;
+            for (int k = 0; k < 3; ++k) rt[6 + k] = (R[3 * k] * S.size[0] + R[3 * k + 1] * S.size[1] + R[3 * k + 2] * S.size[2]) / nl;
+            o[0] = o[1] = 0;
+            o[2] = rt[6] * e[0] + rt[7] * e[1] + rt[8] * e[2];
+            Q.shape = kVisPlane;
+        }
+        for (int k = 0; k < 9; ++k) Q.rt[k] = (float)rt[k];
+        for (int k = 0; k < 3; ++k) { Q.o[k] = (float)o[k]; Q.rgb[k] = p->body_rgba[b][k]; }
+        Q.label = kSegBody0 + b;
+        if (S.shape == PNR_SHAPE_PLANE) { Q.x0 = 0; Q.x1 = P.W - 1; Q.y0 = 0; Q.y1 = P.H - 1; }
+        else {
+            const double d[3] = {-e[0], -e[1], -e[2]};
+            const float cx = (float)(V[0] * d[0] + V[1] * d[1] + V[2] * d[2]), cy = (float)(V[4] * d[0] + V[5] * d[1] + V[6] * d[2]);
+            const float dz = (float)-(V[8] * d[0] + V[9] * d[1] + V[10] * d[2]);
+            sphere_rect(cx, cy, dz, (float)bound, P, Q.x0, Q.x1, Q.y0, Q.y1);
+        }
+    }
+    return PNR_OK;
+}
+
+extern "C" {
+
+int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* p, uint8_t* rgb, float* depth, uint8_t* seg,
+               void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "pnr_render: null params");
+    if (!rgb && !depth && !seg) return fail(h, PNR_ERR_INVALID, "pnr_render: every output is NULL");
+    if ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(seg) |
+         reinterpret_cast<uintptr_t>(joint_state)) & 15u)
+        return fail(h, PNR_ERR_INVALID, "pnr_render: outputs and joint_state must be 16-byte aligned");
+    if (!h->ready && !h->kin_set)
+        return fail(h, PNR_ERR_INVALID, "pnr_render before the first pnr_reset (or pnr_set_state): the target comes from the state");
+    RenderParams P;
+    const int rc = render_setup(h, p, P);
+    if (rc) return rc;
+    DeviceGuard g(h->device);
+    const dim3 grid((unsigned)(h->n * P.tiles)), block(kRenderThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (joint_state) hipLaunchKernelGGL(render_kernel<kLinkSrcBuffer>, grid, block, 0, st, joint_state, h->state, (long long)h->n, P, rgb, depth, seg);
+    else if (h->dyn) hipLaunchKernelGGL(render_kernel<kLinkSrcDyn>, grid, block, 0, st, h->dyn, h->state, (long long)h->n, P, rgb, depth, seg);
+    else hipLaunchKernelGGL(render_kernel<kLinkSrcKin>, grid, block, 0, st, nullptr, h->state, (long long)h->n, P, rgb, depth, seg);
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }

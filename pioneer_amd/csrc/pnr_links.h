@@ -110,6 +110,29 @@ __device__ __forceinline__ void flush_link_tile(const float* __restrict__ lds, f
     for (int j = (nvec << 2) + lane; j < total; j += kWave) stream_store(dst + j, lds[j]);
 }
 
+// env e's joints from the source SRC (also pnr_render.h's)
+template <int SRC>
+__device__ __forceinline__ void load_link_joints(const float* __restrict__ src, const float4* __restrict__ state, const long long n,
+                                                 const long long e, float (&q)[kDof], float (&qd)[kDof])
+{
+    if (SRC == kLinkSrcBuffer) {
+        const float4* js = reinterpret_cast<const float4*>(src) + 3 * e;
+        const float4 a = js[0], b = js[1], c = js[2];
+        q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = b.x; q[5] = b.y;
+        qd[0] = b.z; qd[1] = b.w; qd[2] = c.x; qd[3] = c.y; qd[4] = c.z; qd[5] = c.w;
+    } else if (SRC == kLinkSrcDyn) {
+#pragma unroll
+        for (int i = 0; i < kDof; ++i) { q[i] = src[(long long)i * n + e]; qd[i] = src[(long long)(kDof + i) * n + e]; }
+    } else {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const RawState raw = load_state_raw(state, n, 2 * e + p);
+            qd[3 * p] = raw.p0.w; qd[3 * p + 1] = raw.p1.x; qd[3 * p + 2] = raw.p1.y;
+            q[3 * p] = raw.p1.z; q[3 * p + 1] = raw.p1.w; q[3 * p + 2] = raw.p2.x;
+        }
+    }
+}
+
 template <int SRC>
 __global__ __launch_bounds__(kWave) void link_state_kernel(const float* __restrict__ src, const float4* __restrict__ state,
                                                            float* __restrict__ out, const long long n)
@@ -122,24 +145,7 @@ __global__ __launch_bounds__(kWave) void link_state_kernel(const float* __restri
     float q[kDof], qd[kDof];
 #pragma unroll
     for (int i = 0; i < kDof; ++i) { q[i] = 0.f; qd[i] = 0.f; }
-    if (e < n) {
-        if (SRC == kLinkSrcBuffer) {
-            const float4* js = reinterpret_cast<const float4*>(src) + 3 * e;
-            const float4 a = js[0], b = js[1], c = js[2];
-            q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = b.x; q[5] = b.y;
-            qd[0] = b.z; qd[1] = b.w; qd[2] = c.x; qd[3] = c.y; qd[4] = c.z; qd[5] = c.w;
-        } else if (SRC == kLinkSrcDyn) {
-#pragma unroll
-            for (int i = 0; i < kDof; ++i) { q[i] = src[(long long)i * n + e]; qd[i] = src[(long long)(kDof + i) * n + e]; }
-        } else {
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const RawState raw = load_state_raw(state, n, 2 * e + p);
-                qd[3 * p] = raw.p0.w; qd[3 * p + 1] = raw.p1.x; qd[3 * p + 2] = raw.p1.y;
-                q[3 * p] = raw.p1.z; q[3 * p + 1] = raw.p1.w; q[3 * p + 2] = raw.p2.x;
-            }
-        }
-    }
+    if (e < n) load_link_joints<SRC>(src, state, n, e, q, qd);
     link_states_env(q, qd, tile + lane * kLinkRowFloats);
     wave_lds_sync();
     flush_link_tile(tile, out + tile0 * kLinkRowFloats, nvalid, lane);

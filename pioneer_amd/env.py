@@ -198,6 +198,13 @@ class PioneerKinematicEnv(compat.GymEnv):
         if mode == "human":
             return None
         elif mode == "rgb_array":
+            if self._vec.engine_config.renderer == "engine":               # the URDF's shapes, one pnr_render launch
+                from . import _lib
+                bodies = self.scene.render_bodies()
+                if len(bodies) > _lib.MAX_SCENE:
+                    raise AssertionError(f"the engine renderer draws at most {_lib.MAX_SCENE} created bodies, the scene has {len(bodies)}")
+                js = None if self._vec.engine_config.mode == "dynamic" else self.scene._bullet
+                return self._vec.render_frames(self.render_config, joint_state=js, bodies=bodies)["rgb"][0].cpu().numpy()
             from .render import render_rgb                                 # host-side stick-figure rasteriser
             st = self._state()
             q = st["r"][0]

@@ -1,7 +1,8 @@
 """Roll a trained policy out in the single-env façade and record it — the role of the reference's
 `agent.restore(...)` + `VideoRecorder` evaluation script (temp/pioneer_eval.py:53-78; the only artefact
 the reference ships is such a recording, demo.gif).  Frames come from env.render("rgb_array")
-(bullet_env.py:156-185; here the host-side stick-figure rasteriser of render.py)."""
+(bullet_env.py:156-185; here the host-side stick-figure rasteriser of render.py, or with
+engine_config=EngineConfig(renderer="engine") the engine's pnr_render of the URDF's visual shapes)."""
 from typing import Dict, List, Optional
 
 import numpy as np

@@ -5,11 +5,17 @@ here, so this draws a stick figure: the arm's link frames joined by line segment
 and the target sphere, seen by the camera of ``RenderConfig`` (yaw/pitch/roll about
 ``camera_target`` at ``camera_distance``, z up; vertical FOV projection with near/far clipping).
 Pure NumPy on the host — rendering is not on the step path and touches no env state.
+The engine's own renderer of the URDF's visual shapes (``pnr_render``, ``PioneerVectorEnv.render_frames``,
+``EngineConfig.renderer = "engine"``) takes its camera from ``view_matrix`` below.
 """
 import numpy as np
 
 from . import model
 from .config import RenderConfig
+
+# the URDF's materials for bodies created through env.scene (pioneer_knm_6dof.urdf:3-25): planes, everything else
+GROUND_RGBA = (0.4, 0.4, 0.4, 1.0)      # ground_mat
+OBSTACLE_RGBA = (0.3, 0.3, 0.3, 1.0)    # obstacle_mat
 
 
 def _rot(axis, q):

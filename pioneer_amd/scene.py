@@ -33,6 +33,8 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   links downstream of that joint the velocity v moves them with, as in Bullet).  ``reset_pose`` on a link asserts, as the
   reference's does.  Deviation: link items are NOT in ``scene.items_by_name`` (which holds the created bodies and the target
   only); the reference's ``items_by_name['robot:pointer']`` is ``links_by_name['robot:pointer']`` here.
+* ``render("rgb_array")`` with ``EngineConfig.renderer == "engine"`` draws every created body in ``scene.items`` (the target aside) in
+  its ``Item.rgba_color``: the ``rgba_color`` it was created with, else the URDF's obstacle_mat; planes in ground_mat.
 * ``Item.pose()`` is a ``Pose`` (``.xyz``, ``.rpy``), still a 2-tuple (position, orientation); ``Item.velocity()`` a ``Velocity``
   (linear, angular), zero for created bodies and the target (they are static).
 Build-defined behaviour where the reference delegates to Bullet: parity unpinned, like the rest of the Bullet boundary.
@@ -45,7 +47,8 @@ import numpy as np
 import torch
 
 from . import _lib, model
-from .config import scene_box, scene_plane, scene_sphere
+from .config import SceneBody, scene_box, scene_plane, scene_sphere
+from .render import GROUND_RGBA, OBSTACLE_RGBA
 
 
 class Pose(NamedTuple):
@@ -74,9 +77,11 @@ _ZERO3 = (0.0, 0.0, 0.0)
 class Item:
     """bullet_scene.py:40-67's Item, for the bodies created through Scene (and the target marker)."""
 
-    def __init__(self, name: Optional[str], shape: str, position, orientation, collision: bool, size):
+    def __init__(self, name: Optional[str], shape: str, position, orientation, collision: bool, size, rgba_color=None):
         self.name, self.shape, self.collision, self.size = name, shape, bool(collision), tuple(size)
         self._position, self._orientation = tuple(map(float, position)), tuple(map(float, orientation))
+        # the colour render("rgb_array") draws it in with EngineConfig.renderer == "engine"
+        self.rgba_color = None if rgba_color is None else tuple(map(float, rgba_color))
 
     def pose(self) -> Pose:
         return Pose(self._position, self._orientation)
@@ -216,13 +221,20 @@ class Scene:
             self._env._rebuild_engine(dataclasses.replace(vec.engine_config, scene=tuple(vec.engine_config.scene) + (body,)))
 
     def create_body_sphere(self, name, collision, mass, radius, position, orientation, rgba_color=None):   # bullet_scene.py:193-204
-        self._create(Item(name, "sphere", position, orientation, collision, (radius, 0.0, 0.0)), mass, scene_sphere(radius, position, orientation))
+        self._create(Item(name, "sphere", position, orientation, collision, (radius, 0.0, 0.0), rgba_color or OBSTACLE_RGBA), mass,
+                     scene_sphere(radius, position, orientation))
 
     def create_body_box(self, name, collision, mass, half_extents, position, orientation, rgba_color=None):  # :206-217
-        self._create(Item(name, "box", position, orientation, collision, half_extents), mass, scene_box(half_extents, position, orientation))
+        self._create(Item(name, "box", position, orientation, collision, half_extents, rgba_color or OBSTACLE_RGBA), mass,
+                     scene_box(half_extents, position, orientation))
 
     def create_body_plane(self, name, mass, normal, position, orientation):                                   # :219-227
-        self._create(Item(name, "plane", position, orientation, True, normal), mass, scene_plane(normal, position, orientation))
+        self._create(Item(name, "plane", position, orientation, True, normal, GROUND_RGBA), mass, scene_plane(normal, position, orientation))
+
+    def render_bodies(self):
+        """The created bodies as render_frames draws them: (SceneBody, rgba) of every item but the target."""
+        return [(SceneBody(i.shape, i._position, i._orientation, tuple(map(float, i.size))), i.rgba_color or OBSTACLE_RGBA)
+                for i in self.items if i.name != "target"]
 
     # -- rotations (pybullet.getQuaternionFromEuler / getEulerFromQuaternion: x, y, z, w; roll about x, pitch about y, yaw about z) --
     @staticmethod

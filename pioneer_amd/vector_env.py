@@ -225,6 +225,72 @@ class PioneerVectorEnv:
         self._chk(self.lib.pnr_get_link_states(self._h, _ptr(js), _ptr(res), self._stream()))
         return res
 
+    def render_frames(self, render_config=None, joint_state=None, bodies=None, rgb=True, depth=False, segmentation=False, out=None,
+                      light_direction=(0.4, 0.2, 1.0), ambient=0.45, diffuse=0.55, background=(1.0, 1.0, 1.0), target_rgba=None):
+        """render('rgb_array') of every env in one launch (bullet_env.py:156-185 -> getCameraImage; pnr_render): the URDF's 14
+        visual shapes in their materials' colours, posed by each env's joints, the translucent target sphere and static bodies,
+        seen by the camera of ``render_config`` (a RenderConfig, default RenderConfig(); render.view_matrix, its fov, near, far).
+
+        Returns a dict of device tensors, those asked for: ``rgb`` uint8 [N, H, W, 3], ``depth`` float32 [N, H, W] (eye depth
+        along the view axis, +inf where nothing is hit), ``seg`` uint8 [N, H, W] (``_lib.SEG_*``: 0 background, 1 + link index,
+        12 the target, 13 + body index).  ``joint_state``: as ``link_states`` (None = the handle's own joints).  ``bodies``: None
+        draws ``engine_config.scene`` in the URDF's obstacle_mat colour; else a sequence of (SceneBody, rgba) pairs.
+        Shading: c = clamp(rgb (ambient + diffuse max(0, n . l)), 0, 1) with the defaults light_direction (0.4, 0.2, 1.0) (towards
+        the light, world frame: from above, on the default camera's side), ambient 0.45, diffuse 0.55, a white background;
+        ``target_rgba`` defaults to the env's PioneerKinematicConfig.target_rgba.  ``out`` may carry preallocated ``rgb`` /
+        ``depth`` / ``seg`` tensors, written in place.  Never synchronises."""
+        from . import render as _render
+        from .config import RenderConfig
+        self._check_handle()
+        cfg = render_config or RenderConfig()
+        n, H, W = self.num_envs, int(cfg.render_height), int(cfg.render_width)
+        if bodies is None:
+            bodies = [(b, _render.OBSTACLE_RGBA) for b in self.engine_config.scene]
+        bodies = list(bodies)
+        if len(bodies) > _lib.MAX_SCENE:
+            raise AssertionError(f"at most {_lib.MAX_SCENE} bodies can be drawn, got {len(bodies)}")
+        p = _lib.PnrRenderParams()
+        p.struct_size = C.sizeof(_lib.PnrRenderParams)
+        p.width, p.height, p.n_bodies = W, H, len(bodies)
+        V = _render.view_matrix(cfg)
+        for k, v in enumerate(np.asarray(V, dtype=np.float64).reshape(-1)):
+            p.view[k] = float(v)
+        p.fov_y, p.near_clip, p.far_clip = float(cfg.projection_fov), float(cfg.projection_near), float(cfg.projection_far)
+        for k in range(3):
+            p.light_direction[k] = float(light_direction[k])
+            p.background[k] = float(background[k])
+        p.ambient, p.diffuse = float(ambient), float(diffuse)
+        trgba = self.config.target_rgba if target_rgba is None else target_rgba
+        for k in range(4):
+            p.target_rgba[k] = float(trgba[k])
+        shapes = {"plane": _lib.SHAPE_PLANE, "box": _lib.SHAPE_BOX, "sphere": _lib.SHAPE_SPHERE}
+        for i, (b, rgba) in enumerate(bodies):
+            if b.shape not in shapes:
+                raise AssertionError(f"body {i}: shape must be one of {sorted(shapes)}")
+            p.bodies[i].shape = shapes[b.shape]
+            for k in range(3):
+                p.bodies[i].position[k] = float(b.position[k]); p.bodies[i].size[k] = float(b.size[k])
+            for k in range(4):
+                p.bodies[i].orientation[k] = float(b.orientation[k]); p.body_rgba[i][k] = float(rgba[k])
+        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        out = out or {}
+        res = {}
+        for key, want, shape, dtype in (("rgb", rgb, (n, H, W, 3), torch.uint8), ("depth", depth, (n, H, W), torch.float32),
+                                        ("seg", segmentation, (n, H, W), torch.uint8)):
+            if not want:
+                continue
+            t = out.get(key)
+            if t is None:
+                res[key] = self._new(shape, dtype)
+            else:
+                res[key] = self._in(t, shape, dtype, key)
+                assert res[key].data_ptr() == t.data_ptr(), f"out[{key!r}] is written in place: it must already be a contiguous {dtype} device tensor"
+        if not res:
+            raise AssertionError("render_frames: ask for at least one of rgb, depth, segmentation")
+        self._chk(self.lib.pnr_render(self._h, _ptr(js), p, _ptr(res.get("rgb")), _ptr(res.get("depth")), _ptr(res.get("seg")),
+                                      self._stream()))
+        return res
+
     def observe(self, out=None):
         """observe() without stepping (pioneer_knm_env.py:184-211)."""
         self._check_handle()

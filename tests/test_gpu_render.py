@@ -1,0 +1,322 @@
+"""GPU tests of pnr_render (PioneerVectorEnv.render_frames, render("rgb_array") with EngineConfig.renderer = "engine"): pixels
+against the independent float64 reference of tests/render_ref.py outside its ambiguity band, every joint source, batch
+independence and determinism, output bounds (a > 2^31-byte rgb batch included), validation and the façade."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import link_kinematics_ref  # noqa: F401  (render_ref's chain)
+import render_ref as rr
+
+pytestmark = pytest.mark.gpu
+
+LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416], dtype=np.float32)
+CAMS = {"default": dict(), "close": dict(camera_distance=25.0), "axis": dict(camera_yaw=0.0, camera_pitch=0.0, camera_roll=0.0)}
+GREY = (0.3, 0.3, 0.3, 1.0)
+
+
+def scene_bodies():
+    from pioneer_amd.config import scene_box, scene_plane, scene_sphere
+    return [(scene_box((1.0, 1.5, 3.0), (10.0, 5.0, 0.0), (0.0, 0.0, 0.38268343, 0.92387953)), (0.8, 0.2, 0.6, 1.0)),
+            (scene_sphere(2.0, (-8.0, -6.0, 4.0)), (0.2, 0.7, 0.9, 1.0)),
+            (scene_plane((0.0, 0.0, 1.0), (0.0, 0.0, -0.5)), (0.4, 0.4, 0.4, 1.0))]
+
+
+def ref_bodies(bodies):
+    return [(b.shape, b.position, b.orientation, b.size, rgba) for b, rgba in bodies]
+
+
+def random_state(n, seed):
+    rng = np.random.default_rng(seed)
+    q = (rng.uniform(-1.0, 1.0, size=(n, 6)) * LIMITS).astype(np.float32)
+    tgt = rng.uniform((15, -10, 2), (25, 10, 6), size=(n, 3)).astype(np.float32)
+    return q, tgt
+
+
+def check_env(frames, k, q, tgt, cfg, bodies, min_checked=0.9):
+    """Env k of the engine's frames against the reference at every pixel."""
+    from pioneer_amd import render
+    W, H = cfg.render_width, cfg.render_height
+    yy, xx = np.mgrid[0:H, 0:W]
+    want = rr.render_pixels(q.astype(np.float64), tgt.astype(np.float64), xx.ravel(), yy.ravel(), render.view_matrix(cfg),
+                            cfg.projection_fov, cfg.projection_near, cfg.projection_far, W, H, bodies=ref_bodies(bodies))
+    seg = frames["seg"][k].reshape(-1)
+    rgb = frames["rgb"][k].reshape(-1, 3).astype(np.int32)
+    dep = frames["depth"][k].reshape(-1).astype(np.float64)
+    ok = ~want["band"]
+    assert ok.mean() >= min_checked, ok.mean()
+    bad = ok & (seg != want["seg"])
+    assert not bad.any(), f"env {k}: {bad.sum()} labels differ outside the band, e.g. {np.argwhere(bad)[:5].ravel()}"
+    same = ok & (seg == want["seg"])
+    assert np.abs(rgb[same] - want["rgb"][same].astype(np.int32)).max(initial=0) <= 1
+    fin = same & np.isfinite(want["depth"])
+    assert np.array_equal(np.isinf(dep[same]), np.isinf(want["depth"][same]))
+    assert (np.abs(dep[fin] - want["depth"][fin]) <= 1e-4 * want["depth"][fin]).all()
+    return want
+
+
+def all_outputs(env, cfg, bodies, joint_state=None):
+    fr = env.render_frames(cfg, joint_state=joint_state, bodies=bodies, rgb=True, depth=True, segmentation=True)
+    return {k: v.cpu().numpy() for k, v in fr.items()}
+
+
+@pytest.mark.parametrize("cam", sorted(CAMS))
+@pytest.mark.parametrize("size", [(96, 64), (83, 61)])
+@pytest.mark.parametrize("n", [1, 37, 1000])
+def test_parity_with_the_reference(n, size, cam):
+    from pioneer_amd import PioneerVectorEnv, RenderConfig
+    env = PioneerVectorEnv(n, device="cuda:0", seed=1)
+    q, tgt = random_state(n, 100 * n + size[0] + len(cam))
+    env.reset(joint_positions=q, target_positions=tgt)
+    cfg = RenderConfig(render_width=size[0], render_height=size[1], **CAMS[cam])
+    bodies = scene_bodies()
+    fr = all_outputs(env, cfg, bodies)
+    assert fr["rgb"].shape == (n, size[1], size[0], 3) and fr["depth"].shape == fr["seg"].shape == (n, size[1], size[0])
+    ks = range(n) if n <= 37 else sorted({0, n - 1, *np.random.default_rng(n).choice(n, 10, replace=False).tolist()})
+    labels = set()
+    for k in ks:
+        want = check_env(fr, k, q[k], tgt[k], cfg, bodies)
+        labels |= set(np.unique(want["seg"]).tolist())
+    assert {rr.SEG_BODY0 + 2} <= labels and any(1 < s < rr.SEG_TARGET for s in labels)    # the plane and the arm are in view
+    env.close()
+
+
+def test_joint_sources():
+    from pioneer_amd import EngineConfig, PioneerVectorEnv, RenderConfig
+    n = 37
+    cfg = RenderConfig(render_width=96, render_height=64, camera_distance=60.0)
+    bodies = scene_bodies()
+    q, tgt = random_state(n, 5)
+    rng = np.random.default_rng(6)
+    for mode in ("kinematic", "dynamic"):
+        env = PioneerVectorEnv(n, device="cuda:0", seed=2, engine_config=EngineConfig(mode=mode))
+        env.reset(joint_positions=q, target_positions=tgt)
+        # a caller's buffer (q | qd), only read
+        qb = (rng.uniform(-1.2, 1.2, size=(n, 6)) * LIMITS).astype(np.float32)
+        js = torch.from_numpy(np.concatenate([qb, rng.uniform(-3, 3, size=(n, 6)).astype(np.float32)], axis=1)).cuda()
+        keep = js.clone()
+        fr = all_outputs(env, cfg, bodies, js)
+        assert torch.equal(js, keep)
+        for k in (0, 17, n - 1):
+            check_env(fr, k, qb[k], tgt[k], cfg, bodies)
+        # the handle's own joints
+        if mode == "dynamic":
+            d = env.get_dyn_state()
+            d[6:12] = torch.from_numpy(rng.uniform(-2, 2, size=(6, n)).astype(np.float32)).cuda()
+            env.set_dyn_state(d)
+            for _ in range(3):
+                env.world_step()
+            qs = env.get_dyn_state()[0:6].T.cpu().numpy()
+            assert np.abs(qs - q).max() > 1e-3                                          # the simulated joints moved
+        else:
+            qs = env.get_state().view(torch.float32)[12:18].T.cpu().numpy()
+        fr = all_outputs(env, cfg, bodies)
+        for k in (0, 17, n - 1):
+            check_env(fr, k, qs[k], tgt[k], cfg, bodies)
+        env.close()
+
+
+def test_batch_independence_and_determinism():
+    from pioneer_amd import PioneerVectorEnv, RenderConfig
+    n = 1000
+    cfg = RenderConfig(render_width=83, render_height=61, camera_distance=40.0)
+    bodies = scene_bodies()
+    q, tgt = random_state(n, 9)
+    env = PioneerVectorEnv(n, device="cuda:0", seed=3)
+    env.reset(joint_positions=q, target_positions=tgt)
+    a, b = all_outputs(env, cfg, bodies), all_outputs(env, cfg, bodies)
+    for key in a:
+        assert a[key].tobytes() == b[key].tobytes(), key
+    one = PioneerVectorEnv(1, device="cuda:0", seed=4)
+    for k in (0, 1, 511, n - 1):
+        one.reset(joint_positions=q[k:k + 1], target_positions=tgt[k:k + 1])
+        js = torch.from_numpy(np.concatenate([q[k:k + 1], np.zeros((1, 6), np.float32)], axis=1)).cuda()
+        alone = all_outputs(one, cfg, bodies, js)
+        for key in a:
+            assert alone[key][0].tobytes() == a[key][k].tobytes(), (k, key)
+    env.close(); one.close()
+
+
+def _raw_render(env, p, rgb, depth, seg, js=None):
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    return env.lib.pnr_render(env._h, ptr(js), p, ptr(rgb), ptr(depth), ptr(seg), env._stream())
+
+
+def _params(env, cfg, bodies=()):
+    """A filled pnr_render_params, as render_frames builds it."""
+    from pioneer_amd import _lib, render
+    p = _lib.PnrRenderParams()
+    p.struct_size = C.sizeof(_lib.PnrRenderParams)
+    p.width, p.height, p.n_bodies = cfg.render_width, cfg.render_height, len(bodies)
+    for k, v in enumerate(render.view_matrix(cfg).reshape(-1)):
+        p.view[k] = float(v)
+    p.fov_y, p.near_clip, p.far_clip = cfg.projection_fov, cfg.projection_near, cfg.projection_far
+    p.light_direction[:] = (0.4, 0.2, 1.0)
+    p.ambient, p.diffuse = 0.45, 0.55
+    p.background[:] = (1.0, 1.0, 1.0)
+    p.target_rgba[:] = (1.0, 0.0, 0.0, 0.5)
+    shapes = {"plane": _lib.SHAPE_PLANE, "box": _lib.SHAPE_BOX, "sphere": _lib.SHAPE_SPHERE}
+    for i, (b, rgba) in enumerate(bodies):
+        p.bodies[i].shape = shapes[b.shape]
+        p.bodies[i].position[:] = b.position
+        p.bodies[i].orientation[:] = b.orientation
+        p.bodies[i].size[:] = b.size
+        p.body_rgba[i][:] = rgba
+    return p
+
+
+@pytest.mark.parametrize("n,size", [(1, (17, 5)), (37, (83, 61)), (333, (9, 7))])
+def test_outputs_stop_at_their_last_byte(n, size):
+    from pioneer_amd import PioneerVectorEnv, RenderConfig
+    env = PioneerVectorEnv(n, device="cuda:0", seed=6)
+    q, tgt = random_state(n, 12)
+    env.reset(joint_positions=q, target_positions=tgt)
+    cfg = RenderConfig(render_width=size[0], render_height=size[1], camera_distance=30.0)
+    m = n * size[0] * size[1]
+    guard = 4096
+    rgb = torch.full((3 * m + guard,), 0xA5, dtype=torch.uint8, device="cuda:0")
+    dep = torch.full((m + guard,), -7.25, dtype=torch.float32, device="cuda:0")
+    seg = torch.full((m + guard,), 0x5A, dtype=torch.uint8, device="cuda:0")
+    assert _raw_render(env, _params(env, cfg, scene_bodies()), rgb, dep, seg) == 0
+    fr = all_outputs(env, cfg, scene_bodies())
+    torch.cuda.synchronize()
+    assert (rgb[3 * m:] == 0xA5).all() and (dep[m:] == -7.25).all() and (seg[m:] == 0x5A).all()
+    assert np.array_equal(rgb[:3 * m].cpu().numpy(), fr["rgb"].reshape(-1))
+    assert np.array_equal(dep[:m].cpu().numpy(), fr["depth"].reshape(-1))
+    assert np.array_equal(seg[:m].cpu().numpy(), fr["seg"].reshape(-1))
+    # one output alone writes the same bytes
+    only = torch.full((m + guard,), 0x5A, dtype=torch.uint8, device="cuda:0")
+    assert _raw_render(env, _params(env, cfg, scene_bodies()), None, None, only) == 0
+    assert torch.equal(only, seg)
+    env.close()
+
+
+def test_rgb_batch_beyond_two_gigabytes():
+    from pioneer_amd import PioneerVectorEnv, RenderConfig
+    n = 65536
+    cfg = RenderConfig(render_width=128, render_height=96)
+    assert n * 128 * 96 * 3 > 2 ** 31
+    q, tgt = random_state(n, 13)
+    env = PioneerVectorEnv(n, device="cuda:0", seed=7)
+    env.reset(joint_positions=q, target_positions=tgt)
+    rgb = env.render_frames(cfg, bodies=scene_bodies())["rgb"]
+    last = rgb[n - 1].cpu().numpy()
+    del rgb
+    one = PioneerVectorEnv(1, device="cuda:0", seed=8)
+    one.reset(joint_positions=q[-1:], target_positions=tgt[-1:])
+    alone = one.render_frames(cfg, bodies=scene_bodies())["rgb"][0].cpu().numpy()
+    assert np.array_equal(last, alone) and (last != 255).any()
+    env.close(); one.close()
+
+
+def test_invalid_calls_touch_nothing():
+    from pioneer_amd import PioneerVectorEnv, RenderConfig
+    from pioneer_amd.config import scene_box
+    n = 5
+    cfg = RenderConfig(render_width=16, render_height=8)
+    fresh = PioneerVectorEnv(n, device="cuda:0", seed=9)
+    rgb = torch.full((n * 16 * 8 * 3 + 64,), 7, dtype=torch.uint8, device="cuda:0")
+    dep = torch.full((n * 16 * 8 + 16,), 3.0, dtype=torch.float32, device="cuda:0")
+    seg = torch.full((n * 16 * 8 + 16,), 9, dtype=torch.uint8, device="cuda:0")
+    assert _raw_render(fresh, _params(fresh, cfg), rgb, dep, seg) == -1                        # before the first reset
+    assert b"before the first pnr_reset" in fresh.lib.pnr_last_error(fresh._h)
+    env = fresh
+    env.reset()
+
+    def bad(mutate, outs=(rgb, dep, seg), js=None):
+        p = _params(env, cfg, [(scene_box((1, 1, 1), (5, 0, 0)), (0, 0, 0, 1))])
+        mutate(p)
+        return _raw_render(env, p, *outs, js=js)
+
+    nan = float("nan")
+    cases = [lambda p: setattr(p, "struct_size", 12), lambda p: setattr(p, "width", 0), lambda p: setattr(p, "height", 4097),
+             lambda p: setattr(p, "fov_y", 0.0), lambda p: setattr(p, "fov_y", 180.0), lambda p: setattr(p, "near_clip", 0.0),
+             lambda p: setattr(p, "far_clip", float("inf")), lambda p: setattr(p, "near_clip", nan),
+             lambda p: setattr(p, "far_clip", p.near_clip), lambda p: p.view.__setitem__(3, nan),
+             lambda p: p.view.__setitem__(0, 2.0), lambda p: p.light_direction.__setitem__(1, float("inf")),
+             lambda p: [p.light_direction.__setitem__(k, 0.0) for k in range(3)], lambda p: setattr(p, "n_bodies", 9),
+             lambda p: setattr(p, "n_bodies", -1), lambda p: setattr(p.bodies[0], "shape", 7),
+             lambda p: p.bodies[0].position.__setitem__(0, nan), lambda p: p.bodies[0].size.__setitem__(1, 0.0),
+             lambda p: [p.bodies[0].orientation.__setitem__(k, 0.0) for k in range(4)], lambda p: p.body_rgba[0].__setitem__(2, nan)]
+    for i, mutate in enumerate(cases):
+        assert bad(mutate) == -1, i
+        assert b"PNR_" not in env.lib.pnr_last_error(env._h)
+    assert _raw_render(env, None, rgb, dep, seg) == -1
+    assert bad(lambda p: None, outs=(None, None, None)) == -1
+    off = torch.empty(64, dtype=torch.uint8, device="cuda:0")
+    assert bad(lambda p: None, outs=(rgb[1:], dep, seg)) == -1
+    assert bad(lambda p: None, outs=(rgb, dep[1:], seg)) == -1
+    assert bad(lambda p: None, outs=(rgb, dep, seg[4:])) == -1
+    js = torch.zeros((n * 12 + 4,), dtype=torch.float32, device="cuda:0")
+    assert bad(lambda p: None, js=js[1:]) == -1
+    assert env.lib.pnr_render(None, None, _params(env, cfg), C.c_void_p(off.data_ptr()), None, None, None) == -1
+    torch.cuda.synchronize()
+    assert (rgb == 7).all() and (dep == 3.0).all() and (seg == 9).all()
+    assert bad(lambda p: None) == 0                                             # the unmutated call runs
+    torch.cuda.synchronize()
+    assert not (rgb[:n * 16 * 8 * 3] == 7).all()
+    env.close()
+
+
+def test_facade_engine_renderer():
+    from pioneer_amd import EngineConfig, PioneerKinematicEnv, RenderConfig
+    from pioneer_amd.render import render_rgb
+    cfg = RenderConfig(render_width=96, render_height=64, camera_distance=45.0)
+    env = PioneerKinematicEnv(render_config=cfg, engine_config=EngineConfig(renderer="engine"))
+    env.reset_world(np.array([0.3, 0.4, -0.2, 0.1, 0.5, 0.0]), (18.0, 2.0, 4.0))
+    frame = env.render("rgb_array")
+    assert frame.shape == (64, 96, 3) and frame.dtype == np.uint8
+    same = env._vec.render_frames(cfg, joint_state=env.scene._bullet, bodies=[])["rgb"][0].cpu().numpy()
+    assert np.array_equal(frame, same)
+    # a black box created through the scene is drawn black where the reference labels it
+    env.scene.create_body_box("blackbox", True, 0, (2.0, 2.0, 2.0), (5.0, -12.0, 2.0), (0, 0, 0, 1), rgba_color=(0, 0, 0, 1))
+    env.scene.create_body_plane("ground", 0, (0, 0, 1), (0, 0, -1.0), (0, 0, 0, 1))
+    frame = env.render("rgb_array")
+    from pioneer_amd import render
+    yy, xx = np.mgrid[0:64, 0:96]
+    q = env.scene._bullet[0, :6].cpu().numpy().astype(np.float64)
+    want = rr.render_pixels(q, np.array([18.0, 2.0, 4.0], np.float32).astype(np.float64), xx.ravel(), yy.ravel(),
+                            render.view_matrix(cfg), cfg.projection_fov, cfg.projection_near, cfg.projection_far, 96, 64,
+                            bodies=[("box", (5.0, -12.0, 2.0), (0, 0, 0, 1), (2.0, 2.0, 2.0), (0, 0, 0, 1)),
+                                    ("plane", (0, 0, -1.0), (0, 0, 0, 1), (0, 0, 1), (0.4, 0.4, 0.4, 1))])
+    box = (want["seg"] == rr.SEG_BODY0) & ~want["band"]
+    assert box.sum() > 20
+    assert (frame.reshape(-1, 3)[box] == 0).all()
+    plane = (want["seg"] == rr.SEG_BODY0 + 1) & ~want["band"]
+    assert plane.sum() > 20 and np.abs(frame.reshape(-1, 3)[plane].astype(int) - want["rgb"][plane].astype(int)).max() <= 1
+    # resetJointState moves the drawn arm in kinematic mode
+    before = env.render("rgb_array")
+    env.scene.joints_by_name["robot:hinge1_to_arm1"].reset_state(-0.9)
+    after = env.render("rgb_array")
+    assert (np.abs(before.astype(int) - after.astype(int)).sum(axis=2) > 0).sum() > 30
+    for k in range(7):
+        env.scene.create_body_sphere(f"s{k}", False, 0, 0.5, (0, 0, 30 + k), (0, 0, 0, 1))
+    with pytest.raises(AssertionError):
+        env.render("rgb_array")                                                    # 9 bodies: more than PNR_MAX_SCENE
+    env.close()
+    # the default façade still draws the stick figure
+    host = PioneerKinematicEnv(render_config=cfg)
+    st = host._state()
+    assert np.array_equal(host.render("rgb_array"), render_rgb(st["r"][0], st["target"][0], cfg, host.config.target_radius))
+    host.close()
+
+
+def test_evaluation_gif_with_the_engine_renderer(tmp_path):
+    from PIL import Image
+    from pioneer_amd import EngineConfig, PioneerVectorEnv
+    from pioneer_amd.evaluate import evaluate
+    from pioneer_amd.ppo import PPOConfig, PPOTrainer
+    env = PioneerVectorEnv(512, device="cuda:0", seed=1, engine_config=EngineConfig(max_episode_steps=20))
+    tr = PPOTrainer(env, PPOConfig(rollout_fragment_length=8, num_sgd_iter=1, sgd_minibatch_size=2048))
+    tr.train()
+    ck = tr.save(str(tmp_path / "ck.pt"))
+    env.close()
+    gif = tmp_path / "eval.gif"
+    res = evaluate(ck, episodes=1, max_episode_steps=6, gif_path=str(gif), frame_stride=2, engine_config=EngineConfig(renderer="engine"))
+    assert res["frames"] >= 3
+    im = Image.open(gif)
+    assert im.is_animated and im.n_frames == res["frames"] and im.size == (1280, 800)
+    px = np.asarray(im.convert("RGB"))
+    assert len(np.unique(px.reshape(-1, 3), axis=0)) > 4                          # shaded shapes, not a blank frame

@@ -1,0 +1,223 @@
+"""CPU tests of the engine renderer (pnr_render / PioneerVectorEnv.render_frames / EngineConfig.renderer): the visuals fixture
+and its extractor, pnr_render.h's visual table against the fixture, the float64 reference of tests/render_ref.py against
+render.project, the C ABI layout of pnr_render_params and the façade's configuration.  The GPU side is
+tests/test_gpu_render.py."""
+import ctypes as C
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+import xml.etree.ElementTree as ET
+
+import numpy as np
+import pytest
+
+import render_ref as rr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = rr.load_visuals()
+VISUALS_PER_LINK = {"robot:rotator1": 1, "robot:hinge1": 3, "robot:arm1": 1, "robot:arm2": 1, "robot:rotator2": 1,
+                    "robot:hinge2": 1, "robot:arm3": 2, "robot:rotator3": 1, "robot:effector": 2, "robot:pointer": 1}
+
+
+def _emit_urdf(data) -> str:
+    """A URDF holding exactly the fixture's materials and visuals (numbers written back as text)."""
+    robot = ET.Element("robot", name="pioneer")
+    for name, rgba in data["materials"].items():
+        m = ET.SubElement(robot, "material", name=name)
+        ET.SubElement(m, "color", rgba=" ".join(repr(x) for x in rgba))
+    links = {}
+    for v in data["visuals"]:
+        link = links.get(v["link"])
+        if link is None:
+            link = links[v["link"]] = ET.SubElement(robot, "link", name=v["link"])
+        vis = ET.SubElement(link, "visual")
+        ET.SubElement(vis, "origin", rpy=" ".join(v["rpy"]), xyz=" ".join(repr(x) for x in v["xyz"]))
+        g = ET.SubElement(vis, "geometry")
+        geo = v["geometry"]
+        if geo["type"] == "box":
+            ET.SubElement(g, "box", size=" ".join(repr(x) for x in geo["size"]))
+        elif geo["type"] == "cylinder":
+            ET.SubElement(g, "cylinder", radius=repr(geo["radius"]), length=repr(geo["length"]))
+        else:
+            ET.SubElement(g, "sphere", radius=repr(geo["radius"]))
+        ET.SubElement(vis, "material", name=v["material"])
+    return ET.tostring(robot, encoding="unicode")
+
+
+def test_fixture_holds_the_urdf_visuals():
+    assert sorted(GOLD["materials"]) == ["arm_mat", "ground_mat", "hinge_mat", "obstacle_mat", "pointer_mat", "rotator_mat"]
+    assert len(GOLD["visuals"]) == 14
+    counts = {}
+    for v in GOLD["visuals"]:
+        counts[v["link"]] = counts.get(v["link"], 0) + 1
+    assert counts == VISUALS_PER_LINK
+    assert sorted({tuple(v["rpy"]) for v in GOLD["visuals"]}) == [("0", "-1.5708", "0"), ("0", "0", "0"), ("0", "1.5708", "0"),
+                                                                 ("0", "3.1416", "0")]
+
+
+def test_fixture_round_trips_through_the_extractor(tmp_path):
+    urdf = tmp_path / "visuals.urdf"
+    urdf.write_text(_emit_urdf(GOLD))
+    out = tmp_path / "out.json"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "make_urdf_visuals.py"), str(urdf), str(out)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert json.loads(out.read_text()) == GOLD
+
+
+def _model_constants():
+    src = open(os.path.join(ROOT, "pioneer_amd", "csrc", "pnr_model.h")).read()
+    consts = {m.group(1): float.fromhex(m.group(2)) for m in re.finditer(r"\b(k(?:Cos|Sin)\d_\d+) = (-?0x[0-9a-fp.+-]+)f", src)}
+    tip = re.search(r"kTipX = ([\d.]+), kTipY = ([\d.]+), kTipZ = ([\d.]+)", src)
+    return consts, tuple(float(x) for x in tip.groups())
+
+
+def _c_float(tok, consts):
+    tok = tok.strip()
+    sign = -1.0 if tok.startswith("-") else 1.0
+    tok = tok.lstrip("-")
+    if tok in consts:
+        return sign * consts[tok]
+    assert tok.endswith("f"), tok
+    return sign * float(tok[:-1])
+
+
+def test_render_table_matches_the_fixture():
+    src = open(os.path.join(ROOT, "pioneer_amd", "csrc", "pnr_render.h")).read()
+    rows = re.findall(r"\{(\d+), (\d), kVis(\w+), \{([^}]*)\}, \{([^}]*)\}, \{([^}]*)\}, \{([^}]*)\}\},", src)
+    assert len(rows) == 14
+    consts, tip = _model_constants()
+    chain = [j["child"] for j in json.load(open(os.path.join(ROOT, "tests", "golden", "urdf_chain.json")))["joints"]]
+    body_of_link = {}                                  # moving body = count of revolute joints up to the link, minus one
+    revolute = 0
+    for j in json.load(open(os.path.join(ROOT, "tests", "golden", "urdf_chain.json")))["joints"]:
+        revolute += j["type"] == "revolute"
+        body_of_link[j["child"]] = revolute - 1
+    for row, v in zip(rows, GOLD["visuals"]):
+        link, body, shape = int(row[0]), int(row[1]), row[2].lower()
+        rot = [_c_float(t, consts) for t in row[3].split(",")]
+        t, half, rgba = ([_c_float(x, consts) for x in r.split(",")] for r in row[4:7])
+        assert chain[link] == v["link"] and body == body_of_link[v["link"]]
+        g = v["geometry"]
+        assert shape == g["type"]
+        # rotation: the rpy text values' rotation (all about y here) to float32 rounding of a unit-scale matrix (the table uses
+        # pnr_model.h's float32 cos / sin constants of those values); exact zeros and ones where the rotation has them
+        r_, p_, y_ = (float(s) for s in v["rpy"])
+        assert r_ == 0 and y_ == 0
+        c, s = np.cos(p_), np.sin(p_)
+        want = np.array([c, 0.0, s, 0.0, 1.0, 0.0, -s, 0.0, c])
+        assert np.abs(np.array(rot) - want).max() <= 2.0 ** -23, v
+        assert [rot[k] for k in (1, 3, 4, 5, 7)] == [0.0, 0.0, 1.0, 0.0, 0.0] and rot[2] == -rot[6] and rot[0] == rot[8]
+        # translation, half sizes and colour exactly (the pointer's sphere sits at kTip: the effector_to_pointer origin)
+        xyz = list(v["xyz"])
+        if v["link"] == "robot:pointer":
+            xyz = [a + b for a, b in zip(xyz, tip)]
+        assert t == xyz, v
+        if g["type"] == "box":
+            want = [0.5 * x for x in g["size"]]
+        elif g["type"] == "cylinder":
+            want = [g["radius"], g["radius"], 0.5 * g["length"]]
+        else:
+            want = [g["radius"]] * 3
+        assert half == want, v
+        assert rgba == GOLD["materials"][v["material"]], v
+
+
+def test_python_material_constants_are_the_urdfs():
+    from pioneer_amd import render
+    assert list(render.GROUND_RGBA) == GOLD["materials"]["ground_mat"]
+    assert list(render.OBSTACLE_RGBA) == GOLD["materials"]["obstacle_mat"]
+
+
+@pytest.mark.parametrize("cam", [dict(), dict(camera_distance=25.0, camera_yaw=40.0, camera_pitch=-20.0),
+                                 dict(camera_yaw=0.0, camera_pitch=0.0, camera_roll=0.0)])
+def test_reference_rays_go_through_the_projected_centres(cam):
+    from pioneer_amd import render
+    from pioneer_amd.config import RenderConfig
+    cfg = RenderConfig(render_width=96, render_height=64, **cam)
+    rng = np.random.default_rng(3)
+    lim = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416])
+    V = render.view_matrix(cfg)
+    for _ in range(8):
+        q = rng.uniform(-lim, lim)
+        target = rng.uniform((15, -10, 2), (25, 10, 6))
+        pointer = [P for P in rr.scene_prims(q, target) if P["label"] == rr.SEG_LINK0 + 10][0]["c"]
+        np.testing.assert_allclose(pointer, render.link_origins(q)[-1], atol=1e-12)
+        px, depth = render.project(np.stack([pointer, target]), cfg)
+        if np.isnan(px).any():
+            continue
+        eye, d = rr.rays(V, cfg.projection_fov, cfg.render_width, cfg.render_height, px[:, 0] - 0.5, px[:, 1] - 0.5)
+        for k, centre in enumerate((pointer, target)):
+            np.testing.assert_allclose(eye + depth[k] * d[k], centre, atol=1e-9)
+        out = rr.render_pixels(q, target, px[:, 0] - 0.5, px[:, 1] - 0.5, V, cfg.projection_fov, cfg.projection_near,
+                               cfg.projection_far, cfg.render_width, cfg.render_height)
+        # nothing at those rays lies further than the sphere's front surface (eye depth = ray parameter: centre depth less
+        # radius / |d|); the target is seen there unless something opaque is nearer
+        front = depth - 0.2 / np.linalg.norm(d, axis=1)
+        assert out["depth"][0] <= front[0] + 1e-9 and out["depth"][1] <= front[1] + 1e-9
+        if out["depth"][1] > front[1] - 1e-9:
+            assert out["seg"][1] == rr.SEG_TARGET
+
+
+def test_reference_hit_rules_on_a_plane():
+    """Straight down onto a plane at z = 0: depth, label and the shading rule; the far clip removes it."""
+    from pioneer_amd import render
+    from pioneer_amd.config import RenderConfig
+    cfg = RenderConfig(camera_distance=150.0, camera_pitch=-90.0, camera_yaw=0.0, render_width=8, render_height=8)
+    V = render.view_matrix(cfg)
+    q = np.zeros(6)
+    out = rr.render_pixels(q, (500.0, 500.0, 500.0), [0.0], [0.0], V, 30.0, 0.1, 200.0, 8, 8,
+                           bodies=[("plane", (0, 0, 0), (0, 0, 0, 1), (0, 0, 1), (0.4, 0.4, 0.4, 1))],
+                           light_direction=(0, 0, 1), ambient=0.5, diffuse=0.5)
+    assert out["seg"][0] == rr.SEG_BODY0
+    assert np.all(out["rgb"][0] == np.floor(255 * 0.4 + 0.5))
+    far = rr.render_pixels(q, (500.0, 500.0, 500.0), [0.0], [0.0], V, 30.0, 0.1, 120.0, 8, 8,
+                           bodies=[("plane", (0, 0, 0), (0, 0, 0, 1), (0, 0, 1), (0.4, 0.4, 0.4, 1))])
+    assert far["seg"][0] == rr.SEG_BACKGROUND and np.isinf(far["depth"][0]) and np.all(far["rgb"][0] == 255)
+
+
+def test_renderer_option_is_validated():
+    from pioneer_amd import EngineConfig
+    assert EngineConfig().renderer == "host"
+    assert EngineConfig(renderer="engine").renderer == "engine"
+    with pytest.raises(ValueError, match="renderer"):
+        EngineConfig(renderer="bogus")
+
+
+def test_render_params_layout_matches_the_header(tmp_path):
+    from pioneer_amd import _lib
+    P = _lib.PnrRenderParams
+    header = open(os.path.join(ROOT, "include", "pioneer_amd.h")).read()
+    assert re.search(r"int pnr_render\(pnr_handle h, const float\* joint_state, const pnr_render_params\* p, uint8_t\* rgb, "
+                     r"float\* depth, uint8_t\* seg,\s+void\* stream\);", header)
+    for name, value in (("PNR_SEG_BACKGROUND", _lib.SEG_BACKGROUND), ("PNR_SEG_LINK0", _lib.SEG_LINK0),
+                        ("PNR_SEG_TARGET", _lib.SEG_TARGET), ("PNR_SEG_BODY0", _lib.SEG_BODY0)):
+        assert re.search(rf"\b{name} = {value}\b", header), name
+    fields = [f[0] for f in P._fields_]
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    if cc is None:
+        pytest.skip("no host C compiler to lay the struct out")
+    probe = tmp_path / "probe.c"
+    probe.write_text("#include <stdio.h>\n#include <stddef.h>\n#include \"pioneer_amd.h\"\nint main(void) {\n"
+                     '  printf("size %zu\\n", sizeof(pnr_render_params));\n' +
+                     "".join(f'  printf("{f} %zu\\n", offsetof(pnr_render_params, {f}));\n' for f in fields) + "  return 0;\n}\n")
+    exe = tmp_path / "probe"
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(probe)], check=True, timeout=120)
+    got = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    assert int(got["size"]) == C.sizeof(P)
+    for f in fields:
+        assert int(got[f]) == getattr(P, f).offset, f
+
+
+def test_render_entry_point_rejects_a_null_handle_without_a_device(hip_lib):
+    from pioneer_amd import _lib
+    p = _lib.PnrRenderParams()
+    p.struct_size = C.sizeof(_lib.PnrRenderParams)
+    buf = (C.c_uint8 * 64)()
+    assert hip_lib.pnr_render(None, None, p, C.cast(buf, C.c_void_p), None, None, None) == -1
+    assert b"null handle" in hip_lib.pnr_last_error(None)
+    assert "pnr_render" in _lib.SIGNATURES and "pnr_render.h" in _lib.UNITS["pnr_api.hip"]
+    assert "pnr_render.h" not in _lib.ENV_KERNEL_SOURCES
