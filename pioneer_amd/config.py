@@ -149,6 +149,20 @@ _MODES = {"kinematic": _lib.MODE_KINEMATIC, "dynamic": _lib.MODE_DYNAMIC}
 _CONTROLS = {"position": _lib.CONTROL_POSITION, "velocity": _lib.CONTROL_VELOCITY}
 
 
+_SHAPES = {"plane": _lib.SHAPE_PLANE, "box": _lib.SHAPE_BOX, "sphere": _lib.SHAPE_SPHERE}
+
+
+def fill_scene_body(dst: _lib.PnrSceneBody, body: SceneBody, what: str) -> None:
+    """A SceneBody -> the C struct ``dst``; ``what`` names the body in the error."""
+    if body.shape not in _SHAPES:
+        raise AssertionError(f"{what}: shape must be one of {sorted(_SHAPES)}")
+    dst.shape = _SHAPES[body.shape]
+    for k in range(3):
+        dst.position[k] = float(body.position[k]); dst.size[k] = float(body.size[k])
+    for k in range(4):
+        dst.orientation[k] = float(body.orientation[k])
+
+
 def to_c_config(pioneer: PioneerKinematicConfig, sim: SimulationConfig, engine: EngineConfig) -> _lib.PnrConfig:
     """Dataclasses -> the C struct, starting from pnr_config_default()."""
     lib = _lib.load_library()
@@ -192,18 +206,11 @@ def to_c_config(pioneer: PioneerKinematicConfig, sim: SimulationConfig, engine: 
     c.max_velocity = float(engine.max_velocity)
     c.link_contacts = int(bool(engine.link_contacts))
     c.pd_inertia_scaled = int(bool(engine.pd_inertia_scaled))
-    shapes = {"plane": _lib.SHAPE_PLANE, "box": _lib.SHAPE_BOX, "sphere": _lib.SHAPE_SPHERE}
     if len(engine.scene) > _lib.MAX_SCENE:
         raise AssertionError(f"at most {_lib.MAX_SCENE} scene bodies")
     c.n_scene = len(engine.scene)
     for i, b in enumerate(engine.scene):
-        if b.shape not in shapes:
-            raise AssertionError(f"scene body {i}: shape must be one of {sorted(shapes)}")
-        c.scene[i].shape = shapes[b.shape]
-        for k in range(3):
-            c.scene[i].position[k] = float(b.position[k]); c.scene[i].size[k] = float(b.size[k])
-        for k in range(4):
-            c.scene[i].orientation[k] = float(b.orientation[k])
+        fill_scene_body(c.scene[i], b, f"scene body {i}")
     # SimulationConfig.self_collision / collision_parent (bullet_env.py:43-58) select pybullet's URDF_USE_SELF_COLLISION load
     # flags.  The reference URDF has no <collision> elements, so in the reference they change nothing — and here they
     # are accepted with that same meaning.  What is NOT modelled is self-collision between the build-defined link

@@ -22,7 +22,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
+#include <type_traits>
 
 #include "../../include/pioneer_amd.h"
 
@@ -84,6 +86,115 @@ static int fail(pnr_handle h, int code, const char* fmt, ...)
     return rc;
 }
 
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+template <class T>
+static bool finite_all(const T* v, int k)
+{
+    for (int i = 0; i < k; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+static double sum_sq(const double* v, int k)      // v[0]^2 + v[1]^2 + .. in that order
+{
+    double s = 0;
+    for (int i = 0; i < k; ++i) s += v[i] * v[i];
+    return s;
+}
+
+// an optional double argument left out (NaN) takes its default, as setJointMotorControl2's optional arguments take Bullet's
+static inline double or_default(double given, double dflt) { return given == given ? given : dflt; }
+
+// Runtime flags -> template arguments: f is called with a std::integral_constant whose value is `b` (or `v`, which must be one of
+// Vs: only the listed values are instantiated).  Every kernel launch below is written once inside such a call.
+template <class F>
+static inline void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int... Vs, class F>
+static inline void with_int(int v, F&& f) { (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
+
+// One static body of the scene, checked: `who` names the call in the message, `finite` adds pnr_render's rule
+static int check_scene_body(pnr_handle h, const char* who, int b, const pnr_scene_body& S, bool finite)
+{
+    const auto bad = [&](const char* what) { return fail(h, PNR_ERR_INVALID, "%s %d: %s", who, b, what); };
+    if (S.shape != PNR_SHAPE_PLANE && S.shape != PNR_SHAPE_BOX && S.shape != PNR_SHAPE_SPHERE)
+        return fail(h, PNR_ERR_INVALID, "%s %d: bad shape %d", who, b, S.shape);
+    if (finite && !(finite_all(S.position, 3) && finite_all(S.orientation, 4) && finite_all(S.size, 3))) return bad("non-finite data");
+    if (!(sum_sq(S.orientation, 4) > 0)) return bad("zero orientation quaternion");
+    if (S.shape == PNR_SHAPE_PLANE && !(sum_sq(S.size, 3) > 0)) return bad("zero plane normal");
+    if (S.shape == PNR_SHAPE_BOX && !(S.size[0] > 0 && S.size[1] > 0 && S.size[2] > 0)) return bad("box half extents must be > 0");
+    if (S.shape == PNR_SHAPE_SPHERE && !(S.size[0] > 0)) return bad("sphere radius must be > 0");
+    return PNR_OK;
+}
+
+// .. and its frame: the normalised quaternion as a row-major rotation R; for a plane also the unit world normal R n / |n|
+static void scene_body_frame(const pnr_scene_body& S, double (&R)[9], double (&normal)[3])
+{
+    const double qn = std::sqrt(sum_sq(S.orientation, 4));
+    const double x = S.orientation[0] / qn, y = S.orientation[1] / qn, z = S.orientation[2] / qn, w = S.orientation[3] / qn;
+    const double r[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                         2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                         2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+    for (int k = 0; k < 9; ++k) R[k] = r[k];
+    if (S.shape != PNR_SHAPE_PLANE) return;
+    const double nl = std::sqrt(sum_sq(S.size, 3));
+    for (int k = 0; k < 3; ++k) normal[k] = (R[3 * k] * S.size[0] + R[3 * k + 1] * S.size[1] + R[3 * k + 2] * S.size[2]) / nl;
+}
+
+// One joint's entries of the JointMotorTable, assigned in one place
+struct JointMotor { float kp, kd, cpos, vcap, tcap, r_ref = 0.f, v_ref = 0.f; int from_cmd = 0, kind = kMotorPD; };
+
+static void set_motor(JointMotorTable& W, int j, const JointMotor& m)
+{
+    W.kp[j] = m.kp; W.kd[j] = m.kd; W.cpos[j] = m.cpos; W.vcap[j] = m.vcap; W.tcap[j] = m.tcap;
+    W.r_ref[j] = m.r_ref; W.v_ref[j] = m.v_ref; W.from_cmd[j] = m.from_cmd; W.kind[j] = m.kind;
+}
+
+// The one motor law of pnr_dyn.h (oracle: orc_dyn_motor_torque), folded:
+//   tau = clip(kp (r - q) + kd (clamp(v + cpos (r - q), +-vcap) - qd), +-tcap)
+// A velocity cap turns the position term into the velocity asked for; teleport: no motor at all.
+static JointMotor pd_motor(bool velocity, double kp, double kd, double force_limit, double max_velocity, bool teleport)
+{
+    const bool capped = max_velocity > 0;
+    JointMotor m;
+    m.kp = (teleport || velocity || capped) ? 0.f : (float)kp;
+    m.kd = teleport ? 0.f : (float)kd;
+    m.cpos = (!velocity && capped) ? (float)(kp / kd) : 0.f;
+    m.vcap = capped ? (float)max_velocity : INFINITY;
+    m.tcap = force_limit > 0 ? (float)force_limit : INFINITY;
+    return m;
+}
+
+// the dynamics kernels' PHYS template argument: bit 0 contacts (contact-free handles run instantiations without any contact
+// code), bit 1 the inertia-scaled motor
+static inline int dyn_phys(const DynParams& D) { return ((D.has_ground || D.has_box || D.n_scene > 0) ? 1 : 0) | (D.inertia_scaled ? 2 : 0); }
+
+// whose joints a link query or a render reads (pnr_links.h): the caller's buffer, else the handle's own (h->dyn; kinematic: the state)
+static inline int link_source(pnr_handle h, const float* js) { return js ? kLinkSrcBuffer : (h->dyn ? kLinkSrcDyn : kLinkSrcKin); }
+
+// the argument checks of pnr_get_state / pnr_set_state and their dyn twins
+static int check_state_call(pnr_handle h, const void* words, const char* call, bool dyn)
+{
+    if (!h || !words) return fail(h, PNR_ERR_INVALID, "%s: null argument", call);
+    if (dyn && !h->dyn) return fail(h, PNR_ERR_UNSUPPORTED, "handle is not in dynamics mode");
+    return PNR_OK;
+}
+
+static inline unsigned grid_for(long long n) { return (unsigned)((n + kEnvsPerWave - 1) / kEnvsPerWave); }
+
+// reset_kernel<MODE, OBS, DYN>, MODE 0: pnr_reset, 1: pnr_observe; OBS: 0 no obs, env-major rows 2 (all envs) / 3 (masked),
+// feature-major columns 4 (all) / 1 (masked).  KINDS lists the OBS values the call can ask for: only those are instantiated.
+template <int MODE, int... KINDS>
+static int launch_reset(pnr_handle h, const KParams& P, int obs_kind, void* stream)
+{
+    DeviceGuard g(h->device);
+    with_int<KINDS...>(obs_kind, [&](auto O) { with_bool(h->dyn != nullptr, [&](auto Dyn) {
+        hipLaunchKernelGGL((reset_kernel<MODE, O(), Dyn()>), dim3(grid_for(h->n)), dim3(kWave), 0, (hipStream_t)stream, P, h->dbase);
+    }); });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
 
 static const char g_unit_fp[] = "pnr_build_fp:api=" PNR_UNIT_FINGERPRINT ";";
 
@@ -161,19 +272,8 @@ static int check_config(const pnr_config* c)
     if (c->n_scene > 0 && c->mode != PNR_MODE_DYNAMIC)
         return fail(nullptr, PNR_ERR_INVALID, "scene bodies collide in dynamics mode only (the kinematic arm passes through everything, as the reference's does)");
     for (int b = 0; b < c->n_scene; ++b) {
-        const pnr_scene_body& S = c->scene[b];
-        const double qn = S.orientation[0] * S.orientation[0] + S.orientation[1] * S.orientation[1] +
-                          S.orientation[2] * S.orientation[2] + S.orientation[3] * S.orientation[3];
-        if (!(qn > 0)) return fail(nullptr, PNR_ERR_INVALID, "scene body %d: zero orientation quaternion", b);
-        if (S.shape == PNR_SHAPE_PLANE) {
-            if (!(S.size[0] * S.size[0] + S.size[1] * S.size[1] + S.size[2] * S.size[2] > 0))
-                return fail(nullptr, PNR_ERR_INVALID, "scene body %d: zero plane normal", b);
-        } else if (S.shape == PNR_SHAPE_BOX) {
-            if (!(S.size[0] > 0 && S.size[1] > 0 && S.size[2] > 0))
-                return fail(nullptr, PNR_ERR_INVALID, "scene body %d: box half extents must be > 0", b);
-        } else if (S.shape == PNR_SHAPE_SPHERE) {
-            if (!(S.size[0] > 0)) return fail(nullptr, PNR_ERR_INVALID, "scene body %d: sphere radius must be > 0", b);
-        } else return fail(nullptr, PNR_ERR_INVALID, "scene body %d: bad shape %d", b, S.shape);
+        const int rc = check_scene_body(nullptr, "scene body", b, c->scene[b], false);
+        if (rc) return rc;
     }
     return PNR_OK;
 }
@@ -223,20 +323,13 @@ static void fill_base(pnr_handle h)
     D.has_box = (c.obstacle_half_extents[0] > 0 && c.obstacle_half_extents[1] > 0 && c.obstacle_half_extents[2] > 0) ? 1 : 0;
     for (int k = 0; k < 3; ++k) { D.box_c[k] = (float)c.obstacle_position[k]; D.box_h[k] = (float)c.obstacle_half_extents[k]; }
     D.ptr_radius = (float)c.pointer_radius;
-    {   // the one motor law of pnr_dyn.h (oracle: orc_dyn_motor_torque)
-        const bool capped = c.max_velocity > 0;
-        const bool velocity = c.control_mode == PNR_CONTROL_VELOCITY;
-        D.kp_eff = (velocity || capped) ? 0.f : (float)c.pd_kp;
-        D.c_pos = (!velocity && capped) ? (float)(c.pd_kp / c.pd_kd) : 0.f;
-        D.v_cap = capped ? (float)c.max_velocity : INFINITY;
-        // pnr_world_step: until a joint is commanded it runs the handle's motor on the env's own r, v (teleport: no motor at all)
-        for (int i = 0; i < kDof; ++i) {
-            JointMotorTable& W = h->motors;
-            W.kp[i] = c.teleport ? 0.f : D.kp_eff; W.kd[i] = c.teleport ? 0.f : (float)c.pd_kd; W.cpos[i] = D.c_pos; W.vcap[i] = D.v_cap;
-            W.tcap[i] = c.torque_limit > 0 ? (float)c.torque_limit : INFINITY;
-            W.r_ref[i] = 0.f; W.v_ref[i] = 0.f; W.from_cmd[i] = 1; W.kind[i] = kMotorPD;
-        }
-    }
+    const bool velocity = c.control_mode == PNR_CONTROL_VELOCITY;
+    D.kp_eff = pd_motor(velocity, c.pd_kp, c.pd_kd, c.torque_limit, c.max_velocity, false).kp;    // the kernels apply teleport themselves
+    // pnr_world_step: until a joint is commanded it runs the handle's motor on the env's own r, v
+    JointMotor own = pd_motor(velocity, c.pd_kp, c.pd_kd, c.torque_limit, c.max_velocity, c.teleport);
+    own.from_cmd = 1;
+    D.c_pos = own.cpos; D.v_cap = own.vcap;
+    for (int i = 0; i < kDof; ++i) set_motor(h->motors, i, own);
     D.link_contacts = c.link_contacts ? 1 : 0;
     D.inertia_scaled = c.pd_inertia_scaled ? 1 : 0;
     D.n_scene = h->scene ? c.n_scene : 0;
@@ -247,17 +340,12 @@ static void fill_base(pnr_handle h)
         S = SceneBody{};
         if (b >= c.n_scene) continue;
         const pnr_scene_body& B = c.scene[b];
-        const double qn = std::sqrt(B.orientation[0] * B.orientation[0] + B.orientation[1] * B.orientation[1] +
-                                    B.orientation[2] * B.orientation[2] + B.orientation[3] * B.orientation[3]);
-        const double x = B.orientation[0] / qn, y = B.orientation[1] / qn, z = B.orientation[2] / qn, w = B.orientation[3] / qn;
-        const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                             2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                             2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+        double R[9], normal[3];
+        scene_body_frame(B, R, normal);
         S.shape = B.shape;
         for (int k = 0; k < 3; ++k) { S.pos[k] = (float)B.position[k]; S.size[k] = (float)B.size[k]; }
-        if (B.shape == PNR_SHAPE_PLANE) {               // unit world normal = R n / |n|
-            const double nl = std::sqrt(B.size[0] * B.size[0] + B.size[1] * B.size[1] + B.size[2] * B.size[2]);
-            for (int k = 0; k < 3; ++k) S.rot[k] = (float)((R[3 * k] * B.size[0] + R[3 * k + 1] * B.size[1] + R[3 * k + 2] * B.size[2]) / nl);
+        if (B.shape == PNR_SHAPE_PLANE) {
+            for (int k = 0; k < 3; ++k) S.rot[k] = (float)normal[k];
         } else {
             for (int k = 0; k < 9; ++k) S.rot[k] = (float)R[k];
         }
@@ -302,7 +390,10 @@ int pnr_create(const pnr_config* cfg, int64_t num_envs, int64_t env_id_offset, i
             return fail(nullptr, PNR_ERR_INVALID, "model table: cos/sin constants of joint %d are stale", i);
     }
 
-    pnr_handle h = new (std::nothrow) pnr_env_s();
+    // the half-built handle is pnr_destroy's on every early return
+    struct Destroy { void operator()(pnr_handle p) const { pnr_destroy(p); } };
+    std::unique_ptr<pnr_env_s, Destroy> owner(new (std::nothrow) pnr_env_s());
+    const pnr_handle h = owner.get();
     if (!h) return fail(nullptr, PNR_ERR_NOMEM, "host allocation failed");
     memset(h, 0, sizeof(*h));
     h->cfg = *cfg;
@@ -312,36 +403,31 @@ int pnr_create(const pnr_config* cfg, int64_t num_envs, int64_t env_id_offset, i
     pnr_get_constants(cfg, &h->k);
 
     DeviceGuard g(device_id);
-    hipError_t e = hipMalloc((void**)&h->state, sizeof(float4) * kStatePlanes * 2 * (size_t)num_envs);
-    if (e != hipSuccess) { delete h; return fail(nullptr, PNR_ERR_NOMEM, "hipMalloc(state) failed: %s", hipGetErrorString(e)); }
-    (void)hipMemset(h->state, 0, sizeof(float4) * kStatePlanes * 2 * (size_t)num_envs);
+    const auto alloc = [](void** p, size_t bytes, const char* what, bool zero) {      // *p stays null unless the memory is there
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return fail(nullptr, PNR_ERR_NOMEM, "hipMalloc(%s) failed: %s", what, hipGetErrorString(e));
+        *p = q;
+        if (zero) (void)hipMemset(q, 0, bytes);
+        return (int)PNR_OK;
+    };
+    if ((rc = alloc((void**)&h->state, sizeof(float4) * kStatePlanes * 2 * (size_t)num_envs, "state", true))) return rc;
     if (cfg->mode == PNR_MODE_DYNAMIC) {
-        const size_t bytes = sizeof(float) * PNR_DYN_STATE_WORDS * (size_t)num_envs;
-        e = hipMalloc((void**)&h->dyn, bytes);
-        if (e != hipSuccess) { (void)hipFree(h->state); delete h; return fail(nullptr, PNR_ERR_NOMEM, "hipMalloc(dyn) failed: %s", hipGetErrorString(e)); }
-        (void)hipMemset(h->dyn, 0, bytes);
-        if (cfg->n_scene > 0) {
-            e = hipMalloc((void**)&h->scene, sizeof(SceneBody) * kMaxScene);
-            if (e != hipSuccess) { (void)hipFree(h->dyn); (void)hipFree(h->state); delete h; return fail(nullptr, PNR_ERR_NOMEM, "hipMalloc(scene) failed: %s", hipGetErrorString(e)); }
-        }
+        if ((rc = alloc((void**)&h->dyn, sizeof(float) * PNR_DYN_STATE_WORDS * (size_t)num_envs, "dyn", true))) return rc;
+        if (cfg->n_scene > 0 && (rc = alloc((void**)&h->scene, sizeof(SceneBody) * kMaxScene, "scene", false))) return rc;
     }
     // The zero fills above run on the NULL stream; the caller's first pnr_reset may be issued on a non-blocking stream (every
     // torch.cuda.Stream is one), which is not ordered after NULL-stream work, and reset_env reads the episode counters from
     // these planes.  pnr_create is the one call that synchronises (include/pioneer_amd.h, Conventions): when it returns, the
     // planes are zero for every stream.
-    e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        if (h->scene) (void)hipFree(h->scene);
-        if (h->dyn) (void)hipFree(h->dyn);
-        (void)hipFree(h->state); delete h;
-        return fail(nullptr, PNR_ERR_HIP, "pnr_create: zero fill of the state planes failed: %s", hipGetErrorString(e));
-    }
+    const hipError_t e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return fail(nullptr, PNR_ERR_HIP, "pnr_create: zero fill of the state planes failed: %s", hipGetErrorString(e));
 #if PNR_DIAG_BUILD
     { const char* e_ = getenv("PNR_DIAG"); h->diag = e_ ? atoi(e_) : 0; }
 #endif
     fill_base(h);
     h->base.seed_lo = (unsigned)seed; h->base.seed_hi = (unsigned)(seed >> 32);
-    *out = h;
+    *out = owner.release();
     return PNR_OK;
 }
 
@@ -366,8 +452,6 @@ int pnr_seed(pnr_handle h, uint64_t seed)
 int64_t pnr_num_envs(pnr_handle h) { return h ? h->n : -1; }
 
 const char* pnr_last_error(pnr_handle h) { return h ? h->err : g_err; }
-
-static inline unsigned grid_for(long long n) { return (unsigned)((n + kEnvsPerWave - 1) / kEnvsPerWave); }
 
 // step kernels are persistent over tiles: at most 8 one-wave workgroups per CU (256 CUs)
 // Persistent grid of one-wave workgroups.  One launch per step: 2 048 (two waves per SIMD; with a single tile
@@ -394,29 +478,13 @@ int pnr_reset(pnr_handle h, const uint8_t* mask, const float* joint_pos, const f
               float* obs_out, void* stream)
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    DeviceGuard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    KParams P = h->base;
-    P.mask = mask; P.joint_pos = joint_pos; P.target_pos = target_pos; P.obs = obs_out;
-    const dim3 grid(grid_for(h->n)), block(kWave);
-    const DynParams& D = h->dbase;
-    const bool fm = h->cfg.obs_layout == PNR_FEATURE_MAJOR;
-#define PNR_LAUNCH_RESET(OBSK)                                                                     \
-    do {                                                                                           \
-        if (h->dyn) hipLaunchKernelGGL((reset_kernel<0, OBSK, true>), grid, block, 0, st, P, D);   \
-        else hipLaunchKernelGGL((reset_kernel<0, OBSK, false>), grid, block, 0, st, P, D);         \
-    } while (0)
     if (mask && !h->ready)
         return fail(h, PNR_ERR_INVALID, "the first pnr_reset must be a full one (mask == NULL)");
     if (!mask) h->ready = true;
-    if (!obs_out) PNR_LAUNCH_RESET(0);
-    else if (fm && mask) PNR_LAUNCH_RESET(1);
-    else if (fm) PNR_LAUNCH_RESET(4);
-    else if (!mask) PNR_LAUNCH_RESET(2);
-    else PNR_LAUNCH_RESET(3);
-#undef PNR_LAUNCH_RESET
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    KParams P = h->base;
+    P.mask = mask; P.joint_pos = joint_pos; P.target_pos = target_pos; P.obs = obs_out;
+    const bool fm = h->cfg.obs_layout == PNR_FEATURE_MAJOR;
+    return launch_reset<0, 0, 1, 2, 3, 4>(h, P, !obs_out ? 0 : (fm ? (mask ? 1 : 4) : (mask ? 3 : 2)), stream);
 }
 
 int pnr_observe(pnr_handle h, float* obs_out, void* stream)
@@ -424,19 +492,9 @@ int pnr_observe(pnr_handle h, float* obs_out, void* stream)
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!obs_out) return fail(h, PNR_ERR_INVALID, "pnr_observe: null obs_out");
     if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_observe before the first pnr_reset");
-    DeviceGuard g(h->device);
     KParams P = h->base;
     P.obs = obs_out;
-    const dim3 grid(grid_for(h->n)), block(kWave);
-    const DynParams& D = h->dbase;
-    hipStream_t st = (hipStream_t)stream;
-    const bool fm = h->cfg.obs_layout == PNR_FEATURE_MAJOR;
-    if (fm && h->dyn) hipLaunchKernelGGL((reset_kernel<1, 4, true>), grid, block, 0, st, P, D);
-    else if (fm) hipLaunchKernelGGL((reset_kernel<1, 4, false>), grid, block, 0, st, P, D);
-    else if (h->dyn) hipLaunchKernelGGL((reset_kernel<1, 2, true>), grid, block, 0, st, P, D);
-    else hipLaunchKernelGGL((reset_kernel<1, 2, false>), grid, block, 0, st, P, D);
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    return launch_reset<1, 2, 4>(h, P, h->cfg.obs_layout == PNR_FEATURE_MAJOR ? 4 : 2, stream);
 }
 
 static int launch_step(pnr_handle h, int T, const float* actions, float* obs, float* reward,
@@ -447,9 +505,8 @@ static int launch_step(pnr_handle h, int T, const float* actions, float* obs, fl
         return fail(h, PNR_ERR_INVALID, "actions, obs, reward and done must be non-null");
     if (T < 1) return fail(h, PNR_ERR_INVALID, "T must be >= 1 (got %d)", T);
     if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_step before the first pnr_reset (or pnr_set_state)");
-    if (info && (reinterpret_cast<uintptr_t>(info) & 15u))
-        return fail(h, PNR_ERR_INVALID, "info must be 16-byte aligned");
-    if (h->cfg.action_layout == PNR_ENV_MAJOR && (reinterpret_cast<uintptr_t>(actions) & 7u))
+    if (!aligned16(info)) return fail(h, PNR_ERR_INVALID, "info must be 16-byte aligned");
+    if (h->cfg.action_layout == PNR_ENV_MAJOR && !aligned8(actions))
         return fail(h, PNR_ERR_INVALID, "env-major actions must be 8-byte aligned");
     DeviceGuard g(h->device);
     KParams P = h->base;
@@ -459,43 +516,24 @@ static int launch_step(pnr_handle h, int T, const float* actions, float* obs, fl
     hipStream_t st = (hipStream_t)stream;
     const DynParams& D = h->dbase;
     const bool oem = h->cfg.obs_layout == PNR_ENV_MAJOR, aem = h->cfg.action_layout == PNR_ENV_MAJOR;
-    if (h->cfg.mode == PNR_MODE_DYNAMIC) {
-        // one launch: dyn_step_kernel runs the sub-steps one env per lane, then finishes each step (reward /
-        // TimeLimit / auto-reset / obs) as lane pairs, T times
-        const dim3 gridD((unsigned)((h->n + kDynEnvsPerWg - 1) / kDynEnvsPerWg));
-        // link scales differ from 1 only under randomisation (or after pnr_set_dyn_state, which marks it)
-        const bool rnd = h->cfg.randomize || h->dyn_set;
-        {
-            const KParams& Pt = P;
-            // T > 1: dyn_rollout_kernel loops over the steps inside the launch (state in registers, stores of step t
-            // under the sub-steps of t + 1); T == 1: the lean single-step kernel
-#define PNR_DYN_LAUNCH2(O, A, R, C) do { \
-        if (T > 1) hipLaunchKernelGGL((dyn_rollout_kernel<O, A, R, C>), dim3((gridD.x + kDynRolloutWaves - 1) / kDynRolloutWaves), dim3(kWave * kDynRolloutWaves), 0, st, Pt.state, D.dyn, Pt.actions, Pt.n, Pt.dt, \
-                                      Pt.eps, (float)h->cfg.max_v_to_r, Pt, D); \
-        else hipLaunchKernelGGL((dyn_step_kernel<O, A, R, C>), gridD, dim3(kWave * kDynStepWaves), 0, st, Pt.state, D.dyn, Pt.actions, Pt.n, Pt.dt, \
-                                Pt.eps, (float)h->cfg.max_v_to_r, Pt, D); } while (0)
-            // contact-free handles run instantiations without any contact code
-            // (PHYS: bit 0 contacts, bit 1 the inertia-scaled motor)
-#define PNR_DYN_LAUNCH(O, A, R) do { const bool ct_ = D.has_ground || D.has_box || D.n_scene > 0; \
-        if (D.inertia_scaled) { if (ct_) PNR_DYN_LAUNCH2(O, A, R, 3); else PNR_DYN_LAUNCH2(O, A, R, 2); } \
-        else { if (ct_) PNR_DYN_LAUNCH2(O, A, R, 1); else PNR_DYN_LAUNCH2(O, A, R, 0); } } while (0)
-            if (oem) {
-                if (aem) { if (rnd) PNR_DYN_LAUNCH(true, true, true); else PNR_DYN_LAUNCH(true, true, false); }
-                else { if (rnd) PNR_DYN_LAUNCH(true, false, true); else PNR_DYN_LAUNCH(true, false, false); }
-            } else {
-                if (aem) { if (rnd) PNR_DYN_LAUNCH(false, true, true); else PNR_DYN_LAUNCH(false, true, false); }
-                else { if (rnd) PNR_DYN_LAUNCH(false, false, true); else PNR_DYN_LAUNCH(false, false, false); }
-            }
-#undef PNR_DYN_LAUNCH2
-#undef PNR_DYN_LAUNCH
+    const float mvr = (float)h->cfg.max_v_to_r;
+    with_bool(oem, [&](auto O) { with_bool(aem, [&](auto A) {
+        if (h->cfg.mode != PNR_MODE_DYNAMIC) {
+            hipLaunchKernelGGL((step_kernel<O(), A()>), grid, block, 0, st, P.state, P.actions, P.n, P.dt, P.eps, mvr, P);
+            return;
         }
-        HIP_TRY(h, hipGetLastError());
-        return PNR_OK;
-    }
-    if (oem && aem) hipLaunchKernelGGL((step_kernel<true, true>), grid, block, 0, st, P.state, P.actions, P.n, P.dt, P.eps, (float)h->cfg.max_v_to_r, P);
-    else if (oem && !aem) hipLaunchKernelGGL((step_kernel<true, false>), grid, block, 0, st, P.state, P.actions, P.n, P.dt, P.eps, (float)h->cfg.max_v_to_r, P);
-    else if (!oem && aem) hipLaunchKernelGGL((step_kernel<false, true>), grid, block, 0, st, P.state, P.actions, P.n, P.dt, P.eps, (float)h->cfg.max_v_to_r, P);
-    else hipLaunchKernelGGL((step_kernel<false, false>), grid, block, 0, st, P.state, P.actions, P.n, P.dt, P.eps, (float)h->cfg.max_v_to_r, P);
+        // one launch: the dynamics kernels run the sub-steps one env per lane, then finish each step (reward / TimeLimit /
+        // auto-reset / obs) as lane pairs, T times.  T > 1: dyn_rollout_kernel loops over the steps inside the launch (state in
+        // registers, stores of step t under the sub-steps of t + 1); T == 1: the lean single-step kernel.
+        const unsigned wgs = (unsigned)((h->n + kDynEnvsPerWg - 1) / kDynEnvsPerWg);
+        // link scales differ from 1 only under randomisation (or after pnr_set_dyn_state, which marks it)
+        with_bool(h->cfg.randomize || h->dyn_set, [&](auto R) { with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) {
+            if (T > 1) hipLaunchKernelGGL((dyn_rollout_kernel<O(), A(), R(), C()>), dim3((wgs + kDynRolloutWaves - 1) / kDynRolloutWaves),
+                                          dim3(kWave * kDynRolloutWaves), 0, st, P.state, D.dyn, P.actions, P.n, P.dt, P.eps, mvr, P, D);
+            else hipLaunchKernelGGL((dyn_step_kernel<O(), A(), R(), C()>), dim3(wgs), dim3(kWave * kDynStepWaves), 0, st, P.state, D.dyn,
+                                    P.actions, P.n, P.dt, P.eps, mvr, P, D);
+        }); });
+    }); });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }
@@ -504,31 +542,25 @@ static int launch_step(pnr_handle h, int T, const float* actions, float* obs, fl
 static int set_constraint_motor(pnr_handle h, int joint, bool position, double target_position, double target_velocity,
                                 double position_gain, double velocity_gain, double max_force, double max_velocity)
 {
-    const auto pick = [](double given, double dflt) { return given == given ? given : dflt; };
     if (position ? !std::isfinite(target_position) : !std::isfinite(target_velocity))
         return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: the %s target must be finite", position ? "position" : "velocity");
-    const double vt = pick(target_velocity, PNR_BULLET_TARGET_VELOCITY);
-    const double kp = pick(position_gain, PNR_BULLET_POSITION_GAIN), kd = pick(velocity_gain, PNR_BULLET_VELOCITY_GAIN);
-    const double fmax = pick(max_force, PNR_BULLET_MAX_FORCE), vmax = pick(max_velocity, PNR_BULLET_MAX_VELOCITY);
+    const double vt = or_default(target_velocity, PNR_BULLET_TARGET_VELOCITY);
+    const double kp = or_default(position_gain, PNR_BULLET_POSITION_GAIN), kd = or_default(velocity_gain, PNR_BULLET_VELOCITY_GAIN);
+    const double fmax = or_default(max_force, PNR_BULLET_MAX_FORCE), vmax = or_default(max_velocity, PNR_BULLET_MAX_VELOCITY);
     if (!std::isfinite(vt)) return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: targetVelocity must be finite");
     if (!std::isfinite(kp) || !std::isfinite(kd) || kp < 0 || kd < 0)
         return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: gains must be finite and >= 0 (%g, %g)", kp, kd);
     if (!(fmax >= 0)) return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: force must be >= 0 (%g)", fmax);
-    JointMotorTable& W = h->motors;
-    W.from_cmd[joint] = 0;
-    W.cpos[joint] = 0.f;
-    if (fmax == 0) {                      // Bullet: no motor, the joint is free (as the PD law with zero gains and no cap)
-        W.kind[joint] = kMotorPD;
-        W.kp[joint] = 0.f; W.kd[joint] = 0.f; W.vcap[joint] = INFINITY; W.tcap[joint] = INFINITY;
-        W.r_ref[joint] = 0.f; W.v_ref[joint] = 0.f;
-        return PNR_OK;
+    JointMotor m = pd_motor(false, 0.0, 0.0, 0.0, 0.0, false);   // fmax == 0, Bullet: no motor, the joint is free (the PD law with zero gains, no cap)
+    if (fmax > 0) {
+        m.kind = position ? kMotorPositionConstraint : kMotorVelocityConstraint;
+        m.kp = (float)kp; m.kd = (float)kd;
+        m.vcap = (position && vmax > 0) ? (float)vmax : INFINITY;
+        m.tcap = (float)fmax;
+        m.r_ref = position ? (float)target_position : 0.f;
+        m.v_ref = (float)vt;
     }
-    W.kind[joint] = position ? kMotorPositionConstraint : kMotorVelocityConstraint;
-    W.kp[joint] = (float)kp; W.kd[joint] = (float)kd;
-    W.vcap[joint] = (position && vmax > 0) ? (float)vmax : INFINITY;
-    W.tcap[joint] = (float)fmax;
-    W.r_ref[joint] = position ? (float)target_position : 0.f;
-    W.v_ref[joint] = (float)vt;
+    set_motor(h->motors, joint, m);
     return PNR_OK;
 }
 
@@ -544,23 +576,16 @@ int pnr_set_joint_motor(pnr_handle h, int joint, int control_mode, double target
     if (control_mode != PNR_CONTROL_POSITION && control_mode != PNR_CONTROL_VELOCITY)
         return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: control_mode %d", control_mode);
     const pnr_config& c = h->cfg;
-    // an argument left out (NaN) takes the handle's own value, as setJointMotorControl2's optional arguments take Bullet's defaults
-    const auto pick = [](double given, double dflt) { return given == given ? given : dflt; };
-    const double kp = pick(position_gain, c.pd_kp), kd = pick(velocity_gain, c.pd_kd);
-    const double fmax = pick(max_force, c.torque_limit), vmax = pick(max_velocity, c.max_velocity);
-    if (kd <= 0 && control_mode == PNR_CONTROL_POSITION && vmax > 0)
+    // an argument left out (NaN) takes the handle's own value
+    const double kp = or_default(position_gain, c.pd_kp), kd = or_default(velocity_gain, c.pd_kd);
+    const double fmax = or_default(max_force, c.torque_limit), vmax = or_default(max_velocity, c.max_velocity);
+    const bool velocity = control_mode == PNR_CONTROL_VELOCITY;
+    if (kd <= 0 && !velocity && vmax > 0)
         return fail(h, PNR_ERR_INVALID, "pnr_set_joint_motor: maxVelocity needs velocity_gain > 0");
-    const bool velocity = control_mode == PNR_CONTROL_VELOCITY, capped = !velocity && vmax > 0;
-    JointMotorTable& W = h->motors;       // the folding of fill_base (oracle: orc_dyn_motor_torque), per joint
-    W.kp[joint] = (velocity || capped) ? 0.f : (float)kp;
-    W.kd[joint] = (float)kd;
-    W.cpos[joint] = capped ? (float)(kp / kd) : 0.f;
-    W.vcap[joint] = capped ? (float)vmax : INFINITY;
-    W.tcap[joint] = fmax > 0 ? (float)fmax : INFINITY;
-    W.r_ref[joint] = velocity ? 0.f : (float)target_position;
-    W.v_ref[joint] = (float)pick(target_velocity, 0.0);
-    W.from_cmd[joint] = 0;
-    W.kind[joint] = kMotorPD;
+    JointMotor m = pd_motor(velocity, kp, kd, fmax, velocity ? 0.0 : vmax, false);      // VELOCITY_CONTROL has no maxVelocity
+    m.r_ref = velocity ? 0.f : (float)target_position;
+    m.v_ref = (float)or_default(target_velocity, 0.0);
+    set_motor(h->motors, joint, m);
     return PNR_OK;
 }
 
@@ -580,19 +605,12 @@ int pnr_world_step(pnr_handle h, float* joint_state, void* stream)
     if (joint_state) return fail(h, PNR_ERR_INVALID, "pnr_world_step: joint_state must be NULL in dynamics mode (the simulated joints are the handle's)");
     const DynParams& D = h->dbase;
     const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
-    const bool ct = D.has_ground || D.has_box || D.n_scene > 0;
     bool cm = false;                      // a constraint motor anywhere: the instantiation with motor_constraints
     for (int i = 0; i < kDof; ++i) cm = cm || h->motors.kind[i] != kMotorPD;
     // (always the instantiation that reads the per-env link scales: without randomisation they are stored as 1)
-#define PNR_WORLD_LAUNCH(C, M) hipLaunchKernelGGL((dyn_world_kernel<true, C, M>), grid, dim3(kWave), 0, st, h->state, h->dyn, (long long)h->n, D, h->motors)
-    if (cm) {
-        if (D.inertia_scaled) { if (ct) PNR_WORLD_LAUNCH(3, true); else PNR_WORLD_LAUNCH(2, true); }
-        else { if (ct) PNR_WORLD_LAUNCH(1, true); else PNR_WORLD_LAUNCH(0, true); }
-    } else {
-        if (D.inertia_scaled) { if (ct) PNR_WORLD_LAUNCH(3, false); else PNR_WORLD_LAUNCH(2, false); }
-        else { if (ct) PNR_WORLD_LAUNCH(1, false); else PNR_WORLD_LAUNCH(0, false); }
-    }
-#undef PNR_WORLD_LAUNCH
+    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) { with_bool(cm, [&](auto M) {
+        hipLaunchKernelGGL((dyn_world_kernel<true, C(), M()>), grid, dim3(kWave), 0, st, h->state, h->dyn, (long long)h->n, D, h->motors);
+    }); });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }
@@ -638,10 +656,9 @@ int pnr_diag_sincos(const float* x, float* sin_out, float* cos_out, int64_t n, i
     return PNR_OK;
 }
 
-
 int pnr_get_state(pnr_handle h, uint32_t* words_out, void* stream)
 {
-    if (!h || !words_out) return fail(h, PNR_ERR_INVALID, "pnr_get_state: null argument");
+    if (const int rc = check_state_call(h, words_out, "pnr_get_state", false)) return rc;
     DeviceGuard g(h->device);
     hipLaunchKernelGGL(state_to_words_kernel, dim3((unsigned)((2 * h->n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, h->state, words_out, h->n);
@@ -651,7 +668,7 @@ int pnr_get_state(pnr_handle h, uint32_t* words_out, void* stream)
 
 int pnr_set_state(pnr_handle h, const uint32_t* words_in, void* stream)
 {
-    if (!h || !words_in) return fail(h, PNR_ERR_INVALID, "pnr_set_state: null argument");
+    if (const int rc = check_state_call(h, words_in, "pnr_set_state", false)) return rc;
     DeviceGuard g(h->device);
     h->kin_set = true;
     if (!h->dyn || h->dyn_set) h->ready = true;
@@ -663,8 +680,7 @@ int pnr_set_state(pnr_handle h, const uint32_t* words_in, void* stream)
 
 int pnr_get_dyn_state(pnr_handle h, float* words_out, void* stream)
 {
-    if (!h || !words_out) return fail(h, PNR_ERR_INVALID, "pnr_get_dyn_state: null argument");
-    if (!h->dyn) return fail(h, PNR_ERR_UNSUPPORTED, "handle is not in dynamics mode");
+    if (const int rc = check_state_call(h, words_out, "pnr_get_dyn_state", true)) return rc;
     DeviceGuard g(h->device);
     const size_t bytes = sizeof(float) * PNR_DYN_STATE_WORDS * (size_t)h->n;
     HIP_TRY(h, hipMemcpyAsync(words_out, h->dyn, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -673,8 +689,7 @@ int pnr_get_dyn_state(pnr_handle h, float* words_out, void* stream)
 
 int pnr_set_dyn_state(pnr_handle h, const float* words_in, void* stream)
 {
-    if (!h || !words_in) return fail(h, PNR_ERR_INVALID, "pnr_set_dyn_state: null argument");
-    if (!h->dyn) return fail(h, PNR_ERR_UNSUPPORTED, "handle is not in dynamics mode");
+    if (const int rc = check_state_call(h, words_in, "pnr_set_dyn_state", true)) return rc;
     DeviceGuard g(h->device);
     h->dyn_set = true;
     if (h->kin_set) h->ready = true;
@@ -687,29 +702,24 @@ int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!out) return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: null out");
-    if (reinterpret_cast<uintptr_t>(out) & 15u) return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: out must be 16-byte aligned");
-    if (joint_state && (reinterpret_cast<uintptr_t>(joint_state) & 15u))
+    if (!aligned16(out)) return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: out must be 16-byte aligned");
+    if (!aligned16(joint_state))
         return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: joint_state must be 16-byte aligned");
     if (!joint_state && !h->dyn && !h->ready)
         return fail(h, PNR_ERR_INVALID, "pnr_get_link_states before the first pnr_reset (or pnr_set_state)");
     DeviceGuard g(h->device);
     const dim3 grid((unsigned)((h->n + kWave - 1) / kWave)), block(kWave);
     hipStream_t st = (hipStream_t)stream;
-    if (joint_state) hipLaunchKernelGGL(link_state_kernel<kLinkSrcBuffer>, grid, block, 0, st, joint_state, nullptr, out, (long long)h->n);
-    else if (h->dyn) hipLaunchKernelGGL(link_state_kernel<kLinkSrcDyn>, grid, block, 0, st, h->dyn, nullptr, out, (long long)h->n);
-    else hipLaunchKernelGGL(link_state_kernel<kLinkSrcKin>, grid, block, 0, st, nullptr, h->state, out, (long long)h->n);
+    const int src = link_source(h, joint_state);
+    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
+        hipLaunchKernelGGL(link_state_kernel<S()>, grid, block, 0, st, joint_state ? joint_state : h->dyn,
+                           src == kLinkSrcKin ? h->state : nullptr, out, (long long)h->n);
+    });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }
 
 }  // extern "C"
-
-static bool finite_all(const double* v, int k)
-{
-    for (int i = 0; i < k; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
 
 // pnr_render's checks of its params (nothing launched, nothing written on failure) and the kernel's constants built from them
 static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& P)
@@ -731,30 +741,17 @@ static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& 
                 return fail(h, PNR_ERR_INVALID, "pnr_render: the view matrix's rotation is not orthonormal");
         }
     if (!finite_all(p->light_direction, 3)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite light_direction");
-    const double ll = std::sqrt(p->light_direction[0] * p->light_direction[0] + p->light_direction[1] * p->light_direction[1] +
-                                p->light_direction[2] * p->light_direction[2]);
+    const double ll = std::sqrt(sum_sq(p->light_direction, 3));
     if (!(ll > 0)) return fail(h, PNR_ERR_INVALID, "pnr_render: zero light_direction");
     if (!std::isfinite(p->ambient) || !std::isfinite(p->diffuse)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite ambient or diffuse");
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(p->background[k])) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite background");
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(p->target_rgba[k])) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite target_rgba");
+    if (!finite_all(p->background, 3)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite background");
+    if (!finite_all(p->target_rgba, 4)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite target_rgba");
     if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
         return fail(h, PNR_ERR_INVALID, "pnr_render: n_bodies %d outside 0..%d", p->n_bodies, PNR_MAX_SCENE);
     for (int b = 0; b < p->n_bodies; ++b) {
-        const pnr_scene_body& S = p->bodies[b];
-        if (S.shape != PNR_SHAPE_PLANE && S.shape != PNR_SHAPE_BOX && S.shape != PNR_SHAPE_SPHERE)
-            return fail(h, PNR_ERR_INVALID, "pnr_render: body %d: bad shape %d", b, S.shape);
-        bool ok = finite_all(S.position, 3) && finite_all(S.orientation, 4) && finite_all(S.size, 3);
-        for (int k = 0; k < 4; ++k) ok = ok && std::isfinite(p->body_rgba[b][k]);
-        if (!ok) return fail(h, PNR_ERR_INVALID, "pnr_render: body %d: non-finite data", b);
-        const double qn = S.orientation[0] * S.orientation[0] + S.orientation[1] * S.orientation[1] +
-                          S.orientation[2] * S.orientation[2] + S.orientation[3] * S.orientation[3];
-        const double sn = S.size[0] * S.size[0] + S.size[1] * S.size[1] + S.size[2] * S.size[2];
-        if (!(qn > 0) || (S.shape == PNR_SHAPE_PLANE && !(sn > 0)) ||
-            (S.shape == PNR_SHAPE_BOX && !(S.size[0] > 0 && S.size[1] > 0 && S.size[2] > 0)) ||
-            (S.shape == PNR_SHAPE_SPHERE && !(S.size[0] > 0)))
-            return fail(h, PNR_ERR_INVALID, "pnr_render: body %d: zero quaternion, normal or size", b);
+        const int rc = check_scene_body(h, "pnr_render: body", b, p->bodies[b], true);
+        if (rc) return rc;
+        if (!finite_all(p->body_rgba[b], 4)) return fail(h, PNR_ERR_INVALID, "pnr_render: body %d: non-finite colour", b);
     }
 
     memset(&P, 0, sizeof(P));
@@ -788,28 +785,23 @@ static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& 
     for (int b = 0; b < p->n_bodies; ++b) {
         const pnr_scene_body& S = p->bodies[b];
         RenderPrim& Q = P.bodies[b];
-        const double qn = std::sqrt(S.orientation[0] * S.orientation[0] + S.orientation[1] * S.orientation[1] +
-                                    S.orientation[2] * S.orientation[2] + S.orientation[3] * S.orientation[3]);
-        const double x = S.orientation[0] / qn, y = S.orientation[1] / qn, z = S.orientation[2] / qn, w = S.orientation[3] / qn;
-        const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                             2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                             2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+        double R[9], normal[3];
+        scene_body_frame(S, R, normal);
         const double e[3] = {eye[0] - S.position[0], eye[1] - S.position[1], eye[2] - S.position[2]};
         double rt[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {e[0], e[1], e[2]}, bound = 0;
         if (S.shape == PNR_SHAPE_BOX) {
             for (int i = 0; i < 3; ++i)
                 for (int k = 0; k < 3; ++k) rt[3 * i + k] = R[3 * k + i];
             for (int i = 0; i < 3; ++i) { o[i] = rt[3 * i] * e[0] + rt[3 * i + 1] * e[1] + rt[3 * i + 2] * e[2]; Q.h[i] = (float)S.size[i]; }
-            bound = std::sqrt(S.size[0] * S.size[0] + S.size[1] * S.size[1] + S.size[2] * S.size[2]);
+            bound = std::sqrt(sum_sq(S.size, 3));
             Q.shape = kVisBox;
         } else if (S.shape == PNR_SHAPE_SPHERE) {
             for (int i = 0; i < 3; ++i) Q.h[i] = (float)S.size[0];
             bound = S.size[0];
             Q.shape = kVisSphere;
         } else {                                     // unit world normal R n / |n| as the frame's z row
-            const double nl = std::sqrt(S.size[0] * S.size[0] + S.size[1] * S.size[1] + S.size[2] * S.size[2]);
             for (int k = 0; k < 6; ++k) rt[k] = 0;
-            for (int k = 0; k < 3; ++k) rt[6 + k] = (R[3 * k] * S.size[0] + R[3 * k + 1] * S.size[1] + R[3 * k + 2] * S.size[2]) / nl;
+            for (int k = 0; k < 3; ++k) rt[6 + k] = normal[k];
             o[0] = o[1] = 0;
             o[2] = rt[6] * e[0] + rt[7] * e[1] + rt[8] * e[2];
             Q.shape = kVisPlane;
@@ -836,8 +828,7 @@ int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* 
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!p) return fail(h, PNR_ERR_INVALID, "pnr_render: null params");
     if (!rgb && !depth && !seg) return fail(h, PNR_ERR_INVALID, "pnr_render: every output is NULL");
-    if ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(seg) |
-         reinterpret_cast<uintptr_t>(joint_state)) & 15u)
+    if (!(aligned16(rgb) && aligned16(depth) && aligned16(seg) && aligned16(joint_state)))
         return fail(h, PNR_ERR_INVALID, "pnr_render: outputs and joint_state must be 16-byte aligned");
     if (!h->ready && !h->kin_set)
         return fail(h, PNR_ERR_INVALID, "pnr_render before the first pnr_reset (or pnr_set_state): the target comes from the state");
@@ -847,9 +838,10 @@ int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* 
     DeviceGuard g(h->device);
     const dim3 grid((unsigned)(h->n * P.tiles)), block(kRenderThreads);
     hipStream_t st = (hipStream_t)stream;
-    if (joint_state) hipLaunchKernelGGL(render_kernel<kLinkSrcBuffer>, grid, block, 0, st, joint_state, h->state, (long long)h->n, P, rgb, depth, seg);
-    else if (h->dyn) hipLaunchKernelGGL(render_kernel<kLinkSrcDyn>, grid, block, 0, st, h->dyn, h->state, (long long)h->n, P, rgb, depth, seg);
-    else hipLaunchKernelGGL(render_kernel<kLinkSrcKin>, grid, block, 0, st, nullptr, h->state, (long long)h->n, P, rgb, depth, seg);
+    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(link_source(h, joint_state), [&](auto S) {
+        hipLaunchKernelGGL(render_kernel<S()>, grid, block, 0, st, joint_state ? joint_state : h->dyn, h->state, (long long)h->n, P, rgb,
+                           depth, seg);
+    });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }

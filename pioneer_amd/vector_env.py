@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import EngineConfig, PioneerKinematicConfig, SimulationConfig, to_c_config
+from .config import EngineConfig, PioneerKinematicConfig, SimulationConfig, fill_scene_body, to_c_config
 from .spaces import Box
 
 
@@ -108,6 +108,18 @@ class PioneerVectorEnv:
     def _new(self, shape, dtype=torch.float32):
         return torch.empty(shape, dtype=dtype, device=self.device)
 
+    def _out(self, out, key, shape, dtype=torch.float32, check=True):
+        """The caller's output tensor (``out`` itself, or ``out[key]`` of a dict of them) or, without one, a new tensor.
+        ``check``: the caller's must have this shape and be written in place; else (vector_step, rollout) it is taken as given."""
+        t = out.get(key) if hasattr(out, "get") else out
+        if t is None:
+            return self._new(shape, dtype)
+        if not check:
+            return t
+        res = self._in(t, shape, dtype, key)
+        assert res.data_ptr() == t.data_ptr(), f"{key} is written in place: it must already be a contiguous {dtype} device tensor"
+        return res
+
     # -- gym-ish surface ----------------------------------------------------------------
     def seed(self, seed=None):
         """pioneer_knm_env.py:107-109 (takes effect at the next reset)."""
@@ -131,12 +143,9 @@ class PioneerVectorEnv:
         m = None if mask is None else self._in(torch.as_tensor(mask).to(torch.uint8), (n,), torch.uint8, "mask")
         jp = None if joint_positions is None else self._in(joint_positions, (n, 6), torch.float32, "joint_positions")
         tp = None if target_positions is None else self._in(target_positions, (n, 3), torch.float32, "target_positions")
-        if out is None:
-            obs = self._new(self.obs_shape)
-            if m is not None:
-                self._chk(self.lib.pnr_observe(self._h, _ptr(obs), self._stream()))
-        else:
-            obs = self._in(out, self.obs_shape, torch.float32, "out")
+        obs = self._out(out, "out", self.obs_shape)
+        if out is None and m is not None:
+            self._chk(self.lib.pnr_observe(self._h, _ptr(obs), self._stream()))
         self._chk(self.lib.pnr_reset(self._h, _ptr(m), _ptr(jp), _ptr(tp), _ptr(obs), self._stream()))
         return obs
 
@@ -161,13 +170,11 @@ class PioneerVectorEnv:
         n = self.num_envs
         act = self._in(actions, self.action_shape, torch.float32, "actions")
         out = out or {}
-        obs = out.get("obs") if out.get("obs") is not None else self._new(self.obs_shape)
-        rew = out.get("reward") if out.get("reward") is not None else self._new((n,))
-        done = out.get("done") if out.get("done") is not None else self._new((n,), torch.uint8)
-        trunc = out.get("truncated") if out.get("truncated") is not None else self._new((n,), torch.uint8)
-        info = None
-        if want_info:
-            info = out.get("info") if out.get("info") is not None else self._new((n, _lib.INFO_DIM))
+        obs = self._out(out, "obs", self.obs_shape, check=False)
+        rew = self._out(out, "reward", (n,), check=False)
+        done = self._out(out, "done", (n,), torch.uint8, check=False)
+        trunc = self._out(out, "truncated", (n,), torch.uint8, check=False)
+        info = self._out(out, "info", (n, _lib.INFO_DIM), check=False) if want_info else None
         self._chk(self.lib.pnr_step(self._h, _ptr(act), _ptr(obs), _ptr(rew), _ptr(done), _ptr(trunc),
                                     _ptr(info), self._stream()))
         if want_info:
@@ -181,10 +188,10 @@ class PioneerVectorEnv:
         T = int(actions.shape[0])
         act = self._in(actions, (T,) + tuple(self.action_shape), torch.float32, "actions")
         out = out or {}
-        obs = out.get("obs") if out.get("obs") is not None else self._new((T,) + tuple(self.obs_shape))
-        rew = out.get("reward") if out.get("reward") is not None else self._new((T, n))
-        done = out.get("done") if out.get("done") is not None else self._new((T, n), torch.uint8)
-        trunc = out.get("truncated") if out.get("truncated") is not None else self._new((T, n), torch.uint8)
+        obs = self._out(out, "obs", (T,) + tuple(self.obs_shape), check=False)
+        rew = self._out(out, "reward", (T, n), check=False)
+        done = self._out(out, "done", (T, n), torch.uint8, check=False)
+        trunc = self._out(out, "truncated", (T, n), torch.uint8, check=False)
         self._chk(self.lib.pnr_rollout(self._h, T, _ptr(act), _ptr(obs), _ptr(rew), _ptr(done), _ptr(trunc),
                                        self._stream()))
         return obs, rew, done, trunc
@@ -193,11 +200,8 @@ class PioneerVectorEnv:
         """World.step() alone (bullet_scene.py:273-275; pnr_world_step): the simulator's sub-steps and nothing else.  Dynamics mode:
         ``joint_state`` is None (the handle's q, qd move); kinematic mode: the caller's float32 [N, 12] device buffer (q | qd)."""
         self._check_handle()
-        js = None
-        if joint_state is not None:
-            js = self._in(joint_state, (self.num_envs, 12), torch.float32, "joint_state")
-            assert js.data_ptr() == joint_state.data_ptr(), "joint_state is updated in place: it must already be a contiguous float32 device tensor"
-        self._chk(self.lib.pnr_world_step(self._h, _ptr(js) if js is not None else None, self._stream()))
+        js = None if joint_state is None else self._out(joint_state, "joint_state", (self.num_envs, 12))
+        self._chk(self.lib.pnr_world_step(self._h, _ptr(js), self._stream()))
 
     def set_joint_motor(self, joint, control_mode, target_position=float("nan"), target_velocity=float("nan"), position_gain=float("nan"),
                         velocity_gain=float("nan"), max_force=float("nan"), max_velocity=float("nan")):
@@ -218,10 +222,7 @@ class PioneerVectorEnv:
         self._check_handle()
         n = self.num_envs
         js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
-        shape = (n, _lib.NUM_LINKS, _lib.LINK_STATE_DIM)
-        res = self._new(shape) if out is None else self._in(out, shape, torch.float32, "out")
-        if out is not None:
-            assert res.data_ptr() == out.data_ptr(), "out is written in place: it must already be a contiguous float32 device tensor"
+        res = self._out(out, "out", (n, _lib.NUM_LINKS, _lib.LINK_STATE_DIM))
         self._chk(self.lib.pnr_get_link_states(self._h, _ptr(js), _ptr(res), self._stream()))
         return res
 
@@ -263,28 +264,17 @@ class PioneerVectorEnv:
         trgba = self.config.target_rgba if target_rgba is None else target_rgba
         for k in range(4):
             p.target_rgba[k] = float(trgba[k])
-        shapes = {"plane": _lib.SHAPE_PLANE, "box": _lib.SHAPE_BOX, "sphere": _lib.SHAPE_SPHERE}
         for i, (b, rgba) in enumerate(bodies):
-            if b.shape not in shapes:
-                raise AssertionError(f"body {i}: shape must be one of {sorted(shapes)}")
-            p.bodies[i].shape = shapes[b.shape]
-            for k in range(3):
-                p.bodies[i].position[k] = float(b.position[k]); p.bodies[i].size[k] = float(b.size[k])
+            fill_scene_body(p.bodies[i], b, f"body {i}")
             for k in range(4):
-                p.bodies[i].orientation[k] = float(b.orientation[k]); p.body_rgba[i][k] = float(rgba[k])
+                p.body_rgba[i][k] = float(rgba[k])
         js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
         out = out or {}
         res = {}
         for key, want, shape, dtype in (("rgb", rgb, (n, H, W, 3), torch.uint8), ("depth", depth, (n, H, W), torch.float32),
                                         ("seg", segmentation, (n, H, W), torch.uint8)):
-            if not want:
-                continue
-            t = out.get(key)
-            if t is None:
-                res[key] = self._new(shape, dtype)
-            else:
-                res[key] = self._in(t, shape, dtype, key)
-                assert res[key].data_ptr() == t.data_ptr(), f"out[{key!r}] is written in place: it must already be a contiguous {dtype} device tensor"
+            if want:
+                res[key] = self._out(out, key, shape, dtype)
         if not res:
             raise AssertionError("render_frames: ask for at least one of rgb, depth, segmentation")
         self._chk(self.lib.pnr_render(self._h, _ptr(js), p, _ptr(res.get("rgb")), _ptr(res.get("depth")), _ptr(res.get("seg")),
@@ -294,7 +284,7 @@ class PioneerVectorEnv:
     def observe(self, out=None):
         """observe() without stepping (pioneer_knm_env.py:184-211)."""
         self._check_handle()
-        obs = self._new(self.obs_shape) if out is None else self._in(out, self.obs_shape, torch.float32, "out")
+        obs = self._out(out, "out", self.obs_shape)
         self._chk(self.lib.pnr_observe(self._h, _ptr(obs), self._stream()))
         return obs
 
