@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "pnr_model.h"
 
 namespace pnr {
@@ -98,12 +100,24 @@ __device__ __forceinline__ RawState load_state_raw(const float4* __restrict__ st
     return {st[rec], st[n2 + rec], st[2 * n2 + rec]};
 }
 
+// The one statement of that packing: a half record <-> a, v, r of its three joints and its common words C (c: null = not wanted).
+__device__ __forceinline__ void unpack_record(const RawState& k, float* a, float* v, float* r, float* c = nullptr)
+{
+    a[0] = k.p0.x; a[1] = k.p0.y; a[2] = k.p0.z; v[0] = k.p0.w;
+    v[1] = k.p1.x; v[2] = k.p1.y; r[0] = k.p1.z; r[1] = k.p1.w;
+    r[2] = k.p2.x;
+    if (c) { c[0] = k.p2.y; c[1] = k.p2.z; c[2] = k.p2.w; }
+}
+
+__device__ __forceinline__ RawState pack_record(const float* a, const float* v, const float* r, float c0, float c1, float c2)
+{
+    return {make_float4(a[0], a[1], a[2], v[0]), make_float4(v[1], v[2], r[0], r[1]), make_float4(r[2], c0, c1, c2)};
+}
+
 __device__ __forceinline__ void unpack_state(const RawState& raw, int p, LaneState& s)
 {
-    const float4 p0 = raw.p0, p1 = raw.p1, p2 = raw.p2;
-    s.a[0] = p0.x; s.a[1] = p0.y; s.a[2] = p0.z; s.v[0] = p0.w;
-    s.v[1] = p1.x; s.v[2] = p1.y; s.r[0] = p1.z; s.r[1] = p1.w;
-    s.r[2] = p2.x;
+    const float4 p2 = raw.p2;
+    unpack_record(raw, s.a, s.v, s.r);
     const float o1 = xchg(p2.y), o2 = xchg(p2.z), o3 = xchg(p2.w);
     s.tgt[0] = p ? o1 : p2.y; s.tgt[1] = p ? o2 : p2.z; s.tgt[2] = p ? o3 : p2.w;
     s.pot = p ? p2.y : o1;
@@ -119,10 +133,9 @@ __device__ __forceinline__ void load_state(const float4* __restrict__ st, long l
 __device__ __forceinline__ void store_state(float4* __restrict__ st, long long n, long long rec, int p, const LaneState& s)
 {
     const long long n2 = 2 * n;
-    st[rec] = make_float4(s.a[0], s.a[1], s.a[2], s.v[0]);
-    st[n2 + rec] = make_float4(s.v[1], s.v[2], s.r[0], s.r[1]);
-    st[2 * n2 + rec] = make_float4(s.r[2], p ? s.pot : s.tgt[0], p ? __uint_as_float(s.step) : s.tgt[1],
+    const RawState w = pack_record(s.a, s.v, s.r, p ? s.pot : s.tgt[0], p ? __uint_as_float(s.step) : s.tgt[1],
                                    p ? __uint_as_float(s.episode) : s.tgt[2]);
+    st[rec] = w.p0; st[n2 + rec] = w.p1; st[2 * n2 + rec] = w.p2;
 }
 
 __device__ __forceinline__ void zero_state(LaneState& s)
@@ -566,6 +579,35 @@ __device__ __forceinline__ void flush_feature_tile(const float* __restrict__ lds
         for (int f = half; f < kObsDim; f += 2)
             if (col < nvalid) stream_store(dst + (long long)f * n + col, lds[f * kEnvsPerWave + col]);
     }
+}
+
+// ---- the one obs path of the tile kernels: this lane's entries into its wave's LDS tile, then the tile out as whole lines ----
+template <bool OBS_EM>
+__device__ __forceinline__ std::conditional_t<OBS_EM, SinkLdsTile, SinkLdsFeatureTile> tile_sink(float* tile, int el, int p)
+{
+    return {tile + el * (OBS_EM ? kObsDim : 1), kJpl * p, p};
+}
+
+// the 36 constant entries of this lane's tile slots
+template <bool OBS_EM>
+__device__ __forceinline__ void obs_tile_const(const LaneConsts& K, float* tile, int el, int p)
+{
+    auto sink = tile_sink<OBS_EM>(tile, el, p);
+    emit_obs_const(K, sink);
+}
+
+// emit, sync, flush.  obs: the batch this tile's 32 envs (first env tile0, nvalid of them live) go to, [n][137] or [137][n].
+// emit / flush = false: the timing-only ablations of a -DPNR_DIAG_BUILD=1 variant (literal true in the product library).
+template <bool OBS_EM, bool WITH_CONST = false>
+__device__ __forceinline__ void obs_tile_out(const LaneConsts& K, const LaneState& s, const Pose& q, float* tile, int el, int p, int lane,
+                                             float* obs, long long tile0, long long n, int nvalid, bool emit = true, bool flush = true)
+{
+    auto sink = tile_sink<OBS_EM>(tile, el, p);
+    if (emit) emit_obs<WITH_CONST>(K, s, q, p, sink);
+    wave_lds_sync();
+    if (!flush) return;
+    if (OBS_EM) flush_tile(tile, obs + tile0 * kObsDim, nvalid, lane);
+    else flush_feature_tile(tile, obs + tile0, n, nvalid, lane);
 }
 
 }  // namespace pnr

@@ -31,6 +31,13 @@
 
 namespace pnr {
 
+// first plane of each group of the dyn words above (pnr_get_dyn_state's layout, include/pioneer_amd.h: "q[6] qd[6] link-mass
+// scale[11], friction[6], damping[6], 1 pad"); plane w of env e lies at dyn[w * n + e]
+constexpr int kDynQ = 0, kDynQd = kDynQ + kDof, kDynScale = kDynQd + kDof, kDynFric = kDynScale + kNumLinks,
+              kDynDamp = kDynFric + kDof;
+static_assert(kDynQd == 6 && kDynScale == 12 && kDynFric == 23 && kDynDamp == 29 && kDynDamp + kDof + 1 == PNR_DYN_STATE_WORDS,
+              "the dyn planes are the ABI's 36 words: 35 used + 1 pad");
+
 // a static scene body as the kernels want it: world position, rotation matrix (row-major; a plane keeps its unit world
 // normal in rot[0..2]), size (box half extents | sphere radius in size[0])
 constexpr int kMaxScene = 8;
@@ -809,15 +816,6 @@ __device__ __forceinline__ void motor_constraints(const DynParams& D, const DynM
     for (int i = 0; i < kDof; ++i) qdd[i] += dv[i] * inv_h;
 }
 
-// ---------------------------------------------------------------------------------
-// Phase A of a dynamics step for ONE env in this lane: kinematic command integration (the
-// parity-mode integrator) + nsub sub-steps of ABA + PD.  In: the env's two state records as they
-// lie in HBM (k0/k1/k2[p], see load_state_raw).  Out: the records with a, v, r updated, and the
-// simulated q, qd.  Nothing is stored here: pnr::dyn_step_kernel hands the results to its pair
-// lanes through LDS.
-// ---------------------------------------------------------------------------------
-// RAND = per-env link scales (domain randomisation): loaded from the dyn words; otherwise every scale
-// is 1 and the model folds into literals.
 // `in` carries the pointers and integrator constants the kernel received as preloaded leading arguments
 // (so that the first loads and the integrator do not wait for the kernarg structs).
 struct DynLead {
@@ -861,12 +859,10 @@ __device__ __forceinline__ void dyn_lane_load(const DynLead& in, long long base,
 {
     const long long n = in.n;
     const long long n2 = 2 * n;
-    float4 k0[2], k1[2], k2[2];
+    RawState k[2];
     const float4* s0 = in.state + 2 * base;                       // record 2 * env + p of plane 0 for this workgroup
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        k0[p] = s0[2 * lane + p]; k1[p] = (s0 + n2)[2 * lane + p]; k2[p] = (s0 + 2 * n2)[2 * lane + p];
-    }
+    for (int p = 0; p < 2; ++p) k[p] = {s0[2 * lane + p], (s0 + n2)[2 * lane + p], (s0 + 2 * n2)[2 * lane + p]};
     // the 35 planar dyn words through ONE walking pointer (plane p at dyn + p * n): two address registers in all
     const float* w = in.dyn + base + lane;
 #pragma unroll
@@ -881,30 +877,11 @@ __device__ __forceinline__ void dyn_lane_load(const DynLead& in, long long base,
     for (int i = 0; i < kDof; ++i) { L.damp[i] = *w; w += n; }
     dyn_load_action<ACT_EM>(in.actions, n, base, lane, L.act);   // the first step's action, with everything else
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        L.a[3 * p] = k0[p].x; L.a[3 * p + 1] = k0[p].y; L.a[3 * p + 2] = k0[p].z; L.v[3 * p] = k0[p].w;
-        L.v[3 * p + 1] = k1[p].x; L.v[3 * p + 2] = k1[p].y; L.r[3 * p] = k1[p].z; L.r[3 * p + 1] = k1[p].w;
-        L.r[3 * p + 2] = k2[p].x;
-        L.cw[p][0] = k2[p].y; L.cw[p][1] = k2[p].z; L.cw[p][2] = k2[p].w;
-    }
+    for (int p = 0; p < 2; ++p) unpack_record(k[p], L.a + 3 * p, L.v + 3 * p, L.r + 3 * p, L.cw[p]);
 }
 
-// ---------------------------------------------------------------------------------
-// Phase A of a dynamics step for ONE env in this lane: kinematic command integration (the
-// parity-mode integrator) with the action of this step, then nsub sub-steps of ABA + PD.
-// Nothing is stored here: pnr::dyn_step_kernel hands the results to its pair lanes through LDS.
-// ---------------------------------------------------------------------------------
 // The arithmetic of phase A, shared by the single-step and the rollout kernels (one text, so that both produce
 // the same bits): command integration with the action latched for the next step, then nsub sub-steps of ABA + PD.
-// PNR_DYN_LDS_MODEL=1 (a build-time A/B, north_star's "per-link spatial inertias staged in LDS"): the env's rigid-body model
-// (6 masses, first moment and 6 inertia entries of body 6) and its 12 friction / damping coefficients are written to a
-// per-lane LDS slice [kDynStageWords][64] once per step and re-read at the top of every sub-step instead of living in
-// ~33 registers across the loop.  Default 0: everything in registers (the measured winner).
-#ifndef PNR_DYN_LDS_MODEL
-#define PNR_DYN_LDS_MODEL 0
-#endif
-constexpr int kDynStageWords = 33;
-
 // WORLD (pnr_world_step): the sub-steps alone — no command integration, no teleport — with the per-joint motor table W.
 // CMOTOR (WORLD only): W holds constraint motors as well; their joints get no torque of the table's law, and motor_constraints
 // adds their boxed solve to each sub-step's accelerations.
@@ -912,7 +889,7 @@ template <int PHYS, bool WORLD = false, bool CMOTOR = false>
 __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, float (&a)[kDof], float (&v)[kDof],
                                          float (&r)[kDof], float (&q)[kDof], float (&qd)[kDof], const float (&sc)[kNumLinks],
                                          const float (&fric_)[kDof], const float (&damp_)[kDof], const float (&act)[kDof],
-                                         float* stage = nullptr, const JointMotorTable* W = nullptr)
+                                         const JointMotorTable* W = nullptr)
 {
     if constexpr (!WORLD) {
 #pragma unroll
@@ -925,19 +902,10 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
 
     DynModel M;
     build_model(sc, M);
+    // the copies stay: with the loop reading the caller's arrays, the register allocation of dyn_rollout_kernel<0,1,1,0> moved (270 -> 268 VGPRs)
     float fric[kDof], damp[kDof];
 #pragma unroll
     for (int i = 0; i < kDof; ++i) { fric[i] = fric_[i]; damp[i] = damp_[i]; }
-#if PNR_DYN_LDS_MODEL
-    {
-        float* w = stage + (threadIdx.x & 63);
-#pragma unroll
-        for (int i = 0; i < kDof; ++i) { w[i * 64] = M.m[i]; w[(6 + i) * 64] = fric[i]; w[(12 + i) * 64] = damp[i]; }
-        w[18 * 64] = M.h6.x; w[19 * 64] = M.h6.y; w[20 * 64] = M.h6.z;
-        w[21 * 64] = M.I6.r0.x; w[22 * 64] = M.I6.r0.y; w[23 * 64] = M.I6.r0.z;
-        w[24 * 64] = M.I6.r1.y; w[25 * 64] = M.I6.r1.z; w[26 * 64] = M.I6.r2.z;
-    }
-#endif
 
     if (!WORLD && D.teleport) {   // resetJointState semantics: pioneer_knm_env.py:148, bullet_scene.py:157-165
 #pragma unroll
@@ -959,38 +927,23 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
     for (int i = 0; i < kDof; ++i) { float sn, cn; sincos_bounded(q[i], sn, cn); cs[i] = (f2){cn, sn}; }
     [[maybe_unused]] const float inv_h = CMOTOR ? 1.0f / D.dt_sub : 0.f;
     for (int k = 0; k < D.nsub; ++k) {
-        float tau[kDof], qdd[kDof], ades[kDof];
-#if PNR_DYN_LDS_MODEL
-        {   // re-read the staged model: the offset is opaque per iteration, so nothing is hoisted out of the loop
-            int off = threadIdx.x & 63;
-            asm volatile("" : "+v"(off));
-            const float* w = stage + off;
-#pragma unroll
-            for (int i = 0; i < kDof; ++i) { M.m[i] = w[i * 64]; fric[i] = w[(6 + i) * 64]; damp[i] = w[(12 + i) * 64]; }
-            M.h6 = {w[18 * 64], w[19 * 64], w[20 * 64]};
-            const float i01 = w[22 * 64], i02 = w[23 * 64], i12 = w[25 * 64];
-            M.I6 = {{w[21 * 64], i01, i02}, {i01, w[24 * 64], i12}, {i02, i12, w[26 * 64]}};
-        }
-#endif
+        float tau[kDof], qdd[kDof], ades[kDof], tc[kDof];
 #pragma unroll
         for (int i = 0; i < kDof; ++i) {
-            float tq;
-            if constexpr (WORLD) {      // the joint's own motor (wave-uniform table entries)
-                const float rr = W->from_cmd[i] ? r[i] : W->r_ref[i], vr = W->from_cmd[i] ? v[i] : W->v_ref[i];
-                const float dq = rr - q[i];
-                const float v_ask = fminf(fmaxf(vr + W->cpos[i] * dq, -W->vcap[i]), W->vcap[i]);
-                tq = W->kp[i] * dq + W->kd[i] * (v_ask - qd[i]);
-                if constexpr ((PHYS & 2) != 0) { ades[i] = tq; tq = 0.f; }
-                else { ades[i] = 0.f; tq = fminf(fmaxf(tq, -W->tcap[i]), W->tcap[i]); }
-                if constexpr (CMOTOR) {
-                    if (W->kind[i] != kMotorPD) { ades[i] = 0.f; tq = 0.f; }
-                }
-            } else {
-            const float dq = r[i] - q[i];
-            const float v_ask = fminf(fmaxf(v[i] + cpos * dq, -vcap), vcap);
-            tq = kp * dq + kd * (v_ask - qd[i]);
+            // one motor law; WORLD: the joint's own motor (wave-uniform table entries), which may track a reference of its own
+            // instead of the env's command state
+            const bool cmd = !WORLD || W->from_cmd[i];
+            const float rr = cmd ? r[i] : W->r_ref[i], vr = cmd ? v[i] : W->v_ref[i];
+            const float kpi = WORLD ? W->kp[i] : kp, kdi = WORLD ? W->kd[i] : kd;
+            const float cpi = WORLD ? W->cpos[i] : cpos, vci = WORLD ? W->vcap[i] : vcap;
+            tc[i] = WORLD ? W->tcap[i] : tcap;
+            const float dq = rr - q[i];
+            const float v_ask = fminf(fmaxf(vr + cpi * dq, -vci), vci);
+            float tq = kpi * dq + kdi * (v_ask - qd[i]);
             if constexpr ((PHYS & 2) != 0) { ades[i] = tq; tq = 0.f; }        // an acceleration request: scaled and capped inside the ABA
-            else { ades[i] = 0.f; tq = fminf(fmaxf(tq, -tcap), tcap); }
+            else { ades[i] = 0.f; tq = fminf(fmaxf(tq, -tc[i]), tc[i]); }
+            if constexpr (CMOTOR) {
+                if (W->kind[i] != kMotorPD) { ades[i] = 0.f; tq = 0.f; }
             }
             tq -= damp[i] * qd[i];
             tq -= fric[i] * qd[i] * __builtin_amdgcn_rsqf(qd[i] * qd[i] + kFrictionEps * kFrictionEps);
@@ -1000,9 +953,6 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
             float c[kDof], s[kDof];
 #pragma unroll
             for (int i = 0; i < kDof; ++i) { c[i] = cs[i].x; s[i] = cs[i].y; }
-            float tc[kDof];
-#pragma unroll
-            for (int i = 0; i < kDof; ++i) tc[i] = WORLD ? W->tcap[i] : tcap;
             aba<PHYS>(D, M, c, s, qd, tau, ades, tc, qdd);
             if constexpr (CMOTOR) motor_constraints(D, M, c, s, q, qd, *W, inv_h, qdd);
         }
@@ -1033,14 +983,14 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
 
 template <bool ACT_EM, bool RAND, int PHYS>
 __device__ __forceinline__ void dyn_lane_advance(const DynLead& in, const DynParams& D, long long base, int lane,
-                                                 const float* __restrict__ next_actions, DynLane& L, float* stage = nullptr)
+                                                 const float* __restrict__ next_actions, DynLane& L)
 {
     float act[kDof];
 #pragma unroll
     for (int i = 0; i < kDof; ++i) act[i] = L.act[i];
     // the action after this one is requested now: it arrives under the sub-steps (next_actions: null on the last step)
     if (next_actions) dyn_load_action<ACT_EM>(next_actions, in.n, base, lane, L.act);
-    dyn_core<PHYS>(in, D, L.a, L.v, L.r, L.q, L.qd, L.sc, L.fric, L.damp, act, stage);
+    dyn_core<PHYS>(in, D, L.a, L.v, L.r, L.q, L.qd, L.sc, L.fric, L.damp, act);
 }
 
 // The per-env parameter draws of a reset: Philox blocks 3..8 of the env's counter (the joints and the target
@@ -1070,39 +1020,32 @@ __device__ __forceinline__ void dyn_draw_params(const KParams& P, const DynParam
 }
 
 // ---------------------------------------------------------------------------------
-// Single-step form of phase A (pnr_step): load, dyn_core, re-pack, in one piece.  Kept next to the rollout
+// Single-step form of phase A (pnr_step): load, dyn_core, in one piece.  Kept next to the rollout
 // kernel's dyn_lane_load + dyn_lane_advance: that split form has the same instruction counts but ran 2 % slower as
 // the single-step kernel (A/B inside one library: 32.15 vs 32.85 us per 65 536-env step; SQ_WAIT_INST_ANY +40 %).
 // In: nothing but the env index.  Out: the env's two state records as they lie in HBM (a, v, r updated), q, qd.
 // ---------------------------------------------------------------------------------
 template <bool ACT_EM, bool RAND, int PHYS>
-__device__ __forceinline__ void dyn_substeps_lane(const DynLead& in, const DynParams& D, long long e,
-                                                  float4 (&k0)[2], float4 (&k1)[2], float4 (&k2)[2],
-                                                  float (&q)[kDof], float (&qd)[kDof], float* stage = nullptr)
+__device__ __forceinline__ void dyn_substeps_lane(const DynLead& in, const DynParams& D, long long e, RawState (&k)[2],
+                                                  float (&q)[kDof], float (&qd)[kDof])
 {
     const long long n = in.n;
     const long long n2 = 2 * n;
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        k0[p] = in.state[2 * e + p]; k1[p] = in.state[n2 + 2 * e + p]; k2[p] = in.state[2 * n2 + 2 * e + p];
-    }
+    for (int p = 0; p < 2; ++p) k[p] = {in.state[2 * e + p], in.state[n2 + 2 * e + p], in.state[2 * n2 + 2 * e + p]};
     // dynamics state: every load is issued here, before the first wait — with one wave per SIMD
     // (65 536 envs) nothing else hides a memory round trip
     float sc[kNumLinks], fric[kDof], damp[kDof];
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
-        q[i] = in.dyn[(long long)i * n + e]; qd[i] = in.dyn[(long long)(6 + i) * n + e];
-        fric[i] = in.dyn[(long long)(23 + i) * n + e]; damp[i] = in.dyn[(long long)(29 + i) * n + e];
+        q[i] = in.dyn[(long long)(kDynQ + i) * n + e]; qd[i] = in.dyn[(long long)(kDynQd + i) * n + e];
+        fric[i] = in.dyn[(long long)(kDynFric + i) * n + e]; damp[i] = in.dyn[(long long)(kDynDamp + i) * n + e];
     }
 #pragma unroll
-    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? in.dyn[(long long)(12 + l) * n + e] : 1.0f;
+    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? in.dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
     float a[kDof], v[kDof], r[kDof];
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        a[3 * p] = k0[p].x; a[3 * p + 1] = k0[p].y; a[3 * p + 2] = k0[p].z; v[3 * p] = k0[p].w;
-        v[3 * p + 1] = k1[p].x; v[3 * p + 2] = k1[p].y; r[3 * p] = k1[p].z; r[3 * p + 1] = k1[p].w;
-        r[3 * p + 2] = k2[p].x;
-    }
+    for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
     float act[kDof];
     if (ACT_EM) {
         const float2* a2 = reinterpret_cast<const float2*>(in.actions + e * kDof);
@@ -1112,13 +1055,9 @@ __device__ __forceinline__ void dyn_substeps_lane(const DynLead& in, const DynPa
 #pragma unroll
         for (int i = 0; i < kDof; ++i) act[i] = in.actions[(long long)i * n + e];
     }
-    dyn_core<PHYS>(in, D, a, v, r, q, qd, sc, fric, damp, act, stage);
+    dyn_core<PHYS>(in, D, a, v, r, q, qd, sc, fric, damp, act);
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        k0[p] = make_float4(a[3 * p], a[3 * p + 1], a[3 * p + 2], v[3 * p]);
-        k1[p] = make_float4(v[3 * p + 1], v[3 * p + 2], r[3 * p], r[3 * p + 1]);
-        k2[p].x = r[3 * p + 2];
-    }
+    for (int p = 0; p < 2; ++p) k[p] = pack_record(a + 3 * p, v + 3 * p, r + 3 * p, k[p].p2.y, k[p].p2.z, k[p].p2.w);
 }
 
 // reset of the dynamics words for this lane's joints (called by the pair kernels after reset_env):
@@ -1130,14 +1069,14 @@ __device__ __forceinline__ void dyn_reset_lane(const KParams& P, const DynParams
 #pragma unroll
     for (int i = 0; i < kJpl; ++i) {
         D.dyn[(long long)(kJpl * p + i) * n + e] = s.r[i];
-        D.dyn[(long long)(6 + kJpl * p + i) * n + e] = 0.f;
+        D.dyn[(long long)(kDynQd + kJpl * p + i) * n + e] = 0.f;
     }
     float sc[kNumLinks], fric[kDof], damp[kDof];
     dyn_draw_params(P, D, genv, episode_drawn, sc, fric, damp);
     // lane 0 writes the link scales, each lane its own joints' friction / damping
     if (p == 0) {
 #pragma unroll
-        for (int l = 0; l < kNumLinks; ++l) D.dyn[(long long)(12 + l) * n + e] = sc[l];
+        for (int l = 0; l < kNumLinks; ++l) D.dyn[(long long)(kDynScale + l) * n + e] = sc[l];
     }
 #pragma unroll
     for (int i = 0; i < kJpl; ++i) {
@@ -1146,8 +1085,8 @@ __device__ __forceinline__ void dyn_reset_lane(const KParams& P, const DynParams
         // select into the address and the whole array is demoted to scratch (cf. lane_consts)
         float f0 = fric[i], f1 = fric[kJpl + i], d0 = damp[i], d1 = damp[kJpl + i];
         asm volatile("" : "+v"(f0), "+v"(f1), "+v"(d0), "+v"(d1));
-        D.dyn[(long long)(23 + j) * n + e] = p ? f1 : f0;
-        D.dyn[(long long)(29 + j) * n + e] = p ? d1 : d0;
+        D.dyn[(long long)(kDynFric + j) * n + e] = p ? f1 : f0;
+        D.dyn[(long long)(kDynDamp + j) * n + e] = p ? d1 : d0;
     }
 }
 

@@ -18,6 +18,40 @@
 namespace pnr {
 
 // ---------------------------------------------------------------------------------
+// The outcome of one env step, for the kinematic and the dynamics kernels alike: the reward block of
+// pioneer_knm_env.py:157-165 and gym.wrappers.TimeLimit.  Both lanes of a pair compute the same.
+// ---------------------------------------------------------------------------------
+struct Outcome { float pot, r_pot, r_step, r_done, rw; bool done, trunc; };
+
+// `o`: what the reward sees — this lane's joints, the env's target, its potential before the step and its step count after it
+template <bool DYN>
+__device__ __forceinline__ Outcome step_outcome(const KParams& P, const LaneState& o, int p, float dist)
+{
+    Outcome c;
+    c.pot = P.pot_m / (dist / P.pot_s + 1.0f);                    // :232-236
+    c.done = done_predicate(o, p, dist, P.done_dist, P.done_dist_d);   // :160
+    c.r_pot = c.pot - o.pot;
+    c.r_step = -P.penalty;
+    c.r_done = c.done ? P.award_done : 0.0f;
+    c.rw = (c.r_pot + c.r_step) + c.r_done;                       // :165
+    // gym.wrappers.TimeLimit: truncated = elapsed >= max and not done
+    c.trunc = (P.max_steps > 0) && (o.step >= (uint32_t)P.max_steps) && !c.done;
+    // a lane whose simulation diverged (non-finite pose) is cut like a time-out, so auto-reset recovers
+    // it instead of carrying NaNs forever (kinematic mode keeps the reference's NaN-propagating behaviour)
+    if (DYN && !(dist == dist && __builtin_fabsf(dist) <= 3.0e38f)) c.trunc = !c.done;
+    return c;
+}
+
+// the env's four results at output index o = t * n + e (one lane of the pair)
+__device__ __forceinline__ void store_outcome(const KParams& P, const Outcome& c, float dist, long long o)
+{
+    stream_store(P.reward + o, c.rw);
+    stream_store(P.done + o, (uint8_t)c.done);
+    if (P.trunc) stream_store(P.trunc + o, (uint8_t)c.trunc);
+    if (P.info) stream_store(reinterpret_cast<float4*>(P.info) + o, make_float4(c.r_pot, c.r_step, c.r_done, dist));
+}
+
+// ---------------------------------------------------------------------------------
 // step / rollout kernel: BulletEnv.step (bullet_env.py:192-197) for T steps.
 // One wave = 32 envs (lane pair per env), one wave per workgroup.
 // ---------------------------------------------------------------------------------
@@ -82,8 +116,7 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
     bool first_tile = true;
 
     // the 36 constant obs entries of this lane's tile slots: once per kernel, under the load latency
-    if (OBS_EM) { SinkLdsTile sink{tile + el * kObsDim, kJpl * p, p}; emit_obs_const(K, sink); }
-    else { SinkLdsFeatureTile sink{tile + el, kJpl * p, p}; emit_obs_const(K, sink); }
+    obs_tile_const<OBS_EM>(K, tile, el, p);
 
     for (; tix < ntiles; tix += tstride) {
     const long long tile0 = tix * kEnvsPerWave;
@@ -139,29 +172,13 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
         Pose q;
         compute_pose(s, p, q);
 
-        // -- reward block, pioneer_knm_env.py:157-165 (both lanes, identical) ----------
-        const float old_pot = s.pot;
-        const float pot = P.pot_m / (q.dist / P.pot_s + 1.0f);        // :232-236
-        const bool done = done_predicate(s, p, q.dist, P.done_dist, P.done_dist_d);   // :160
-        const float r_pot = pot - old_pot;
-        const float r_step = -P.penalty;
-        const float r_done = done ? P.award_done : 0.0f;
-        const float rw = (r_pot + r_step) + r_done;                   // :165
-        s.pot = pot;
-        // gym.wrappers.TimeLimit: truncated = elapsed >= max and not done
-        const bool trunc = (P.max_steps > 0) && (s.step >= (uint32_t)P.max_steps) && !done;
-
-        if (valid && p == 0) {
-            const long long o = (long long)t * n + e;
-            stream_store(P.reward + o, rw);
-            stream_store(P.done + o, (uint8_t)done);
-            if (P.trunc) stream_store(P.trunc + o, (uint8_t)trunc);
-            if (P.info) stream_store(reinterpret_cast<float4*>(P.info) + o, make_float4(r_pot, r_step, r_done, q.dist));
-        }
+        const Outcome oc = step_outcome<false>(P, s, p, q.dist);
+        s.pot = oc.pot;
+        if (valid && p == 0) store_outcome(P, oc, q.dist, (long long)t * n + e);
 
         // -- in-kernel auto-reset (BulletEnv.reset as the sampler would call it) -----
         // `done`/`trunc` are identical in both lanes of a pair, so pairs stay together
-        if (P.auto_reset && (done || trunc)) {
+        if (P.auto_reset && (oc.done || oc.trunc)) {
             reset_env(P, K, s, p, P.env_off + (unsigned long long)e, nullptr, nullptr);
             compute_pose(s, p, q);
         }
@@ -170,19 +187,8 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
         if (t == P.T - 1 && valid && !diag_nostate) store_state(state_, n, rec, p, s);
 
         // -- observe() ----------------------------------------------------------------
-        float* obs_t = P.obs + (long long)t * n * kObsDim;
         if (t > 0 || !first_tile) wave_lds_sync();   // previous flush done before the tile is rewritten
-        if (OBS_EM) {
-            SinkLdsTile sink{tile + el * kObsDim, kJpl * p, p};
-            if (!diag_noemit) emit_obs<false>(K, s, q, p, sink);
-            wave_lds_sync();
-            if (!diag_noflush) flush_tile(tile, obs_t + tile0 * kObsDim, nvalid, lane);
-        } else {
-            SinkLdsFeatureTile sink{tile + el, kJpl * p, p};
-            emit_obs<false>(K, s, q, p, sink);
-            wave_lds_sync();
-            flush_feature_tile(tile, obs_t + tile0, n, nvalid, lane);
-        }
+        obs_tile_out<OBS_EM>(K, s, q, tile, el, p, lane, P.obs + (long long)t * n * kObsDim, tile0, n, nvalid, !diag_noemit, !diag_noflush);
     }
     first_tile = false;
     }   // tile loop
@@ -206,204 +212,27 @@ constexpr int kHandRecFloats = 3 * 2 * kDynEnvsPerWg * 4;  // three float4 plane
 constexpr int kHandFloats = kHandRecFloats + 2 * kDof * kDynEnvsPerWg;
 static_assert(kHandFloats <= kTileFloats, "the hand-off area must fit into the obs tile it aliases");
 
-template <bool OBS_EM>
-__device__ __forceinline__ void dyn_finish_tile(const KParams& P, const DynParams& D, const LaneConsts& K, const RawState& raw,
-                                                const float (&dq)[kJpl], const float (&dqd)[kJpl], float* tile,
-                                                long long tile0, int lane, bool tile_in_use)
-{
-    const int p = lane & 1, el = lane >> 1;
-    const long long n = P.n;
-    const long long e = tile0 + el;
-    const bool valid = e < n;               // the pair shares `valid`, so DPP partners are live
-    const int nvalid = (int)((n - tile0) < kEnvsPerWave ? (n - tile0) : kEnvsPerWave);
-
-    LaneState s;
-    unpack_state(raw, p, s);                // all-zero records for lanes past the end
-    LaneState o = s;                        // what reward / obs see: the simulated q, qd
-#pragma unroll
-    for (int i = 0; i < kJpl; ++i) {
-        o.r[i] = dq[i];
-        // teleport = reference semantics: obs shows the env's own v (pioneer_knm_env.py:202)
-        o.v[i] = D.teleport ? s.v[i] : dqd[i];
-    }
-    s.step += 1;                                                  // bullet_env.py:193
-    o.step = s.step;
-
-    Pose q;
-    compute_pose(o, p, q);
-
-    // -- reward block, pioneer_knm_env.py:157-165 (both lanes, identical) ----------
-    const float old_pot = s.pot;
-    const float pot = P.pot_m / (q.dist / P.pot_s + 1.0f);        // :232-236
-    const bool done = done_predicate(o, p, q.dist, P.done_dist, P.done_dist_d);   // :160
-    const float r_pot = pot - old_pot;
-    const float r_step = -P.penalty;
-    const float r_done = done ? P.award_done : 0.0f;
-    const float rw = (r_pot + r_step) + r_done;                   // :165
-    s.pot = pot;
-    // gym.wrappers.TimeLimit: truncated = elapsed >= max and not done
-    bool trunc = (P.max_steps > 0) && (s.step >= (uint32_t)P.max_steps) && !done;
-    // a lane whose simulation diverged (non-finite pose) is cut like a time-out, so auto-reset recovers
-    // it instead of carrying NaNs forever (kinematic mode keeps the reference's NaN-propagating behaviour)
-    if (!(q.dist == q.dist && __builtin_fabsf(q.dist) <= 3.0e38f)) trunc = !done;
-
-    if (valid && p == 0) {
-        stream_store(P.reward + e, rw);
-        stream_store(P.done + e, (uint8_t)done);
-        if (P.trunc) stream_store(P.trunc + e, (uint8_t)trunc);
-        if (P.info) stream_store(reinterpret_cast<float4*>(P.info) + e, make_float4(r_pot, r_step, r_done, q.dist));
-    }
-
-    // -- in-kernel auto-reset (BulletEnv.reset as the sampler would call it) -----
-    // `done`/`trunc` are identical in both lanes of a pair, so pairs stay together
-    o.pot = pot;
-    const bool redraw = P.auto_reset && (done || trunc);
-    if (redraw) {
-        reset_env(P, K, s, p, P.env_off + (unsigned long long)e, nullptr, nullptr);
-        if (valid) dyn_reset_lane(P, D, s, p, e, P.env_off + (unsigned long long)e, s.episode - 1);   // q = r, qd = 0, new draws
-        o = s;
-        compute_pose(o, p, q);
-    }
-    if (valid) {
-        store_state(P.state, n, 2 * tile0 + lane, p, s);
-        if (!redraw) {
-#pragma unroll
-            for (int i = 0; i < kJpl; ++i) {
-                D.dyn[(long long)(kJpl * p + i) * n + e] = dq[i];
-                D.dyn[(long long)(6 + kJpl * p + i) * n + e] = dqd[i];
-            }
-        }
-    }
-
-    // -- observe() ----------------------------------------------------------------
-    // (timing-only ablations of a -DPNR_DIAG_BUILD=1 variant, PNR_DIAG bits as in step_kernel: 2 no obs flush, 4 no obs emit; in the
-    // product library `diag` is the literal 0)
-    const int diag = PNR_DIAG_BUILD ? P.diag : 0;
-    if (tile_in_use) wave_lds_sync();       // previous flush done before the tile is rewritten
-    if (OBS_EM) {
-        SinkLdsTile sink{tile + el * kObsDim, kJpl * p, p};
-        if (!(diag & 4)) emit_obs<false>(K, o, q, p, sink);
-        wave_lds_sync();
-        if (!(diag & 2)) flush_tile(tile, P.obs + tile0 * kObsDim, nvalid, lane);
-    } else {
-        SinkLdsFeatureTile sink{tile + el, kJpl * p, p};
-        emit_obs<false>(K, o, q, p, sink);
-        wave_lds_sync();
-        flush_feature_tile(tile, P.obs + tile0, n, nvalid, lane);
-    }
-}
-
-// Leading scalar arguments as in step_kernel: preloaded into SGPRs, they repeat P.state / D.dyn / P.actions /
-// P.n / P.dt / P.eps and carry max_v_to_r.
-// PNR_DYN_STEP_WAVES = 2 (default): the workgroup is TWO waves.  Wave 0 runs phase A for the 64 envs (wave 1 waits at the barrier
-// and takes no issue slot); in phase B each wave finishes ONE of the two 32-env tiles in an obs tile of its own, side by side on
-// two SIMDs, instead of wave 0 finishing them one after the other (phase B is ~40 % of the step's fixed cost).  1 = the r02 form (A/B).
-#ifndef PNR_DYN_STEP_WAVES
-#define PNR_DYN_STEP_WAVES 2
-#endif
-constexpr int kDynStepWaves = PNR_DYN_STEP_WAVES;
-static_assert(kDynStepWaves == 1 || kDynStepWaves == 2, "one or two waves per dynamics-step workgroup");
-
-template <bool OBS_EM, bool ACT_EM, bool RAND, int PHYS>
-__global__ __launch_bounds__(kWave * kDynStepWaves) void dyn_step_kernel(const float4* __restrict__ state_, const float* __restrict__ dyn_,
-                                                         const float* __restrict__ actions_, const long long n_,
-                                                         const double dt_, const double eps_, const float max_v_to_r_,
-                                                         const KParams P, const DynParams D)
-{
-    __shared__ __attribute__((aligned(16))) float lds[kDynStepWaves * kTileFloats];
-    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
-    const long long n = n_;
-    const long long base = (long long)blockIdx.x * kDynEnvsPerWg;
-    float* tile = lds + wv * kTileFloats;                         // this wave's obs tile
-    float4* hrec = reinterpret_cast<float4*>(lds);                // hand-off (head of tile 0): [3][2 * 64] records, index 2 * env + p
-    float* hq = lds + kHandRecFloats;                             // [12][64]: q then qd
-    const auto handoff_sync = [] { if (kDynStepWaves == 1) wave_lds_sync(); else __syncthreads(); };
-
-    // ---- phase A: one env per lane (wave 0)
-    if (wv == 0) {
-        const long long e = base + lane;
-        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 k0[2] = {z4, z4}, k1[2] = {z4, z4}, k2[2] = {z4, z4};
-        float q[kDof] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, qd[kDof] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const DynLead lead = {state_, dyn_, actions_, n_, dt_, eps_, max_v_to_r_};
-        if (e < n) dyn_substeps_lane<ACT_EM, RAND, PHYS>(lead, D, e, k0, k1, k2, q, qd, lds);   // the LDS is free during phase A
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            hrec[2 * lane + p] = k0[p];
-            hrec[2 * kDynEnvsPerWg + 2 * lane + p] = k1[p];
-            hrec[4 * kDynEnvsPerWg + 2 * lane + p] = k2[p];
-        }
-#pragma unroll
-        for (int i = 0; i < kDof; ++i) {
-            hq[i * kDynEnvsPerWg + lane] = q[i];
-            hq[(kDof + i) * kDynEnvsPerWg + lane] = qd[i];
-        }
-    }
-    handoff_sync();
-
-    // ---- phase B: lane pairs; every tile's hand-off records leave LDS before tile 0 (which they alias) is reused
-    const int p = lane & 1, el = lane >> 1;
-    RawState raw0, raw1;
-    float dq0[kJpl], dqd0[kJpl], dq1[kJpl], dqd1[kJpl];
-    {
-        // one wave: tiles 0 and 1; two waves: wave wv takes tile wv (raw0 / dq0 / dqd0)
-        const int t0 = kDynStepWaves == 1 ? 0 : wv;
-        const int r0 = 2 * kEnvsPerWave * t0 + lane, r1 = 2 * kEnvsPerWave + lane;        // record 2 * env + p
-        raw0 = {hrec[r0], hrec[2 * kDynEnvsPerWg + r0], hrec[4 * kDynEnvsPerWg + r0]};
-        raw1 = {hrec[r1], hrec[2 * kDynEnvsPerWg + r1], hrec[4 * kDynEnvsPerWg + r1]};
-#pragma unroll
-        for (int i = 0; i < kJpl; ++i) {
-            dq0[i] = hq[(kJpl * p + i) * kDynEnvsPerWg + kEnvsPerWave * t0 + el];
-            dqd0[i] = hq[(kDof + kJpl * p + i) * kDynEnvsPerWg + kEnvsPerWave * t0 + el];
-            dq1[i] = hq[(kJpl * p + i) * kDynEnvsPerWg + kEnvsPerWave + el];
-            dqd1[i] = hq[(kDof + kJpl * p + i) * kDynEnvsPerWg + kEnvsPerWave + el];
-        }
-    }
-    handoff_sync();
-    const LaneConsts K = lane_consts(p);
-    // the 36 constant obs entries of this lane's tile slots: once per kernel
-    if (OBS_EM) { SinkLdsTile sink{tile + el * kObsDim, kJpl * p, p}; emit_obs_const(K, sink); }
-    else { SinkLdsFeatureTile sink{tile + el, kJpl * p, p}; emit_obs_const(K, sink); }
-
-    if (kDynStepWaves == 1) {
-        dyn_finish_tile<OBS_EM>(P, D, K, raw0, dq0, dqd0, tile, base, lane, false);
-        if (base + kEnvsPerWave < n)
-            dyn_finish_tile<OBS_EM>(P, D, K, raw1, dq1, dqd1, tile, base + kEnvsPerWave, lane, true);
-    } else if (base + (long long)kEnvsPerWave * wv < n) {
-        dyn_finish_tile<OBS_EM>(P, D, K, raw0, dq0, dqd0, tile, base + (long long)kEnvsPerWave * wv, lane, false);
-    }
-}
-
-
-// independent waves per workgroup of dyn_rollout_kernel (own LDS slice, own 64 envs each).  A/B r03 in one run, twice: 25.60 us per
-// rollout step with four (256 workgroups = one wave per SIMD by construction) against 25.65 with one: its waves already landed one per
-// SIMD, so the r02 form stays.
-#ifndef PNR_DYN_ROLLOUT_WAVES
-#define PNR_DYN_ROLLOUT_WAVES 1
-#endif
-constexpr int kDynRolloutWaves = PNR_DYN_ROLLOUT_WAVES;
-constexpr int kComFloats = 2 * kWave * 4;                  // common words of each lane's two envs between steps: float4 [2][64]
-constexpr int kRstFloats = (1 + kDof) * kDynEnvsPerWg;     // reset notes: episode flag + new r [7][64]
-
 struct DynTileRegs {      // what phase A handed over for this lane's record of one env
     RawState raw;         // a, v, r of the lane's three joints (+ the common words on the first step)
     float q[kJpl], qd[kJpl];
 };
 
-__device__ __forceinline__ void dyn_write_handoff(float* hand, int lane, const DynLane& L)
+// phase A's results for the lane's env: its two state records and the simulated q, qd
+__device__ __forceinline__ void dyn_write_handoff(float* hand, int lane, const RawState (&k)[2], const float (&q)[kDof],
+                                                  const float (&qd)[kDof])
 {
     float4* hrec = reinterpret_cast<float4*>(hand);               // [3][2 * 64] records, index 2 * env + p
     float* hq = hand + kHandRecFloats;                            // [12][64]: q then qd
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        hrec[2 * lane + p] = make_float4(L.a[3 * p], L.a[3 * p + 1], L.a[3 * p + 2], L.v[3 * p]);
-        hrec[2 * kDynEnvsPerWg + 2 * lane + p] = make_float4(L.v[3 * p + 1], L.v[3 * p + 2], L.r[3 * p], L.r[3 * p + 1]);
-        hrec[4 * kDynEnvsPerWg + 2 * lane + p] = make_float4(L.r[3 * p + 2], L.cw[p][0], L.cw[p][1], L.cw[p][2]);
+        hrec[2 * lane + p] = k[p].p0;
+        hrec[2 * kDynEnvsPerWg + 2 * lane + p] = k[p].p1;
+        hrec[4 * kDynEnvsPerWg + 2 * lane + p] = k[p].p2;
     }
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
-        hq[i * kDynEnvsPerWg + lane] = L.q[i];
-        hq[(kDof + i) * kDynEnvsPerWg + lane] = L.qd[i];
+        hq[i * kDynEnvsPerWg + lane] = q[i];
+        hq[(kDof + i) * kDynEnvsPerWg + lane] = qd[i];
     }
 }
 
@@ -420,12 +249,14 @@ __device__ __forceinline__ void dyn_read_handoff(const float* hand, int env, int
     }
 }
 
-// One 32-env tile of phase B.  The env's common words (target | potential, step, episode) arrive with the first
-// hand-off; between the steps of a looped launch they wait in `com` (LDS), so that nothing of phase B stays in
-// registers during the sub-steps.
-template <bool OBS_EM>
-__device__ __forceinline__ void dyn_rollout_tile(const KParams& P, const DynParams& D, const LaneConsts& K, const DynTileRegs& in,
-                                                float4* com, float* tile, float* rst, long long tile0, int t, int lane,
+// One 32-env tile of phase B at step t of the launch, for both dynamics kernels.  ROLLOUT (dyn_rollout_kernel): the env's common
+// words (target | potential, step, episode) arrive with the first hand-off; between the steps of the looped launch they wait in
+// `com` (LDS), so that nothing of phase B stays in registers during the sub-steps; a reset is noted in `rst` for the env's phase-A
+// lane, and state / dyn words go back to memory on the last step only.  Otherwise (dyn_step_kernel: t = 0, no com, no rst) every
+// step is the last.
+template <bool OBS_EM, bool ROLLOUT>
+__device__ __forceinline__ void dyn_finish_tile(const KParams& P, const DynParams& D, const LaneConsts& K, const DynTileRegs& in,
+                                                float4* com, float* rst, float* tile, long long tile0, int t, int lane,
                                                 bool tile_in_use)
 {
     const int p = lane & 1, el = lane >> 1;
@@ -433,12 +264,12 @@ __device__ __forceinline__ void dyn_rollout_tile(const KParams& P, const DynPara
     const long long e = tile0 + el;
     const bool valid = e < n;               // the pair shares `valid`, so DPP partners are live
     const int nvalid = (int)((n - tile0) < kEnvsPerWave ? (n - tile0) : kEnvsPerWave);
-    const bool last = t == P.T - 1;
+    const bool last = !ROLLOUT || t == P.T - 1;
 
     LaneState s;
     {
-        RawState raw = in.raw;
-        if (t > 0) { const float4 c = *com; raw.p2.y = c.y; raw.p2.z = c.z; raw.p2.w = c.w; }
+        RawState raw = in.raw;              // all-zero records for lanes past the end
+        if (ROLLOUT && t > 0) { const float4 c = *com; raw.p2.y = c.y; raw.p2.z = c.z; raw.p2.w = c.w; }
         unpack_state(raw, p, s);            // a, v, r of this lane's joints + the env's common words
     }
     LaneState o = s;                        // what reward / obs see: the simulated q, qd
@@ -454,42 +285,25 @@ __device__ __forceinline__ void dyn_rollout_tile(const KParams& P, const DynPara
     Pose q;
     compute_pose(o, p, q);
 
-    // -- reward block, pioneer_knm_env.py:157-165 (both lanes, identical) ----------
-    const float old_pot = s.pot;
-    const float pot = P.pot_m / (q.dist / P.pot_s + 1.0f);        // :232-236
-    const bool done = done_predicate(o, p, q.dist, P.done_dist, P.done_dist_d);   // :160
-    const float r_pot = pot - old_pot;
-    const float r_step = -P.penalty;
-    const float r_done = done ? P.award_done : 0.0f;
-    const float rw = (r_pot + r_step) + r_done;                   // :165
-    s.pot = pot;
-    // gym.wrappers.TimeLimit: truncated = elapsed >= max and not done
-    bool trunc = (P.max_steps > 0) && (s.step >= (uint32_t)P.max_steps) && !done;
-    // a lane whose simulation diverged (non-finite pose) is cut like a time-out, so auto-reset recovers
-    // it instead of carrying NaNs forever (kinematic mode keeps the reference's NaN-propagating behaviour)
-    if (!(q.dist == q.dist && __builtin_fabsf(q.dist) <= 3.0e38f)) trunc = !done;
-
-    if (valid && p == 0) {
-        const long long oi = (long long)t * n + e;
-        stream_store(P.reward + oi, rw);
-        stream_store(P.done + oi, (uint8_t)done);
-        if (P.trunc) stream_store(P.trunc + oi, (uint8_t)trunc);
-        if (P.info) stream_store(reinterpret_cast<float4*>(P.info) + oi, make_float4(r_pot, r_step, r_done, q.dist));
-    }
+    const Outcome oc = step_outcome<true>(P, o, p, q.dist);
+    s.pot = oc.pot;
+    o.pot = oc.pot;
+    if (valid && p == 0) store_outcome(P, oc, q.dist, (long long)t * n + e);
 
     // -- in-kernel auto-reset (BulletEnv.reset as the sampler would call it) -----
     // `done`/`trunc` are identical in both lanes of a pair, so pairs stay together
-    o.pot = pot;
-    const bool redraw = P.auto_reset && (done || trunc);
+    const bool redraw = P.auto_reset && (oc.done || oc.trunc);
     if (redraw) {
         reset_env(P, K, s, p, P.env_off + (unsigned long long)e, nullptr, nullptr);
         if (valid) {
             dyn_reset_lane(P, D, s, p, e, P.env_off + (unsigned long long)e, s.episode - 1);   // q = r, qd = 0, new draws
-            // note for the env's phase-A lane: the counter after the reset (>= 1) and the new joints
-            const int env = el + (int)(tile0 & (kDynEnvsPerWg - 1));
-            if (p == 0) rst[env] = __uint_as_float(s.episode);
+            if (ROLLOUT) {
+                // note for the env's phase-A lane: the counter after the reset (>= 1) and the new joints
+                const int env = el + (int)(tile0 & (kDynEnvsPerWg - 1));
+                if (p == 0) rst[env] = __uint_as_float(s.episode);
 #pragma unroll
-            for (int i = 0; i < kJpl; ++i) rst[(1 + kJpl * p + i) * kDynEnvsPerWg + env] = s.r[i];
+                for (int i = 0; i < kJpl; ++i) rst[(1 + kJpl * p + i) * kDynEnvsPerWg + env] = s.r[i];
+            }
         }
         o = s;
         compute_pose(o, p, q);
@@ -499,29 +313,90 @@ __device__ __forceinline__ void dyn_rollout_tile(const KParams& P, const DynPara
         if (!redraw) {
 #pragma unroll
             for (int i = 0; i < kJpl; ++i) {
-                D.dyn[(long long)(kJpl * p + i) * n + e] = in.q[i];
-                D.dyn[(long long)(6 + kJpl * p + i) * n + e] = in.qd[i];
+                D.dyn[(long long)(kDynQ + kJpl * p + i) * n + e] = in.q[i];
+                D.dyn[(long long)(kDynQd + kJpl * p + i) * n + e] = in.qd[i];
             }
         }
     }
-    *com = make_float4(0.f, p ? s.pot : s.tgt[0], p ? __uint_as_float(s.step) : s.tgt[1],
-                        p ? __uint_as_float(s.episode) : s.tgt[2]);
+    if (ROLLOUT) *com = make_float4(0.f, p ? s.pot : s.tgt[0], p ? __uint_as_float(s.step) : s.tgt[1],
+                                    p ? __uint_as_float(s.episode) : s.tgt[2]);
 
     // -- observe() ----------------------------------------------------------------
-    float* obs_t = P.obs + (long long)t * n * kObsDim;
+    // (timing-only ablations of a -DPNR_DIAG_BUILD=1 variant, PNR_DIAG bits as in step_kernel: 2 no obs flush, 4 no obs emit; in the
+    // product library `diag` is the literal 0)
+    const int diag = PNR_DIAG_BUILD ? P.diag : 0;
     if (tile_in_use) wave_lds_sync();       // previous flush done before the tile is rewritten
-    if (OBS_EM) {
-        SinkLdsTile sink{tile + el * kObsDim, kJpl * p, p};
-        emit_obs<false>(K, o, q, p, sink);
-        wave_lds_sync();
-        flush_tile(tile, obs_t + tile0 * kObsDim, nvalid, lane);
-    } else {
-        SinkLdsFeatureTile sink{tile + el, kJpl * p, p};
-        emit_obs<false>(K, o, q, p, sink);
-        wave_lds_sync();
-        flush_feature_tile(tile, obs_t + tile0, n, nvalid, lane);
-    }
+    obs_tile_out<OBS_EM>(K, o, q, tile, el, p, lane, P.obs + (long long)t * n * kObsDim, tile0, n, nvalid, !(diag & 4), !(diag & 2));
 }
+
+// Leading scalar arguments as in step_kernel: preloaded into SGPRs, they repeat P.state / D.dyn / P.actions /
+// P.n / P.dt / P.eps and carry max_v_to_r.
+// The workgroup is TWO waves.  Wave 0 runs phase A for the 64 envs (wave 1 waits at the barrier and takes no issue slot); in
+// phase B each wave finishes ONE of the two 32-env tiles in an obs tile of its own, side by side on two SIMDs, instead of wave 0
+// finishing them one after the other (phase B is ~40 % of the step's fixed cost; the one-wave form: DESIGN_HISTORY.md).
+constexpr int kDynStepWaves = 2;
+
+template <bool OBS_EM, bool ACT_EM, bool RAND, int PHYS>
+__global__ __launch_bounds__(kWave * kDynStepWaves) void dyn_step_kernel(const float4* __restrict__ state_, const float* __restrict__ dyn_,
+                                                         const float* __restrict__ actions_, const long long n_,
+                                                         const double dt_, const double eps_, const float max_v_to_r_,
+                                                         const KParams P, const DynParams D)
+{
+    __shared__ __attribute__((aligned(16))) float lds[kDynStepWaves * kTileFloats];
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+    const long long n = n_;
+    const long long base = (long long)blockIdx.x * kDynEnvsPerWg;
+    float* tile = lds + wv * kTileFloats;                         // this wave's obs tile
+    float* hand = lds;                                            // the hand-off area: the head of tile 0
+
+    // ---- phase A: one env per lane (wave 0)
+    if (wv == 0) {
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        RawState k[2] = {{z4, z4, z4}, {z4, z4, z4}};               // all-zero records for lanes past the end
+        float q[kDof] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, qd[kDof] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const DynLead lead = {state_, dyn_, actions_, n_, dt_, eps_, max_v_to_r_};
+        if (base + lane < n) dyn_substeps_lane<ACT_EM, RAND, PHYS>(lead, D, base + lane, k, q, qd);
+        // dyn_write_handoff's text, spelled out: through the call, this kernel's register allocation moved by 1-6 VGPRs in 24 of its
+        // 32 instantiations (same instruction mix; listings compared with tools/device_code_diff.py), so the call waits for a compiler
+        // that does not care
+        float4* hrec = reinterpret_cast<float4*>(hand);
+        float* hq = hand + kHandRecFloats;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            hrec[2 * lane + p] = k[p].p0;
+            hrec[2 * kDynEnvsPerWg + 2 * lane + p] = k[p].p1;
+            hrec[4 * kDynEnvsPerWg + 2 * lane + p] = k[p].p2;
+        }
+#pragma unroll
+        for (int i = 0; i < kDof; ++i) {
+            hq[i * kDynEnvsPerWg + lane] = q[i];
+            hq[(kDof + i) * kDynEnvsPerWg + lane] = qd[i];
+        }
+    }
+    __syncthreads();
+
+    // ---- phase B: lane pairs, wave wv takes tile wv; both tiles' hand-off values leave LDS before tile 0 (which they alias) is reused
+    const int p = lane & 1, el = lane >> 1;
+    DynTileRegs g;
+    dyn_read_handoff(hand, kEnvsPerWave * wv + el, p, g);
+    __syncthreads();
+    const LaneConsts K = lane_consts(p);
+    // the 36 constant obs entries of this lane's tile slots: once per kernel
+    obs_tile_const<OBS_EM>(K, tile, el, p);
+
+    if (base + (long long)kEnvsPerWave * wv < n)
+        dyn_finish_tile<OBS_EM, false>(P, D, K, g, nullptr, nullptr, tile, base + (long long)kEnvsPerWave * wv, 0, lane, false);
+}
+
+// independent waves per workgroup of dyn_rollout_kernel (own LDS slice, own 64 envs each).  A/B r03 in one run, twice: 25.60 us per
+// rollout step with four (256 workgroups = one wave per SIMD by construction) against 25.65 with one: its waves already landed one per
+// SIMD, so the r02 form stays.
+#ifndef PNR_DYN_ROLLOUT_WAVES
+#define PNR_DYN_ROLLOUT_WAVES 1
+#endif
+constexpr int kDynRolloutWaves = PNR_DYN_ROLLOUT_WAVES;
+constexpr int kComFloats = 2 * kWave * 4;                  // common words of each lane's two envs between steps: float4 [2][64]
+constexpr int kRstFloats = (1 + kDof) * kDynEnvsPerWg;     // reset notes: episode flag + new r [7][64]
 
 // pnr_rollout in dynamics mode: P.T steps in ONE launch.  Same two phases as dyn_step_kernel, but the env's
 // a, v, r, q, qd and parameters stay in its phase-A lane's registers from step to step, the pair lanes keep the
@@ -538,7 +413,7 @@ __global__ __launch_bounds__(kWave * kDynRolloutWaves) void dyn_rollout_kernel(c
 {
     // kDynRolloutWaves independent waves per workgroup (each with its own LDS slice and its own 64 envs; no barrier between them):
     // at 65 536 envs the 1 024 waves are 256 workgroups = exactly one wave per SIMD, whatever the dispatcher does
-    constexpr int kPerWave = kTileFloats + kComFloats + kRstFloats + kHandFloats + (PNR_DYN_LDS_MODEL ? kDynStageWords * 64 : 0);
+    constexpr int kPerWave = kTileFloats + kComFloats + kRstFloats + kHandFloats;
     __shared__ __attribute__((aligned(16))) float lds_all[kDynRolloutWaves * kPerWave];
     float* lds = lds_all + (threadIdx.x >> 6) * kPerWave;
     float* tile = lds;
@@ -563,19 +438,19 @@ __global__ __launch_bounds__(kWave * kDynRolloutWaves) void dyn_rollout_kernel(c
 #pragma unroll
     for (int i = 0; i < kDof; ++i) L.act[i] = 0.f;
     if (liveA) dyn_lane_load<ACT_EM, RAND>(lead, base, lane, L);
-    {   // the 36 constant obs entries of this lane's tile slots: once per kernel (nothing else writes them)
-        const LaneConsts K0 = lane_consts(p);
-        if (OBS_EM) { SinkLdsTile sink{tile + el * kObsDim, kJpl * p, p}; emit_obs_const(K0, sink); }
-        else { SinkLdsFeatureTile sink{tile + el, kJpl * p, p}; emit_obs_const(K0, sink); }
-    }
+    // the 36 constant obs entries of this lane's tile slots: once per kernel (nothing else writes them)
+    obs_tile_const<OBS_EM>(lane_consts(p), tile, el, p);
 
     const int T = P.T;
     if (base >= n) return;          // a wave past the end of the batch (whole wave: no barrier follows in this kernel)
     for (int t = 0; t < T; ++t) {
         // ---- phase A: one env per lane
-        if (liveA) dyn_lane_advance<ACT_EM, RAND, PHYS>(lead, D, base, lane, t + 1 < T ? actions_ + (long long)(t + 1) * n * kDof : nullptr, L,
-                                                           lds + kTileFloats + kComFloats + kRstFloats + kHandFloats);
-        dyn_write_handoff(hand, lane, L);
+        if (liveA) dyn_lane_advance<ACT_EM, RAND, PHYS>(lead, D, base, lane, t + 1 < T ? actions_ + (long long)(t + 1) * n * kDof : nullptr, L);
+        {
+            const RawState k[2] = {pack_record(L.a, L.v, L.r, L.cw[0][0], L.cw[0][1], L.cw[0][2]),
+                                   pack_record(L.a + 3, L.v + 3, L.r + 3, L.cw[1][0], L.cw[1][1], L.cw[1][2])};
+            dyn_write_handoff(hand, lane, k, L.q, L.qd);
+        }
         rst[lane] = 0.f;                                // no reset noted yet (episode counters are >= 1)
         wave_lds_sync();
 
@@ -590,12 +465,12 @@ __global__ __launch_bounds__(kWave * kDynRolloutWaves) void dyn_rollout_kernel(c
             {
                 DynTileRegs g;
                 dyn_read_handoff(hand, elb, pb, g);
-                dyn_rollout_tile<OBS_EM>(P, D, Kb, g, com + lane_b, tile, rst, base, t, lane_b, t > 0);
+                dyn_finish_tile<OBS_EM, true>(P, D, Kb, g, com + lane_b, rst, tile, base, t, lane_b, t > 0);
             }
             if (base + kEnvsPerWave < n) {
                 DynTileRegs g;
                 dyn_read_handoff(hand, kEnvsPerWave + elb, pb, g);
-                dyn_rollout_tile<OBS_EM>(P, D, Kb, g, com + kWave + lane_b, tile, rst, base + kEnvsPerWave, t, lane_b, true);
+                dyn_finish_tile<OBS_EM, true>(P, D, Kb, g, com + kWave + lane_b, rst, tile, base + kEnvsPerWave, t, lane_b, true);
             }
             // ---- back to phase A: envs that were reset continue from the new draw
             if (t + 1 < T) {
@@ -653,7 +528,7 @@ __global__ __launch_bounds__(kWave) void reset_kernel(const KParams P, const Dyn
 #pragma unroll
         for (int i = 0; i < kJpl; ++i) {
             const float qi = valid ? D.dyn[(long long)(kJpl * p + i) * n + e] : 0.f;
-            const float qdi = valid ? D.dyn[(long long)(6 + kJpl * p + i) * n + e] : 0.f;
+            const float qdi = valid ? D.dyn[(long long)(kDynQd + kJpl * p + i) * n + e] : 0.f;
             s.r[i] = qi;
             if (!D.teleport) s.v[i] = qdi;
         }
@@ -664,16 +539,8 @@ __global__ __launch_bounds__(kWave) void reset_kernel(const KParams P, const Dyn
         if (OBS == 1) {
             SinkDirect sink{P.obs + e, n, kJpl * p, p, active};
             emit_obs(K, s, q, p, sink);
-        } else if (OBS == 2) {
-            SinkLdsTile sink{tile + el * kObsDim, kJpl * p, p};
-            emit_obs(K, s, q, p, sink);
-            wave_lds_sync();
-            flush_tile(tile, P.obs + tile0 * kObsDim, nvalid, lane);
-        } else if (OBS == 4) {
-            SinkLdsFeatureTile sink{tile + el, kJpl * p, p};
-            emit_obs(K, s, q, p, sink);
-            wave_lds_sync();
-            flush_feature_tile(tile, P.obs + tile0, n, nvalid, lane);
+        } else if (OBS == 2 || OBS == 4) {
+            obs_tile_out<OBS == 2, true>(K, s, q, tile, el, p, lane, P.obs, tile0, n, nvalid);
         } else {
             SinkDirect sink{P.obs + e * kObsDim, 1, kJpl * p, p, active};
             emit_obs(K, s, q, p, sink);
@@ -693,27 +560,25 @@ __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restri
 {
     const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
     if (e >= n) return;
-    const long long n2 = 2 * n;
     float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof];
+    const long long n2 = 2 * n;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {           // the env's command state r, v: what a joint without a command of its own tracks
-        const float4 k0 = state[2 * e + p], k1 = state[n2 + 2 * e + p], k2 = state[2 * n2 + 2 * e + p];
-        a[3 * p] = k0.x; a[3 * p + 1] = k0.y; a[3 * p + 2] = k0.z; v[3 * p] = k0.w;
-        v[3 * p + 1] = k1.x; v[3 * p + 2] = k1.y; r[3 * p] = k1.z; r[3 * p + 1] = k1.w;
-        r[3 * p + 2] = k2.x;
+        const RawState k = {state[2 * e + p], state[n2 + 2 * e + p], state[2 * n2 + 2 * e + p]};
+        unpack_record(k, a + 3 * p, v + 3 * p, r + 3 * p);
     }
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
-        q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(6 + i) * n + e];
-        fric[i] = dyn[(long long)(23 + i) * n + e]; damp[i] = dyn[(long long)(29 + i) * n + e];
+        q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
+        fric[i] = dyn[(long long)(kDynFric + i) * n + e]; damp[i] = dyn[(long long)(kDynDamp + i) * n + e];
         act[i] = 0.f;
     }
 #pragma unroll
-    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(12 + l) * n + e] : 1.0f;
+    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
     const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
-    dyn_core<PHYS, true, CMOTOR>(lead, D, a, v, r, q, qd, sc, fric, damp, act, nullptr, &W);
+    dyn_core<PHYS, true, CMOTOR>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &W);
 #pragma unroll
-    for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(6 + i) * n + e] = qd[i]; }
+    for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
 }
 
 // The same call on a kinematic-mode handle: there is no simulated state, the caller holds the joints as Bullet would after

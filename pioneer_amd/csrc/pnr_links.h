@@ -122,7 +122,7 @@ __device__ __forceinline__ void load_link_joints(const float* __restrict__ src, 
         qd[0] = b.z; qd[1] = b.w; qd[2] = c.x; qd[3] = c.y; qd[4] = c.z; qd[5] = c.w;
     } else if (SRC == kLinkSrcDyn) {
 #pragma unroll
-        for (int i = 0; i < kDof; ++i) { q[i] = src[(long long)i * n + e]; qd[i] = src[(long long)(kDof + i) * n + e]; }
+        for (int i = 0; i < kDof; ++i) { q[i] = src[(long long)i * n + e]; qd[i] = src[(long long)(kDynQd + i) * n + e]; }
     } else {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
