@@ -42,7 +42,8 @@ extern "C" {
  *      (before `stream`), pnr_mlp_step gained `planes`; pnr_create waits for its zero fill (Conventions)
  *   5  new entry points pnr_world_step, pnr_set_joint_motor, pnr_build_fingerprint; `planes` == 2 now means two SCALED FP16 planes
  *      (was: two bf16 planes) in every pnr_mlp_* call; pnr_mlp_train_step checks every argument before its first launch and
- *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render */
+ *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
+ *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -53,6 +54,7 @@ extern "C" {
 #define PNR_DYN_STATE_WORDS 36 /* dynamics mode: q[6] qd[6] + 24 params       */
 #define PNR_NUM_LINKS 11       /* pnr_get_link_states: links per env (URDF joint order) */
 #define PNR_LINK_STATE_DIM 13  /* floats per link record                      */
+#define PNR_JACOBIAN_DIM 36    /* pnr_get_jacobian: 6 rows x 6 joint columns per env */
 
 enum pnr_status {
     PNR_OK = 0,
@@ -330,6 +332,68 @@ int pnr_set_dyn_state(pnr_handle h, const float* words_in, void* stream);
  * float32 arithmetic.  Parity unpinned (Bullet's own link states are not reproduced bit for bit).
  */
 int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void* stream);
+
+/*
+ * calculateJacobian for link `link` (0..10, Bullet's link_index as in pnr_get_link_states) of every env, one launch.
+ *   local_point  HOST pointer to 3 doubles, a point in the link's frame (PyBullet's localPosition); NULL = the frame origin
+ *   joint_state  as pnr_get_link_states ([num_envs][12] q | qd, 16-byte aligned, only q is read); NULL = the handle's own
+ *                joints (PNR_ERR_INVALID before the first pnr_reset or pnr_set_state)
+ *   out          [num_envs][6][6] float32 row-major, 16-byte aligned; nothing past num_envs * PNR_JACOBIAN_DIM floats is written.
+ *                rows 0-2: world linear velocity of the point per unit velocity of joint j (column j, URDF revolute order);
+ *                rows 3-5: world angular velocity of the link per unit velocity of joint j.
+ *                Columns of joints that are not between the base and the link are exactly 0; link 0 gives all zeros.
+ * So out . qd is the link's velocity as pnr_get_link_states reports it (at the point), and tau = J^T f maps a world force
+ * at the point to joint torques.  Any finite joint value is accepted; non-finite input gives non-finite output, unchecked.
+ * PNR_ERR_INVALID, nothing launched and no output touched, for: a null handle or out, link outside 0..10, a non-finite
+ * local_point, misaligned pointers.  float32 arithmetic, asynchronous on `stream`, no allocation: capturable into a graph.
+ */
+int pnr_get_jacobian(pnr_handle h, const float* joint_state, int32_t link, const double* local_point, float* out, void* stream);
+
+/*
+ * Position-only inverse kinematics (calculateInverseKinematics without an orientation) for every env, one launch: joint
+ * angles inside the URDF limits that put a point of a link on a world target.  Plain damped least squares; per env,
+ * independently of every other env (an env's result does not depend on the batch around it, bit for bit):
+ *
+ *     q  = clamp(q_init, r_lo, r_hi)
+ *     repeat up to max_iterations times:
+ *         e = target - p(q);   stop (frozen from now on) if |e| <= tolerance        (float32 distance)
+ *         J = the three linear rows of the Jacobian at q                          (3 x 6, as pnr_get_jacobian)
+ *         y = (J J^T + lambda^2 I)^-1 e                                           (3 x 3, symmetric positive definite)
+ *         dq = J^T y;   dq *= min(1, max_step / max_j |dq_j|)
+ *         q = clamp(q + dq, r_lo, r_hi)
+ *
+ *   target_pos  [num_envs][3] float32 world positions, or NULL = each env's own target (pnr_get_state words 18-20;
+ *               PNR_ERR_INVALID before the first pnr_reset or pnr_set_state)
+ *   q_init      [num_envs][6] float32, or NULL = the rest pose q = 0; clamped into the joint limits before the first iteration
+ *   q_out       [num_envs][6] float32 (8-byte aligned), always inside [r_lo, r_hi] of pnr_get_constants
+ *   residual_out [num_envs] float32 or NULL: |target - point(q_out)| as the kernel's float32 forward kinematics sees it
+ *   iterations_out [num_envs] int32 or NULL: iterations this env took (max_iterations if it never met the tolerance)
+ *
+ * Measured basin (float64 restatement of the chain, default parameters): from the rest pose every target of the box
+ * (15, -8, 2) .. (22, 8, 6) converges in <= 7 iterations; from uniformly random starts inside the limits 17-23 % of the solves
+ * end in a local minimum at a joint limit.  That is why NULL means the rest pose and not the env's current pose.  About 3 %
+ * of the reference's target box (15, -10, 2) .. (25, 10, 6) cannot be reached at all (its far corners, |t| >= 25.4); from the
+ * rest pose alone about 4 % of it is not reached (one target in a hundred stops in a local minimum of that start).
+ *
+ * PNR_ERR_INVALID, nothing launched and no output touched, for: a null handle, params or q_out, a wrong struct_size, link
+ * outside 0..10, max_iterations outside 1..1024, a non-finite or non-positive damping or max_step, a negative or non-finite
+ * tolerance, a non-finite local_point, misaligned pointers (q_out 8 bytes, the others 4).  Non-finite joint or target values
+ * give non-finite outputs, unchecked; the loop is bounded by max_iterations.  float32 arithmetic, asynchronous on `stream`,
+ * no allocation, no synchronisation: capturable into a graph.
+ */
+typedef struct pnr_ik_params {
+    uint32_t struct_size;     /* sizeof(pnr_ik_params) */
+    int32_t  link;            /* 0..10; default 10 (robot:pointer) */
+    double   local_point[3];  /* a point in the link's frame; default 0 */
+    int32_t  max_iterations;  /* 1..1024; default 32 */
+    int32_t  reserved;
+    double   damping;         /* lambda > 0, default 1.0 */
+    double   max_step;        /* > 0, rad: cap on the largest joint change of one iteration, default 0.5 */
+    double   tolerance;       /* >= 0: an env stops once its float32 distance is <= tolerance; default 1e-3 */
+} pnr_ik_params;
+int pnr_ik_params_default(pnr_ik_params* p);
+int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, const float* q_init,
+                 float* q_out, float* residual_out, int32_t* iterations_out, void* stream);
 
 /*
  * render('rgb_array') for every env in one launch (bullet_env.py:156-185 -> getCameraImage): one camera shared by all envs,

@@ -35,6 +35,7 @@ INFO_DIM = 4
 DYN_STATE_WORDS = 36
 NUM_LINKS = 11          # pnr_get_link_states: link records per env (Bullet's link_index order, model.LINKS[1:])
 LINK_STATE_DIM = 13     # position[3], quaternion x y z w [4], linear velocity[3], angular velocity[3]
+JACOBIAN_DIM = 36       # pnr_get_jacobian: 6 rows (linear xyz, angular xyz) x 6 joint columns per env
 
 PNR_OK = 0
 ENV_MAJOR, FEATURE_MAJOR = 0, 1
@@ -71,6 +72,12 @@ class PnrRenderParams(C.Structure):
         ("background", C.c_float * 3), ("target_rgba", C.c_float * 4), ("reserved", C.c_int32),
         ("bodies", PnrSceneBody * MAX_SCENE), ("body_rgba", (C.c_float * 4) * MAX_SCENE),
     ]
+
+
+class PnrIkParams(C.Structure):
+    """pnr_ik_params of include/pioneer_amd.h (pnr_solve_ik's point, iteration cap, damping, step cap and tolerance)."""
+    _fields_ = [("struct_size", C.c_uint32), ("link", C.c_int32), ("local_point", C.c_double * 3), ("max_iterations", C.c_int32),
+                ("reserved", C.c_int32), ("damping", C.c_double), ("max_step", C.c_double), ("tolerance", C.c_double)]
 
 
 class PnrConfig(C.Structure):
@@ -157,6 +164,9 @@ SIGNATURES = {
     "pnr_get_dyn_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_dyn_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_get_link_states": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "pnr_get_jacobian": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_double * 3), _VP, _VP]),
+    "pnr_ik_params_default": (C.c_int, [C.POINTER(PnrIkParams)]),
+    "pnr_solve_ik": (C.c_int, [_VP, C.POINTER(PnrIkParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
     "pnr_diag_sincos": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, _VP]),
     "pnr_ppo_loss": (C.c_int, [C.c_int64] + [_VP] * 12 + [C.c_float] * 3 + [_VP] * 3 + [C.c_int64, _VP, _VP]),
@@ -189,7 +199,7 @@ SIGNATURES = {
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 UNITS = {
     "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_links.h",
-                    "pnr_render.h"],
+                    "pnr_render.h", "pnr_ik.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_sampler.h"],
 }
 SOURCES = sorted({f for deps in UNITS.values() for f in deps})      # every file a unit includes: what _stale() watches

@@ -42,6 +42,7 @@
 #include "pnr_env_kernels.h"
 #include "pnr_links.h"
 #include "pnr_render.h"
+#include "pnr_ik.h"
 
 // =====================================================================================
 // host side
@@ -715,6 +716,87 @@ int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void
         hipLaunchKernelGGL(link_state_kernel<S()>, grid, block, 0, st, joint_state ? joint_state : h->dyn,
                            src == kLinkSrcKin ? h->state : nullptr, out, (long long)h->n);
     });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+// (link, local_point) -> the moving body that carries the link and the point's offset in that body's frame: every fixed joint of
+// the URDF has rpy 0 and, but for effector_to_pointer (kTip), xyz 0, so a link's frame is its body's frame moved by a constant
+static ChainPoint chain_point(int link, const double* local_point)
+{
+    double o[3] = {0, 0, 0};
+    if (local_point) for (int k = 0; k < 3; ++k) o[k] = local_point[k];
+    if (link == kNumLinks - 1) { o[0] += kTipX; o[1] += kTipY; o[2] += kTipZ; }
+    return {kLinkBody[link], (float)o[0], (float)o[1], (float)o[2]};
+}
+
+static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+int pnr_get_jacobian(pnr_handle h, const float* joint_state, int32_t link, const double* local_point, float* out, void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!out) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: null out");
+    if (link < 0 || link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: link %d outside 0..%d", link, kNumLinks - 1);
+    if (local_point && !finite_all(local_point, 3)) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: non-finite local_point");
+    if (!aligned16(out) || !aligned16(joint_state))
+        return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: out and joint_state must be 16-byte aligned");
+    if (!joint_state && !h->ready && !(h->dyn && h->dyn_set))
+        return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian before the first pnr_reset (or pnr_set_state)");
+    DeviceGuard g(h->device);
+    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave)), block(kWave);
+    hipStream_t st = (hipStream_t)stream;
+    const int src = link_source(h, joint_state);
+    const ChainPoint P = chain_point(link, local_point);
+    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
+        hipLaunchKernelGGL(jacobian_kernel<S()>, grid, block, 0, st, joint_state ? joint_state : h->dyn,
+                           src == kLinkSrcKin ? h->state : nullptr, out, (long long)h->n, P);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+int pnr_ik_params_default(pnr_ik_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_ik_params_default: null params");
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_ik_params);
+    p->link = kNumLinks - 1;
+    p->max_iterations = 32;
+    p->damping = 1.0;
+    p->max_step = 0.5;
+    p->tolerance = 1e-3;
+    return PNR_OK;
+}
+
+int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, const float* q_init,
+                 float* q_out, float* residual_out, int32_t* iterations_out, void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: null params");
+    if (!q_out) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: null q_out");
+    if (p->struct_size != sizeof(pnr_ik_params))
+        return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_ik_params));
+    if (p->link < 0 || p->link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: link %d outside 0..%d", p->link, kNumLinks - 1);
+    if (p->max_iterations < 1 || p->max_iterations > 1024)
+        return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: max_iterations %d outside 1..1024", p->max_iterations);
+    if (!(std::isfinite(p->damping) && p->damping > 0)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: damping must be finite and > 0");
+    if (!(std::isfinite(p->max_step) && p->max_step > 0)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: max_step must be finite and > 0");
+    if (!(std::isfinite(p->tolerance) && p->tolerance >= 0)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: tolerance must be finite and >= 0");
+    if (!finite_all(p->local_point, 3)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: non-finite local_point");
+    if (!aligned8(q_out)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: q_out must be 8-byte aligned");
+    if (!(aligned4(target_pos) && aligned4(q_init) && aligned4(residual_out) && aligned4(iterations_out)))
+        return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: float32 / int32 arrays must be 4-byte aligned");
+    if (!target_pos && !h->ready && !h->kin_set)
+        return fail(h, PNR_ERR_INVALID, "pnr_solve_ik before the first pnr_reset (or pnr_set_state): the target comes from the state");
+    DeviceGuard g(h->device);
+    IkArgs A;
+    A.target = target_pos; A.state = h->state; A.q_init = q_init;
+    A.q_out = q_out; A.residual = residual_out; A.iterations = iterations_out;
+    A.n = h->n;
+    A.point = chain_point(p->link, p->local_point);
+    A.max_iter = p->max_iterations;
+    A.lambda2 = (float)(p->damping * p->damping); A.max_step = (float)p->max_step; A.tol = (float)p->tolerance;
+    hipLaunchKernelGGL(ik_kernel, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream, A);
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }

@@ -1,0 +1,204 @@
+// pnr_ik.h — pnr_get_jacobian and pnr_solve_ik: the Jacobian of a point of a URDF link (PyBullet's calculateJacobian) and
+// position-only damped-least-squares inverse kinematics (calculateInverseKinematics without an orientation) for every env,
+// one launch each.  Included by pnr_api.hip only; it adds two kernels and edits none of the others.
+//
+// Shape of both: one env per lane, one 64-lane wave per workgroup, as link_state_kernel.  The host resolves (link,
+// local_point) into the moving body that carries the link and the point's offset in that body's frame; both arrive as
+// kernel arguments, so every `J <= body` test below is a scalar branch.
+//
+// jacobian_kernel: one outward sweep (pose_outward) gives each joint's world axis a_j and origin o_j and the point; column j
+// is a_j x (point - o_j) | a_j.  The 36 floats of an env go into an LDS tile of [64][37] floats (the odd row stride keeps
+// the ds_write_b32 of each 32-lane half on 32 distinct banks, as pnr_links.h's 143 does) and the tile leaves as ONE contiguous span of 16-byte
+// non-temporal stores.  36 floats per env are a whole number of float4s, so the span has no partial tail.
+//
+// ik_kernel: q[6], the six sin/cos pairs, the 18 entries of the linear Jacobian and the 3 x 3 system live in registers; the
+// loop's trip count is the wave-uniform max_iterations, a converged lane is frozen by selects, and the wave leaves early once
+// a ballot finds every lane frozen.  The pose code exists ONCE in the loop (the residual of the result is the loop's own last
+// pose), so a lane's arithmetic does not depend on how many trips its neighbours need: results are bit-identical whatever
+// the batch around an env.  Outputs are 32 B per env: plain per-lane stores (three float2 of q, one float, one int).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "pnr_device.h"
+#include "pnr_dyn.h"
+#include "pnr_links.h"
+
+// float32 against a float64 reference, tolerance-checked: let a*b+c fuse
+#pragma clang fp contract(fast)
+
+namespace pnr {
+
+constexpr int kJacDim = 36;                                     // 6 rows x 6 joint columns
+constexpr int kJacRowStride = kJacDim + 1;                      // LDS row stride, odd
+constexpr int kJacTileFloats = kWave * kJacRowStride;           // 2 368 floats = 9 472 B per wave
+static_assert(kJacRowStride % 2 == 1, "an odd row stride keeps the per-lane LDS writes conflict-free");
+static_assert(kJacDim % 4 == 0, "an env's row is a whole number of float4s: the flush has no partial tail");
+
+// the point a Jacobian or an IK solve is about: offset `off` in the frame of moving body `body` (-1: the static base)
+struct ChainPoint { int body; float ox, oy, oz; };
+
+// The chain's Jacobian at the joint angles whose cosines / sines are c, s: per joint J <= body the world axis (ang) and
+// axis x (point - origin) (lin); exactly zero for the joints beyond the body.  point: the point's world position.
+__device__ __forceinline__ void chain_jacobian(const float (&c)[kDof], const float (&s)[kDof], const ChainPoint& P,
+                                               V3 (&lin)[kDof], V3 (&ang)[kDof], V3& point)
+{
+    const V3 off = {P.ox, P.oy, P.oz};
+    V3 org[kDof];
+    M3 R = diag3(1.f);
+    V3 p = {0.f, 0.f, 0.f};
+    point = off;
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        ang[J] = {0.f, 0.f, 0.f};
+        org[J] = {0.f, 0.f, 0.f};
+        if (J <= P.body) {
+            M3 Rn; V3 pn;
+            pose_outward<J>(R, p, c[J], s[J], Rn, pn);
+            R = Rn; p = pn;
+            ang[J] = col(R, (int)kJoints[J].axis);
+            org[J] = p;
+            if (J == P.body) point = p + mul(R, off);
+        }
+    });
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        lin[J] = {0.f, 0.f, 0.f};
+        if (J <= P.body) lin[J] = cross(ang[J], point - org[J]);
+    });
+}
+
+// Copy a wave's tile (rows [0, nvalid) of 36 floats at stride 37) to its contiguous place in out[n][6][6]: 16-byte lane-linear
+// non-temporal stores (dst is 16-byte aligned: the caller's buffer is, and every tile starts 9 216 B further on).  A float4
+// never straddles two rows (36 = 9 x 4).  Nothing past row nvalid is written.
+__device__ __forceinline__ void flush_jacobian_tile(const float* __restrict__ lds, float* __restrict__ dst, int nvalid, int lane)
+{
+    constexpr int kVecPerRow = kJacDim / 4;
+    const int nvec = nvalid * kVecPerRow;
+    float4* dst4 = reinterpret_cast<float4*>(dst);
+    for (int j = lane; j < nvec; j += kWave) {
+        const int r = j / kVecPerRow;
+        const float* src = lds + r * kJacRowStride + 4 * (j - r * kVecPerRow);
+        stream_store(dst4 + j, make_float4(src[0], src[1], src[2], src[3]));
+    }
+}
+
+template <int SRC>
+__global__ __launch_bounds__(kWave) void jacobian_kernel(const float* __restrict__ src, const float4* __restrict__ state,
+                                                         float* __restrict__ out, const long long n, const ChainPoint P)
+{
+    __shared__ __attribute__((aligned(16))) float tile[kJacTileFloats];
+    const int lane = threadIdx.x;
+    const long long tile0 = (long long)blockIdx.x * kWave;
+    const long long e = tile0 + lane;
+    const int nvalid = (int)((n - tile0) < kWave ? (n - tile0) : kWave);
+    float q[kDof], qd[kDof];
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) { q[i] = 0.f; qd[i] = 0.f; }
+    if (e < n) load_link_joints<SRC>(src, state, n, e, q, qd);
+    float c[kDof], s[kDof];
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) sincos_any(q[i], s[i], c[i]);       // any finite joint value, as pnr_get_link_states
+    V3 lin[kDof], ang[kDof], point;
+    chain_jacobian(c, s, P, lin, ang, point);
+    float* row = tile + lane * kJacRowStride;
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        row[J] = lin[J].x; row[kDof + J] = lin[J].y; row[2 * kDof + J] = lin[J].z;
+        row[3 * kDof + J] = ang[J].x; row[4 * kDof + J] = ang[J].y; row[5 * kDof + J] = ang[J].z;
+    });
+    wave_lds_sync();
+    flush_jacobian_tile(tile, out + tile0 * kJacDim, nvalid, lane);
+}
+
+struct IkArgs {
+    const float* target;       // [n][3], or null: the env's own target (state words 18-20)
+    const float4* state;       // the handle's state planes (read only when target is null)
+    const float* q_init;       // [n][6], or null: the rest pose
+    float* q_out;              // [n][6], 8-byte aligned
+    float* residual;           // [n] or null
+    int* iterations;           // [n] or null
+    long long n;
+    ChainPoint point;
+    int max_iter;
+    float lambda2, max_step, tol;
+};
+
+// The iteration law of include/pioneer_amd.h (pnr_solve_ik), one env per lane.
+__global__ __launch_bounds__(kWave) void ik_kernel(const IkArgs A)
+{
+    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
+    const bool live = e < A.n;
+    float q[kDof];
+    V3 tgt = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) q[i] = 0.f;
+    if (live) {
+        if (A.target) { const float* t = A.target + 3 * e; tgt = {t[0], t[1], t[2]}; }
+        else { const float4 w = A.state[2 * (2 * A.n) + 2 * e]; tgt = {w.y, w.z, w.w}; }
+        if (A.q_init) {
+            const float* qi = A.q_init + kDof * e;
+#pragma unroll
+            for (int i = 0; i < kDof; ++i) q[i] = qi[i];
+        }
+    }
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        q[J] = fminf(fmaxf(q[J], limit_lo(J)), limit_hi(J));
+    });
+    bool frozen = !live;
+    int iters = 0;
+    float dist = 0.f;
+    for (int it = 0; ; ++it) {
+        float c[kDof], s[kDof];
+#pragma unroll
+        for (int i = 0; i < kDof; ++i) sincos_bounded(q[i], s[i], c[i]);     // q is inside the limits
+        V3 lin[kDof], ang[kDof], point;
+        chain_jacobian(c, s, A.point, lin, ang, point);
+        const V3 err = tgt - point;
+        dist = sqrtf(dot(err, err));
+        if (it == A.max_iter) break;                                         // the pose of the result: its residual
+        frozen = frozen || dist <= A.tol;
+        if (__builtin_amdgcn_ballot_w64(!frozen) == 0) break;
+        // A = J J^T + lambda^2 I (symmetric positive definite: every pivot below is >= lambda^2), solved as L D L^T
+        float a00 = A.lambda2, a01 = 0.f, a02 = 0.f, a11 = A.lambda2, a12 = 0.f, a22 = A.lambda2;
+        static_for<kDof>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            const V3 g = lin[J];
+            a00 += g.x * g.x; a01 += g.x * g.y; a02 += g.x * g.z;
+            a11 += g.y * g.y; a12 += g.y * g.z; a22 += g.z * g.z;
+        });
+        const float i0 = fast_rcp(a00);
+        const float l10 = a01 * i0, l20 = a02 * i0;
+        const float d1 = a11 - l10 * a01, u12 = a12 - l20 * a01;
+        const float i1 = fast_rcp(d1);
+        const float l21 = u12 * i1;
+        const float d2 = a22 - l20 * a02 - l21 * u12;
+        const float i2 = fast_rcp(d2);
+        const float z0 = err.x, z1 = err.y - l10 * z0, z2 = err.z - l20 * z0 - l21 * z1;
+        const float y2 = z2 * i2, y1 = z1 * i1 - l21 * y2, y0 = z0 * i0 - l10 * y1 - l20 * y2;
+        const V3 y = {y0, y1, y2};
+        float dq[kDof], big = 0.f;
+        static_for<kDof>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            dq[J] = dot(lin[J], y);
+            big = fmaxf(big, fabsf(dq[J]));
+        });
+        const float scale = big > A.max_step ? A.max_step * fast_rcp(big) : 1.f;
+        static_for<kDof>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            const float qn = fminf(fmaxf(q[J] + scale * dq[J], limit_lo(J)), limit_hi(J));
+            q[J] = frozen ? q[J] : qn;
+        });
+        iters += frozen ? 0 : 1;
+    }
+    if (!live) return;
+    float2* qo = reinterpret_cast<float2*>(A.q_out) + 3 * e;
+    qo[0] = make_float2(q[0], q[1]); qo[1] = make_float2(q[2], q[3]); qo[2] = make_float2(q[4], q[5]);
+    if (A.residual) A.residual[e] = dist;
+    if (A.iterations) A.iterations[e] = iters;
+}
+
+}  // namespace pnr
+
+#pragma clang fp contract(off)

@@ -194,6 +194,14 @@ class PioneerKinematicEnv(compat.GymEnv):
     def observe(self) -> Observation:                                      # :184-211
         return self._vec.observe()[0].double().cpu().numpy()
 
+    def solve_ik(self, target_position: Optional[Tuple[float, float, float]] = None) -> Tuple[np.ndarray, float]:
+        """calculateInverseKinematics for robot:pointer (position only, PioneerVectorEnv.solve_ik from the rest pose): the
+        joint positions (float64 [6], inside the joint limits) that put the pointer on ``target_position`` (default: the
+        env's target) and the distance left; ``reset_world(joint_positions=...)`` takes them as they are."""
+        tgt = None if target_position is None else np.asarray(target_position, dtype=np.float32).reshape(1, 3)
+        q, residual, _ = self._vec.solve_ik(target=tgt)
+        return q[0].double().cpu().numpy(), float(residual[0].item())
+
     def render(self, mode="human"):                                        # bullet_env.py:156-185
         if mode == "human":
             return None

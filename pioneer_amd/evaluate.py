@@ -31,8 +31,10 @@ def load_policy(checkpoint: str, device):
 def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, gif_path: Optional[str] = None,
              device="cuda:0", mode: str = "kinematic", seed: Optional[int] = 0, frame_stride: int = 1,
              deterministic: bool = True, engine_config=None) -> Dict:
-    """Returns {"episode_rewards", "episode_lengths", "successes", "frames"}; writes an animated GIF of all
-    episodes when gif_path is given (24 frames per second, the env's metadata rate)."""
+    """Returns {"episode_rewards", "episode_lengths", "successes", "targets_reachable", "frames"}; writes an animated GIF of
+    all episodes when gif_path is given (24 frames per second, the env's metadata rate).  targets_reachable: the fraction of
+    the episodes' targets the pointer can get within done_distance of at all (PioneerVectorEnv.target_reachable, one call per
+    reset) — what tells "did not reach" from "could not reach"."""
     device = torch.device(device)
     model, filt, cfg = load_policy(checkpoint, device)
     env = TimeLimit(PioneerKinematicEnv(device=device, mode=mode, engine_config=engine_config), max_episode_steps=max_episode_steps)
@@ -41,9 +43,10 @@ def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, g
     a_max = torch.from_numpy(env.action_space.high).to(device)
     gen = torch.Generator(device=device).manual_seed(0 if seed is None else seed)
     frames: List[np.ndarray] = []
-    rewards, lengths, successes = [], [], []
+    rewards, lengths, successes, reachable = [], [], [], []
     for _ in range(episodes):
         obs = env.reset()
+        reachable.append(bool(env.env._vec.target_reachable()[0].item()))
         total, steps, done, info = 0.0, 0, False, {}
         while not done:
             x = filt(torch.as_tensor(obs, dtype=torch.float32, device=device).unsqueeze(0))
@@ -63,4 +66,5 @@ def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, g
         from PIL import Image
         imgs = [Image.fromarray(f) for f in frames]
         imgs[0].save(gif_path, save_all=True, append_images=imgs[1:], duration=int(1000 * frame_stride / fps), loop=0)
-    return {"episode_rewards": rewards, "episode_lengths": lengths, "successes": successes, "frames": len(frames)}
+    return {"episode_rewards": rewards, "episode_lengths": lengths, "successes": successes,
+            "targets_reachable": float(np.mean(reachable)) if reachable else float("nan"), "frames": len(frames)}

@@ -226,6 +226,55 @@ class PioneerVectorEnv:
         self._chk(self.lib.pnr_get_link_states(self._h, _ptr(js), _ptr(res), self._stream()))
         return res
 
+    def jacobian(self, link=10, local_point=None, joint_state=None, out=None):
+        """calculateJacobian of link ``link`` (0..10, ``LINK_NAMES`` order; default robot:pointer) of every env, one launch
+        (pnr_get_jacobian): float32 ``[N, 6, 6]`` on the env's device.  Rows 0-2: world linear velocity of ``local_point`` (a
+        point in the link's frame, default its origin) per unit velocity of joint j (column j); rows 3-5: the link's world
+        angular velocity per unit joint velocity.  Columns of joints beyond the link are exactly 0.  ``joint_state``: as
+        ``link_states`` (``[N, 12]`` = q | qd, only q is read; None = the handle's own joints).  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        lp = None if local_point is None else (C.c_double * 3)(*(float(v) for v in local_point))
+        res = self._out(out, "out", (n, 6, 6))
+        self._chk(self.lib.pnr_get_jacobian(self._h, _ptr(js), int(link), lp, _ptr(res), self._stream()))
+        return res
+
+    def solve_ik(self, target=None, q_init=None, link=10, local_point=None, max_iterations=32, damping=1.0, max_step=0.5,
+                 tolerance=1e-3, out=None):
+        """calculateInverseKinematics (position only) for every env, one launch (pnr_solve_ik): joint angles inside the limits
+        that put ``local_point`` of ``link`` on ``target`` (``[N, 3]`` world positions; None = each env's own target), by the
+        damped-least-squares iteration of include/pioneer_amd.h from ``q_init`` (``[N, 6]``; None = the rest pose q = 0, from
+        which every target of the reachable inner box converges; random starts end in local minima at joint limits).
+        Returns ``(q [N, 6] float32, residual [N] float32, iterations [N] int32)``: residual is the distance left,
+        iterations == max_iterations where the tolerance was never met (the target is out of reach, or the start was bad).
+        ``out`` may carry preallocated ``q`` / ``residual`` / ``iterations`` tensors, written in place.  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        p = _lib.PnrIkParams()
+        self._chk(self.lib.pnr_ik_params_default(p))
+        p.link, p.max_iterations = int(link), int(max_iterations)
+        if local_point is not None:
+            for k in range(3):
+                p.local_point[k] = float(local_point[k])
+        p.damping, p.max_step, p.tolerance = float(damping), float(max_step), float(tolerance)
+        tgt = None if target is None else self._in(target, (n, 3), torch.float32, "target")
+        qi = None if q_init is None else self._in(q_init, (n, 6), torch.float32, "q_init")
+        out = out or {}
+        q = self._out(out, "q", (n, 6))
+        res = self._out(out, "residual", (n,))
+        its = self._out(out, "iterations", (n,), torch.int32)
+        self._chk(self.lib.pnr_solve_ik(self._h, p, _ptr(tgt), _ptr(qi), _ptr(q), _ptr(res), _ptr(its), self._stream()))
+        return q, res, its
+
+    def target_reachable(self, within=None):
+        """bool ``[N]``: can the pointer get within ``within`` (default the config's ``done_distance``) of the env's own target
+        without leaving the joint limits?  ``solve_ik()`` from the rest pose with all defaults; about 3 % of the reference's
+        target box (its far corners) cannot be reached, and such an episode can only end at the time limit.  True is exact; False
+        means "not reached from the rest pose", which for about one target in a hundred is a local minimum of that start."""
+        within = float(self.config.done_distance if within is None else within)
+        return self.solve_ik()[1] <= within
+
     def render_frames(self, render_config=None, joint_state=None, bodies=None, rgb=True, depth=False, segmentation=False, out=None,
                       light_direction=(0.4, 0.2, 1.0), ambient=0.45, diffuse=0.55, background=(1.0, 1.0, 1.0), target_rgba=None):
         """render('rgb_array') of every env in one launch (bullet_env.py:156-185 -> getCameraImage; pnr_render): the URDF's 14
