@@ -299,6 +299,16 @@ class DynOracle(COracle):
         self.lib.orc_dyn_aba_ext(self._one(e), _ptr(tau, C.c_double), C.c_double(gravity), _ptr(f, C.c_double), _ptr(qdd, C.c_double))
         return qdd
 
+    def aba_motor(self, tau, ades=None, tcap=0.0, gravity=0.0, fext=None, e=0):
+        """orc_dyn_aba_motor: the ABA with + clip(D_i ades[i], +-tcap) on joint i (the pd_inertia_scaled motor; tcap <= 0: no cap)."""
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        a = None if ades is None else np.ascontiguousarray(ades, dtype=np.float64)
+        f = None if fext is None else np.ascontiguousarray(fext, dtype=np.float64).reshape(DOF, 6)
+        qdd = np.empty(DOF)
+        self.lib.orc_dyn_aba_motor(self._one(e), _ptr(tau, C.c_double), _ptr(a, C.c_double), C.c_double(tcap), C.c_double(gravity),
+                                   _ptr(f, C.c_double), _ptr(qdd, C.c_double))
+        return qdd
+
     def motor_torque(self, r_ref, v_ref, q, qd):
         self.lib.orc_dyn_motor_torque.restype = C.c_double
         return self.lib.orc_dyn_motor_torque(C.byref(self.d), C.c_double(r_ref), C.c_double(v_ref), C.c_double(q), C.c_double(qd))

@@ -4,6 +4,15 @@ brings its velocity to rhs (VELOCITY: v*; POSITION: kp (q* - q) / h + qd + kd (v
 +-force, solved jointly over the chain.  Bullet parity is unpinned (its semantics are recalled, pybullet is not available):
 these tests check the law's own consequences — deadbeat velocities, the 0.9^m error decay of Bullet's default position gains,
 a saturated motor as a constant torque against the unchanged oracle — and that a batch computes each env as alone.
+
+The boxed solve itself (mass matrix, Cholesky, active set, pass cap) is compared with the float64 reference of
+tests/constraint_motor_ref.py on the input sets of tests/constraint_motor_cases.py, every env, at Q_TOL / QD_TOL, plus the
+deadbeat bound on joints that are free with margin (second half of this file; tests/test_constraint_motor_cpu.py asserts that
+those inputs bite).  Each of these tests prints its worst |dq|, |dqd| and |qd - rhs| per step and writes the scenario's worst
+values through tests/test_gpu_dynamics.py's _record_margin (keys cmotor_mixed, cmotor_subset, cmotor_skip10, cmotor_scaled).
+MEASURED VALUES: not recorded yet — these tests have not run on an MI355X; the first run on one should copy the cmotor_* values
+here and, where one is within 2x of the bar, say why (cond(M) x float32 first).
+Expected from a float32 emulation of the solve alone at cond(M) ~ 700 (median) .. 3 000: about 1e-6 rad/s.
 """
 import ctypes as C
 import math
@@ -270,3 +279,136 @@ def test_create_rejects_the_constraint_modes_as_the_step_law():
         c.control_mode = mode
         h = C.c_void_p()
         assert lib.pnr_create(c, 4, 0, 0, 0, C.byref(h)) == -1 and not h.value
+
+
+# ---- the boxed solve against the float64 reference (tests/constraint_motor_ref.py) ------------------------------------------
+# The input sets are tests/constraint_motor_cases.py's; tests/test_constraint_motor_cpu.py asserts on the reference that they
+# bite (every joint free and clamped on either side, mixed patterns, pass counts that differ inside a wave, wrong solvers off
+# by more than 10 QD_TOL on most envs).  The boxed solution is a Lipschitz-continuous function of its data and the scenarios
+# have no contacts: no env sits on a discontinuity, so EVERY env is compared.
+#
+# FREE_SLACK: a joint the reference calls free "with margin" must end the sub-step on rhs to the deadbeat bound, since dv = d
+# holds exactly for a free joint in any pattern.  The margin is the joint's own slack in velocity units, A_ii (F_i - |tau_i|):
+# the kernel decides free / clamped on float32 values of h tau = (M dv)_i, whose error is about cond(M) 2^-24 (cond(M) <= 3 000
+# on these inputs) of the velocity the joint's whole force adds in a sub-step (<= 1 rad/s here), i.e. <= 2e-4 rad/s; 1e-3 is
+# five times that.
+FREE_SLACK = 1e-3
+
+
+def _set_motors(env, motors):
+    L = _lib()
+    modes = {"velocity_constraint": L.CONTROL_VELOCITY_CONSTRAINT, "position_constraint": L.CONTROL_POSITION_CONSTRAINT}
+    for j, m in enumerate(motors):
+        if m is None:
+            continue                                                  # uncommanded: the env-wide law on the command state
+        mode = modes.get(m["kind"])
+        if mode is None:
+            mode = L.CONTROL_VELOCITY if m["control_mode"] == 1 else L.CONTROL_POSITION
+        env.set_joint_motor(j, mode, **{k: v for k, v in m.items() if k not in ("kind", "control_mode")})
+
+
+def _against_reference(case, n):
+    """Runs an input set's re-randomised world steps on the engine and on the reference; asserts the project's bar on q and qd
+    of every env and the deadbeat bound on the joints that are free with margin; records the worst deviations."""
+    import constraint_motor_cases as cases
+    import constraint_motor_ref as ref
+    from test_gpu_dynamics import _record_margin
+    c = cases.CASES[case]
+    env = make(n, gravity=cases.GRAVITY, frame_skip=c["frame_skip"], seed=c["seed"], **c["engine"])
+    orc = cases.make_oracle(case, n)
+    assert np.array_equal(env.a_max, orc.a_max)
+    for act in cases.command_actions(case, n, env.a_max):
+        env.vector_step(torch.from_numpy(act).cuda())
+    _set_motors(env, c["motors"])
+    # the engine's command state and per-env draws are the ones the CPU tests' conditions were asserted on
+    words = env.get_state().cpu().numpy().view(np.uint32)
+    assert np.array_equal(words[:21], orc.state_words()[:21]) and np.array_equal(dyn(env)[12:35], orc.dyn_words()[12:35])
+    if c.get("command_steps"):
+        st = env.state_dict()
+        assert np.all(st["r"] != 0) and np.all(st["v"] != 0), "the command state must have moved off zero"
+    orc.load_state_words(words)
+    worst_q = worst_qd = worst_free = 0.0
+    tight = 0
+    for step in range(c["steps"]):
+        load(env, *cases.states(case, n, step))
+        orc.load_dyn_words(dyn(env))
+        infos = ref.world_step(orc, c["motors"], c["frame_skip"])
+        env.world_step()
+        d = dyn(env).astype(np.float64)
+        q, qd = d[0:6].T, d[6:12].T
+        dq, dqd = np.abs(q - orc.dstate["q"]).max(), np.abs(qd - orc.dstate["qd"]).max()
+        worst_q, worst_qd = max(worst_q, float(dq)), max(worst_qd, float(dqd))
+        print(f"cmotor_{case} n={n} step={step}: |dq| {dq:.3e} |dqd| {dqd:.3e}")
+        assert all(np.all(i["consistent"] == 1) for i in infos)
+        assert dq <= Q_TOL and dqd <= QD_TOL, (case, n, step, dq, dqd)
+        last = infos[-1]
+        S = last["S"]
+        rhs = last["rhs"][:, S]
+        free = (last["pattern"] == 0) & (last["slack"] >= FREE_SLACK) & (orc.dstate["qd"][:, S] == last["qd_plus"][:, S])
+        err = np.abs(qd[:, S] - rhs) / np.maximum(1.0, np.abs(rhs))
+        tight += int(free.sum())
+        if free.any():
+            worst_free = max(worst_free, float(err[free].max()))
+            print(f"cmotor_{case} n={n} step={step}: free joints {int(free.sum())}, |qd - rhs| {err[free].max():.3e}")
+            assert err[free].max() <= 1e-5, (case, n, step, err[free].max())
+    assert tight >= n, "the deadbeat bound must have been asserted on a joint per env at least"
+    env.close()
+    if n == max(k for s, k in CMOTOR_SETS if s == case):
+        _record_margin("cmotor_" + case, worst_q, worst_qd)
+    return worst_q, worst_qd, worst_free
+
+
+CMOTOR_SETS = [("mixed", 1), ("mixed", 37), ("mixed", 64), ("mixed", 1000), ("subset", 37), ("subset", 1000), ("skip10", 64), ("scaled", 64)]
+
+
+@pytest.mark.parametrize("n", [1, 37, 64, 1000])
+def test_mixed_velocity_motors_solve_the_boxed_problem(n):
+    """Six velocity motors whose forces are of the size their targets need: free, +F and -F joints share one solve in most envs
+    (the r_c = h tcl - H_cf d_f coupling), joints are clamped and freed again, and the lanes of a wave need 3 to 8 passes."""
+    _against_reference("mixed", n)
+
+
+@pytest.mark.parametrize("n", [37, 1000])
+def test_subset_with_position_motors_next_to_pd_and_uncommanded_joints(n):
+    """S = {0, 2, 3, 5}: joints 0 and 3 on position motors with gains of their own and a maxVelocity that caps rhs in 40-70 % of
+    the envs, joint 1 on a per-joint PD motor, joint 4 uncommanded on the env-wide law, tracking a command state that three
+    vector steps moved off zero."""
+    _against_reference("subset", n)
+
+
+def test_ten_sub_steps_with_the_pattern_changing_between_them():
+    """frame_skip 10, free-running through the reference's ten sub-steps: the motors pull the joints onto their targets within
+    the step, so the pattern changes between sub-steps in most envs."""
+    _against_reference("skip10", 64)
+
+
+def test_constraint_motors_next_to_the_inertia_scaled_law():
+    """pd_inertia_scaled (PHYS bit 1 of the CMOTOR instantiation): constraint motors on joints 0, 2, 5, the env-wide
+    acceleration-level law, scaled and capped inside the ABA, on joints 1, 3, 4."""
+    _against_reference("scaled", 64)
+
+
+def test_joint_limits_hold_against_a_motor_and_release_inward():
+    """Joints that start on a limit with an ample motor pushing outward stay on it with qd == 0; pushing inward they leave at
+    rhs.  Even envs start on the upper limits, odd envs on the lower ones; the targets alternate in sign."""
+    L = _lib()
+    n = 64
+    env = make(n, gravity=9.81, frame_skip=1, seed=8, randomize=True)
+    hi, lo = env.r_hi.astype(np.float64), env.r_lo.astype(np.float64)
+    q0 = np.where((np.arange(n) % 2 == 0)[:, None], hi, lo)
+    load(env, q0)
+    q0 = dyn(env)[0:6].T.astype(np.float64)
+    assert np.array_equal(q0, np.where((np.arange(n) % 2 == 0)[:, None], hi, lo))
+    vs = np.array([0.5, -0.5, 0.4, -0.6, 0.8, -1.0])
+    for j in range(6):
+        env.set_joint_motor(j, L.CONTROL_VELOCITY_CONSTRAINT, target_velocity=vs[j], max_force=AMPLE)
+    outward = ((q0 == hi) & (vs > 0)) | ((q0 == lo) & (vs < 0))
+    assert outward.any(axis=0).all() and (~outward).any(axis=0).all()
+    env.world_step()
+    d = dyn(env).astype(np.float64)
+    q, qd = d[0:6].T, d[6:12].T
+    assert np.array_equal(q[outward], q0[outward]) and np.all(qd[outward] == 0.0)
+    want = np.broadcast_to(vs, (n, 6))
+    assert np.all(np.abs(qd - want)[~outward] <= 1e-5 * np.maximum(1.0, np.abs(want[~outward])))
+    assert np.abs(q - (q0 + H * want))[~outward].max() <= 3e-7 + H * 1e-5
+    env.close()
