@@ -457,10 +457,14 @@ const char* pnr_last_error(pnr_handle h) { return h ? h->err : g_err; }
 // step kernels are persistent over tiles: at most 8 one-wave workgroups per CU (256 CUs)
 // Persistent grid of one-wave workgroups.  One launch per step: 2 048 (two waves per SIMD; with a single tile
 // per wave the second wave is what overlaps one tile's stores with another's arithmetic).  Long rollouts
-// (pnr_rollout, T >= 8): 1 024 = ONE wave per SIMD — each wave's stores of step t drain under its own step
-// t + 1, and a second wave on the SIMD only contends for issue slots (6.5-7.2 vs 7.2-7.5 us per 65 536-env
+// (pnr_rollout, T >= 8): 1 024 = ONE wave per SIMD — a second wave on the SIMD only contends for issue slots
+// (a wave's own flush does NOT drain under its next step: the t loop's back edge waits vmcnt(0) for the prefetched
+// action, which is queued behind the flush; DESIGN_HISTORY.md) (6.5-7.2 vs 7.2-7.5 us per 65 536-env
 // step at T = 32; 768 and 1 536 are worse than either; at T = 2, 4 the 2 048 grid still wins: 8.7 / 8.1 vs
 // 10.0 / 8.6 us).  The -DPNR_DIAG_BUILD=1 variant reads overrides from the environment (grid-cap experiments).
+// Which form of step_kernel runs is a pure function of (T, n): the ONE-PASS instantiation (a wave = one tile, one step; no
+// loops, no prefetch) when T == 1 and grid_for(n) <= the single-step cap of 2 048 waves, i.e. pnr_step at n <= 65 536, where
+// every tile has a wave of its own; the general form for everything else (pnr_rollout, batches above 65 536 envs).
 static inline unsigned step_grid_for(long long n, int T)
 {
 #if PNR_DIAG_BUILD
@@ -474,6 +478,7 @@ static inline unsigned step_grid_for(long long n, int T)
     const unsigned c = (unsigned)(T >= 8 ? cap_roll : cap);
     return tiles < c ? tiles : c;
 }
+static inline bool step_one_pass(long long n, int T) { return T == 1 && step_grid_for(n, T) == grid_for(n); }
 
 int pnr_reset(pnr_handle h, const uint8_t* mask, const float* joint_pos, const float* target_pos,
               float* obs_out, void* stream)
@@ -520,7 +525,9 @@ static int launch_step(pnr_handle h, int T, const float* actions, float* obs, fl
     const float mvr = (float)h->cfg.max_v_to_r;
     with_bool(oem, [&](auto O) { with_bool(aem, [&](auto A) {
         if (h->cfg.mode != PNR_MODE_DYNAMIC) {
-            hipLaunchKernelGGL((step_kernel<O(), A()>), grid, block, 0, st, P.state, P.actions, P.n, P.dt, P.eps, mvr, P);
+            with_bool(step_one_pass(h->n, T), [&](auto S) {
+                hipLaunchKernelGGL((step_kernel<O(), A(), S()>), grid, block, 0, st, P.state, P.actions, P.n, P.dt, P.eps, mvr, P);
+            });
             return;
         }
         // one launch: the dynamics kernels run the sub-steps one env per lane, then finish each step (reward / TimeLimit /

@@ -63,12 +63,22 @@ __device__ __forceinline__ void store_outcome(const KParams& P, const Outcome& c
 // own tiles, no barrier — so this only changes what the dispatcher places: with four-wave workgroups a rollout's 1 024 waves are 256
 // workgroups = exactly one per CU, one wave per SIMD, where 1 024 one-wave workgroups landed unevenly (A/B r03 in one run, twice:
 // 7.36 -> 6.33 us per rollout step at 65 536 envs; single steps unchanged, 10.38 vs 10.31 us).
+// Two forms of one body (which runs when: step_one_pass, pnr_api.hip).  The GENERAL form is persistent: a wave strides over tiles
+// and loops over the T steps of a launch, with the next tile's and the next step's loads requested ahead of the stores.  ONE_PASS
+// folds both loops and the prefetch blocks away — a wave is one tile and one step, T is the literal 1 — for pnr_step at
+// n <= 65 536, where every tile has a wave of its own, all 2 048 waves walk load / compute / emit / flush in lock-step and the head
+// is paid in full.  What the loops cost there is everything LLVM hoists in front of them (the reset path's Philox key schedule,
+// prefetch addresses, rollout strides): gfx950 listing, <true, true>: 447 instructions between the first loads and the integrator,
+// 193 VGPRs, 106 SGPRs and 92 v_writelane / v_readlane scalar spills in the general form; 48 instructions (the tile's 36 constant
+// entries among them), 119 VGPRs, 74 SGPRs and no spill in the one-pass form.  Both forms request the three state planes and the
+// first action back to back, fetch P's scalars and write the constants behind them, and wait first for plane 0 alone; the new
+// action is waited for where the state store consumes it.
 #ifndef PNR_STEP_WAVES
 #define PNR_STEP_WAVES 4
 #endif
 constexpr int kStepWaves = PNR_STEP_WAVES;
 
-template <bool OBS_EM, bool ACT_EM>
+template <bool OBS_EM, bool ACT_EM, bool ONE_PASS = false>
 __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __restrict__ state_, const float* __restrict__ actions_,
                                                      const long long n_, const double dt_, const double eps_,
                                                      const float max_v_to_r_, const KParams P)
@@ -107,18 +117,34 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
 
     const long long tstride = (long long)gridDim.x * kStepWaves;
     long long tix = (long long)blockIdx.x * kStepWaves + (threadIdx.x >> 6);
-    RawState raw = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-    float act0[kJpl] = {0.f, 0.f, 0.f};
-    if (tix < ntiles && tix * kEnvsPerWave + el < n) {
-        raw = load_state_raw(state_, n, 2 * tix * kEnvsPerWave + lane);
-        load_act0(tix * kEnvsPerWave + el, act0);
+    if (tix >= ntiles) return;              // a whole wave past the last tile (no barrier follows in this kernel)
+
+    // The head of the launch.  Every wave of a launch is here at the same time and HBM idles until the first flush, so what
+    // stands between kernel entry and the integrator is paid in full: the three state planes and the first action are requested
+    // back to back, with no branch round them (the join's register copies would wait for the first plane before the last load
+    // is out): a lane past the end reads the tile's first env again — in bounds, and nothing of such a lane is ever stored.
+    RawState raw;
+    float act0[kJpl];
+    {
+        const bool in = tix * kEnvsPerWave + el < n;
+        raw = load_state_raw(state_, n, 2 * tix * kEnvsPerWave + (in ? lane : p));
+        load_act0(tix * kEnvsPerWave + (in ? el : 0), act0);
+        __builtin_amdgcn_sched_barrier(0);  // nothing that needs a loaded value is scheduled in between
     }
     bool first_tile = true;
 
     // the 36 constant obs entries of this lane's tile slots: once per kernel, under the load latency
     obs_tile_const<OBS_EM>(K, tile, el, p);
+    if (ONE_PASS) {
+        // .. and so are the common path's words of P: asked for here, they are scalar loads issued before the first vmcnt wait;
+        // the barrier keeps the integrator's converts (and with them that wait) below the constants
+        asm volatile("" :: "s"(P.obs), "s"(P.reward), "s"(P.done), "s"(P.trunc), "s"(P.info), "s"(P.max_steps), "s"(P.auto_reset),
+                     "s"(P.pot_m), "s"(P.pot_s), "s"(P.penalty), "s"(P.award_done), "s"(P.done_dist), "s"(P.done_dist_d));
+        __builtin_amdgcn_sched_barrier(0);
+    }
 
-    for (; tix < ntiles; tix += tstride) {
+    const int T = ONE_PASS ? 1 : P.T;
+    for (; tix < ntiles; tix += tstride) {  // ONE_PASS: left at the end of the first pass, i.e. a plain `if` (true here)
     const long long tile0 = tix * kEnvsPerWave;
     const long long e = tile0 + el;
     const long long rec = 2 * tile0 + lane; // state record index (2e + p)
@@ -126,11 +152,11 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
     const int nvalid = (int)((n - tile0) < kEnvsPerWave ? (n - tile0) : kEnvsPerWave);
 
     LaneState s;
-    unpack_state(raw, p, s);                // all-zero records for lanes past the end
+    unpack_state(raw, p, s);                // lanes past the end: the tile's first env (first tile) or all-zero records
     float act_first[kJpl] = {act0[0], act0[1], act0[2]};
 
-    // prefetch the next tile
-    {
+    // prefetch the next tile (ONE_PASS: there is none)
+    if (!ONE_PASS) {
         const long long nt = tix + tstride;
         if (nt < ntiles && nt * kEnvsPerWave + el < n) {
             raw = load_state_raw(state_, n, 2 * nt * kEnvsPerWave + lane);
@@ -140,15 +166,19 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
         }
     }
 
-    if (diag & 16) { if (valid) P.reward[e] = s.pot; continue; }   // launch + state-load floor
+    if (diag & 16) {                                               // launch + state-load floor
+        if (valid) P.reward[e] = s.pot;
+        if (ONE_PASS) break;                                       // .. the one-pass form's `continue`
+        continue;
+    }
 
-    for (int t = 0; t < P.T; ++t) {
+    for (int t = 0; t < T; ++t) {
         {
             // -- action of this step (this lane's three joints) ----------------------
             // this step's action was requested one step (or one tile) ago; request the next one now,
             // ahead of this step's obs stores (VMEM ops of a wave retire in order)
             float act[kJpl] = {act_first[0], act_first[1], act_first[2]};
-            if (t + 1 < P.T && valid) {
+            if (t + 1 < T && valid) {
                 const float* A = actions_ + (long long)(t + 1) * n * kDof;
                 if (ACT_EM) {
                     const float* a3 = A + e * kDof + kJpl * p;
@@ -184,13 +214,14 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
         }
 
         // state goes out before the obs is packed: its stores drain under the LDS emit
-        if (t == P.T - 1 && valid && !diag_nostate) store_state(state_, n, rec, p, s);
+        if (t == T - 1 && valid && !diag_nostate) store_state(state_, n, rec, p, s);
 
         // -- observe() ----------------------------------------------------------------
         if (t > 0 || !first_tile) wave_lds_sync();   // previous flush done before the tile is rewritten
         obs_tile_out<OBS_EM>(K, s, q, tile, el, p, lane, P.obs + (long long)t * n * kObsDim, tile0, n, nvalid, !diag_noemit, !diag_noflush);
     }
     first_tile = false;
+    if (ONE_PASS) break;
     }   // tile loop
 }
 
