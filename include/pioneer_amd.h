@@ -43,7 +43,7 @@ extern "C" {
  *   5  new entry points pnr_world_step, pnr_set_joint_motor, pnr_build_fingerprint; `planes` == 2 now means two SCALED FP16 planes
  *      (was: two bf16 planes) in every pnr_mlp_* call; pnr_mlp_train_step checks every argument before its first launch and
  *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
- *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik */
+ *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -394,6 +394,55 @@ typedef struct pnr_ik_params {
 int pnr_ik_params_default(pnr_ik_params* p);
 int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, const float* q_init,
                  float* q_out, float* residual_out, int32_t* iterations_out, void* stream);
+
+/*
+ * calculateInverseDynamics for every env, one launch: the joint torques of
+ *     tau = M(q) qdd + C(q, qd) qd + G(q)
+ * on the rigid-body model the dynamics mode steps (six merged moving bodies; oracle/pnr_dyn_oracle.h describes it), by
+ * recursive Newton-Euler.  Gravity is the handle's pnr_config.gravity along -z.
+ *   joint_state  [num_envs][12] float32 (q[6] | qd[6]), 16-byte aligned, read only, as pnr_get_link_states; NULL = the handle's
+ *                own joints (dynamics mode the simulated q, qd; kinematic mode the env's r and v)
+ *   joint_accel  [num_envs][6] float32 qdd, 16-byte aligned, read only; NULL = qdd 0: the bias forces C qd + G (with qd = 0 as
+ *                well: the gravity torques G(q))
+ *   flags        PNR_INVDYN_NO_GRAVITY leaves G(q) out.  PNR_INVDYN_JOINT_LOSSES adds the engine's joint damping and smoothed
+ *                Coulomb friction at qd, damping_i qd_i + friction_i qd_i / sqrt(qd_i^2 + 0.05^2): the torque is then exactly
+ *                what a sub-step of the engine needs to realise qdd away from contacts and joint limits.  Without it the call is
+ *                PyBullet's: no damping, friction, contacts, motors or limits.  Any other bit: PNR_ERR_INVALID.
+ *   out          [num_envs][6] float32 env-major, 16-byte aligned; nothing past num_envs * 6 floats is written
+ * Link masses: on a dynamics-mode handle the per-env link scales of its dyn state (pnr_get_dyn_state words 12-22) and, for the
+ * losses, its per-env friction and damping (words 23-34), whatever the joint source; on a kinematic-mode handle every scale is 1
+ * and the losses use pnr_config.joint_friction / joint_damping.  PNR_ERR_INVALID before the first pnr_reset (or pnr_set_state /
+ * pnr_set_dyn_state): on a dynamics-mode handle always (the scales do not exist yet), on a kinematic-mode one with a NULL
+ * joint_state.  PNR_ERR_INVALID, nothing launched and no output touched, also for a null handle or out, misaligned pointers or
+ * unknown flag bits.  Non-finite input gives non-finite output, unchecked.  float32 arithmetic, asynchronous on `stream`, no
+ * allocation: capturable into a graph.  Parity unpinned.
+ */
+#define PNR_INVDYN_NO_GRAVITY   1   /* leave G(q) out */
+#define PNR_INVDYN_JOINT_LOSSES 2   /* add the engine's joint damping and smoothed Coulomb friction at qd */
+int pnr_inverse_dynamics(pnr_handle h, const float* joint_state, const float* joint_accel, int32_t flags, float* out, void* stream);
+
+/*
+ * calculateMassMatrix for every env, one launch: the joint-space inertia M(q) of the same model (composite rigid bodies).
+ *   joint_state  as pnr_inverse_dynamics; only q is read
+ *   out          [num_envs][6][6] float32 row-major, 16-byte aligned: the full symmetric matrix, both triangles written from one
+ *                computed value (out[i][j] == out[j][i] bit for bit); nothing past num_envs * 36 floats is written
+ * Joint sources, link masses, refusals and conventions as pnr_inverse_dynamics.
+ */
+int pnr_mass_matrix(pnr_handle h, const float* joint_state, float* out, void* stream);
+
+/*
+ * pnr_world_step on a dynamics-mode handle with a joint torque per env (PyBullet's TORQUE_CONTROL).
+ *   joint_torques  [num_envs][6] float32 env-major, caller-owned device memory, 16-byte aligned, read only.  The torque is added
+ *                  to each joint's torque in every sub-step of THIS call, after the motor law's own cap and before damping and
+ *                  friction; it lasts this call only and must be given again for the next step, as in Bullet.
+ * The joints' motors stay as pnr_set_joint_motor left them and act as well: a caller who wants pure torque control first gives
+ * the joints zero gains (PNR_CONTROL_VELOCITY with velocity_gain 0, the PD law), as one disables Bullet's default motor with
+ * force 0.  PNR_ERR_UNSUPPORTED: a kinematic-mode handle; a motor table that holds a constraint motor (PNR_CONTROL_*_CONSTRAINT:
+ * torque input together with the boxed solve is not built).  PNR_ERR_INVALID: a null handle, NULL or misaligned joint_torques,
+ * before the first pnr_reset.  Nothing is launched and the state is untouched on every refusal.  Asynchronous on `stream`, no
+ * allocation: capturable into a graph.  Parity unpinned.
+ */
+int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* stream);
 
 /*
  * render('rgb_array') for every env in one launch (bullet_env.py:156-185 -> getCameraImage): one camera shared by all envs,

@@ -36,6 +36,7 @@ DYN_STATE_WORDS = 36
 NUM_LINKS = 11          # pnr_get_link_states: link records per env (Bullet's link_index order, model.LINKS[1:])
 LINK_STATE_DIM = 13     # position[3], quaternion x y z w [4], linear velocity[3], angular velocity[3]
 JACOBIAN_DIM = 36       # pnr_get_jacobian: 6 rows (linear xyz, angular xyz) x 6 joint columns per env
+INVDYN_NO_GRAVITY, INVDYN_JOINT_LOSSES = 1, 2      # pnr_inverse_dynamics flags (PNR_INVDYN_*)
 
 PNR_OK = 0
 ENV_MAJOR, FEATURE_MAJOR = 0, 1
@@ -158,6 +159,7 @@ SIGNATURES = {
     "pnr_rollout": (C.c_int, [_VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pnr_observe": (C.c_int, [_VP, _VP, _VP]),
     "pnr_world_step": (C.c_int, [_VP, _VP, _VP]),
+    "pnr_world_step_torques": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_joint_motor": (C.c_int, [_VP, C.c_int32, C.c_int32] + [C.c_double] * 6),
     "pnr_get_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_state": (C.c_int, [_VP, _VP, _VP]),
@@ -165,6 +167,8 @@ SIGNATURES = {
     "pnr_set_dyn_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_get_link_states": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_get_jacobian": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_double * 3), _VP, _VP]),
+    "pnr_inverse_dynamics": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
+    "pnr_mass_matrix": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_ik_params_default": (C.c_int, [C.POINTER(PnrIkParams)]),
     "pnr_solve_ik": (C.c_int, [_VP, C.POINTER(PnrIkParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
@@ -199,7 +203,7 @@ SIGNATURES = {
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 UNITS = {
     "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_links.h",
-                    "pnr_render.h", "pnr_ik.h"],
+                    "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_sampler.h"],
 }
 SOURCES = sorted({f for deps in UNITS.values() for f in deps})      # every file a unit includes: what _stale() watches

@@ -43,6 +43,7 @@
 #include "pnr_links.h"
 #include "pnr_render.h"
 #include "pnr_ik.h"
+#include "pnr_invdyn.h"
 
 // =====================================================================================
 // host side
@@ -623,6 +624,28 @@ int pnr_world_step(pnr_handle h, float* joint_state, void* stream)
     return PNR_OK;
 }
 
+int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (h->cfg.mode != PNR_MODE_DYNAMIC)
+        return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_torques: joint torques exist in dynamics mode only");
+    if (!joint_torques) return fail(h, PNR_ERR_INVALID, "pnr_world_step_torques: null joint_torques");
+    if (!aligned16(joint_torques)) return fail(h, PNR_ERR_INVALID, "pnr_world_step_torques: joint_torques must be 16-byte aligned");
+    if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_world_step_torques before the first pnr_reset (or pnr_set_state)");
+    for (int i = 0; i < kDof; ++i)
+        if (h->motors.kind[i] != kMotorPD)
+            return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_torques: joint %d is on a constraint motor (torque input with the boxed solve is not built)", i);
+    DeviceGuard g(h->device);
+    const DynParams& D = h->dbase;
+    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
+    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) {
+        hipLaunchKernelGGL((dyn_world_torque_kernel<true, C()>), grid, dim3(kWave), 0, (hipStream_t)stream, h->state, h->dyn,
+                           (long long)h->n, joint_torques, D, h->motors);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
 }  // extern "C"
 
 int pnr_env_rollout_params(pnr_handle h, pnr::KParams* out, float* max_v_to_r, int* device)
@@ -757,6 +780,54 @@ int pnr_get_jacobian(pnr_handle h, const float* joint_state, int32_t link, const
     with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
         hipLaunchKernelGGL(jacobian_kernel<S()>, grid, block, 0, st, joint_state ? joint_state : h->dyn,
                            src == kLinkSrcKin ? h->state : nullptr, out, (long long)h->n, P);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+// the checks pnr_inverse_dynamics and pnr_mass_matrix share (nothing launched, nothing written on failure)
+static int check_invdyn_call(pnr_handle h, const char* call, const float* joint_state, const float* joint_accel, const float* out)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!out) return fail(h, PNR_ERR_INVALID, "%s: null out", call);
+    if (!aligned16(out) || !aligned16(joint_state) || !aligned16(joint_accel))
+        return fail(h, PNR_ERR_INVALID, "%s: out, joint_state and joint_accel must be 16-byte aligned", call);
+    // a dynamics-mode handle's link scales are drawn by the first reset: no model before it, whatever the joint source
+    if (h->dyn ? !(h->ready || h->dyn_set) : (!joint_state && !h->ready))
+        return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)", call);
+    return PNR_OK;
+}
+
+int pnr_inverse_dynamics(pnr_handle h, const float* joint_state, const float* joint_accel, int32_t flags, float* out, void* stream)
+{
+    if (const int rc = check_invdyn_call(h, "pnr_inverse_dynamics", joint_state, joint_accel, out)) return rc;
+    if (flags & ~(PNR_INVDYN_NO_GRAVITY | PNR_INVDYN_JOINT_LOSSES))
+        return fail(h, PNR_ERR_INVALID, "pnr_inverse_dynamics: unknown flags 0x%x", (unsigned)flags);
+    DeviceGuard g(h->device);
+    const int src = link_source(h, joint_state);
+    InvDynArgs A;
+    A.src = joint_state ? joint_state : h->dyn;
+    A.state = src == kLinkSrcKin ? h->state : nullptr;
+    A.dyn = h->dyn; A.accel = joint_accel; A.out = out; A.n = h->n;
+    A.gravity = (flags & PNR_INVDYN_NO_GRAVITY) ? 0.f : (float)h->cfg.gravity;
+    A.loss_gain = (flags & PNR_INVDYN_JOINT_LOSSES) ? 1.f : 0.f;
+    A.damping0 = (float)h->cfg.joint_damping; A.friction0 = (float)h->cfg.joint_friction;
+    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
+        hipLaunchKernelGGL(inverse_dynamics_kernel<S()>, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream, A);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+int pnr_mass_matrix(pnr_handle h, const float* joint_state, float* out, void* stream)
+{
+    if (const int rc = check_invdyn_call(h, "pnr_mass_matrix", joint_state, nullptr, out)) return rc;
+    DeviceGuard g(h->device);
+    const int src = link_source(h, joint_state);
+    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
+        hipLaunchKernelGGL(mass_matrix_kernel<S()>, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream,
+                           joint_state ? joint_state : h->dyn, src == kLinkSrcKin ? h->state : nullptr, (const float*)h->dyn, out,
+                           (long long)h->n);
     });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;

@@ -885,11 +885,13 @@ __device__ __forceinline__ void dyn_lane_load(const DynLead& in, long long base,
 // WORLD (pnr_world_step): the sub-steps alone — no command integration, no teleport — with the per-joint motor table W.
 // CMOTOR (WORLD only): W holds constraint motors as well; their joints get no torque of the table's law, and motor_constraints
 // adds their boxed solve to each sub-step's accelerations.
-template <int PHYS, bool WORLD = false, bool CMOTOR = false>
+// TORQUE (WORLD only, pnr_world_step_torques): tau_ext[6], the caller's joint torques of this call, are added to each joint's
+// torque in every sub-step, after the motor law's own cap and before damping and friction (PyBullet's TORQUE_CONTROL).
+template <int PHYS, bool WORLD = false, bool CMOTOR = false, bool TORQUE = false>
 __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, float (&a)[kDof], float (&v)[kDof],
                                          float (&r)[kDof], float (&q)[kDof], float (&qd)[kDof], const float (&sc)[kNumLinks],
                                          const float (&fric_)[kDof], const float (&damp_)[kDof], const float (&act)[kDof],
-                                         const JointMotorTable* W = nullptr)
+                                         const JointMotorTable* W = nullptr, const float* tau_ext = nullptr)
 {
     if constexpr (!WORLD) {
 #pragma unroll
@@ -945,6 +947,7 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
             if constexpr (CMOTOR) {
                 if (W->kind[i] != kMotorPD) { ades[i] = 0.f; tq = 0.f; }
             }
+            if constexpr (TORQUE) tq += tau_ext[i];
             tq -= damp[i] * qd[i];
             tq -= fric[i] * qd[i] * __builtin_amdgcn_rsqf(qd[i] * qd[i] + kFrictionEps * kFrictionEps);
             tau[i] = tq;

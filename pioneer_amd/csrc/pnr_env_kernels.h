@@ -612,6 +612,42 @@ __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restri
     for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
 }
 
+// pnr_world_step_torques: the same step with the lane's six joint torques (tau_ext [n][6], env-major, 24 B per env, 8-byte
+// aligned since the buffer is 16-byte aligned) loaded with everything else, before the sub-step loop, and handed to
+// dyn_core<.., TORQUE = true>.  PD motors only: the host refuses a table that holds a constraint motor.  A kernel of its own,
+// with the load text repeated: with both kernels routed through one shared device function, dyn_world_kernel's scalar address
+// arithmetic came out two instructions shorter than before, and its instructions are required not to move.
+template <bool RAND, int PHYS>
+__global__ __launch_bounds__(kWave) void dyn_world_torque_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
+                                                                 const float* __restrict__ tau_ext, const DynParams D,
+                                                                 const JointMotorTable W)
+{
+    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
+    if (e >= n) return;
+    float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
+    const long long n2 = 2 * n;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const RawState k = {state[2 * e + p], state[n2 + 2 * e + p], state[2 * n2 + 2 * e + p]};
+        unpack_record(k, a + 3 * p, v + 3 * p, r + 3 * p);
+    }
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) {
+        q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
+        fric[i] = dyn[(long long)(kDynFric + i) * n + e]; damp[i] = dyn[(long long)(kDynDamp + i) * n + e];
+        act[i] = 0.f;
+    }
+#pragma unroll
+    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
+    const float2* t2 = reinterpret_cast<const float2*>(tau_ext) + 3 * e;
+    const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
+    tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
+    const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
+    dyn_core<PHYS, true, false, true>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &W, tx);
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
+}
+
 // The same call on a kinematic-mode handle: there is no simulated state, the caller holds the joints as Bullet would after
 // resetJointState(position, velocity) — js [n][12] = q[6] | qd[6] — and with no gravity, no motor and no collision shapes
 // (the reference's URDF and defaults) frame_skip x stepSimulation carries each joint on at its velocity:

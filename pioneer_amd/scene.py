@@ -22,6 +22,9 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   created body never touches it: in kinematic mode a body is a record (``items_by_name``), as inert as in the reference.  In dynamics
   mode a body with a collision shape becomes a static scene body of the engine (``EngineConfig.scene``; the handle is rebuilt with the
   env's state and the joints' motors carried over).  ``mass > 0`` asserts: moving bodies are not modelled (the reference never creates one).
+* ``control_torque(torque)`` (setJointMotorControl2 with TORQUE_CONTROL; the reference's Joint has no such method, Bullet does):
+  dynamics mode with the PD motors: the joint's torque for the next ``world.step()`` alone (``pnr_world_step_torques``), next to its
+  motor; kinematic mode and ``joint_motor == "constraint"`` raise.
 * ``world.step()``: ``frame_skip`` × ``stepSimulation`` = ONE engine launch (``pnr_world_step``), nothing on the host.  Dynamics
   mode: the articulated-body sub-steps (gravity, contacts with the scene's bodies, limits, every joint's motor) and nothing else —
   no command integration, reward or observation.  Kinematic mode: each joint carries on at the velocity it was reset with
@@ -184,6 +187,18 @@ class Joint:
         mode = _lib.CONTROL_VELOCITY_CONSTRAINT if self._constraint() else _lib.CONTROL_VELOCITY
         self._set_motor(mode, None, velocity, None, None, max_force, None)
 
+    def control_torque(self, torque: float):
+        """setJointMotorControl2(TORQUE_CONTROL, force=torque): this joint's torque for the NEXT ``world.step()`` only (the step
+        applies the recorded torques through ``world_step(joint_torques=...)`` and clears them).  It is added to what the joint's
+        motor gives, so pure torque control first gives the joint zero gains on the engine's PD law
+        (``vec.set_joint_motor(j, CONTROL_VELOCITY, target_velocity=0, velocity_gain=0)``), as one disables Bullet's default
+        motor.  Dynamics mode with the PD motors only."""
+        if not self._dynamic():
+            raise _lib.PnrError(-5, "Joint.control_torque: joint torques exist in dynamics mode only")
+        if self._constraint():
+            raise _lib.PnrError(-5, "Joint.control_torque: not built together with joint_motor=\"constraint\" (the boxed solve)")
+        self._env.world._torques[self.index] = float(torque)
+
 
 class Scene:
     def __init__(self, env):
@@ -264,6 +279,7 @@ class World:
         self._env = env
         sc = env.simulation_config
         self.timestep, self.frame_skip, self.gravity_force = sc.timestep, sc.frame_skip, sc.gravity
+        self._torques: Dict[int, float] = {}                                   # Joint.control_torque: joint -> torque of the next step
 
     @property
     def step_time(self) -> float:
@@ -272,4 +288,9 @@ class World:
     def step(self):
         """frame_skip x stepSimulation: ONE launch of the engine (pnr_world_step), no host arithmetic."""
         vec = self._env._vec
+        if self._torques:                                                      # recorded for this step alone (TORQUE_CONTROL)
+            tau = torch.tensor([[self._torques.get(j, 0.0) for j in range(6)]], dtype=torch.float32, device=vec.device)
+            self._torques = {}
+            vec.world_step(joint_torques=tau)
+            return
         vec.world_step(None if vec.engine_config.mode == "dynamic" else self._env.scene._bullet)

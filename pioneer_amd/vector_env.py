@@ -196,12 +196,48 @@ class PioneerVectorEnv:
                                        self._stream()))
         return obs, rew, done, trunc
 
-    def world_step(self, joint_state=None):
+    def world_step(self, joint_state=None, joint_torques=None):
         """World.step() alone (bullet_scene.py:273-275; pnr_world_step): the simulator's sub-steps and nothing else.  Dynamics mode:
-        ``joint_state`` is None (the handle's q, qd move); kinematic mode: the caller's float32 [N, 12] device buffer (q | qd)."""
+        ``joint_state`` is None (the handle's q, qd move); kinematic mode: the caller's float32 [N, 12] device buffer (q | qd).
+        ``joint_torques`` (dynamics mode; float32 ``[N, 6]`` on the env's device, only read): PyBullet's TORQUE_CONTROL
+        (pnr_world_step_torques) — added to each joint's torque in every sub-step of this call only, next to the joints' motors as
+        ``set_joint_motor`` left them (zero gains first for pure torque control).  Never synchronises."""
         self._check_handle()
+        if joint_torques is not None:
+            if joint_state is not None:
+                raise AssertionError("world_step: joint_torques act on the handle's simulated joints; joint_state must be None")
+            tq = self._in(joint_torques, (self.num_envs, 6), torch.float32, "joint_torques")
+            self._chk(self.lib.pnr_world_step_torques(self._h, _ptr(tq), self._stream()))
+            return
         js = None if joint_state is None else self._out(joint_state, "joint_state", (self.num_envs, 12))
         self._chk(self.lib.pnr_world_step(self._h, _ptr(js), self._stream()))
+
+    def inverse_dynamics(self, joint_accel=None, joint_state=None, gravity=True, joint_losses=False, out=None):
+        """calculateInverseDynamics of every env, one launch (pnr_inverse_dynamics): float32 ``[N, 6]`` joint torques
+        tau = M(q) q̈ + C(q, q̇) q̇ + G(q) on the model the dynamics mode steps.  ``joint_accel``: ``[N, 6]`` q̈ (None = 0: the bias
+        forces).  ``joint_state``: as ``link_states`` (``[N, 12]`` = q | q̇; None = the handle's own joints).  ``gravity=False``
+        leaves G(q) out; ``joint_losses=True`` adds the engine's joint damping and friction at q̇, so that
+        ``world_step(joint_torques=tau)`` realises q̈ away from contacts and limits.  Dynamics mode uses the handle's per-env link
+        scales (and friction / damping); kinematic mode the nominal model.  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        acc = None if joint_accel is None else self._in(joint_accel, (n, 6), torch.float32, "joint_accel")
+        flags = (0 if gravity else _lib.INVDYN_NO_GRAVITY) | (_lib.INVDYN_JOINT_LOSSES if joint_losses else 0)
+        res = self._out(out, "out", (n, 6))
+        self._chk(self.lib.pnr_inverse_dynamics(self._h, _ptr(js), _ptr(acc), flags, _ptr(res), self._stream()))
+        return res
+
+    def mass_matrix(self, joint_state=None, out=None):
+        """calculateMassMatrix of every env, one launch (pnr_mass_matrix): float32 ``[N, 6, 6]``, the symmetric joint-space inertia
+        M(q) of the same model (``out[:, i, j] == out[:, j, i]`` bit for bit).  ``joint_state``: as ``inverse_dynamics`` (only q is
+        read).  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        res = self._out(out, "out", (n, 6, 6))
+        self._chk(self.lib.pnr_mass_matrix(self._h, _ptr(js), _ptr(res), self._stream()))
+        return res
 
     def set_joint_motor(self, joint, control_mode, target_position=float("nan"), target_velocity=float("nan"), position_gain=float("nan"),
                         velocity_gain=float("nan"), max_force=float("nan"), max_velocity=float("nan")):

@@ -1,0 +1,156 @@
+"""Independent float64 reference of pnr_inverse_dynamics, pnr_mass_matrix and pnr_world_step_torques.
+
+Built on the float64 oracle's forward dynamics alone (DynOracle.aba_ext, which tests/test_dyn_oracle.py validates), in the style
+of tests/constraint_motor_ref.py, whose free_dynamics it uses for the torque world step; it reads nothing of pioneer_amd and
+restates neither a mass-matrix algorithm nor an inverse-dynamics recursion:
+  * M^-1 comes column by column from the ABA's affinity in tau (ABA(e_j) at qd = 0 without gravity), and M = inv(M^-1);
+  * bias = C(q, qd) qd + G(q) = -M ABA(0, gravity);
+  * tau = M qdd + bias, plus the engine's joint losses damping qd + friction qd / sqrt(qd^2 + eps^2) when asked for;
+  * a torque world step is qdd = qdd_free + M^-1 tau_ext per sub-step, then the semi-implicit Euler and inelastic joint limits of
+    constraint_motor_ref.substep.
+
+newton_euler() is a SECOND statement of the same torques, from tests/golden/urdf_chain.json alone: a world-frame Newton-Euler
+sweep over the 11 URDF links (mass s_l, inertia s_l 1 about the link frame origin), projected on the joint axes.  Every array
+of it has the dtype it is called with: in float64 the CPU tests hold it against the ABA-based reference; in float32 it is the
+"float32 floor" the GPU tests derive their tight bars from (what float32 arithmetic alone costs on the test's inputs).
+"""
+import numpy as np
+
+import constraint_motor_ref as cref
+import link_kinematics_ref as lk
+
+DOF = 6
+LINKS = 11
+FRICTION_EPS = cref.FRICTION_EPS
+
+
+def set_states(orc, q, qd, scales=None, friction=None, damping=None):
+    """Put q, qd [n, 6] (and optionally the per-env parameters) into the oracle's dynamics state."""
+    orc.dstate["q"], orc.dstate["qd"] = np.asarray(q, dtype=np.float64), np.asarray(qd, dtype=np.float64)
+    if scales is not None:
+        orc.dstate["mass_scale"] = np.asarray(scales, dtype=np.float64)
+    if friction is not None:
+        orc.dstate["friction"] = np.asarray(friction, dtype=np.float64)
+    if damping is not None:
+        orc.dstate["damping"] = np.asarray(damping, dtype=np.float64)
+
+
+def aba(orc, tau, gravity):
+    """qdd [n, 6] of the oracle's ABA at its current states: no contacts, motors, damping or friction."""
+    tau = np.broadcast_to(np.asarray(tau, dtype=np.float64), (orc.n, DOF))
+    return np.stack([orc.aba_ext(tau[e], gravity, None, e) for e in range(orc.n)])
+
+
+def mass_and_bias(orc, gravity):
+    """M [n, 6, 6], M^-1 [n, 6, 6] and bias = C qd + G [n, 6] at the oracle's current states.  M^-1 depends on q alone: its
+    columns are taken at qd = 0 without gravity, where ABA(e_j) IS column j (no difference of two large accelerations)."""
+    n = orc.n
+    qdd0 = aba(orc, np.zeros(DOF), gravity)
+    qd = orc.dstate["qd"].copy()
+    orc.dstate["qd"] = 0.0
+    Minv = np.empty((n, DOF, DOF))
+    eye = np.eye(DOF)
+    for j in range(DOF):
+        Minv[:, :, j] = aba(orc, eye[j], 0.0)
+    orc.dstate["qd"] = qd
+    M = np.linalg.inv(Minv)
+    return M, Minv, -np.einsum("nij,nj->ni", M, qdd0)
+
+
+def losses(orc):
+    qd = orc.dstate["qd"]
+    return orc.dstate["damping"] * qd + orc.dstate["friction"] * qd / np.sqrt(qd * qd + FRICTION_EPS ** 2)
+
+
+def inverse_dynamics(orc, qdd=None, gravity=0.0, joint_losses=False):
+    """tau [n, 6] = M qdd + C qd + G (+ the joint losses)."""
+    M, _, bias = mass_and_bias(orc, gravity)
+    tau = bias if qdd is None else bias + np.einsum("nij,nj->ni", M, np.asarray(qdd, dtype=np.float64))
+    return tau + losses(orc) if joint_losses else tau
+
+
+def torque_substep(orc, motors, tau_ext, h=1.0 / 240):
+    """One sub-step with the external joint torques tau_ext [n, 6], in place on orc.dstate (motors: PD kinds or None only)."""
+    assert not cref.constraint_set(motors)
+    qdd_free, Minv = cref.free_dynamics(orc, motors)
+    qdd = qdd_free + np.einsum("nij,nj->ni", Minv, np.asarray(tau_ext, dtype=np.float64))
+    q, qd = orc.dstate["q"], orc.dstate["qd"]
+    qd_plus = qd + h * qdd
+    lo, hi = np.array(orc.p.r_lo[:], dtype=np.float64), np.array(orc.p.r_hi[:], dtype=np.float64)
+    qn = q + h * qd_plus
+    qdn = qd_plus.copy()
+    qdn[(qn > hi) & (qdn > 0)] = 0.0
+    qdn[(qn < lo) & (qdn < 0)] = 0.0
+    orc.dstate["q"], orc.dstate["qd"] = np.clip(qn, lo, hi), qdn
+
+
+def world_step_torques(orc, motors, tau_ext, frame_skip=None, h=1.0 / 240):
+    for _ in range(orc.d.frame_skip if frame_skip is None else frame_skip):
+        torque_substep(orc, motors, tau_ext, h)
+
+
+# ---- the second statement: world-frame Newton-Euler over the URDF links, in the caller's dtype -----------------------------------
+def _axis_rotation(axis, q, T):
+    a = np.asarray(axis, dtype=T)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]], dtype=T)
+    s, c = np.sin(q)[:, None, None], np.cos(q)[:, None, None]
+    return (np.eye(3, dtype=T)[None] + s * K[None] + (T(1) - c) * (K @ K)[None]).astype(T)
+
+
+def _sweep(q, qd, qdd, gravity, T, chain):
+    """Per link: origin p, angular acceleration, linear acceleration of the origin (gravity as the base's +g z), the number of
+    revolute joints up to it; per revolute joint: world axis and origin."""
+    n = q.shape[0]
+    z = np.zeros((n, 3), dtype=T)
+    g0 = z.copy()
+    g0[:, 2] = T(gravity)
+    frames = {"world": (np.broadcast_to(np.eye(3, dtype=T), (n, 3, 3)), z, z, z, g0)}
+    links, joints, qi = [], [], 0
+    for j in chain:
+        Rp, pp, wp, alp, accp = frames[j["parent"]]
+        d = (Rp @ np.asarray(j["xyz"], dtype=T)).astype(T)
+        p = pp + d
+        R = (Rp @ lk.rpy_rotation(j["rpy"]).astype(T)).astype(T)
+        w, al = wp, alp
+        acc = accp + np.cross(alp, d) + np.cross(wp, np.cross(wp, d))
+        if j["type"] == "revolute":
+            axis = np.asarray(j["axis"], dtype=T)
+            a = (R @ axis).astype(T)
+            w = wp + qd[:, qi:qi + 1] * a
+            al = alp + qdd[:, qi:qi + 1] * a + qd[:, qi:qi + 1] * np.cross(wp, a)
+            R = (R @ _axis_rotation(axis, q[:, qi], T)).astype(T)
+            joints.append((a, p))
+            qi += 1
+        frames[j["child"]] = (R, p, w, al, acc)
+        links.append((p, al.astype(T), acc.astype(T), len(joints)))
+    return links, joints
+
+
+def newton_euler(q, qd, qdd, scales, gravity, dtype=np.float64, chain=None):
+    """tau [n, 6] in `dtype`: sum over the links l and their upstream joints j of
+    (a_j x (p_l - o_j)) . s_l acc_l + a_j . s_l alpha_l   (mass 1 and inertia 1 per link, scaled; omega x I omega = 0)."""
+    T = np.dtype(dtype).type
+    chain = chain or lk.load_chain()
+    q, qd, qdd, scales = (np.atleast_2d(np.asarray(x, dtype=T)) for x in (q, qd, qdd, scales))
+    links, joints = _sweep(q, qd, qdd, gravity, T, chain)
+    tau = np.zeros((q.shape[0], DOF), dtype=T)
+    for l, (p, al, acc, nj) in enumerate(links):
+        s = scales[:, l:l + 1]
+        F, N = s * acc, s * al
+        for j in range(nj):
+            a, o = joints[j]
+            tau[:, j] += (np.cross(a, p - o) * F).sum(axis=1) + (a * N).sum(axis=1)
+    assert tau.dtype == np.dtype(dtype)
+    return tau
+
+
+def newton_euler_mass_matrix(q, scales, dtype=np.float64, chain=None):
+    """M [n, 6, 6] in `dtype`: column j is newton_euler at qd = 0, no gravity, qdd = e_j."""
+    q = np.atleast_2d(np.asarray(q, dtype=dtype))
+    zero = np.zeros_like(q)
+    cols = []
+    for j in range(DOF):
+        e = zero.copy()
+        e[:, j] = 1
+        cols.append(newton_euler(q, zero, e, scales, 0.0, dtype, chain))
+    return np.stack(cols, axis=2)
