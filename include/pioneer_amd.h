@@ -43,7 +43,8 @@ extern "C" {
  *   5  new entry points pnr_world_step, pnr_set_joint_motor, pnr_build_fingerprint; `planes` == 2 now means two SCALED FP16 planes
  *      (was: two bf16 planes) in every pnr_mlp_* call; pnr_mlp_train_step checks every argument before its first launch and
  *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
- *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques */
+ *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
+ *      pnr_contact_params_default, pnr_get_contacts */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -443,6 +444,57 @@ int pnr_mass_matrix(pnr_handle h, const float* joint_state, float* out, void* st
  * allocation: capturable into a graph.  Parity unpinned.
  */
 int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* stream);
+
+/*
+ * getContactPoints / getClosestPoints for every env, one launch: each of the arm's 23 contact sample spheres against up to
+ * PNR_MAX_SCENE static bodies given with the call (as pnr_render's: a kinematic-mode handle can ask too).
+ *   Samples: the sample spheres the dynamics mode collides with link_contacts (oracle/pnr_dyn_oracle.h describes them: 8 on
+ *   arm1, 7 on arm2, 2 on rotator2 + hinge2, 3 on arm3, 3 on the effector's needle), in that order; sample 22 is the pointer's
+ *   sphere, of pnr_config.pointer_radius.  Always all 23, each with its SURFACE against each body's surface.  The signed
+ *   distance forms are the step's for scene bodies: plane, sphere, oriented box (inside a box: out through the nearest face).
+ *   The step's one quirk is NOT part of the query: with link_contacts = 0 the step lets the pointer meet ground_z with its
+ *   centre; here the pointer, too, touches with its surface.
+ *   joint_state     as pnr_get_link_states ([num_envs][12] q | qd, 16-byte aligned, read only); NULL = the handle's own joints
+ *                   (dynamics mode the simulated q, qd; kinematic mode the env's r and v)
+ *   p               the bodies (shape, position, orientation, size as in pnr_config.scene; body index = position in this
+ *                   list) and the penalty law's gains contact_kp, contact_kd
+ *   body_positions  [num_envs][n_bodies][3] float32 or NULL: a world position per env that replaces bodies[b].position for
+ *                   that env (orientation and size stay shared): the per-env obstacle.  Ignored when n_bodies == 0.
+ *   points          [num_envs][PNR_CONTACT_SAMPLES][PNR_CONTACT_DIM] float32 or NULL.  The record of sample s, against the
+ *                   nearest body (smallest signed distance; the lower index on a tie):
+ *                     [0]   signed distance, surface to surface (< 0: penetrating); +inf when n_bodies == 0
+ *                     [1:4] unit world normal on the body towards the sample (contactNormalOnB); 0 when n_bodies == 0
+ *                     [4:7] world position on the sample's surface, centre - radius n (positionOnA); the position on the
+ *                           body (positionOnB) is [4:7] - [0] n
+ *                     [7]   that body's index as a float; -1 when n_bodies == 0
+ *                     [8]   that body's normal force on the sample: max(0, kp depth - kd (v . n)) if depth = -distance > 0,
+ *                           else 0; v is the sample centre's world velocity from qd
+ *   summary         [num_envs][4] float32 or NULL: the smallest distance over the samples, that sample's index (the lowest
+ *                   on a tie; 0 when n_bodies == 0), that sample's body, the number of samples with distance < 0
+ *   joint_torques   [num_envs][6] float32 or NULL: tau_c = sum_s J_s(q)^T F_s, F_s the sum over ALL bodies of the force above
+ *                   on sample s (what the step accumulates): joint j's entry is a_j . ((pos_s - o_j) x F_s) over the samples
+ *                   outboard of it.  pnr_world_step_torques with these on a contact-free handle is a step with contacts.
+ * At least one output must be non-NULL; nothing is written past num_envs rows of any output; outputs 16-byte aligned,
+ * body_positions 4-byte.  An env's results do not depend on the batch around it, bit for bit.
+ * PNR_ERR_INVALID, nothing launched and no output touched, for: a null handle or params, a wrong struct_size, n_bodies outside
+ * 0..PNR_MAX_SCENE, a bad shape or non-finite / degenerate body data (as pnr_render), negative or non-finite gains, misaligned
+ * pointers, all outputs NULL, a NULL joint_state before the first pnr_reset (or pnr_set_state).  Non-finite joint values or
+ * body_positions give non-finite output, unchecked.  float32 arithmetic, asynchronous on `stream`, no allocation, no
+ * synchronisation: capturable into a graph.  Parity unpinned: Bullet's narrow phase and manifolds are not reproduced (one point
+ * per sample, against analytic shapes).
+ */
+#define PNR_CONTACT_SAMPLES 23      /* the sample spheres, in table order; sample 22 is the pointer */
+#define PNR_CONTACT_DIM 9
+typedef struct pnr_contact_params {
+    uint32_t struct_size;                    /* sizeof(pnr_contact_params) */
+    int32_t  n_bodies;                       /* 0 .. PNR_MAX_SCENE */
+    double   contact_kp, contact_kd;         /* the penalty law's gains, finite and >= 0; default pnr_config's 2000, 50 */
+    pnr_scene_body bodies[PNR_MAX_SCENE];    /* as pnr_config.scene / pnr_render_params.bodies */
+} pnr_contact_params;
+int pnr_contact_params_default(pnr_contact_params* p);
+int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_params* p,
+                     const float* body_positions, float* points, float* summary,
+                     float* joint_torques, void* stream);
 
 /*
  * render('rgb_array') for every env in one launch (bullet_env.py:156-185 -> getCameraImage): one camera shared by all envs,

@@ -35,6 +35,8 @@ INFO_DIM = 4
 DYN_STATE_WORDS = 36
 NUM_LINKS = 11          # pnr_get_link_states: link records per env (Bullet's link_index order, model.LINKS[1:])
 LINK_STATE_DIM = 13     # position[3], quaternion x y z w [4], linear velocity[3], angular velocity[3]
+CONTACT_SAMPLES = 23    # pnr_get_contacts: sample spheres per env (model.CONTACT_SAMPLE_LINKS names their links); 22 is the pointer
+CONTACT_DIM = 9         # distance, normal[3], position on the sample[3], body index, normal force
 JACOBIAN_DIM = 36       # pnr_get_jacobian: 6 rows (linear xyz, angular xyz) x 6 joint columns per env
 INVDYN_NO_GRAVITY, INVDYN_JOINT_LOSSES = 1, 2      # pnr_inverse_dynamics flags (PNR_INVDYN_*)
 
@@ -73,6 +75,12 @@ class PnrRenderParams(C.Structure):
         ("background", C.c_float * 3), ("target_rgba", C.c_float * 4), ("reserved", C.c_int32),
         ("bodies", PnrSceneBody * MAX_SCENE), ("body_rgba", (C.c_float * 4) * MAX_SCENE),
     ]
+
+
+class PnrContactParams(C.Structure):
+    """pnr_contact_params of include/pioneer_amd.h (pnr_get_contacts's bodies and penalty gains)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_bodies", C.c_int32), ("contact_kp", C.c_double), ("contact_kd", C.c_double),
+                ("bodies", PnrSceneBody * MAX_SCENE)]
 
 
 class PnrIkParams(C.Structure):
@@ -172,6 +180,8 @@ SIGNATURES = {
     "pnr_ik_params_default": (C.c_int, [C.POINTER(PnrIkParams)]),
     "pnr_solve_ik": (C.c_int, [_VP, C.POINTER(PnrIkParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
+    "pnr_contact_params_default": (C.c_int, [C.POINTER(PnrContactParams)]),
+    "pnr_get_contacts": (C.c_int, [_VP, _VP, C.POINTER(PnrContactParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_diag_sincos": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, _VP]),
     "pnr_ppo_loss": (C.c_int, [C.c_int64] + [_VP] * 12 + [C.c_float] * 3 + [_VP] * 3 + [C.c_int64, _VP, _VP]),
     "pnr_mlp_pack_elems": (C.c_int64, []),
@@ -203,7 +213,7 @@ SIGNATURES = {
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 UNITS = {
     "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_links.h",
-                    "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h"],
+                    "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h", "pnr_contacts.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_sampler.h"],
 }
 SOURCES = sorted({f for deps in UNITS.values() for f in deps})      # every file a unit includes: what _stale() watches

@@ -44,6 +44,7 @@
 #include "pnr_render.h"
 #include "pnr_ik.h"
 #include "pnr_invdyn.h"
+#include "pnr_contacts.h"
 
 // =====================================================================================
 // host side
@@ -142,6 +143,22 @@ static void scene_body_frame(const pnr_scene_body& S, double (&R)[9], double (&n
     if (S.shape != PNR_SHAPE_PLANE) return;
     const double nl = std::sqrt(sum_sq(S.size, 3));
     for (int k = 0; k < 3; ++k) normal[k] = (R[3 * k] * S.size[0] + R[3 * k + 1] * S.size[1] + R[3 * k + 2] * S.size[2]) / nl;
+}
+
+// .. and as the kernels want it (pnr_dyn.h SceneBody): float32, pre-rotated; a plane keeps its unit world normal in rot[0..2]
+static SceneBody scene_body_device(const pnr_scene_body& B)
+{
+    SceneBody S = SceneBody{};
+    double R[9], normal[3];
+    scene_body_frame(B, R, normal);
+    S.shape = B.shape;
+    for (int k = 0; k < 3; ++k) { S.pos[k] = (float)B.position[k]; S.size[k] = (float)B.size[k]; }
+    if (B.shape == PNR_SHAPE_PLANE) {
+        for (int k = 0; k < 3; ++k) S.rot[k] = (float)normal[k];
+    } else {
+        for (int k = 0; k < 9; ++k) S.rot[k] = (float)R[k];
+    }
+    return S;
 }
 
 // One joint's entries of the JointMotorTable, assigned in one place
@@ -341,16 +358,7 @@ static void fill_base(pnr_handle h)
         SceneBody& S = host_scene[b];
         S = SceneBody{};
         if (b >= c.n_scene) continue;
-        const pnr_scene_body& B = c.scene[b];
-        double R[9], normal[3];
-        scene_body_frame(B, R, normal);
-        S.shape = B.shape;
-        for (int k = 0; k < 3; ++k) { S.pos[k] = (float)B.position[k]; S.size[k] = (float)B.size[k]; }
-        if (B.shape == PNR_SHAPE_PLANE) {
-            for (int k = 0; k < 3; ++k) S.rot[k] = (float)normal[k];
-        } else {
-            for (int k = 0; k < 9; ++k) S.rot[k] = (float)R[k];
-        }
+        S = scene_body_device(c.scene[b]);
     }
     if (h->scene) (void)hipMemcpy(h->scene, host_scene, sizeof(host_scene), hipMemcpyHostToDevice);
     D.joint_damping = (float)c.joint_damping; D.joint_friction = (float)c.joint_friction;
@@ -875,6 +883,53 @@ int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, 
     A.max_iter = p->max_iterations;
     A.lambda2 = (float)(p->damping * p->damping); A.max_step = (float)p->max_step; A.tol = (float)p->tolerance;
     hipLaunchKernelGGL(ik_kernel, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream, A);
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+int pnr_contact_params_default(pnr_contact_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_contact_params_default: null params");
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_contact_params);
+    p->contact_kp = 2000.0; p->contact_kd = 50.0;       // pnr_config_default's
+    return PNR_OK;
+}
+
+int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_params* p, const float* body_positions, float* points,
+                     float* summary, float* joint_torques, void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: null params");
+    if (p->struct_size != sizeof(pnr_contact_params))
+        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_contact_params));
+    if (!points && !summary && !joint_torques) return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: every output is NULL");
+    if (!(aligned16(points) && aligned16(summary) && aligned16(joint_torques) && aligned16(joint_state)))
+        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: outputs and joint_state must be 16-byte aligned");
+    if (!aligned4(body_positions)) return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: body_positions must be 4-byte aligned");
+    if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
+        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: n_bodies %d outside 0..%d", p->n_bodies, PNR_MAX_SCENE);
+    if (!(std::isfinite(p->contact_kp) && std::isfinite(p->contact_kd) && p->contact_kp >= 0 && p->contact_kd >= 0))
+        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: contact_kp and contact_kd must be finite and >= 0");
+    for (int b = 0; b < p->n_bodies; ++b)
+        if (const int rc = check_scene_body(h, "pnr_get_contacts: body", b, p->bodies[b], true)) return rc;
+    if (!joint_state && !h->ready && !(h->dyn && h->dyn_set))
+        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts before the first pnr_reset (or pnr_set_state)");
+    const int src = link_source(h, joint_state);
+    ContactArgs A;
+    memset(&A, 0, sizeof(A));
+    A.src = joint_state ? joint_state : h->dyn;
+    A.state = src == kLinkSrcKin ? h->state : nullptr;
+    A.body_pos = p->n_bodies > 0 ? body_positions : nullptr;
+    A.points = points; A.summary = summary; A.torques = joint_torques;
+    A.n = h->n;
+    A.ckp = (float)p->contact_kp; A.ckd = (float)p->contact_kd; A.ptr_radius = (float)h->cfg.pointer_radius;
+    A.n_bodies = p->n_bodies;
+    for (int b = 0; b < p->n_bodies; ++b) A.bodies[b] = scene_body_device(p->bodies[b]);
+    DeviceGuard g(h->device);
+    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
+        hipLaunchKernelGGL(contacts_kernel<S()>, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream, A);
+    });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }

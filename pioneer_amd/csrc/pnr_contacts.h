@@ -1,0 +1,267 @@
+// pnr_contacts.h — pnr_get_contacts: for every env, the signed distance of each of the arm's 23 contact sample spheres
+// (pnr_model.h kCapsules, in table order; sample 22 is the pointer) to the nearest of up to eight static bodies, the contact
+// normal, point and penalty force there, a per-env summary and the joint torques of all contact forces: the batched form of
+// getContactPoints / getClosestPoints.  Included by pnr_api.hip only; it adds a kernel and edits none of the step kernels.
+//
+// Per env: q[6], qd[6] in (48-96 B), 23 records of 9 floats out (828 B) + one float4 + six floats.  The signed-distance forms
+// (plane, sphere, oriented box with the nearest-face rule inside) and the penalty law max(0, kp depth - kd v.n) are those of
+// pnr_dyn.h sample_contact's scene-body loop, restated here so that the step kernels' code does not move.  Every sample
+// touches with its SURFACE; the step's one quirk (link_contacts = 0: the pointer meets ground_z with its centre) is not part
+// of the query.
+//
+// Shape (as pnr_links.h): one env per lane, one 64-lane wave per workgroup.  The pose and velocity sweep over the six moving
+// bodies runs in registers, the 23 samples are unrolled from the compile-time table, the body loop is a wave-uniform runtime
+// loop over the by-value kernel argument (scalar loads).  Each output is a wave-uniform branch on its pointer.  The records go
+// to an LDS tile of [64][207] floats (row stride 207 is odd: the lanes' ds_write_b32 hit 64 distinct banks; 52 992 B) that
+// leaves as ONE contiguous span of 16-byte non-temporal stores; summary and joint_torques are 16 + 24 B per lane and go out
+// as plain per-lane stores.  No cross-lane arithmetic: an env's results do not depend on the batch around it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+#include "pnr_device.h"
+#include "pnr_dyn.h"
+#include "pnr_links.h"
+
+// float32 against a float64 reference, tolerance-checked: let a*b+c fuse
+#pragma clang fp contract(fast)
+
+namespace pnr {
+
+constexpr int kContactDim = 9;
+constexpr int kContactSamples = kCapsules[0].n + kCapsules[1].n + kCapsules[2].n + kCapsules[3].n + kCapsules[4].n;
+constexpr int kContactRowFloats = kContactSamples * kContactDim;     // 207 floats = 828 B per env
+constexpr int kContactTileFloats = kWave * kContactRowFloats;         // 13 248 floats = 52 992 B per wave
+static_assert(kNumCapsules == 5 && kContactSamples == 23, "the sample table is pnr_model.h kCapsules");
+static_assert(kContactRowFloats % 2 == 1, "an odd row stride keeps the per-lane LDS writes conflict-free");
+static_assert(kContactTileFloats * sizeof(float) <= 65536, "the tile is static LDS");
+
+struct ContactArgs {
+    const float* src;           // joint source (pnr_links.h load_link_joints)
+    const float4* state;        // kinematic-mode state planes (kLinkSrcKin) or null
+    const float* body_pos;      // [n][n_bodies][3] per-env body positions or null
+    float* points;              // [n][23][9] or null
+    float* summary;             // [n][4] or null
+    float* torques;             // [n][6] or null
+    long long n;
+    float ckp, ckd, ptr_radius;
+    int n_bodies;
+    SceneBody bodies[kMaxScene];   // as the step uploads them: world position, row-major rotation (plane: unit normal in rot[0..2]), size
+};
+
+// The bodies are read where the launch put them, in the kernel-argument segment (constant address space), 16 scalar dwords per
+// body at a wave-uniform index: indexing the by-value argument itself with the loop counter makes the compiler copy the whole
+// struct to scratch first.  ContactArgs is the kernel's only argument, so the segment starts with it.
+typedef const __attribute__((address_space(4))) int* ContactBodyWords;
+static_assert(sizeof(SceneBody) == 16 * sizeof(int) && offsetof(ContactArgs, bodies) % 4 == 0, "a SceneBody is 16 dwords");
+
+__device__ __forceinline__ ContactBodyWords contact_body_words()
+{
+    typedef const __attribute__((address_space(4))) char* Bytes;
+    return (ContactBodyWords)((Bytes)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(ContactArgs, bodies));
+}
+
+__device__ __forceinline__ SceneBody load_contact_body(ContactBodyWords w, int b)
+{
+    w += 16 * b;
+    SceneBody S;
+    S.shape = w[0];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { S.pos[k] = __int_as_float(w[1 + k]); S.size[k] = __int_as_float(w[13 + k]); }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) S.rot[k] = __int_as_float(w[4 + k]);
+    return S;
+}
+
+// world pose and velocity of one moving body's frame
+struct ContactFrame { M3 R; V3 p, v, w; };
+
+// body J from its parent B (the sweep of pnr_links.h link_body_outward without the quaternion); axis = the joint's world axis
+template <int J>
+__device__ __forceinline__ void contact_frame_outward(const ContactFrame& B, float q, float qd, ContactFrame& C, V3& axis)
+{
+    float sn, cs;
+    sincos_any(q, sn, cs);
+    pose_outward<J>(B.R, B.p, cs, sn, C.R, C.p);
+    axis = col(C.R, (int)kJoints[J].axis);
+    C.w = B.w + qd * axis;
+    C.v = B.v + cross(B.w, C.p - B.p);
+}
+
+// signed distance of the point `pos` to the body S placed at `o`, and the body's unit outward normal there (world frame)
+__device__ __forceinline__ void body_distance(const SceneBody& S, V3 o, V3 pos, float& sdf, V3& nrm)
+{
+    const V3 dd = pos - o;
+    if (S.shape == 1) {                                // plane: unit world normal in rot[0..2]
+        nrm = {S.rot[0], S.rot[1], S.rot[2]};
+        sdf = dot(nrm, dd);
+    } else if (S.shape == 3) {                         // sphere
+        const float len = sqrtf(dot(dd, dd));
+        sdf = len - S.size[0];
+        nrm = len > 0.f ? (1.f / len) * dd : V3{0.f, 0.f, 1.f};
+    } else {                                           // oriented box: into its frame, out again with the normal
+        const V3 l = {S.rot[0] * dd.x + S.rot[3] * dd.y + S.rot[6] * dd.z, S.rot[1] * dd.x + S.rot[4] * dd.y + S.rot[7] * dd.z,
+                      S.rot[2] * dd.x + S.rot[5] * dd.y + S.rot[8] * dd.z};
+        const V3 q = {fabsf(l.x) - S.size[0], fabsf(l.y) - S.size[1], fabsf(l.z) - S.size[2]};
+        const V3 out = {fmaxf(q.x, 0.f), fmaxf(q.y, 0.f), fmaxf(q.z, 0.f)};
+        const float out2 = dot(out, out);
+        V3 nl;
+        if (out2 > 0.f) {
+            const float len = sqrtf(out2);
+            sdf = len;
+            nl = {(l.x < 0.f ? -out.x : out.x) / len, (l.y < 0.f ? -out.y : out.y) / len, (l.z < 0.f ? -out.z : out.z) / len};
+        } else {                                       // inside: out through the nearest face
+            const int km = (q.x >= q.y && q.x >= q.z) ? 0 : (q.y >= q.z ? 1 : 2);
+            sdf = comp(q, km);
+            nl = {km == 0 ? (l.x < 0.f ? -1.f : 1.f) : 0.f, km == 1 ? (l.y < 0.f ? -1.f : 1.f) : 0.f,
+                  km == 2 ? (l.z < 0.f ? -1.f : 1.f) : 0.f};
+        }
+        nrm = {S.rot[0] * nl.x + S.rot[1] * nl.y + S.rot[2] * nl.z, S.rot[3] * nl.x + S.rot[4] * nl.y + S.rot[5] * nl.z,
+               S.rot[6] * nl.x + S.rot[7] * nl.y + S.rot[8] * nl.z};
+    }
+}
+
+// per-env running summary: smallest distance, its sample and body, number of penetrating samples
+struct ContactSummary { float dist, sample, body, count; };
+
+// One sample sphere (centre c in the frame B, radius) against every body: its record into rec (9 floats of this lane's LDS
+// row, or null), the summary, and F = the sum over ALL bodies of the penalty force on it; pos = its centre in the world.
+__device__ __forceinline__ void contact_sample(const ContactArgs& A, ContactBodyWords bw, const float* __restrict__ bp, const ContactFrame& B, V3 c,
+                                               float radius, int s, float* rec, ContactSummary& sm, V3& pos, V3& F)
+{
+    const V3 rel = mul(B.R, c);
+    pos = B.p + rel;
+    const V3 vel = B.v + cross(B.w, rel);
+    float best = INFINITY, bestf = 0.f, bestb = -1.f;
+    V3 bestn = {0.f, 0.f, 0.f};
+    F = {0.f, 0.f, 0.f};
+    // software-pipelined: body b + 1 is on its way (scalar loads) while body b is worked on; with one wave per SIMD nothing else
+    // hides that latency.  The index stays inside bodies[kMaxScene] whatever n_bodies is.
+    SceneBody next = load_contact_body(bw, 0);
+#pragma unroll 1
+    for (int b = 0; b < A.n_bodies; ++b) {             // wave-uniform
+        const SceneBody S = next;
+        next = load_contact_body(bw, b + 1 < kMaxScene ? b + 1 : b);
+        V3 o = {S.pos[0], S.pos[1], S.pos[2]};
+        if (bp) o = {bp[3 * b], bp[3 * b + 1], bp[3 * b + 2]};
+        float sdf;
+        V3 nrm;
+        body_distance(S, o, pos, sdf, nrm);
+        const float depth = radius - sdf;              // surface to surface
+        const float fn = A.ckp * depth - A.ckd * dot(vel, nrm);
+        const float f = (depth > 0.f && fn > 0.f) ? fn : 0.f;
+        F = F + f * nrm;
+        if (-depth < best) { best = -depth; bestn = nrm; bestb = (float)b; bestf = f; }
+    }
+    if (rec) {
+        const V3 on = pos - radius * bestn;
+        rec[0] = best;
+        rec[1] = bestn.x; rec[2] = bestn.y; rec[3] = bestn.z;
+        rec[4] = on.x; rec[5] = on.y; rec[6] = on.z;
+        rec[7] = bestb;
+        rec[8] = bestf;
+    }
+    if (s == 0 || best < sm.dist) { sm.dist = best; sm.sample = (float)s; sm.body = bestb; }
+    sm.count += best < 0.f ? 1.f : 0.f;
+}
+
+// first sample index of capsule ci (table order)
+__host__ __device__ constexpr int contact_sample_base(int ci)
+{
+    int k = 0;
+    for (int i = 0; i < ci; ++i) k += kCapsules[i].n;
+    return k;
+}
+
+// one env: the 23 records into `row` (207 floats, or null), the summary, tau_j = sum_s a_j . ((pos_s - o_j) x F_s)
+__device__ __forceinline__ void contacts_env(const ContactArgs& A, const float* __restrict__ bp, const float (&q)[kDof],
+                                             const float (&qd)[kDof], float* row, ContactSummary& sm, float (&tau)[kDof])
+{
+    const bool want_tau = A.torques != nullptr;
+    const ContactBodyWords bw = contact_body_words();
+    ContactFrame b;
+    b.R = diag3(1.f); b.p = {0.f, 0.f, 0.f}; b.v = {0.f, 0.f, 0.f}; b.w = {0.f, 0.f, 0.f};
+    V3 axis[kDof], org[kDof];
+    sm = {INFINITY, 0.f, -1.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < kDof; ++j) tau[j] = 0.f;
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        ContactFrame c;
+        contact_frame_outward<J>(b, q[J], qd[J], c, axis[J]);
+        b = c;
+        org[J] = b.p;
+        static_for<kNumCapsules>([&](auto ci_) {
+            constexpr int ci = decltype(ci_)::value;
+            if constexpr (kCapsules[ci].body == J) {
+                static_for<kCapsules[ci].n>([&](auto i_) {
+                    constexpr int i = decltype(i_)::value;
+                    constexpr CapsuleDef K = kCapsules[ci];
+                    constexpr int s = contact_sample_base(ci) + i;
+                    constexpr float t = K.n > 1 ? (float)((double)i / (double)(K.n - 1)) : 0.f;
+                    constexpr bool tip = (ci == kNumCapsules - 1) && (i == K.n - 1);
+                    const V3 cen = tip ? V3{(float)kTipX, (float)kTipY, (float)kTipZ}
+                                       : V3{K.ax + t * (K.bx - K.ax), K.ay + t * (K.by - K.ay), K.az + t * (K.bz - K.az)};
+                    V3 pos, F;
+                    contact_sample(A, bw, bp, b, cen, K.radius < 0.f ? A.ptr_radius : K.radius, s, row ? row + kContactDim * s : nullptr, sm,
+                                   pos, F);
+                    if (want_tau) {
+                        static_for<J + 1>([&](auto k_) {                // the joints between the base and this body
+                            constexpr int k = decltype(k_)::value;
+                            tau[k] += dot(axis[k], cross(pos - org[k], F));
+                        });
+                    }
+                });
+            }
+        });
+    });
+}
+
+// a wave's tile (rows [0, nvalid) of 207 floats) to its contiguous place in points[n][23][9], exactly as flush_link_tile: 16-byte
+// lane-linear non-temporal stores (every tile starts 52 992 B after the last, so dst stays 16-byte aligned), a short last
+// tile's tail as single floats.  Nothing past row nvalid is written.
+__device__ __forceinline__ void flush_contact_tile(const float* __restrict__ lds, float* __restrict__ dst, int nvalid, int lane)
+{
+    const int total = nvalid * kContactRowFloats;
+    const int nvec = total >> 2;
+    const float4* src4 = reinterpret_cast<const float4*>(lds);
+    float4* dst4 = reinterpret_cast<float4*>(dst);
+    for (int j = lane; j < nvec; j += kWave) stream_store(dst4 + j, src4[j]);
+    for (int j = (nvec << 2) + lane; j < total; j += kWave) stream_store(dst + j, lds[j]);
+}
+
+template <int SRC>
+__global__ __launch_bounds__(kWave) void contacts_kernel(const ContactArgs A)
+{
+    __shared__ __attribute__((aligned(16))) float tile[kContactTileFloats];
+    const int lane = threadIdx.x;
+    const long long tile0 = (long long)blockIdx.x * kWave;
+    const long long e = tile0 + lane;
+    const int nvalid = (int)((A.n - tile0) < kWave ? (A.n - tile0) : kWave);
+    float q[kDof], qd[kDof];
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) { q[i] = 0.f; qd[i] = 0.f; }
+    if (e < A.n) load_link_joints<SRC>(A.src, A.state, A.n, e, q, qd);
+    // a lane past the batch computes on the last env's body positions and stores nothing
+    const float* bp = A.body_pos ? A.body_pos + (e < A.n ? e : A.n - 1) * (3 * A.n_bodies) : nullptr;
+    ContactSummary sm;
+    float tau[kDof];
+    contacts_env(A, bp, q, qd, A.points ? tile + lane * kContactRowFloats : nullptr, sm, tau);
+    if (e < A.n) {
+        if (A.summary) reinterpret_cast<float4*>(A.summary)[e] = make_float4(sm.dist, sm.sample, sm.body, sm.count);
+        if (A.torques) {
+            float2* t2 = reinterpret_cast<float2*>(A.torques) + 3 * e;
+            t2[0] = make_float2(tau[0], tau[1]); t2[1] = make_float2(tau[2], tau[3]); t2[2] = make_float2(tau[4], tau[5]);
+        }
+    }
+    if (A.points) {
+        wave_lds_sync();
+        flush_contact_tile(tile, A.points + tile0 * kContactRowFloats, nvalid, lane);
+    }
+}
+
+}  // namespace pnr
+
+#pragma clang fp contract(off)

@@ -34,7 +34,10 @@ def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, g
     """Returns {"episode_rewards", "episode_lengths", "successes", "targets_reachable", "frames"}; writes an animated GIF of
     all episodes when gif_path is given (24 frames per second, the env's metadata rate).  targets_reachable: the fraction of
     the episodes' targets the pointer can get within done_distance of at all (PioneerVectorEnv.target_reachable, one call per
-    reset) — what tells "did not reach" from "could not reach"."""
+    reset) — what tells "did not reach" from "could not reach".  When the env has at least one collision body
+    (PioneerVectorEnv.collision_bodies: the engine_config's ground_z, obstacle box or scene) the result also holds collision_steps,
+    the share of the evaluated steps with any penetrating contact sample, and min_clearance, the smallest sample-to-body distance
+    seen (one PioneerVectorEnv.contacts launch per step); without a body the result is unchanged."""
     device = torch.device(device)
     model, filt, cfg = load_policy(checkpoint, device)
     env = TimeLimit(PioneerKinematicEnv(device=device, mode=mode, engine_config=engine_config), max_episode_steps=max_episode_steps)
@@ -44,6 +47,8 @@ def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, g
     gen = torch.Generator(device=device).manual_seed(0 if seed is None else seed)
     frames: List[np.ndarray] = []
     rewards, lengths, successes, reachable = [], [], [], []
+    has_bodies = len(env.env._vec.collision_bodies()) > 0
+    touching, clearance = 0, float("inf")
     for _ in range(episodes):
         obs = env.reset()
         reachable.append(bool(env.env._vec.target_reachable()[0].item()))
@@ -56,6 +61,10 @@ def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, g
                 act = torch.maximum(torch.minimum(act, a_max), -a_max)
             obs, reward, done, info = env.step(act[0].cpu().numpy())
             total += reward; steps += 1
+            if has_bodies:
+                smallest, _, _, count = env.env._vec.contacts(points=False)["summary"][0].tolist()
+                touching += count > 0
+                clearance = min(clearance, smallest)
             if gif_path is not None and steps % frame_stride == 0:
                 frames.append(env.render(mode="rgb_array"))
         rewards.append(total); lengths.append(steps)
@@ -66,5 +75,9 @@ def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, g
         from PIL import Image
         imgs = [Image.fromarray(f) for f in frames]
         imgs[0].save(gif_path, save_all=True, append_images=imgs[1:], duration=int(1000 * frame_stride / fps), loop=0)
-    return {"episode_rewards": rewards, "episode_lengths": lengths, "successes": successes,
-            "targets_reachable": float(np.mean(reachable)) if reachable else float("nan"), "frames": len(frames)}
+    result = {"episode_rewards": rewards, "episode_lengths": lengths, "successes": successes,
+              "targets_reachable": float(np.mean(reachable)) if reachable else float("nan"), "frames": len(frames)}
+    if has_bodies:
+        result["collision_steps"] = touching / max(1, sum(lengths))
+        result["min_clearance"] = clearance
+    return result

@@ -38,6 +38,12 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   only); the reference's ``items_by_name['robot:pointer']`` is ``links_by_name['robot:pointer']`` here.
 * ``render("rgb_array")`` with ``EngineConfig.renderer == "engine"`` draws every created body in ``scene.items`` (the target aside) in
   its ``Item.rgba_color``: the ``rgba_color`` it was created with, else the URDF's obstacle_mat; planes in ground_mat.
+* ``scene.contact_points(item=None)`` / ``scene.closest_points(distance, item=None)``: pybullet.getContactPoints / getClosestPoints
+  between the arm and the bodies created through ``env.scene`` with a collision shape, as ``ContactPoint`` tuples (PyBullet's field
+  names), one engine launch (``pnr_get_contacts``), either mode.  The arm's geometry is the engine's 23 contact sample spheres
+  (``CONTACT_SAMPLE_LINKS`` gives each one's URDF link): one entry per sample, against its nearest body.  bodyUniqueIdA is 0 (the
+  arm), bodyUniqueIdB 1 + the body's place among the created collision bodies, linkIndexB -1 (a base).  Deviation: PyBullet's
+  manifolds (several points per pair) are not reproduced.
 * ``Item.pose()`` is a ``Pose`` (``.xyz``, ``.rpy``), still a 2-tuple (position, orientation); ``Item.velocity()`` a ``Velocity``
   (linear, angular), zero for created bodies and the target (they are static).
 Build-defined behaviour where the reference delegates to Bullet: parity unpinned, like the rest of the Bullet boundary.
@@ -73,6 +79,25 @@ class Velocity(NamedTuple):
     linear: Tuple[float, float, float]
     angular: Tuple[float, float, float]
 
+
+class ContactPoint(NamedTuple):
+    """One entry of pybullet.getContactPoints / getClosestPoints, in PyBullet's names.  A is the arm, B the created body."""
+    contactFlag: int
+    bodyUniqueIdA: int
+    bodyUniqueIdB: int
+    linkIndexA: int
+    linkIndexB: int
+    positionOnA: Tuple[float, float, float]
+    positionOnB: Tuple[float, float, float]
+    contactNormalOnB: Tuple[float, float, float]
+    contactDistance: float
+    normalForce: float
+
+
+# the URDF link (Bullet's link_index) of each of the engine's 23 contact sample spheres, in the engine's order: 8 on arm1, 7 on
+# arm2, 2 on rotator2 (+ hinge2), 3 on arm3, 2 on the effector's needle, and the pointer's own sphere
+CONTACT_SAMPLE_LINKS = (3,) * 8 + (4,) * 7 + (5,) * 2 + (7,) * 3 + (9,) * 2 + (10,)
+assert len(CONTACT_SAMPLE_LINKS) == _lib.CONTACT_SAMPLES
 
 _ZERO3 = (0.0, 0.0, 0.0)
 
@@ -250,6 +275,43 @@ class Scene:
         """The created bodies as render_frames draws them: (SceneBody, rgba) of every item but the target."""
         return [(SceneBody(i.shape, i._position, i._orientation, tuple(map(float, i.size))), i.rgba_color or OBSTACLE_RGBA)
                 for i in self.items if i.name != "target"]
+
+    # -- contacts (pybullet.getContactPoints / getClosestPoints) ------------------------------------------------------------
+    def collision_items(self) -> List[Item]:
+        """The created bodies with a collision shape, in creation order: a body's place here is its body index in the engine's
+        query and bodyUniqueIdB - 1."""
+        return [i for i in self.items if i.collision and i.name != "target" and not isinstance(i, LinkItem)]
+
+    def _contact_records(self, item: Optional[Item], keep) -> List[ContactPoint]:
+        bodies = self.collision_items()
+        if len(bodies) > _lib.MAX_SCENE:
+            raise AssertionError(f"the engine queries at most {_lib.MAX_SCENE} created bodies, the scene has {len(bodies)}")
+        vec = self._env._vec
+        js = None if vec.engine_config.mode == "dynamic" else self._bullet
+        sb = [SceneBody(i.shape, i._position, i._orientation, tuple(map(float, i.size))) for i in bodies]
+        rec = vec.contacts(joint_state=js, bodies=sb, summary=False)["points"][0].double().cpu().numpy()
+        out = []
+        for s, r in enumerate(rec):
+            b = int(r[7])
+            if b < 0 or not keep(float(r[0])):
+                continue
+            if isinstance(item, LinkItem) and CONTACT_SAMPLE_LINKS[s] != item.link_index:
+                continue
+            if item is not None and not isinstance(item, LinkItem) and bodies[b] is not item:
+                continue
+            n, on_a = r[1:4], r[4:7]
+            out.append(ContactPoint(0, 0, 1 + b, CONTACT_SAMPLE_LINKS[s], -1, tuple(map(float, on_a)), tuple(map(float, on_a - r[0] * n)),
+                                    tuple(map(float, n)), float(r[0]), float(r[8])))
+        return out
+
+    def contact_points(self, item: Optional[Item] = None) -> List[ContactPoint]:
+        """getContactPoints: the samples that penetrate their nearest created body (contactDistance < 0).  ``item``: a link item
+        (only that link's samples) or a created body (only contacts with it)."""
+        return self._contact_records(item, lambda d: d < 0.0)
+
+    def closest_points(self, distance: float, item: Optional[Item] = None) -> List[ContactPoint]:
+        """getClosestPoints: the samples within ``distance`` of their nearest created body (contactDistance <= distance)."""
+        return self._contact_records(item, lambda d: d <= float(distance))
 
     # -- rotations (pybullet.getQuaternionFromEuler / getEulerFromQuaternion: x, y, z, w; roll about x, pitch about y, yaw about z) --
     @staticmethod

@@ -366,6 +366,64 @@ class PioneerVectorEnv:
                                       self._stream()))
         return res
 
+    def collision_bodies(self):
+        """The env's own collision world as a body list, in the order that is the body index of ``contacts()``: the ``ground_z``
+        plane (normal +z) if set, the obstacle box (``obstacle_position`` / ``obstacle_half_extents``) if set, then
+        ``engine_config.scene`` in its own order."""
+        from .config import scene_box, scene_plane
+        ec = self.engine_config
+        bodies = []
+        if ec.ground_z == ec.ground_z:
+            bodies.append(scene_plane((0.0, 0.0, 1.0), (0.0, 0.0, float(ec.ground_z))))
+        if all(float(h) > 0 for h in ec.obstacle_half_extents):
+            bodies.append(scene_box(ec.obstacle_half_extents, ec.obstacle_position))
+        return bodies + list(ec.scene)
+
+    def contacts(self, joint_state=None, bodies=None, body_positions=None, points=True, summary=True, joint_torques=False, out=None):
+        """getContactPoints / getClosestPoints of every env, one launch (pnr_get_contacts): the arm's 23 contact sample spheres
+        (``_lib.CONTACT_SAMPLES``; ``scene.CONTACT_SAMPLE_LINKS`` names their URDF links, sample 22 is the pointer) against static
+        bodies, surface to surface.  Works in either mode.  Returns a dict of device tensors, those asked for:
+
+        ``points`` float32 ``[N, 23, 9]``: per sample, against its nearest body, the signed distance (< 0: penetrating; +inf
+        without bodies), the unit world normal on the body towards the sample [3], the world position on the sample's surface
+        [3] (the position on the body is that minus distance x normal), the body index (-1 without bodies) and that body's
+        normal force max(0, kp depth - kd v.n);
+        ``summary`` float32 ``[N, 4]``: the smallest distance, its sample, its body, the number of penetrating samples;
+        ``joint_torques`` float32 ``[N, 6]``: the joint torques of all contact forces, sum_s J_s^T F_s over all bodies — given to
+        ``world_step(joint_torques=...)`` of a contact-free env they reproduce a step with contacts.
+
+        ``bodies``: a sequence of SceneBody (config.scene_plane / scene_box / scene_sphere), at most 8; the BODY INDEX is the
+        position in it.  None = the env's own collision world, ``collision_bodies()``: the ``ground_z`` plane if set, the
+        obstacle box if set, then ``engine_config.scene``.  ``body_positions`` (float32 ``[N, len(bodies), 3]``): a world position
+        per env in place of each body's own (orientation and size stay shared): the per-env obstacle.  ``joint_state``: as
+        ``link_states`` (None = the handle's own joints).  The gains are the config's ``contact_kp`` / ``contact_kd``; the
+        pointer's radius its ``pointer_radius``.  ``out`` may carry preallocated ``points`` / ``summary`` / ``joint_torques``
+        tensors, written in place.  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        bodies = self.collision_bodies() if bodies is None else list(bodies)
+        if len(bodies) > _lib.MAX_SCENE:
+            raise AssertionError(f"at most {_lib.MAX_SCENE} bodies can be queried, got {len(bodies)}")
+        p = _lib.PnrContactParams()
+        self._chk(self.lib.pnr_contact_params_default(p))
+        p.n_bodies = len(bodies)
+        p.contact_kp, p.contact_kd = float(self.engine_config.contact_kp), float(self.engine_config.contact_kd)
+        for i, b in enumerate(bodies):
+            fill_scene_body(p.bodies[i], b, f"body {i}")
+        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        bp = None if body_positions is None else self._in(body_positions, (n, len(bodies), 3), torch.float32, "body_positions")
+        out = out or {}
+        res = {}
+        for key, want, shape in (("points", points, (n, _lib.CONTACT_SAMPLES, _lib.CONTACT_DIM)), ("summary", summary, (n, 4)),
+                                 ("joint_torques", joint_torques, (n, 6))):
+            if want:
+                res[key] = self._out(out, key, shape)
+        if not res:
+            raise AssertionError("contacts: ask for at least one of points, summary, joint_torques")
+        self._chk(self.lib.pnr_get_contacts(self._h, _ptr(js), p, _ptr(bp), _ptr(res.get("points")), _ptr(res.get("summary")),
+                                            _ptr(res.get("joint_torques")), self._stream()))
+        return res
+
     def observe(self, out=None):
         """observe() without stepping (pioneer_knm_env.py:184-211)."""
         self._check_handle()
