@@ -212,8 +212,8 @@ SIGNATURES = {
 
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 UNITS = {
-    "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_links.h",
-                    "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h", "pnr_contacts.h"],
+    "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_query.h",
+                    "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h", "pnr_contacts.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_sampler.h"],
 }
 SOURCES = sorted({f for deps in UNITS.values() for f in deps})      # every file a unit includes: what _stale() watches

@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <type_traits>
@@ -89,8 +90,18 @@ static int fail(pnr_handle h, int code, const char* fmt, ...)
     return rc;
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+static inline bool aligned16(const void* p) { return aligned_to(p, 16); }
+static inline bool aligned8(const void* p) { return aligned_to(p, 8); }
+
+// a call's pointer arguments against their alignment, in the order given (a null pointer passes); `call` names it in the message
+struct AlignedArg { const void* p; const char* name; unsigned align; };
+static int check_aligned(pnr_handle h, const char* call, std::initializer_list<AlignedArg> args)
+{
+    for (const AlignedArg& a : args)
+        if (!aligned_to(a.p, a.align)) return fail(h, PNR_ERR_INVALID, "%s: %s must be %u-byte aligned", call, a.name, a.align);
+    return PNR_OK;
+}
 
 template <class T>
 static bool finite_all(const T* v, int k)
@@ -189,8 +200,33 @@ static JointMotor pd_motor(bool velocity, double kp, double kd, double force_lim
 // code), bit 1 the inertia-scaled motor
 static inline int dyn_phys(const DynParams& D) { return ((D.has_ground || D.has_box || D.n_scene > 0) ? 1 : 0) | (D.inertia_scaled ? 2 : 0); }
 
-// whose joints a link query or a render reads (pnr_links.h): the caller's buffer, else the handle's own (h->dyn; kinematic: the state)
-static inline int link_source(pnr_handle h, const float* js) { return js ? kLinkSrcBuffer : (h->dyn ? kLinkSrcDyn : kLinkSrcKin); }
+// whose joints a query or a render reads (pnr_query.h): the caller's buffer, else the handle's own (h->dyn; kinematic: the state)
+struct JointSource { int kind; const float* src; const float4* state; };
+static inline JointSource joint_source(pnr_handle h, const float* js)
+{
+    return js ? JointSource{kJointSrcBuffer, js, nullptr} : h->dyn ? JointSource{kJointSrcDyn, h->dyn, nullptr} : JointSource{kJointSrcKin, nullptr, h->state};
+}
+
+// one launch of a kernel of one env per lane and one wave per workgroup: kernel(S)(args...), S = the joint source `kind`
+template <class K, class... Args>
+static int launch_env_waves(pnr_handle h, void* stream, int kind, K&& kernel, Args... args)
+{
+    DeviceGuard g(h->device);
+    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
+    with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(kind, [&](auto S) {
+        hipLaunchKernelGGL(kernel(S), grid, dim3(kWave), 0, (hipStream_t)stream, args...);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+// What a query needs of the handle when the caller brings no data of its own, one predicate per rule.  They differ, and
+// pnr_get_link_states' is the odd one: it takes a dynamics handle whose joints were never set.
+static inline bool has_own_joints(pnr_handle h) { return h->ready || (h->dyn && h->dyn_set); }     // pnr_get_jacobian, pnr_get_contacts
+static inline bool has_own_joints_or_planes(pnr_handle h) { return h->ready || h->dyn; }           // pnr_get_link_states
+static inline bool has_link_scales(pnr_handle h) { return h->ready || h->dyn_set; }                // dynamics mode: drawn by the first reset
+static inline bool has_own_target(pnr_handle h) { return h->ready || h->kin_set; }                 // pnr_solve_ik, pnr_render
+static int before_first_reset(pnr_handle h, const char* call, const char* why = "") { return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)%s", call, why); }
 
 // the argument checks of pnr_get_state / pnr_set_state and their dyn twins
 static int check_state_call(pnr_handle h, const void* words, const char* call, bool dyn)
@@ -741,21 +777,10 @@ int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!out) return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: null out");
-    if (!aligned16(out)) return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: out must be 16-byte aligned");
-    if (!aligned16(joint_state))
-        return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: joint_state must be 16-byte aligned");
-    if (!joint_state && !h->dyn && !h->ready)
-        return fail(h, PNR_ERR_INVALID, "pnr_get_link_states before the first pnr_reset (or pnr_set_state)");
-    DeviceGuard g(h->device);
-    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave)), block(kWave);
-    hipStream_t st = (hipStream_t)stream;
-    const int src = link_source(h, joint_state);
-    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
-        hipLaunchKernelGGL(link_state_kernel<S()>, grid, block, 0, st, joint_state ? joint_state : h->dyn,
-                           src == kLinkSrcKin ? h->state : nullptr, out, (long long)h->n);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    if (const int rc = check_aligned(h, "pnr_get_link_states", {{out, "out", 16}, {joint_state, "joint_state", 16}})) return rc;
+    if (!joint_state && !has_own_joints_or_planes(h)) return before_first_reset(h, "pnr_get_link_states");
+    const JointSource J = joint_source(h, joint_state);
+    return launch_env_waves(h, stream, J.kind, [](auto S) { return link_state_kernel<S()>; }, J.src, J.state, out, (long long)h->n);
 }
 
 // (link, local_point) -> the moving body that carries the link and the point's offset in that body's frame: every fixed joint of
@@ -768,29 +793,17 @@ static ChainPoint chain_point(int link, const double* local_point)
     return {kLinkBody[link], (float)o[0], (float)o[1], (float)o[2]};
 }
 
-static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 int pnr_get_jacobian(pnr_handle h, const float* joint_state, int32_t link, const double* local_point, float* out, void* stream)
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!out) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: null out");
     if (link < 0 || link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: link %d outside 0..%d", link, kNumLinks - 1);
     if (local_point && !finite_all(local_point, 3)) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: non-finite local_point");
-    if (!aligned16(out) || !aligned16(joint_state))
-        return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: out and joint_state must be 16-byte aligned");
-    if (!joint_state && !h->ready && !(h->dyn && h->dyn_set))
-        return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian before the first pnr_reset (or pnr_set_state)");
-    DeviceGuard g(h->device);
-    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave)), block(kWave);
-    hipStream_t st = (hipStream_t)stream;
-    const int src = link_source(h, joint_state);
-    const ChainPoint P = chain_point(link, local_point);
-    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
-        hipLaunchKernelGGL(jacobian_kernel<S()>, grid, block, 0, st, joint_state ? joint_state : h->dyn,
-                           src == kLinkSrcKin ? h->state : nullptr, out, (long long)h->n, P);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    if (const int rc = check_aligned(h, "pnr_get_jacobian", {{out, "out", 16}, {joint_state, "joint_state", 16}})) return rc;
+    if (!joint_state && !has_own_joints(h)) return before_first_reset(h, "pnr_get_jacobian");
+    const JointSource J = joint_source(h, joint_state);
+    return launch_env_waves(h, stream, J.kind, [](auto S) { return jacobian_kernel<S()>; }, J.src, J.state, out, (long long)h->n,
+                            chain_point(link, local_point));
 }
 
 // the checks pnr_inverse_dynamics and pnr_mass_matrix share (nothing launched, nothing written on failure)
@@ -798,11 +811,9 @@ static int check_invdyn_call(pnr_handle h, const char* call, const float* joint_
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!out) return fail(h, PNR_ERR_INVALID, "%s: null out", call);
-    if (!aligned16(out) || !aligned16(joint_state) || !aligned16(joint_accel))
-        return fail(h, PNR_ERR_INVALID, "%s: out, joint_state and joint_accel must be 16-byte aligned", call);
+    if (const int rc = check_aligned(h, call, {{out, "out", 16}, {joint_state, "joint_state", 16}, {joint_accel, "joint_accel", 16}})) return rc;
     // a dynamics-mode handle's link scales are drawn by the first reset: no model before it, whatever the joint source
-    if (h->dyn ? !(h->ready || h->dyn_set) : (!joint_state && !h->ready))
-        return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)", call);
+    if (h->dyn ? !has_link_scales(h) : (!joint_state && !has_own_joints(h))) return before_first_reset(h, call);
     return PNR_OK;
 }
 
@@ -811,34 +822,22 @@ int pnr_inverse_dynamics(pnr_handle h, const float* joint_state, const float* jo
     if (const int rc = check_invdyn_call(h, "pnr_inverse_dynamics", joint_state, joint_accel, out)) return rc;
     if (flags & ~(PNR_INVDYN_NO_GRAVITY | PNR_INVDYN_JOINT_LOSSES))
         return fail(h, PNR_ERR_INVALID, "pnr_inverse_dynamics: unknown flags 0x%x", (unsigned)flags);
-    DeviceGuard g(h->device);
-    const int src = link_source(h, joint_state);
+    const JointSource J = joint_source(h, joint_state);
     InvDynArgs A;
-    A.src = joint_state ? joint_state : h->dyn;
-    A.state = src == kLinkSrcKin ? h->state : nullptr;
+    A.src = J.src; A.state = J.state;
     A.dyn = h->dyn; A.accel = joint_accel; A.out = out; A.n = h->n;
     A.gravity = (flags & PNR_INVDYN_NO_GRAVITY) ? 0.f : (float)h->cfg.gravity;
     A.loss_gain = (flags & PNR_INVDYN_JOINT_LOSSES) ? 1.f : 0.f;
     A.damping0 = (float)h->cfg.joint_damping; A.friction0 = (float)h->cfg.joint_friction;
-    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
-        hipLaunchKernelGGL(inverse_dynamics_kernel<S()>, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream, A);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    return launch_env_waves(h, stream, J.kind, [](auto S) { return inverse_dynamics_kernel<S()>; }, A);
 }
 
 int pnr_mass_matrix(pnr_handle h, const float* joint_state, float* out, void* stream)
 {
     if (const int rc = check_invdyn_call(h, "pnr_mass_matrix", joint_state, nullptr, out)) return rc;
-    DeviceGuard g(h->device);
-    const int src = link_source(h, joint_state);
-    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
-        hipLaunchKernelGGL(mass_matrix_kernel<S()>, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream,
-                           joint_state ? joint_state : h->dyn, src == kLinkSrcKin ? h->state : nullptr, (const float*)h->dyn, out,
-                           (long long)h->n);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    const JointSource J = joint_source(h, joint_state);
+    return launch_env_waves(h, stream, J.kind, [](auto S) { return mass_matrix_kernel<S()>; }, J.src, J.state, (const float*)h->dyn, out,
+                            (long long)h->n);
 }
 
 int pnr_ik_params_default(pnr_ik_params* p)
@@ -869,12 +868,9 @@ int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, 
     if (!(std::isfinite(p->max_step) && p->max_step > 0)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: max_step must be finite and > 0");
     if (!(std::isfinite(p->tolerance) && p->tolerance >= 0)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: tolerance must be finite and >= 0");
     if (!finite_all(p->local_point, 3)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: non-finite local_point");
-    if (!aligned8(q_out)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: q_out must be 8-byte aligned");
-    if (!(aligned4(target_pos) && aligned4(q_init) && aligned4(residual_out) && aligned4(iterations_out)))
-        return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: float32 / int32 arrays must be 4-byte aligned");
-    if (!target_pos && !h->ready && !h->kin_set)
-        return fail(h, PNR_ERR_INVALID, "pnr_solve_ik before the first pnr_reset (or pnr_set_state): the target comes from the state");
-    DeviceGuard g(h->device);
+    if (const int rc = check_aligned(h, "pnr_solve_ik", {{q_out, "q_out", 8}, {target_pos, "target_pos", 4}, {q_init, "q_init", 4},
+                                                          {residual_out, "residual_out", 4}, {iterations_out, "iterations_out", 4}})) return rc;
+    if (!target_pos && !has_own_target(h)) return before_first_reset(h, "pnr_solve_ik", ": the target comes from the state");
     IkArgs A;
     A.target = target_pos; A.state = h->state; A.q_init = q_init;
     A.q_out = q_out; A.residual = residual_out; A.iterations = iterations_out;
@@ -882,9 +878,7 @@ int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, 
     A.point = chain_point(p->link, p->local_point);
     A.max_iter = p->max_iterations;
     A.lambda2 = (float)(p->damping * p->damping); A.max_step = (float)p->max_step; A.tol = (float)p->tolerance;
-    hipLaunchKernelGGL(ik_kernel, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream, A);
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    return launch_env_waves(h, stream, kJointSrcBuffer, [](auto) { return ik_kernel; }, A);      // (no joint source: one form)
 }
 
 int pnr_contact_params_default(pnr_contact_params* p)
@@ -904,34 +898,26 @@ int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_p
     if (p->struct_size != sizeof(pnr_contact_params))
         return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_contact_params));
     if (!points && !summary && !joint_torques) return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: every output is NULL");
-    if (!(aligned16(points) && aligned16(summary) && aligned16(joint_torques) && aligned16(joint_state)))
-        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: outputs and joint_state must be 16-byte aligned");
-    if (!aligned4(body_positions)) return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: body_positions must be 4-byte aligned");
+    if (const int rc = check_aligned(h, "pnr_get_contacts", {{points, "points", 16}, {summary, "summary", 16}, {joint_torques, "joint_torques", 16},
+                                                              {joint_state, "joint_state", 16}, {body_positions, "body_positions", 4}})) return rc;
     if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
         return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: n_bodies %d outside 0..%d", p->n_bodies, PNR_MAX_SCENE);
     if (!(std::isfinite(p->contact_kp) && std::isfinite(p->contact_kd) && p->contact_kp >= 0 && p->contact_kd >= 0))
         return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: contact_kp and contact_kd must be finite and >= 0");
     for (int b = 0; b < p->n_bodies; ++b)
         if (const int rc = check_scene_body(h, "pnr_get_contacts: body", b, p->bodies[b], true)) return rc;
-    if (!joint_state && !h->ready && !(h->dyn && h->dyn_set))
-        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts before the first pnr_reset (or pnr_set_state)");
-    const int src = link_source(h, joint_state);
+    if (!joint_state && !has_own_joints(h)) return before_first_reset(h, "pnr_get_contacts");
+    const JointSource J = joint_source(h, joint_state);
     ContactArgs A;
     memset(&A, 0, sizeof(A));
-    A.src = joint_state ? joint_state : h->dyn;
-    A.state = src == kLinkSrcKin ? h->state : nullptr;
+    A.src = J.src; A.state = J.state;
     A.body_pos = p->n_bodies > 0 ? body_positions : nullptr;
     A.points = points; A.summary = summary; A.torques = joint_torques;
     A.n = h->n;
     A.ckp = (float)p->contact_kp; A.ckd = (float)p->contact_kd; A.ptr_radius = (float)h->cfg.pointer_radius;
     A.n_bodies = p->n_bodies;
     for (int b = 0; b < p->n_bodies; ++b) A.bodies[b] = scene_body_device(p->bodies[b]);
-    DeviceGuard g(h->device);
-    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(src, [&](auto S) {
-        hipLaunchKernelGGL(contacts_kernel<S()>, dim3((unsigned)((h->n + kWave - 1) / kWave)), dim3(kWave), 0, (hipStream_t)stream, A);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    return launch_env_waves(h, stream, J.kind, [](auto S) { return contacts_kernel<S()>; }, A);
 }
 
 }  // extern "C"
@@ -1043,19 +1029,17 @@ int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* 
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!p) return fail(h, PNR_ERR_INVALID, "pnr_render: null params");
     if (!rgb && !depth && !seg) return fail(h, PNR_ERR_INVALID, "pnr_render: every output is NULL");
-    if (!(aligned16(rgb) && aligned16(depth) && aligned16(seg) && aligned16(joint_state)))
-        return fail(h, PNR_ERR_INVALID, "pnr_render: outputs and joint_state must be 16-byte aligned");
-    if (!h->ready && !h->kin_set)
-        return fail(h, PNR_ERR_INVALID, "pnr_render before the first pnr_reset (or pnr_set_state): the target comes from the state");
+    if (const int rc = check_aligned(h, "pnr_render", {{rgb, "rgb", 16}, {depth, "depth", 16}, {seg, "seg", 16}, {joint_state, "joint_state", 16}})) return rc;
+    if (!has_own_target(h)) return before_first_reset(h, "pnr_render", ": the target comes from the state");
     RenderParams P;
     const int rc = render_setup(h, p, P);
     if (rc) return rc;
     DeviceGuard g(h->device);
     const dim3 grid((unsigned)(h->n * P.tiles)), block(kRenderThreads);
     hipStream_t st = (hipStream_t)stream;
-    with_int<kLinkSrcBuffer, kLinkSrcDyn, kLinkSrcKin>(link_source(h, joint_state), [&](auto S) {
-        hipLaunchKernelGGL(render_kernel<S()>, grid, block, 0, st, joint_state ? joint_state : h->dyn, h->state, (long long)h->n, P, rgb,
-                           depth, seg);
+    const JointSource J = joint_source(h, joint_state);       // (the kernel reads the target from h->state whatever the source)
+    with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(J.kind, [&](auto S) {
+        hipLaunchKernelGGL(render_kernel<S()>, grid, block, 0, st, J.src, h->state, (long long)h->n, P, rgb, depth, seg);
     });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;

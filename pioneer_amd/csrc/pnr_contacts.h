@@ -9,12 +9,11 @@
 // touches with its SURFACE; the step's one quirk (link_contacts = 0: the pointer meets ground_z with its centre) is not part
 // of the query.
 //
-// Shape (as pnr_links.h): one env per lane, one 64-lane wave per workgroup.  The pose and velocity sweep over the six moving
-// bodies runs in registers, the 23 samples are unrolled from the compile-time table, the body loop is a wave-uniform runtime
-// loop over the by-value kernel argument (scalar loads).  Each output is a wave-uniform branch on its pointer.  The records go
-// to an LDS tile of [64][207] floats (row stride 207 is odd: the lanes' ds_write_b32 hit 64 distinct banks; 52 992 B) that
-// leaves as ONE contiguous span of 16-byte non-temporal stores; summary and joint_torques are 16 + 24 B per lane and go out
-// as plain per-lane stores.  No cross-lane arithmetic: an env's results do not depend on the batch around it.
+// Shape: the tile kernel of pnr_query.h.  The pose and velocity sweep over the six moving bodies runs in registers, the 23
+// samples are unrolled from the compile-time table, the body loop is a wave-uniform runtime loop over the by-value kernel
+// argument (scalar loads).  Each output is a wave-uniform branch on its pointer.  The records go to a dense LDS tile of
+// [64][207] floats (52 992 B); summary and joint_torques are 16 + 24 B per lane and go out as plain per-lane stores.  No
+// cross-lane arithmetic: an env's results do not depend on the batch around it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,7 +22,7 @@
 
 #include "pnr_device.h"
 #include "pnr_dyn.h"
-#include "pnr_links.h"
+#include "pnr_query.h"
 
 // float32 against a float64 reference, tolerance-checked: let a*b+c fuse
 #pragma clang fp contract(fast)
@@ -39,8 +38,8 @@ static_assert(kContactRowFloats % 2 == 1, "an odd row stride keeps the per-lane 
 static_assert(kContactTileFloats * sizeof(float) <= 65536, "the tile is static LDS");
 
 struct ContactArgs {
-    const float* src;           // joint source (pnr_links.h load_link_joints)
-    const float4* state;        // kinematic-mode state planes (kLinkSrcKin) or null
+    const float* src;           // joint source (pnr_query.h load_joints)
+    const float4* state;        // kinematic-mode state planes (kJointSrcKin) or null
     const float* body_pos;      // [n][n_bodies][3] per-env body positions or null
     float* points;              // [n][23][9] or null
     float* summary;             // [n][4] or null
@@ -78,16 +77,14 @@ __device__ __forceinline__ SceneBody load_contact_body(ContactBodyWords w, int b
 // world pose and velocity of one moving body's frame
 struct ContactFrame { M3 R; V3 p, v, w; };
 
-// body J from its parent B (the sweep of pnr_links.h link_body_outward without the quaternion); axis = the joint's world axis
+// body J from its parent B: pose_outward at the full angle's cos / sin, velocity_outward; axis = the joint's world axis
 template <int J>
 __device__ __forceinline__ void contact_frame_outward(const ContactFrame& B, float q, float qd, ContactFrame& C, V3& axis)
 {
     float sn, cs;
     sincos_any(q, sn, cs);
     pose_outward<J>(B.R, B.p, cs, sn, C.R, C.p);
-    axis = col(C.R, (int)kJoints[J].axis);
-    C.w = B.w + qd * axis;
-    C.v = B.v + cross(B.w, C.p - B.p);
+    velocity_outward<J>(B, qd, C, axis);
 }
 
 // signed distance of the point `pos` to the body S placed at `o`, and the body's unit outward normal there (world frame)
@@ -219,46 +216,28 @@ __device__ __forceinline__ void contacts_env(const ContactArgs& A, const float* 
     });
 }
 
-// a wave's tile (rows [0, nvalid) of 207 floats) to its contiguous place in points[n][23][9], exactly as flush_link_tile: 16-byte
-// lane-linear non-temporal stores (every tile starts 52 992 B after the last, so dst stays 16-byte aligned), a short last
-// tile's tail as single floats.  Nothing past row nvalid is written.
-__device__ __forceinline__ void flush_contact_tile(const float* __restrict__ lds, float* __restrict__ dst, int nvalid, int lane)
-{
-    const int total = nvalid * kContactRowFloats;
-    const int nvec = total >> 2;
-    const float4* src4 = reinterpret_cast<const float4*>(lds);
-    float4* dst4 = reinterpret_cast<float4*>(dst);
-    for (int j = lane; j < nvec; j += kWave) stream_store(dst4 + j, src4[j]);
-    for (int j = (nvec << 2) + lane; j < total; j += kWave) stream_store(dst + j, lds[j]);
-}
-
 template <int SRC>
 __global__ __launch_bounds__(kWave) void contacts_kernel(const ContactArgs A)
 {
     __shared__ __attribute__((aligned(16))) float tile[kContactTileFloats];
-    const int lane = threadIdx.x;
-    const long long tile0 = (long long)blockIdx.x * kWave;
-    const long long e = tile0 + lane;
-    const int nvalid = (int)((A.n - tile0) < kWave ? (A.n - tile0) : kWave);
+    const EnvLane L = env_lane(A.n);
     float q[kDof], qd[kDof];
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) { q[i] = 0.f; qd[i] = 0.f; }
-    if (e < A.n) load_link_joints<SRC>(A.src, A.state, A.n, e, q, qd);
+    load_lane_joints<SRC>(A.src, A.state, A.n, L, q, qd);
     // a lane past the batch computes on the last env's body positions and stores nothing
-    const float* bp = A.body_pos ? A.body_pos + (e < A.n ? e : A.n - 1) * (3 * A.n_bodies) : nullptr;
+    const float* bp = A.body_pos ? A.body_pos + (L.live ? L.e : A.n - 1) * (3 * A.n_bodies) : nullptr;
     ContactSummary sm;
     float tau[kDof];
-    contacts_env(A, bp, q, qd, A.points ? tile + lane * kContactRowFloats : nullptr, sm, tau);
-    if (e < A.n) {
-        if (A.summary) reinterpret_cast<float4*>(A.summary)[e] = make_float4(sm.dist, sm.sample, sm.body, sm.count);
+    contacts_env(A, bp, q, qd, A.points ? tile + L.lane * kContactRowFloats : nullptr, sm, tau);
+    if (L.live) {
+        if (A.summary) reinterpret_cast<float4*>(A.summary)[L.e] = make_float4(sm.dist, sm.sample, sm.body, sm.count);
         if (A.torques) {
-            float2* t2 = reinterpret_cast<float2*>(A.torques) + 3 * e;
+            float2* t2 = reinterpret_cast<float2*>(A.torques) + 3 * L.e;
             t2[0] = make_float2(tau[0], tau[1]); t2[1] = make_float2(tau[2], tau[3]); t2[2] = make_float2(tau[4], tau[5]);
         }
     }
     if (A.points) {
         wave_lds_sync();
-        flush_contact_tile(tile, A.points + tile0 * kContactRowFloats, nvalid, lane);
+        flush_dense_tile(tile, A.points + L.tile0 * kContactRowFloats, L.nvalid * kContactRowFloats, L.lane);
     }
 }
 

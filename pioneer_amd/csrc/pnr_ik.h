@@ -2,14 +2,12 @@
 // position-only damped-least-squares inverse kinematics (calculateInverseKinematics without an orientation) for every env,
 // one launch each.  Included by pnr_api.hip only; it adds two kernels and edits none of the others.
 //
-// Shape of both: one env per lane, one 64-lane wave per workgroup, as link_state_kernel.  The host resolves (link,
+// Shape of both: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  The host resolves (link,
 // local_point) into the moving body that carries the link and the point's offset in that body's frame; both arrive as
 // kernel arguments, so every `J <= body` test below is a scalar branch.
 //
 // jacobian_kernel: one outward sweep (pose_outward) gives each joint's world axis a_j and origin o_j and the point; column j
-// is a_j x (point - o_j) | a_j.  The 36 floats of an env go into an LDS tile of [64][37] floats (the odd row stride keeps
-// the ds_write_b32 of each 32-lane half on 32 distinct banks, as pnr_links.h's 143 does) and the tile leaves as ONE contiguous span of 16-byte
-// non-temporal stores.  36 floats per env are a whole number of float4s, so the span has no partial tail.
+// is a_j x (point - o_j) | a_j.  The 36 floats of an env go into the 6 x 6 LDS tile of pnr_query.h and leave through its flush.
 //
 // ik_kernel: q[6], the six sin/cos pairs, the 18 entries of the linear Jacobian and the 3 x 3 system live in registers; the
 // loop's trip count is the wave-uniform max_iterations, a converged lane is frozen by selects, and the wave leaves early once
@@ -22,18 +20,12 @@
 
 #include "pnr_device.h"
 #include "pnr_dyn.h"
-#include "pnr_links.h"
+#include "pnr_query.h"
 
 // float32 against a float64 reference, tolerance-checked: let a*b+c fuse
 #pragma clang fp contract(fast)
 
 namespace pnr {
-
-constexpr int kJacDim = 36;                                     // 6 rows x 6 joint columns
-constexpr int kJacRowStride = kJacDim + 1;                      // LDS row stride, odd
-constexpr int kJacTileFloats = kWave * kJacRowStride;           // 2 368 floats = 9 472 B per wave
-static_assert(kJacRowStride % 2 == 1, "an odd row stride keeps the per-lane LDS writes conflict-free");
-static_assert(kJacDim % 4 == 0, "an env's row is a whole number of float4s: the flush has no partial tail");
 
 // the point a Jacobian or an IK solve is about: offset `off` in the frame of moving body `body` (-1: the static base)
 struct ChainPoint { int body; float ox, oy, oz; };
@@ -68,47 +60,27 @@ __device__ __forceinline__ void chain_jacobian(const float (&c)[kDof], const flo
     });
 }
 
-// Copy a wave's tile (rows [0, nvalid) of 36 floats at stride 37) to its contiguous place in out[n][6][6]: 16-byte lane-linear
-// non-temporal stores (dst is 16-byte aligned: the caller's buffer is, and every tile starts 9 216 B further on).  A float4
-// never straddles two rows (36 = 9 x 4).  Nothing past row nvalid is written.
-__device__ __forceinline__ void flush_jacobian_tile(const float* __restrict__ lds, float* __restrict__ dst, int nvalid, int lane)
-{
-    constexpr int kVecPerRow = kJacDim / 4;
-    const int nvec = nvalid * kVecPerRow;
-    float4* dst4 = reinterpret_cast<float4*>(dst);
-    for (int j = lane; j < nvec; j += kWave) {
-        const int r = j / kVecPerRow;
-        const float* src = lds + r * kJacRowStride + 4 * (j - r * kVecPerRow);
-        stream_store(dst4 + j, make_float4(src[0], src[1], src[2], src[3]));
-    }
-}
-
 template <int SRC>
 __global__ __launch_bounds__(kWave) void jacobian_kernel(const float* __restrict__ src, const float4* __restrict__ state,
                                                          float* __restrict__ out, const long long n, const ChainPoint P)
 {
-    __shared__ __attribute__((aligned(16))) float tile[kJacTileFloats];
-    const int lane = threadIdx.x;
-    const long long tile0 = (long long)blockIdx.x * kWave;
-    const long long e = tile0 + lane;
-    const int nvalid = (int)((n - tile0) < kWave ? (n - tile0) : kWave);
+    __shared__ __attribute__((aligned(16))) float tile[kMat6TileFloats];
+    const EnvLane L = env_lane(n);
     float q[kDof], qd[kDof];
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) { q[i] = 0.f; qd[i] = 0.f; }
-    if (e < n) load_link_joints<SRC>(src, state, n, e, q, qd);
+    load_lane_joints<SRC>(src, state, n, L, q, qd);
     float c[kDof], s[kDof];
 #pragma unroll
     for (int i = 0; i < kDof; ++i) sincos_any(q[i], s[i], c[i]);       // any finite joint value, as pnr_get_link_states
     V3 lin[kDof], ang[kDof], point;
     chain_jacobian(c, s, P, lin, ang, point);
-    float* row = tile + lane * kJacRowStride;
+    float* row = tile + L.lane * kMat6RowStride;
     static_for<kDof>([&](auto jc) {
         constexpr int J = decltype(jc)::value;
         row[J] = lin[J].x; row[kDof + J] = lin[J].y; row[2 * kDof + J] = lin[J].z;
         row[3 * kDof + J] = ang[J].x; row[4 * kDof + J] = ang[J].y; row[5 * kDof + J] = ang[J].z;
     });
     wave_lds_sync();
-    flush_jacobian_tile(tile, out + tile0 * kJacDim, nvalid, lane);
+    flush_mat6_tile(tile, out + L.tile0 * kMat6Dim, L.nvalid, L.lane);
 }
 
 struct IkArgs {

@@ -2,7 +2,7 @@
 // every env, one launch each, on the rigid-body model the ABA of pnr_dyn.h steps (six merged bodies, per-env link scales).
 // Included by pnr_api.hip only; it adds two kernels and edits none of the others.
 //
-// Shape of both: one env per lane, one 64-lane wave per workgroup, as pnr_ik.h.  The joints come through load_link_joints<SRC>;
+// Shape of both: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  The joints come through load_joints<SRC>;
 // a dynamics-mode handle's link scales, friction and damping are read planar (plane w of env e at dyn[w * n + e]: consecutive
 // lanes, consecutive words); a kinematic-mode handle has no such planes (dyn == null, a wave-uniform branch): scales 1 and the
 // config's joint_damping / joint_friction as kernel arguments.  sin / cos by sincos_any: a caller's joints are unbounded.
@@ -13,16 +13,14 @@
 // the IK outputs (the wave's three stores cover one contiguous 1 536-B span, every line of it written whole by this wave).
 //
 // mass_matrix_kernel: mass_matrix() of pnr_dyn.h (the CRBA the constraint motor uses) gives the packed lower triangle; each
-// value is written to both triangles of the env's row of the Jacobian's LDS tile ([64][37] floats), which leaves through
-// flush_jacobian_tile as one contiguous span of 16-byte non-temporal stores.
+// value is written to both triangles of the env's row of the 6 x 6 LDS tile of pnr_query.h, which leaves through its flush.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "pnr_device.h"
 #include "pnr_dyn.h"
-#include "pnr_ik.h"
-#include "pnr_links.h"
+#include "pnr_query.h"
 
 // float32 against a float64 reference, tolerance-checked: let a*b+c fuse
 #pragma clang fp contract(fast)
@@ -90,7 +88,7 @@ __device__ __forceinline__ void rnea(float gravity, const DynModel& M, const flo
 // what both kernels read of an env: joints, link scales (and for the losses friction and damping)
 template <int SRC, bool LOSSES>
 __device__ __forceinline__ void invdyn_load(const float* __restrict__ src, const float4* __restrict__ state,
-                                            const float* __restrict__ dyn, const long long n, const long long e, const bool live,
+                                            const float* __restrict__ dyn, const long long n, const EnvLane& L,
                                             const float damping0, const float friction0, float (&q)[kDof], float (&qd)[kDof],
                                             float (&sc)[kNumLinks], float (&fric)[kDof], float (&damp)[kDof])
 {
@@ -98,8 +96,9 @@ __device__ __forceinline__ void invdyn_load(const float* __restrict__ src, const
     for (int i = 0; i < kDof; ++i) { q[i] = 0.f; qd[i] = 0.f; fric[i] = friction0; damp[i] = damping0; }
 #pragma unroll
     for (int l = 0; l < kNumLinks; ++l) sc[l] = 1.0f;
-    if (!live) return;
-    load_link_joints<SRC>(src, state, n, e, q, qd);
+    if (!L.live) return;                                              // ONE branch around every load: not load_lane_joints
+    const long long e = L.e;
+    load_joints<SRC>(src, state, n, e, q, qd);
     if (dyn) {                                                        // wave-uniform: a dynamics-mode handle
 #pragma unroll
         for (int l = 0; l < kNumLinks; ++l) sc[l] = dyn[(long long)(kDynScale + l) * n + e];
@@ -115,7 +114,7 @@ __device__ __forceinline__ void invdyn_load(const float* __restrict__ src, const
 
 struct InvDynArgs {
     const float* src;          // caller's [n][12], or the handle's dyn words (SRC)
-    const float4* state;       // kinematic-mode state planes (kLinkSrcKin only)
+    const float4* state;       // kinematic-mode state planes (kJointSrcKin only)
     const float* dyn;          // the handle's dyn words [36][n] (link scales, friction, damping), or null: kinematic mode
     const float* accel;        // [n][6] or null: qdd = 0
     float* out;                // [n][6], 16-byte aligned
@@ -128,14 +127,13 @@ struct InvDynArgs {
 template <int SRC>
 __global__ __launch_bounds__(kWave) void inverse_dynamics_kernel(const InvDynArgs A)
 {
-    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
-    const bool live = e < A.n;
+    const EnvLane L = env_lane(A.n);
     float q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], qdd[kDof];
-    invdyn_load<SRC, true>(A.src, A.state, A.dyn, A.n, e, live, A.damping0, A.friction0, q, qd, sc, fric, damp);
+    invdyn_load<SRC, true>(A.src, A.state, A.dyn, A.n, L, A.damping0, A.friction0, q, qd, sc, fric, damp);
 #pragma unroll
     for (int i = 0; i < kDof; ++i) qdd[i] = 0.f;
-    if (live && A.accel) {
-        const float2* a2 = reinterpret_cast<const float2*>(A.accel) + 3 * e;
+    if (L.live && A.accel) {
+        const float2* a2 = reinterpret_cast<const float2*>(A.accel) + 3 * L.e;
         const float2 x0 = a2[0], x1 = a2[1], x2 = a2[2];
         qdd[0] = x0.x; qdd[1] = x0.y; qdd[2] = x1.x; qdd[3] = x1.y; qdd[4] = x2.x; qdd[5] = x2.y;
     }
@@ -151,8 +149,8 @@ __global__ __launch_bounds__(kWave) void inverse_dynamics_kernel(const InvDynArg
         const float loss = damp[i] * qd[i] + fric[i] * qd[i] * __builtin_amdgcn_rsqf(qd[i] * qd[i] + kFrictionEps * kFrictionEps);
         tau[i] += A.loss_gain * loss;
     }
-    if (!live) return;
-    float2* o = reinterpret_cast<float2*>(A.out) + 3 * e;
+    if (!L.live) return;
+    float2* o = reinterpret_cast<float2*>(A.out) + 3 * L.e;
     o[0] = make_float2(tau[0], tau[1]); o[1] = make_float2(tau[2], tau[3]); o[2] = make_float2(tau[4], tau[5]);
 }
 
@@ -160,14 +158,10 @@ template <int SRC>
 __global__ __launch_bounds__(kWave) void mass_matrix_kernel(const float* __restrict__ src, const float4* __restrict__ state,
                                                             const float* __restrict__ dyn, float* __restrict__ out, const long long n)
 {
-    __shared__ __attribute__((aligned(16))) float tile[kJacTileFloats];
-    static_assert(kDof * kDof == kJacDim, "M(q) fills the Jacobian's tile row");
-    const int lane = threadIdx.x;
-    const long long tile0 = (long long)blockIdx.x * kWave;
-    const long long e = tile0 + lane;
-    const int nvalid = (int)((n - tile0) < kWave ? (n - tile0) : kWave);
+    __shared__ __attribute__((aligned(16))) float tile[kMat6TileFloats];
+    const EnvLane L = env_lane(n);
     float q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof];
-    invdyn_load<SRC, false>(src, state, dyn, n, e, e < n, 0.f, 0.f, q, qd, sc, fric, damp);
+    invdyn_load<SRC, false>(src, state, dyn, n, L, 0.f, 0.f, q, qd, sc, fric, damp);
     DynModel M;
     build_model(sc, M);
     float c[kDof], s[kDof];
@@ -175,7 +169,7 @@ __global__ __launch_bounds__(kWave) void mass_matrix_kernel(const float* __restr
     for (int i = 0; i < kDof; ++i) sincos_any(q[i], s[i], c[i]);
     float H[kTri];
     mass_matrix(M, c, s, H);
-    float* row = tile + lane * kJacRowStride;
+    float* row = tile + L.lane * kMat6RowStride;
     static_for<kDof>([&](auto i_) {
         constexpr int i = decltype(i_)::value;
         static_for<kDof>([&](auto j_) {
@@ -184,7 +178,7 @@ __global__ __launch_bounds__(kWave) void mass_matrix_kernel(const float* __restr
         });
     });
     wave_lds_sync();
-    flush_jacobian_tile(tile, out + tile0 * kJacDim, nvalid, lane);
+    flush_mat6_tile(tile, out + L.tile0 * kMat6Dim, L.nvalid, L.lane);
 }
 
 }  // namespace pnr

@@ -251,11 +251,8 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
     // ---- prologue: body poses (wave 0), then one record per primitive ----
     if (tid < kWave) {
         float q[kDof], qd[kDof];
-        load_link_joints<SRC>(src, state, n, e, q, qd);
-        LinkBody b;
-        b.R = diag3(1.f); b.p = {0.f, 0.f, 0.f};
-        b.qx = b.qy = b.qz = 0.f; b.qw = 1.f;
-        b.v = {0.f, 0.f, 0.f}; b.w = {0.f, 0.f, 0.f};
+        load_joints<SRC>(src, state, n, e, q, qd);
+        LinkBody b = link_base();
         static_for<kDof>([&](auto jc) {
             constexpr int J = decltype(jc)::value;
             LinkBody c;

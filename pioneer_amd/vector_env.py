@@ -120,6 +120,17 @@ class PioneerVectorEnv:
         assert res.data_ptr() == t.data_ptr(), f"{key} is written in place: it must already be a contiguous {dtype} device tensor"
         return res
 
+    def _joints(self, joint_state):
+        """A query's optional ``joint_state`` ``[N, 12]`` (q | qd) as a float32 device tensor; None = the handle's own joints."""
+        return None if joint_state is None else self._in(joint_state, (self.num_envs, 12), torch.float32, "joint_state")
+
+    def _asked(self, out, specs, nothing):
+        """The outputs asked for ((key, wanted, shape, dtype) in ``specs``), from ``out`` or new; none: AssertionError(``nothing``)."""
+        res = {key: self._out(out or {}, key, shape, dtype) for key, want, shape, dtype in specs if want}
+        if not res:
+            raise AssertionError(nothing)
+        return res
+
     # -- gym-ish surface ----------------------------------------------------------------
     def seed(self, seed=None):
         """pioneer_knm_env.py:107-109 (takes effect at the next reset)."""
@@ -221,7 +232,7 @@ class PioneerVectorEnv:
         scales (and friction / damping); kinematic mode the nominal model.  Never synchronises."""
         self._check_handle()
         n = self.num_envs
-        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        js = self._joints(joint_state)
         acc = None if joint_accel is None else self._in(joint_accel, (n, 6), torch.float32, "joint_accel")
         flags = (0 if gravity else _lib.INVDYN_NO_GRAVITY) | (_lib.INVDYN_JOINT_LOSSES if joint_losses else 0)
         res = self._out(out, "out", (n, 6))
@@ -234,7 +245,7 @@ class PioneerVectorEnv:
         read).  Never synchronises."""
         self._check_handle()
         n = self.num_envs
-        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        js = self._joints(joint_state)
         res = self._out(out, "out", (n, 6, 6))
         self._chk(self.lib.pnr_mass_matrix(self._h, _ptr(js), _ptr(res), self._stream()))
         return res
@@ -257,7 +268,7 @@ class PioneerVectorEnv:
         (dynamics mode: the simulated q, qd; kinematic mode: the env's r, v)."""
         self._check_handle()
         n = self.num_envs
-        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        js = self._joints(joint_state)
         res = self._out(out, "out", (n, _lib.NUM_LINKS, _lib.LINK_STATE_DIM))
         self._chk(self.lib.pnr_get_link_states(self._h, _ptr(js), _ptr(res), self._stream()))
         return res
@@ -270,7 +281,7 @@ class PioneerVectorEnv:
         ``link_states`` (``[N, 12]`` = q | qd, only q is read; None = the handle's own joints).  Never synchronises."""
         self._check_handle()
         n = self.num_envs
-        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        js = self._joints(joint_state)
         lp = None if local_point is None else (C.c_double * 3)(*(float(v) for v in local_point))
         res = self._out(out, "out", (n, 6, 6))
         self._chk(self.lib.pnr_get_jacobian(self._h, _ptr(js), int(link), lp, _ptr(res), self._stream()))
@@ -353,15 +364,9 @@ class PioneerVectorEnv:
             fill_scene_body(p.bodies[i], b, f"body {i}")
             for k in range(4):
                 p.body_rgba[i][k] = float(rgba[k])
-        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
-        out = out or {}
-        res = {}
-        for key, want, shape, dtype in (("rgb", rgb, (n, H, W, 3), torch.uint8), ("depth", depth, (n, H, W), torch.float32),
-                                        ("seg", segmentation, (n, H, W), torch.uint8)):
-            if want:
-                res[key] = self._out(out, key, shape, dtype)
-        if not res:
-            raise AssertionError("render_frames: ask for at least one of rgb, depth, segmentation")
+        js = self._joints(joint_state)
+        res = self._asked(out, (("rgb", rgb, (n, H, W, 3), torch.uint8), ("depth", depth, (n, H, W), torch.float32),
+                                ("seg", segmentation, (n, H, W), torch.uint8)), "render_frames: ask for at least one of rgb, depth, segmentation")
         self._chk(self.lib.pnr_render(self._h, _ptr(js), p, _ptr(res.get("rgb")), _ptr(res.get("depth")), _ptr(res.get("seg")),
                                       self._stream()))
         return res
@@ -410,16 +415,10 @@ class PioneerVectorEnv:
         p.contact_kp, p.contact_kd = float(self.engine_config.contact_kp), float(self.engine_config.contact_kd)
         for i, b in enumerate(bodies):
             fill_scene_body(p.bodies[i], b, f"body {i}")
-        js = None if joint_state is None else self._in(joint_state, (n, 12), torch.float32, "joint_state")
+        js = self._joints(joint_state)
         bp = None if body_positions is None else self._in(body_positions, (n, len(bodies), 3), torch.float32, "body_positions")
-        out = out or {}
-        res = {}
-        for key, want, shape in (("points", points, (n, _lib.CONTACT_SAMPLES, _lib.CONTACT_DIM)), ("summary", summary, (n, 4)),
-                                 ("joint_torques", joint_torques, (n, 6))):
-            if want:
-                res[key] = self._out(out, key, shape)
-        if not res:
-            raise AssertionError("contacts: ask for at least one of points, summary, joint_torques")
+        res = self._asked(out, (("points", points, (n, _lib.CONTACT_SAMPLES, _lib.CONTACT_DIM), torch.float32), ("summary", summary, (n, 4), torch.float32),
+                                ("joint_torques", joint_torques, (n, 6), torch.float32)), "contacts: ask for at least one of points, summary, joint_torques")
         self._chk(self.lib.pnr_get_contacts(self._h, _ptr(js), p, _ptr(bp), _ptr(res.get("points")), _ptr(res.get("summary")),
                                             _ptr(res.get("joint_torques")), self._stream()))
         return res

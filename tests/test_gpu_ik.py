@@ -10,6 +10,7 @@ import torch
 
 import ik_ref
 import link_kinematics_ref as lk
+from env_joints import dyn_joints, kin_joints
 
 pytestmark = pytest.mark.gpu
 
@@ -26,16 +27,6 @@ def inner_targets(n, seed):
     rng = np.random.default_rng(seed)
     lo, hi = np.array(INNER_LO), np.array(INNER_HI)
     return (lo + (hi - lo) * rng.random((n, 3))).astype(np.float32)
-
-
-def kin_joints(env):
-    f = env.get_state().view(torch.float32).cpu().numpy()
-    return f[12:18].T.copy(), f[6:12].T.copy()
-
-
-def dyn_joints(env):
-    d = env.get_dyn_state().cpu().numpy()
-    return d[0:6].T.copy(), d[6:12].T.copy()
 
 
 def check_jacobians(env, q, qd, joint_state=None):

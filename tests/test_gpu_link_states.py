@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import link_kinematics_ref as ref
+from env_joints import dyn_joints, kin_joints
 
 pytestmark = pytest.mark.gpu
 
@@ -36,16 +37,6 @@ def check_records(rec, q, qd):
         got, exp = rec[..., lo:lo + 3], want[..., lo:lo + 3]
         bound = tol * (1.0 + np.linalg.norm(exp, axis=-1))
         assert (np.abs(got - exp).max(axis=-1) <= bound).all(), f"velocity [{lo}:{lo + 3}] error {np.abs(got - exp).max():.3g}"
-
-
-def kin_joints(env):
-    f = env.get_state().view(torch.float32).cpu().numpy()
-    return f[12:18].T.copy(), f[6:12].T.copy()
-
-
-def dyn_joints(env):
-    d = env.get_dyn_state().cpu().numpy()
-    return d[0:6].T.copy(), d[6:12].T.copy()
 
 
 @pytest.mark.parametrize("n", [1, 37, 64, 1000, 65536])

@@ -1,0 +1,129 @@
+"""GPU test of what the per-env query kernels share (pioneer_amd/csrc/pnr_query.h): the joint sources, the one-env-per-lane
+prologue and the two tile flushes, through every call that uses them — link_states, jacobian, mass_matrix, inverse_dynamics,
+contacts (points, summary, joint_torques) and solve_ik — for each of the three joint sources.
+
+The same first envs run at n = 1 (one ragged tile of one row: the dense flush's float-by-float tail carries 143 % 4 = 3 and
+207 % 4 = 3 floats), n = 65 (a full tile and a one-row tile) and n = 130 (two full tiles and two rows).  An env's record depends
+on nothing but its own inputs, so env 0 must come out bit-identical at the three sizes and envs 0..64 at n = 65 and n = 130; a
+prologue that mixes lanes up or a flush that misplaces a tile shows as a difference.  Every output sits in front of a 64-element
+sentinel guard that the call must leave alone.  The handle's own source is written through set_state / set_dyn_state from the
+n = 130 env's first columns, so the smaller envs hold the same words (link scales, targets and all).
+
+Accuracy is not this file's business: tests/test_gpu_link_states.py, test_gpu_ik.py, test_gpu_inverse_dynamics.py and
+test_gpu_contact_query.py hold every call to its float64 reference, and test_gpu_contact_query.py's
+test_nothing_past_n_rows_and_each_output_alone asserts the guard for the caller's buffer at its own sizes."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+SIZES = (130, 65, 1)                     # the largest first: the smaller envs take its words
+GUARD = 64
+SENTINEL = -7.25
+LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416], dtype=np.float32)
+LOCAL_POINT = (0.3, -0.2, 0.5)
+KINDS = ("buffer", "kinematic_own", "dynamic_own")
+
+
+def T(x, dtype=torch.float32):
+    return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype, device="cuda:0")
+
+
+def inputs():
+    """q, qd, qdd [130, 6], IK targets [130, 3], per-env body positions [130, 3, 3]: float32, fixed"""
+    rng = np.random.default_rng(20)
+    n = SIZES[0]
+    q = rng.uniform(-0.9, 0.9, size=(n, 6)).astype(np.float32) * LIMITS
+    qd = rng.uniform(-2.0, 2.0, size=(n, 6)).astype(np.float32)
+    qdd = rng.uniform(-5.0, 5.0, size=(n, 6)).astype(np.float32)
+    lo, hi = np.array((15.0, -8.0, 2.0)), np.array((22.0, 8.0, 6.0))
+    targets = (lo + (hi - lo) * rng.random((n, 3))).astype(np.float32)
+    base = np.array([[0.0, 0.0, -2.0], [10.0, 5.0, 0.0], [15.0, 0.0, 4.0]])
+    body_pos = (base[None] + rng.uniform(-1.0, 1.0, size=(n, 3, 3))).astype(np.float32)
+    return q, qd, qdd, targets, body_pos
+
+
+def bodies():
+    from pioneer_amd.config import scene_box, scene_plane, scene_sphere
+    return [scene_plane((0.0, 0.0, 1.0), (0.0, 0.0, -2.0)), scene_box((0.5, 0.5, 5.0), (10.0, 5.0, 0.0)), scene_sphere(1.0, (15.0, 0.0, 4.0))]
+
+
+def make_env(kind, n, q, qd, words):
+    """an env of n envs whose source `kind` holds the first n rows of q | qd; (env, joint_state argument).  words: the raw state
+    of the n = 130 env of this kind once it exists ({} before)"""
+    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig
+    dyn = kind == "dynamic_own"
+    env = PioneerVectorEnv(n, device="cuda:0", seed=9, simulation_config=SimulationConfig(gravity=9.81) if dyn else None,
+                           engine_config=EngineConfig(mode="dynamic" if dyn else "kinematic", auto_reset=False, max_episode_steps=0))
+    env.reset()
+    if not words:
+        w = env.get_state()
+        if kind == "kinematic_own":
+            f = w.view(torch.float32)
+            f[6:12], f[12:18] = T(qd.T), T(q.T)
+        words["kin"] = w.clone()
+        if dyn:
+            d = env.get_dyn_state()
+            d[0:6], d[6:12] = T(q.T), T(qd.T)
+            words["dyn"] = d.clone()
+    env.set_state(words["kin"][:, :n].contiguous())
+    if dyn:
+        env.set_dyn_state(words["dyn"][:, :n].contiguous())
+    return env, (T(np.concatenate([q[:n], qd[:n]], axis=1)) if kind == "buffer" else None)
+
+
+class Guarded:
+    """output tensors that each end in a sentinel guard"""
+
+    def __init__(self):
+        self.flat = {}
+
+    def new(self, key, shape, dtype=torch.float32):
+        numel = int(np.prod(shape))
+        fill = SENTINEL if dtype.is_floating_point else int(SENTINEL)                # -7: no iteration count
+        self.flat[key] = (torch.full((numel + GUARD,), fill, dtype=dtype, device="cuda:0"), numel, fill)
+        return self.flat[key][0][:numel].view(shape)
+
+    def check(self):
+        for key, (flat, numel, fill) in self.flat.items():
+            assert bool((flat[numel:] == fill).all()), f"{key}: the guard behind the output was written"
+            assert not bool((flat[:numel] == fill).any()), f"{key}: part of the output was not written"
+
+
+def run_queries(env, js, n, q, qdd, targets, body_pos, own_target):
+    """every query call once, each output guarded; {name: tensor}"""
+    g = Guarded()
+    res = {"link_states": env.link_states(js, out=g.new("link_states", (n, 11, 13))),
+           "jacobian": env.jacobian(10, LOCAL_POINT, js, out=g.new("jacobian", (n, 6, 6))),
+           "mass_matrix": env.mass_matrix(js, out=g.new("mass_matrix", (n, 6, 6))),
+           "inverse_dynamics": env.inverse_dynamics(T(qdd[:n]), js, joint_losses=True, out=g.new("inverse_dynamics", (n, 6)))}
+    out = {"points": g.new("points", (n, 23, 9)), "summary": g.new("summary", (n, 4)), "joint_torques": g.new("joint_torques", (n, 6))}
+    res.update(env.contacts(joint_state=js, bodies=bodies(), body_positions=T(body_pos[:n]), joint_torques=True, out=out))
+    # solve_ik has no joint source; its own two sources are the caller's targets and the env's own (state words 18-20)
+    out = {"q": g.new("ik_q", (n, 6)), "residual": g.new("ik_residual", (n,)), "iterations": g.new("ik_iterations", (n,), torch.int32)}
+    ik = env.solve_ik(None if own_target else T(targets[:n]), T(0.3 * q[:n]), max_iterations=6, out=out)
+    res.update(zip(("ik_q", "ik_residual", "ik_iterations"), ik))
+    torch.cuda.synchronize()
+    g.check()
+    for key, t in res.items():
+        assert t.data_ptr() == g.flat[key][0].data_ptr(), f"{key} was not written in place"
+    return res
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_an_envs_records_are_the_same_bits_in_every_tile_shape(kind):
+    q, qd, qdd, targets, body_pos = inputs()
+    words, results = {}, {}
+    for n in SIZES:
+        env, js = make_env(kind, n, q, qd, words)
+        results[n] = run_queries(env, js, n, q, qdd, targets, body_pos, own_target=kind != "buffer")
+        env.close()
+    bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t  # noqa: E731
+    for key, big in results[130].items():
+        assert bool(torch.isfinite(big.float()).all()), key
+        assert torch.equal(bits(results[65][key]), bits(big[:65])), f"{kind} {key}: envs 0..64 differ between n = 65 and n = 130"
+        assert torch.equal(bits(results[1][key]), bits(big[:1])), f"{kind} {key}: env 0 differs between n = 1 and n = 130"
+        assert torch.equal(bits(results[1][key]), bits(results[65][key][:1])), f"{kind} {key}: env 0 differs between n = 1 and n = 65"
+    # the inputs reached the kernels: the records differ from env to env
+    assert not torch.equal(results[130]["link_states"][0], results[130]["link_states"][129])
