@@ -214,7 +214,8 @@ SIGNATURES = {
 UNITS = {
     "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_query.h",
                     "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h", "pnr_contacts.h"],
-    "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_sampler.h"],
+    "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",
+                      "pnr_mlp_gather.h", "pnr_mlp_backward.h", "pnr_mlp_wgrad.h", "pnr_mlp_adam.h", "pnr_sampler.h"],
 }
 SOURCES = sorted({f for deps in UNITS.values() for f in deps})      # every file a unit includes: what _stale() watches
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize",
@@ -223,7 +224,7 @@ HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-cont
 # the sources that define the env-side kernels (what the counter passes under profiles/ were taken on)
 ENV_KERNEL_SOURCES = ["pnr_env_kernels.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h"]
 # .. and the learner's (profiles/*learner_pmc_traffic.json: the bytes bench.py quotes in ppo_loop.roofline)
-LEARNER_KERNEL_SOURCES = ["pnr_learn.hip", "pnr_mlp.h", "pnr_ppo.h"]
+LEARNER_KERNEL_SOURCES = ["pnr_learn.hip", *[f for f in UNITS["pnr_learn.hip"] if f.startswith("pnr_mlp")], "pnr_ppo.h"]
 
 
 def source_fingerprint(files=ENV_KERNEL_SOURCES) -> str:

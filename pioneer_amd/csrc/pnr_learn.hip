@@ -1,5 +1,6 @@
-// pnr_learn.hip — the PPO host driver's kernels (pnr_mlp.h: both MLPs as bf16 MFMA kernels, weight gradients, Adam;
-// pnr_ppo.h: loss, GAE, filter moments, shuffle) and their C ABI (include/pioneer_amd.h, section "PPO driver").  A
+// pnr_learn.hip — the PPO host driver's kernels (pnr_mlp*.h: both MLPs as MFMA kernels on 16-bit operand planes, a header per kernel
+// role — forward / fused, gather, backward-data, weight gradients, Adam — over the common pnr_mlp.h; pnr_ppo.h: loss, GAE, filter
+// moments, shuffle; pnr_sampler.h: the resident rollout) and their C ABI (include/pioneer_amd.h, section "PPO driver").  A
 // translation unit of its own: it shares nothing with the env engine but the error plumbing, and the two compile in parallel.
 // gfx950 only; no CPU fallback.
 #include <hip/hip_runtime.h>
@@ -14,6 +15,11 @@
 #include "pnr_device.h"
 #include "pnr_ppo.h"
 #include "pnr_mlp.h"
+#include "pnr_mlp_forward.h"
+#include "pnr_mlp_gather.h"
+#include "pnr_mlp_backward.h"
+#include "pnr_mlp_wgrad.h"
+#include "pnr_mlp_adam.h"
 #include "pnr_sampler.h"
 
 using namespace pnr;
@@ -38,6 +44,57 @@ extern "C" int pnr_mlp_set_stamp_buffer(void* p) { g_mlp_stamps = static_cast<un
 static unsigned long long* g_wg_stamps = nullptr;      // the weight-gradient kernel's: [2 nets][4 roles][slices][8 waves][26]
 extern "C" int pnr_mlp_set_wgrad_stamp_buffer(void* p) { g_wg_stamps = static_cast<unsigned long long*>(p); return 0; }
 #endif
+
+// ---- plumbing that the calls below share.  How every call ends: the status of its launches
+static int launch_status()
+{
+    HIP_TRY(nullptr, hipGetLastError());
+    return PNR_OK;
+}
+
+// the MeanStdFilter vectors of a call: all four or none
+static int filter_check(const char* who, const float* f_loc, const float* f_inv, const float* f_lo, const float* f_hi)
+{
+    if ((f_loc || f_inv || f_lo || f_hi) && !(f_loc && f_inv && f_lo && f_hi))
+        return fail(nullptr, PNR_ERR_INVALID, "%s: the four filter vectors come together or not at all", who);
+    return PNR_OK;
+}
+
+// the instantiation for `planes` operand planes (1: bf16, 2: fp16 pairs, 3: bf16 triples; checked by the caller)
+template <bool FUSED>
+static void launch_forward(int planes, dim3 grid, hipStream_t st, const MlpFwdParams& P)
+{
+    if (planes == 1) hipLaunchKernelGGL((mlp_forward_kernel<FUSED, 1>), grid, dim3(kFwdThreads), 0, st, P);
+    else if (planes == 2) hipLaunchKernelGGL((mlp_forward_kernel<FUSED, 2>), grid, dim3(kFwdThreads), 0, st, P);
+    else hipLaunchKernelGGL((mlp_forward_kernel<FUSED, 3>), grid, dim3(kFwdThreads), 0, st, P);
+}
+static void launch_wgrad(int planes, dim3 grid, hipStream_t st, const MlpWgradParams& P)
+{
+    if (planes == 1) hipLaunchKernelGGL(mlp_wgrad_kernel<1>, grid, dim3(kWgThreads), 0, st, P);
+    else if (planes == 2) hipLaunchKernelGGL(mlp_wgrad_kernel<2>, grid, dim3(kWgThreads), 0, st, P);
+    else hipLaunchKernelGGL(mlp_wgrad_kernel<3>, grid, dim3(kWgThreads), 0, st, P);
+}
+
+// what the plain forward's two callers (pnr_mlp_forward, pnr_mlp_act) fill alike; everything else stays null
+static MlpFwdParams forward_params(int64_t batch, const float* obs, const float* f_loc, const float* f_inv, const float* f_lo, const float* f_hi,
+                                   const void* wpack, const float* bias, float* head, void* xs, int first_net, int n_nets)
+{
+    MlpFwdParams P = {};
+    P.gscale = 1.f; P.obs = obs; P.f_loc = f_loc; P.f_inv = f_inv; P.f_lo = f_lo; P.f_hi = f_hi; P.bias = bias; P.head = head;
+    P.wpack = static_cast<const __bf16*>(wpack); P.xs = static_cast<__bf16*>(xs); P.B = batch; P.first_net = first_net; P.n_nets = n_nets;
+    return P;
+}
+
+// the C ABI's twelve per-net tensors (w1, b1, w2, b2, w3, b3 of the policy net, then of the value net) handed to set(net, w1, .., b3);
+// a null one fails with "<null_msg> k of net n" before anything is set (null_msg null: the caller has checked them)
+template <class T, class SET>
+static int per_net_tensors(T* const* t, const char* null_msg, SET&& set)
+{
+    for (int i = 0; null_msg && i < 6 * kMlpNets; ++i)
+        if (!t[i]) return fail(nullptr, PNR_ERR_INVALID, "%s %d of net %d", null_msg, i % 6, i / 6);
+    for (int n = 0; n < kMlpNets; ++n) set(n, t[6 * n + 0], t[6 * n + 1], t[6 * n + 2], t[6 * n + 3], t[6 * n + 4], t[6 * n + 5]);
+    return PNR_OK;
+}
 
 extern "C" {
 
@@ -64,8 +121,7 @@ int pnr_ppo_loss(int64_t batch, const int64_t* idx, const float* head_policy, co
     if (means)
         hipLaunchKernelGGL(ppo_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial_sums, (long long)blocks,
                            (long long)batch, means, (float*)nullptr);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 // ---- the host driver's MLPs (pnr_mlp.h) ------------------------------------------------------------------------
@@ -105,16 +161,12 @@ int pnr_mlp_pack(const float* const* params, int32_t n3_policy, int32_t n3_value
     if (n3_policy < 1 || n3_policy > kMlpHead || n3_value < 1 || n3_value > kMlpHead)
         return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_pack: head widths must be in 1..16");
     MlpPackParams P;
-    for (int n = 0; n < kMlpNets; ++n) {
-        for (int k = 0; k < 6; ++k)
-            if (!params[6 * n + k]) return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_pack: null parameter %d of net %d", k, n);
-        P.net[n] = {params[6 * n + 0], params[6 * n + 1], params[6 * n + 2], params[6 * n + 3], params[6 * n + 4], params[6 * n + 5],
-                    n == 0 ? n3_policy : n3_value};
-    }
+    if (int rc = per_net_tensors(params, "pnr_mlp_pack: null parameter", [&](int n, auto... t) {
+            P.net[n] = {t..., n == 0 ? n3_policy : n3_value};
+        })) return rc;
     P.wpack = static_cast<__bf16*>(wpack); P.bias = bias; P.planes = planes;
     hipLaunchKernelGGL(mlp_pack_kernel, dim3((kPackElems + kBiasElems + 255) / 256, kMlpNets), dim3(256), 0, (hipStream_t)stream, P);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_mlp_forward(int64_t batch, const float* obs, const int64_t* idx, const float* f_loc, const float* f_inv,
@@ -126,21 +178,13 @@ int pnr_mlp_forward(int64_t batch, const float* obs, const int64_t* idx, const f
     if (planes > 1 && (xs || h1 || h2))
         return fail(nullptr, PNR_ERR_UNSUPPORTED, "pnr_mlp_forward: split operands (planes %d) save no activations: pnr_mlp_backward is bf16-only", planes);
     if (first_net < 0 || n_nets < 1 || first_net + n_nets > kMlpNets) return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_forward: bad net range");
-    if ((f_loc || f_inv || f_lo || f_hi) && !(f_loc && f_inv && f_lo && f_hi))
-        return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_forward: the four filter vectors come together or not at all");
+    if (int rc = filter_check("pnr_mlp_forward", f_loc, f_inv, f_lo, f_hi)) return rc;
     if ((h1 == nullptr) != (h2 == nullptr)) return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_forward: h1 and h2 come together");
-    MlpFwdParams P = {};
-    P.gscale = 1.f;
-    P.obs = obs; P.idx = reinterpret_cast<const long long*>(idx); P.f_loc = f_loc; P.f_inv = f_inv; P.f_lo = f_lo; P.f_hi = f_hi;
-    P.wpack = static_cast<const __bf16*>(wpack); P.bias = bias; P.head = head;
-    P.xs = static_cast<__bf16*>(xs); P.h1 = static_cast<__bf16*>(h1); P.h2 = static_cast<__bf16*>(h2);
-    P.B = batch; P.first_net = first_net; P.n_nets = n_nets;
-    const dim3 grid((unsigned)((batch + kMlpBM - 1) / kMlpBM), n_nets);
-    if (planes == 1) hipLaunchKernelGGL((mlp_forward_kernel<false, 1>), grid, dim3(kFwdThreads), 0, (hipStream_t)stream, P);
-    else if (planes == 2) hipLaunchKernelGGL((mlp_forward_kernel<false, 2>), grid, dim3(kFwdThreads), 0, (hipStream_t)stream, P);
-    else hipLaunchKernelGGL((mlp_forward_kernel<false, 3>), grid, dim3(kFwdThreads), 0, (hipStream_t)stream, P);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    MlpFwdParams P = forward_params(batch, obs, f_loc, f_inv, f_lo, f_hi, wpack, bias, head, xs, first_net, n_nets);
+    P.idx = reinterpret_cast<const long long*>(idx);
+    P.h1 = static_cast<__bf16*>(h1); P.h2 = static_cast<__bf16*>(h2);
+    launch_forward<false>(planes, dim3((unsigned)((batch + kMlpBM - 1) / kMlpBM), n_nets), (hipStream_t)stream, P);
+    return launch_status();
 }
 
 int64_t pnr_ppo_gae_scratch(int64_t n) { return n < 1 ? 0 : ((n + 63) / 64) * 8; }
@@ -173,8 +217,7 @@ int pnr_ppo_gae(int32_t T, int64_t n, const float* reward, const float* values, 
     if (stats)
         hipLaunchKernelGGL(gae_finish_kernel, dim3(1), dim3(64), 0, st, stats->scratch, blocks, (long long)T * n, stats->w_sum, stats->w_len,
                            stats->w_cnt, stats->w_max, stats->w_min, stats->adv_stats);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int64_t pnr_filter_moments_scratch(int64_t rows) { return rows < 1 ? 0 : ((rows + kFmRows - 1) / kFmRows) * 2 * kFmCols; }
@@ -191,16 +234,14 @@ int pnr_filter_moments(int64_t rows, const float* obs, const float* pivot, float
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(filter_moments_kernel, dim3((unsigned)blocks), dim3(kFmThreads), 0, st, obs, (long long)rows, pivot, scratch);
     hipLaunchKernelGGL(filter_moments_finish_kernel, dim3(kFmCols, 2), dim3(256), 0, st, scratch, blocks, (long long)rows, dsum, dsq, dn);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_filter_merge(double* dn, double* dsum, double* dsq, const float* pivot, double* n, double* mean, double* m2, void* stream)
 {
     if (!dn || !dsum || !dsq || !pivot || !n || !mean || !m2) return fail(nullptr, PNR_ERR_INVALID, "pnr_filter_merge: null argument");
     hipLaunchKernelGGL(filter_merge_kernel, dim3(1), dim3(kFmThreads), 0, (hipStream_t)stream, dn, dsum, dsq, pivot, n, mean, m2);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_filter_prepare(const double* n, const double* mean, const double* m2, double clip, float* loc, float* inv, float* lo, float* hi,
@@ -208,8 +249,7 @@ int pnr_filter_prepare(const double* n, const double* mean, const double* m2, do
 {
     if (!n || !mean || !m2 || !loc || !inv || !lo || !hi) return fail(nullptr, PNR_ERR_INVALID, "pnr_filter_prepare: null argument");
     hipLaunchKernelGGL(filter_prepare_kernel, dim3(1), dim3(kFmThreads), 0, (hipStream_t)stream, n, mean, m2, clip, loc, inv, lo, hi);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_permutation(int64_t n, uint64_t seed, uint64_t stream_id, int64_t* out, void* stream)
@@ -221,8 +261,7 @@ int pnr_permutation(int64_t n, uint64_t seed, uint64_t stream_id, int64_t* out, 
     const int half = (bits + 1) / 2 < 1 ? 1 : (bits + 1) / 2;
     hipLaunchKernelGGL(permutation_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<long long*>(out), (long long)n, half, (unsigned long long)seed, (unsigned long long)stream_id);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_mlp_act(int64_t batch, const float* obs, const float* f_loc, const float* f_inv, const float* f_lo, const float* f_hi,
@@ -234,24 +273,15 @@ int pnr_mlp_act(int64_t batch, const float* obs, const float* f_loc, const float
     if (!planes_ok(planes)) return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_act: planes must be 1, 2 or 3 (got %d)", planes);
     if (planes > 1 && xs_out)
         return fail(nullptr, PNR_ERR_UNSUPPORTED, "pnr_mlp_act: split operands (planes %d): the learner gathers its inputs from the observations, xs_out must be NULL", planes);
-    if ((f_loc || f_inv || f_lo || f_hi) && !(f_loc && f_inv && f_lo && f_hi))
-        return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_act: the four filter vectors come together or not at all");
+    if (int rc = filter_check("pnr_mlp_act", f_loc, f_inv, f_lo, f_hi)) return rc;
     if (a_max && (!env_actions || env_actions == actions))
         return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_act: clipping (a_max) needs its own env_actions buffer");
-    MlpFwdParams P = {};
-    P.gscale = 1.f;
-    P.obs = obs; P.f_loc = f_loc; P.f_inv = f_inv; P.f_lo = f_lo; P.f_hi = f_hi;
-    P.wpack = static_cast<const __bf16*>(wpack); P.bias = bias; P.head = head;
-    P.B = batch; P.first_net = 0; P.n_nets = kMlpNets;
+    // (xs_out: the nets' input as they saw it, for the learner, or null)
+    MlpFwdParams P = forward_params(batch, obs, f_loc, f_inv, f_lo, f_hi, wpack, bias, head, xs_out, 0, kMlpNets);
     P.noise = noise; P.a_max = a_max; P.mean = mean; P.log_std = log_std; P.values = values; P.actions = actions;
     P.env_actions = a_max ? env_actions : actions;
-    P.xs = static_cast<__bf16*>(xs_out);                     // the nets' input as they saw it, for the learner (or null)
-    const dim3 grid((unsigned)((batch + kMlpBM - 1) / kMlpBM), kMlpNets);
-    if (planes == 1) hipLaunchKernelGGL((mlp_forward_kernel<false, 1>), grid, dim3(kFwdThreads), 0, (hipStream_t)stream, P);
-    else if (planes == 2) hipLaunchKernelGGL((mlp_forward_kernel<false, 2>), grid, dim3(kFwdThreads), 0, (hipStream_t)stream, P);
-    else hipLaunchKernelGGL((mlp_forward_kernel<false, 3>), grid, dim3(kFwdThreads), 0, (hipStream_t)stream, P);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    launch_forward<false>(planes, dim3((unsigned)((batch + kMlpBM - 1) / kMlpBM), kMlpNets), (hipStream_t)stream, P);
+    return launch_status();
 }
 
 int pnr_ppo_rollout(pnr_handle h, int32_t T, const float* f_loc, const float* f_inv, const float* f_lo, const float* f_hi,
@@ -267,8 +297,7 @@ int pnr_ppo_rollout(pnr_handle h, int32_t T, const float* f_loc, const float* f_
     if (T < 1) return hfail("pnr_ppo_rollout: T must be >= 1");
     if (!wpack || !bias || !noise || !obs || !mean || !log_std || !values || !actions || !reward || !done)
         return hfail("pnr_ppo_rollout: null argument");
-    if ((f_loc || f_inv || f_lo || f_hi) && !(f_loc && f_inv && f_lo && f_hi))
-        return hfail("pnr_ppo_rollout: the four filter vectors come together or not at all");
+    if (int frc = filter_check("pnr_ppo_rollout", f_loc, f_inv, f_lo, f_hi)) return frc;
     if (reinterpret_cast<uintptr_t>(mean) & 7u || reinterpret_cast<uintptr_t>(log_std) & 7u || reinterpret_cast<uintptr_t>(actions) & 7u)
         return hfail("pnr_ppo_rollout: mean, log_std and actions must be 8-byte aligned");
     S.T = T;
@@ -280,8 +309,7 @@ int pnr_ppo_rollout(pnr_handle h, int32_t T, const float* f_loc, const float* f_
     S.mean = mean; S.log_std = log_std; S.values = values; S.actions = actions; S.xs = static_cast<__bf16*>(xs_out);
     DeviceGuard g(device);
     hipLaunchKernelGGL(ppo_rollout_kernel, dim3((unsigned)((S.K.n + kMlpBM - 1) / kMlpBM)), dim3(kFwdThreads), 0, (hipStream_t)stream, S);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_mlp_backward(int64_t batch, const float* g_head, const void* wpack, const void* xs, const void* h1, const void* h2,
@@ -303,21 +331,16 @@ int pnr_mlp_backward(int64_t batch, const float* g_head, const void* wpack, cons
     MlpWgradParams Wp = {};
     Wp.gscale = 1.f;
     Wp.g_head = g_head; Wp.xs = static_cast<const __bf16*>(xs); Wp.h1 = Bp.h1; Wp.h2 = Bp.h2; Wp.dz1 = Bp.dz1; Wp.dz2 = Bp.dz2;
-    Wp.slabs = slabs; Wp.B = batch; Wp.slice_rows = rows; Wp.first_net = 0; Wp.w3part = nullptr; Wp.n_nets = kMlpNets; Wp.stamps = nullptr;
-    Wp.act_plane = 0; Wp.xs_plane = 0;
-    hipLaunchKernelGGL(mlp_wgrad_kernel<1>, dim3((unsigned)slices, kWgParts, kMlpNets), dim3(kWgThreads), 0, st, Wp);
+    Wp.slabs = slabs; Wp.B = batch; Wp.slice_rows = rows; Wp.first_net = 0; Wp.n_nets = kMlpNets;      // (no w3part: role 3 reads H2, dZ2 and G)
+    launch_wgrad(1, dim3((unsigned)slices, kWgParts, kMlpNets), st, Wp);
     MlpReduceParams Rp;
     Rp.slabs = slabs; Rp.slices = (int)slices; Rp.accumulate = accumulate; Rp.scale = scale;
-    for (int n = 0; n < kMlpNets; ++n) {
-        for (int k = 0; k < 6; ++k)
-            if (!grads[6 * n + k]) return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_backward: null gradient %d of net %d", k, n);
-        Rp.gw1[n] = grads[6 * n + 0]; Rp.gb1[n] = grads[6 * n + 1]; Rp.gw2[n] = grads[6 * n + 2];
-        Rp.gb2[n] = grads[6 * n + 3]; Rp.gw3[n] = grads[6 * n + 4]; Rp.gb3[n] = grads[6 * n + 5];
-    }
+    if (int rc = per_net_tensors(grads, "pnr_mlp_backward: null gradient", [&](int n, float* w1, float* b1, float* w2, float* b2, float* w3, float* b3) {
+            Rp.gw1[n] = w1; Rp.gb1[n] = b1; Rp.gw2[n] = w2; Rp.gb2[n] = b2; Rp.gw3[n] = w3; Rp.gb3[n] = b3;
+        })) return rc;
     Rp.n3[0] = n3_policy; Rp.n3[1] = n3_value;
     hipLaunchKernelGGL(mlp_reduce_kernel, dim3((kGradElems + 255) / 256, kMlpNets), dim3(256), 0, st, Rp);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int64_t pnr_mlp_grad_floats(void) { return (int64_t)kMlpNets * kGradElems; }
@@ -351,10 +374,9 @@ static void mlp_launch_adam(const pnr_mlp_step* s, const float* grad, int slices
     A.partials = loss_rows > 0 ? s->partials : nullptr; A.loss_rows = loss_rows; A.batch = s->batch; A.means = s->means;
     A.kl_coeff = s->kl_coeff; A.ent_coeff = s->entropy_coeff; A.vf_coeff = s->vf_loss_coeff;
     A.grad = grad; A.slices = slices; A.grad_scale = scale;
-    for (int n = 0; n < kMlpNets; ++n) {
-        A.w1[n] = s->params[6 * n + 0]; A.b1[n] = s->params[6 * n + 1]; A.w2[n] = s->params[6 * n + 2];
-        A.b2[n] = s->params[6 * n + 3]; A.w3[n] = s->params[6 * n + 4]; A.b3[n] = s->params[6 * n + 5];
-    }
+    per_net_tensors(s->params, nullptr, [&](int n, float* w1, float* b1, float* w2, float* b2, float* w3, float* b3) {
+        A.w1[n] = w1; A.b1[n] = b1; A.w2[n] = w2; A.b2[n] = b2; A.w3[n] = w3; A.b3[n] = b3;
+    });
     A.n3[0] = s->n3_policy; A.n3[1] = s->n3_value;
     A.m = s->adam_m; A.v = s->adam_v; A.step = s->adam_step;
     A.lr = s->lr; A.beta1 = s->beta1; A.beta2 = s->beta2; A.eps = s->eps;
@@ -374,8 +396,7 @@ int pnr_ppo_pack_record(int64_t rows, const float* actions, const float* logp_ol
     R.actions = actions; R.logp = logp_old; R.mean = mean_old; R.log_std = log_std_old; R.adv = adv; R.vtarg = value_target;
     R.values = value_old; R.adv_mu = adv_mu; R.adv_den = adv_den; R.aos = record_rows; R.rows = rows;
     hipLaunchKernelGGL(record_pack_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_mlp_gather(int64_t batch, const int64_t* idx, const float* obs, const float* f_loc, const float* f_inv, const float* f_lo,
@@ -391,8 +412,7 @@ int pnr_mlp_gather(int64_t batch, const int64_t* idx, const float* obs, const fl
     if (batch < 1 || !(obs || xs_rows) || !(soa || record_rows) || !xs_out ||
         !actions_out || !logp_out || !mean_out || !log_std_out || !adv_out || !value_target_out || !value_old_out)
         return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_gather: null argument or empty batch");
-    if ((f_loc || f_inv || f_lo || f_hi) && !(f_loc && f_inv && f_lo && f_hi))
-        return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_gather: the four filter vectors come together or not at all");
+    if (int rc = filter_check("pnr_mlp_gather", f_loc, f_inv, f_lo, f_hi)) return rc;
     MlpGatherParams G;
     G.obs = obs; G.idx = reinterpret_cast<const long long*>(idx); G.f_loc = f_loc; G.f_inv = f_inv; G.f_lo = f_lo; G.f_hi = f_hi;
     G.actions = actions; G.logp = logp_old; G.mean = mean_old; G.log_std = log_std_old; G.adv = adv; G.vtarg = value_target;
@@ -400,8 +420,7 @@ int pnr_mlp_gather(int64_t batch, const int64_t* idx, const float* obs, const fl
     G.mean_out = mean_out; G.log_std_out = log_std_out; G.adv_out = adv_out; G.vtarg_out = value_target_out; G.values_out = value_old_out;
     G.B = batch; G.planes = planes;
     hipLaunchKernelGGL(mlp_gather_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(kMlpThreads), 0, (hipStream_t)stream, G);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_mlp_train_step(const pnr_mlp_step* s, void* stream)
@@ -413,8 +432,7 @@ int pnr_mlp_train_step(const pnr_mlp_step* s, void* stream)
         !s->value_old || !s->kl_coeff || !s->entropy_coeff || !s->head || (!s->g_head && !s->w3_partials) || !s->xs || !s->h1 || !s->h2 ||
         !s->dz1 || !s->dz2 || !s->partials || !s->slabs || !s->means)
         return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_train_step: null argument or empty batch");
-    if ((s->f_loc || s->f_inv || s->f_lo || s->f_hi) && !(s->f_loc && s->f_inv && s->f_lo && s->f_hi))
-        return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_train_step: the four filter vectors come together or not at all");
+    if ((rc = filter_check("pnr_mlp_train_step", s->f_loc, s->f_inv, s->f_lo, s->f_hi))) return rc;
     if (reinterpret_cast<uintptr_t>(s->slabs) & 15) return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_train_step: slabs must be 16-byte aligned");
     long long slices, rows;
     mlp_slicing(B, &slices, &rows);
@@ -468,32 +486,24 @@ int pnr_mlp_train_step(const pnr_mlp_step* s, void* stream)
 #if PNR_MLP_STAMPS
     F.stamps = g_mlp_stamps;
 #endif
-    if (planes == 1) hipLaunchKernelGGL((mlp_forward_kernel<true, 1>), tiles, dim3(kFwdThreads), 0, st, F);
-    else if (planes == 2) hipLaunchKernelGGL((mlp_forward_kernel<true, 2>), tiles, dim3(kFwdThreads), 0, st, F);
-    else hipLaunchKernelGGL((mlp_forward_kernel<true, 3>), tiles, dim3(kFwdThreads), 0, st, F);
+    launch_forward<true>(planes, tiles, st, F);
     if (s->flat_grad)       // no Adam launch here (the caller all-reduces first): the loss means get a small launch of their own
         hipLaunchKernelGGL(ppo_loss_finish_split_kernel, dim3(1), dim3(256), 0, st, s->partials, prow, B, s->means, (float*)nullptr,
                            s->kl_coeff, s->entropy_coeff, s->vf_loss_coeff);
     MlpWgradParams Wp = {};
-    Wp.gscale = 1.f;
     Wp.g_head = s->g_head; Wp.xs = F.xs_in ? F.xs_in : F.xs; Wp.h1 = F.h1; Wp.h2 = F.h2; Wp.dz1 = F.dz1; Wp.dz2 = F.dz2;
     Wp.slabs = s->slabs; Wp.B = B; Wp.slice_rows = rows; Wp.first_net = s->first_net; Wp.w3part = F.w3part; Wp.n_nets = nets;
-    Wp.stamps = nullptr;
 #if PNR_MLP_STAMPS
     Wp.stamps = g_wg_stamps;
 #endif
     Wp.act_plane = F.act_plane; Wp.xs_plane = F.xs_plane; Wp.gscale = F.gscale;
-    const dim3 wgrid((unsigned)slices, kWgParts, nets);
-    if (planes == 1) hipLaunchKernelGGL(mlp_wgrad_kernel<1>, wgrid, dim3(kWgThreads), 0, st, Wp);
-    else if (planes == 2) hipLaunchKernelGGL(mlp_wgrad_kernel<2>, wgrid, dim3(kWgThreads), 0, st, Wp);
-    else hipLaunchKernelGGL(mlp_wgrad_kernel<3>, wgrid, dim3(kWgThreads), 0, st, Wp);
+    launch_wgrad(planes, dim3((unsigned)slices, kWgParts, nets), st, Wp);
     if (s->flat_grad)
         hipLaunchKernelGGL(mlp_reduce_flat_kernel, dim3((nets * kGradElems + 255) / 256), dim3(256), 0, st, s->slabs, (int)slices, s->flat_grad,
                            s->first_net * kGradElems, nets * kGradElems);
     else
         mlp_launch_adam(s, s->slabs, (int)slices, 1.0f, st, prow);      // + the loss means, in the same launch
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 int pnr_mlp_adam(const pnr_mlp_step* s, const float* flat_grad, float grad_scale, void* stream)
@@ -502,8 +512,7 @@ int pnr_mlp_adam(const pnr_mlp_step* s, const float* flat_grad, float grad_scale
     if (rc) return rc;
     if (!flat_grad || (reinterpret_cast<uintptr_t>(flat_grad) & 15)) return fail(nullptr, PNR_ERR_INVALID, "pnr_mlp_adam: null or not 16-byte aligned gradient");
     mlp_launch_adam(s, flat_grad, 1, grad_scale, (hipStream_t)stream);
-    HIP_TRY(nullptr, hipGetLastError());
-    return PNR_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kFwdThreads, 2) void ppo_rollout_kernel(const Rollo
         for (int j = 0; j < CPT; ++j) {
             const int col = CPT * part + j;
             float y = x[j];
-            if (filt) y = fminf(fmaxf((y - fv[col]) * fv[kMlpInPad + col], fv[2 * kMlpInPad + col]), fv[3 * kMlpInPad + col]);
+            if (filt) y = mlp_filter_col(y, fv, col);
             x[j] = (live && col < kMlpIn) ? y : 0.f;
         }
 #pragma unroll
@@ -130,15 +130,10 @@ __global__ __launch_bounds__(kFwdThreads, 2) void ppo_rollout_kernel(const Rollo
     }
     mlp_barrier();
 
-    const auto bias16 = [&](const float* b) {                         // this wave's 16 bias values of a layer: an MFMA's C operand
-        f32x16 v;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const f32x4 q = *reinterpret_cast<const f32x4*>(b + 32 * w + 8 * k + 4 * h);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[4 * k + j] = q[j];
-        }
-        return v;
+    const auto bias16 = [&](const float* b) {                         // this wave's 16 bias values of a layer (from LDS): an MFMA's C operand
+        f32x4 q[4];
+        mlp_bias_load(b, w, h, q);
+        return mlp_bias16(q);
     };
     const auto tanh_tile = [&](const f32x16 (&acc)[kMlpCB], __bf16* tile) {
 #pragma unroll

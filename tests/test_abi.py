@@ -176,6 +176,27 @@ def test_library_built_from_other_sources_is_refused(tmp_path):
     assert r.returncode != 0 and "was built from other sources" in r.stderr, r.stdout + r.stderr[-2000:]
 
 
+def test_units_list_exactly_the_files_they_include():
+    """_lib.UNITS is what a unit's fingerprint is taken over: a header that a unit includes but the list does not name could change
+    without the library being rebuilt or refused.  The quoted #include lines, followed from the .hip file, must give the list."""
+    from pioneer_amd import _lib
+    for unit, listed in _lib.UNITS.items():
+        found, todo = set(), [unit]
+        while todo:
+            name = todo.pop()
+            if name in found:
+                continue
+            found.add(name)
+            with open(os.path.join(_lib.CSRC, name)) as f:
+                for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), flags=re.M):
+                    if os.path.normpath(os.path.join(_lib.CSRC, inc)) != os.path.normpath(_lib.HEADER):     # the C ABI header: hashed by name
+                        todo.append(inc)
+        assert found == set(listed), (unit, sorted(found ^ set(listed)))
+        assert len(listed) == len(set(listed)), unit
+    assert set(_lib.LEARNER_KERNEL_SOURCES) <= set(_lib.UNITS["pnr_learn.hip"])
+    assert {f for f in _lib.UNITS["pnr_learn.hip"] if f.startswith("pnr_mlp")} <= set(_lib.LEARNER_KERNEL_SOURCES)
+
+
 def test_spaces_and_helpers():
     from pioneer_amd.spaces import Box
     from pioneer_amd.env import arr2str

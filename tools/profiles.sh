@@ -11,7 +11,7 @@ DYN="$R/bench.py --mode dynamic --randomize --gravity 9.81 --warmup 20 --no-cpu-
 prof() { # name, rocprof args..., -- program args
   name=$1; shift
   rm -rf /tmp/p_$name
-  rocprofv3 "$@" > $O/prof_${TAG}_$name.log 2>&1 || { tail -5 $O/prof_${TAG}_$name.log; exit 1; }
+  timeout -k 10 ${PROF_TIMEOUT:-900} rocprofv3 "$@" > $O/prof_${TAG}_$name.log 2>&1 || { tail -5 $O/prof_${TAG}_$name.log; exit 1; }   # every pass under its own time limit
   find /tmp/p_$name -name '*.db' | head -1
 }
 has() { case " $WHAT " in *" $1 "*) return 0;; *) return 1;; esac; }
