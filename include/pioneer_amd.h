@@ -44,7 +44,7 @@ extern "C" {
  *      (was: two bf16 planes) in every pnr_mlp_* call; pnr_mlp_train_step checks every argument before its first launch and
  *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
  *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
- *      pnr_contact_params_default, pnr_get_contacts */
+ *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -395,6 +395,79 @@ typedef struct pnr_ik_params {
 int pnr_ik_params_default(pnr_ik_params* p);
 int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, const float* q_init,
                  float* q_out, float* residual_out, int32_t* iterations_out, void* stream);
+
+/*
+ * Pose inverse kinematics (calculateInverseKinematics(..., targetOrientation=...)) for every env, one launch: joint angles inside
+ * the URDF limits that put a point of a link on a world target AND turn the link to a target orientation (mode
+ * PNR_IK_ORIENT_FULL), or point one axis of the link along the target's (PNR_IK_ORIENT_AXIS: the roll about the axis stays
+ * free).  Damped least squares on the 6 x 6 system, the damping growing with the error; per env, independently of every other env
+ * (an env's result does not depend on the batch around it, bit for bit):
+ *
+ *     q  = clamp(q_init, r_lo, r_hi)
+ *     repeat up to max_iterations times:
+ *         e_p = target_pos - p(q)                                                 (the point of the link, as pnr_solve_ik)
+ *         (s, c) = sine vector and cosine of the rotation still to make, R(q) the link's world rotation:
+ *             FULL: s = 1/2 sum_k r_k x t_k, c = (sum_k r_k . t_k - 1) / 2        (r_k, t_k: columns of R(q), R_target; s is the
+ *                   vector of the antisymmetric part of R_target R(q)^T)
+ *             AXIS: s = u x v, c = u . v                                          (u = R(q) a, v = R_target a, a = local_axis)
+ *         angle = atan2(|s|, c) in [0, pi];   e_o = s angle / max(|s|, 1e-12)     (a world-frame rotation vector, rad)
+ *         stop (frozen from now on) if |e_p| <= tolerance and angle <= angle_tolerance        (float32)
+ *         e = [e_p ; w e_o];   J = [J_lin ; w J_ang]                              (w = orientation_weight, length per rad)
+ *         lambda^2 = damping^2 + error_damping (|e_p|^2 + w^2 angle^2)
+ *         y = (J J^T + lambda^2 I)^-1 e                                           (6 x 6, symmetric positive definite; L D L^T
+ *                                                                                  with every pivot held at >= lambda^2)
+ *         dq = J^T y;   dq *= min(1, max_step / max_j |dq_j|)
+ *         q = clamp(q + dq, r_lo, r_hi)
+ *
+ * Where the rotation axis cannot be formed (half a turn in FULL mode, opposite vectors in AXIS mode: |s| = 0 with c < 0) the
+ * max() makes the orientation step zero: outputs stay finite, `angle` stays pi, and the position part still moves the arm.
+ * The damping is error-scaled because the rest pose is a wrist singularity (joints 4 and 6 are collinear at q5 = 0): far from
+ * the target the step is cautious, near it the iteration is almost Gauss-Newton.
+ *
+ *   target_pos   [num_envs][3] float32 world positions, or NULL = each env's own target (PNR_ERR_INVALID before the first
+ *                pnr_reset or pnr_set_state)
+ *   target_quat  [num_envs][4] float32 (x, y, z, w), required; normalised by the kernel, the sign of w does not matter
+ *   q_init       [num_envs][6] float32, or NULL = the rest pose q = 0; clamped into the joint limits before the first iteration
+ *   q_out        [num_envs][6] float32 (8-byte aligned), always inside [r_lo, r_hi] of pnr_get_constants
+ *   residual_out [num_envs] float32 or NULL: |target_pos - point(q_out)| as the kernel's float32 forward kinematics sees it
+ *   angle_out    [num_envs] float32 or NULL: the angle left (rad), as the kernel sees it
+ *   iterations_out [num_envs] int32 or NULL: iterations this env took (max_iterations if it never met both tolerances)
+ *
+ * Measured basin (float64 restatement of the law, default parameters, 4 096 poses per set): starts within +-0.2 rad per joint
+ * of a solution whose |q5| >= 0.4 converge 100 % in <= 8 iterations (99 % in <= 4); AXIS-mode pointing along world +x anywhere
+ * in the box (15, -8, 2) .. (22, 8, 6) converges 100 % from the rest pose in <= 6 iterations.  From the rest pose to the full
+ * pose of random joints at 0.8-0.9 of the limits 88 % converge (the rest stop in local minima at joint limits or on the other
+ * wrist branch; multi-start search is the caller's); with lambda = 1 and no error term (pnr_solve_ik's damping) only 74-76 % do,
+ * and 98 % of the near starts.  orientation_weight 1, 3, 10, 30 give 94, 91, 88, 89 % from the rest pose and 100 % near.
+ *
+ * PNR_ERR_INVALID, nothing launched and no output touched, for: a null handle, params, q_out or target_quat, a wrong
+ * struct_size, link outside 0..10, a mode outside {0, 1}, max_iterations outside 1..1024, a non-finite or non-positive damping,
+ * max_step or orientation_weight, a negative or non-finite error_damping, tolerance or angle_tolerance, a non-finite local_point,
+ * a non-finite or zero local_axis, misaligned pointers (q_out 8 bytes, the others 4), target_pos NULL before the first reset.
+ * Non-finite targets give non-finite residuals, unchecked; the loop is bounded by max_iterations.  float32 arithmetic,
+ * asynchronous on `stream`, no allocation, no synchronisation: capturable into a graph.
+ */
+enum pnr_ik_orient {
+    PNR_IK_ORIENT_FULL = 0,   /* the link's full orientation */
+    PNR_IK_ORIENT_AXIS = 1    /* only local_axis is aligned with the target's; the roll about it is free */
+};
+typedef struct pnr_ik_pose_params {
+    uint32_t struct_size;       /* sizeof(pnr_ik_pose_params) */
+    int32_t  link;              /* 0..10; default 10 (robot:pointer) */
+    double   local_point[3];    /* a point in the link's frame; default 0 */
+    int32_t  max_iterations;    /* 1..1024; default 32 */
+    int32_t  mode;              /* PNR_IK_ORIENT_FULL (default) or PNR_IK_ORIENT_AXIS */
+    double   local_axis[3];     /* AXIS mode: the axis in the link's frame, any length > 0 (normalised by the host); default (1, 0, 0) */
+    double   damping;           /* > 0, default 0.03 */
+    double   error_damping;     /* >= 0, default 0.01 */
+    double   orientation_weight; /* w > 0, length per rad, default 10 */
+    double   max_step;          /* > 0, rad: cap on the largest joint change of one iteration, default 0.5 */
+    double   tolerance;         /* >= 0, length; default 1e-3 */
+    double   angle_tolerance;   /* >= 0, rad; default 1e-3 */
+} pnr_ik_pose_params;
+int pnr_ik_pose_params_default(pnr_ik_pose_params* p);
+int pnr_solve_ik_pose(pnr_handle h, const pnr_ik_pose_params* p, const float* target_pos, const float* target_quat, const float* q_init,
+                      float* q_out, float* residual_out, float* angle_out, int32_t* iterations_out, void* stream);
 
 /*
  * calculateInverseDynamics for every env, one launch: the joint torques of

@@ -89,6 +89,17 @@ class PnrIkParams(C.Structure):
                 ("reserved", C.c_int32), ("damping", C.c_double), ("max_step", C.c_double), ("tolerance", C.c_double)]
 
 
+IK_ORIENT_FULL, IK_ORIENT_AXIS = 0, 1      # pnr_ik_pose_params.mode
+
+
+class PnrIkPoseParams(C.Structure):
+    """pnr_ik_pose_params of include/pioneer_amd.h (pnr_solve_ik_pose's point, orientation mode, damping, weight, tolerances)."""
+    _fields_ = [("struct_size", C.c_uint32), ("link", C.c_int32), ("local_point", C.c_double * 3), ("max_iterations", C.c_int32),
+                ("mode", C.c_int32), ("local_axis", C.c_double * 3), ("damping", C.c_double), ("error_damping", C.c_double),
+                ("orientation_weight", C.c_double), ("max_step", C.c_double), ("tolerance", C.c_double),
+                ("angle_tolerance", C.c_double)]
+
+
 class PnrConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
@@ -179,6 +190,8 @@ SIGNATURES = {
     "pnr_mass_matrix": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_ik_params_default": (C.c_int, [C.POINTER(PnrIkParams)]),
     "pnr_solve_ik": (C.c_int, [_VP, C.POINTER(PnrIkParams), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pnr_ik_pose_params_default": (C.c_int, [C.POINTER(PnrIkPoseParams)]),
+    "pnr_solve_ik_pose": (C.c_int, [_VP, C.POINTER(PnrIkPoseParams)] + [_VP] * 8),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
     "pnr_contact_params_default": (C.c_int, [C.POINTER(PnrContactParams)]),
     "pnr_get_contacts": (C.c_int, [_VP, _VP, C.POINTER(PnrContactParams), _VP, _VP, _VP, _VP, _VP]),

@@ -881,6 +881,66 @@ int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, 
     return launch_env_waves(h, stream, kJointSrcBuffer, [](auto) { return ik_kernel; }, A);      // (no joint source: one form)
 }
 
+int pnr_ik_pose_params_default(pnr_ik_pose_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_ik_pose_params_default: null params");
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_ik_pose_params);
+    p->link = kNumLinks - 1;
+    p->max_iterations = 32;
+    p->mode = PNR_IK_ORIENT_FULL;
+    p->local_axis[0] = 1.0;
+    p->damping = 0.03;
+    p->error_damping = 0.01;
+    p->orientation_weight = 10.0;
+    p->max_step = 0.5;
+    p->tolerance = 1e-3;
+    p->angle_tolerance = 1e-3;
+    return PNR_OK;
+}
+
+int pnr_solve_ik_pose(pnr_handle h, const pnr_ik_pose_params* p, const float* target_pos, const float* target_quat, const float* q_init,
+                      float* q_out, float* residual_out, float* angle_out, int32_t* iterations_out, void* stream)
+{
+    const char* call = "pnr_solve_ik_pose";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "%s: null params", call);
+    if (!q_out) return fail(h, PNR_ERR_INVALID, "%s: null q_out", call);
+    if (!target_quat) return fail(h, PNR_ERR_INVALID, "%s: null target_quat", call);
+    if (p->struct_size != sizeof(pnr_ik_pose_params))
+        return fail(h, PNR_ERR_INVALID, "%s: params struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_ik_pose_params));
+    if (p->link < 0 || p->link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "%s: link %d outside 0..%d", call, p->link, kNumLinks - 1);
+    if (p->mode != PNR_IK_ORIENT_FULL && p->mode != PNR_IK_ORIENT_AXIS)
+        return fail(h, PNR_ERR_INVALID, "%s: mode %d outside {0, 1} (full orientation, one axis)", call, p->mode);
+    if (p->max_iterations < 1 || p->max_iterations > 1024)
+        return fail(h, PNR_ERR_INVALID, "%s: max_iterations %d outside 1..1024", call, p->max_iterations);
+    const struct { double v; const char* name; bool zero_ok; } scalars[] = {
+        {p->damping, "damping", false}, {p->max_step, "max_step", false}, {p->orientation_weight, "orientation_weight", false},
+        {p->error_damping, "error_damping", true}, {p->tolerance, "tolerance", true}, {p->angle_tolerance, "angle_tolerance", true}};
+    for (const auto& s : scalars)
+        if (!(std::isfinite(s.v) && (s.zero_ok ? s.v >= 0 : s.v > 0)))
+            return fail(h, PNR_ERR_INVALID, "%s: %s must be finite and %s 0", call, s.name, s.zero_ok ? ">=" : ">");
+    if (!finite_all(p->local_point, 3)) return fail(h, PNR_ERR_INVALID, "%s: non-finite local_point", call);
+    const double* ax = p->local_axis;
+    const double axis_len = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+    if (!finite_all(ax, 3) || !std::isfinite(axis_len) || !(axis_len > 0))
+        return fail(h, PNR_ERR_INVALID, "%s: local_axis must be finite and not zero", call);
+    if (const int rc = check_aligned(h, call, {{q_out, "q_out", 8}, {target_pos, "target_pos", 4}, {target_quat, "target_quat", 4},
+                                               {q_init, "q_init", 4}, {residual_out, "residual_out", 4}, {angle_out, "angle_out", 4},
+                                               {iterations_out, "iterations_out", 4}})) return rc;
+    if (!target_pos && !has_own_target(h)) return before_first_reset(h, call, ": the target comes from the state");
+    IkPoseArgs A;
+    A.target = target_pos; A.state = h->state; A.quat = target_quat; A.q_init = q_init;
+    A.q_out = q_out; A.residual = residual_out; A.angle = angle_out; A.iterations = iterations_out;
+    A.n = h->n;
+    A.point = chain_point(p->link, p->local_point);
+    A.max_iter = p->max_iterations; A.axis_mode = p->mode == PNR_IK_ORIENT_AXIS;
+    A.axis = {(float)(ax[0] / axis_len), (float)(ax[1] / axis_len), (float)(ax[2] / axis_len)};
+    A.damping2 = (float)(p->damping * p->damping); A.error_damping = (float)p->error_damping; A.weight = (float)p->orientation_weight;
+    A.max_step = (float)p->max_step; A.tol = (float)p->tolerance; A.angle_tol = (float)p->angle_tolerance;
+    return launch_env_waves(h, stream, kJointSrcBuffer, [](auto) { return ik_pose_kernel; }, A);  // (no joint source: one form)
+}
+
 int pnr_contact_params_default(pnr_contact_params* p)
 {
     if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_contact_params_default: null params");

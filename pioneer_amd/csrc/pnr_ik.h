@@ -1,8 +1,9 @@
-// pnr_ik.h — pnr_get_jacobian and pnr_solve_ik: the Jacobian of a point of a URDF link (PyBullet's calculateJacobian) and
-// position-only damped-least-squares inverse kinematics (calculateInverseKinematics without an orientation) for every env,
-// one launch each.  Included by pnr_api.hip only; it adds two kernels and edits none of the others.
+// pnr_ik.h — pnr_get_jacobian, pnr_solve_ik and pnr_solve_ik_pose: the Jacobian of a point of a URDF link (PyBullet's
+// calculateJacobian), position-only damped-least-squares inverse kinematics (calculateInverseKinematics without an orientation)
+// and pose inverse kinematics (with targetOrientation: a full orientation or one axis to point) for every env, one launch each.
+// Included by pnr_api.hip only; it adds three kernels and edits none of the others.
 //
-// Shape of both: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  The host resolves (link,
+// Shape of all: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  The host resolves (link,
 // local_point) into the moving body that carries the link and the point's offset in that body's frame; both arrive as
 // kernel arguments, so every `J <= body` test below is a scalar branch.
 //
@@ -14,6 +15,15 @@
 // a ballot finds every lane frozen.  The pose code exists ONCE in the loop (the residual of the result is the loop's own last
 // pose), so a lane's arithmetic does not depend on how many trips its neighbours need: results are bit-identical whatever
 // the batch around an env.  Outputs are 32 B per env: plain per-lane stores (three float2 of q, one float, one int).
+//
+// ik_pose_kernel: ik_kernel's shape with a 6 x 6 system.  The target's rotation matrix is formed once from the normalised
+// quaternion; per trip chain_jacobian also hands out the carrying body's rotation R (= the link's: every fixed joint has rpy 0),
+// the rotation still to make comes as its sine vector s and cosine c (FULL: s = 1/2 sum_k r_k x t_k over the columns of R and
+// R_target, c = (trace - 1) / 2; AXIS: s = u x v, c = u . v), angle = atan2(|s|, c), e_o = s angle / max(|s|, 1e-12): where
+// the axis cannot be formed (half a turn, opposite vectors) the orientation step is zero and everything stays finite.  The
+// orientation weight is folded into the angular rows once; the 21 unique entries of J J^T + lambda^2 I are summed joint by
+// joint and solved by an unrolled L D L^T whose pivots are held at >= lambda^2 (their exact-arithmetic floor: float32 rounding
+// of a near-singular J J^T must not make one zero or negative).  Outputs are 36 B per env.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,8 +42,9 @@ struct ChainPoint { int body; float ox, oy, oz; };
 
 // The chain's Jacobian at the joint angles whose cosines / sines are c, s: per joint J <= body the world axis (ang) and
 // axis x (point - origin) (lin); exactly zero for the joints beyond the body.  point: the point's world position.
+// Rbody, where asked for: the body's world rotation (the identity for the static base).
 __device__ __forceinline__ void chain_jacobian(const float (&c)[kDof], const float (&s)[kDof], const ChainPoint& P,
-                                               V3 (&lin)[kDof], V3 (&ang)[kDof], V3& point)
+                                               V3 (&lin)[kDof], V3 (&ang)[kDof], V3& point, M3* Rbody = nullptr)
 {
     const V3 off = {P.ox, P.oy, P.oz};
     V3 org[kDof];
@@ -58,6 +69,7 @@ __device__ __forceinline__ void chain_jacobian(const float (&c)[kDof], const flo
         lin[J] = {0.f, 0.f, 0.f};
         if (J <= P.body) lin[J] = cross(ang[J], point - org[J]);
     });
+    if (Rbody) *Rbody = R;
 }
 
 template <int SRC>
@@ -168,6 +180,161 @@ __global__ __launch_bounds__(kWave) void ik_kernel(const IkArgs A)
     float2* qo = reinterpret_cast<float2*>(A.q_out) + 3 * e;
     qo[0] = make_float2(q[0], q[1]); qo[1] = make_float2(q[2], q[3]); qo[2] = make_float2(q[4], q[5]);
     if (A.residual) A.residual[e] = dist;
+    if (A.iterations) A.iterations[e] = iters;
+}
+
+struct IkPoseArgs {
+    const float* target;       // [n][3], or null: the env's own target (state words 18-20)
+    const float4* state;       // the handle's state planes (read only when target is null)
+    const float* quat;         // [n][4] x, y, z, w; normalised here
+    const float* q_init;       // [n][6], or null: the rest pose
+    float* q_out;              // [n][6], 8-byte aligned
+    float* residual;           // [n] or null
+    float* angle;              // [n] or null
+    int* iterations;           // [n] or null
+    long long n;
+    ChainPoint point;
+    int max_iter, axis_mode;   // axis_mode: PNR_IK_ORIENT_AXIS (align `axis` only), else the full orientation
+    V3 axis;                   // unit, in the link's frame
+    float damping2, error_damping, weight, max_step, tol, angle_tol;
+};
+
+constexpr float kIkSineFloor = 1e-12f;                           // below it the rotation axis is not formed: a zero step
+template <int I, int J> constexpr int kLow = I * (I + 1) / 2 + J;   // entry (I, J <= I) of a packed lower triangle
+
+// The iteration law of include/pioneer_amd.h (pnr_solve_ik_pose), one env per lane.
+__global__ __launch_bounds__(kWave) void ik_pose_kernel(const IkPoseArgs A)
+{
+    constexpr int kPose = 6, kTriN = kPose * (kPose + 1) / 2;
+    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
+    const bool live = e < A.n;
+    float q[kDof];
+    V3 tgt = {0.f, 0.f, 0.f};
+    float qx = 0.f, qy = 0.f, qz = 0.f, qw = 1.f;
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) q[i] = 0.f;
+    if (live) {
+        if (A.target) { const float* t = A.target + 3 * e; tgt = {t[0], t[1], t[2]}; }
+        else { const float4 w = A.state[2 * (2 * A.n) + 2 * e]; tgt = {w.y, w.z, w.w}; }
+        const float* tq = A.quat + 4 * e;
+        qx = tq[0]; qy = tq[1]; qz = tq[2]; qw = tq[3];
+        if (A.q_init) {
+            const float* qi = A.q_init + kDof * e;
+#pragma unroll
+            for (int i = 0; i < kDof; ++i) q[i] = qi[i];
+        }
+    }
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        q[J] = fminf(fmaxf(q[J], limit_lo(J)), limit_hi(J));
+    });
+    // the target's rotation, columns t0 t1 t2 (the quaternion's sign cancels in every product); in AXIS mode only v = R_target a
+    const float qinv = 1.0f / sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
+    qx *= qinv; qy *= qinv; qz *= qinv; qw *= qinv;
+    const V3 t0 = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy + qz * qw), 2.f * (qx * qz - qy * qw)};
+    const V3 t1 = {2.f * (qx * qy - qz * qw), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz + qx * qw)};
+    const V3 t2 = {2.f * (qx * qz + qy * qw), 2.f * (qy * qz - qx * qw), 1.f - 2.f * (qx * qx + qy * qy)};
+    const V3 tv = A.axis.x * t0 + A.axis.y * t1 + A.axis.z * t2;
+    bool frozen = !live;
+    int iters = 0;
+    float dist = 0.f, angle = 0.f;
+    for (int it = 0; ; ++it) {
+        float c[kDof], s[kDof];
+#pragma unroll
+        for (int i = 0; i < kDof; ++i) sincos_bounded(q[i], s[i], c[i]);     // q is inside the limits
+        V3 lin[kDof], ang[kDof], point;
+        M3 R;
+        chain_jacobian(c, s, A.point, lin, ang, point, &R);
+        const V3 err = tgt - point;
+        const float dist2 = dot(err, err);
+        dist = sqrtf(dist2);
+        V3 sv;
+        float cs;
+        if (A.axis_mode) {
+            const V3 u = mul(R, A.axis);
+            sv = cross(u, tv); cs = dot(u, tv);
+        } else {
+            const V3 r0 = col(R, 0), r1 = col(R, 1), r2 = col(R, 2);
+            sv = 0.5f * (cross(r0, t0) + cross(r1, t1) + cross(r2, t2));
+            cs = 0.5f * (dot(r0, t0) + dot(r1, t1) + dot(r2, t2) - 1.f);
+        }
+        const float sn = sqrtf(dot(sv, sv));
+        angle = atan2f(sn, cs);
+        if (it == A.max_iter) break;                                         // the pose of the result: its residuals
+        frozen = frozen || (dist <= A.tol && angle <= A.angle_tol);
+        if (__builtin_amdgcn_ballot_w64(!frozen) == 0) break;
+        // e = [e_p ; w e_o], rows g[J] = column J of [J_lin ; w J_ang]
+        const float wa = A.weight * angle;
+        const float ko = wa * fast_rcp(fmaxf(sn, kIkSineFloor));
+        const float er[kPose] = {err.x, err.y, err.z, ko * sv.x, ko * sv.y, ko * sv.z};
+        const float lambda2 = A.damping2 + A.error_damping * (dist2 + wa * wa);
+        float g[kDof][kPose];
+        static_for<kDof>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            g[J][0] = lin[J].x; g[J][1] = lin[J].y; g[J][2] = lin[J].z;
+            g[J][3] = A.weight * ang[J].x; g[J][4] = A.weight * ang[J].y; g[J][5] = A.weight * ang[J].z;
+        });
+        // a = J J^T + lambda^2 I, its lower triangle: symmetric positive definite, every pivot of L D L^T >= lambda^2
+        float a[kTriN];
+        static_for<kPose>([&](auto ic) {
+            constexpr int I = decltype(ic)::value;
+            static_for<I + 1>([&](auto kc) {
+                constexpr int K = decltype(kc)::value;
+                float sum = I == K ? lambda2 : 0.f;
+                static_for<kDof>([&](auto jc) { constexpr int J = decltype(jc)::value; sum += g[J][I] * g[J][K]; });
+                a[kLow<I, K>] = sum;
+            });
+        });
+        float u[kTriN], l[kTriN], inv[kPose];                                // u_ik = l_ik d_k
+        static_for<kPose>([&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            float d = a[kLow<K, K>];
+            static_for<K>([&](auto mc_) { constexpr int M = decltype(mc_)::value; d -= l[kLow<K, M>] * u[kLow<K, M>]; });
+            inv[K] = fast_rcp(fmaxf(d, lambda2));
+            static_for<kPose>([&](auto ic) {
+                constexpr int I = decltype(ic)::value;
+                if constexpr (I > K) {
+                    float t = a[kLow<I, K>];
+                    static_for<K>([&](auto mc_) { constexpr int M = decltype(mc_)::value; t -= l[kLow<I, M>] * u[kLow<K, M>]; });
+                    u[kLow<I, K>] = t;
+                    l[kLow<I, K>] = t * inv[K];
+                }
+            });
+        });
+        float z[kPose], y[kPose];
+        static_for<kPose>([&](auto ic) {
+            constexpr int I = decltype(ic)::value;
+            z[I] = er[I];
+            static_for<I>([&](auto mc_) { constexpr int M = decltype(mc_)::value; z[I] -= l[kLow<I, M>] * z[M]; });
+        });
+        static_for<kPose>([&](auto ic) {
+            constexpr int I = kPose - 1 - decltype(ic)::value;
+            y[I] = z[I] * inv[I];
+            static_for<kPose>([&](auto mc_) {
+                constexpr int M = decltype(mc_)::value;
+                if constexpr (M > I) y[I] -= l[kLow<M, I>] * y[M];
+            });
+        });
+        float dq[kDof], big = 0.f;
+        static_for<kDof>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            dq[J] = 0.f;
+            static_for<kPose>([&](auto ic) { constexpr int I = decltype(ic)::value; dq[J] += g[J][I] * y[I]; });
+            big = fmaxf(big, fabsf(dq[J]));
+        });
+        const float scale = big > A.max_step ? A.max_step * fast_rcp(big) : 1.f;
+        static_for<kDof>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            const float qn = fminf(fmaxf(q[J] + scale * dq[J], limit_lo(J)), limit_hi(J));
+            q[J] = frozen ? q[J] : qn;
+        });
+        iters += frozen ? 0 : 1;
+    }
+    if (!live) return;
+    float2* qo = reinterpret_cast<float2*>(A.q_out) + 3 * e;
+    qo[0] = make_float2(q[0], q[1]); qo[1] = make_float2(q[2], q[3]); qo[2] = make_float2(q[4], q[5]);
+    if (A.residual) A.residual[e] = dist;
+    if (A.angle) A.angle[e] = angle;
     if (A.iterations) A.iterations[e] = iters;
 }
 

@@ -202,6 +202,17 @@ class PioneerKinematicEnv(compat.GymEnv):
         q, residual, _ = self._vec.solve_ik(target=tgt)
         return q[0].double().cpu().numpy(), float(residual[0].item())
 
+    def solve_ik_pose(self, target_orientation, target_position: Optional[Tuple[float, float, float]] = None,
+                      align_axis: Optional[Tuple[float, float, float]] = None) -> Tuple[np.ndarray, float, float]:
+        """calculateInverseKinematics with a targetOrientation for robot:pointer (PioneerVectorEnv.solve_ik_pose from the rest
+        pose): the joint positions (float64 [6], inside the joint limits) that put the pointer on ``target_position`` (default:
+        the env's target) with the orientation ``target_orientation`` (quaternion x, y, z, w), or with only its local
+        ``align_axis`` along the target's; the distance and the angle (rad) left."""
+        quat = np.asarray(target_orientation, dtype=np.float32).reshape(1, 4)
+        tgt = None if target_position is None else np.asarray(target_position, dtype=np.float32).reshape(1, 3)
+        q, residual, angle, _ = self._vec.solve_ik_pose(quat, target=tgt, align_axis=align_axis)
+        return q[0].double().cpu().numpy(), float(residual[0].item()), float(angle[0].item())
+
     def render(self, mode="human"):                                        # bullet_env.py:156-185
         if mode == "human":
             return None

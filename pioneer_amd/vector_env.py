@@ -314,6 +314,44 @@ class PioneerVectorEnv:
         self._chk(self.lib.pnr_solve_ik(self._h, p, _ptr(tgt), _ptr(qi), _ptr(q), _ptr(res), _ptr(its), self._stream()))
         return q, res, its
 
+    def solve_ik_pose(self, target_orientation, target=None, q_init=None, link=10, local_point=None, align_axis=None,
+                      max_iterations=32, damping=0.03, error_damping=0.01, orientation_weight=10.0, max_step=0.5, tolerance=1e-3,
+                      angle_tolerance=1e-3, out=None):
+        """calculateInverseKinematics with a targetOrientation for every env, one launch (pnr_solve_ik_pose): joint angles inside
+        the limits that put ``local_point`` of ``link`` on ``target`` (``[N, 3]``; None = each env's own target) and turn the
+        link to ``target_orientation`` (``[N, 4]`` quaternions x, y, z, w; normalised by the kernel).  ``align_axis`` None asks
+        for the full orientation; a 3-vector in the link's frame asks only for that axis to point along the target's (the roll
+        about it stays free).  The error-damped least-squares iteration of include/pioneer_amd.h from ``q_init`` (``[N, 6]``;
+        None = the rest pose: pointing tasks converge from it, 88 % of full poses do; starts near a solution all converge).
+        Returns ``(q [N, 6] float32, residual [N] float32, angle [N] float32 rad, iterations [N] int32)``; iterations ==
+        max_iterations where the tolerances were never met.  ``out`` may carry preallocated ``q`` / ``residual`` / ``angle`` /
+        ``iterations`` tensors, written in place.  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        p = _lib.PnrIkPoseParams()
+        self._chk(self.lib.pnr_ik_pose_params_default(p))
+        p.link, p.max_iterations = int(link), int(max_iterations)
+        if local_point is not None:
+            for k in range(3):
+                p.local_point[k] = float(local_point[k])
+        if align_axis is not None:
+            p.mode = _lib.IK_ORIENT_AXIS
+            for k in range(3):
+                p.local_axis[k] = float(align_axis[k])
+        p.damping, p.error_damping, p.orientation_weight = float(damping), float(error_damping), float(orientation_weight)
+        p.max_step, p.tolerance, p.angle_tolerance = float(max_step), float(tolerance), float(angle_tolerance)
+        quat = self._in(target_orientation, (n, 4), torch.float32, "target_orientation")
+        tgt = None if target is None else self._in(target, (n, 3), torch.float32, "target")
+        qi = None if q_init is None else self._in(q_init, (n, 6), torch.float32, "q_init")
+        out = out or {}
+        q = self._out(out, "q", (n, 6))
+        res = self._out(out, "residual", (n,))
+        ang = self._out(out, "angle", (n,))
+        its = self._out(out, "iterations", (n,), torch.int32)
+        self._chk(self.lib.pnr_solve_ik_pose(self._h, p, _ptr(tgt), _ptr(quat), _ptr(qi), _ptr(q), _ptr(res), _ptr(ang), _ptr(its),
+                                             self._stream()))
+        return q, res, ang, its
+
     def target_reachable(self, within=None):
         """bool ``[N]``: can the pointer get within ``within`` (default the config's ``done_distance``) of the env's own target
         without leaving the joint limits?  ``solve_ik()`` from the rest pose with all defaults; about 3 % of the reference's
