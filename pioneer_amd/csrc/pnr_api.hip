@@ -524,6 +524,12 @@ static inline unsigned step_grid_for(long long n, int T)
     return tiles < c ? tiles : c;
 }
 static inline bool step_one_pass(long long n, int T) { return T == 1 && step_grid_for(n, T) == grid_for(n); }
+// .. and whether the one-pass form takes the row-ordered obs path (obs_tile_rows_out; env-major observations only): when the launch
+// has more waves than SIMDs (256 CUs x 4), i.e. 32 768 < n <= 65 536.  There two waves share a SIMD, the launch is bound by its store
+// stream and the early flush shortens it (-4.3 % at 65 536 envs, -2.6 % at 49 152); up to one wave per SIMD the longer per-wave
+// chain is what the launch waits for (equal at 32 768, +17 % at 16 384, +20 % at 8 192).
+constexpr unsigned kOneWavePerSimd = 1024;
+static inline bool step_row_pass(long long n, int T) { return step_one_pass(n, T) && grid_for(n) > kOneWavePerSimd; }
 
 int pnr_reset(pnr_handle h, const uint8_t* mask, const float* joint_pos, const float* target_pos,
               float* obs_out, void* stream)
@@ -570,9 +576,10 @@ static int launch_step(pnr_handle h, int T, const float* actions, float* obs, fl
     const float mvr = (float)h->cfg.max_v_to_r;
     with_bool(oem, [&](auto O) { with_bool(aem, [&](auto A) {
         if (h->cfg.mode != PNR_MODE_DYNAMIC) {
-            with_bool(step_one_pass(h->n, T), [&](auto S) {
-                hipLaunchKernelGGL((step_kernel<O(), A(), S()>), grid, block, 0, st, P.state, P.actions, P.n, P.dt, P.eps, mvr, P);
-            });
+            with_bool(step_one_pass(h->n, T), [&](auto S) { with_bool(step_row_pass(h->n, T), [&](auto R) {
+                hipLaunchKernelGGL((step_kernel<O(), A(), S(), R() && S() && O()>), grid, block, 0, st, P.state, P.actions, P.n, P.dt,
+                                   P.eps, mvr, P);
+            }); });
             return;
         }
         // one launch: the dynamics kernels run the sub-steps one env per lane, then finish each step (reward / TimeLimit /

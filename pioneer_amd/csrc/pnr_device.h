@@ -610,4 +610,118 @@ __device__ __forceinline__ void obs_tile_out(const LaneConsts& K, const LaneStat
     else flush_feature_tile(tile, obs + tile0, n, nvalid, lane);
 }
 
+// ---- the one-pass step_kernel's obs path for the env-major tile: the linear entries first, then the trig in ROW order with the flush under it ----
+// obs_tile_out finishes all 32 rows at once — every lane evaluates the twelve sin / cos pairs of its own half row before any
+// lane has a complete row — so no obs store leaves before the last of them.  Here a lane writes in phase 1 only what needs no new
+// trig: r, cos r, sin r, the tail, and the ARGUMENTS dlo, dhi, v, a (the floats emit_obs forms) in their own columns 54.., 72..,
+// 90.., 108...  Phase 2 takes the tile's 32 x 24 arguments as one flat list j = 64 it + lane (row j / 24, argument j % 24, cos
+// to column + 6, sin to column + 12), twelve unrolled iterations: after iteration `it` the rows below 64 (it + 1) / 24 are
+// complete, and every 1-KiB chunk of the tile inside them goes out right then, the rest of the trig running under the stores.
+// Each argument goes through the function emit_obs gives it (sincos_bounded; sincos_any for a): the same bits.
+constexpr int kTrigArgs = 4 * kDof;                                  // per row: dlo, dhi, v, a of six joints
+constexpr int kTrigIters = kEnvsPerWave * kTrigArgs / kWave;         // 12
+constexpr int kChunkFloats = 4 * kWave;                              // one wave-wide dwordx4 store
+// (row, argument) of iteration it + 3 is that of iteration it, eight rows on: three tile offsets per lane, the rest immediates
+constexpr int kTrigPeriod = 3, kTrigPeriodRows = kTrigPeriod * kWave / kTrigArgs;
+static_assert(kEnvsPerWave * kTrigArgs == kTrigIters * kWave && kTrigPeriod * kWave == kTrigPeriodRows * kTrigArgs &&
+              kTrigIters % kTrigPeriod == 0, "the row pass is written for 32 rows of 24 arguments on 64 lanes");
+
+// whole chunks inside the rows that are complete after `iters` iterations
+constexpr int row_pass_chunks(int iters) { return (kWave * iters / kTrigArgs) * kObsDim / kChunkFloats; }
+
+// where this lane's arguments sit
+struct RowPassLane {
+    int off[kTrigPeriod];      // tile offset of the argument of iterations 0, 1, 2
+    bool is_a[kTrigPeriod];    // .. and whether it is an action (sincos_any)
+};
+
+__device__ __forceinline__ RowPassLane row_pass_lane(int lane)
+{
+    RowPassLane L;
+#pragma unroll
+    for (int k = 0; k < kTrigPeriod; ++k) {
+        const int j = kWave * k + lane, row = j / kTrigArgs, arg = j - kTrigArgs * row, grp = arg / kDof;
+        L.off[k] = row * kObsDim + 54 + arg + 2 * kDof * grp;             // column 54 + 18 grp + joint
+        L.is_a[k] = grp == 3;
+    }
+    return L;
+}
+
+// dst: the tile's place in the batch, obs + tile0 * 137.  emit / flush as in obs_tile_out: no emit skips both phases.
+__device__ __forceinline__ void obs_tile_rows_out(const LaneConsts& K, const LaneState& s, const Pose& q, float* tile, int el, int p,
+                                                  int lane, float* __restrict__ dst, int nvalid, bool emit = true, bool flush = true)
+{
+    // -- phase 1: this lane's half row, everything but the new sin / cos
+    if (emit) {
+        SinkLdsTile out = tile_sink<true>(tile, el, p);
+#pragma unroll
+        for (int i = 0; i < kJpl; ++i) {
+            const float lim = K.lim[i];
+            out.putj(0 + i, s.r[i]); out.putj(6 + i, q.c[i]); out.putj(12 + i, q.s[i]);
+            out.putj(54 + i, s.r[i] - (-lim));                            // float32 subtractions, :191-192
+            out.putj(72 + i, lim - s.r[i]);
+            out.putj(90 + i, s.v[i]);
+            out.putj(108 + i, s.a[i]);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out.putt(126 + k, 132 + k, p ? q.diff[k] : q.ptr[k]);
+        out.putt(129, 135, p ? q.dist : s.tgt[0]);
+        out.putt(130, 136, p ? s.pot : s.tgt[1]);
+        out.putt0(131, s.tgt[2]);
+    }
+    wave_lds_sync();
+
+    // -- phase 2: the arguments of all twelve iterations leave LDS first (their columns are not written below)
+    const RowPassLane L = row_pass_lane(lane);
+    float x[kTrigIters];
+    if (emit) {
+#pragma unroll
+        for (int it = 0; it < kTrigIters; ++it) x[it] = tile[L.off[it % kTrigPeriod] + (it / kTrigPeriod) * kTrigPeriodRows * kObsDim];
+    }
+    const int total = nvalid * kObsDim;
+    const bool vec = (reinterpret_cast<uintptr_t>(dst) & 15u) == 0;
+    const int nchunk = (flush && vec) ? total / kChunkFloats : 0;        // wave-uniform; <= row_pass_chunks(kTrigIters)
+    const float4* src4 = reinterpret_cast<const float4*>(tile);
+    float4* dst4 = reinterpret_cast<float4*>(dst);
+#pragma unroll
+    for (int it = 0; it < kTrigIters; ++it) {
+        if (emit) {
+            float* o = tile + L.off[it % kTrigPeriod] + (it / kTrigPeriod) * kTrigPeriodRows * kObsDim;
+            float sn, cs;
+            const bool far = L.is_a[it % kTrigPeriod] & !(__builtin_fabsf(x[it]) <= 131072.0f);
+            if (far) sincosf(x[it], &sn, &cs);                           // sincos_any's rare branch
+            else sincos_bounded(x[it], sn, cs);
+            o[kDof] = cs; o[2 * kDof] = sn;
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int c = row_pass_chunks(it); c < row_pass_chunks(it + 1); ++c)
+            if (c < nchunk) stream_store(dst4 + c * kWave + lane, src4[c * kWave + lane]);
+    }
+    if (!flush) return;
+    // the ragged end behind the last whole chunk; an unaligned destination goes out as single floats
+    if (vec) {
+        const int nvec = total >> 2;
+        for (int j = nchunk * kWave + lane; j < nvec; j += kWave) stream_store(dst4 + j, src4[j]);
+        for (int j = (nvec << 2) + lane; j < total; j += kWave) stream_store(dst + j, tile[j]);
+    } else {
+        for (int j = lane; j < total; j += kWave) stream_store(dst + j, tile[j]);
+    }
+}
+
+// step_kernel's choice.  The row pass pays where all waves of a launch reach the emit together, HBM idles until the first store and
+// the launch is long enough to be bound by its stores: the one-pass form at more than one wave per SIMD (9.87 -> 9.40 us at 65 536
+// envs, 8.10 -> 7.89 at 49 152; same-box A/B).  Elsewhere it only lengthens a wave's own chain (twelve LDS round trips, ~170 more
+// instructions): one wave per SIMD and fewer (5.5 -> 6.4 us at 16 384 envs, 5.1 -> 6.1 at 8 192; equal at 32 768), and the persistent
+// general form, whose waves are out of phase and feed the store stream anyway (pnr_rollout 6.24 -> 7.37 us per step, 262 144 envs
+// 31.2 -> 32.3 us).  Those keep obs_tile_out.
+template <bool OBS_EM, bool ROW_PASS>
+__device__ __forceinline__ void step_obs_out(const LaneConsts& K, const LaneState& s, const Pose& q, float* tile, int el, int p, int lane,
+                                             float* obs, long long tile0, long long n, int nvalid, bool emit, bool flush)
+{
+    static_assert(OBS_EM || !ROW_PASS, "the row pass is written for the env-major tile");
+    if constexpr (ROW_PASS) obs_tile_rows_out(K, s, q, tile, el, p, lane, obs + tile0 * kObsDim, nvalid, emit, flush);
+    else obs_tile_out<OBS_EM>(K, s, q, tile, el, p, lane, obs, tile0, n, nvalid, emit, flush);
+}
+
 }  // namespace pnr

@@ -72,17 +72,20 @@ __device__ __forceinline__ void store_outcome(const KParams& P, const Outcome& c
 // 193 VGPRs, 106 SGPRs and 92 v_writelane / v_readlane scalar spills in the general form; 48 instructions (the tile's 36 constant
 // entries among them), 119 VGPRs, 74 SGPRs and no spill in the one-pass form.  Both forms request the three state planes and the
 // first action back to back, fetch P's scalars and write the constants behind them, and wait first for plane 0 alone; the new
-// action is waited for where the state store consumes it.
+// action is waited for where the state store consumes it.  ROW_PASS (one-pass form, env-major observations, more than one wave per
+// SIMD: step_row_pass, pnr_api.hip) also starts the obs stores early: the tile's sin / cos are evaluated in row order with the
+// flush under them (obs_tile_rows_out, pnr_device.h); every other launch emits a lane's half row at once (obs_tile_out).
 #ifndef PNR_STEP_WAVES
 #define PNR_STEP_WAVES 4
 #endif
 constexpr int kStepWaves = PNR_STEP_WAVES;
 
-template <bool OBS_EM, bool ACT_EM, bool ONE_PASS = false>
+template <bool OBS_EM, bool ACT_EM, bool ONE_PASS = false, bool ROW_PASS = false>
 __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __restrict__ state_, const float* __restrict__ actions_,
                                                      const long long n_, const double dt_, const double eps_,
                                                      const float max_v_to_r_, const KParams P)
 {
+    static_assert(!ROW_PASS || (OBS_EM && ONE_PASS), "the row-ordered obs path belongs to the one-pass form with an env-major tile");
     __shared__ __attribute__((aligned(16))) float tiles_[kStepWaves * kTileFloats];
     float* tile = tiles_ + (threadIdx.x >> 6) * kTileFloats;
 
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
 
         // -- observe() ----------------------------------------------------------------
         if (t > 0 || !first_tile) wave_lds_sync();   // previous flush done before the tile is rewritten
-        obs_tile_out<OBS_EM>(K, s, q, tile, el, p, lane, P.obs + (long long)t * n * kObsDim, tile0, n, nvalid, !diag_noemit, !diag_noflush);
+        step_obs_out<OBS_EM, ROW_PASS>(K, s, q, tile, el, p, lane, P.obs + (long long)t * n * kObsDim, tile0, n, nvalid, !diag_noemit, !diag_noflush);
     }
     first_tile = false;
     if (ONE_PASS) break;

@@ -17,8 +17,9 @@ def main():
         if mode == "dynamic":
             k = [v for n, v in ks.items() if "dyn_step_kernelILb1ELb1ELb1E" in n][0]
         else:
-            # 65 536 envs, one step per launch: the one-pass instantiation (trailing bool set; tools' prefix step_kernelILb1ELb1E)
-            k = [v for n, v in ks.items() if "step_kernelILb1ELb1ELb1E" in n and "dyn" not in n][0]
+            # 65 536 envs, one step per launch: the one-pass instantiation with the row-ordered obs path (both trailing bools set;
+            # tools' prefix step_kernelILb1ELb1E)
+            k = [v for n, v in ks.items() if "step_kernelILb1ELb1ELb1ELb1E" in n and "dyn" not in n][0]
         return k["counters_per_dispatch"][counter], k["rows"]
     f_kib, n = pick(fetch, "FETCH_SIZE")
     w_kib, _ = pick(write, "WRITE_SIZE")
