@@ -44,7 +44,8 @@ extern "C" {
  *      (was: two bf16 planes) in every pnr_mlp_* call; pnr_mlp_train_step checks every argument before its first launch and
  *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
  *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
- *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose */
+ *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
+ *      pnr_ray_test */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -620,6 +621,58 @@ typedef struct pnr_render_params {
 } pnr_render_params;
 int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* p, uint8_t* rgb, float* depth, uint8_t* seg,
                void* stream);
+
+/*
+ * rayTest / rayTestBatch for every env, one launch: n_rays segments per env against that env's solids.
+ *   Ray r is the segment from + t (to - from), t in [0, 1]: rays[...][0:3] is `from`, [3:6] is `to`, float32, 4-byte aligned,
+ *   read only.  rays_per_env = 0: rays is [n_rays][6], shared by all envs; 1: [num_envs][n_rays][6].  parent_link = -1: the
+ *   rays are in the world frame; 0 .. 10: in the frame of that URDF link of EACH env (pnr_get_link_states' link index,
+ *   PyBullet's parentLinkIndex; link 0 is the base, the world frame): a sensor mounted on the arm.
+ *   joint_state     as pnr_get_link_states ([num_envs][12] q | qd, 16-byte aligned, read only); NULL = the handle's own joints
+ *                   (dynamics mode the simulated q, kinematic mode the env's r)
+ *   body_positions  as pnr_get_contacts: [num_envs][n_bodies][3] float32 or NULL, a world position per env in place of
+ *                   bodies[b].position.  Ignored when n_bodies == 0.
+ *   Solids, selected by hit_mask (every shape is a solid):
+ *     PNR_RAY_HIT_BODIES  bodies[] (as pnr_contact_params.bodies); a plane is the half-space below its surface
+ *     PNR_RAY_HIT_ARM     the URDF's 14 <visual> shapes posed by the env's joints: pnr_render's primitives, so a ray and a
+ *                         pixel see the same arm
+ *     PNR_RAY_HIT_TARGET  a sphere of pnr_config.target_radius at the env's target (pnr_get_state words 18-20), opaque here
+ *   Hit rule: a ray hits a solid at its entering parameter t_n if it starts outside the solid and 0 <= t_n <= 1.  A ray that
+ *   starts inside a solid does not hit that solid (Bullet's rule for convex shapes; it makes a sensor inside the pointer's
+ *   sphere usable).  The smallest t_n over the enabled solids wins; on a tie the order is arm visuals in table order, then the
+ *   target, then bodies by index.  A zero-length ray misses.
+ *   Outputs (at least one non-NULL, each 16-byte aligned; nothing past the last row is written):
+ *     hits      [num_envs][n_rays][PNR_RAY_DIM] float32:
+ *                 [0]   hit fraction t_n; 1 on a miss (PyBullet's convention)
+ *                 [1:4] world hit position; `to` in the world frame on a miss
+ *                 [4:7] unit outward world normal; 0 on a miss
+ *                 [7]   the enum pnr_seg label as a float: 0 miss, 1 + link, 12 the target, 13 + body
+ *     fractions [num_envs][n_rays] float32: [0] alone (the tensor that goes into an observation)
+ * PNR_ERR_INVALID, nothing launched and no output touched, for: a null handle or params, a wrong struct_size, n_rays outside
+ * 1..PNR_MAX_RAYS, parent_link outside -1..10, n_bodies outside 0..PNR_MAX_SCENE, a hit_mask that is 0 or has unknown bits,
+ * rays_per_env not 0 or 1, NULL rays, both outputs NULL, misaligned pointers, a bad shape or non-finite / degenerate body data (as
+ * pnr_get_contacts), a NULL joint_state or PNR_RAY_HIT_TARGET before the first pnr_reset (or pnr_set_state).  With a caller's
+ * joint_state and no TARGET bit a fresh handle is accepted: nothing of the state is read.  Non-finite rays or joints give
+ * non-finite or missing hits, unchecked.  An env's results do not depend on the batch around it, bit for bit.  float32
+ * arithmetic, asynchronous on `stream`, no allocation, no synchronisation: capturable into a graph.  Parity unpinned: Bullet's
+ * ray casts against its own collision shapes are not reproduced (the reference URDF has no <collision>, so Bullet itself would
+ * hit the bodies only: the default mask).
+ */
+#define PNR_RAY_DIM 8
+#define PNR_MAX_RAYS 1024                       /* per env */
+enum pnr_ray_hit { PNR_RAY_HIT_BODIES = 1, PNR_RAY_HIT_ARM = 2, PNR_RAY_HIT_TARGET = 4 };
+typedef struct pnr_ray_params {
+    uint32_t struct_size;     /* sizeof(pnr_ray_params) */
+    int32_t  n_rays;          /* 1 .. PNR_MAX_RAYS rays per env */
+    int32_t  rays_per_env;    /* 0: rays is [n_rays][6], shared by all envs; 1: [num_envs][n_rays][6] */
+    int32_t  parent_link;     /* -1: rays are in the world frame; 0 .. 10: in that URDF link's frame of EACH env */
+    int32_t  hit_mask;        /* pnr_ray_hit bits, non-zero; default PNR_RAY_HIT_BODIES */
+    int32_t  n_bodies;        /* 0 .. PNR_MAX_SCENE */
+    pnr_scene_body bodies[PNR_MAX_SCENE];       /* as pnr_contact_params.bodies */
+} pnr_ray_params;
+int pnr_ray_params_default(pnr_ray_params* p);
+int pnr_ray_test(pnr_handle h, const float* joint_state, const pnr_ray_params* p, const float* rays,
+                 const float* body_positions, float* hits, float* fractions, void* stream);
 
 /* Diagnostic: the engine's float32 sin/cos (the np.sin/np.cos replacement used
  * for obs entries, pioneer_knm_env.py:195-203) over a device array x[n].

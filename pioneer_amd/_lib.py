@@ -37,6 +37,9 @@ NUM_LINKS = 11          # pnr_get_link_states: link records per env (Bullet's li
 LINK_STATE_DIM = 13     # position[3], quaternion x y z w [4], linear velocity[3], angular velocity[3]
 CONTACT_SAMPLES = 23    # pnr_get_contacts: sample spheres per env (model.CONTACT_SAMPLE_LINKS names their links); 22 is the pointer
 CONTACT_DIM = 9         # distance, normal[3], position on the sample[3], body index, normal force
+RAY_DIM = 8             # pnr_ray_test: hit fraction, world position[3], unit world normal[3], pnr_seg label as a float
+MAX_RAYS = 1024         # .. rays per env, at most
+RAY_HIT_BODIES, RAY_HIT_ARM, RAY_HIT_TARGET = 1, 2, 4      # pnr_ray_params.hit_mask bits (enum pnr_ray_hit)
 JACOBIAN_DIM = 36       # pnr_get_jacobian: 6 rows (linear xyz, angular xyz) x 6 joint columns per env
 INVDYN_NO_GRAVITY, INVDYN_JOINT_LOSSES = 1, 2      # pnr_inverse_dynamics flags (PNR_INVDYN_*)
 
@@ -81,6 +84,12 @@ class PnrContactParams(C.Structure):
     """pnr_contact_params of include/pioneer_amd.h (pnr_get_contacts's bodies and penalty gains)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_bodies", C.c_int32), ("contact_kp", C.c_double), ("contact_kd", C.c_double),
                 ("bodies", PnrSceneBody * MAX_SCENE)]
+
+
+class PnrRayParams(C.Structure):
+    """pnr_ray_params of include/pioneer_amd.h (pnr_ray_test's ray layout, parent link, hit mask and bodies)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rays", C.c_int32), ("rays_per_env", C.c_int32), ("parent_link", C.c_int32),
+                ("hit_mask", C.c_int32), ("n_bodies", C.c_int32), ("bodies", PnrSceneBody * MAX_SCENE)]
 
 
 class PnrIkParams(C.Structure):
@@ -195,6 +204,8 @@ SIGNATURES = {
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
     "pnr_contact_params_default": (C.c_int, [C.POINTER(PnrContactParams)]),
     "pnr_get_contacts": (C.c_int, [_VP, _VP, C.POINTER(PnrContactParams), _VP, _VP, _VP, _VP, _VP]),
+    "pnr_ray_params_default": (C.c_int, [C.POINTER(PnrRayParams)]),
+    "pnr_ray_test": (C.c_int, [_VP, _VP, C.POINTER(PnrRayParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_diag_sincos": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, _VP]),
     "pnr_ppo_loss": (C.c_int, [C.c_int64] + [_VP] * 12 + [C.c_float] * 3 + [_VP] * 3 + [C.c_int64, _VP, _VP]),
     "pnr_mlp_pack_elems": (C.c_int64, []),
@@ -226,7 +237,7 @@ SIGNATURES = {
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 UNITS = {
     "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_query.h",
-                    "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h", "pnr_contacts.h"],
+                    "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h", "pnr_contacts.h", "pnr_rays.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",
                       "pnr_mlp_gather.h", "pnr_mlp_backward.h", "pnr_mlp_wgrad.h", "pnr_mlp_adam.h", "pnr_sampler.h"],
 }

@@ -46,6 +46,7 @@
 #include "pnr_ik.h"
 #include "pnr_invdyn.h"
 #include "pnr_contacts.h"
+#include "pnr_rays.h"
 
 // =====================================================================================
 // host side
@@ -170,6 +171,33 @@ static SceneBody scene_body_device(const pnr_scene_body& B)
         for (int k = 0; k < 9; ++k) S.rot[k] = (float)R[k];
     }
     return S;
+}
+
+// .. and as the ray casters want it (pnr_render, pnr_ray_test): the world -> primitive rotation rows rt, the half sizes h and the
+// bounding radius (a plane: rows 0 and 1 zero, row 2 its unit world normal, no bound).  Returns the kVis* shape.
+static int scene_body_prim(const pnr_scene_body& S, double (&rt)[9], float (&h)[3], double& bound)
+{
+    double R[9], normal[3];
+    scene_body_frame(S, R, normal);
+    const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int k = 0; k < 9; ++k) rt[k] = ident[k];
+    h[0] = h[1] = h[2] = 0.f;
+    bound = 0;
+    if (S.shape == PNR_SHAPE_BOX) {
+        for (int i = 0; i < 3; ++i)
+            for (int k = 0; k < 3; ++k) rt[3 * i + k] = R[3 * k + i];
+        for (int i = 0; i < 3; ++i) h[i] = (float)S.size[i];
+        bound = std::sqrt(sum_sq(S.size, 3));
+        return kVisBox;
+    }
+    if (S.shape == PNR_SHAPE_SPHERE) {
+        for (int i = 0; i < 3; ++i) h[i] = (float)S.size[0];
+        bound = S.size[0];
+        return kVisSphere;
+    }
+    for (int k = 0; k < 6; ++k) rt[k] = 0;           // unit world normal R n / |n| as the frame's z row
+    for (int k = 0; k < 3; ++k) rt[6 + k] = normal[k];
+    return kVisPlane;
 }
 
 // One joint's entries of the JointMotorTable, assigned in one place
@@ -1053,27 +1081,11 @@ static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& 
     for (int b = 0; b < p->n_bodies; ++b) {
         const pnr_scene_body& S = p->bodies[b];
         RenderPrim& Q = P.bodies[b];
-        double R[9], normal[3];
-        scene_body_frame(S, R, normal);
         const double e[3] = {eye[0] - S.position[0], eye[1] - S.position[1], eye[2] - S.position[2]};
-        double rt[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {e[0], e[1], e[2]}, bound = 0;
-        if (S.shape == PNR_SHAPE_BOX) {
-            for (int i = 0; i < 3; ++i)
-                for (int k = 0; k < 3; ++k) rt[3 * i + k] = R[3 * k + i];
-            for (int i = 0; i < 3; ++i) { o[i] = rt[3 * i] * e[0] + rt[3 * i + 1] * e[1] + rt[3 * i + 2] * e[2]; Q.h[i] = (float)S.size[i]; }
-            bound = std::sqrt(sum_sq(S.size, 3));
-            Q.shape = kVisBox;
-        } else if (S.shape == PNR_SHAPE_SPHERE) {
-            for (int i = 0; i < 3; ++i) Q.h[i] = (float)S.size[0];
-            bound = S.size[0];
-            Q.shape = kVisSphere;
-        } else {                                     // unit world normal R n / |n| as the frame's z row
-            for (int k = 0; k < 6; ++k) rt[k] = 0;
-            for (int k = 0; k < 3; ++k) rt[6 + k] = normal[k];
-            o[0] = o[1] = 0;
-            o[2] = rt[6] * e[0] + rt[7] * e[1] + rt[8] * e[2];
-            Q.shape = kVisPlane;
-        }
+        double rt[9], bound;
+        Q.shape = scene_body_prim(S, rt, Q.h, bound);
+        double o[3];                                 // the eye in the primitive frame (a plane: o[2] = n . (eye - point))
+        for (int i = 0; i < 3; ++i) o[i] = rt[3 * i] * e[0] + rt[3 * i + 1] * e[1] + rt[3 * i + 2] * e[2];
         for (int k = 0; k < 9; ++k) Q.rt[k] = (float)rt[k];
         for (int k = 0; k < 3; ++k) { Q.o[k] = (float)o[k]; Q.rgb[k] = p->body_rgba[b][k]; }
         Q.label = kSegBody0 + b;
@@ -1107,6 +1119,87 @@ int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* 
     const JointSource J = joint_source(h, joint_state);       // (the kernel reads the target from h->state whatever the source)
     with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(J.kind, [&](auto S) {
         hipLaunchKernelGGL(render_kernel<S()>, grid, block, 0, st, J.src, h->state, (long long)h->n, P, rgb, depth, seg);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+}  // extern "C"
+
+// one static body as pnr_ray_test's kernel reads it (pnr_rays.h RayPrim), in world space once for all envs
+static RayPrim ray_body_record(const pnr_scene_body& S, int b)
+{
+    RayPrim Q;
+    memset(&Q, 0, sizeof(Q));
+    double rt[9], bound;
+    Q.shape = scene_body_prim(S, rt, Q.h, bound);
+    Q.bound2 = Q.shape == kVisPlane ? INFINITY : ray_bound2((float)bound);
+    for (int k = 0; k < 9; ++k) Q.rt[k] = (float)rt[k];
+    for (int k = 0; k < 3; ++k) Q.c[k] = (float)S.position[k];
+    Q.label = kSegBody0 + b;
+    return Q;
+}
+
+extern "C" {
+
+int pnr_ray_params_default(pnr_ray_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_ray_params_default: null params");
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_ray_params);
+    p->n_rays = 1; p->parent_link = -1; p->hit_mask = PNR_RAY_HIT_BODIES;
+    return PNR_OK;
+}
+
+int pnr_ray_test(pnr_handle h, const float* joint_state, const pnr_ray_params* p, const float* rays, const float* body_positions,
+                 float* hits, float* fractions, void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: null params");
+    if (p->struct_size != sizeof(pnr_ray_params))
+        return fail(h, PNR_ERR_INVALID, "pnr_ray_test: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_ray_params));
+    if (p->n_rays < 1 || p->n_rays > PNR_MAX_RAYS) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: n_rays %d outside 1..%d", p->n_rays, PNR_MAX_RAYS);
+    if (p->rays_per_env != 0 && p->rays_per_env != 1) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: rays_per_env must be 0 or 1");
+    if (p->parent_link < -1 || p->parent_link >= kNumLinks)
+        return fail(h, PNR_ERR_INVALID, "pnr_ray_test: parent_link %d outside -1..%d", p->parent_link, kNumLinks - 1);
+    constexpr int all = PNR_RAY_HIT_BODIES | PNR_RAY_HIT_ARM | PNR_RAY_HIT_TARGET;
+    if (p->hit_mask == 0 || (p->hit_mask & ~all)) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: hit_mask %d is empty or has unknown bits", p->hit_mask);
+    if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
+        return fail(h, PNR_ERR_INVALID, "pnr_ray_test: n_bodies %d outside 0..%d", p->n_bodies, PNR_MAX_SCENE);
+    if (!rays) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: null rays");
+    if (!hits && !fractions) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: every output is NULL");
+    if (const int rc = check_aligned(h, "pnr_ray_test", {{rays, "rays", 4}, {hits, "hits", 16}, {fractions, "fractions", 16},
+                                                          {joint_state, "joint_state", 16}, {body_positions, "body_positions", 4}})) return rc;
+    for (int b = 0; b < p->n_bodies; ++b)
+        if (const int rc = check_scene_body(h, "pnr_ray_test: body", b, p->bodies[b], true)) return rc;
+    if (!joint_state && !has_own_joints(h)) return before_first_reset(h, "pnr_ray_test");
+    if ((p->hit_mask & PNR_RAY_HIT_TARGET) && !has_own_target(h)) return before_first_reset(h, "pnr_ray_test", ": the target comes from the state");
+    const JointSource J = joint_source(h, joint_state);
+    RayArgs A;
+    memset(&A, 0, sizeof(A));
+    A.src = J.src; A.state = h->state;                 // (the target is read from h->state whatever the joint source)
+    A.rays = rays; A.body_pos = p->n_bodies > 0 ? body_positions : nullptr;
+    A.hits = hits; A.fractions = fractions;
+    A.n = h->n; A.total = h->n * (long long)p->n_rays;
+    A.n_rays = p->n_rays; A.per_env = p->rays_per_env;
+    A.parent_body = p->parent_link >= 1 ? kLinkBody[p->parent_link] : -1;       // link 0 is the base: the world frame
+    A.parent_tip = p->parent_link == kNumLinks - 1;
+    A.mask = p->hit_mask; A.n_bodies = p->n_bodies;
+    // pairs per workgroup: 256, or fewer where 256 pairs would span more than kRayMaxEnvs envs; whole waves where it can
+    long long span = (long long)(kRayMaxEnvs - 1) * p->n_rays;
+    span = span >= kRayThreads ? kRayThreads : (span >= kWave ? span / kWave * kWave : span);
+    A.span = (int)span;
+    const long long touched = (span + p->n_rays - 2) / p->n_rays + 1;
+    A.max_envs = (int)(touched < h->n ? touched : h->n);
+    A.target_radius = (float)h->cfg.target_radius;
+    for (int b = 0; b < p->n_bodies; ++b) A.bodies[b] = ray_body_record(p->bodies[b], b);
+    const long long groups = (A.total + span - 1) / span;
+    if (groups > 0x7fffffffLL) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: %lld envs x %d rays exceed one launch", h->n, p->n_rays);
+    DeviceGuard g(h->device);
+    const dim3 grid((unsigned)groups), block((unsigned)((span + kWave - 1) / kWave * kWave));
+    const size_t lds = sizeof(float) * (size_t)ray_lds_words(A.max_envs);
+    with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(J.kind, [&](auto S) {
+        hipLaunchKernelGGL(ray_kernel<S()>, grid, block, lds, (hipStream_t)stream, A);
     });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;

@@ -138,31 +138,32 @@ __device__ __forceinline__ void put_prim(RenderPrim& Q, const RenderParams& P, c
     sphere_rect(cx, cy, depth, bound, P, Q.x0, Q.x1, Q.y0, Q.y1);
 }
 
-// the ray eye + t d (t = eye depth) against one primitive: the entering and the leaving parameter (tn <= tf when it hits)
-__device__ __forceinline__ void intersect(const RenderPrim& Q, int shape, V3 dw, float& tn, float& tf)
+// the ray o + t d against one primitive: the entering and the leaving parameter (tn <= tf when it hits).  o: the ray's origin in
+// the primitive frame; rt: world -> primitive rotation (rows), h: half sizes, dw: the world direction.  Shared with pnr_rays.h,
+// whose origins differ per ray.
+__device__ __forceinline__ void intersect_at(V3 o, const float* rt, const float* h, int shape, V3 dw, float& tn, float& tf)
 {
-    const V3 o = {Q.o[0], Q.o[1], Q.o[2]};
     if (shape == kVisSphere) {                                       // |o + t d|^2 = r^2 from the closest approach
         const float a = dot(dw, dw), tc = -dot(o, dw) * fast_rcp(a);
         const V3 v = o + tc * dw;
-        const float disc = Q.h[0] * Q.h[0] - dot(v, v);
+        const float disc = h[0] * h[0] - dot(v, v);
         const float half = sqrtf(fmaxf(disc, 0.f) * fast_rcp(a));
         tn = disc >= 0.f ? tc - half : 1.f;
         tf = disc >= 0.f ? tc + half : 0.f;
         return;
     }
-    const V3 d = {Q.rt[0] * dw.x + Q.rt[1] * dw.y + Q.rt[2] * dw.z, Q.rt[3] * dw.x + Q.rt[4] * dw.y + Q.rt[5] * dw.z,
-                  Q.rt[6] * dw.x + Q.rt[7] * dw.y + Q.rt[8] * dw.z};
+    const V3 d = {rt[0] * dw.x + rt[1] * dw.y + rt[2] * dw.z, rt[3] * dw.x + rt[4] * dw.y + rt[5] * dw.z,
+                  rt[6] * dw.x + rt[7] * dw.y + rt[8] * dw.z};
     if (shape == kVisPlane) {
         tn = tf = -o.z * fast_rcp(nonzero(d.z));
         return;
     }
     const float iz = fast_rcp(nonzero(d.z));
-    const float za = (-Q.h[2] - o.z) * iz, zb = (Q.h[2] - o.z) * iz;
+    const float za = (-h[2] - o.z) * iz, zb = (h[2] - o.z) * iz;
     if (shape == kVisBox) {
         const float ix = fast_rcp(nonzero(d.x)), iy = fast_rcp(nonzero(d.y));
-        const float xa = (-Q.h[0] - o.x) * ix, xb = (Q.h[0] - o.x) * ix;
-        const float ya = (-Q.h[1] - o.y) * iy, yb = (Q.h[1] - o.y) * iy;
+        const float xa = (-h[0] - o.x) * ix, xb = (h[0] - o.x) * ix;
+        const float ya = (-h[1] - o.y) * iy, yb = (h[1] - o.y) * iy;
         tn = fmaxf(fmaxf(fminf(xa, xb), fminf(ya, yb)), fminf(za, zb));
         tf = fminf(fminf(fmaxf(xa, xb), fmaxf(ya, yb)), fmaxf(za, zb));
         return;
@@ -172,30 +173,40 @@ __device__ __forceinline__ void intersect(const RenderPrim& Q, int shape, V3 dw,
     const bool along = a < 1e-24f;
     const float tc = along ? 0.f : -(o.x * d.x + o.y * d.y) * fast_rcp(a);
     const float vx = o.x + tc * d.x, vy = o.y + tc * d.y;
-    const float disc = Q.h[0] * Q.h[0] - (vx * vx + vy * vy);
+    const float disc = h[0] * h[0] - (vx * vx + vy * vy);
     const float half = along ? 1e30f : sqrtf(fmaxf(disc, 0.f) * fast_rcp(a));
     tn = disc >= 0.f ? fmaxf(tc - half, fminf(za, zb)) : 1.f;
     tf = disc >= 0.f ? fminf(tc + half, fmaxf(za, zb)) : 0.f;
 }
 
-// outward unit normal (world) of primitive Q at the ray parameter t
-__device__ __forceinline__ V3 hit_normal(const RenderPrim& Q, V3 dw, float t)
+// .. of the ray from the eye (t = eye depth): the record holds the eye in the primitive frame
+__device__ __forceinline__ void intersect(const RenderPrim& Q, int shape, V3 dw, float& tn, float& tf)
 {
-    const V3 o = {Q.o[0], Q.o[1], Q.o[2]};
-    const V3 r0 = {Q.rt[0], Q.rt[1], Q.rt[2]}, r1 = {Q.rt[3], Q.rt[4], Q.rt[5]}, r2 = {Q.rt[6], Q.rt[7], Q.rt[8]};
-    const int shape = Q.shape;
+    intersect_at(V3{Q.o[0], Q.o[1], Q.o[2]}, Q.rt, Q.h, shape, dw, tn, tf);
+}
+
+// outward normal (world, not normalised) of a primitive at the parameter t of the ray o + t d (arguments as intersect_at's)
+__device__ __forceinline__ V3 hit_normal_at(V3 o, const float* rt, const float* h, int shape, V3 dw, float t)
+{
+    const V3 r0 = {rt[0], rt[1], rt[2]}, r1 = {rt[3], rt[4], rt[5]}, r2 = {rt[6], rt[7], rt[8]};
     if (shape == kVisSphere) return o + t * dw;
     if (shape == kVisPlane) return r2;
     const V3 p = o + t * V3{dot(r0, dw), dot(r1, dw), dot(r2, dw)};      // hit point in the primitive frame
     V3 nl;
     if (shape == kVisBox) {                                         // the face whose slab the point lies on
-        const float ax = fabsf(p.x) / Q.h[0], ay = fabsf(p.y) / Q.h[1], az = fabsf(p.z) / Q.h[2];
+        const float ax = fabsf(p.x) / h[0], ay = fabsf(p.y) / h[1], az = fabsf(p.z) / h[2];
         nl = (ax >= ay && ax >= az) ? V3{p.x, 0.f, 0.f} : (ay >= az ? V3{0.f, p.y, 0.f} : V3{0.f, 0.f, p.z});
     } else {                                                        // cylinder: a cap or the side
         const float rad = sqrtf(p.x * p.x + p.y * p.y);
-        nl = fabsf(p.z) / Q.h[2] >= rad / Q.h[0] ? V3{0.f, 0.f, p.z} : V3{p.x, p.y, 0.f};
+        nl = fabsf(p.z) / h[2] >= rad / h[0] ? V3{0.f, 0.f, p.z} : V3{p.x, p.y, 0.f};
     }
     return nl.x * r0 + nl.y * r1 + nl.z * r2;                       // R n = R^T's rows weighted
+}
+
+// .. of primitive Q at the eye ray's parameter t
+__device__ __forceinline__ V3 hit_normal(const RenderPrim& Q, V3 dw, float t)
+{
+    return hit_normal_at(V3{Q.o[0], Q.o[1], Q.o[2]}, Q.rt, Q.h, Q.shape, dw, t);
 }
 
 // Lambert with ambient: rgb (ambient + diffuse max(0, n . l)), clamped to [0, 1]; the normal faces the viewer

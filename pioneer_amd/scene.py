@@ -44,6 +44,11 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   (``CONTACT_SAMPLE_LINKS`` gives each one's URDF link): one entry per sample, against its nearest body.  bodyUniqueIdA is 0 (the
   arm), bodyUniqueIdB 1 + the body's place among the created collision bodies, linkIndexB -1 (a base).  Deviation: PyBullet's
   manifolds (several points per pair) are not reproduced.
+* ``scene.ray_test(ray_from, ray_to)`` / ``scene.ray_test_batch(ray_froms, ray_tos, parent_item=None)``: pybullet.rayTest /
+  rayTestBatch against the created collision bodies and the arm's visual shapes, as ``RayHit`` tuples (PyBullet's field names),
+  one engine launch (``pnr_ray_test``), either mode; ``parent_item`` a link item in whose frame the rays are given.  Ids as in
+  ``ContactPoint``: the arm is body 0 with linkIndex the URDF link, a created body 1 + its place among the created collision
+  bodies with linkIndex -1; a miss is (-1, -1, 1.0, (0, 0, 0), (0, 0, 0)).  ``ray_fan(n, length, start)`` makes a range sensor's rays.
 * ``Item.pose()`` is a ``Pose`` (``.xyz``, ``.rpy``), still a 2-tuple (position, orientation); ``Item.velocity()`` a ``Velocity``
   (linear, angular), zero for created bodies and the target (they are static).
 Build-defined behaviour where the reference delegates to Bullet: parity unpinned, like the rest of the Bullet boundary.
@@ -92,6 +97,27 @@ class ContactPoint(NamedTuple):
     contactNormalOnB: Tuple[float, float, float]
     contactDistance: float
     normalForce: float
+
+
+class RayHit(NamedTuple):
+    """One entry of pybullet.rayTest / rayTestBatch, in PyBullet's names.  A miss is (-1, -1, 1.0, (0, 0, 0), (0, 0, 0))."""
+    objectUniqueId: int
+    linkIndex: int
+    hitFraction: float
+    hitPosition: Tuple[float, float, float]
+    hitNormal: Tuple[float, float, float]
+
+
+def ray_fan(n: int, length: float, start: float = 0.0) -> np.ndarray:
+    """A range sensor's rays as a float32 ``[n, 6]`` array (from | to): ``n`` directions spread over the sphere (the Fibonacci
+    lattice), each ray from ``start`` to ``length`` along its direction, in the frame the rays are cast in (for a sensor mounted
+    on a link: ``ray_test(rays, parent_link=...)``).  ``start`` > 0 keeps the rays' origins off the mount's own surface."""
+    k = np.arange(int(n), dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / float(n)
+    r = np.sqrt(np.maximum(1.0 - z * z, 0.0))
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+    return np.concatenate([float(start) * d, float(length) * d], axis=1).astype(np.float32)
 
 
 # the URDF link (Bullet's link_index) of each of the engine's 23 contact sample spheres, in the engine's order: 8 on arm1, 7 on
@@ -312,6 +338,43 @@ class Scene:
     def closest_points(self, distance: float, item: Optional[Item] = None) -> List[ContactPoint]:
         """getClosestPoints: the samples within ``distance`` of their nearest created body (contactDistance <= distance)."""
         return self._contact_records(item, lambda d: d <= float(distance))
+
+    # -- ray casts (pybullet.rayTest / rayTestBatch) ---------------------------------------------------------------------------
+    @staticmethod
+    def _ray_hits(hits: np.ndarray) -> List[RayHit]:
+        """pnr_ray_test's ``[R, 8]`` rows as RayHit tuples: the arm is body 0 with linkIndex the URDF link, a created body
+        1 + its place in ``collision_items()`` with linkIndex -1, a miss PyBullet's (-1, -1, 1.0, (0, 0, 0), (0, 0, 0))."""
+        out = []
+        for r in np.asarray(hits, dtype=np.float64):
+            label = int(r[7])
+            if label == _lib.SEG_BACKGROUND or label == _lib.SEG_TARGET:       # (the façade never enables the target)
+                out.append(RayHit(-1, -1, 1.0, _ZERO3, _ZERO3))
+                continue
+            body, link = (1 + label - _lib.SEG_BODY0, -1) if label >= _lib.SEG_BODY0 else (0, label - _lib.SEG_LINK0)
+            out.append(RayHit(body, link, float(r[0]), tuple(map(float, r[1:4])), tuple(map(float, r[4:7]))))
+        return out
+
+    def ray_test_batch(self, ray_froms, ray_tos, parent_item: Optional[LinkItem] = None) -> List[RayHit]:
+        """rayTestBatch: one RayHit per ray against the bodies created through ``env.scene`` with a collision shape and the arm's
+        visual shapes, one engine launch (``pnr_ray_test``), either mode.  ``parent_item``: a link item (``links_by_name[...]``)
+        in whose frame the rays are given (PyBullet's parentObjectUniqueId / parentLinkIndex); None: the world frame.  Deviation:
+        Bullet casts against collision shapes, of which the reference's arm has none; here the arm is its visual shapes."""
+        bodies = self.collision_items()
+        if len(bodies) > _lib.MAX_SCENE:
+            raise AssertionError(f"the engine queries at most {_lib.MAX_SCENE} created bodies, the scene has {len(bodies)}")
+        if parent_item is not None and not isinstance(parent_item, LinkItem):
+            raise AssertionError("parent_item must be a link item (scene.links_by_name[...])")
+        rays = np.concatenate([np.asarray(ray_froms, dtype=np.float32).reshape(-1, 3), np.asarray(ray_tos, dtype=np.float32).reshape(-1, 3)], axis=1)
+        vec = self._env._vec
+        js = None if vec.engine_config.mode == "dynamic" else self._bullet
+        sb = [SceneBody(i.shape, i._position, i._orientation, tuple(map(float, i.size))) for i in bodies]
+        hits = vec.ray_test(rays, parent_link=-1 if parent_item is None else parent_item.link_index, hit_arm=True, bodies=sb,
+                            joint_state=js)["hits"][0].cpu().numpy()
+        return self._ray_hits(hits)
+
+    def ray_test(self, ray_from, ray_to) -> RayHit:
+        """rayTest: the first hit of the segment ray_from -> ray_to (world frame); see ``ray_test_batch``."""
+        return self.ray_test_batch([ray_from], [ray_to])[0]
 
     # -- rotations (pybullet.getQuaternionFromEuler / getEulerFromQuaternion: x, y, z, w; roll about x, pitch about y, yaw about z) --
     @staticmethod

@@ -461,6 +461,54 @@ class PioneerVectorEnv:
                                             _ptr(res.get("joint_torques")), self._stream()))
         return res
 
+    def ray_test(self, rays, parent_link=-1, hit_arm=False, hit_target=False, hit_bodies=True, bodies=None, body_positions=None,
+                 joint_state=None, hits=True, fractions=False, out=None):
+        """rayTest / rayTestBatch of every env, one launch (pnr_ray_test): range sensors and line-of-sight checks.  ``rays``: a
+        float32 tensor ``[R, 6]`` (shared by all envs) or ``[N, R, 6]`` (per env), R <= ``_lib.MAX_RAYS``; a ray is the segment
+        from ``[..., 0:3]`` to ``[..., 3:6]``, in the world frame (``parent_link=-1``) or in the frame of URDF link
+        ``parent_link`` (0 .. 10, ``link_states``' index) of EACH env: a sensor mounted on the arm.  Returns a dict of device
+        tensors, those asked for:
+
+        ``hits`` float32 ``[N, R, 8]``: the hit fraction (1 on a miss, PyBullet's convention), the world hit position [3] (``to``
+        on a miss), the unit outward world normal [3] (0 on a miss) and the ``_lib.SEG_*`` label as a float (0 miss, 1 + link,
+        12 the target, 13 + body index);
+        ``fractions`` float32 ``[N, R]``: the hit fraction alone, the tensor that goes into an observation.
+
+        What a ray can hit: ``hit_bodies`` the static ``bodies`` (a sequence of SceneBody, at most 8, planes as half-spaces below
+        their surface; None = ``collision_bodies()``, as in ``contacts()``; ``body_positions`` ``[N, len(bodies), 3]`` a world
+        position per env), ``hit_arm`` the URDF's 14 visual shapes posed by the env's joints (what ``render_frames`` draws),
+        ``hit_target`` the target sphere.  Every shape is a solid; a ray that starts inside one does not hit it.  The default is
+        what Bullet would hit: the reference URDF has no collision shapes.  ``joint_state``: as ``link_states`` (None = the
+        handle's own joints).  ``out`` may carry preallocated ``hits`` / ``fractions`` tensors, written in place.  Never
+        synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        if not isinstance(rays, torch.Tensor):
+            rays = torch.as_tensor(np.asarray(rays), dtype=torch.float32)
+        if rays.dim() not in (2, 3) or rays.shape[-1] != 6 or (rays.dim() == 3 and rays.shape[0] != n):
+            raise AssertionError(f"rays must have shape (R, 6) or ({n}, R, 6), got {tuple(rays.shape)}")
+        nr = int(rays.shape[-2])
+        if not 1 <= nr <= _lib.MAX_RAYS:
+            raise AssertionError(f"between 1 and {_lib.MAX_RAYS} rays per env, got {nr}")
+        rays = self._in(rays, tuple(rays.shape), torch.float32, "rays")
+        bodies = self.collision_bodies() if bodies is None else list(bodies)
+        if len(bodies) > _lib.MAX_SCENE:
+            raise AssertionError(f"at most {_lib.MAX_SCENE} bodies can be queried, got {len(bodies)}")
+        p = _lib.PnrRayParams()
+        self._chk(self.lib.pnr_ray_params_default(p))
+        p.n_rays, p.rays_per_env, p.parent_link = nr, int(rays.dim() == 3), int(parent_link)
+        p.hit_mask = (_lib.RAY_HIT_BODIES if hit_bodies else 0) | (_lib.RAY_HIT_ARM if hit_arm else 0) | (_lib.RAY_HIT_TARGET if hit_target else 0)
+        p.n_bodies = len(bodies)
+        for i, b in enumerate(bodies):
+            fill_scene_body(p.bodies[i], b, f"body {i}")
+        js = self._joints(joint_state)
+        bp = None if body_positions is None else self._in(body_positions, (n, len(bodies), 3), torch.float32, "body_positions")
+        res = self._asked(out, (("hits", hits, (n, nr, _lib.RAY_DIM), torch.float32), ("fractions", fractions, (n, nr), torch.float32)),
+                          "ray_test: ask for at least one of hits, fractions")
+        self._chk(self.lib.pnr_ray_test(self._h, _ptr(js), p, _ptr(rays), _ptr(bp), _ptr(res.get("hits")), _ptr(res.get("fractions")),
+                                        self._stream()))
+        return res
+
     def observe(self, out=None):
         """observe() without stepping (pioneer_knm_env.py:184-211)."""
         self._check_handle()
