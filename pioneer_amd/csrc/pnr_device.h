@@ -207,30 +207,86 @@ __device__ __forceinline__ void sincos_any(float x, float& sn, float& cs)
 // ---- integrator: pioneer_knm_env.py:113-146 -------------------------------------
 // One joint.  Cast sequence = the reference's NumPy 1.x arithmetic (float32
 // stores, float64 intermediates); bit-exact against oracle/pnr_oracle.c.
-__device__ __forceinline__ void integrate_joint(float a0, float v0, float r0, float vmax, float rlo, float rhi,
-                                                double dt, double eps, float& v_out, float& r_out)
+// The arithmetic is stated once, in three pieces, and put together twice: integrate_joint branches round the saturation
+// piece per joint; integrate_joints3 (step_kernel) runs the pieces of a lane's three joints side by side.
+struct JointStep {
+    float v1;                  // the new velocity, before the position limits
+    bool hi, lo;               // it left [-vmax, vmax]
+    double dt_p1, dt_p2;       // the step's two parts: up to the saturation, and at vsat
+};
+
+__device__ __forceinline__ JointStep joint_predict(float a0, float v0, float vmax, double dt)
 {
-    float v1 = (float)((double)v0 + (double)a0 * dt);            // :121
-    double dt_p1 = dt, dt_p2 = 0.0;                              // :122-123
-    const bool hi = v1 > vmax, lo = v1 < -vmax;                  // :125, :129
-    if (hi || lo) {
-        const float vsat = hi ? vmax : -vmax;
-        const float num = vsat - v0;                             // float32 - float32
-        double q = (double)num / ((double)a0 + eps);             // :126, :130 (eps added, not sign-matched)
-        // np.clip(q, 0, dt), NaN-propagating
-        q = (q != q) ? q : (q < 0.0 ? 0.0 : (q > dt ? dt : q));
-        dt_p1 = q;
-        dt_p2 = dt - dt_p1;                                      // :127, :131
-        v1 = vsat;                                               // :128, :132
-    }
+    JointStep j;
+    j.v1 = (float)((double)v0 + (double)a0 * dt);                // :121
+    j.dt_p1 = dt; j.dt_p2 = 0.0;                                 // :122-123
+    j.hi = j.v1 > vmax; j.lo = j.v1 < -vmax;                     // :125, :129
+    return j;
+}
+
+// the time at which the velocity reaches its bound; meaningful where j.hi || j.lo (elsewhere a number nobody uses)
+__device__ __forceinline__ double joint_sat_time(const JointStep& j, float a0, float v0, float vmax, double eps)
+{
+    const float vsat = j.hi ? vmax : -vmax;
+    const float num = vsat - v0;                                 // float32 - float32
+    return (double)num / ((double)a0 + eps);                     // :126, :130 (eps added, not sign-matched)
+}
+
+// `sat`: this joint saturates (the literal true under integrate_joint's branch, a select per value in integrate_joints3)
+__device__ __forceinline__ void joint_saturate(JointStep& j, bool sat, double q, float vmax, double dt)
+{
+    // np.clip(q, 0, dt), NaN-propagating: q != q ? q : (q < 0 ? 0 : (q > dt ? dt : q)), as two flat selects (both compares are false
+    // for a NaN, which so passes through; nested, the three tests came out as three levels of exec-mask regions per joint)
+    const double qc = q > dt ? dt : q;
+    q = q < 0.0 ? 0.0 : qc;
+    j.dt_p1 = sat ? q : dt;
+    j.dt_p2 = sat ? dt - q : 0.0;                                // :127, :131
+    j.v1 = sat ? (j.hi ? vmax : -vmax) : j.v1;                   // :128, :132
+}
+
+__device__ __forceinline__ void joint_finish(const JointStep& j, float v0, float r0, float rlo, float rhi, float& v_out, float& r_out)
+{
+    float v1 = j.v1;
     const float vs = v0 + v1;                                    // float32 + float32
     const double half = 0.5 * (double)vs;
-    const double r1d = ((double)r0 + half * dt_p1) + (double)v1 * dt_p2;  // :134
+    const double r1d = ((double)r0 + half * j.dt_p1) + (double)v1 * j.dt_p2;  // :134
     float r1 = (float)r1d;
     if (r1 >= rhi) { r1 = rhi; v1 = 0.0f; }                      // :135-137
     if (r1 <= rlo) { r1 = rlo; v1 = 0.0f; }                      // :139-141
     v_out = v1;
     r_out = r1;
+}
+
+__device__ __forceinline__ void integrate_joint(float a0, float v0, float r0, float vmax, float rlo, float rhi,
+                                                double dt, double eps, float& v_out, float& r_out)
+{
+    JointStep j = joint_predict(a0, v0, vmax, dt);
+    if (j.hi || j.lo) joint_saturate(j, true, joint_sat_time(j, a0, v0, vmax, eps), vmax, dt);
+    joint_finish(j, v0, r0, rlo, rhi, v_out, r_out);
+}
+
+// A lane's three joints (limits -lim[i], lim[i]) side by side: ONE branch on "some joint of this lane saturates" — a wave in which
+// nothing does skips the block — and under it the three quotients in one basic block, so that their strictly dependent f64
+// division chains (v_div_scale, v_rcp_f64, four FMAs, ..) interleave, with the clip and the choice per joint as selects.  The
+// values are integrate_joint's: a joint that does not saturate computes a quotient and drops it (no floating-point traps here).
+// The empty asm holds the block together: with plain selects LLVM sinks each division back under a branch of its own
+// (a select whose operand is a division becomes a branch), three chains one after the other again.
+__device__ __forceinline__ void integrate_joints3(const float (&a0)[kJpl], float (&v)[kJpl], float (&r)[kJpl], const float (&vmax)[kJpl],
+                                                  const float (&lim)[kJpl], double dt, double eps)
+{
+    static_assert(kJpl == 3, "integrate_joints3 is written for three joints per lane");
+    JointStep j[kJpl] = {joint_predict(a0[0], v[0], vmax[0], dt), joint_predict(a0[1], v[1], vmax[1], dt),
+                         joint_predict(a0[2], v[2], vmax[2], dt)};
+    if ((j[0].hi || j[0].lo) || (j[1].hi || j[1].lo) || (j[2].hi || j[2].lo)) {
+        double q0 = joint_sat_time(j[0], a0[0], v[0], vmax[0], eps), q1 = joint_sat_time(j[1], a0[1], v[1], vmax[1], eps),
+               q2 = joint_sat_time(j[2], a0[2], v[2], vmax[2], eps);
+        asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
+        joint_saturate(j[0], j[0].hi || j[0].lo, q0, vmax[0], dt);
+        joint_saturate(j[1], j[1].hi || j[1].lo, q1, vmax[1], dt);
+        joint_saturate(j[2], j[2].hi || j[2].lo, q2, vmax[2], dt);
+    }
+#pragma unroll
+    for (int i = 0; i < kJpl; ++i) joint_finish(j[i], v[i], r[i], -lim[i], lim[i], v[i], r[i]);
 }
 
 // ---- forward kinematics of robot:pointer ---------------------------------------
@@ -633,11 +689,15 @@ constexpr int row_pass_chunks(int iters) { return (kWave * iters / kTrigArgs) * 
 struct RowPassLane {
     int off[kTrigPeriod];      // tile offset of the argument of iterations 0, 1, 2
     bool is_a[kTrigPeriod];    // .. and whether it is an action (sincos_any)
+    int tail;                  // phase 1: tile offset of this lane's first tail entry (column 126, or 132 for the pair's second lane)
 };
 
+// Nothing here depends on a loaded value: step_kernel forms it in the head of the launch, under the latency of the first loads
+// (the `/ 24` arithmetic and the tail columns were ~55 instructions between the state stores and the first obs store).
 __device__ __forceinline__ RowPassLane row_pass_lane(int lane)
 {
     RowPassLane L;
+    L.tail = (lane >> 1) * kObsDim + 126 + 6 * (lane & 1);
 #pragma unroll
     for (int k = 0; k < kTrigPeriod; ++k) {
         const int j = kWave * k + lane, row = j / kTrigArgs, arg = j - kTrigArgs * row, grp = arg / kDof;
@@ -648,8 +708,10 @@ __device__ __forceinline__ RowPassLane row_pass_lane(int lane)
 }
 
 // dst: the tile's place in the batch, obs + tile0 * 137.  emit / flush as in obs_tile_out: no emit skips both phases.
-__device__ __forceinline__ void obs_tile_rows_out(const LaneConsts& K, const LaneState& s, const Pose& q, float* tile, int el, int p,
-                                                  int lane, float* __restrict__ dst, int nvalid, bool emit = true, bool flush = true)
+// L: row_pass_lane(lane), formed by the caller ahead of time.
+__device__ __forceinline__ void obs_tile_rows_out(const LaneConsts& K, const LaneState& s, const Pose& q, const RowPassLane& L, float* tile,
+                                                  int el, int p, int lane, float* __restrict__ dst, int nvalid, bool emit = true,
+                                                  bool flush = true)
 {
     // -- phase 1: this lane's half row, everything but the new sin / cos
     if (emit) {
@@ -663,16 +725,17 @@ __device__ __forceinline__ void obs_tile_rows_out(const LaneConsts& K, const Lan
             out.putj(90 + i, s.v[i]);
             out.putj(108 + i, s.a[i]);
         }
+        // the tail as emit_obs writes it (putt: columns 126.. for the pair's first lane, 132.. for its second), from one offset
+        float* tl = tile + L.tail;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) out.putt(126 + k, 132 + k, p ? q.diff[k] : q.ptr[k]);
-        out.putt(129, 135, p ? q.dist : s.tgt[0]);
-        out.putt(130, 136, p ? s.pot : s.tgt[1]);
-        out.putt0(131, s.tgt[2]);
+        for (int k = 0; k < 3; ++k) tl[k] = p ? q.diff[k] : q.ptr[k];
+        tl[3] = p ? q.dist : s.tgt[0];
+        tl[4] = p ? s.pot : s.tgt[1];
+        if (!p) tl[5] = s.tgt[2];
     }
     wave_lds_sync();
 
     // -- phase 2: the arguments of all twelve iterations leave LDS first (their columns are not written below)
-    const RowPassLane L = row_pass_lane(lane);
     float x[kTrigIters];
     if (emit) {
 #pragma unroll
@@ -716,11 +779,11 @@ __device__ __forceinline__ void obs_tile_rows_out(const LaneConsts& K, const Lan
 // general form, whose waves are out of phase and feed the store stream anyway (pnr_rollout 6.24 -> 7.37 us per step, 262 144 envs
 // 31.2 -> 32.3 us).  Those keep obs_tile_out.
 template <bool OBS_EM, bool ROW_PASS>
-__device__ __forceinline__ void step_obs_out(const LaneConsts& K, const LaneState& s, const Pose& q, float* tile, int el, int p, int lane,
-                                             float* obs, long long tile0, long long n, int nvalid, bool emit, bool flush)
+__device__ __forceinline__ void step_obs_out(const LaneConsts& K, const LaneState& s, const Pose& q, const RowPassLane& L, float* tile, int el,
+                                             int p, int lane, float* obs, long long tile0, long long n, int nvalid, bool emit, bool flush)
 {
     static_assert(OBS_EM || !ROW_PASS, "the row pass is written for the env-major tile");
-    if constexpr (ROW_PASS) obs_tile_rows_out(K, s, q, tile, el, p, lane, obs + tile0 * kObsDim, nvalid, emit, flush);
+    if constexpr (ROW_PASS) obs_tile_rows_out(K, s, q, L, tile, el, p, lane, obs + tile0 * kObsDim, nvalid, emit, flush);
     else obs_tile_out<OBS_EM>(K, s, q, tile, el, p, lane, obs, tile0, n, nvalid, emit, flush);
 }
 

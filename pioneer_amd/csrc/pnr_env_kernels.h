@@ -71,10 +71,15 @@ __device__ __forceinline__ void store_outcome(const KParams& P, const Outcome& c
 // prefetch addresses, rollout strides): gfx950 listing, <true, true>: 447 instructions between the first loads and the integrator,
 // 193 VGPRs, 106 SGPRs and 92 v_writelane / v_readlane scalar spills in the general form; 48 instructions (the tile's 36 constant
 // entries among them), 119 VGPRs, 74 SGPRs and no spill in the one-pass form.  Both forms request the three state planes and the
-// first action back to back, fetch P's scalars and write the constants behind them, and wait first for plane 0 alone; the new
-// action is waited for where the state store consumes it.  ROW_PASS (one-pass form, env-major observations, more than one wave per
+// first action back to back, fetch P's scalars and write the constants behind them, and wait first for plane 0 alone.  The
+// integrator takes the lane's three joints side by side (integrate_joints3, pnr_device.h: one branch, three interleaved f64 division
+// chains, where three nested exec-mask regions per joint ran one after the other).  The new action: the general form waits for it
+// where the state store consumes it; the one-pass form right behind the integrator, in front of every store of the step, so that no
+// `s_waitcnt vmcnt` stands behind a store (it would wait for that store's acknowledgement) anywhere between the first outcome store
+// and the first obs store.  ROW_PASS (one-pass form, env-major observations, more than one wave per
 // SIMD: step_row_pass, pnr_api.hip) also starts the obs stores early: the tile's sin / cos are evaluated in row order with the
-// flush under them (obs_tile_rows_out, pnr_device.h); every other launch emits a lane's half row at once (obs_tile_out).
+// flush under them (obs_tile_rows_out, pnr_device.h; what that pass derives from the lane id alone is formed in the head, under
+// the first loads); every other launch emits a lane's half row at once (obs_tile_out).
 #ifndef PNR_STEP_WAVES
 #define PNR_STEP_WAVES 4
 #endif
@@ -138,6 +143,14 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
 
     // the 36 constant obs entries of this lane's tile slots: once per kernel, under the load latency
     obs_tile_const<OBS_EM>(K, tile, el, p);
+    // .. and where the row pass finds this lane's trig arguments and tail columns: integer work on the lane id alone; the asm keeps
+    // the results in registers from here on (unpinned, the `/ 24` arithmetic is sunk back between the state stores and the first
+    // obs store, where every wave of the launch pays for it with HBM idle)
+    RowPassLane rowl = {};
+    if (ROW_PASS) {
+        rowl = row_pass_lane(lane);
+        asm volatile("" : "+v"(rowl.off[0]), "+v"(rowl.off[1]), "+v"(rowl.off[2]), "+v"(rowl.tail));
+    }
     if (ONE_PASS) {
         // .. and so are the common path's words of P: asked for here, they are scalar loads issued before the first vmcnt wait;
         // the barrier keeps the integrator's converts (and with them that wait) below the constants
@@ -192,13 +205,16 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
                 }
             }
             // -- act(): integrate the PREVIOUS action, then latch the new one -------
-#pragma unroll
-            for (int i = 0; i < kJpl; ++i) {
-                const float lim = K.lim[i];
-                if (!(diag & 32)) integrate_joint(s.a[i], s.v[i], s.r[i], vmax[i], -lim, lim, dt_, eps_, s.v[i], s.r[i]);
-            }
+            if (!(diag & 32)) integrate_joints3(s.a, s.v, s.r, vmax, K.lim, dt_, eps_);
 #pragma unroll
             for (int i = 0; i < kJpl; ++i) s.a[i] = act[i];           // :144 (quirk Q1)
+            // One-pass form: the new action is waited for HERE, unconditionally, in front of every store of the step.  On gfx9
+            // vmcnt counts stores too, until the write is acknowledged: left to its first consumer, the wait sat in front of the
+            // state stores (behind the outcome stores, whose acknowledgement it then waited for as well) and, that one being
+            // inside the `valid` branch, again in phase 1 of the row pass (behind the state stores).  The action is the last load
+            // issued and the integrator has run since, so the wait costs nothing here; the asm has side effects, so neither the
+            // scheduler nor the stores move across it.
+            if (ONE_PASS) asm volatile("" :: "v"(s.a[0]), "v"(s.a[1]), "v"(s.a[2]));
         }
         s.step += 1;                                                  // bullet_env.py:193
 
@@ -221,7 +237,7 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
 
         // -- observe() ----------------------------------------------------------------
         if (t > 0 || !first_tile) wave_lds_sync();   // previous flush done before the tile is rewritten
-        step_obs_out<OBS_EM, ROW_PASS>(K, s, q, tile, el, p, lane, P.obs + (long long)t * n * kObsDim, tile0, n, nvalid, !diag_noemit, !diag_noflush);
+        step_obs_out<OBS_EM, ROW_PASS>(K, s, q, rowl, tile, el, p, lane, P.obs + (long long)t * n * kObsDim, tile0, n, nvalid, !diag_noemit, !diag_noflush);
     }
     first_tile = false;
     if (ONE_PASS) break;
