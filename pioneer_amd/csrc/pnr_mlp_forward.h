@@ -192,6 +192,9 @@ __device__ __forceinline__ void mlp_tile_b2_products(const __bf16* ztile, int zs
 // (ppo_value_sample).  hd: the tile's head rows [64][16] float32, gt: its head gradients [64][kGS] bf16 (written here, with the
 // float32 copy to g_head), rl: the parked record (rec_early) — all LDS; wsum [8 waves][4]: the waves' partial loss sums.
 // As one thread per sample on wave 0 the other seven waves waited 4 300 cycles of a tile's 38 000 for it (profiles/r03_d_mlp_stamps.json).
+// A second statement of ppo_policy_sample, so it has a checker of its own: tests/test_gpu_fused_loss.py holds g_head, the means and
+// layer 3's bias gradient against a float64 reference sample by sample (clamp bounds, both clip sides, every record path, one-hot batches
+// at the tile edges), as test_gpu_ppo.py::test_fused_loss_matches_autograd does for the stand-alone kernel.
 // this thread's share of the tile's record, in registers (the compact layout of the fused kernel has no LDS to park it in): requested
 // early — from inside the layer-2 product — by the thread that uses it: sample tid >> 3, action dimension tid & 7
 struct MlpLossRec {

@@ -435,14 +435,100 @@ def test_gae_logp_kernel_equals_the_host_formulas():
         assert float(((out["logp"] - lp).abs() / (lp.abs() + 1)).max()) < 5e-6
 
 
+GAE_SENTINEL = -4242.5
+
+
+def _tailed(T, N, dev, fill=float("nan")):
+    """A [T, N] output as the head of a longer allocation whose tail must stay untouched."""
+    store = torch.full((T * N + 256,), fill, device=dev)
+    store[T * N:] = GAE_SENTINEL
+    return store, store[:T * N].view(T, N)
+
+
+def _tail_untouched(store, T, N):
+    return bool((store[T * N:] == GAE_SENTINEL).all())
+
+
+@pytest.mark.parametrize("N", [1, 63, 64, 65, 130])
+@pytest.mark.parametrize("T", [1, 2, 7, 8, 9, 15, 17, 33])
+def test_gae_logp_kernel_at_the_edges_of_its_unrolled_scan(T, N):
+    """The scan walks eight steps per trip with clamped loads past its ends: rollouts shorter than a trip, exactly one, one more
+    and one less, two trips and more (T), envs short of a wave, a wave, one over and two waves plus two (N); lambda = 0 as well.
+    Advantages and value targets bit for bit, terminals equal, log-probs to the rounding of exp; nothing is written behind an
+    output.  Then, through the C ABI, the optional arguments the Python wrapper always passes: no `truncated`, no `actions`
+    (log-probs untouched, terminals still written), neither (no second grid row at all)."""
+    import ctypes as C
+    from pioneer_amd import _lib
+    from pioneer_amd.ppo import compute_gae, gaussian_logp, hip_gae_logp
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(100 * T + N)
+    r = torch.randn(T, N, generator=g, device=dev)
+    v = torch.randn(T, N, generator=g, device=dev) * 3
+    last = torch.randn(N, generator=g, device=dev)
+    done = (torch.rand(T, N, generator=g, device=dev) < 0.15).to(torch.uint8)
+    trunc = ((torch.rand(T, N, generator=g, device=dev) < 0.15) & (done == 0)).to(torch.uint8)
+    mean = torch.randn(T, N, 6, generator=g, device=dev)
+    log_std = torch.rand(T, N, 6, generator=g, device=dev) * 4 - 3
+    act = mean + torch.exp(log_std) * torch.randn(T, N, 6, generator=g, device=dev)
+    lp = gaussian_logp(act, mean, log_std)
+    term = (done | trunc).float()
+    for gamma, lam in ((0.99, 1.0), (0.97, 0.9), (0.97, 0.0)):
+        stores, out = {}, {}
+        for k in ("logp", "adv", "vtarg", "terminals"):
+            stores[k], out[k] = _tailed(T, N, dev)
+        hip_gae_logp(r, v, last, done, trunc, act, mean, log_std, gamma, lam, **out)
+        adv, vt = compute_gae(r, v, last, term, gamma, lam)
+        assert torch.equal(out["terminals"], term)
+        assert torch.equal(out["adv"], adv) and torch.equal(out["vtarg"], vt)
+        assert float((out["logp"] - lp).abs().max()) <= 2e-5 * float(lp.abs().max())
+        assert float(((out["logp"] - lp).abs() / (lp.abs() + 1)).max()) < 5e-6
+        assert all(_tail_untouched(stores[k], T, N) for k in stores)
+    lib = _lib.load_library()
+    P = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+    gamma, lam = 0.97, 0.9
+
+    def call(trunc_, act_, terminals_):
+        stores, out = {}, {}
+        for k in ("logp", "adv", "vtarg", "terminals"):
+            stores[k], out[k] = _tailed(T, N, dev)
+        _lib.check(lib.pnr_ppo_gae(T, N, P(r), P(v), P(last), P(done), P(trunc_), P(act_), P(mean if act_ is not None else None),
+                                   P(log_std if act_ is not None else None), gamma, lam, P(out["logp"]), P(out["adv"]), P(out["vtarg"]),
+                                   P(out["terminals"]) if terminals_ else None, None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        torch.cuda.synchronize()
+        assert all(_tail_untouched(stores[k], T, N) for k in stores)
+        return out
+
+    adv_d, vt_d = compute_gae(r, v, last, done.float(), gamma, lam)
+    adv_t, vt_t = compute_gae(r, v, last, term, gamma, lam)
+    o = call(None, act, True)                                     # no `truncated`: terminal = done
+    assert torch.equal(o["terminals"], done.float()) and torch.equal(o["adv"], adv_d) and torch.equal(o["vtarg"], vt_d)
+    assert float(((o["logp"] - lp).abs() / (lp.abs() + 1)).max()) < 5e-6
+    o = call(trunc, None, True)                                   # no `actions`: the log-probs are not touched
+    assert bool(torch.isnan(o["logp"]).all()) and torch.equal(o["terminals"], term)
+    assert torch.equal(o["adv"], adv_t) and torch.equal(o["vtarg"], vt_t)
+    o = call(trunc, None, False)                                  # neither: the scan alone
+    assert bool(torch.isnan(o["logp"]).all()) and bool(torch.isnan(o["terminals"]).all())
+    assert torch.equal(o["adv"], adv_t) and torch.equal(o["vtarg"], vt_t)
+
+
 def test_gae_kernel_bookkeeping_equals_episode_stats_and_advantage_moments():
     """The optional bookkeeping of pnr_ppo_gae over three consecutive rollouts (carry-over of running returns included,
     one rollout without any terminal, terminals on the first and last step) against EpisodeStats.step() on the same
     data, and the advantages' moments against float64 sums."""
+    _gae_bookkeeping(32, 4099)
+
+
+@pytest.mark.parametrize("T", [7, 9])
+def test_gae_kernel_bookkeeping_around_one_trip_of_its_forward_pass(T):
+    """The same with one step less and one more than the eight the bookkeeping pass loads per trip (its loads past T are clamped),
+    on two waves plus two envs; the outputs' tails stay untouched."""
+    _gae_bookkeeping(T, 130)
+
+
+def _gae_bookkeeping(T, N):
     from pioneer_amd.ppo import EpisodeStats, compute_gae, hip_gae_logp
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(8)
-    T, N = 32, 4099
     a, b = EpisodeStats(N, dev), EpisodeStats(N, dev)
     adv_stats = torch.zeros(3, dtype=torch.float64, device=dev)
     for it in range(3):
@@ -455,8 +541,11 @@ def test_gae_kernel_bookkeeping_equals_episode_stats_and_advantage_moments():
         if it == 2:
             done[0] = 1; trunc[0] = 0; done[-1] = 0; trunc[-1] = 1
         act = torch.randn(T, N, 6, generator=g, device=dev); z = torch.zeros(T, N, 6, device=dev)
-        out = {k: torch.empty(T, N, device=dev) for k in ("logp", "adv", "vtarg")}
+        stores, out = {}, {}
+        for k in ("logp", "adv", "vtarg"):
+            stores[k], out[k] = _tailed(T, N, dev)
         hip_gae_logp(r, v, last, done, trunc, act, z, z, 0.99, 0.95, stats=b, adv_stats=adv_stats, **out)
+        assert all(_tail_untouched(stores[k], T, N) for k in stores)
         term = (done | trunc).float()
         for t in range(T):
             a.step(r[t], term[t])
@@ -474,7 +563,8 @@ def test_gae_kernel_bookkeeping_equals_episode_stats_and_advantage_moments():
         assert all((ra[k] == rb[k]) or (ra[k] != ra[k] and rb[k] != rb[k]) or abs(ra[k] - rb[k]) <= 1e-6 for k in ra)
 
 
-@pytest.mark.parametrize("n", [1, 2, 5, 4099, 32768, 524288, 1000003])
+# (3, 4, 16, 17, 256, 257, 65536, 65537: domains of exactly n and of almost 4 n — the longest cycle walks —, odd and even bit widths)
+@pytest.mark.parametrize("n", [1, 2, 5, 4099, 32768, 524288, 1000003, 3, 4, 16, 17, 256, 257, 65536, 65537])
 def test_permutation_kernel_is_a_permutation(n):
     from pioneer_amd.ppo import hip_permutation
     dev = torch.device("cuda", 0)
@@ -497,7 +587,23 @@ def test_permutation_kernel_is_a_permutation(n):
         assert abs(float(q) - 0.5) < 0.02
 
 
-@pytest.mark.parametrize("rows", [1, 511, 4099, 32 * 2048])
+def test_permutation_kernel_uses_all_64_bits_of_seed_and_stream():
+    from pioneer_amd.ppo import hip_permutation
+    dev = torch.device("cuda", 0)
+    n, seed, stream = 4099, (1 << 40) + 11, (1 << 33) + 5
+    out = torch.full((n + 3,), -7, dtype=torch.int64, device=dev)
+    p = hip_permutation(n, seed, stream, out).clone()
+    assert bool((out[n:] == -7).all())
+    assert torch.equal(torch.sort(p).values, torch.arange(n, device=dev))
+    assert torch.equal(p, hip_permutation(n, seed, stream, out))
+    # the bits above 2^32 are part of the key
+    assert not torch.equal(p, hip_permutation(n, seed & 0xFFFFFFFF, stream, out))
+    assert not torch.equal(p, hip_permutation(n, seed, stream & 0xFFFFFFFF, out))
+
+
+# (512, 513, 520: the 8-row unroll's tail at a block edge; 131073 rows = 257 blocks: the finishing kernel's thread 0 adds a second
+#  partial row — the workload's 524 288 rows are 1 024 blocks)
+@pytest.mark.parametrize("rows", [1, 511, 4099, 32 * 2048, 512, 513, 520, 131073])
 def test_filter_moment_kernel_equals_the_float64_sums(rows):
     """MeanStdFilter.observe on the GPU (pnr_filter_moments) against float64 column sums of the same deviations: relative
     error of a float32 partial sum over <= 512 rows; constant columns (36 of the 137 observation entries) exactly 0; two
