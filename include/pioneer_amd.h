@@ -45,7 +45,7 @@ extern "C" {
  *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
  *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
  *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
- *      pnr_ray_test */
+ *      pnr_ray_test, pnr_world_step_wrenches */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -518,6 +518,50 @@ int pnr_mass_matrix(pnr_handle h, const float* joint_state, float* out, void* st
  * allocation: capturable into a graph.  Parity unpinned.
  */
 int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* stream);
+
+/*
+ * pnr_world_step on a dynamics-mode handle with the caller's wrenches on links of the arm: PyBullet's applyExternalForce /
+ * applyExternalTorque for every env, in the world step's own launch.  One call is one World.step (frame_skip sub-steps of length
+ * timestep) exactly as pnr_world_step_torques, with n_specs <= PNR_MAX_LINK_WRENCHES wrench records per env.
+ *
+ * Record j.  Call-uniform: specs[j] = {link, frame} (host memory, read during the call).  link is 0..10, the index of
+ * pnr_get_link_states; frame is PNR_FRAME_LINK or PNR_FRAME_WORLD (pybullet's LINK_FRAME = 1 and WORLD_FRAME = 2 as recalled, not
+ * verified against a PyBullet install).  Per env: nine floats of wrenches, force[3] | position[3] | torque[3].
+ *
+ * The URDF link maps to its dynamic body b (the six moving bodies, fixed joints merged) with the link origin's fixed offset d in
+ * body coordinates (0 for every link but robot:pointer, which sits at (3.6, 0, 1.9) in the last body).  The URDF's fixed joints
+ * carry no rotation, so link axes are body axes.  Link 0 (robot:base) is welded to the world: a record on it is accepted and
+ * does nothing.
+ *   PNR_FRAME_LINK   force, torque and position are in the link's frame (= Bullet's link COM frame: the inertial origins are
+ *                    identity) and turn with the link.  In body coordinates, constant over the call:
+ *                      f_b = force,   n_b = (d + position) x force + torque
+ *   PNR_FRAME_WORLD  force and torque stay fixed in the world for the whole call; position is a world point, and the wrench acts
+ *                    on the material point of the link that lies there at the pose q0 of the call's start:
+ *                      p_b = R_b(q0)^T (position - o_b(q0)), fixed afterwards;
+ *                    in sub-step k, with the body's rotation at its start:  f_b = R_b(q_k)^T force,
+ *                      n_b = p_b x f_b + R_b(q_k)^T torque
+ * fext[b] += (n_b, f_b), summed over the records and added to the contact wrenches where the handle has contacts; it is
+ * subtracted from the body's bias force in the articulated-body recursion, as the contacts are.  Motor law, caps, damping,
+ * friction, joint limits and the integrator are untouched.
+ *   hold_substeps  the records act in the first hold_substeps sub-steps of the call; <= 0 or >= frame_skip: all of them (the
+ *                  force lasts one World.step).  1 is Bullet's literal behaviour under the reference's World.step (external
+ *                  forces are cleared after one stepSimulation).  Nothing persists after the call.
+ *   wrenches       [num_envs][n_specs][9] float32, caller-owned device memory, 16-byte aligned, read only
+ *   joint_torques  [num_envs][6] float32, 16-byte aligned, read only, or NULL for none: exactly pnr_world_step_torques' torques,
+ *                  in the same launch (a computed-torque controller under a disturbance is one call)
+ * PNR_ERR_UNSUPPORTED: a kinematic-mode handle; a motor table that holds a constraint motor (as pnr_world_step_torques).
+ * PNR_ERR_INVALID: a null handle, NULL specs or wrenches, misaligned wrenches or joint_torques, n_specs outside
+ * 1..PNR_MAX_LINK_WRENCHES, a link outside 0..10, an unknown frame, before the first pnr_reset.  Every refusal is decided before
+ * any launch and leaves the state untouched.  Device data is not inspected: a NaN or inf in wrenches gives that env non-finite
+ * joints and no error.  Asynchronous on `stream`, never synchronises, no allocation: capturable into a graph.  Parity unpinned:
+ * the reference never applies a force; checked against the float64 oracle's forward dynamics with external body forces.
+ */
+#define PNR_MAX_LINK_WRENCHES 4
+#define PNR_FRAME_LINK  1
+#define PNR_FRAME_WORLD 2
+typedef struct pnr_link_wrench_spec { int32_t link; int32_t frame; } pnr_link_wrench_spec;
+int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int n_specs, const float* wrenches,
+                            const float* joint_torques, int hold_substeps, void* stream);
 
 /*
  * getContactPoints / getClosestPoints for every env, one launch: each of the arm's 23 contact sample spheres against up to

@@ -42,6 +42,9 @@ MAX_RAYS = 1024         # .. rays per env, at most
 RAY_HIT_BODIES, RAY_HIT_ARM, RAY_HIT_TARGET = 1, 2, 4      # pnr_ray_params.hit_mask bits (enum pnr_ray_hit)
 JACOBIAN_DIM = 36       # pnr_get_jacobian: 6 rows (linear xyz, angular xyz) x 6 joint columns per env
 INVDYN_NO_GRAVITY, INVDYN_JOINT_LOSSES = 1, 2      # pnr_inverse_dynamics flags (PNR_INVDYN_*)
+MAX_LINK_WRENCHES = 4   # pnr_world_step_wrenches: wrench records per env, at most (PNR_MAX_LINK_WRENCHES)
+WRENCH_DIM = 9          # .. force[3], position[3], torque[3] per record
+FRAME_LINK, FRAME_WORLD = 1, 2                     # .. a record's frame (PNR_FRAME_*; pybullet's LINK_FRAME / WORLD_FRAME)
 
 PNR_OK = 0
 ENV_MAJOR, FEATURE_MAJOR = 0, 1
@@ -58,6 +61,11 @@ class PnrError(RuntimeError):
 
 MAX_SCENE = 8
 SHAPE_PLANE, SHAPE_BOX, SHAPE_SPHERE = 1, 2, 3
+
+
+class PnrLinkWrenchSpec(C.Structure):
+    """pnr_link_wrench_spec of include/pioneer_amd.h (the call-uniform part of one wrench record of pnr_world_step_wrenches)."""
+    _fields_ = [("link", C.c_int32), ("frame", C.c_int32)]
 
 
 class PnrSceneBody(C.Structure):
@@ -188,6 +196,7 @@ SIGNATURES = {
     "pnr_observe": (C.c_int, [_VP, _VP, _VP]),
     "pnr_world_step": (C.c_int, [_VP, _VP, _VP]),
     "pnr_world_step_torques": (C.c_int, [_VP, _VP, _VP]),
+    "pnr_world_step_wrenches": (C.c_int, [_VP, C.POINTER(PnrLinkWrenchSpec), C.c_int, _VP, _VP, C.c_int, _VP]),
     "pnr_set_joint_motor": (C.c_int, [_VP, C.c_int32, C.c_int32] + [C.c_double] * 6),
     "pnr_get_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_state": (C.c_int, [_VP, _VP, _VP]),

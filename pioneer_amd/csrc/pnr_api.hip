@@ -725,6 +725,48 @@ int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* strea
     return PNR_OK;
 }
 
+int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int n_specs, const float* wrenches,
+                            const float* joint_torques, int hold_substeps, void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (h->cfg.mode != PNR_MODE_DYNAMIC)
+        return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_wrenches: link wrenches exist in dynamics mode only");
+    if (!specs) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: null specs");
+    if (!wrenches) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: null wrenches");
+    if (!aligned16(wrenches)) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: wrenches must be 16-byte aligned");
+    if (joint_torques && !aligned16(joint_torques))
+        return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: joint_torques must be 16-byte aligned");
+    if (n_specs < 1 || n_specs > PNR_MAX_LINK_WRENCHES)
+        return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: n_specs %d out of [1, %d]", n_specs, PNR_MAX_LINK_WRENCHES);
+    LinkWrenchTable T = {};
+    T.n = n_specs;
+    T.last_world_body = -1;
+    for (int j = 0; j < kMaxWrench; ++j) T.lbody[j] = T.wbody[j] = -1;
+    for (int j = 0; j < n_specs; ++j) {
+        const int link = specs[j].link, frame = specs[j].frame;
+        if (link < 0 || link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: record %d: link %d out of [0, %d)", j, link, kNumLinks);
+        if (frame != PNR_FRAME_LINK && frame != PNR_FRAME_WORLD)
+            return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: record %d: unknown frame %d (1: link, 2: world)", j, frame);
+        (frame == PNR_FRAME_WORLD ? T.wbody : T.lbody)[j] = kLinkBody[link];   // -1: robot:base, welded to the world: the record does nothing
+        if (link == kNumLinks - 1) { T.d[j][0] = (float)kTipX; T.d[j][1] = (float)kTipY; T.d[j][2] = (float)kTipZ; }   // every other link origin is its body's
+        if (T.wbody[j] > T.last_world_body) T.last_world_body = T.wbody[j];
+    }
+    if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches before the first pnr_reset (or pnr_set_state)");
+    for (int i = 0; i < kDof; ++i)
+        if (h->motors.kind[i] != kMotorPD)
+            return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_wrenches: joint %d is on a constraint motor (wrench input with the boxed solve is not built)", i);
+    DeviceGuard g(h->device);
+    const DynParams& D = h->dbase;
+    T.hold = (hold_substeps <= 0 || hold_substeps >= D.nsub) ? D.nsub : hold_substeps;
+    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
+    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) {
+        hipLaunchKernelGGL((dyn_world_wrench_kernel<true, C()>), grid, dim3(kWave), 0, (hipStream_t)stream, h->state, h->dyn,
+                           (long long)h->n, wrenches, joint_torques, D, h->motors, T);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
 }  // extern "C"
 
 int pnr_env_rollout_params(pnr_handle h, pnr::KParams* out, float* max_v_to_r, int* device)

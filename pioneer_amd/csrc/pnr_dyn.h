@@ -612,14 +612,114 @@ __device__ __forceinline__ void contact_wrenches(const DynParams& D, const float
     pose_outward<5>(R, p, c[5], s[5], Rn, pn); R = Rn; p = pn; body_contacts<5>(D, R, p, v[5], fext[5]);
 }
 
+// ---------------------------------------------------------------------------------
+// pnr_world_step_wrenches: the caller's wrenches on links of the arm (PyBullet's applyExternalForce / applyExternalTorque; the law
+// is stated in include/pioneer_amd.h).  The call-uniform part of the records travels by value, as the motor table does: every
+// branch on it is wave-uniform, and no per-lane array is ever indexed by it (body and record indices are compile-time, the table
+// only decides whether a piece of code runs).
+// ---------------------------------------------------------------------------------
+constexpr int kMaxWrench = PNR_MAX_LINK_WRENCHES;
+struct LinkWrenchTable {
+    int n;                          // records per env, 1..kMaxWrench (the stride of the input; the kernel loads records 0..n-1)
+    // the dynamic body (0..5) of the record's link, in the entry of the record's frame; the other entry, and both for a record that
+    // does nothing (beyond n, or on robot:base, which is welded to the world), are -1: one scalar compare decides a block
+    int lbody[kMaxWrench];          // PNR_FRAME_LINK records
+    int wbody[kMaxWrench];          // PNR_FRAME_WORLD records
+    float d[kMaxWrench][3];         // the link origin in its body's coordinates (kTip for the pointer, 0 for every other link)
+    int last_world_body;            // the outermost body that carries a world-frame record; -1: none (no rotation is built)
+    int hold;                       // the records act in sub-steps 0 .. hold - 1 (1 .. nsub)
+};
+// One lane's records, nine floats each.  As loaded: force | position | torque.  After wrench_prepare, a link-frame record is
+// f_b | n_b | - (its constant body wrench) and a world-frame record F | p_b | T (the world force and torque, the material point
+// in body coordinates).
+struct WrenchLane { float w[kMaxWrench][9]; };
+
+// R <- R * R(axis_J, q_J): the rotation part of pose_outward
+template <int J>
+__device__ __forceinline__ M3 rot_outward(const M3& Rp, float c, float s)
+{
+    constexpr int AXJ = (int)kJoints[J].axis;
+    return {rot<AXJ>(Rp.r0, c, -s), rot<AXJ>(Rp.r1, c, -s), rot<AXJ>(Rp.r2, c, -s)};
+}
+
+// before the sub-steps, at the pose q0 of the call's start (c, s = cos / sin q0)
+__device__ __forceinline__ void wrench_prepare(const LinkWrenchTable& T, const float (&c)[kDof], const float (&s)[kDof], WrenchLane& L)
+{
+    static_for<kMaxWrench>([&](auto j_) {
+        constexpr int j = decltype(j_)::value;
+        if (T.lbody[j] >= 0) {                                         // n_b = (d + position) x force + torque
+            float (&w)[9] = L.w[j];
+            const V3 F = {w[0], w[1], w[2]}, P = {w[3] + T.d[j][0], w[4] + T.d[j][1], w[5] + T.d[j][2]};
+            const V3 nb = cross(P, F) + V3{w[6], w[7], w[8]};
+            w[3] = nb.x; w[4] = nb.y; w[5] = nb.z;
+        }
+    });
+    if (T.last_world_body < 0) return;
+    M3 R = diag3(1.f);
+    V3 p = {0.f, 0.f, 0.f};
+    static_for<kDof>([&](auto b_) {
+        constexpr int B = decltype(b_)::value;
+        if (B <= T.last_world_body) {
+            M3 Rn; V3 pn;
+            pose_outward<B>(R, p, c[B], s[B], Rn, pn); R = Rn; p = pn;
+            static_for<kMaxWrench>([&](auto j_) {
+                constexpr int j = decltype(j_)::value;
+                if (T.wbody[j] == B) {                                // p_b = R_b(q0)^T (position - o_b(q0))
+                    float (&w)[9] = L.w[j];
+                    const V3 pb = mulT(R, V3{w[3], w[4], w[5]} - p);
+                    w[3] = pb.x; w[4] = pb.y; w[5] = pb.z;
+                }
+            });
+        }
+    });
+}
+
+// one sub-step's fext[body] = (n_b, f_b) of all records, at the pose whose cos / sin are c, s
+__device__ __forceinline__ void wrench_forces(const LinkWrenchTable& T, const float (&c)[kDof], const float (&s)[kDof], const WrenchLane& L,
+                                              P3 (&fext)[kDof])
+{
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) fext[i] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+    static_for<kMaxWrench>([&](auto j_) {
+        constexpr int j = decltype(j_)::value;
+        if (T.lbody[j] >= 0) {
+            const float (&w)[9] = L.w[j];
+            const P3 f = pack(V3{w[3], w[4], w[5]}, V3{w[0], w[1], w[2]});
+            static_for<kDof>([&](auto b_) {
+                constexpr int B = decltype(b_)::value;
+                if (T.lbody[j] == B) fext[B] = fext[B] + f;
+            });
+        }
+    });
+    if (T.last_world_body < 0) return;
+    M3 R = diag3(1.f);
+    static_for<kDof>([&](auto b_) {
+        constexpr int B = decltype(b_)::value;
+        if (B <= T.last_world_body) {
+            R = rot_outward<B>(R, c[B], s[B]);
+            static_for<kMaxWrench>([&](auto j_) {
+                constexpr int j = decltype(j_)::value;
+                if (T.wbody[j] == B) {                                // f_b = R^T F, n_b = p_b x f_b + R^T T
+                    const float (&w)[9] = L.w[j];
+                    const V3 fb = mulT(R, V3{w[0], w[1], w[2]});
+                    const V3 nb = cross(V3{w[3], w[4], w[5]}, fb) + mulT(R, V3{w[6], w[7], w[8]});
+                    fext[B] = fext[B] + pack(nb, fb);
+                }
+            });
+        }
+    });
+}
+
 // qdd = ABA(q, qd, tau).  CONTACT: the penalty contacts' external forces are subtracted from the bodies' bias forces
 // (a separate instantiation: the contact-free kernels carry none of that code or its registers)
 // c, s: cos / sin of the joint angles (dyn_core carries them across the sub-steps)
 // PHYS: bit 0 = contacts, bit 1 = the inertia-scaled motor (its acceleration requests in ades, torque cap tcap)
-template <int PHYS>
+// EXT (pnr_world_step_wrenches): ext[6], the caller's wrenches of this sub-step in body coordinates; the contacts add into the same
+// fext, and body 0 (which carries no contact samples) has its bias force reduced as well
+template <int PHYS, bool EXT = false>
 __device__ __forceinline__ void aba(const DynParams& D, const DynModel& M, const float (&c)[kDof], const float (&s)[kDof],
                                     const float (&qd)[kDof], const float (&tau)[kDof], const float (&ades)[kDof], const float (&tcap)[kDof],
-                                    float (&qdd)[kDof])
+                                    float (&qdd)[kDof], const P3* ext = nullptr)
 {
     constexpr bool CONTACT = (PHYS & 1) != 0, SCALED = (PHYS & 2) != 0;
 
@@ -634,30 +734,31 @@ __device__ __forceinline__ void aba(const DynParams& D, const DynModel& M, const
     vel_outward<5>(v[4], c[5], s[5], qd[5], v[5]);
 
     P3 fext[kDof];
-    if (CONTACT) {
+    if (CONTACT || EXT) {
 #pragma unroll
-        for (int i = 0; i < kDof; ++i) fext[i] = v0;
-        contact_wrenches(D, c, s, v, fext);
+        for (int i = 0; i < kDof; ++i) fext[i] = EXT ? ext[i] : v0;
     }
+    if (CONTACT) contact_wrenches(D, c, s, v, fext);
 
     // pass 2: tip -> base
     DynBody B[kDof];
     SIp IA, IP; P3 pA, pP;
     rigid_body<5>(M, v[5], IA, pA);
-    if (CONTACT) pA = pA - fext[5];
+    if (CONTACT || EXT) pA = pA - fext[5];
     rigid_body<4>(M, v[4], IP, pP);
-    if (CONTACT) pP = pP - fext[4];
+    if (CONTACT || EXT) pP = pP - fext[4];
     aba_inward<5, SCALED>(IA, pA, v[5], qd[5], tau[5], ades[5], tcap[5], c[5], s[5], B[5], IP, pP);
     IA = IP; pA = pP; rigid_body<3>(M, v[3], IP, pP);
-    if (CONTACT) pP = pP - fext[3];
+    if (CONTACT || EXT) pP = pP - fext[3];
     aba_inward<4, SCALED>(IA, pA, v[4], qd[4], tau[4], ades[4], tcap[4], c[4], s[4], B[4], IP, pP);
     IA = IP; pA = pP; rigid_body<2>(M, v[2], IP, pP);
-    if (CONTACT) pP = pP - fext[2];
+    if (CONTACT || EXT) pP = pP - fext[2];
     aba_inward<3, SCALED>(IA, pA, v[3], qd[3], tau[3], ades[3], tcap[3], c[3], s[3], B[3], IP, pP);
     IA = IP; pA = pP; rigid_body<1>(M, v[1], IP, pP);
-    if (CONTACT) pP = pP - fext[1];
+    if (CONTACT || EXT) pP = pP - fext[1];
     aba_inward<2, SCALED>(IA, pA, v[2], qd[2], tau[2], ades[2], tcap[2], c[2], s[2], B[2], IP, pP);
     IA = IP; pA = pP; rigid_body<0>(M, v[0], IP, pP);
+    if (EXT) pP = pP - fext[0];
     aba_inward<1, SCALED>(IA, pA, v[1], qd[1], tau[1], ades[1], tcap[1], c[1], s[1], B[1], IP, pP);
     IA = IP; pA = pP;
     aba_inward<0, SCALED>(IA, pA, v[0], qd[0], tau[0], ades[0], tcap[0], c[0], s[0], B[0], IP, pP);
@@ -887,11 +988,14 @@ __device__ __forceinline__ void dyn_lane_load(const DynLead& in, long long base,
 // adds their boxed solve to each sub-step's accelerations.
 // TORQUE (WORLD only, pnr_world_step_torques): tau_ext[6], the caller's joint torques of this call, are added to each joint's
 // torque in every sub-step, after the motor law's own cap and before damping and friction (PyBullet's TORQUE_CONTROL).
-template <int PHYS, bool WORLD = false, bool CMOTOR = false, bool TORQUE = false>
+// WRENCH (WORLD only, pnr_world_step_wrenches): the lane's link wrench records XL under the table X; converted once at the call's
+// first pose, they give each of the first X->hold sub-steps its fext (a wave-uniform compare on the loop counter).
+template <int PHYS, bool WORLD = false, bool CMOTOR = false, bool TORQUE = false, bool WRENCH = false>
 __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, float (&a)[kDof], float (&v)[kDof],
                                          float (&r)[kDof], float (&q)[kDof], float (&qd)[kDof], const float (&sc)[kNumLinks],
                                          const float (&fric_)[kDof], const float (&damp_)[kDof], const float (&act)[kDof],
-                                         const JointMotorTable* W = nullptr, const float* tau_ext = nullptr)
+                                         const JointMotorTable* W = nullptr, const float* tau_ext = nullptr,
+                                         const LinkWrenchTable* X = nullptr, WrenchLane* XL = nullptr)
 {
     if constexpr (!WORLD) {
 #pragma unroll
@@ -928,6 +1032,12 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
 #pragma unroll
     for (int i = 0; i < kDof; ++i) { float sn, cn; sincos_bounded(q[i], sn, cn); cs[i] = (f2){cn, sn}; }
     [[maybe_unused]] const float inv_h = CMOTOR ? 1.0f / D.dt_sub : 0.f;
+    if constexpr (WRENCH) {
+        float c[kDof], s[kDof];
+#pragma unroll
+        for (int i = 0; i < kDof; ++i) { c[i] = cs[i].x; s[i] = cs[i].y; }
+        wrench_prepare(*X, c, s, *XL);
+    }
     for (int k = 0; k < D.nsub; ++k) {
         float tau[kDof], qdd[kDof], ades[kDof], tc[kDof];
 #pragma unroll
@@ -956,7 +1066,15 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
             float c[kDof], s[kDof];
 #pragma unroll
             for (int i = 0; i < kDof; ++i) { c[i] = cs[i].x; s[i] = cs[i].y; }
-            aba<PHYS>(D, M, c, s, qd, tau, ades, tc, qdd);
+            if constexpr (WRENCH) {
+                P3 fx[kDof];
+                if (k < X->hold) wrench_forces(*X, c, s, *XL, fx);
+                else {
+#pragma unroll
+                    for (int i = 0; i < kDof; ++i) fx[i] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+                }
+                aba<PHYS, true>(D, M, c, s, qd, tau, ades, tc, qdd, fx);
+            } else aba<PHYS>(D, M, c, s, qd, tau, ades, tc, qdd);
             if constexpr (CMOTOR) motor_constraints(D, M, c, s, q, qd, *W, inv_h, qdd);
         }
 #pragma unroll

@@ -667,6 +667,56 @@ __global__ __launch_bounds__(kWave) void dyn_world_torque_kernel(const float4* _
     for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
 }
 
+// pnr_world_step_wrenches: the torque step with up to four link wrench records per env (wrenches [n][T.n][9], env-major: force |
+// position | torque) under the by-value table T.  Everything is loaded before the sub-step loop and the records stay in registers
+// over it (36 VGPRs; the kernel has no scratch).  tau_ext may be null: a wave-uniform branch loads zeros, so the call without joint
+// torques costs no second set of instantiations.  A kernel of its own with the load text repeated, as dyn_world_torque_kernel.
+template <bool RAND, int PHYS>
+__global__ __launch_bounds__(kWave) void dyn_world_wrench_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
+                                                                 const float* __restrict__ wrenches, const float* __restrict__ tau_ext,
+                                                                 const DynParams D, const JointMotorTable W, const LinkWrenchTable T)
+{
+    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
+    if (e >= n) return;
+    float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
+    const long long n2 = 2 * n;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const RawState k = {state[2 * e + p], state[n2 + 2 * e + p], state[2 * n2 + 2 * e + p]};
+        unpack_record(k, a + 3 * p, v + 3 * p, r + 3 * p);
+    }
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) {
+        q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
+        fric[i] = dyn[(long long)(kDynFric + i) * n + e]; damp[i] = dyn[(long long)(kDynDamp + i) * n + e];
+        act[i] = 0.f;
+    }
+#pragma unroll
+    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
+    WrenchLane XL;
+    const float* wr = wrenches + e * (9 * T.n);
+    static_for<kMaxWrench>([&](auto j_) {
+        constexpr int j = decltype(j_)::value;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) XL.w[j][i] = 0.f;
+        if (j < T.n) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) XL.w[j][i] = wr[9 * j + i];
+        }
+    });
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) tx[i] = 0.f;
+    if (tau_ext) {
+        const float2* t2 = reinterpret_cast<const float2*>(tau_ext) + 3 * e;
+        const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
+        tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
+    }
+    const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
+    dyn_core<PHYS, true, false, true, true>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &W, tx, &T, &XL);
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
+}
+
 // The same call on a kinematic-mode handle: there is no simulated state, the caller holds the joints as Bullet would after
 // resetJointState(position, velocity) — js [n][12] = q[6] | qd[6] — and with no gravity, no motor and no collision shapes
 // (the reference's URDF and defaults) frame_skip x stepSimulation carries each joint on at its velocity:

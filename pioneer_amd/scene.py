@@ -25,6 +25,11 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
 * ``control_torque(torque)`` (setJointMotorControl2 with TORQUE_CONTROL; the reference's Joint has no such method, Bullet does):
   dynamics mode with the PD motors: the joint's torque for the next ``world.step()`` alone (``pnr_world_step_torques``), next to its
   motor; kinematic mode and ``joint_motor == "constraint"`` raise.
+* ``apply_force(force, position=None, frame="world")`` / ``apply_torque(torque, frame="world")`` on a link item (applyExternalForce /
+  applyExternalTorque; the reference's Item has no such method, Bullet does): dynamics mode: queued for the next ``world.step()``
+  alone, which hands them (at most four) and any ``control_torque`` to the engine in one launch (``pnr_world_step_wrenches``) and
+  clears them, as ``reset()`` does.  They act over the whole ``world.step()``; Bullet clears them after one stepSimulation
+  (``PioneerVectorEnv.world_step(hold_substeps=1)``).  A fifth record and kinematic mode raise AssertionError.
 * ``world.step()``: ``frame_skip`` × ``stepSimulation`` = ONE engine launch (``pnr_world_step``), nothing on the host.  Dynamics
   mode: the articulated-body sub-steps (gravity, contacts with the scene's bodies, limits, every joint's motor) and nothing else —
   no command integration, reward or observation.  Kinematic mode: each joint carries on at the velocity it was reset with
@@ -170,6 +175,27 @@ class LinkItem(Item):
 
     def reset_pose(self, position, orientation):
         raise AssertionError("Position can be reset only for base items: to control linked items use joint methods")   # :69-71
+
+    def _queue_wrench(self, what: str, frame: str, force, position, torque):
+        env = self._scene._env
+        assert env._vec.engine_config.mode == "dynamic", f"{what}: external forces exist in dynamics mode only"
+        assert frame in ("link", "world"), f"{what}: frame must be 'link' or 'world', got {frame!r}"
+        queue = env.world._wrenches
+        assert len(queue) < _lib.MAX_LINK_WRENCHES, f"{what}: at most {_lib.MAX_LINK_WRENCHES} forces and torques per world.step()"
+        if position is None:                                                   # the link origin, in the record's frame
+            position = self.pose().position if frame == "world" else _ZERO3
+        queue.append(((self.link_index, frame), tuple(map(float, force)) + tuple(map(float, position)) + tuple(map(float, torque))))
+
+    def apply_force(self, force, position=None, frame: str = "world"):
+        """applyExternalForce on this link for the NEXT ``world.step()`` only (``pnr_world_step_wrenches``; the step consumes the
+        queued forces and torques, at most four, and clears them).  ``frame`` ``"world"``: a world force at the world point
+        ``position``, taken on the link at the step's first pose; ``"link"``: a force that turns with the link, at a point of the
+        link's frame.  ``position=None``: the link origin.  Dynamics mode only."""
+        self._queue_wrench("apply_force", frame, force, position, _ZERO3)
+
+    def apply_torque(self, torque, frame: str = "world"):
+        """applyExternalTorque on this link for the NEXT ``world.step()`` only; see ``apply_force``."""
+        self._queue_wrench("apply_torque", frame, _ZERO3, _ZERO3, torque)
 
     def __repr__(self) -> str:
         return f"Item(name={self.name}, link_index={self.link_index})"
@@ -405,6 +431,7 @@ class World:
         sc = env.simulation_config
         self.timestep, self.frame_skip, self.gravity_force = sc.timestep, sc.frame_skip, sc.gravity
         self._torques: Dict[int, float] = {}                                   # Joint.control_torque: joint -> torque of the next step
+        self._wrenches: List[tuple] = []                                       # LinkItem.apply_force / apply_torque: ((link, frame), 9 floats)
 
     @property
     def step_time(self) -> float:
@@ -413,9 +440,17 @@ class World:
     def step(self):
         """frame_skip x stepSimulation: ONE launch of the engine (pnr_world_step), no host arithmetic."""
         vec = self._env._vec
+        tau = None
         if self._torques:                                                      # recorded for this step alone (TORQUE_CONTROL)
             tau = torch.tensor([[self._torques.get(j, 0.0) for j in range(6)]], dtype=torch.float32, device=vec.device)
             self._torques = {}
+        if self._wrenches:                                                     # .. and the links' external forces and torques
+            specs = [s for s, _ in self._wrenches]
+            rec = torch.tensor([[w for _, w in self._wrenches]], dtype=torch.float32, device=vec.device)
+            self._wrenches = []
+            vec.world_step(joint_torques=tau, link_wrenches=(specs, rec))
+            return
+        if tau is not None:
             vec.world_step(joint_torques=tau)
             return
         vec.world_step(None if vec.engine_config.mode == "dynamic" else self._env.scene._bullet)

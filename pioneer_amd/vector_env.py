@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .config import EngineConfig, PioneerKinematicConfig, SimulationConfig, fill_scene_body, to_c_config
+from .model import LINK_NAMES
 from .spaces import Box
 
 
@@ -207,13 +208,48 @@ class PioneerVectorEnv:
                                        self._stream()))
         return obs, rew, done, trunc
 
-    def world_step(self, joint_state=None, joint_torques=None):
+    def _wrench_specs(self, specs):
+        """``world_step``'s ``(link, frame)`` pairs as a pnr_link_wrench_spec array: link an index or a ``LINK_NAMES`` name, frame
+        ``"link"`` / ``"world"``.  The count and the index range are the engine's to refuse."""
+        frames = {"link": _lib.FRAME_LINK, "world": _lib.FRAME_WORLD}
+        arr = (_lib.PnrLinkWrenchSpec * max(len(specs), 1))()
+        for j, (link, frame) in enumerate(specs):
+            if isinstance(link, str):
+                if link not in LINK_NAMES:
+                    raise AssertionError(f"world_step: no link named {link!r}")
+                link = LINK_NAMES.index(link)
+            if frame not in frames:
+                raise AssertionError(f"world_step: frame must be 'link' or 'world', got {frame!r}")
+            arr[j].link, arr[j].frame = int(link), frames[frame]
+        return arr
+
+    def world_step(self, joint_state=None, joint_torques=None, link_wrenches=None, hold_substeps=None):
         """World.step() alone (bullet_scene.py:273-275; pnr_world_step): the simulator's sub-steps and nothing else.  Dynamics mode:
         ``joint_state`` is None (the handle's q, qd move); kinematic mode: the caller's float32 [N, 12] device buffer (q | qd).
         ``joint_torques`` (dynamics mode; float32 ``[N, 6]`` on the env's device, only read): PyBullet's TORQUE_CONTROL
         (pnr_world_step_torques) — added to each joint's torque in every sub-step of this call only, next to the joints' motors as
-        ``set_joint_motor`` left them (zero gains first for pure torque control).  Never synchronises."""
+        ``set_joint_motor`` left them (zero gains first for pure torque control).
+        ``link_wrenches`` (dynamics mode) = ``(specs, tensor)``: PyBullet's applyExternalForce / applyExternalTorque
+        (pnr_world_step_wrenches), in the same launch as ``joint_torques`` when both are given.  ``specs``: up to
+        ``_lib.MAX_LINK_WRENCHES`` pairs ``(link, frame)``, the same for every env — ``link`` an index 0..10 or a ``LINK_NAMES``
+        name, ``frame`` ``"link"`` or ``"world"``; ``tensor``: float32 ``[N, K, 9]`` on the env's device, only read, per record
+        force[3] | position[3] | torque[3] in that frame (``"world"``: a world point, taken on the link at the call's first pose;
+        ``"link"``: a point of the link's frame).  ``hold_substeps``: the records act in that many of the call's first sub-steps
+        (None, <= 0 or >= frame_skip: all of them; 1: Bullet's literal clearing after one stepSimulation).  Never synchronises."""
         self._check_handle()
+        if link_wrenches is not None:
+            if joint_state is not None:
+                raise AssertionError("world_step: link_wrenches act on the handle's simulated joints; joint_state must be None")
+            specs, tensor = link_wrenches
+            specs = list(specs)
+            arr = self._wrench_specs(specs)
+            wr = self._in(tensor, (self.num_envs, len(specs), _lib.WRENCH_DIM), torch.float32, "link_wrenches")
+            tq = None if joint_torques is None else self._in(joint_torques, (self.num_envs, 6), torch.float32, "joint_torques")
+            self._chk(self.lib.pnr_world_step_wrenches(self._h, arr, len(specs), _ptr(wr), _ptr(tq),
+                                                       0 if hold_substeps is None else int(hold_substeps), self._stream()))
+            return
+        if hold_substeps is not None:
+            raise AssertionError("world_step: hold_substeps belongs to link_wrenches")
         if joint_torques is not None:
             if joint_state is not None:
                 raise AssertionError("world_step: joint_torques act on the handle's simulated joints; joint_state must be None")
