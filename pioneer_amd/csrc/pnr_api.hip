@@ -2,9 +2,10 @@
 // Pioneer-arm engine.  gfx950 only; no CPU fallback.
 //
 // Execution shape: a lane PAIR per env (three joints per lane), one 64-lane wave
-// = 32 envs per workgroup.  State lives in HBM as three float4 planes [3][2n]
-// (24 words per env), so a wave moves each plane with one 1-KiB dwordx4
-// instruction.  Observations are staged through a 17.5 KB LDS tile and leave as
+// = 32 envs per workgroup.  State lives in HBM as two float4 planes [2][2n], a
+// float2 hot half [2n] and a float4 cold part [n] (24 words per env, pnr_device.h),
+// so a wave moves each plane with one 1-KiB dwordx4 instruction and stores the
+// cold part only where it resets an env.  Observations are staged through a 17.5 KB LDS tile and leave as
 // 16-byte stores: env-major rows of a wave are one contiguous 17.5 KB span;
 // feature-major columns leave as 128-B segments, eight features per
 // instruction, as non-temporal stores (write-once streaming data must not churn

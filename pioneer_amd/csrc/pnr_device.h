@@ -34,7 +34,7 @@ constexpr int kTileFloats = kEnvsPerWave * kObsDim;
 
 // Kernel parameters (by value -> kernarg segment -> scalar loads).
 struct KParams {
-    float4* state;             // [3][2n] float4 planes (library-owned), see load_state
+    float4* state;             // 6n float4 (library-owned), see load_state_raw
     const float* actions;      // step / rollout
     float* obs;
     float* reward;
@@ -87,21 +87,86 @@ __device__ __forceinline__ float xchg(float x)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, false));
 }
 
-// State in HBM: three float4 planes [3][2n]; record (e, p) at index 2e + p:
-//   plane 0: a[3p] a[3p+1] a[3p+2] v[3p]
-//   plane 1: v[3p+1] v[3p+2] r[3p] r[3p+1]
-//   plane 2: r[3p+2] C0 C1 C2     p = 0: C = target xyz; p = 1: C = potential, step_index, episode
-// so a wave reads/writes each plane with one lane-contiguous 1-KiB dwordx4.
-struct RawState { float4 p0, p1, p2; };
+// State in HBM: 6n float4 (96 B per env, sizeof(float4) * kStatePlanes * 2 * n), in four parts.  Record (e, p) has index 2e + p:
+//   plane 0   float4 [2n] at float4 index 0:    a[3p] a[3p+1] a[3p+2] v[3p]
+//   plane 1   float4 [2n] at float4 index 2n:   v[3p+1] v[3p+2] r[3p] r[3p+1]
+//   hot half  float2 [2n] at float4 index 4n:   r[3p+2] H        p = 0: H = potential; p = 1: H = step_index
+//   cold part float4 [n]  at float4 index 5n:   target x, y, z, episode         (index e)
+// so a wave of lane pairs reads / writes planes 0 and 1 with one lane-contiguous 1-KiB dwordx4 each and the hot half with one
+// 512-B dwordx2: the 80 bytes of an env that every step changes.  The cold part changes only where an env is reset (or the
+// caller sets the state): a step loads it (both lanes of a pair the same 16 bytes) and stores it inside the reset branch only.
+struct RawState { float4 p0, p1; float2 h; float4 c; };     // what a lane of the pair loads: its half record and the env's cold words
+
+__device__ __forceinline__ float2* state_hot(float4* st, long long n) { return reinterpret_cast<float2*>(st + 4 * n); }
+__device__ __forceinline__ const float2* state_hot(const float4* st, long long n) { return reinterpret_cast<const float2*>(st + 4 * n); }
+__device__ __forceinline__ float4* state_cold(float4* st, long long n) { return st + 5 * n; }
+__device__ __forceinline__ const float4* state_cold(const float4* st, long long n) { return st + 5 * n; }
 
 __device__ __forceinline__ RawState load_state_raw(const float4* __restrict__ st, long long n, long long rec)
 {
-    const long long n2 = 2 * n;
-    return {st[rec], st[n2 + rec], st[2 * n2 + rec]};
+    return {st[rec], st[2 * n + rec], state_hot(st, n)[rec], state_cold(st, n)[rec >> 1]};
 }
 
-// The one statement of that packing: a half record <-> a, v, r of its three joints and its common words C (c: null = not wanted).
-__device__ __forceinline__ void unpack_record(const RawState& k, float* a, float* v, float* r, float* c = nullptr)
+// cold: the env's target or episode changed (both lanes of the pair pass the same; the pair's first lane writes the 16 bytes)
+__device__ __forceinline__ void store_state_raw(float4* __restrict__ st, long long n, long long rec, int p, const RawState& w, bool cold)
+{
+    st[rec] = w.p0; st[2 * n + rec] = w.p1; state_hot(st, n)[rec] = w.h;
+    if (cold && !p) state_cold(st, n)[rec >> 1] = w.c;
+}
+
+// The one statement of the packing: a half record <-> a, v, r of its three joints
+__device__ __forceinline__ void unpack_record(const RawState& k, float* a, float* v, float* r)
+{
+    a[0] = k.p0.x; a[1] = k.p0.y; a[2] = k.p0.z; v[0] = k.p0.w;
+    v[1] = k.p1.x; v[2] = k.p1.y; r[0] = k.p1.z; r[1] = k.p1.w;
+    r[2] = k.h.x;
+}
+
+__device__ __forceinline__ RawState pack_state(int p, const LaneState& s)
+{
+    return {make_float4(s.a[0], s.a[1], s.a[2], s.v[0]), make_float4(s.v[1], s.v[2], s.r[0], s.r[1]),
+            make_float2(s.r[2], p ? __uint_as_float(s.step) : s.pot),
+            make_float4(s.tgt[0], s.tgt[1], s.tgt[2], __uint_as_float(s.episode))};
+}
+
+// the pair's lanes each hold one of potential / step_index: one DPP exchange
+__device__ __forceinline__ void unpack_state(const RawState& raw, int p, LaneState& s)
+{
+    unpack_record(raw, s.a, s.v, s.r);
+    s.tgt[0] = raw.c.x; s.tgt[1] = raw.c.y; s.tgt[2] = raw.c.z;
+    s.episode = __float_as_uint(raw.c.w);
+    const float o = xchg(raw.h.y);
+    s.pot = p ? o : raw.h.y;
+    s.step = __float_as_uint(p ? raw.h.y : o);
+}
+
+__device__ __forceinline__ void load_state(const float4* __restrict__ st, long long n, long long rec, int p, LaneState& s)
+{
+    unpack_state(load_state_raw(st, n, rec), p, s);
+}
+
+__device__ __forceinline__ void store_state(float4* __restrict__ st, long long n, long long rec, int p, const LaneState& s, bool cold)
+{
+    store_state_raw(st, n, rec, p, pack_state(p, s), cold);
+}
+
+// One lane, both halves of env base + off (kernels of one env per lane): the env's two half records with their common words
+// alongside — C = target xyz for the first half, potential, step_index, episode for the second — as the dynamics kernels carry
+// them in registers and through their LDS hand-off.  The addresses are (plane pointer + the wave's first env) + lane offset.
+struct HalfRec { float4 p0, p1, p2; };                      // p2 = r[3p+2] C0 C1 C2
+
+__device__ __forceinline__ void load_env_halves(const float4* __restrict__ st, long long n, long long base, int off, HalfRec (&k)[2])
+{
+    const float4* s0 = st + 2 * base;
+    const float4* s1 = st + 2 * n + 2 * base;
+    const float2* sh = state_hot(st, n) + 2 * base;
+    const float4 c = (state_cold(st, n) + base)[off];
+    const float2 h0 = sh[2 * off], h1 = sh[2 * off + 1];
+    k[0] = {s0[2 * off], s1[2 * off], make_float4(h0.x, c.x, c.y, c.z)};
+    k[1] = {s0[2 * off + 1], s1[2 * off + 1], make_float4(h1.x, h0.y, h1.y, c.w)};
+}
+
+__device__ __forceinline__ void unpack_record(const HalfRec& k, float* a, float* v, float* r, float* c = nullptr)
 {
     a[0] = k.p0.x; a[1] = k.p0.y; a[2] = k.p0.z; v[0] = k.p0.w;
     v[1] = k.p1.x; v[2] = k.p1.y; r[0] = k.p1.z; r[1] = k.p1.w;
@@ -109,12 +174,13 @@ __device__ __forceinline__ void unpack_record(const RawState& k, float* a, float
     if (c) { c[0] = k.p2.y; c[1] = k.p2.z; c[2] = k.p2.w; }
 }
 
-__device__ __forceinline__ RawState pack_record(const float* a, const float* v, const float* r, float c0, float c1, float c2)
+__device__ __forceinline__ HalfRec pack_record(const float* a, const float* v, const float* r, float c0, float c1, float c2)
 {
     return {make_float4(a[0], a[1], a[2], v[0]), make_float4(v[1], v[2], r[0], r[1]), make_float4(r[2], c0, c1, c2)};
 }
 
-__device__ __forceinline__ void unpack_state(const RawState& raw, int p, LaneState& s)
+// a pair lane's LaneState from its half record: the common words of the other half cross by DPP
+__device__ __forceinline__ void unpack_state(const HalfRec& raw, int p, LaneState& s)
 {
     const float4 p2 = raw.p2;
     unpack_record(raw, s.a, s.v, s.r);
@@ -123,19 +189,6 @@ __device__ __forceinline__ void unpack_state(const RawState& raw, int p, LaneSta
     s.pot = p ? p2.y : o1;
     s.step = __float_as_uint(p ? p2.z : o2);
     s.episode = __float_as_uint(p ? p2.w : o3);
-}
-
-__device__ __forceinline__ void load_state(const float4* __restrict__ st, long long n, long long rec, int p, LaneState& s)
-{
-    unpack_state(load_state_raw(st, n, rec), p, s);
-}
-
-__device__ __forceinline__ void store_state(float4* __restrict__ st, long long n, long long rec, int p, const LaneState& s)
-{
-    const long long n2 = 2 * n;
-    const RawState w = pack_record(s.a, s.v, s.r, p ? s.pot : s.tgt[0], p ? __uint_as_float(s.step) : s.tgt[1],
-                                   p ? __uint_as_float(s.episode) : s.tgt[2]);
-    st[rec] = w.p0; st[n2 + rec] = w.p1; st[2 * n2 + rec] = w.p2;
 }
 
 __device__ __forceinline__ void zero_state(LaneState& s)

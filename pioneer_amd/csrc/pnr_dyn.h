@@ -959,11 +959,8 @@ template <bool ACT_EM, bool RAND>
 __device__ __forceinline__ void dyn_lane_load(const DynLead& in, long long base, int lane, DynLane& L)
 {
     const long long n = in.n;
-    const long long n2 = 2 * n;
-    RawState k[2];
-    const float4* s0 = in.state + 2 * base;                       // record 2 * env + p of plane 0 for this workgroup
-#pragma unroll
-    for (int p = 0; p < 2; ++p) k[p] = {s0[2 * lane + p], (s0 + n2)[2 * lane + p], (s0 + 2 * n2)[2 * lane + p]};
+    HalfRec k[2];
+    load_env_halves(in.state, n, base, lane, k);                  // (the workgroup's first env in the uniform part of the addresses)
     // the 35 planar dyn words through ONE walking pointer (plane p at dyn + p * n): two address registers in all
     const float* w = in.dyn + base + lane;
 #pragma unroll
@@ -1147,13 +1144,11 @@ __device__ __forceinline__ void dyn_draw_params(const KParams& P, const DynParam
 // In: nothing but the env index.  Out: the env's two state records as they lie in HBM (a, v, r updated), q, qd.
 // ---------------------------------------------------------------------------------
 template <bool ACT_EM, bool RAND, int PHYS>
-__device__ __forceinline__ void dyn_substeps_lane(const DynLead& in, const DynParams& D, long long e, RawState (&k)[2],
+__device__ __forceinline__ void dyn_substeps_lane(const DynLead& in, const DynParams& D, long long e, HalfRec (&k)[2],
                                                   float (&q)[kDof], float (&qd)[kDof])
 {
     const long long n = in.n;
-    const long long n2 = 2 * n;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) k[p] = {in.state[2 * e + p], in.state[n2 + 2 * e + p], in.state[2 * n2 + 2 * e + p]};
+    load_env_halves(in.state, n, e, 0, k);
     // dynamics state: every load is issued here, before the first wait — with one wave per SIMD
     // (65 536 envs) nothing else hides a memory round trip
     float sc[kNumLinks], fric[kDof], damp[kDof];

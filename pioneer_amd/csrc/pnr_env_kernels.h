@@ -70,7 +70,7 @@ __device__ __forceinline__ void store_outcome(const KParams& P, const Outcome& c
 // is paid in full.  What the loops cost there is everything LLVM hoists in front of them (the reset path's Philox key schedule,
 // prefetch addresses, rollout strides): gfx950 listing, <true, true>: 447 instructions between the first loads and the integrator,
 // 193 VGPRs, 106 SGPRs and 92 v_writelane / v_readlane scalar spills in the general form; 48 instructions (the tile's 36 constant
-// entries among them), 119 VGPRs, 74 SGPRs and no spill in the one-pass form.  Both forms request the three state planes and the
+// entries among them), 119 VGPRs, 74 SGPRs and no spill in the one-pass form.  Both forms request the state record's four parts and the
 // first action back to back, fetch P's scalars and write the constants behind them, and wait first for plane 0 alone.  The
 // integrator takes the lane's three joints side by side (integrate_joints3, pnr_device.h: one branch, three interleaved f64 division
 // chains, where three nested exec-mask regions per joint ran one after the other).  The new action: the general form waits for it
@@ -128,9 +128,10 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
     if (tix >= ntiles) return;              // a whole wave past the last tile (no barrier follows in this kernel)
 
     // The head of the launch.  Every wave of a launch is here at the same time and HBM idles until the first flush, so what
-    // stands between kernel entry and the integrator is paid in full: the three state planes and the first action are requested
-    // back to back, with no branch round them (the join's register copies would wait for the first plane before the last load
-    // is out): a lane past the end reads the tile's first env again — in bounds, and nothing of such a lane is ever stored.
+    // stands between kernel entry and the integrator is paid in full: the state record's four parts (planes 0 and 1, hot half,
+    // cold part: the integrator waits for the first three only) and the first action are requested back to back, with no branch
+    // round them (the join's register copies would wait for the first plane before the last load is out): a lane past the end
+    // reads the tile's first env again — in bounds, and nothing of such a lane is ever stored.
     RawState raw;
     float act0[kJpl];
     {
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
             raw = load_state_raw(state_, n, 2 * nt * kEnvsPerWave + lane);
             load_act0(nt * kEnvsPerWave + el, act0);
         } else {
-            raw = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+            raw = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float2(0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
         }
     }
 
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
         continue;
     }
 
+    bool cold = false;                      // some step of this launch reset the env: its target and episode go out with the state
     for (int t = 0; t < T; ++t) {
         {
             // -- action of this step (this lane's three joints) ----------------------
@@ -230,10 +232,11 @@ __global__ __launch_bounds__(kWave * kStepWaves) void step_kernel(float4* __rest
         if (P.auto_reset && (oc.done || oc.trunc)) {
             reset_env(P, K, s, p, P.env_off + (unsigned long long)e, nullptr, nullptr);
             compute_pose(s, p, q);
+            cold = true;
         }
 
         // state goes out before the obs is packed: its stores drain under the LDS emit
-        if (t == T - 1 && valid && !diag_nostate) store_state(state_, n, rec, p, s);
+        if (t == T - 1 && valid && !diag_nostate) store_state(state_, n, rec, p, s, cold);
 
         // -- observe() ----------------------------------------------------------------
         if (t > 0 || !first_tile) wave_lds_sync();   // previous flush done before the tile is rewritten
@@ -263,12 +266,12 @@ constexpr int kHandFloats = kHandRecFloats + 2 * kDof * kDynEnvsPerWg;
 static_assert(kHandFloats <= kTileFloats, "the hand-off area must fit into the obs tile it aliases");
 
 struct DynTileRegs {      // what phase A handed over for this lane's record of one env
-    RawState raw;         // a, v, r of the lane's three joints (+ the common words on the first step)
+    HalfRec raw;          // a, v, r of the lane's three joints (+ the common words on the first step)
     float q[kJpl], qd[kJpl];
 };
 
 // phase A's results for the lane's env: its two state records and the simulated q, qd
-__device__ __forceinline__ void dyn_write_handoff(float* hand, int lane, const RawState (&k)[2], const float (&q)[kDof],
+__device__ __forceinline__ void dyn_write_handoff(float* hand, int lane, const HalfRec (&k)[2], const float (&q)[kDof],
                                                   const float (&qd)[kDof])
 {
     float4* hrec = reinterpret_cast<float4*>(hand);               // [3][2 * 64] records, index 2 * env + p
@@ -318,7 +321,7 @@ __device__ __forceinline__ void dyn_finish_tile(const KParams& P, const DynParam
 
     LaneState s;
     {
-        RawState raw = in.raw;              // all-zero records for lanes past the end
+        HalfRec raw = in.raw;               // all-zero records for lanes past the end
         if (ROLLOUT && t > 0) { const float4 c = *com; raw.p2.y = c.y; raw.p2.z = c.z; raw.p2.w = c.w; }
         unpack_state(raw, p, s);            // a, v, r of this lane's joints + the env's common words
     }
@@ -359,7 +362,7 @@ __device__ __forceinline__ void dyn_finish_tile(const KParams& P, const DynParam
         compute_pose(o, p, q);
     }
     if (valid && last) {
-        store_state(P.state, n, 2 * tile0 + lane, p, s);
+        store_state(P.state, n, 2 * tile0 + lane, p, s, ROLLOUT || redraw);   // (a rollout: some earlier step may have reset the env)
         if (!redraw) {
 #pragma unroll
             for (int i = 0; i < kJpl; ++i) {
@@ -402,7 +405,7 @@ __global__ __launch_bounds__(kWave * kDynStepWaves) void dyn_step_kernel(const f
     // ---- phase A: one env per lane (wave 0)
     if (wv == 0) {
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        RawState k[2] = {{z4, z4, z4}, {z4, z4, z4}};               // all-zero records for lanes past the end
+        HalfRec k[2] = {{z4, z4, z4}, {z4, z4, z4}};               // all-zero records for lanes past the end
         float q[kDof] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, qd[kDof] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         const DynLead lead = {state_, dyn_, actions_, n_, dt_, eps_, max_v_to_r_};
         if (base + lane < n) dyn_substeps_lane<ACT_EM, RAND, PHYS>(lead, D, base + lane, k, q, qd);
@@ -497,7 +500,7 @@ __global__ __launch_bounds__(kWave * kDynRolloutWaves) void dyn_rollout_kernel(c
         // ---- phase A: one env per lane
         if (liveA) dyn_lane_advance<ACT_EM, RAND, PHYS>(lead, D, base, lane, t + 1 < T ? actions_ + (long long)(t + 1) * n * kDof : nullptr, L);
         {
-            const RawState k[2] = {pack_record(L.a, L.v, L.r, L.cw[0][0], L.cw[0][1], L.cw[0][2]),
+            const HalfRec k[2] = {pack_record(L.a, L.v, L.r, L.cw[0][0], L.cw[0][1], L.cw[0][2]),
                                    pack_record(L.a + 3, L.v + 3, L.r + 3, L.cw[1][0], L.cw[1][1], L.cw[1][2])};
             dyn_write_handoff(hand, lane, k, L.q, L.qd);
         }
@@ -569,7 +572,7 @@ __global__ __launch_bounds__(kWave) void reset_kernel(const KParams P, const Dyn
             reset_env(P, K, s, p, P.env_off + (unsigned long long)e,
                       P.joint_pos ? P.joint_pos + e * kDof : nullptr,
                       P.target_pos ? P.target_pos + e * 3 : nullptr);
-            store_state(P.state, n, rec, p, s);
+            store_state(P.state, n, rec, p, s, true);
             if (DYN) dyn_reset_lane(P, D, s, p, e, P.env_off + (unsigned long long)e, s.episode - 1);
         }
     }
@@ -611,12 +614,10 @@ __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restri
     const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
     if (e >= n) return;
     float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof];
-    const long long n2 = 2 * n;
+    HalfRec k[2];                           // the env's command state r, v: what a joint without a command of its own tracks
+    load_env_halves(state, n, e, 0, k);
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {           // the env's command state r, v: what a joint without a command of its own tracks
-        const RawState k = {state[2 * e + p], state[n2 + 2 * e + p], state[2 * n2 + 2 * e + p]};
-        unpack_record(k, a + 3 * p, v + 3 * p, r + 3 * p);
-    }
+    for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
         q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
@@ -644,12 +645,10 @@ __global__ __launch_bounds__(kWave) void dyn_world_torque_kernel(const float4* _
     const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
     if (e >= n) return;
     float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
-    const long long n2 = 2 * n;
+    HalfRec k[2];
+    load_env_halves(state, n, e, 0, k);
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const RawState k = {state[2 * e + p], state[n2 + 2 * e + p], state[2 * n2 + 2 * e + p]};
-        unpack_record(k, a + 3 * p, v + 3 * p, r + 3 * p);
-    }
+    for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
         q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
@@ -679,12 +678,10 @@ __global__ __launch_bounds__(kWave) void dyn_world_wrench_kernel(const float4* _
     const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
     if (e >= n) return;
     float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
-    const long long n2 = 2 * n;
+    HalfRec k[2];
+    load_env_halves(state, n, e, 0, k);
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const RawState k = {state[2 * e + p], state[n2 + 2 * e + p], state[2 * n2 + 2 * e + p]};
-        unpack_record(k, a + 3 * p, v + 3 * p, r + 3 * p);
-    }
+    for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
         q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
@@ -735,29 +732,27 @@ __global__ void kin_world_kernel(float* __restrict__ js, long long n, float step
     js[e * 12 + j] = q; js[e * 12 + 6 + j] = qd;
 }
 
-// canonical planar words [24][n] (include/pioneer_amd.h) <-> the engine's pair records
-__device__ __forceinline__ int word_of(int p, int plane, int comp)
-{
-    // which canonical word sits in (half p, plane, component)
-    const int k = plane * 4 + comp;            // 0..11 within the half record
-    if (k < 3) return 0 + 3 * p + k;           // a
-    if (k < 6) return 6 + 3 * p + (k - 3);     // v
-    if (k < 9) return 12 + 3 * p + (k - 6);    // r
-    return (p ? 21 : 18) + (k - 9);            // target xyz | potential, step, episode
-}
-
+// canonical planar words [24][n] (include/pioneer_amd.h) <-> the engine's records (pnr_device.h): one thread per half record
 __global__ void state_to_words_kernel(const float4* __restrict__ st, uint32_t* __restrict__ w, long long n)
 {
     const long long rec = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (rec >= 2 * n) return;
     const long long e = rec >> 1; const int p = (int)(rec & 1);
+    const RawState k = load_state_raw(st, n, rec);
+    float a[kJpl], v[kJpl], r[kJpl];
+    unpack_record(k, a, v, r);
 #pragma unroll
-    for (int pl = 0; pl < kStatePlanes; ++pl) {
-        const float4 v = st[(long long)pl * 2 * n + rec];
-        w[(long long)word_of(p, pl, 0) * n + e] = __float_as_uint(v.x);
-        w[(long long)word_of(p, pl, 1) * n + e] = __float_as_uint(v.y);
-        w[(long long)word_of(p, pl, 2) * n + e] = __float_as_uint(v.z);
-        w[(long long)word_of(p, pl, 3) * n + e] = __float_as_uint(v.w);
+    for (int i = 0; i < kJpl; ++i) {
+        w[(long long)(0 + kJpl * p + i) * n + e] = __float_as_uint(a[i]);
+        w[(long long)(6 + kJpl * p + i) * n + e] = __float_as_uint(v[i]);
+        w[(long long)(12 + kJpl * p + i) * n + e] = __float_as_uint(r[i]);
+    }
+    if (p == 0) {
+        w[18LL * n + e] = __float_as_uint(k.c.x); w[19LL * n + e] = __float_as_uint(k.c.y); w[20LL * n + e] = __float_as_uint(k.c.z);
+        w[21LL * n + e] = __float_as_uint(k.h.y);                   // potential
+        w[23LL * n + e] = __float_as_uint(k.c.w);                   // episode
+    } else {
+        w[22LL * n + e] = __float_as_uint(k.h.y);                   // step_index
     }
 }
 
@@ -766,14 +761,13 @@ __global__ void words_to_state_kernel(float4* __restrict__ st, const uint32_t* _
     const long long rec = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (rec >= 2 * n) return;
     const long long e = rec >> 1; const int p = (int)(rec & 1);
-#pragma unroll
-    for (int pl = 0; pl < kStatePlanes; ++pl) {
-        st[(long long)pl * 2 * n + rec] =
-            make_float4(__uint_as_float(w[(long long)word_of(p, pl, 0) * n + e]),
-                        __uint_as_float(w[(long long)word_of(p, pl, 1) * n + e]),
-                        __uint_as_float(w[(long long)word_of(p, pl, 2) * n + e]),
-                        __uint_as_float(w[(long long)word_of(p, pl, 3) * n + e]));
-    }
+    const auto word = [&](int k) { return __uint_as_float(w[(long long)k * n + e]); };
+    RawState k;
+    k.p0 = make_float4(word(0 + kJpl * p), word(1 + kJpl * p), word(2 + kJpl * p), word(6 + kJpl * p));
+    k.p1 = make_float4(word(7 + kJpl * p), word(8 + kJpl * p), word(12 + kJpl * p), word(13 + kJpl * p));
+    k.h = make_float2(word(14 + kJpl * p), word(p ? 22 : 21));
+    k.c = make_float4(word(18), word(19), word(20), word(23));
+    store_state_raw(st, n, rec, p, k, true);
 }
 
 __global__ void diag_sincos_kernel(const float* __restrict__ x, float* __restrict__ sn, float* __restrict__ cs,

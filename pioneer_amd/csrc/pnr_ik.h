@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kWave) void ik_kernel(const IkArgs A)
     for (int i = 0; i < kDof; ++i) q[i] = 0.f;
     if (live) {
         if (A.target) { const float* t = A.target + 3 * e; tgt = {t[0], t[1], t[2]}; }
-        else { const float4 w = A.state[2 * (2 * A.n) + 2 * e]; tgt = {w.y, w.z, w.w}; }
+        else { const float4 w = state_cold(A.state, A.n)[e]; tgt = {w.x, w.y, w.z}; }
         if (A.q_init) {
             const float* qi = A.q_init + kDof * e;
 #pragma unroll
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(kWave) void ik_pose_kernel(const IkPoseArgs A)
     for (int i = 0; i < kDof; ++i) q[i] = 0.f;
     if (live) {
         if (A.target) { const float* t = A.target + 3 * e; tgt = {t[0], t[1], t[2]}; }
-        else { const float4 w = A.state[2 * (2 * A.n) + 2 * e]; tgt = {w.y, w.z, w.w}; }
+        else { const float4 w = state_cold(A.state, A.n)[e]; tgt = {w.x, w.y, w.z}; }
         const float* tq = A.quat + 4 * e;
         qx = tq[0]; qy = tq[1]; qz = tq[2]; qw = tq[3];
         if (A.q_init) {

@@ -31,7 +31,7 @@ namespace pnr {
 enum : int {
     kJointSrcBuffer = 0,   // caller's [n][12] float32 (q | qd), 16-byte aligned
     kJointSrcDyn = 1,      // dynamics-mode planar words [36][n]: q = words 0-5, qd = 6-11
-    kJointSrcKin = 2,      // kinematic-mode state planes (load_state_raw's layout): q = r (words 12-17), qd = v (6-11)
+    kJointSrcKin = 2,      // kinematic-mode state records (load_env_halves, pnr_device.h): q = r (words 12-17), qd = v (6-11)
 };
 
 // env e's joints from the source SRC
@@ -48,12 +48,11 @@ __device__ __forceinline__ void load_joints(const float* __restrict__ src, const
 #pragma unroll
         for (int i = 0; i < kDof; ++i) { q[i] = src[(long long)i * n + e]; qd[i] = src[(long long)(kDynQd + i) * n + e]; }
     } else {
+        HalfRec k[2];
+        load_env_halves(state, n, e, 0, k);
+        float a[kDof];
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const RawState raw = load_state_raw(state, n, 2 * e + p);
-            qd[3 * p] = raw.p0.w; qd[3 * p + 1] = raw.p1.x; qd[3 * p + 2] = raw.p1.y;
-            q[3 * p] = raw.p1.z; q[3 * p + 1] = raw.p1.w; q[3 * p + 2] = raw.p2.x;
-        }
+        for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, qd + 3 * p, q + 3 * p);
     }
 }
 

@@ -175,9 +175,9 @@ __global__ __launch_bounds__(kRayThreads) void ray_kernel(const RayArgs A)
     }
     if (with_target) {
         for (int slot = tid; slot < nenv; slot += nthreads) {         // the target (state words 18-20)
-            const float4 w = A.state[2 * (2 * A.n) + 2 * (e0 + slot)];
+            const float4 w = state_cold(A.state, A.n)[e0 + slot];
             const float half[3] = {A.target_radius, A.target_radius, A.target_radius};
-            put_ray_prim(recs[slot * kRayEnvPrims + kNumVisuals], diag3(1.f), V3{w.y, w.z, w.w}, kVisSphere, half, A.target_radius, kSegTarget);
+            put_ray_prim(recs[slot * kRayEnvPrims + kNumVisuals], diag3(1.f), V3{w.x, w.y, w.z}, kVisSphere, half, A.target_radius, kSegTarget);
         }
     }
     if (nb > 0) {

@@ -279,9 +279,9 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
     __syncthreads();
     const int nprim = 1 + kNumVisuals + P.n_static;
     if (tid == 0) {                                                  // the target (state words 18-20)
-        const float4 w = state[2 * (2 * n) + 2 * e];
+        const float4 w = state_cold(state, n)[e];
         const float half[3] = {P.target_radius, P.target_radius, P.target_radius};
-        put_prim(prims[0], P, diag3(1.f), V3{w.y, w.z, w.w}, kVisSphere, half, P.target_radius, P.target_rgb, kSegTarget);
+        put_prim(prims[0], P, diag3(1.f), V3{w.x, w.y, w.z}, kVisSphere, half, P.target_radius, P.target_rgb, kSegTarget);
     } else if (tid <= kNumVisuals) {
         const VisualDef& D = kVisuals[tid - 1];
         const float* w = pose[D.body];

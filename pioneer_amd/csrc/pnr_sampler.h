@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kFwdThreads, 2) void ppo_rollout_kernel(const Rollo
     float* fv = reinterpret_cast<float*>(w3l + kMlpNets * kMlpHead * kMlpHid);   // loc | inv | lo | hi, 4 x 144
     float* bl = fv + 4 * kMlpInPad;                                  // [2 nets][b1 | b2 | b3]
     float* actl = bl + kMlpNets * kBiasElems;                        // [64][8] the step's env actions
-    float4* stl = reinterpret_cast<float4*>(actl + kMlpBM * 8);      // [3][128] the 64 envs' state records (pnr_device.h's planes)
+    float4* stl = reinterpret_cast<float4*>(actl + kMlpBM * 8);      // the 64 envs' state records, laid out as a state of kMlpBM envs (pnr_device.h)
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int c = lane & 31, h = lane >> 5;
@@ -90,9 +90,9 @@ __global__ __launch_bounds__(kFwdThreads, 2) void ppo_rollout_kernel(const Rollo
     if (env_wave) {
         const int p = lane & 1, el = lane >> 1;
         const long long tile0 = e0 + kEnvsPerWave * wv;
-        RawState raw = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+        RawState raw = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float2(0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
         if (tile0 + el < n) raw = load_state_raw(S.K.state, n, 2 * tile0 + lane);
-        stl[kWave * wv + lane] = raw.p0; stl[2 * kMlpBM + kWave * wv + lane] = raw.p1; stl[4 * kMlpBM + kWave * wv + lane] = raw.p2;
+        store_state_raw(stl, kMlpBM, kWave * wv + lane, p, raw, true);
         const LaneConsts K = lane_consts(p);
         SinkLdsTile sink{ot + wv * kTileFloats + el * kObsDim, kJpl * p, p};
         emit_obs_const(K, sink);
@@ -297,8 +297,7 @@ __global__ __launch_bounds__(kFwdThreads, 2) void ppo_rollout_kernel(const Rollo
                                       S.max_v_to_r * (K.lim[2] - (-K.lim[2]))};
             LaneState s;
             {
-                const RawState raw = {stl[kWave * wv + lane], stl[2 * kMlpBM + kWave * wv + lane], stl[4 * kMlpBM + kWave * wv + lane]};
-                unpack_state(raw, p, s);
+                unpack_state(load_state_raw(stl, kMlpBM, kWave * wv + lane), p, s);
             }
             const float* al = actl + (kEnvsPerWave * wv + el) * 8 + kJpl * p;
             const float act[kJpl] = {al[0], al[1], al[2]};
@@ -332,7 +331,7 @@ __global__ __launch_bounds__(kFwdThreads, 2) void ppo_rollout_kernel(const Rollo
                 reset_env(S.K, K, s, p, S.K.env_off + (unsigned long long)e, nullptr, nullptr);
                 compute_pose(s, p, q);
             }
-            store_state(stl, kMlpBM, kWave * wv + lane, p, s);
+            store_state(stl, kMlpBM, kWave * wv + lane, p, s, true);
             // observe(): into this wave's tile (its constant entries are in place since the prologue), then to obs slot t + 1
             float* tile = ot + wv * kTileFloats;
             SinkLdsTile sink{tile + el * kObsDim, kJpl * p, p};
@@ -378,10 +377,7 @@ __global__ __launch_bounds__(kFwdThreads, 2) void ppo_rollout_kernel(const Rollo
         const int el = lane >> 1;
         const long long tile0 = e0 + kEnvsPerWave * wv;
         if (tile0 + el < n) {
-            const long long rec = 2 * tile0 + lane, n2 = 2 * n;
-            S.K.state[rec] = stl[kWave * wv + lane];
-            S.K.state[n2 + rec] = stl[2 * kMlpBM + kWave * wv + lane];
-            S.K.state[2 * n2 + rec] = stl[4 * kMlpBM + kWave * wv + lane];
+            store_state_raw(S.K.state, n, 2 * tile0 + lane, lane & 1, load_state_raw(stl, kMlpBM, kWave * wv + lane), true);
         }
     }
 }
