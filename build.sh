@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build the HIP library (gfx950; two translation units compiled in parallel, see pioneer_amd/_lib.py) and the CPU oracle in-tree.
+# Build the HIP library (gfx950; its translation units compiled in parallel, see pioneer_amd/_lib.py) and the CPU oracle in-tree.
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 cd "$HERE"

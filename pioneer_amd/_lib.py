@@ -244,9 +244,13 @@ SIGNATURES = {
 
 
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
+_ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h"]      # what every env-engine unit includes
 UNITS = {
-    "pnr_api.hip": ["pnr_api.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h", "pnr_env_kernels.h", "pnr_query.h",
-                    "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h", "pnr_contacts.h", "pnr_rays.h"],
+    # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (108, 80 of them dynamics mode's)
+    "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
+    # the query entry points of the C ABI and their kernels (23)
+    "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",
+                        "pnr_contacts.h", "pnr_rays.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",
                       "pnr_mlp_gather.h", "pnr_mlp_backward.h", "pnr_mlp_wgrad.h", "pnr_mlp_adam.h", "pnr_sampler.h"],
 }
@@ -272,7 +276,10 @@ def source_fingerprint(files=ENV_KERNEL_SOURCES) -> str:
     return h.hexdigest()[:16]
 
 
-UNIT_TAGS = {"pnr_api.hip": "api", "pnr_learn.hip": "learn"}       # the names the units stamp themselves with (g_unit_fp)
+# the names the units stamp themselves with (g_unit_fp); pnr_build_fingerprint() joins the stamps in this, UNITS', order
+UNIT_TAGS = {"pnr_api.hip": "api", "pnr_queries.hip": "queries", "pnr_learn.hip": "learn"}
+# the units whose code reads PNR_DIAG_BUILD (the step kernels' timing-only ablations): what a -DPNR_DIAG_BUILD=1 variant rebuilds
+DIAG_UNITS = ("pnr_api.hip",)
 
 
 def unit_fingerprint(unit: str, extra_flags=()) -> str:
@@ -317,11 +324,12 @@ def _stale() -> bool:
 
 
 def build_library(force: bool = False, verbose: bool = False, extra_flags=(), out_path: str = None, units=None) -> str:
-    """hipcc --offload-arch=gfx950 -> pioneer_amd/csrc/libpioneer_amd.so (in-tree): the two translation units are compiled in
+    """hipcc --offload-arch=gfx950 -> pioneer_amd/csrc/libpioneer_amd.so (in-tree): the translation units are compiled in
     parallel (only those whose object does not carry the fingerprint of the current sources) and linked.  extra_flags / out_path
     build a variant next to it (e.g. -DPNR_DIAG_BUILD=1 for the timing-only ablations), with objects of its own; `units` names the translation units the flags concern (e.g. ("pnr_learn.hip",) for an
-    MLP kernel A/B) — the others are linked from the default build's objects.  A full forced build takes ~95 s on 8 cores
-    (pnr_api.hip: ~95 s, pnr_learn.hip: ~20 s, in parallel)."""
+    MLP kernel A/B) — the others are linked from the default build's objects.  Measured on 8 cores: a full forced build 92 s, which is
+    pnr_api.hip's (pnr_queries.hip ~15 s, pnr_learn.hip ~20 s, in parallel; with the queries in that unit it was 129 s); after a
+    change to pnr_rays.h 15 s (was 133 s), after one to pnr_env_kernels.h 116 s (was 133 s)."""
     variant = out_path is not None or bool(extra_flags)
     if variant:
         force = True

@@ -1,7 +1,10 @@
-// pnr_api.hip — kernels + C ABI (include/pioneer_amd.h) of the MI355X-native
-// Pioneer-arm engine.  gfx950 only; no CPU fallback.
+// pnr_api.hip — the core unit of the MI355X-native Pioneer-arm engine's C ABI (include/pioneer_amd.h): the handle, the error
+// plumbing, config / create / destroy, reset / observe / step / rollout / world step with every one of their argument checks,
+// the joint motors, the state getters and setters.  It launches every kernel of pnr_env_kernels.h: step_kernel, reset_kernel,
+// the dynamics-mode step, rollout and world-step kernels, kin_world_kernel, the two state converters and diag_sincos_kernel
+// (why the dynamics kernels compile here: DESIGN.md 3m).  The queries are pnr_queries.hip's.  gfx950 only; no CPU fallback.
 //
-// Execution shape: a lane PAIR per env (three joints per lane), one 64-lane wave
+// Execution shape of the step kernels: a lane PAIR per env (three joints per lane), one 64-lane wave
 // = 32 envs per workgroup.  State lives in HBM as two float4 planes [2][2n], a
 // float2 hot half [2n] and a float4 cold part [n] (24 words per env, pnr_device.h),
 // so a wave moves each plane with one 1-KiB dwordx4 instruction and stores the
@@ -26,7 +29,7 @@
 #include <initializer_list>
 #include <memory>
 #include <new>
-#include <type_traits>
+#include <string>
 
 #include "../../include/pioneer_amd.h"
 
@@ -38,39 +41,13 @@
 #define PNR_DIAG_BUILD 0
 #endif
 
-#include "pnr_host.h"
-#include "pnr_device.h"
-#include "pnr_dyn.h"
+#include "pnr_env_host.h"
 #include "pnr_env_kernels.h"
-#include "pnr_links.h"
-#include "pnr_render.h"
-#include "pnr_ik.h"
-#include "pnr_invdyn.h"
-#include "pnr_contacts.h"
-#include "pnr_rays.h"
 
 // =====================================================================================
 // host side
 // =====================================================================================
 using namespace pnr;
-
-struct pnr_env_s {
-    pnr_config cfg;
-    pnr_constants k;
-    KParams base;        // constants pre-filled; pointers set per call
-    DynParams dbase;     // dynamics-mode constants (zeroed in kinematic mode)
-    JointMotorTable motors;   // pnr_world_step's per-joint motors (pnr_set_joint_motor); fill_base: every joint on the handle's own law
-    long long n;
-    unsigned long long env_off;
-    int device;
-    float4* state;
-    float* dyn;          // dynamics-mode planar words [36][n] or null
-    SceneBody* scene;    // dynamics-mode static scene bodies [kMaxScene] or null
-    int diag;            // -DPNR_DIAG_BUILD=1 variant only: the PNR_DIAG environment variable at create time; else 0
-    bool ready;          // a full reset has happened, or the state was set explicitly
-    bool kin_set, dyn_set;  // pnr_set_state / pnr_set_dyn_state seen (both needed in dynamics mode)
-    char err[512];
-};
 
 static thread_local char g_err[512] = "";
 
@@ -83,7 +60,7 @@ int pnr_failv(char* handle_err, int code, const char* fmt, va_list ap)
     return code;
 }
 
-static int fail(pnr_handle h, int code, const char* fmt, ...)
+int fail(pnr_handle h, int code, const char* fmt, ...)       // (pnr_env_host.h: the env units' one error call)
 {
     va_list ap;
     va_start(ap, fmt);
@@ -92,114 +69,11 @@ static int fail(pnr_handle h, int code, const char* fmt, ...)
     return rc;
 }
 
-static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 static inline bool aligned16(const void* p) { return aligned_to(p, 16); }
 static inline bool aligned8(const void* p) { return aligned_to(p, 8); }
 
-// a call's pointer arguments against their alignment, in the order given (a null pointer passes); `call` names it in the message
-struct AlignedArg { const void* p; const char* name; unsigned align; };
-static int check_aligned(pnr_handle h, const char* call, std::initializer_list<AlignedArg> args)
-{
-    for (const AlignedArg& a : args)
-        if (!aligned_to(a.p, a.align)) return fail(h, PNR_ERR_INVALID, "%s: %s must be %u-byte aligned", call, a.name, a.align);
-    return PNR_OK;
-}
-
-template <class T>
-static bool finite_all(const T* v, int k)
-{
-    for (int i = 0; i < k; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-static double sum_sq(const double* v, int k)      // v[0]^2 + v[1]^2 + .. in that order
-{
-    double s = 0;
-    for (int i = 0; i < k; ++i) s += v[i] * v[i];
-    return s;
-}
-
 // an optional double argument left out (NaN) takes its default, as setJointMotorControl2's optional arguments take Bullet's
 static inline double or_default(double given, double dflt) { return given == given ? given : dflt; }
-
-// Runtime flags -> template arguments: f is called with a std::integral_constant whose value is `b` (or `v`, which must be one of
-// Vs: only the listed values are instantiated).  Every kernel launch below is written once inside such a call.
-template <class F>
-static inline void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-template <int... Vs, class F>
-static inline void with_int(int v, F&& f) { (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
-
-// One static body of the scene, checked: `who` names the call in the message, `finite` adds pnr_render's rule
-static int check_scene_body(pnr_handle h, const char* who, int b, const pnr_scene_body& S, bool finite)
-{
-    const auto bad = [&](const char* what) { return fail(h, PNR_ERR_INVALID, "%s %d: %s", who, b, what); };
-    if (S.shape != PNR_SHAPE_PLANE && S.shape != PNR_SHAPE_BOX && S.shape != PNR_SHAPE_SPHERE)
-        return fail(h, PNR_ERR_INVALID, "%s %d: bad shape %d", who, b, S.shape);
-    if (finite && !(finite_all(S.position, 3) && finite_all(S.orientation, 4) && finite_all(S.size, 3))) return bad("non-finite data");
-    if (!(sum_sq(S.orientation, 4) > 0)) return bad("zero orientation quaternion");
-    if (S.shape == PNR_SHAPE_PLANE && !(sum_sq(S.size, 3) > 0)) return bad("zero plane normal");
-    if (S.shape == PNR_SHAPE_BOX && !(S.size[0] > 0 && S.size[1] > 0 && S.size[2] > 0)) return bad("box half extents must be > 0");
-    if (S.shape == PNR_SHAPE_SPHERE && !(S.size[0] > 0)) return bad("sphere radius must be > 0");
-    return PNR_OK;
-}
-
-// .. and its frame: the normalised quaternion as a row-major rotation R; for a plane also the unit world normal R n / |n|
-static void scene_body_frame(const pnr_scene_body& S, double (&R)[9], double (&normal)[3])
-{
-    const double qn = std::sqrt(sum_sq(S.orientation, 4));
-    const double x = S.orientation[0] / qn, y = S.orientation[1] / qn, z = S.orientation[2] / qn, w = S.orientation[3] / qn;
-    const double r[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                         2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                         2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
-    for (int k = 0; k < 9; ++k) R[k] = r[k];
-    if (S.shape != PNR_SHAPE_PLANE) return;
-    const double nl = std::sqrt(sum_sq(S.size, 3));
-    for (int k = 0; k < 3; ++k) normal[k] = (R[3 * k] * S.size[0] + R[3 * k + 1] * S.size[1] + R[3 * k + 2] * S.size[2]) / nl;
-}
-
-// .. and as the kernels want it (pnr_dyn.h SceneBody): float32, pre-rotated; a plane keeps its unit world normal in rot[0..2]
-static SceneBody scene_body_device(const pnr_scene_body& B)
-{
-    SceneBody S = SceneBody{};
-    double R[9], normal[3];
-    scene_body_frame(B, R, normal);
-    S.shape = B.shape;
-    for (int k = 0; k < 3; ++k) { S.pos[k] = (float)B.position[k]; S.size[k] = (float)B.size[k]; }
-    if (B.shape == PNR_SHAPE_PLANE) {
-        for (int k = 0; k < 3; ++k) S.rot[k] = (float)normal[k];
-    } else {
-        for (int k = 0; k < 9; ++k) S.rot[k] = (float)R[k];
-    }
-    return S;
-}
-
-// .. and as the ray casters want it (pnr_render, pnr_ray_test): the world -> primitive rotation rows rt, the half sizes h and the
-// bounding radius (a plane: rows 0 and 1 zero, row 2 its unit world normal, no bound).  Returns the kVis* shape.
-static int scene_body_prim(const pnr_scene_body& S, double (&rt)[9], float (&h)[3], double& bound)
-{
-    double R[9], normal[3];
-    scene_body_frame(S, R, normal);
-    const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int k = 0; k < 9; ++k) rt[k] = ident[k];
-    h[0] = h[1] = h[2] = 0.f;
-    bound = 0;
-    if (S.shape == PNR_SHAPE_BOX) {
-        for (int i = 0; i < 3; ++i)
-            for (int k = 0; k < 3; ++k) rt[3 * i + k] = R[3 * k + i];
-        for (int i = 0; i < 3; ++i) h[i] = (float)S.size[i];
-        bound = std::sqrt(sum_sq(S.size, 3));
-        return kVisBox;
-    }
-    if (S.shape == PNR_SHAPE_SPHERE) {
-        for (int i = 0; i < 3; ++i) h[i] = (float)S.size[0];
-        bound = S.size[0];
-        return kVisSphere;
-    }
-    for (int k = 0; k < 6; ++k) rt[k] = 0;           // unit world normal R n / |n| as the frame's z row
-    for (int k = 0; k < 3; ++k) rt[6 + k] = normal[k];
-    return kVisPlane;
-}
 
 // One joint's entries of the JointMotorTable, assigned in one place
 struct JointMotor { float kp, kd, cpos, vcap, tcap, r_ref = 0.f, v_ref = 0.f; int from_cmd = 0, kind = kMotorPD; };
@@ -228,34 +102,6 @@ static JointMotor pd_motor(bool velocity, double kp, double kd, double force_lim
 // the dynamics kernels' PHYS template argument: bit 0 contacts (contact-free handles run instantiations without any contact
 // code), bit 1 the inertia-scaled motor
 static inline int dyn_phys(const DynParams& D) { return ((D.has_ground || D.has_box || D.n_scene > 0) ? 1 : 0) | (D.inertia_scaled ? 2 : 0); }
-
-// whose joints a query or a render reads (pnr_query.h): the caller's buffer, else the handle's own (h->dyn; kinematic: the state)
-struct JointSource { int kind; const float* src; const float4* state; };
-static inline JointSource joint_source(pnr_handle h, const float* js)
-{
-    return js ? JointSource{kJointSrcBuffer, js, nullptr} : h->dyn ? JointSource{kJointSrcDyn, h->dyn, nullptr} : JointSource{kJointSrcKin, nullptr, h->state};
-}
-
-// one launch of a kernel of one env per lane and one wave per workgroup: kernel(S)(args...), S = the joint source `kind`
-template <class K, class... Args>
-static int launch_env_waves(pnr_handle h, void* stream, int kind, K&& kernel, Args... args)
-{
-    DeviceGuard g(h->device);
-    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
-    with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(kind, [&](auto S) {
-        hipLaunchKernelGGL(kernel(S), grid, dim3(kWave), 0, (hipStream_t)stream, args...);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
-}
-
-// What a query needs of the handle when the caller brings no data of its own, one predicate per rule.  They differ, and
-// pnr_get_link_states' is the odd one: it takes a dynamics handle whose joints were never set.
-static inline bool has_own_joints(pnr_handle h) { return h->ready || (h->dyn && h->dyn_set); }     // pnr_get_jacobian, pnr_get_contacts
-static inline bool has_own_joints_or_planes(pnr_handle h) { return h->ready || h->dyn; }           // pnr_get_link_states
-static inline bool has_link_scales(pnr_handle h) { return h->ready || h->dyn_set; }                // dynamics mode: drawn by the first reset
-static inline bool has_own_target(pnr_handle h) { return h->ready || h->kin_set; }                 // pnr_solve_ik, pnr_render
-static int before_first_reset(pnr_handle h, const char* call, const char* why = "") { return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)%s", call, why); }
 
 // the argument checks of pnr_get_state / pnr_set_state and their dyn twins
 static int check_state_call(pnr_handle h, const void* words, const char* call, bool dyn)
@@ -288,9 +134,12 @@ int pnr_abi_version(void) { return PNR_ABI_VERSION; }
 
 const char* pnr_build_fingerprint(void)
 {
-    static char buf[96] = "";
-    if (!buf[0]) snprintf(buf, sizeof(buf), "%s%s", g_unit_fp + 13, pnr_unit_fingerprint_learn() + 13);   // past "pnr_build_fp:"
-    return buf;
+    static const std::string joined = [] {                  // every unit's "<tag>=<sha16>;" (past "pnr_build_fp:"), in _lib.UNITS order
+        std::string s;
+        for (const char* fp : {g_unit_fp, pnr_unit_fingerprint_queries(), pnr_unit_fingerprint_learn()}) s += fp + 13;
+        return s;
+    }();
+    return joined.c_str();
 }
 
 int pnr_config_default(pnr_config* c)
@@ -848,403 +697,6 @@ int pnr_set_dyn_state(pnr_handle h, const float* words_in, void* stream)
     if (h->kin_set) h->ready = true;
     const size_t bytes = sizeof(float) * PNR_DYN_STATE_WORDS * (size_t)h->n;
     HIP_TRY(h, hipMemcpyAsync(h->dyn, words_in, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return PNR_OK;
-}
-
-int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void* stream)
-{
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (!out) return fail(h, PNR_ERR_INVALID, "pnr_get_link_states: null out");
-    if (const int rc = check_aligned(h, "pnr_get_link_states", {{out, "out", 16}, {joint_state, "joint_state", 16}})) return rc;
-    if (!joint_state && !has_own_joints_or_planes(h)) return before_first_reset(h, "pnr_get_link_states");
-    const JointSource J = joint_source(h, joint_state);
-    return launch_env_waves(h, stream, J.kind, [](auto S) { return link_state_kernel<S()>; }, J.src, J.state, out, (long long)h->n);
-}
-
-// (link, local_point) -> the moving body that carries the link and the point's offset in that body's frame: every fixed joint of
-// the URDF has rpy 0 and, but for effector_to_pointer (kTip), xyz 0, so a link's frame is its body's frame moved by a constant
-static ChainPoint chain_point(int link, const double* local_point)
-{
-    double o[3] = {0, 0, 0};
-    if (local_point) for (int k = 0; k < 3; ++k) o[k] = local_point[k];
-    if (link == kNumLinks - 1) { o[0] += kTipX; o[1] += kTipY; o[2] += kTipZ; }
-    return {kLinkBody[link], (float)o[0], (float)o[1], (float)o[2]};
-}
-
-int pnr_get_jacobian(pnr_handle h, const float* joint_state, int32_t link, const double* local_point, float* out, void* stream)
-{
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (!out) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: null out");
-    if (link < 0 || link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: link %d outside 0..%d", link, kNumLinks - 1);
-    if (local_point && !finite_all(local_point, 3)) return fail(h, PNR_ERR_INVALID, "pnr_get_jacobian: non-finite local_point");
-    if (const int rc = check_aligned(h, "pnr_get_jacobian", {{out, "out", 16}, {joint_state, "joint_state", 16}})) return rc;
-    if (!joint_state && !has_own_joints(h)) return before_first_reset(h, "pnr_get_jacobian");
-    const JointSource J = joint_source(h, joint_state);
-    return launch_env_waves(h, stream, J.kind, [](auto S) { return jacobian_kernel<S()>; }, J.src, J.state, out, (long long)h->n,
-                            chain_point(link, local_point));
-}
-
-// the checks pnr_inverse_dynamics and pnr_mass_matrix share (nothing launched, nothing written on failure)
-static int check_invdyn_call(pnr_handle h, const char* call, const float* joint_state, const float* joint_accel, const float* out)
-{
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (!out) return fail(h, PNR_ERR_INVALID, "%s: null out", call);
-    if (const int rc = check_aligned(h, call, {{out, "out", 16}, {joint_state, "joint_state", 16}, {joint_accel, "joint_accel", 16}})) return rc;
-    // a dynamics-mode handle's link scales are drawn by the first reset: no model before it, whatever the joint source
-    if (h->dyn ? !has_link_scales(h) : (!joint_state && !has_own_joints(h))) return before_first_reset(h, call);
-    return PNR_OK;
-}
-
-int pnr_inverse_dynamics(pnr_handle h, const float* joint_state, const float* joint_accel, int32_t flags, float* out, void* stream)
-{
-    if (const int rc = check_invdyn_call(h, "pnr_inverse_dynamics", joint_state, joint_accel, out)) return rc;
-    if (flags & ~(PNR_INVDYN_NO_GRAVITY | PNR_INVDYN_JOINT_LOSSES))
-        return fail(h, PNR_ERR_INVALID, "pnr_inverse_dynamics: unknown flags 0x%x", (unsigned)flags);
-    const JointSource J = joint_source(h, joint_state);
-    InvDynArgs A;
-    A.src = J.src; A.state = J.state;
-    A.dyn = h->dyn; A.accel = joint_accel; A.out = out; A.n = h->n;
-    A.gravity = (flags & PNR_INVDYN_NO_GRAVITY) ? 0.f : (float)h->cfg.gravity;
-    A.loss_gain = (flags & PNR_INVDYN_JOINT_LOSSES) ? 1.f : 0.f;
-    A.damping0 = (float)h->cfg.joint_damping; A.friction0 = (float)h->cfg.joint_friction;
-    return launch_env_waves(h, stream, J.kind, [](auto S) { return inverse_dynamics_kernel<S()>; }, A);
-}
-
-int pnr_mass_matrix(pnr_handle h, const float* joint_state, float* out, void* stream)
-{
-    if (const int rc = check_invdyn_call(h, "pnr_mass_matrix", joint_state, nullptr, out)) return rc;
-    const JointSource J = joint_source(h, joint_state);
-    return launch_env_waves(h, stream, J.kind, [](auto S) { return mass_matrix_kernel<S()>; }, J.src, J.state, (const float*)h->dyn, out,
-                            (long long)h->n);
-}
-
-int pnr_ik_params_default(pnr_ik_params* p)
-{
-    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_ik_params_default: null params");
-    memset(p, 0, sizeof(*p));
-    p->struct_size = (uint32_t)sizeof(pnr_ik_params);
-    p->link = kNumLinks - 1;
-    p->max_iterations = 32;
-    p->damping = 1.0;
-    p->max_step = 0.5;
-    p->tolerance = 1e-3;
-    return PNR_OK;
-}
-
-int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, const float* q_init,
-                 float* q_out, float* residual_out, int32_t* iterations_out, void* stream)
-{
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (!p) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: null params");
-    if (!q_out) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: null q_out");
-    if (p->struct_size != sizeof(pnr_ik_params))
-        return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_ik_params));
-    if (p->link < 0 || p->link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: link %d outside 0..%d", p->link, kNumLinks - 1);
-    if (p->max_iterations < 1 || p->max_iterations > 1024)
-        return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: max_iterations %d outside 1..1024", p->max_iterations);
-    if (!(std::isfinite(p->damping) && p->damping > 0)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: damping must be finite and > 0");
-    if (!(std::isfinite(p->max_step) && p->max_step > 0)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: max_step must be finite and > 0");
-    if (!(std::isfinite(p->tolerance) && p->tolerance >= 0)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: tolerance must be finite and >= 0");
-    if (!finite_all(p->local_point, 3)) return fail(h, PNR_ERR_INVALID, "pnr_solve_ik: non-finite local_point");
-    if (const int rc = check_aligned(h, "pnr_solve_ik", {{q_out, "q_out", 8}, {target_pos, "target_pos", 4}, {q_init, "q_init", 4},
-                                                          {residual_out, "residual_out", 4}, {iterations_out, "iterations_out", 4}})) return rc;
-    if (!target_pos && !has_own_target(h)) return before_first_reset(h, "pnr_solve_ik", ": the target comes from the state");
-    IkArgs A;
-    A.target = target_pos; A.state = h->state; A.q_init = q_init;
-    A.q_out = q_out; A.residual = residual_out; A.iterations = iterations_out;
-    A.n = h->n;
-    A.point = chain_point(p->link, p->local_point);
-    A.max_iter = p->max_iterations;
-    A.lambda2 = (float)(p->damping * p->damping); A.max_step = (float)p->max_step; A.tol = (float)p->tolerance;
-    return launch_env_waves(h, stream, kJointSrcBuffer, [](auto) { return ik_kernel; }, A);      // (no joint source: one form)
-}
-
-int pnr_ik_pose_params_default(pnr_ik_pose_params* p)
-{
-    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_ik_pose_params_default: null params");
-    memset(p, 0, sizeof(*p));
-    p->struct_size = (uint32_t)sizeof(pnr_ik_pose_params);
-    p->link = kNumLinks - 1;
-    p->max_iterations = 32;
-    p->mode = PNR_IK_ORIENT_FULL;
-    p->local_axis[0] = 1.0;
-    p->damping = 0.03;
-    p->error_damping = 0.01;
-    p->orientation_weight = 10.0;
-    p->max_step = 0.5;
-    p->tolerance = 1e-3;
-    p->angle_tolerance = 1e-3;
-    return PNR_OK;
-}
-
-int pnr_solve_ik_pose(pnr_handle h, const pnr_ik_pose_params* p, const float* target_pos, const float* target_quat, const float* q_init,
-                      float* q_out, float* residual_out, float* angle_out, int32_t* iterations_out, void* stream)
-{
-    const char* call = "pnr_solve_ik_pose";
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (!p) return fail(h, PNR_ERR_INVALID, "%s: null params", call);
-    if (!q_out) return fail(h, PNR_ERR_INVALID, "%s: null q_out", call);
-    if (!target_quat) return fail(h, PNR_ERR_INVALID, "%s: null target_quat", call);
-    if (p->struct_size != sizeof(pnr_ik_pose_params))
-        return fail(h, PNR_ERR_INVALID, "%s: params struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_ik_pose_params));
-    if (p->link < 0 || p->link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "%s: link %d outside 0..%d", call, p->link, kNumLinks - 1);
-    if (p->mode != PNR_IK_ORIENT_FULL && p->mode != PNR_IK_ORIENT_AXIS)
-        return fail(h, PNR_ERR_INVALID, "%s: mode %d outside {0, 1} (full orientation, one axis)", call, p->mode);
-    if (p->max_iterations < 1 || p->max_iterations > 1024)
-        return fail(h, PNR_ERR_INVALID, "%s: max_iterations %d outside 1..1024", call, p->max_iterations);
-    const struct { double v; const char* name; bool zero_ok; } scalars[] = {
-        {p->damping, "damping", false}, {p->max_step, "max_step", false}, {p->orientation_weight, "orientation_weight", false},
-        {p->error_damping, "error_damping", true}, {p->tolerance, "tolerance", true}, {p->angle_tolerance, "angle_tolerance", true}};
-    for (const auto& s : scalars)
-        if (!(std::isfinite(s.v) && (s.zero_ok ? s.v >= 0 : s.v > 0)))
-            return fail(h, PNR_ERR_INVALID, "%s: %s must be finite and %s 0", call, s.name, s.zero_ok ? ">=" : ">");
-    if (!finite_all(p->local_point, 3)) return fail(h, PNR_ERR_INVALID, "%s: non-finite local_point", call);
-    const double* ax = p->local_axis;
-    const double axis_len = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-    if (!finite_all(ax, 3) || !std::isfinite(axis_len) || !(axis_len > 0))
-        return fail(h, PNR_ERR_INVALID, "%s: local_axis must be finite and not zero", call);
-    if (const int rc = check_aligned(h, call, {{q_out, "q_out", 8}, {target_pos, "target_pos", 4}, {target_quat, "target_quat", 4},
-                                               {q_init, "q_init", 4}, {residual_out, "residual_out", 4}, {angle_out, "angle_out", 4},
-                                               {iterations_out, "iterations_out", 4}})) return rc;
-    if (!target_pos && !has_own_target(h)) return before_first_reset(h, call, ": the target comes from the state");
-    IkPoseArgs A;
-    A.target = target_pos; A.state = h->state; A.quat = target_quat; A.q_init = q_init;
-    A.q_out = q_out; A.residual = residual_out; A.angle = angle_out; A.iterations = iterations_out;
-    A.n = h->n;
-    A.point = chain_point(p->link, p->local_point);
-    A.max_iter = p->max_iterations; A.axis_mode = p->mode == PNR_IK_ORIENT_AXIS;
-    A.axis = {(float)(ax[0] / axis_len), (float)(ax[1] / axis_len), (float)(ax[2] / axis_len)};
-    A.damping2 = (float)(p->damping * p->damping); A.error_damping = (float)p->error_damping; A.weight = (float)p->orientation_weight;
-    A.max_step = (float)p->max_step; A.tol = (float)p->tolerance; A.angle_tol = (float)p->angle_tolerance;
-    return launch_env_waves(h, stream, kJointSrcBuffer, [](auto) { return ik_pose_kernel; }, A);  // (no joint source: one form)
-}
-
-int pnr_contact_params_default(pnr_contact_params* p)
-{
-    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_contact_params_default: null params");
-    memset(p, 0, sizeof(*p));
-    p->struct_size = (uint32_t)sizeof(pnr_contact_params);
-    p->contact_kp = 2000.0; p->contact_kd = 50.0;       // pnr_config_default's
-    return PNR_OK;
-}
-
-int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_params* p, const float* body_positions, float* points,
-                     float* summary, float* joint_torques, void* stream)
-{
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (!p) return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: null params");
-    if (p->struct_size != sizeof(pnr_contact_params))
-        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_contact_params));
-    if (!points && !summary && !joint_torques) return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: every output is NULL");
-    if (const int rc = check_aligned(h, "pnr_get_contacts", {{points, "points", 16}, {summary, "summary", 16}, {joint_torques, "joint_torques", 16},
-                                                              {joint_state, "joint_state", 16}, {body_positions, "body_positions", 4}})) return rc;
-    if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
-        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: n_bodies %d outside 0..%d", p->n_bodies, PNR_MAX_SCENE);
-    if (!(std::isfinite(p->contact_kp) && std::isfinite(p->contact_kd) && p->contact_kp >= 0 && p->contact_kd >= 0))
-        return fail(h, PNR_ERR_INVALID, "pnr_get_contacts: contact_kp and contact_kd must be finite and >= 0");
-    for (int b = 0; b < p->n_bodies; ++b)
-        if (const int rc = check_scene_body(h, "pnr_get_contacts: body", b, p->bodies[b], true)) return rc;
-    if (!joint_state && !has_own_joints(h)) return before_first_reset(h, "pnr_get_contacts");
-    const JointSource J = joint_source(h, joint_state);
-    ContactArgs A;
-    memset(&A, 0, sizeof(A));
-    A.src = J.src; A.state = J.state;
-    A.body_pos = p->n_bodies > 0 ? body_positions : nullptr;
-    A.points = points; A.summary = summary; A.torques = joint_torques;
-    A.n = h->n;
-    A.ckp = (float)p->contact_kp; A.ckd = (float)p->contact_kd; A.ptr_radius = (float)h->cfg.pointer_radius;
-    A.n_bodies = p->n_bodies;
-    for (int b = 0; b < p->n_bodies; ++b) A.bodies[b] = scene_body_device(p->bodies[b]);
-    return launch_env_waves(h, stream, J.kind, [](auto S) { return contacts_kernel<S()>; }, A);
-}
-
-}  // extern "C"
-
-// pnr_render's checks of its params (nothing launched, nothing written on failure) and the kernel's constants built from them
-static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& P)
-{
-    if (p->struct_size != sizeof(pnr_render_params))
-        return fail(h, PNR_ERR_INVALID, "pnr_render: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_render_params));
-    if (p->width < 1 || p->width > 4096 || p->height < 1 || p->height > 4096)
-        return fail(h, PNR_ERR_INVALID, "pnr_render: image size %d x %d outside 1..4096", p->width, p->height);
-    if (!(p->fov_y > 0 && p->fov_y < 180)) return fail(h, PNR_ERR_INVALID, "pnr_render: fov_y must lie in (0, 180) degrees");
-    if (!(std::isfinite(p->near_clip) && std::isfinite(p->far_clip) && p->near_clip > 0 && p->far_clip > 0))
-        return fail(h, PNR_ERR_INVALID, "pnr_render: near_clip and far_clip must be finite and > 0");
-    if (!(p->near_clip < p->far_clip)) return fail(h, PNR_ERR_INVALID, "pnr_render: near_clip must be < far_clip");
-    if (!finite_all(p->view, 16)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite view matrix");
-    const double* V = p->view;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) {
-            const double d = V[4 * a] * V[4 * b] + V[4 * a + 1] * V[4 * b + 1] + V[4 * a + 2] * V[4 * b + 2];
-            if (!(std::fabs(d - (a == b ? 1.0 : 0.0)) <= 1e-5))
-                return fail(h, PNR_ERR_INVALID, "pnr_render: the view matrix's rotation is not orthonormal");
-        }
-    if (!finite_all(p->light_direction, 3)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite light_direction");
-    const double ll = std::sqrt(sum_sq(p->light_direction, 3));
-    if (!(ll > 0)) return fail(h, PNR_ERR_INVALID, "pnr_render: zero light_direction");
-    if (!std::isfinite(p->ambient) || !std::isfinite(p->diffuse)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite ambient or diffuse");
-    if (!finite_all(p->background, 3)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite background");
-    if (!finite_all(p->target_rgba, 4)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite target_rgba");
-    if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
-        return fail(h, PNR_ERR_INVALID, "pnr_render: n_bodies %d outside 0..%d", p->n_bodies, PNR_MAX_SCENE);
-    for (int b = 0; b < p->n_bodies; ++b) {
-        const int rc = check_scene_body(h, "pnr_render: body", b, p->bodies[b], true);
-        if (rc) return rc;
-        if (!finite_all(p->body_rgba[b], 4)) return fail(h, PNR_ERR_INVALID, "pnr_render: body %d: non-finite colour", b);
-    }
-
-    memset(&P, 0, sizeof(P));
-    // the eye axes are the rows of the view rotation; the eye sits at -R^T t
-    double eye[3];
-    for (int k = 0; k < 3; ++k) eye[k] = -(V[k] * V[3] + V[4 + k] * V[7] + V[8 + k] * V[11]);
-    for (int k = 0; k < 3; ++k) {
-        P.eye[k] = (float)eye[k];
-        P.right[k] = (float)V[k]; P.up[k] = (float)V[4 + k]; P.back[k] = (float)V[8 + k];
-        P.light[k] = (float)(p->light_direction[k] / ll);
-        P.bg[k] = p->background[k];
-        P.target_rgb[k] = p->target_rgba[k];
-    }
-    const double tan_half = std::tan(0.5 * p->fov_y * M_PI / 180.0);
-    P.sy = (float)tan_half;
-    P.sx = (float)(tan_half * (double)p->width / (double)p->height);
-    P.near_clip = (float)p->near_clip; P.far_clip = (float)p->far_clip;
-    P.ambient = (float)p->ambient; P.diffuse = (float)p->diffuse;
-    P.target_alpha = p->target_rgba[3];
-    P.target_radius = (float)h->cfg.target_radius;
-    P.W = p->width; P.H = p->height; P.HW = p->width * p->height;
-    // pixels per lane: 4 (1 024-pixel tiles) unless that leaves fewer than ~4 096 workgroups (one env at 1280 x 800: 4 000 of 256)
-    const long long total = h->n * (long long)P.HW;
-    P.ppl = total >= 4096LL * 1024 ? 4 : (total >= 4096LL * 512 ? 2 : 1);
-    const int tile_px = kRenderThreads * P.ppl;
-    P.tiles = (P.HW + tile_px - 1) / tile_px;
-    if (h->n * (long long)P.tiles > 0x7fffffffLL)
-        return fail(h, PNR_ERR_INVALID, "pnr_render: %lld envs x %d tiles exceed one launch", h->n, P.tiles);
-    // the static bodies, in world space once for all envs
-    P.n_static = p->n_bodies;
-    for (int b = 0; b < p->n_bodies; ++b) {
-        const pnr_scene_body& S = p->bodies[b];
-        RenderPrim& Q = P.bodies[b];
-        const double e[3] = {eye[0] - S.position[0], eye[1] - S.position[1], eye[2] - S.position[2]};
-        double rt[9], bound;
-        Q.shape = scene_body_prim(S, rt, Q.h, bound);
-        double o[3];                                 // the eye in the primitive frame (a plane: o[2] = n . (eye - point))
-        for (int i = 0; i < 3; ++i) o[i] = rt[3 * i] * e[0] + rt[3 * i + 1] * e[1] + rt[3 * i + 2] * e[2];
-        for (int k = 0; k < 9; ++k) Q.rt[k] = (float)rt[k];
-        for (int k = 0; k < 3; ++k) { Q.o[k] = (float)o[k]; Q.rgb[k] = p->body_rgba[b][k]; }
-        Q.label = kSegBody0 + b;
-        if (S.shape == PNR_SHAPE_PLANE) { Q.x0 = 0; Q.x1 = P.W - 1; Q.y0 = 0; Q.y1 = P.H - 1; }
-        else {
-            const double d[3] = {-e[0], -e[1], -e[2]};
-            const float cx = (float)(V[0] * d[0] + V[1] * d[1] + V[2] * d[2]), cy = (float)(V[4] * d[0] + V[5] * d[1] + V[6] * d[2]);
-            const float dz = (float)-(V[8] * d[0] + V[9] * d[1] + V[10] * d[2]);
-            sphere_rect(cx, cy, dz, (float)bound, P, Q.x0, Q.x1, Q.y0, Q.y1);
-        }
-    }
-    return PNR_OK;
-}
-
-extern "C" {
-
-int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* p, uint8_t* rgb, float* depth, uint8_t* seg,
-               void* stream)
-{
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (!p) return fail(h, PNR_ERR_INVALID, "pnr_render: null params");
-    if (!rgb && !depth && !seg) return fail(h, PNR_ERR_INVALID, "pnr_render: every output is NULL");
-    if (const int rc = check_aligned(h, "pnr_render", {{rgb, "rgb", 16}, {depth, "depth", 16}, {seg, "seg", 16}, {joint_state, "joint_state", 16}})) return rc;
-    if (!has_own_target(h)) return before_first_reset(h, "pnr_render", ": the target comes from the state");
-    RenderParams P;
-    const int rc = render_setup(h, p, P);
-    if (rc) return rc;
-    DeviceGuard g(h->device);
-    const dim3 grid((unsigned)(h->n * P.tiles)), block(kRenderThreads);
-    hipStream_t st = (hipStream_t)stream;
-    const JointSource J = joint_source(h, joint_state);       // (the kernel reads the target from h->state whatever the source)
-    with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(J.kind, [&](auto S) {
-        hipLaunchKernelGGL(render_kernel<S()>, grid, block, 0, st, J.src, h->state, (long long)h->n, P, rgb, depth, seg);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
-}
-
-}  // extern "C"
-
-// one static body as pnr_ray_test's kernel reads it (pnr_rays.h RayPrim), in world space once for all envs
-static RayPrim ray_body_record(const pnr_scene_body& S, int b)
-{
-    RayPrim Q;
-    memset(&Q, 0, sizeof(Q));
-    double rt[9], bound;
-    Q.shape = scene_body_prim(S, rt, Q.h, bound);
-    Q.bound2 = Q.shape == kVisPlane ? INFINITY : ray_bound2((float)bound);
-    for (int k = 0; k < 9; ++k) Q.rt[k] = (float)rt[k];
-    for (int k = 0; k < 3; ++k) Q.c[k] = (float)S.position[k];
-    Q.label = kSegBody0 + b;
-    return Q;
-}
-
-extern "C" {
-
-int pnr_ray_params_default(pnr_ray_params* p)
-{
-    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_ray_params_default: null params");
-    memset(p, 0, sizeof(*p));
-    p->struct_size = (uint32_t)sizeof(pnr_ray_params);
-    p->n_rays = 1; p->parent_link = -1; p->hit_mask = PNR_RAY_HIT_BODIES;
-    return PNR_OK;
-}
-
-int pnr_ray_test(pnr_handle h, const float* joint_state, const pnr_ray_params* p, const float* rays, const float* body_positions,
-                 float* hits, float* fractions, void* stream)
-{
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (!p) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: null params");
-    if (p->struct_size != sizeof(pnr_ray_params))
-        return fail(h, PNR_ERR_INVALID, "pnr_ray_test: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_ray_params));
-    if (p->n_rays < 1 || p->n_rays > PNR_MAX_RAYS) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: n_rays %d outside 1..%d", p->n_rays, PNR_MAX_RAYS);
-    if (p->rays_per_env != 0 && p->rays_per_env != 1) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: rays_per_env must be 0 or 1");
-    if (p->parent_link < -1 || p->parent_link >= kNumLinks)
-        return fail(h, PNR_ERR_INVALID, "pnr_ray_test: parent_link %d outside -1..%d", p->parent_link, kNumLinks - 1);
-    constexpr int all = PNR_RAY_HIT_BODIES | PNR_RAY_HIT_ARM | PNR_RAY_HIT_TARGET;
-    if (p->hit_mask == 0 || (p->hit_mask & ~all)) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: hit_mask %d is empty or has unknown bits", p->hit_mask);
-    if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
-        return fail(h, PNR_ERR_INVALID, "pnr_ray_test: n_bodies %d outside 0..%d", p->n_bodies, PNR_MAX_SCENE);
-    if (!rays) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: null rays");
-    if (!hits && !fractions) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: every output is NULL");
-    if (const int rc = check_aligned(h, "pnr_ray_test", {{rays, "rays", 4}, {hits, "hits", 16}, {fractions, "fractions", 16},
-                                                          {joint_state, "joint_state", 16}, {body_positions, "body_positions", 4}})) return rc;
-    for (int b = 0; b < p->n_bodies; ++b)
-        if (const int rc = check_scene_body(h, "pnr_ray_test: body", b, p->bodies[b], true)) return rc;
-    if (!joint_state && !has_own_joints(h)) return before_first_reset(h, "pnr_ray_test");
-    if ((p->hit_mask & PNR_RAY_HIT_TARGET) && !has_own_target(h)) return before_first_reset(h, "pnr_ray_test", ": the target comes from the state");
-    const JointSource J = joint_source(h, joint_state);
-    RayArgs A;
-    memset(&A, 0, sizeof(A));
-    A.src = J.src; A.state = h->state;                 // (the target is read from h->state whatever the joint source)
-    A.rays = rays; A.body_pos = p->n_bodies > 0 ? body_positions : nullptr;
-    A.hits = hits; A.fractions = fractions;
-    A.n = h->n; A.total = h->n * (long long)p->n_rays;
-    A.n_rays = p->n_rays; A.per_env = p->rays_per_env;
-    A.parent_body = p->parent_link >= 1 ? kLinkBody[p->parent_link] : -1;       // link 0 is the base: the world frame
-    A.parent_tip = p->parent_link == kNumLinks - 1;
-    A.mask = p->hit_mask; A.n_bodies = p->n_bodies;
-    // pairs per workgroup: 256, or fewer where 256 pairs would span more than kRayMaxEnvs envs; whole waves where it can
-    long long span = (long long)(kRayMaxEnvs - 1) * p->n_rays;
-    span = span >= kRayThreads ? kRayThreads : (span >= kWave ? span / kWave * kWave : span);
-    A.span = (int)span;
-    const long long touched = (span + p->n_rays - 2) / p->n_rays + 1;
-    A.max_envs = (int)(touched < h->n ? touched : h->n);
-    A.target_radius = (float)h->cfg.target_radius;
-    for (int b = 0; b < p->n_bodies; ++b) A.bodies[b] = ray_body_record(p->bodies[b], b);
-    const long long groups = (A.total + span - 1) / span;
-    if (groups > 0x7fffffffLL) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: %lld envs x %d rays exceed one launch", h->n, p->n_rays);
-    DeviceGuard g(h->device);
-    const dim3 grid((unsigned)groups), block((unsigned)((span + kWave - 1) / kWave * kWave));
-    const size_t lds = sizeof(float) * (size_t)ray_lds_words(A.max_envs);
-    with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(J.kind, [&](auto S) {
-        hipLaunchKernelGGL(ray_kernel<S()>, grid, block, lds, (hipStream_t)stream, A);
-    });
-    HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }
 

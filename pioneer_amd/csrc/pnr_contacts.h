@@ -1,7 +1,7 @@
 // pnr_contacts.h — pnr_get_contacts: for every env, the signed distance of each of the arm's 23 contact sample spheres
 // (pnr_model.h kCapsules, in table order; sample 22 is the pointer) to the nearest of up to eight static bodies, the contact
 // normal, point and penalty force there, a per-env summary and the joint torques of all contact forces: the batched form of
-// getContactPoints / getClosestPoints.  Included by pnr_api.hip only; it adds a kernel and edits none of the step kernels.
+// getContactPoints / getClosestPoints.  Included by pnr_queries.hip only, whose code object holds no step kernel.
 //
 // Per env: q[6], qd[6] in (48-96 B), 23 records of 9 floats out (828 B) + one float4 + six floats.  The signed-distance forms
 // (plane, sphere, oriented box with the nearest-face rule inside) and the penalty law max(0, kp depth - kd v.n) are those of

@@ -1,0 +1,105 @@
+// pnr_env_host.h — host-side pieces that both of the env engine's translation units need (pnr_api.hip: the core, every step and
+// world-step kernel; pnr_queries.hip: the query entry points): the handle, the error call, small argument helpers, the flag ->
+// template-argument dispatch and the static scene bodies.  Nothing here is exported, and pnr_learn.hip does not include it (a
+// handle is opaque to the learner).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <type_traits>
+
+#include "../../include/pioneer_amd.h"
+#include "pnr_host.h"
+#include "pnr_device.h"
+#include "pnr_dyn.h"
+
+struct pnr_env_s {
+    pnr_config cfg;
+    pnr_constants k;
+    pnr::KParams base;        // constants pre-filled; pointers set per call
+    pnr::DynParams dbase;     // dynamics-mode constants (zeroed in kinematic mode)
+    pnr::JointMotorTable motors;   // pnr_world_step's per-joint motors (pnr_set_joint_motor); fill_base: every joint on the handle's own law
+    long long n;
+    unsigned long long env_off;
+    int device;
+    float4* state;
+    float* dyn;          // dynamics-mode planar words [36][n] or null
+    pnr::SceneBody* scene;    // dynamics-mode static scene bodies [kMaxScene] or null
+    int diag;            // -DPNR_DIAG_BUILD=1 variant only: the PNR_DIAG environment variable at create time; else 0
+    bool ready;          // a full reset has happened, or the state was set explicitly
+    bool kin_set, dyn_set;  // pnr_set_state / pnr_set_dyn_state seen (both needed in dynamics mode)
+    char err[512];
+};
+
+// records the message in the handle (h == nullptr: in the thread's buffer) and returns `code`; defined in pnr_api.hip on pnr_failv
+__attribute__((visibility("hidden"))) int fail(pnr_handle h, int code, const char* fmt, ...);
+
+static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+
+template <class T>
+static bool finite_all(const T* v, int k)
+{
+    for (int i = 0; i < k; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+static double sum_sq(const double* v, int k)      // v[0]^2 + v[1]^2 + .. in that order
+{
+    double s = 0;
+    for (int i = 0; i < k; ++i) s += v[i] * v[i];
+    return s;
+}
+
+// Runtime flags -> template arguments: f is called with a std::integral_constant whose value is `b` (or `v`, which must be one of
+// Vs: only the listed values are instantiated).  Every kernel launch of the env units is written once inside such a call.
+template <class F>
+static inline void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int... Vs, class F>
+static inline void with_int(int v, F&& f) { (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
+
+// One static body of the scene, checked: `who` names the call in the message, `finite` adds pnr_render's rule
+static int check_scene_body(pnr_handle h, const char* who, int b, const pnr_scene_body& S, bool finite)
+{
+    const auto bad = [&](const char* what) { return fail(h, PNR_ERR_INVALID, "%s %d: %s", who, b, what); };
+    if (S.shape != PNR_SHAPE_PLANE && S.shape != PNR_SHAPE_BOX && S.shape != PNR_SHAPE_SPHERE)
+        return fail(h, PNR_ERR_INVALID, "%s %d: bad shape %d", who, b, S.shape);
+    if (finite && !(finite_all(S.position, 3) && finite_all(S.orientation, 4) && finite_all(S.size, 3))) return bad("non-finite data");
+    if (!(sum_sq(S.orientation, 4) > 0)) return bad("zero orientation quaternion");
+    if (S.shape == PNR_SHAPE_PLANE && !(sum_sq(S.size, 3) > 0)) return bad("zero plane normal");
+    if (S.shape == PNR_SHAPE_BOX && !(S.size[0] > 0 && S.size[1] > 0 && S.size[2] > 0)) return bad("box half extents must be > 0");
+    if (S.shape == PNR_SHAPE_SPHERE && !(S.size[0] > 0)) return bad("sphere radius must be > 0");
+    return PNR_OK;
+}
+
+// .. and its frame: the normalised quaternion as a row-major rotation R; for a plane also the unit world normal R n / |n|
+static void scene_body_frame(const pnr_scene_body& S, double (&R)[9], double (&normal)[3])
+{
+    const double qn = std::sqrt(sum_sq(S.orientation, 4));
+    const double x = S.orientation[0] / qn, y = S.orientation[1] / qn, z = S.orientation[2] / qn, w = S.orientation[3] / qn;
+    const double r[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                         2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                         2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+    for (int k = 0; k < 9; ++k) R[k] = r[k];
+    if (S.shape != PNR_SHAPE_PLANE) return;
+    const double nl = std::sqrt(sum_sq(S.size, 3));
+    for (int k = 0; k < 3; ++k) normal[k] = (R[3 * k] * S.size[0] + R[3 * k + 1] * S.size[1] + R[3 * k + 2] * S.size[2]) / nl;
+}
+
+// .. and as the kernels want it (pnr_dyn.h SceneBody): float32, pre-rotated; a plane keeps its unit world normal in rot[0..2]
+static pnr::SceneBody scene_body_device(const pnr_scene_body& B)
+{
+    pnr::SceneBody S = pnr::SceneBody{};
+    double R[9], normal[3];
+    scene_body_frame(B, R, normal);
+    S.shape = B.shape;
+    for (int k = 0; k < 3; ++k) { S.pos[k] = (float)B.position[k]; S.size[k] = (float)B.size[k]; }
+    if (B.shape == PNR_SHAPE_PLANE) {
+        for (int k = 0; k < 3; ++k) S.rot[k] = (float)normal[k];
+    } else {
+        for (int k = 0; k < 9; ++k) S.rot[k] = (float)R[k];
+    }
+    return S;
+}

@@ -1,5 +1,5 @@
-// pnr_host.h — host-side plumbing shared by the library's two translation units (pnr_api.hip: the env engine and its
-// C ABI; pnr_learn.hip: the PPO driver's kernels and their C ABI).  Nothing here is exported.
+// pnr_host.h — host-side plumbing shared by all of the library's translation units (the env engine's two, pnr_api.hip and
+// pnr_queries.hip, see pnr_env_host.h; pnr_learn.hip: the PPO driver's kernels and their C ABI).  Nothing here is exported.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +14,8 @@
 #ifndef PNR_UNIT_FINGERPRINT
 #define PNR_UNIT_FINGERPRINT "unstamped"
 #endif
+// pnr_build_fingerprint() (pnr_api.hip) joins the units' strings in _lib.UNITS order; the core's own has no accessor.
+extern "C" __attribute__((visibility("hidden"))) const char* pnr_unit_fingerprint_queries(void);
 extern "C" __attribute__((visibility("hidden"))) const char* pnr_unit_fingerprint_learn(void);
 
 // writes the message into the handle's buffer (or the thread's, for handle-less calls) and returns `code`

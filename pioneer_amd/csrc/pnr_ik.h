@@ -1,7 +1,7 @@
 // pnr_ik.h — pnr_get_jacobian, pnr_solve_ik and pnr_solve_ik_pose: the Jacobian of a point of a URDF link (PyBullet's
 // calculateJacobian), position-only damped-least-squares inverse kinematics (calculateInverseKinematics without an orientation)
 // and pose inverse kinematics (with targetOrientation: a full orientation or one axis to point) for every env, one launch each.
-// Included by pnr_api.hip only; it adds three kernels and edits none of the others.
+// Included by pnr_queries.hip only, whose code object holds no step kernel.
 //
 // Shape of all: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  The host resolves (link,
 // local_point) into the moving body that carries the link and the point's offset in that body's frame; both arrive as

@@ -1,6 +1,6 @@
 // pnr_invdyn.h — pnr_inverse_dynamics and pnr_mass_matrix: PyBullet's calculateInverseDynamics and calculateMassMatrix for
 // every env, one launch each, on the rigid-body model the ABA of pnr_dyn.h steps (six merged bodies, per-env link scales).
-// Included by pnr_api.hip only; it adds two kernels and edits none of the others.
+// Included by pnr_queries.hip only, whose code object holds no step kernel.
 //
 // Shape of both: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  The joints come through load_joints<SRC>;
 // a dynamics-mode handle's link scales, friction and damping are read planar (plane w of env e at dyn[w * n + e]: consecutive

@@ -1,6 +1,6 @@
 // pnr_links.h — pnr_get_link_states: world pose and velocity of every URDF link of every env, the batched form of
 // Item.pose() / Item.velocity() on a link item (bullet_scene.py:53-67 -> getLinkState(computeLinkVelocity=1,
-// computeForwardKinematics=1)).  Included by pnr_api.hip only; it adds a kernel and edits none of the step kernels.
+// computeForwardKinematics=1)).  Included by pnr_queries.hip only, whose code object holds no step kernel.
 //
 // Per env: q[6], qd[6] in, 11 link records of 13 floats out ([0:3] position, [3:7] quaternion x y z w with w >= 0,
 // [7:10] linear velocity of the frame origin, [10:13] angular velocity; world frame).  Link k is Bullet's link_index

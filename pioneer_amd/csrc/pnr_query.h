@@ -1,6 +1,6 @@
 // pnr_query.h — what the per-env query kernels share (pnr_links.h, pnr_ik.h, pnr_invdyn.h, pnr_contacts.h, pnr_render.h):
 // where an env's joints come from, the "one env per lane" prologue, the two LDS-tile flushes and the velocity half of the outward
-// sweep.  It defines no kernel and touches none of the step kernels' headers.
+// sweep.  It defines no kernel and touches none of the step kernels' headers.  Included, with them, by pnr_queries.hip only.
 //
 // The tile kernels' shape: one env per lane, one 64-lane wave per workgroup.  A lane computes its env's record in registers and
 // drops it into its row of an LDS tile whose row stride is ODD (the lanes' ds_write_b32 then hit distinct banks); after

@@ -2,7 +2,7 @@
 // segments from + t (to - from), t in [0, 1], given in the world frame or in the frame of one URDF link of EACH env (a sensor
 // mounted on the arm).  Solids, by mask: the caller's static bodies (planes are half-spaces below their surface), the URDF's 14
 // visual shapes posed by the env's joints (pnr_render.h kVisuals: a ray and a pixel see the same arm), the target sphere.
-// Included by pnr_api.hip only; it adds a kernel and edits none of the others.
+// Included by pnr_queries.hip only, whose code object holds no step kernel.
 //
 // Hit rule: a ray hits a convex solid at its entering parameter tn when tn <= tf (the line meets it) and 0 <= tn <= 1.  A ray
 // that starts inside has tn < 0 and does not hit that solid (Bullet's rule for convex shapes); a plane is hit only from above

@@ -1,6 +1,6 @@
 // pnr_render.h — pnr_render: camera images of every env (rgb, eye depth, segmentation) from the URDF's <visual> shapes, the
 // target sphere and the caller's static bodies: the batched form of the reference's render('rgb_array')
-// (bullet_env.py:156-185 -> getCameraImage).  Included by pnr_api.hip only; it adds a kernel and edits none of the others.
+// (bullet_env.py:156-185 -> getCameraImage).  Included by pnr_queries.hip only, whose code object holds no step kernel.
 //
 // Scene of one env: the 14 visuals of the URDF posed by the env's joints (table below, in moving-body frames), the target
 // sphere (translucent) and up to kMaxScene static bodies shared by all envs.  Every shape is analytic: a ray meets a box by

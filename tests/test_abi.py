@@ -197,6 +197,85 @@ def test_units_list_exactly_the_files_they_include():
     assert {f for f in _lib.UNITS["pnr_learn.hip"] if f.startswith("pnr_mlp")} <= set(_lib.LEARNER_KERNEL_SOURCES)
 
 
+def test_units_tags_and_stamps_agree():
+    """One .hip file per unit and one tag per unit; a unit stamps itself with its own tag, once, and with nobody else's (the
+    loader's `[a-z]+` must match a tag, and two units with one tag would hide each other's fingerprint)."""
+    from pioneer_amd import _lib
+    assert sorted(f for f in os.listdir(_lib.CSRC) if f.endswith(".hip")) == sorted(_lib.UNITS)
+    assert list(_lib.UNIT_TAGS) == list(_lib.UNITS)
+    tags = list(_lib.UNIT_TAGS.values())
+    assert len(set(tags)) == len(tags) and all(re.fullmatch(r"[a-z]+", t) for t in tags), tags
+    for unit, tag in _lib.UNIT_TAGS.items():
+        src = open(os.path.join(_lib.CSRC, unit)).read()
+        assert re.findall(r"pnr_build_fp:([a-z]+)=", src) == [tag], unit
+    assert set(_lib.DIAG_UNITS) <= set(_lib.UNITS)
+    for unit in _lib.UNITS:                      # .. and only the core reads the environment (in its -DPNR_DIAG_BUILD=1 variant)
+        assert ("getenv" in open(os.path.join(_lib.CSRC, unit)).read()) == (unit == "pnr_api.hip"), unit
+
+
+def defined_dynamic_symbols(path):
+    """The names a shared library (ELF64, little endian) defines in its dynamic symbol table: what `nm -D --defined-only` lists."""
+    import struct
+    blob = open(path, "rb").read()
+    assert blob[:6] == b"\x7fELF\x02\x01"
+    shoff, = struct.unpack_from("<Q", blob, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
+    names = []
+    for _, kind, _, _, off, size, link, _, _, entsize in sections:
+        if kind != 11:                                       # SHT_DYNSYM
+            continue
+        strings = sections[link][4]
+        for k in range(size // entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", blob, off + k * entsize)
+            if st_shndx != 0:                                # defined here
+                names.append(blob[strings + st_name:blob.index(b"\0", strings + st_name)].decode())
+    return names
+
+
+def test_internal_functions_are_not_exported(hip_lib):
+    """Whatever the two internal headers declare with hidden visibility is for the library's own units: no such name may be
+    resolvable in the shared library (the names are read from the headers), under its C name or a C++ one, and the pnr_* names
+    the library does define for others are exactly the C ABI's."""
+    from pioneer_amd import _lib
+    exported = defined_dynamic_symbols(_lib.LIB_PATH)
+    assert sorted(s for s in exported if s.startswith("pnr_")) == sorted(_lib.SIGNATURES)
+    names = []
+    for header in ("pnr_host.h", "pnr_env_host.h"):
+        src = open(os.path.join(_lib.CSRC, header)).read()
+        names += re.findall(r'visibility\("hidden"\)\)\)[^;(]*?(\w+)\s*\(', src)
+    assert {"pnr_failv", "fail", "pnr_env_rollout_params", "pnr_unit_fingerprint_learn", "pnr_unit_fingerprint_queries"} <= set(names), names
+    assert len(names) == len(set(names)) and not set(names) & set(_lib.SIGNATURES)
+    for name in names:
+        with pytest.raises(AttributeError):
+            getattr(hip_lib, name)
+        mangled = f"{len(name)}{name}"                       # the identifier inside an Itanium-mangled name
+        assert not [s for s in exported if s.startswith("_Z") and mangled in s], name
+
+
+@pytest.mark.parametrize("touched, stale", [
+    ("pnr_rays.h", {"pnr_queries.hip"}),
+    ("pnr_env_kernels.h", {"pnr_api.hip"}),
+    ("pnr_dyn.h", {"pnr_api.hip", "pnr_queries.hip"}),
+    ("pnr_mlp.h", {"pnr_learn.hip"}),
+])
+def test_a_changed_header_makes_only_the_units_that_include_it_stale(hip_lib, tmp_path, monkeypatch, touched, stale):
+    """The point of the units: a change recompiles what includes the changed file and nothing else.  On a copy of the sources
+    (nothing is compiled; the built library stands in for the objects: it carries every unit's stamp)."""
+    import shutil
+    from pioneer_amd import _lib
+    assert not any(_lib._unit_stale(u, _lib.LIB_PATH) for u in _lib.UNITS)
+    copy = tmp_path / "csrc"
+    copy.mkdir()
+    for f in _lib.SOURCES:
+        shutil.copy(os.path.join(_lib.CSRC, f), copy / f)
+    monkeypatch.setattr(_lib, "CSRC", str(copy))
+    assert not any(_lib._unit_stale(u, _lib.LIB_PATH) for u in _lib.UNITS)
+    with open(copy / touched, "a") as f:
+        f.write("// touched\n")
+    assert {u for u in _lib.UNITS if _lib._unit_stale(u, _lib.LIB_PATH)} == stale
+
+
 def test_spaces_and_helpers():
     from pioneer_amd.spaces import Box
     from pioneer_amd.env import arr2str

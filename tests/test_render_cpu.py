@@ -219,5 +219,5 @@ def test_render_entry_point_rejects_a_null_handle_without_a_device(hip_lib):
     buf = (C.c_uint8 * 64)()
     assert hip_lib.pnr_render(None, None, p, C.cast(buf, C.c_void_p), None, None, None) == -1
     assert b"null handle" in hip_lib.pnr_last_error(None)
-    assert "pnr_render" in _lib.SIGNATURES and "pnr_render.h" in _lib.UNITS["pnr_api.hip"]
+    assert "pnr_render" in _lib.SIGNATURES and "pnr_render.h" in _lib.UNITS["pnr_queries.hip"]
     assert "pnr_render.h" not in _lib.ENV_KERNEL_SOURCES

@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
-"""Compare the device code of two builds of one translation unit, kernel by kernel (what a host-only refactor must leave alone).
+"""Compare the device code of two builds kernel by kernel (what a host-only refactor must leave alone).  Each side is one or
+more listings: the library's kernels are spread over its translation units (_lib.UNITS: pnr_api.hip and pnr_queries.hip for the
+env engine, pnr_learn.hip for the learner), and a kernel may move between them.
 
-    hipcc <_lib.HIPCC_FLAGS> --cuda-device-only -S -o before.s pioneer_amd/csrc/pnr_api.hip      # at the old commit
-    hipcc <_lib.HIPCC_FLAGS> --cuda-device-only -S -o after.s pioneer_amd/csrc/pnr_api.hip       # at the new one
-    python tools/device_code_diff.py before.s after.s
+    for u in pnr_api pnr_queries; do                 # at the old commit: into before/, at the new one: into after/
+        hipcc <_lib.HIPCC_FLAGS> --cuda-device-only -S -o before/$u.s pioneer_amd/csrc/$u.hip
+    done
+    python tools/device_code_diff.py --before before/*.s --after after/*.s
 
 Order is ignored: each listing is split at the kernel symbols into the function body (label .. its .Lfunc_end) and the
 .amdhsa_kernel descriptor block, compared as text.  For a body that differs the per-opcode count delta (after - before) is printed
 with it: "reordered only" when the instruction mix is the same.  Masked: the function's index in the listing, which numbers its local labels
-(.LBB<i>_<k>, .Lfunc_end<i>), and the assembler comments, which quote those labels.  Exit status 0: same kernel names, no body
-or descriptor differs."""
+(.LBB<i>_<k>, .Lfunc_end<i>), and the assembler comments, which quote those labels.  A kernel that two listings of one side hold
+is an error (two units would compile, and the library would hold, the same kernel).  Exit status 0: no such kernel, same kernel
+names, no body or descriptor differs; then the number of kernels each listing holds is printed too."""
+import argparse
 import collections
 import re
 import sys
@@ -27,6 +32,17 @@ def kernels(path):
     return out
 
 
+def side(paths):
+    """({kernel: (body, descriptor)}, {kernel: its listing}, [(kernel, listing, listing) held twice]) of one side's listings"""
+    merged, where, twice = {}, {}, []
+    for path in paths:
+        for name, k in kernels(path).items():
+            if name in merged:
+                twice.append((name, where[name], path))
+            merged[name], where[name] = k, path
+    return merged, where, twice
+
+
 def opcode_delta(x, y):
     """after - before counts of every opcode whose count differs between two function bodies"""
     ops = lambda body: collections.Counter(ln.split()[0] for ln in body.splitlines() if ln.startswith("\t") and not ln.startswith("\t."))
@@ -35,7 +51,10 @@ def opcode_delta(x, y):
 
 
 def main(before, after):
-    a, b = kernels(before), kernels(after)
+    (a, a_where, a_twice), (b, b_where, b_twice) = side(before), side(after)
+    for when, twice in (("before", a_twice), ("after", b_twice)):
+        for name, p, q in twice:
+            print(f"twice {when}: {name}  ({p}, {q})")
     gone, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     bodies = [k for k in a if k in b and a[k][0] != b[k][0]]
     descs = [k for k in a if k in b and a[k][1] != b[k][1]]
@@ -43,10 +62,19 @@ def main(before, after):
         for k in names:
             delta = opcode_delta(a[k][0], b[k][0]) if names is bodies else None
             print(f"{what}: {k}" + ("" if delta is None else f"  {delta or 'reordered only'}"))
+    bad = bool(a_twice or b_twice or gone or new or bodies or descs)
+    if not bad:
+        for when, where in (("before", a_where), ("after", b_where)):
+            for path, count in collections.Counter(where.values()).items():
+                print(f"{when}: {count:4d} kernels from {path}")
     print(f"{len(a)} kernels before, {len(b)} after; names {'equal' if not gone and not new else 'DIFFER'}; "
-          f"{len(bodies)} bodies differ, {len(descs)} descriptors differ")
-    return 1 if gone or new or bodies or descs else 0
+          f"{len(a_twice) + len(b_twice)} kernels twice on a side; {len(bodies)} bodies differ, {len(descs)} descriptors differ")
+    return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:3]))
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--before", nargs="+", required=True, metavar="LISTING")
+    ap.add_argument("--after", nargs="+", required=True, metavar="LISTING")
+    args = ap.parse_args()
+    sys.exit(main(args.before, args.after))

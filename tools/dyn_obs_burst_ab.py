@@ -32,7 +32,7 @@ print(json.dumps({"us": e0.elapsed_time(e1) / K * 1e3}))
 
 lib = os.path.join(_lib.CSRC, "libpioneer_amd_diag.so")
 if not os.path.exists(lib):
-    _lib.build_library(extra_flags=["-DPNR_DIAG_BUILD=1"], out_path=lib, units=("pnr_api.hip",))
+    _lib.build_library(extra_flags=["-DPNR_DIAG_BUILD=1"], out_path=lib, units=_lib.DIAG_UNITS)
 for n in (65536, 8192):
     row = {"envs": n}
     for name, diag in (("full", "0"), ("no_obs_flush", "2"), ("no_obs_emit_no_flush", "6")):
