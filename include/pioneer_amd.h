@@ -45,7 +45,7 @@ extern "C" {
  *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
  *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
  *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
- *      pnr_ray_test, pnr_world_step_wrenches */
+ *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -562,6 +562,46 @@ int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* strea
 typedef struct pnr_link_wrench_spec { int32_t link; int32_t frame; } pnr_link_wrench_spec;
 int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int n_specs, const float* wrenches,
                             const float* joint_torques, int hold_substeps, void* stream);
+
+/*
+ * getJointState for every env of a dynamics-mode handle, one launch: per revolute joint its position, velocity, ACCELERATION and
+ * MOTOR TORQUE, and optionally the joint's REACTION WRENCH.  The call evaluates exactly what the FIRST SUB-STEP of
+ * pnr_world_step, pnr_world_step_torques or pnr_world_step_wrenches would evaluate if called with the same arguments, and takes
+ * nothing: no word of the state is written.  It reads the joints, the handle's command state r, v, the motor table as
+ * pnr_set_joint_motor left it, the per-env link scales, friction and damping, and the handle's contacts.
+ *   joint_state    as pnr_get_link_states ([num_envs][12] q | qd, 16-byte aligned, read only); NULL = the handle's simulated q, qd
+ *   joint_torques  [num_envs][6] float32, 16-byte aligned, read only, or NULL: pnr_world_step_torques' torques
+ *   specs, n_specs, wrenches
+ *                  up to PNR_MAX_LINK_WRENCHES wrench records per env: specs, layout ([num_envs][n_specs][9], 16-byte aligned) and
+ *                  frames are pnr_world_step_wrenches'.  A PNR_FRAME_WORLD record's point is taken on the link at the current
+ *                  pose, which is that call's q0.  n_specs == 0 with NULL specs and NULL wrenches: no records.
+ *   joints_out     [num_envs][6][4] float32, 16-byte aligned: q, qd, qdd, tau_motor per joint; nothing past num_envs * 24 floats
+ *                  is written.
+ *                  qdd is the acceleration the sub-step would integrate: the articulated-body algorithm's output, after the boxed
+ *                  solve where the table holds constraint motors, BEFORE the integrator and its joint-limit clamp.  The clamp is
+ *                  a select of the integrator (q held at the limit, qd zeroed) and not a force: it shows in neither output.
+ *                  tau_motor is what the joint's own motor applies: the PD table law's torque after its cap; under
+ *                  pd_inertia_scaled the scaled and capped torque clip(D_i ades_i, +-cap) the recursion applies; for a constraint
+ *                  motor the boxed solve's torque.  It contains neither the caller's joint_torques nor damping nor friction.
+ *   reaction_out   [num_envs][6][6] float32, 16-byte aligned, or NULL (not computed); nothing past num_envs * 36 floats is
+ *                  written.  Per revolute joint b: (Fx, Fy, Fz, Mx, My, Mz), the wrench the PARENT body exerts ON body b through
+ *                  the joint, taken AT body b's origin (which lies on the joint axis) and expressed IN body b's coordinates:
+ *                  the child link's frame, since the URDF's fixed joints carry no rotation and the inertial origins are identity.
+ *                  Bodies are the six merged moving bodies.  It carries everything distal to the joint: the inertial forces of
+ *                  bodies b..5 at qdd and gravity, minus the contact wrenches and the caller's wrenches on them.  Its moment along
+ *                  the joint axis is the joint's total torque, tau_motor + joint_torque - damping - friction; the other five
+ *                  components are the bearing load.  An arm at rest under gravity shows (0, 0, +weight) at joint 0.  Sign and
+ *                  frame against Bullet's jointReactionForces are unpinned, as everything in dynamics mode.
+ * The refusals are the world-step calls', so that "same arguments, same answer" holds.  PNR_ERR_UNSUPPORTED: a kinematic-mode
+ * handle (nothing is simulated there); joint_torques or wrench records with a motor table that holds a constraint motor.
+ * PNR_ERR_INVALID: a null handle or joints_out; a misaligned pointer; n_specs outside 0..PNR_MAX_LINK_WRENCHES, n_specs > 0 with
+ * NULL specs or wrenches, n_specs == 0 with either of them; a link outside 0..10; an unknown frame; before the first pnr_reset.
+ * Every refusal is decided before any launch and touches no output.  Device data is not inspected.  float32 arithmetic,
+ * asynchronous on `stream`, never synchronises, no allocation: capturable into a graph.  Parity unpinned; checked against the
+ * float64 oracle's forward dynamics and a world-frame Newton-Euler sweep over the URDF's links.
+ */
+int pnr_get_joint_states(pnr_handle h, const float* joint_state, const float* joint_torques, const pnr_link_wrench_spec* specs,
+                         int32_t n_specs, const float* wrenches, float* joints_out, float* reaction_out, void* stream);
 
 /*
  * getContactPoints / getClosestPoints for every env, one launch: each of the arm's 23 contact sample spheres against up to

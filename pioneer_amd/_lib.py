@@ -44,6 +44,8 @@ JACOBIAN_DIM = 36       # pnr_get_jacobian: 6 rows (linear xyz, angular xyz) x 6
 INVDYN_NO_GRAVITY, INVDYN_JOINT_LOSSES = 1, 2      # pnr_inverse_dynamics flags (PNR_INVDYN_*)
 MAX_LINK_WRENCHES = 4   # pnr_world_step_wrenches: wrench records per env, at most (PNR_MAX_LINK_WRENCHES)
 WRENCH_DIM = 9          # .. force[3], position[3], torque[3] per record
+JOINT_STATE_DIM = 4     # pnr_get_joint_states: q, qd, qdd, tau_motor per joint
+REACTION_DIM = 6        # .. Fx, Fy, Fz, Mx, My, Mz per joint
 FRAME_LINK, FRAME_WORLD = 1, 2                     # .. a record's frame (PNR_FRAME_*; pybullet's LINK_FRAME / WORLD_FRAME)
 
 PNR_OK = 0
@@ -206,6 +208,7 @@ SIGNATURES = {
     "pnr_get_jacobian": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_double * 3), _VP, _VP]),
     "pnr_inverse_dynamics": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
     "pnr_mass_matrix": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "pnr_get_joint_states": (C.c_int, [_VP, _VP, _VP, C.POINTER(PnrLinkWrenchSpec), C.c_int32, _VP, _VP, _VP, _VP]),
     "pnr_ik_params_default": (C.c_int, [C.POINTER(PnrIkParams)]),
     "pnr_solve_ik": (C.c_int, [_VP, C.POINTER(PnrIkParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pnr_ik_pose_params_default": (C.c_int, [C.POINTER(PnrIkPoseParams)]),
@@ -248,9 +251,9 @@ _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr
 UNITS = {
     # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (108, 80 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
-    # the query entry points of the C ABI and their kernels (23)
+    # the query entry points of the C ABI and their kernels (35)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",
-                        "pnr_contacts.h", "pnr_rays.h"],
+                        "pnr_jointstate.h", "pnr_contacts.h", "pnr_rays.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",
                       "pnr_mlp_gather.h", "pnr_mlp_backward.h", "pnr_mlp_wgrad.h", "pnr_mlp_adam.h", "pnr_sampler.h"],
 }
@@ -328,7 +331,7 @@ def build_library(force: bool = False, verbose: bool = False, extra_flags=(), ou
     parallel (only those whose object does not carry the fingerprint of the current sources) and linked.  extra_flags / out_path
     build a variant next to it (e.g. -DPNR_DIAG_BUILD=1 for the timing-only ablations), with objects of its own; `units` names the translation units the flags concern (e.g. ("pnr_learn.hip",) for an
     MLP kernel A/B) — the others are linked from the default build's objects.  Measured on 8 cores: a full forced build 92 s, which is
-    pnr_api.hip's (pnr_queries.hip ~15 s, pnr_learn.hip ~20 s, in parallel; with the queries in that unit it was 129 s); after a
+    pnr_api.hip's (pnr_queries.hip ~15 s, ~25 s since pnr_jointstate.h; pnr_learn.hip ~20 s, in parallel; with the queries in that unit it was 129 s); after a
     change to pnr_rays.h 15 s (was 133 s), after one to pnr_env_kernels.h 116 s (was 133 s)."""
     variant = out_path is not None or bool(extra_flags)
     if variant:

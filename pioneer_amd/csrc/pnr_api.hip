@@ -99,10 +99,6 @@ static JointMotor pd_motor(bool velocity, double kp, double kd, double force_lim
     return m;
 }
 
-// the dynamics kernels' PHYS template argument: bit 0 contacts (contact-free handles run instantiations without any contact
-// code), bit 1 the inertia-scaled motor
-static inline int dyn_phys(const DynParams& D) { return ((D.has_ground || D.has_box || D.n_scene > 0) ? 1 : 0) | (D.inertia_scaled ? 2 : 0); }
-
 // the argument checks of pnr_get_state / pnr_set_state and their dyn twins
 static int check_state_call(pnr_handle h, const void* words, const char* call, bool dyn)
 {
@@ -586,21 +582,8 @@ int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int
     if (!aligned16(wrenches)) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: wrenches must be 16-byte aligned");
     if (joint_torques && !aligned16(joint_torques))
         return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: joint_torques must be 16-byte aligned");
-    if (n_specs < 1 || n_specs > PNR_MAX_LINK_WRENCHES)
-        return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: n_specs %d out of [1, %d]", n_specs, PNR_MAX_LINK_WRENCHES);
-    LinkWrenchTable T = {};
-    T.n = n_specs;
-    T.last_world_body = -1;
-    for (int j = 0; j < kMaxWrench; ++j) T.lbody[j] = T.wbody[j] = -1;
-    for (int j = 0; j < n_specs; ++j) {
-        const int link = specs[j].link, frame = specs[j].frame;
-        if (link < 0 || link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: record %d: link %d out of [0, %d)", j, link, kNumLinks);
-        if (frame != PNR_FRAME_LINK && frame != PNR_FRAME_WORLD)
-            return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: record %d: unknown frame %d (1: link, 2: world)", j, frame);
-        (frame == PNR_FRAME_WORLD ? T.wbody : T.lbody)[j] = kLinkBody[link];   // -1: robot:base, welded to the world: the record does nothing
-        if (link == kNumLinks - 1) { T.d[j][0] = (float)kTipX; T.d[j][1] = (float)kTipY; T.d[j][2] = (float)kTipZ; }   // every other link origin is its body's
-        if (T.wbody[j] > T.last_world_body) T.last_world_body = T.wbody[j];
-    }
+    LinkWrenchTable T;
+    if (const int rc = fill_wrench_table(h, "pnr_world_step_wrenches", specs, n_specs, T)) return rc;      // (pnr_env_host.h)
     if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches before the first pnr_reset (or pnr_set_state)");
     for (int i = 0; i < kDof; ++i)
         if (h->motors.kind[i] != kMotorPD)

@@ -1,6 +1,6 @@
 // pnr_env_host.h — host-side pieces that both of the env engine's translation units need (pnr_api.hip: the core, every step and
 // world-step kernel; pnr_queries.hip: the query entry points): the handle, the error call, small argument helpers, the flag ->
-// template-argument dispatch and the static scene bodies.  Nothing here is exported, and pnr_learn.hip does not include it (a
+// template-argument dispatch, the static scene bodies and the world step's table builders (which pnr_get_joint_states shares).  Nothing here is exported, and pnr_learn.hip does not include it (a
 // handle is opaque to the learner).
 #pragma once
 
@@ -102,4 +102,36 @@ static pnr::SceneBody scene_body_device(const pnr_scene_body& B)
         for (int k = 0; k < 9; ++k) S.rot[k] = (float)R[k];
     }
     return S;
+}
+
+// the dynamics kernels' PHYS template argument: bit 0 contacts (contact-free handles run instantiations without any contact
+// code), bit 1 the inertia-scaled motor
+static inline int dyn_phys(const pnr::DynParams& D) { return ((D.has_ground || D.has_box || D.n_scene > 0) ? 1 : 0) | (D.inertia_scaled ? 2 : 0); }
+
+// pnr_world_step_wrenches' and pnr_get_joint_states' records: a table without records ..
+static inline void empty_wrench_table(pnr::LinkWrenchTable& T)
+{
+    T = pnr::LinkWrenchTable{};
+    T.last_world_body = -1;
+    for (int j = 0; j < pnr::kMaxWrench; ++j) T.lbody[j] = T.wbody[j] = -1;
+}
+
+// .. and the caller's specs, checked (`call` names the entry point in the message); T.hold is the caller's to set
+static int fill_wrench_table(pnr_handle h, const char* call, const pnr_link_wrench_spec* specs, int n_specs, pnr::LinkWrenchTable& T)
+{
+    using namespace pnr;
+    if (n_specs < 1 || n_specs > PNR_MAX_LINK_WRENCHES)
+        return fail(h, PNR_ERR_INVALID, "%s: n_specs %d out of [1, %d]", call, n_specs, PNR_MAX_LINK_WRENCHES);
+    empty_wrench_table(T);
+    T.n = n_specs;
+    for (int j = 0; j < n_specs; ++j) {
+        const int link = specs[j].link, frame = specs[j].frame;
+        if (link < 0 || link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "%s: record %d: link %d out of [0, %d)", call, j, link, kNumLinks);
+        if (frame != PNR_FRAME_LINK && frame != PNR_FRAME_WORLD)
+            return fail(h, PNR_ERR_INVALID, "%s: record %d: unknown frame %d (1: link, 2: world)", call, j, frame);
+        (frame == PNR_FRAME_WORLD ? T.wbody : T.lbody)[j] = kLinkBody[link];   // -1: robot:base, welded to the world: the record does nothing
+        if (link == kNumLinks - 1) { T.d[j][0] = (float)kTipX; T.d[j][1] = (float)kTipY; T.d[j][2] = (float)kTipZ; }   // every other link origin is its body's
+        if (T.wbody[j] > T.last_world_body) T.last_world_body = T.wbody[j];
+    }
+    return PNR_OK;
 }

@@ -1,5 +1,5 @@
 // pnr_queries.hip — the query entry points of the C ABI (include/pioneer_amd.h) and their kernels: link states, Jacobian,
-// inverse dynamics and mass matrix, the two IK solvers, contacts, render, ray casts.  A query reads the handle (or the
+// inverse dynamics and mass matrix, joint states, the two IK solvers, contacts, render, ray casts.  A query reads the handle (or the
 // caller's joints) and writes the caller's buffers; it never changes an env.  The kernels are the query headers' (pnr_query.h:
 // their shared scaffold); the handle and the host helpers shared with the core unit pnr_api.hip are pnr_env_host.h's.  A unit
 // of its own so that a query's code object holds no step kernel and a change to one recompiles neither.
@@ -16,6 +16,7 @@
 #include "pnr_render.h"
 #include "pnr_ik.h"
 #include "pnr_invdyn.h"
+#include "pnr_jointstate.h"
 #include "pnr_contacts.h"
 #include "pnr_rays.h"
 
@@ -155,6 +156,49 @@ int pnr_mass_matrix(pnr_handle h, const float* joint_state, float* out, void* st
     const JointSource J = joint_source(h, joint_state);
     return launch_env_waves(h, stream, J.kind, [](auto S) { return mass_matrix_kernel<S()>; }, J.src, J.state, (const float*)h->dyn, out,
                             (long long)h->n);
+}
+
+int pnr_get_joint_states(pnr_handle h, const float* joint_state, const float* joint_torques, const pnr_link_wrench_spec* specs,
+                         int32_t n_specs, const float* wrenches, float* joints_out, float* reaction_out, void* stream)
+{
+    const char* call = "pnr_get_joint_states";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (h->cfg.mode != PNR_MODE_DYNAMIC)
+        return fail(h, PNR_ERR_UNSUPPORTED, "%s: motor torques, accelerations and reactions exist in dynamics mode only", call);
+    if (!joints_out) return fail(h, PNR_ERR_INVALID, "%s: null joints_out", call);
+    if (const int rc = check_aligned(h, call, {{joints_out, "joints_out", 16}, {reaction_out, "reaction_out", 16}, {joint_state, "joint_state", 16},
+                                               {joint_torques, "joint_torques", 16}, {wrenches, "wrenches", 16}})) return rc;
+    LinkWrenchTable T;
+    if (n_specs == 0) {
+        if (specs || wrenches) return fail(h, PNR_ERR_INVALID, "%s: n_specs 0 goes with NULL specs and NULL wrenches", call);
+        empty_wrench_table(T);
+    } else {
+        if (!specs) return fail(h, PNR_ERR_INVALID, "%s: null specs", call);
+        if (!wrenches) return fail(h, PNR_ERR_INVALID, "%s: null wrenches", call);
+        if (const int rc = fill_wrench_table(h, call, specs, n_specs, T)) return rc;
+    }
+    if (!h->ready) return before_first_reset(h, call);
+    bool cm = false;                                   // a constraint motor anywhere: the instantiation with motor_constraints
+    for (int i = 0; i < kDof; ++i) cm = cm || h->motors.kind[i] != kMotorPD;
+    const bool ext = joint_torques || n_specs > 0;
+    if (cm && ext)
+        return fail(h, PNR_ERR_UNSUPPORTED, "%s: a joint is on a constraint motor (torque or wrench input with the boxed solve is not built)", call);
+    T.hold = 1;                                        // (one sub-step is looked at: the records act in it)
+    JointStateArgs A;
+    A.joints_in = joint_state; A.state = h->state; A.dyn = h->dyn;
+    A.tau_ext = joint_torques; A.wrenches = wrenches;
+    A.joints = joints_out; A.reaction = reaction_out; A.n = h->n;
+    DeviceGuard g(h->device);
+    const DynParams& D = h->dbase;
+    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
+    // the world step's own distinctions: contacts / inertia-scaled (dyn_phys), constraint motors, external inputs present or not
+    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) {
+        with_int<0, 1, 2>(cm ? 2 : (ext ? 1 : 0), [&](auto K) {
+            hipLaunchKernelGGL((joint_state_kernel<C(), K() == 2, K() == 1>), grid, dim3(kWave), 0, (hipStream_t)stream, A, D, h->motors, T);
+        });
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
 }
 
 int pnr_ik_params_default(pnr_ik_params* p)

@@ -1,4 +1,4 @@
-// pnr_query.h — what the per-env query kernels share (pnr_links.h, pnr_ik.h, pnr_invdyn.h, pnr_contacts.h, pnr_render.h):
+// pnr_query.h — what the per-env query kernels share (pnr_links.h, pnr_ik.h, pnr_invdyn.h, pnr_jointstate.h, pnr_contacts.h, pnr_render.h):
 // where an env's joints come from, the "one env per lane" prologue, the two LDS-tile flushes and the velocity half of the outward
 // sweep.  It defines no kernel and touches none of the step kernels' headers.  Included, with them, by pnr_queries.hip only.
 //

@@ -30,6 +30,13 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   alone, which hands them (at most four) and any ``control_torque`` to the engine in one launch (``pnr_world_step_wrenches``) and
   clears them, as ``reset()`` does.  They act over the whole ``world.step()``; Bullet clears them after one stepSimulation
   (``PioneerVectorEnv.world_step(hold_substeps=1)``).  A fifth record and kinematic mode raise AssertionError.
+* ``joint.state()`` / ``joint.acceleration()`` / ``scene.joint_states()``: pybullet.getJointState as ``JointState`` tuples (PyBullet's
+  four field names), all six joints from ONE engine launch (``pnr_get_joint_states``).  Dynamics mode: what the first sub-step of the
+  next ``world.step()`` would evaluate, looked at and not taken: the motor's torque after its cap, the reaction wrench the parent
+  exerts on the joint's child link (Fx, Fy, Fz, Mx, My, Mz at the child link's origin, in its frame), and q̈.  Torques queued by
+  ``control_torque`` and wrenches queued by ``apply_force`` / ``apply_torque`` are included and NOT consumed: the sensor sees the
+  shove that is about to act.  Kinematic mode: position and velocity as ``position()`` / ``velocity()``; nothing is simulated there,
+  so the reaction is six zeros, the torque 0.0 and the acceleration 0.0.  Sign and frame against Bullet's are unpinned.
 * ``world.step()``: ``frame_skip`` × ``stepSimulation`` = ONE engine launch (``pnr_world_step``), nothing on the host.  Dynamics
   mode: the articulated-body sub-steps (gravity, contacts with the scene's bodies, limits, every joint's motor) and nothing else —
   no command integration, reward or observation.  Kinematic mode: each joint carries on at the velocity it was reset with
@@ -88,6 +95,14 @@ class Velocity(NamedTuple):
     """bullet_scene.py:33-36: world linear and angular velocity."""
     linear: Tuple[float, float, float]
     angular: Tuple[float, float, float]
+
+
+class JointState(NamedTuple):
+    """pybullet.getJointState, in PyBullet's names (the reference's binding decodes these four, bullet_bindings.py:48-51)."""
+    joint_position: float
+    joint_velocity: float
+    joint_reaction_forces: Tuple[float, float, float, float, float, float]
+    applied_joint_motor_torque: float
 
 
 class ContactPoint(NamedTuple):
@@ -227,6 +242,16 @@ class Joint:
             return float(self._env._vec.get_dyn_state()[6 + self.index, 0])
         return float(self._env.scene._bullet[0, 6 + self.index])
 
+    def state(self) -> JointState:
+        """getJointState of this joint (module docstring).  Every call is one engine launch and a copy to the host, and that
+        launch answers all six joints: to read several, call ``Scene.joint_states()`` once."""
+        return self._env.scene.joint_states()[self.index]
+
+    def acceleration(self) -> float:
+        """q̈ the next ``world.step()``'s first sub-step would integrate (before its joint-limit clamp); 0.0 in kinematic mode.
+        One launch and host copy per call, as ``state()``."""
+        return float(self._env.scene._joint_state_tensors()[0][self.index, 2])
+
     def reset_state(self, position: float, velocity: Optional[float] = None):
         """resetJointState (bullet_scene.py:157-165): the SIMULATOR's joint is put at ``position`` (and ``velocity``, else 0); the
         env's own r / v are not touched (the reference's are not either)."""
@@ -297,6 +322,27 @@ class Scene:
         if self._env._vec.engine_config.mode != "dynamic":
             self._bullet[0, 0:6] = self._env._vec.get_state().view(torch.float32)[12:18, 0]
             self._bullet[0, 6:12] = 0.0
+
+    def _joint_state_tensors(self):
+        """(joints [6, 4] = q, q̇, q̈, τ_motor; reaction [6, 6]) of the one env as host arrays, from one launch; kinematic mode: the
+        simulator's q, q̇ and zeros."""
+        vec = self._env._vec
+        if vec.engine_config.mode != "dynamic":
+            joints = np.zeros((6, 4))
+            joints[:, 0:2] = self._bullet[0].cpu().numpy().reshape(2, 6).T
+            return joints, np.zeros((6, 6))
+        world = self._env.world
+        tau = world._torque_tensor(vec.device) if world._torques else None
+        wr = world._wrench_records(vec.device) if world._wrenches else None
+        res = vec.joint_states(joint_torques=tau, link_wrenches=wr)
+        return res["joints"][0].cpu().numpy(), res["reaction"][0].cpu().numpy()
+
+    def joint_states(self) -> List[JointState]:
+        """getJointStates of the six joints, one engine launch (module docstring): what is queued for the next ``world.step()`` is
+        included and stays queued."""
+        joints, reaction = self._joint_state_tensors()
+        return [JointState(float(joints[i, 0]), float(joints[i, 1]), tuple(float(x) for x in reaction[i]), float(joints[i, 3]))
+                for i in range(6)]
 
     # -- items -----------------------------------------------------------------------------------------------------------
     def add_item(self, item: Item):
@@ -437,16 +483,23 @@ class World:
     def step_time(self) -> float:
         return self.timestep * self.frame_skip
 
+    def _torque_tensor(self, device):
+        """the queued ``control_torque`` values as the engine's [1, 6] tensor"""
+        return torch.tensor([[self._torques.get(j, 0.0) for j in range(6)]], dtype=torch.float32, device=device)
+
+    def _wrench_records(self, device):
+        """the queued ``apply_force`` / ``apply_torque`` records as ``world_step``'s ``(specs, [1, K, 9] tensor)``"""
+        return [s for s, _ in self._wrenches], torch.tensor([[w for _, w in self._wrenches]], dtype=torch.float32, device=device)
+
     def step(self):
         """frame_skip x stepSimulation: ONE launch of the engine (pnr_world_step), no host arithmetic."""
         vec = self._env._vec
         tau = None
         if self._torques:                                                      # recorded for this step alone (TORQUE_CONTROL)
-            tau = torch.tensor([[self._torques.get(j, 0.0) for j in range(6)]], dtype=torch.float32, device=vec.device)
+            tau = self._torque_tensor(vec.device)
             self._torques = {}
         if self._wrenches:                                                     # .. and the links' external forces and torques
-            specs = [s for s, _ in self._wrenches]
-            rec = torch.tensor([[w for _, w in self._wrenches]], dtype=torch.float32, device=vec.device)
+            specs, rec = self._wrench_records(vec.device)
             self._wrenches = []
             vec.world_step(joint_torques=tau, link_wrenches=(specs, rec))
             return

@@ -286,6 +286,32 @@ class PioneerVectorEnv:
         self._chk(self.lib.pnr_mass_matrix(self._h, _ptr(js), _ptr(res), self._stream()))
         return res
 
+    def joint_states(self, joint_state=None, joint_torques=None, link_wrenches=None, reaction=True, out=None):
+        """getJointState of every env, one launch (pnr_get_joint_states; dynamics mode): what the first sub-step of
+        ``world_step`` with the same ``joint_torques`` / ``link_wrenches`` would evaluate, looked at and not taken.  Returns a dict of
+        device tensors: ``joints`` float32 ``[N, 6, 4]`` = q, q̇, q̈, τ_motor per joint (q̈ before the integrator and its joint-limit
+        clamp; τ_motor the joint's own motor after its cap, without the caller's torques, damping or friction) and, with
+        ``reaction``, ``reaction`` float32 ``[N, 6, 6]`` = (Fx, Fy, Fz, Mx, My, Mz) per joint: the wrench the parent exerts on the
+        joint's child body, at the child link's origin in the child link's frame; its moment along the joint axis is the joint's
+        total torque.  ``joint_state``: as ``link_states`` (None = the simulated q, q̇).  ``joint_torques`` and ``link_wrenches =
+        (specs, tensor)``: as ``world_step`` (a world-frame record's point is taken at the current pose).  ``out`` may carry
+        preallocated ``joints`` / ``reaction`` tensors, written in place.  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        js = self._joints(joint_state)
+        tq = None if joint_torques is None else self._in(joint_torques, (n, 6), torch.float32, "joint_torques")
+        arr, wr, k = None, None, 0
+        if link_wrenches is not None:
+            specs, tensor = link_wrenches
+            specs = list(specs)
+            arr, k = self._wrench_specs(specs), len(specs)
+            wr = self._in(tensor, (n, k, _lib.WRENCH_DIM), torch.float32, "link_wrenches")
+        res = self._asked(out, (("joints", True, (n, _lib.DOF, _lib.JOINT_STATE_DIM), torch.float32),
+                                ("reaction", reaction, (n, _lib.DOF, _lib.REACTION_DIM), torch.float32)), "")
+        self._chk(self.lib.pnr_get_joint_states(self._h, _ptr(js), _ptr(tq), arr, k, _ptr(wr), _ptr(res["joints"]),
+                                                _ptr(res.get("reaction")), self._stream()))
+        return res
+
     def set_joint_motor(self, joint, control_mode, target_position=float("nan"), target_velocity=float("nan"), position_gain=float("nan"),
                         velocity_gain=float("nan"), max_force=float("nan"), max_velocity=float("nan")):
         """Joint.control_position / control_velocity (bullet_scene.py:123-155; pnr_set_joint_motor) for ``joint`` of every env.
