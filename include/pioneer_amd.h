@@ -45,7 +45,7 @@ extern "C" {
  *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
  *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
  *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
- *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states */
+ *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -562,6 +562,39 @@ int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* strea
 typedef struct pnr_link_wrench_spec { int32_t link; int32_t frame; } pnr_link_wrench_spec;
 int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int n_specs, const float* wrenches,
                             const float* joint_torques, int hold_substeps, void* stream);
+
+/*
+ * pnr_world_step on a dynamics-mode handle with motor targets of each env's own: PyBullet's setJointMotorControlArray followed by
+ * stepSimulation, once per env.  One call is one World.step (frame_skip sub-steps on the handle's simulated q, qd) exactly as
+ * pnr_world_step, but for every joint j with bit j of joint_mask set, env e's motor of joint j takes, for THIS call only,
+ *     targetPosition = targets[e][j],   targetVelocity = targets[e][6 + j]
+ * in place of what the motor table holds for that joint (pnr_set_joint_motor's target_position / target_velocity).
+ *   joint_mask     bits 0..5, at least one set
+ *   targets        [num_envs][12] float32, position[6] | velocity[6] (the q | qd layout of every joint_state argument of this
+ *                  header), caller-owned device memory, 16-byte aligned, read only.  The entries of joints outside joint_mask take
+ *                  no part in the result and may hold anything, NaN included.
+ *   joint_torques  [num_envs][6] float32, 16-byte aligned, read only, or NULL for none: exactly pnr_world_step_torques' torques,
+ *                  in the same launch
+ * Everything else about joint j's motor stays as pnr_set_joint_motor left it and is the same for all envs: the law (PD position,
+ * PD velocity or a constraint motor), the gains, the force cap, maxVelocity.  A masked joint nobody commanded keeps the handle's
+ * own law (pnr_config.control_mode, pd_kp, pd_kd, torque_limit, max_velocity) with the env's targets standing in for its command
+ * state r[j], v[j]; on a teleport handle such a joint has no motor and its targets do nothing, and neither do those of a constraint
+ * motor set with force == 0 (no motor).  Joints outside joint_mask behave exactly as in pnr_world_step.  The position entry of a
+ * joint on a velocity law has no effect on the result; under the PD velocity law it is multiplied by a zero gain, so it must be
+ * FINITE (a NaN or inf there gives that env non-finite joints).  Device data is not inspected and no error is raised for it.
+ * Nothing persists after the call: the command state, the motor table and every dyn word but q, qd are left bit for bit.
+ *
+ * Contract: for every env e the call gives what pnr_world_step (with joint_torques: pnr_world_step_torques) gives env e on a
+ * handle in the same state whose motor table holds env e's entries as the targets of the masked joints — to float32 rounding, the
+ * two being different kernels.  An env's result does not depend on the batch around it, bit for bit.
+ * PNR_ERR_UNSUPPORTED: a kinematic-mode handle; joint_torques non-NULL with a constraint motor anywhere in the table (as
+ * pnr_world_step_torques: torque input together with the boxed solve is not built).  PNR_ERR_INVALID: a null handle, NULL or
+ * misaligned targets, misaligned joint_torques, joint_mask == 0 or with a bit above 5, before the first pnr_reset.  Every refusal
+ * is decided before any launch and leaves the state untouched.  Asynchronous on `stream`, never synchronises, no allocation:
+ * capturable into a graph.  Parity unpinned: checked per env against the float64 oracle's world step and the constraint motor's
+ * float64 reference under that env's table.
+ */
+int pnr_world_step_targets(pnr_handle h, uint32_t joint_mask, const float* targets, const float* joint_torques, void* stream);
 
 /*
  * getJointState for every env of a dynamics-mode handle, one launch: per revolute joint its position, velocity, ACCELERATION and

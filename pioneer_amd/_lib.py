@@ -199,6 +199,7 @@ SIGNATURES = {
     "pnr_world_step": (C.c_int, [_VP, _VP, _VP]),
     "pnr_world_step_torques": (C.c_int, [_VP, _VP, _VP]),
     "pnr_world_step_wrenches": (C.c_int, [_VP, C.POINTER(PnrLinkWrenchSpec), C.c_int, _VP, _VP, C.c_int, _VP]),
+    "pnr_world_step_targets": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP]),
     "pnr_set_joint_motor": (C.c_int, [_VP, C.c_int32, C.c_int32] + [C.c_double] * 6),
     "pnr_get_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_state": (C.c_int, [_VP, _VP, _VP]),
@@ -249,7 +250,7 @@ SIGNATURES = {
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h"]      # what every env-engine unit includes
 UNITS = {
-    # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (108, 80 of them dynamics mode's)
+    # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (116, 88 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
     # the query entry points of the C ABI and their kernels (35)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",

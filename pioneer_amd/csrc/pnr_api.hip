@@ -571,6 +571,40 @@ int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* strea
     return PNR_OK;
 }
 
+int pnr_world_step_targets(pnr_handle h, uint32_t joint_mask, const float* targets, const float* joint_torques, void* stream)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "pnr_world_step_targets: null handle");
+    if (h->cfg.mode != PNR_MODE_DYNAMIC)
+        return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_targets: joint motors exist in dynamics mode only");
+    if (!targets) return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets: null targets");
+    if (!aligned16(targets)) return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets: targets must be 16-byte aligned");
+    if (joint_torques && !aligned16(joint_torques))
+        return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets: joint_torques must be 16-byte aligned");
+    if (joint_mask == 0 || joint_mask >> kDof)
+        return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets: joint_mask 0x%x must name at least one of joints 0..5 and no other bit", joint_mask);
+    if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets before the first pnr_reset (or pnr_set_state)");
+    bool cm = false;                      // a constraint motor anywhere: the instantiation with motor_constraints
+    for (int i = 0; i < kDof; ++i) {
+        if (h->motors.kind[i] == kMotorPD) continue;
+        cm = true;
+        if (joint_torques)
+            return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_targets: joint %d is on a constraint motor (torque input with the boxed solve is not built)", i);
+    }
+    // this call's table: the masked joints track the lane's r, v, where the kernel puts the env's targets; h->motors stays as it is
+    JointMotorTable W = h->motors;
+    for (int i = 0; i < kDof; ++i)
+        if ((joint_mask >> i) & 1u) W.from_cmd[i] = 1;
+    DeviceGuard g(h->device);
+    const DynParams& D = h->dbase;
+    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
+    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) { with_bool(cm, [&](auto M) {
+        hipLaunchKernelGGL((dyn_world_target_kernel<true, C(), M()>), grid, dim3(kWave), 0, (hipStream_t)stream, h->state, h->dyn,
+                           (long long)h->n, targets, joint_torques, (unsigned)joint_mask, D, W);
+    }); });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
 int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int n_specs, const float* wrenches,
                             const float* joint_torques, int hold_substeps, void* stream)
 {

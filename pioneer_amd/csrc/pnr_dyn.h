@@ -864,9 +864,12 @@ __device__ __forceinline__ void chol_solve6(float (&G)[kTri], const float (&r)[k
 }
 
 // qdd: in qdd_free (the constraint joints' motor torque 0), out qdd_free + M^-1 tau_S.  q, qd: the sub-step's start.
+// LANE_REF (pnr_world_step_targets): a joint with from_cmd set takes its targets from the lane's r, v, as the PD law of dyn_core
+// does, instead of the table's r_ref, v_ref; every other instantiation keeps the table's and never looks at r, v.
+template <bool LANE_REF = false>
 __device__ __forceinline__ void motor_constraints(const DynParams& D, const DynModel& M, const float (&c)[kDof], const float (&s)[kDof],
                                                   const float (&q)[kDof], const float (&qd)[kDof], const JointMotorTable& W,
-                                                  float inv_h, float (&qdd)[kDof])
+                                                  float inv_h, float (&qdd)[kDof], const float* r = nullptr, const float* v = nullptr)
 {
     float H[kTri];
     mass_matrix(M, c, s, H);
@@ -876,8 +879,12 @@ __device__ __forceinline__ void motor_constraints(const DynParams& D, const DynM
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
         in_s[i] = W.kind[i] != kMotorPD;
-        const float vp = W.kp[i] * (W.r_ref[i] - q[i]) * inv_h + qd[i] + W.kd[i] * (W.v_ref[i] - qd[i]);
-        rhs[i] = W.kind[i] == kMotorVelocityConstraint ? W.v_ref[i] : fminf(fmaxf(vp, -W.vcap[i]), W.vcap[i]);
+        float r_ref = W.r_ref[i], v_ref = W.v_ref[i];
+        if constexpr (LANE_REF) {
+            if (W.from_cmd[i]) { r_ref = r[i]; v_ref = v[i]; }
+        }
+        const float vp = W.kp[i] * (r_ref - q[i]) * inv_h + qd[i] + W.kd[i] * (v_ref - qd[i]);
+        rhs[i] = W.kind[i] == kMotorVelocityConstraint ? v_ref : fminf(fmaxf(vp, -W.vcap[i]), W.vcap[i]);
         b[i] = qd[i] + h * qdd[i];
         d[i] = rhs[i] - b[i];
         fr[i] = in_s[i];
@@ -987,7 +994,9 @@ __device__ __forceinline__ void dyn_lane_load(const DynLead& in, long long base,
 // torque in every sub-step, after the motor law's own cap and before damping and friction (PyBullet's TORQUE_CONTROL).
 // WRENCH (WORLD only, pnr_world_step_wrenches): the lane's link wrench records XL under the table X; converted once at the call's
 // first pose, they give each of the first X->hold sub-steps its fext (a wave-uniform compare on the loop counter).
-template <int PHYS, bool WORLD = false, bool CMOTOR = false, bool TORQUE = false, bool WRENCH = false>
+// LANE_REF (CMOTOR only, pnr_world_step_targets): a constraint joint with from_cmd set tracks the lane's r, v as well, as the PD
+// joints always did; the caller has put the env's own targets there.
+template <int PHYS, bool WORLD = false, bool CMOTOR = false, bool TORQUE = false, bool WRENCH = false, bool LANE_REF = false>
 __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, float (&a)[kDof], float (&v)[kDof],
                                          float (&r)[kDof], float (&q)[kDof], float (&qd)[kDof], const float (&sc)[kNumLinks],
                                          const float (&fric_)[kDof], const float (&damp_)[kDof], const float (&act)[kDof],
@@ -1072,7 +1081,8 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
                 }
                 aba<PHYS, true>(D, M, c, s, qd, tau, ades, tc, qdd, fx);
             } else aba<PHYS>(D, M, c, s, qd, tau, ades, tc, qdd);
-            if constexpr (CMOTOR) motor_constraints(D, M, c, s, q, qd, *W, inv_h, qdd);
+            if constexpr (CMOTOR && LANE_REF) motor_constraints<true>(D, M, c, s, q, qd, *W, inv_h, qdd, r, v);
+            else if constexpr (CMOTOR) motor_constraints(D, M, c, s, q, qd, *W, inv_h, qdd);
         }
 #pragma unroll
         for (int i = 0; i < kDof; ++i) {   // semi-implicit Euler + inelastic joint limits (selects, no branches)

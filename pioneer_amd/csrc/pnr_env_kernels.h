@@ -714,6 +714,59 @@ __global__ __launch_bounds__(kWave) void dyn_world_wrench_kernel(const float4* _
     for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
 }
 
+// pnr_world_step_targets: the world step with the env's OWN motor targets (targets [n][12], env-major: position[6] | velocity[6],
+// 48 B per env, 16-byte aligned) for the joints of `mask`.  The world kernels hold the env's command state r, v in registers for the
+// from_cmd joints anyway; here the masked joints' r, v are the lane's targets instead (a wave-uniform select per joint, before the
+// sub-step loop: the twelve loaded values die there and the loop carries what dyn_world_kernel's carries), and the host hands over
+// a copy of the table with from_cmd set for the masked joints.  dyn_core's PD law needs nothing more; motor_constraints reads the
+// lane's values for such a joint under LANE_REF.  The row is loaded whole (three float4) and the unmasked joints' entries are
+// dropped by the select, never used in arithmetic.  tau_ext [n][6] may be null: a wave-uniform branch, as in
+// dyn_world_wrench_kernel; the CMOTOR instantiation never reads it (the host refuses torques next to a constraint motor).  A kernel of
+// its own with the load text repeated, as dyn_world_torque_kernel.
+template <bool RAND, int PHYS, bool CMOTOR>
+__global__ __launch_bounds__(kWave) void dyn_world_target_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
+                                                                 const float* __restrict__ targets, const float* __restrict__ tau_ext,
+                                                                 const unsigned mask, const DynParams D, const JointMotorTable W)
+{
+    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
+    if (e >= n) return;
+    float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
+    HalfRec k[2];
+    load_env_halves(state, n, e, 0, k);
+    const float4* g4 = reinterpret_cast<const float4*>(targets) + 3 * e;
+    const float4 g0 = g4[0], g1 = g4[1], g2 = g4[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) {
+        q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
+        fric[i] = dyn[(long long)(kDynFric + i) * n + e]; damp[i] = dyn[(long long)(kDynDamp + i) * n + e];
+        act[i] = 0.f;
+    }
+#pragma unroll
+    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) tx[i] = 0.f;
+    if constexpr (!CMOTOR) {
+        if (tau_ext) {
+            const float2* t2 = reinterpret_cast<const float2*>(tau_ext) + 3 * e;
+            const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
+            tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
+        }
+    }
+    const float tp[kDof] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y}, tv[kDof] = {g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) {
+        const bool own = (mask >> i) & 1u;
+        r[i] = own ? tp[i] : r[i];
+        v[i] = own ? tv[i] : v[i];
+    }
+    const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
+    dyn_core<PHYS, true, CMOTOR, !CMOTOR, false, CMOTOR>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &W, tx);
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
+}
+
 // The same call on a kinematic-mode handle: there is no simulated state, the caller holds the joints as Bullet would after
 // resetJointState(position, velocity) — js [n][12] = q[6] | qd[6] — and with no gravity, no motor and no collision shapes
 // (the reference's URDF and defaults) frame_skip x stepSimulation carries each joint on at its velocity:

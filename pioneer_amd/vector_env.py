@@ -223,7 +223,8 @@ class PioneerVectorEnv:
             arr[j].link, arr[j].frame = int(link), frames[frame]
         return arr
 
-    def world_step(self, joint_state=None, joint_torques=None, link_wrenches=None, hold_substeps=None):
+    def world_step(self, joint_state=None, joint_torques=None, link_wrenches=None, hold_substeps=None, motor_targets=None,
+                   motor_joints=None):
         """World.step() alone (bullet_scene.py:273-275; pnr_world_step): the simulator's sub-steps and nothing else.  Dynamics mode:
         ``joint_state`` is None (the handle's q, qd move); kinematic mode: the caller's float32 [N, 12] device buffer (q | qd).
         ``joint_torques`` (dynamics mode; float32 ``[N, 6]`` on the env's device, only read): PyBullet's TORQUE_CONTROL
@@ -235,8 +236,35 @@ class PioneerVectorEnv:
         name, ``frame`` ``"link"`` or ``"world"``; ``tensor``: float32 ``[N, K, 9]`` on the env's device, only read, per record
         force[3] | position[3] | torque[3] in that frame (``"world"``: a world point, taken on the link at the call's first pose;
         ``"link"``: a point of the link's frame).  ``hold_substeps``: the records act in that many of the call's first sub-steps
-        (None, <= 0 or >= frame_skip: all of them; 1: Bullet's literal clearing after one stepSimulation).  Never synchronises."""
+        (None, <= 0 or >= frame_skip: all of them; 1: Bullet's literal clearing after one stepSimulation).
+        ``motor_targets`` (dynamics mode; float32 ``[N, 12]`` on the env's device, only read): PyBullet's
+        setJointMotorControlArray per env (pnr_world_step_targets) — position[6] | velocity[6], each env's own targetPosition /
+        targetVelocity for the joints of ``motor_joints`` (an iterable of joint indices 0..5; None: all six), for this call only;
+        law, gains, force cap and maxVelocity of each joint stay as ``set_joint_motor`` left them (a joint nobody commanded: the
+        EngineConfig's law, the targets standing in for the env's command state).  The other joints' entries are ignored (NaN is
+        fine); the position entry of a joint on a velocity law must be finite.  Combines with ``joint_torques`` (same launch), not
+        with ``joint_state`` or ``link_wrenches``.  Never synchronises."""
         self._check_handle()
+        if motor_targets is not None:
+            if joint_state is not None:
+                raise AssertionError("world_step: motor_targets drive the handle's simulated joints; joint_state must be None")
+            if link_wrenches is not None:
+                raise AssertionError("world_step: per-env motor_targets together with link_wrenches is not built "
+                                     "(pnr_world_step_targets takes joint_torques only)")
+            if hold_substeps is not None:
+                raise AssertionError("world_step: hold_substeps belongs to link_wrenches")
+            joints = range(6) if motor_joints is None else [int(j) for j in motor_joints]
+            if any(j < 0 or j >= 6 for j in joints):
+                raise AssertionError(f"world_step: motor_joints must be joint indices 0..5, got {list(joints)}")
+            mask = 0
+            for j in joints:
+                mask |= 1 << j
+            tg = self._in(motor_targets, (self.num_envs, 12), torch.float32, "motor_targets")
+            tq = None if joint_torques is None else self._in(joint_torques, (self.num_envs, 6), torch.float32, "joint_torques")
+            self._chk(self.lib.pnr_world_step_targets(self._h, mask, _ptr(tg), _ptr(tq), self._stream()))
+            return
+        if motor_joints is not None:
+            raise AssertionError("world_step: motor_joints belongs to motor_targets")
         if link_wrenches is not None:
             if joint_state is not None:
                 raise AssertionError("world_step: link_wrenches act on the handle's simulated joints; joint_state must be None")
