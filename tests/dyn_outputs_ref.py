@@ -11,9 +11,9 @@ columns, the reward and the flags (tests/test_dyn_outputs_ref_cpu.py proves the 
 """
 import numpy as np
 
+from bars import POS_IDX, POS_TOL, REW_TOL, TRIG_IDX, check_obs
 from oracle import DynOracle
 from oracle.binding import ORC_DEV
-from test_gpu_parity import POS_TOL, REW_TOL, check_obs
 
 TILE = 32            # a workgroup of the dynamics kernels owns 64 envs and finishes them as two 32-env tiles
 
@@ -68,7 +68,6 @@ def check_outputs(got, want, award_done=5.0):
 
 def worst_outputs(got, want):
     """The measured worst deviations behind check_outputs, for the margins file (never part of a verdict)."""
-    from test_gpu_parity import POS_IDX, TRIG_IDX
     g_obs, g_rew, _, _, g_info = got
     w_obs, w_rew, _, _, w_info = want
     if len(np.asarray(g_rew)) == 0:

@@ -19,6 +19,7 @@ float32 moves three world steps by less than a quarter of the bars).
 """
 import numpy as np
 
+import bars
 import ik_ref
 from oracle import DynOracle
 from oracle.binding import ORC_DEV
@@ -29,7 +30,7 @@ SIZES = [1, 37, 64, 1000]
 STEPS = 3
 H = 1.0 / 240
 FRAME_SKIP = 10
-Q_TOL, QD_TOL = 5e-5, 2e-3                                            # tests/test_gpu_dynamics.py
+Q_TOL, QD_TOL = bars.Q_TOL, bars.QD_TOL                               # read through this module by tests/test_external_force_cpu.py
 
 FREE = [dict(kind="pd", control_mode=1, target_velocity=0.0, position_gain=0.0, velocity_gain=0.0, max_force=0.0)] * DOF
 TRACK = [None] * DOF                                                  # the env-wide law on the env's command state

@@ -173,7 +173,6 @@ DOF = 6
 N_MAX = 1000
 H = 1.0 / 240
 FLOOR_MARGIN = 8.0
-QD_TOL = xcases.QD_TOL
 SIZES = [1, 37, 64, 1000]
 FAMILIES = list(xcases.FAMILIES)                                      # A B C D Dc
 CONSTRAINT = ["mixed", "subset", "scaled"]

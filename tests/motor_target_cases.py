@@ -10,13 +10,12 @@ into the table; a masked joint's are replaced, per env, by that env's row of `ta
 """
 import numpy as np
 
+import bars
 from oracle import DynOracle
 from oracle.binding import ORC_DEV
 
 DOF = 6
-# the dynamics tests' bar for re-synchronised world steps against the float64 oracle (tests/test_gpu_dynamics.py, where its
-# derivation is written down)
-Q_TOL, QD_TOL = 5e-5, 2e-3
+Q_TOL, QD_TOL = bars.Q_TOL, bars.QD_TOL                               # read through this module by tests/test_motor_targets_cpu.py
 FULL = tuple(range(DOF))
 
 

@@ -10,10 +10,10 @@ import pytest
 
 import constraint_motor_cases as cases
 import constraint_motor_ref as ref
+from bars import QD_TOL
 from oracle import DynOracle
 from oracle.binding import ORC_DEV
 
-QD_TOL = 2e-3                                                         # tests/test_gpu_dynamics.py
 H = 1.0 / 240
 GPU_SETS = [("mixed", 1), ("mixed", 37), ("mixed", 64), ("mixed", 1000), ("subset", 37), ("subset", 1000), ("skip10", 64), ("scaled", 64)]
 

@@ -21,48 +21,27 @@ import numpy as np
 import pytest
 import torch
 
+from bars import Q_TOL, QD_TOL
+from gpu_support import dyn_env, dyn_words, lib as _lib, load_joints, set_motors
 from oracle import DynOracle
 from oracle.binding import ORC_DEV
 
 pytestmark = pytest.mark.gpu
 
-# the dynamics tests' bar for re-synchronised world steps against the float64 oracle (tests/test_gpu_dynamics.py, Q_TOL / QD_TOL
-# and the measurements they rest on)
-Q_TOL, QD_TOL = 5e-5, 2e-3
 NAN = float("nan")
 H = 1.0 / 240
 AMPLE = 1e9                                                           # a force no sub-step here needs
 BOX = dict(obstacle_position=(10.0, 5.0, 0.0), obstacle_half_extents=(0.5, 0.5, 5.0))
 
 
-def _lib():
-    from pioneer_amd import _lib
-    return _lib
-
-
 def make(n, gravity=0.0, frame_skip=10, seed=0, **eng):
-    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig
-    env = PioneerVectorEnv(n, device="cuda:0", seed=seed, simulation_config=SimulationConfig(gravity=gravity, frame_skip=frame_skip),
-                           engine_config=EngineConfig(mode="dynamic", auto_reset=False, max_episode_steps=0, **eng))
-    env.reset()
-    return env
+    return dyn_env(n, seed, gravity, frame_skip, **eng)
 
 
 def poses(env, seed, frac):
     """per-env joint angles inside frac x the joint limits"""
     rng = np.random.default_rng(seed)
     return rng.uniform(frac * env.r_lo.astype(np.float64), frac * env.r_hi.astype(np.float64), size=(env.num_envs, 6))
-
-
-def load(env, q, qd=None):
-    d = env.get_dyn_state()
-    d[0:6] = torch.as_tensor(np.ascontiguousarray(q.T), dtype=torch.float32, device=d.device)
-    d[6:12] = 0.0 if qd is None else torch.as_tensor(np.ascontiguousarray(qd.T), dtype=torch.float32, device=d.device)
-    env.set_dyn_state(d)
-
-
-def dyn(env):
-    return env.get_dyn_state().cpu().numpy()
 
 
 def test_velocity_motors_are_deadbeat_and_integrate_exactly():
@@ -73,14 +52,14 @@ def test_velocity_motors_are_deadbeat_and_integrate_exactly():
     n, K = 16, 24
     env = make(n, frame_skip=1, joint_damping=0.5, joint_friction=0.2)
     q0 = poses(env, 1, 0.5)
-    load(env, q0)
-    q0 = dyn(env)[0:6].T.astype(np.float64)
+    load_joints(env, q0)
+    q0 = dyn_words(env)[0:6].T.astype(np.float64)
     vs = np.array([0.5, -0.3, 0.2, 1.0, -0.4, 2.0])
     for j in range(6):
         env.set_joint_motor(j, L.CONTROL_VELOCITY_CONSTRAINT, target_velocity=vs[j], max_force=AMPLE)
     for k in range(1, K + 1):
         env.world_step()
-        d = dyn(env).astype(np.float64)
+        d = dyn_words(env).astype(np.float64)
         qd, q = d[6:12].T, d[0:6].T
         assert np.all(np.abs(qd - vs) <= 1e-5 * np.maximum(1.0, np.abs(vs))), (k, np.abs(qd - vs).max())
         err = np.abs(q - (q0 + k * H * vs)).max()
@@ -99,7 +78,7 @@ def test_saturated_motor_is_a_constant_torque_like_the_oracle(n, k):
     F = {0: 50.0, 5: 2.0}[k]
     env = make(n, gravity=9.81, seed=3, randomize=True, ground_z=0.0, link_contacts=True, **BOX)
     orc = DynOracle(n, seed=3, precision=ORC_DEV, dyn=dict(gravity=9.81, randomize=1, ground_z=0.0, link_contacts=1, **BOX))
-    load(env, poses(env, 10 + k, 0.6))
+    load_joints(env, poses(env, 10 + k, 0.6))
     env.set_joint_motor(k, L.CONTROL_VELOCITY_CONSTRAINT, target_velocity=50.0, max_force=F)
     orc.set_joint_motor(k, 1, target_velocity=1e3, velocity_gain=1e6, max_force=F)
     for j in range(6):
@@ -107,13 +86,13 @@ def test_saturated_motor_is_a_constant_torque_like_the_oracle(n, k):
             env.set_joint_motor(j, L.CONTROL_VELOCITY_CONSTRAINT, target_velocity=0.0, max_force=0.0)
             orc.set_joint_motor(j, 1, target_velocity=0.0, velocity_gain=0.0)
     orc.load_state_words(env.get_state().cpu().numpy().view(np.uint32))
-    start = dyn(env)[6 + k].astype(np.float64)
+    start = dyn_words(env)[6 + k].astype(np.float64)
     for step in range(10):
-        before = dyn(env)
+        before = dyn_words(env)
         orc.load_dyn_words(before)
         env.world_step()
         orc.world_step()
-        d = dyn(env).astype(np.float64)
+        d = dyn_words(env).astype(np.float64)
         dq = np.abs(d[0:6].T - orc.dstate["q"]).max()
         dqd = np.abs(d[6:12].T - orc.dstate["qd"]).max()
         assert dq <= Q_TOL and dqd <= QD_TOL, (step, dq, dqd)
@@ -130,16 +109,16 @@ def test_position_motor_with_bullet_defaults_closes_a_tenth_per_substep():
     env = make(n)
     q0 = poses(env, 2, 0.4)
     q0[:, j] = np.linspace(0.3, 0.6, n)
-    load(env, q0)
-    e0 = -dyn(env)[j].astype(np.float64)                              # q* = 0
+    load_joints(env, q0)
+    e0 = -dyn_words(env)[j].astype(np.float64)                              # q* = 0
     for i in range(6):
         if i != j:
             env.set_joint_motor(i, L.CONTROL_VELOCITY_CONSTRAINT, target_velocity=0.0, max_force=AMPLE)
     env.set_joint_motor(j, L.CONTROL_POSITION_CONSTRAINT, target_position=0.0)
-    held = dyn(env)[0:6]
+    held = dyn_words(env)[0:6]
     for w in range(1, 4):
         env.world_step()
-        d = dyn(env).astype(np.float64)
+        d = dyn_words(env).astype(np.float64)
         want = e0 * 0.9 ** (10 * w)
         assert np.all(np.abs(-d[j] - want) <= 1e-4 * np.abs(want)), (w, -d[j], want)
         others = [i for i in range(6) if i != j]
@@ -152,7 +131,7 @@ def test_position_motor_max_velocity_caps_the_speed():
     n, j = 8, 4
     env = make(n, frame_skip=1)
     q0 = poses(env, 4, 0.3)
-    load(env, q0)
+    load_joints(env, q0)
     for i in range(6):
         if i != j:
             env.set_joint_motor(i, L.CONTROL_VELOCITY_CONSTRAINT, target_velocity=0.0, max_force=AMPLE)
@@ -160,7 +139,7 @@ def test_position_motor_max_velocity_caps_the_speed():
     top = 0.0
     for _ in range(30):
         env.world_step()
-        qd = dyn(env)[6 + j].astype(np.float64)
+        qd = dyn_words(env)[6 + j].astype(np.float64)
         assert np.all(np.abs(qd) <= 0.3 + 1e-5), qd
         top = max(top, float(qd.min()))
     assert top >= 0.3 - 1e-5, "far from its target the motor runs at maxVelocity"
@@ -224,12 +203,12 @@ def _motors(env):
 def test_batch_envs_equal_single_env_handles_bit_for_bit(n):
     cfg = dict(gravity=9.81, seed=5, randomize=True, ground_z=0.0, link_contacts=True, **BOX)
     env = make(n, **cfg)
-    load(env, poses(env, 20, 0.6))
+    load_joints(env, poses(env, 20, 0.6))
     _motors(env)
     words, d0 = env.get_state().clone(), env.get_dyn_state().clone()
     for _ in range(3):
         env.world_step()
-    got = dyn(env)
+    got = dyn_words(env)
     for e in sorted({0, 1, n // 2, n - 1}):
         one = make(1, **cfg)
         one.set_state(words[:, e:e + 1].contiguous())
@@ -237,7 +216,7 @@ def test_batch_envs_equal_single_env_handles_bit_for_bit(n):
         _motors(one)
         for _ in range(3):
             one.world_step()
-        assert np.array_equal(dyn(one)[:, 0].view(np.uint32), got[:, e].view(np.uint32)), e
+        assert np.array_equal(dyn_words(one)[:, 0].view(np.uint32), got[:, e].view(np.uint32)), e
         one.close()
     env.close()
 
@@ -249,7 +228,7 @@ def test_invalid_arguments_leave_the_motor_table_unchanged():
     env, ref = make(n, **cfg), make(n, **cfg)
     q = poses(env, 30, 0.5)
     for h in (env, ref):
-        load(h, q)
+        load_joints(h, q)
         h.set_joint_motor(1, L.CONTROL_POSITION_CONSTRAINT, target_position=0.3, max_force=800.0)
         h.set_joint_motor(3, L.CONTROL_VELOCITY_CONSTRAINT, target_velocity=0.5)
     bad = [dict(joint=1, control_mode=L.CONTROL_POSITION_CONSTRAINT, target_position=NAN),
@@ -265,7 +244,7 @@ def test_invalid_arguments_leave_the_motor_table_unchanged():
         assert ei.value.code == -1, kw                                 # PNR_ERR_INVALID
     for _ in range(3):
         env.world_step(); ref.world_step()
-    assert np.array_equal(dyn(env).view(np.uint32), dyn(ref).view(np.uint32))
+    assert np.array_equal(dyn_words(env).view(np.uint32), dyn_words(ref).view(np.uint32))
     env.close(); ref.close()
 
 
@@ -295,18 +274,6 @@ def test_create_rejects_the_constraint_modes_as_the_step_law():
 FREE_SLACK = 1e-3
 
 
-def _set_motors(env, motors):
-    L = _lib()
-    modes = {"velocity_constraint": L.CONTROL_VELOCITY_CONSTRAINT, "position_constraint": L.CONTROL_POSITION_CONSTRAINT}
-    for j, m in enumerate(motors):
-        if m is None:
-            continue                                                  # uncommanded: the env-wide law on the command state
-        mode = modes.get(m["kind"])
-        if mode is None:
-            mode = L.CONTROL_VELOCITY if m["control_mode"] == 1 else L.CONTROL_POSITION
-        env.set_joint_motor(j, mode, **{k: v for k, v in m.items() if k not in ("kind", "control_mode")})
-
-
 def _against_reference(case, n):
     """Runs an input set's re-randomised world steps on the engine and on the reference; asserts the project's bar on q and qd
     of every env and the deadbeat bound on the joints that are free with margin; records the worst deviations."""
@@ -319,10 +286,10 @@ def _against_reference(case, n):
     assert np.array_equal(env.a_max, orc.a_max)
     for act in cases.command_actions(case, n, env.a_max):
         env.vector_step(torch.from_numpy(act).cuda())
-    _set_motors(env, c["motors"])
+    set_motors(env, c["motors"])
     # the engine's command state and per-env draws are the ones the CPU tests' conditions were asserted on
     words = env.get_state().cpu().numpy().view(np.uint32)
-    assert np.array_equal(words[:21], orc.state_words()[:21]) and np.array_equal(dyn(env)[12:35], orc.dyn_words()[12:35])
+    assert np.array_equal(words[:21], orc.state_words()[:21]) and np.array_equal(dyn_words(env)[12:35], orc.dyn_words()[12:35])
     if c.get("command_steps"):
         st = env.state_dict()
         assert np.all(st["r"] != 0) and np.all(st["v"] != 0), "the command state must have moved off zero"
@@ -330,11 +297,11 @@ def _against_reference(case, n):
     worst_q = worst_qd = worst_free = 0.0
     tight = 0
     for step in range(c["steps"]):
-        load(env, *cases.states(case, n, step))
-        orc.load_dyn_words(dyn(env))
+        load_joints(env, *cases.states(case, n, step))
+        orc.load_dyn_words(dyn_words(env))
         infos = ref.world_step(orc, c["motors"], c["frame_skip"])
         env.world_step()
-        d = dyn(env).astype(np.float64)
+        d = dyn_words(env).astype(np.float64)
         q, qd = d[0:6].T, d[6:12].T
         dq, dqd = np.abs(q - orc.dstate["q"]).max(), np.abs(qd - orc.dstate["qd"]).max()
         worst_q, worst_qd = max(worst_q, float(dq)), max(worst_qd, float(dqd))
@@ -396,8 +363,8 @@ def test_joint_limits_hold_against_a_motor_and_release_inward():
     env = make(n, gravity=9.81, frame_skip=1, seed=8, randomize=True)
     hi, lo = env.r_hi.astype(np.float64), env.r_lo.astype(np.float64)
     q0 = np.where((np.arange(n) % 2 == 0)[:, None], hi, lo)
-    load(env, q0)
-    q0 = dyn(env)[0:6].T.astype(np.float64)
+    load_joints(env, q0)
+    q0 = dyn_words(env)[0:6].T.astype(np.float64)
     assert np.array_equal(q0, np.where((np.arange(n) % 2 == 0)[:, None], hi, lo))
     vs = np.array([0.5, -0.5, 0.4, -0.6, 0.8, -1.0])
     for j in range(6):
@@ -405,7 +372,7 @@ def test_joint_limits_hold_against_a_motor_and_release_inward():
     outward = ((q0 == hi) & (vs > 0)) | ((q0 == lo) & (vs < 0))
     assert outward.any(axis=0).all() and (~outward).any(axis=0).all()
     env.world_step()
-    d = dyn(env).astype(np.float64)
+    d = dyn_words(env).astype(np.float64)
     q, qd = d[0:6].T, d[6:12].T
     assert np.array_equal(q[outward], q0[outward]) and np.all(qd[outward] == 0.0)
     want = np.broadcast_to(vs, (n, 6))

@@ -16,10 +16,11 @@ import torch
 
 import contact_query_cases as cases
 import contact_query_ref as ref
+from bars import Q_TOL, QD_TOL
+from gpu_support import dev, dyn_env, f64, kin_env, lib as _lib, load_joints
 
 pytestmark = pytest.mark.gpu
 
-Q_TOL, QD_TOL = 5e-5, 2e-3                                            # tests/test_gpu_dynamics.py
 SENTINEL = -7.25
 SIZES = list(cases.SIZES)
 KEYS = ("points", "summary", "joint_torques")
@@ -27,19 +28,6 @@ KEYS = ("points", "summary", "joint_torques")
 # into that box (measured: none of 200 000 uniform poses; at the limit q2 = 1.309 arm1's last sample is still 0.15 clear of the
 # box's top), so joint 2 sits at 1.467; reset_world takes its joint_positions as they are, like the reference's.
 FACADE_POSE = (0.536, 1.467, -1.275, 0.446, -1.434, -1.607)
-
-
-def _lib():
-    from pioneer_amd import _lib
-    return _lib
-
-
-def T(x):
-    return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32, device="cuda:0")
-
-
-def f64(t):
-    return t.double().cpu().numpy()
 
 
 def scene_bodies(bodies=cases.SCENE_A):
@@ -51,36 +39,26 @@ def scene_bodies(bodies=cases.SCENE_A):
 
 
 def make_kin(n, reset=True):
-    from pioneer_amd import EngineConfig, PioneerVectorEnv
-    env = PioneerVectorEnv(n, device="cuda:0", seed=cases.SEED, engine_config=EngineConfig(auto_reset=False, max_episode_steps=0))
-    if reset:
-        env.reset()
-    return env
+    return kin_env(n, cases.SEED, reset, auto_reset=False, max_episode_steps=0)
 
 
 def make_dyn(n, gravity=9.81, frame_skip=1, **eng):
-    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig
-    env = PioneerVectorEnv(n, device="cuda:0", seed=cases.SEED, simulation_config=SimulationConfig(gravity=gravity, frame_skip=frame_skip),
-                           engine_config=EngineConfig(mode="dynamic", auto_reset=False, max_episode_steps=0, **eng))
-    env.reset()
-    return env
+    return dyn_env(n, cases.SEED, gravity, frame_skip, **eng)
 
 
 def source(kind, n, q, qd):
     """(env, joint_state argument) for a joint source holding q | qd"""
     if kind == "buffer":
-        return make_kin(n), T(np.concatenate([q, qd], axis=1))
+        return make_kin(n), dev(np.concatenate([q, qd], axis=1))
     if kind == "dynamic_own":
         env = make_dyn(n)
-        d = env.get_dyn_state()
-        d[0:6], d[6:12] = T(q.T), T(qd.T)
-        env.set_dyn_state(d)
+        load_joints(env, q, qd)
         return env, None
     assert kind == "kinematic_own"                                    # the env's r (state words 12-17) and v (6-11)
     env = make_kin(n)
     w = env.get_state()
     f = w.view(torch.float32)
-    f[6:12], f[12:18] = T(qd.T), T(q.T)
+    f[6:12], f[12:18] = dev(qd.T), dev(q.T)
     env.set_state(w)
     return env, None
 
@@ -128,7 +106,7 @@ def test_contacts_against_the_reference(n, kind):
     env, js = source(kind, n, q, qd)
     before = None if js is None else js.clone()
     for family in "AB":
-        bp = T(cases.family_b_positions(n)) if family == "B" else None
+        bp = dev(cases.family_b_positions(n)) if family == "B" else None
         res = env.contacts(joint_state=js, bodies=scene_bodies(), body_positions=bp, joint_torques=True)
         torch.cuda.synchronize()
         check_against_reference(res, family, n)
@@ -140,8 +118,8 @@ def test_contacts_against_the_reference(n, kind):
 @pytest.mark.parametrize("n", SIZES)
 def test_nothing_past_n_rows_and_each_output_alone(n):
     env = make_kin(n)
-    js = T(cases.joint_state(n))
-    bp = T(cases.family_b_positions(n))
+    js = dev(cases.joint_state(n))
+    bp = dev(cases.family_b_positions(n))
     shapes = {"points": (ref.SAMPLES, ref.DIM), "summary": (4,), "joint_torques": (6,)}
     pad = 3
     big = {k: torch.full((n + pad,) + s, SENTINEL, device="cuda:0") for k, s in shapes.items()}
@@ -175,13 +153,13 @@ def test_an_envs_results_do_not_depend_on_the_batch():
     k, lane = 777, 5
     js_all, bp_all = cases.joint_state(cases.N_MAX), cases.family_b_positions(cases.N_MAX)
     big = make_kin(cases.N_MAX)
-    in_batch = big.contacts(joint_state=T(js_all), bodies=scene_bodies(), body_positions=T(bp_all), joint_torques=True)
+    in_batch = big.contacts(joint_state=dev(js_all), bodies=scene_bodies(), body_positions=dev(bp_all), joint_torques=True)
     one = make_kin(1)
-    alone = one.contacts(joint_state=T(js_all[k:k + 1]), bodies=scene_bodies(), body_positions=T(bp_all[k:k + 1]), joint_torques=True)
+    alone = one.contacts(joint_state=dev(js_all[k:k + 1]), bodies=scene_bodies(), body_positions=dev(bp_all[k:k + 1]), joint_torques=True)
     wave = make_kin(64)
     js64, bp64 = js_all[:64].copy(), bp_all[:64].copy()
     js64[lane], bp64[lane] = js_all[k], bp_all[k]
-    moved = wave.contacts(joint_state=T(js64), bodies=scene_bodies(), body_positions=T(bp64), joint_torques=True)
+    moved = wave.contacts(joint_state=dev(js64), bodies=scene_bodies(), body_positions=dev(bp64), joint_torques=True)
     torch.cuda.synchronize()
     for key in KEYS:
         same = torch.equal(in_batch[key][k], alone[key][0]) and torch.equal(in_batch[key][k], moved[key][lane])
@@ -198,8 +176,8 @@ def test_refusals_touch_nothing():
     n = 64
     env = make_kin(n)
     lib, h, st = env.lib, env._h, env._stream()
-    js = T(cases.joint_state(n))
-    bp = T(cases.family_b_positions(n))
+    js = dev(cases.joint_state(n))
+    bp = dev(cases.family_b_positions(n))
     pts = torch.full((n + 1, ref.SAMPLES, ref.DIM), SENTINEL, device="cuda:0")
     sm = torch.full((n + 1, 4), SENTINEL, device="cuda:0")
     tq = torch.full((n + 1, 6), SENTINEL, device="cuda:0")
@@ -271,8 +249,8 @@ def test_refusals_touch_nothing():
 def test_the_call_is_captured_and_replayed():
     n = 1000
     env = make_kin(n)
-    js_a, js_b = T(cases.joint_state(n)), T(cases.joint_state(n)[::-1].copy())
-    bp = T(cases.family_b_positions(n))
+    js_a, js_b = dev(cases.joint_state(n)), dev(cases.joint_state(n)[::-1].copy())
+    bp = dev(cases.family_b_positions(n))
     js = js_a.clone()
     out = {"points": torch.empty((n, ref.SAMPLES, ref.DIM), device="cuda:0"), "summary": torch.empty((n, 4), device="cuda:0"),
            "joint_torques": torch.empty((n, 6), device="cuda:0")}
@@ -325,7 +303,7 @@ def test_query_torques_reproduce_a_step_with_contacts():
     Q = make_dyn(n, randomize=True, link_contacts=True)
     Q0 = make_dyn(n, randomize=True, link_contacts=True)
     d = P.get_dyn_state()
-    d[0:6], d[6:12] = T(q.T), T(qd.T)
+    d[0:6], d[6:12] = dev(q.T), dev(qd.T)
     for env in (P, Q, Q0):
         env.set_dyn_state(d.clone())
         for j in range(6):                                            # zero gains: no motor torque at all

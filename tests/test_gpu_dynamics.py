@@ -2,17 +2,8 @@
 
 PARITY UNPINNED at the reference (it pins no dynamics): the oracle itself is validated by
 tests/test_dyn_oracle.py.  Tolerances (float32 kernel, 10 sub-steps, vs float64):
-  re-synchronised single steps: |dq| <= 5e-5 rad, |dqd| <= 2e-3 rad/s; free-running 40 steps under PD tracking:
+  re-synchronised single steps: Q_TOL, QD_TOL (tests/bars.py, where they are derived); free-running 40 steps under PD tracking:
   |dq| <= 5e-4.
-Where Q_TOL = 5e-5 comes from (measured worst single-step deviations over 2 048 envs x 25 steps, MI355X, r02;
-every run rewrites gpurun_out/dyn_parity_margins.json): pd 4.3e-6, gravity_friction 9.5e-7, ground 9.5e-7,
-box 7.2e-7, randomized 1.2e-5, torque_limited 2.1e-5 rad (= 88 float32 ulps of a joint angle near pi); |dqd| at most
-1.2e-3 rad/s (randomized).  The two large ones are the scenarios that weaken the PD loop's contraction of rounding
-differences: a saturated torque cap applies the same clipped torque whatever the tracking error, so float32-vs-float64
-differences of the ABA accelerations (|qdd| up to ~500 rad/s^2 here, relative error ~1e-6 x the conditioning of the
-articulated inertia) are integrated open-loop over the ten sub-steps; per-env link scales down to 0.5 raise the
-accelerations the same way.  r01 first set 2e-5 from the pd / gravity scenarios alone and torque_limited missed it
-by 5 % (2.098e-5); 5e-5 is 2.4x the worst measured value, QD_TOL = 2e-3 is 1.7x.
 """
 import math
 
@@ -20,12 +11,12 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import COracle, DynOracle
+from bars import POS_TOL, PTR_TOL, Q_TOL, QD_TOL, ROLL_OBS_TOL, ROLL_REW_TOL
+from gpu_support import dyn_words, engine_config_from_oracle_names, words
+from oracle import DynOracle
 from oracle.binding import ORC_DEV
 
 pytestmark = pytest.mark.gpu
-
-Q_TOL, QD_TOL = 5e-5, 2e-3
 
 _c, _s = math.cos(0.35), math.sin(0.35)
 _ax = np.array([1.0, 2.0, 0.5]) / np.linalg.norm([1.0, 2.0, 0.5])
@@ -35,23 +26,8 @@ SCENE = (("plane", (0.0, 0.0, 1.0), (0.0, math.sin(0.1), 0.0, math.cos(0.1)), (0
 
 
 def make(n, seed=0, auto_reset=False, max_steps=0, layout="env_major", gravity=0.0, **dyn):
-    from pioneer_amd import PioneerVectorEnv, EngineConfig, SimulationConfig
-    from pioneer_amd.config import SceneBody
-    ek = dict(dyn)
-    eng = EngineConfig(mode="dynamic", auto_reset=auto_reset, max_episode_steps=max_steps, obs_layout=layout,
-                       pd_kp=ek.pop("kp", 4000.0), pd_kd=ek.pop("kd", 400.0), torque_limit=ek.pop("torque_limit", 0.0),
-                       teleport=bool(ek.pop("teleport", 0)), randomize=bool(ek.pop("randomize", 0)),
-                       joint_damping=ek.pop("joint_damping", 0.0), joint_friction=ek.pop("joint_friction", 0.0),
-                       ground_z=ek.pop("ground_z", float("nan")),
-                       contact_kp=ek.pop("contact_kp", 2000.0), contact_kd=ek.pop("contact_kd", 50.0),
-                       obstacle_position=ek.pop("obstacle_position", (10.0, 5.0, 0.0)),
-                       obstacle_half_extents=ek.pop("obstacle_half_extents", (0.0, 0.0, 0.0)),
-                       pointer_radius=ek.pop("pointer_radius", 0.2),
-                       control_mode={0: "position", 1: "velocity"}[ek.pop("control_mode", 0)],
-                       max_velocity=ek.pop("max_velocity", 0.0), link_contacts=bool(ek.pop("link_contacts", 0)),
-                       pd_inertia_scaled=bool(ek.pop("pd_inertia_scaled", 0)),
-                       scene=tuple(SceneBody(sh, tuple(p), tuple(q), tuple(sz)) for sh, p, q, sz in ek.pop("scene", ())))
-    assert not ek
+    from pioneer_amd import PioneerVectorEnv, SimulationConfig
+    eng = engine_config_from_oracle_names(dyn, auto_reset=auto_reset, max_episode_steps=max_steps, obs_layout=layout)
     env = PioneerVectorEnv(n, device="cuda:0", seed=seed, simulation_config=SimulationConfig(gravity=gravity),
                            engine_config=eng)
     od = dict(dyn); od["gravity"] = gravity
@@ -61,8 +37,8 @@ def make(n, seed=0, auto_reset=False, max_steps=0, layout="env_major", gravity=0
 
 
 def sync_oracle_from_gpu(env, orc):
-    orc.load_state_words(env.get_state().cpu().numpy().view(np.uint32))
-    orc.load_dyn_words(env.get_dyn_state().cpu().numpy())
+    orc.load_state_words(words(env))
+    orc.load_dyn_words(dyn_words(env))
 
 
 def test_teleport_zero_gravity_equals_kinematic_kernel():
@@ -114,8 +90,8 @@ def test_single_step_parity_resynced(scenario):
     n = 2048
     env, orc = make(n, seed=5, **cfg)
     obs = env.reset(); oobs = orc.reset()
-    assert np.abs(obs.double().cpu().numpy() - oobs).max() < 3e-5
-    assert np.array_equal(env.get_dyn_state().cpu().numpy()[:35], orc.dyn_words()[:35])   # q=r, qd=0, draws
+    assert np.abs(obs.double().cpu().numpy() - oobs).max() < POS_TOL
+    assert np.array_equal(dyn_words(env)[:35], orc.dyn_words()[:35])   # q=r, qd=0, draws
     rng = np.random.RandomState(1)
     worst_q = worst_qd = 0.0
     for t in range(25):
@@ -123,7 +99,7 @@ def test_single_step_parity_resynced(scenario):
         sync_oracle_from_gpu(env, orc)
         obs, rew, done, trunc = env.vector_step(torch.from_numpy(act).cuda())
         oobs, orew, odone, otrunc = orc.step(act)
-        w = env.get_dyn_state().cpu().numpy().astype(np.float64)
+        w = dyn_words(env).astype(np.float64)
         eq = np.abs(w[0:6].T - orc.dstate["q"]).max(1); eqd = np.abs(w[6:12].T - orc.dstate["qd"]).max(1)
         o = obs.double().cpu().numpy()
         loose = scenario.startswith("box") or scenario == "links_ground" or scenario.startswith("scene")
@@ -140,11 +116,11 @@ def test_single_step_parity_resynced(scenario):
         else:
             assert eq.max() <= Q_TOL and eqd.max() <= QD_TOL
             assert np.abs(o[:, 0:6] - oobs[:, 0:6]).max() <= Q_TOL
-            assert np.abs(o[:, 126:129] - oobs[:, 126:129]).max() <= 1e-3      # pointer: 30-unit arm x 2e-5 rad
+            assert np.abs(o[:, 126:129] - oobs[:, 126:129]).max() <= PTR_TOL
             assert np.abs(o[:, 90:96] - oobs[:, 90:96]).max() <= QD_TOL
         # the kinematic command state stays bit-exact
-        assert np.array_equal(env.get_state().cpu().numpy().view(np.uint32)[:21], orc.state_words()[:21])
-    st = env.get_dyn_state().cpu().numpy()
+        assert np.array_equal(words(env)[:21], orc.state_words()[:21])
+    st = dyn_words(env)
     assert np.all(st[0:6].T <= env.r_hi) and np.all(st[0:6].T >= env.r_lo)
     if scenario.startswith("scene"):
         # the comparison above means something only if the bodies are touched: every one of the three shapes, alone, is in
@@ -187,19 +163,11 @@ def test_free_running_tracking_and_autoreset():
         obs, rew, done, trunc = env.vector_step(torch.from_numpy(act).cuda())
         oobs, orew, odone, otrunc = orc.step(act)
         assert np.array_equal(trunc.cpu().numpy(), otrunc)
-        w = env.get_dyn_state().cpu().numpy().astype(np.float64)
+        w = dyn_words(env).astype(np.float64)
         assert np.abs(w[0:6].T - orc.dstate["q"]).max() <= 5e-4
         assert np.array_equal(w[12:35], orc.dyn_words()[12:35].astype(np.float64))   # per-env parameters after resets
-    assert np.array_equal(env.get_state().cpu().numpy().view(np.uint32)[22:], orc.state_words()[22:])
+    assert np.array_equal(words(env)[22:], orc.state_words()[22:])
     env.close()
-
-
-# pnr_step and pnr_rollout run two separately compiled kernels in dynamics mode (dyn_step_kernel / dyn_rollout_kernel)
-# that share one text of the arithmetic, compiled with fp contraction allowed: the same expression may be fused
-# differently in the two, so their float32 results agree to rounding, not to the bit (kinematic mode, which has a
-# bit-exactness contract, is compiled without contraction and IS identical between the two entry points).
-ROLL_OBS_TOL = 2e-3     # abs, after <= 11 steps of rounding-level differences through the PD loop (positions up to ~30)
-ROLL_REW_TOL = 2e-3
 
 
 def _close(a, b, tol):
@@ -262,7 +230,7 @@ def test_ragged_batches_against_the_oracle(n):
     with randomisation, gravity, TimeLimit and auto-reset on; every output row is compared."""
     env, orc = make(n, seed=9, auto_reset=True, max_steps=6, gravity=9.81, randomize=1)
     obs = env.reset(); oobs = orc.reset()
-    assert obs.shape == (n, 137) and np.abs(obs.double().cpu().numpy() - oobs).max() < 3e-5
+    assert obs.shape == (n, 137) and np.abs(obs.double().cpu().numpy() - oobs).max() < POS_TOL
     rng = np.random.RandomState(n)
     for t in range(14):                                   # two time-limit resets per env
         act = (rng.uniform(-0.3, 0.3, (n, 6)) * env.a_max).astype(np.float32)
@@ -270,14 +238,14 @@ def test_ragged_batches_against_the_oracle(n):
         obs, rew, done, trunc = env.vector_step(torch.from_numpy(act).cuda())
         oobs, orew, odone, otrunc = orc.step(act)
         assert np.array_equal(trunc.cpu().numpy(), otrunc) and np.array_equal(done.cpu().numpy(), odone)
-        w = env.get_dyn_state().cpu().numpy().astype(np.float64)
+        w = dyn_words(env).astype(np.float64)
         assert np.abs(w[0:6].T - orc.dstate["q"]).max() <= Q_TOL and np.abs(w[6:12].T - orc.dstate["qd"]).max() <= QD_TOL
         o = obs.double().cpu().numpy()
-        assert np.abs(o[:, 0:6] - oobs[:, 0:6]).max() <= Q_TOL and np.abs(o[:, 126:129] - oobs[:, 126:129]).max() <= 1e-3
+        assert np.abs(o[:, 0:6] - oobs[:, 0:6]).max() <= Q_TOL and np.abs(o[:, 126:129] - oobs[:, 126:129]).max() <= PTR_TOL
         assert np.abs(rew.double().cpu().numpy() - orew).max() <= 2e-3
-        assert np.array_equal(env.get_state().cpu().numpy().view(np.uint32), orc.state_words()) or \
-            np.array_equal(env.get_state().cpu().numpy().view(np.uint32)[:21], orc.state_words()[:21])
-        assert np.array_equal(env.get_dyn_state().cpu().numpy()[12:35], orc.dyn_words()[12:35])   # per-env draws after resets
+        assert np.array_equal(words(env), orc.state_words()) or \
+            np.array_equal(words(env)[:21], orc.state_words()[:21])
+        assert np.array_equal(dyn_words(env)[12:35], orc.dyn_words()[12:35])   # per-env draws after resets
     env.close()
 
 
@@ -437,8 +405,8 @@ def test_reference_demo_loop_on_a_dynamics_facade_matches_the_oracle():
                                                       scene=[("box", (10, 5, 0), q, (0.5, 0.5, 5.0)), ("plane", (0, 0, 0), q, (0, 0, 1.0))]))
     # a pose whose arm reaches down and outward, towards the bodies
     env.reset_world(joint_positions=np.array([0.45, 1.0, 0.9, 0.0, 0.3, 0.0]), target_position=(20.0, 0.0, 4.0))
-    orc.load_state_words(env._vec.get_state().cpu().numpy().view(np.uint32))
-    orc.load_dyn_words(env._vec.get_dyn_state().cpu().numpy())
+    orc.load_state_words(words(env._vec))
+    orc.load_dyn_words(dyn_words(env._vec))
     target_joint = env.scene.joints_by_name["robot:hinge1_to_arm1"]                 # :276
     velocity, worst, touched = 1.0, 0.0, 0
     for count in range(60):
@@ -448,11 +416,11 @@ def test_reference_demo_loop_on_a_dynamics_facade_matches_the_oracle():
             velocity = 1.0
         if target_joint.position() > target_joint.upper_limit - 0.01 * rr:
             velocity = -1.0
-        orc.load_dyn_words(env._vec.get_dyn_state().cpu().numpy())                  # the oracle takes the engine's state, then both step
+        orc.load_dyn_words(dyn_words(env._vec))                  # the oracle takes the engine's state, then both step
         touched += int(orc.contact_wrenches()[0])
         env.world.step()                                                            # :295
         orc.world_step()
-        got = env._vec.get_dyn_state().cpu().numpy().astype(np.float64)[:12, 0]
+        got = dyn_words(env._vec).astype(np.float64)[:12, 0]
         want = np.concatenate([orc.dstate["q"][0], orc.dstate["qd"][0]])
         worst = max(worst, float(np.abs(got[:6] - want[:6]).max()))
         assert np.abs(got[:6] - want[:6]).max() <= Q_TOL and np.abs(got[6:] - want[6:]).max() <= QD_TOL, (count, got, want)
@@ -474,7 +442,7 @@ def test_per_joint_motors_drive_world_step_like_the_oracle(inertia_scaled):
     orc = DynOracle(1, seed=0, precision=ORC_DEV, dyn=dict(gravity=9.81, kp=eng["pd_kp"], kd=eng["pd_kd"], torque_limit=2000.0, joint_damping=0.2,
                                                       joint_friction=0.1, pd_inertia_scaled=int(inertia_scaled)))
     env.reset_world(joint_positions=np.array([0.2, -0.3, 0.5, 0.1, -0.2, 0.3]), target_position=(20.0, 0.0, 4.0))
-    orc.load_state_words(env._vec.get_state().cpu().numpy().view(np.uint32))
+    orc.load_state_words(words(env._vec))
     J = env.scene.joints
     J[0].control_velocity(velocity=0.8, max_force=(30.0 if inertia_scaled else 900.0))
     orc.set_joint_motor(0, 1, target_velocity=0.8, max_force=(30.0 if inertia_scaled else 900.0))
@@ -484,9 +452,9 @@ def test_per_joint_motors_drive_world_step_like_the_oracle(inertia_scaled):
     J[4].control_position(-0.5)                                                     # every optional argument left to the EngineConfig
     orc.set_joint_motor(4, 0, target_position=-0.5)
     for count in range(40):
-        orc.load_dyn_words(env._vec.get_dyn_state().cpu().numpy())
+        orc.load_dyn_words(dyn_words(env._vec))
         env.world.step(); orc.world_step()
-        got = env._vec.get_dyn_state().cpu().numpy().astype(np.float64)[:12, 0]
+        got = dyn_words(env._vec).astype(np.float64)[:12, 0]
         want = np.concatenate([orc.dstate["q"][0], orc.dstate["qd"][0]])
         assert np.abs(got[:6] - want[:6]).max() <= Q_TOL and np.abs(got[6:] - want[6:]).max() <= QD_TOL, (count, got, want)
     # the motors did their job (loosely: this is a torque-limited servo on a heavy arm under gravity, 1.7 s in)

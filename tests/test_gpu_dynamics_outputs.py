@@ -4,7 +4,7 @@ dyn_rollout_kernel in all 2 x 32 instantiations <OBS_EM, ACT_EM, RAND, PHYS 0..3
 tests/test_gpu_dynamics.py compares phase A (the sub-steps: q, qd) with the float64 dynamics oracle at Q_TOL / QD_TOL.  This file
 adds phase B (dyn_finish_tile: reward, done with its float64 re-evaluation, TimeLimit, auto-reset, the row) against the
 zero-sub-step oracle of tests/dyn_outputs_ref.py, which is loaded with the engine's OWN post-step q, qd: phase A's integration
-error drops out and the kinematic suite's tolerances (tests/test_gpu_parity.py: exact linear columns, TRIG_TOL, POS_TOL, POT_TOL,
+error drops out and the kinematic suite's tolerances (tests/bars.py: exact linear columns, TRIG_TOL, POS_TOL, POT_TOL,
 REW_TOL, flags equal for every env) hold for every env.  Parity unpinned, like all of dynamics mode.
 
 Shared setup: gravity 9.81 and done_distance = 6.0, reset with explicit joints (uniform inside the limits) and targets 3 .. 9
@@ -29,14 +29,14 @@ import numpy as np
 import pytest
 import torch
 
+from bars import POS_TOL, POT_TOL, PTR_TOL, Q_TOL, QD_TOL, REW_TOL, ROLL_OBS_TOL, ROLL_REW_TOL, TRIG_TOL
 from dyn_outputs_ref import check_outputs, full_oracle, load_q_qd, merge_worst, phase_b_oracle, targets_near, worst_outputs
-from test_gpu_dynamics import Q_TOL, QD_TOL, ROLL_OBS_TOL, ROLL_REW_TOL, _record_margin
-from test_gpu_parity import POS_TOL, POT_TOL, REW_TOL, TRIG_TOL
+from gpu_support import dyn_words, engine_config_from_oracle_names, words
+from test_gpu_dynamics import _record_margin
 
 pytestmark = pytest.mark.gpu
 
 DONE_DISTANCE, AWARD_DONE = 6.0, 5.0
-PTR_TOL = 1e-3      # tests/test_gpu_dynamics.py's pointer tolerance: a 30-unit arm x 2e-5 rad
 PHYS = {
     0: dict(),
     1: dict(ground_z=8.0),
@@ -51,28 +51,15 @@ def record(case, figures):
 
 
 def make_env(n, seed, layout="env_major", act_layout="env_major", auto_reset=False, max_steps=3, done_distance=DONE_DISTANCE, **dyn):
-    """A dynamics-mode env with gravity 9.81; `dyn` in the oracle's names (tests/test_gpu_dynamics.py make)."""
-    from pioneer_amd import EngineConfig, PioneerKinematicConfig, PioneerVectorEnv, SimulationConfig
-    ek = dict(dyn)
-    eng = EngineConfig(mode="dynamic", auto_reset=auto_reset, max_episode_steps=max_steps, obs_layout=layout, action_layout=act_layout,
-                       pd_kp=ek.pop("kp", 4000.0), pd_kd=ek.pop("kd", 400.0), randomize=bool(ek.pop("randomize", 0)),
-                       joint_damping=ek.pop("joint_damping", 0.0), ground_z=ek.pop("ground_z", float("nan")),
-                       pd_inertia_scaled=bool(ek.pop("pd_inertia_scaled", 0)))
-    assert not ek
+    """A dynamics-mode env with gravity 9.81; `dyn` in the oracle's names."""
+    from pioneer_amd import PioneerKinematicConfig, PioneerVectorEnv, SimulationConfig
+    eng = engine_config_from_oracle_names(dyn, auto_reset=auto_reset, max_episode_steps=max_steps, obs_layout=layout, action_layout=act_layout)
     return PioneerVectorEnv(n, device="cuda:0", seed=seed, pioneer_config=PioneerKinematicConfig(done_distance=done_distance),
                             simulation_config=SimulationConfig(gravity=9.81), engine_config=eng)
 
 
 def orc_kw(seed, auto_reset=False, max_steps=3, done_distance=DONE_DISTANCE, **dyn):
     return dict(seed=seed, auto_reset=auto_reset, max_episode_steps=max_steps, dyn=dict(dyn, gravity=9.81), done_distance=done_distance)
-
-
-def words(env):
-    return env.get_state().cpu().numpy().view(np.uint32)
-
-
-def dynw(env):
-    return env.get_dyn_state().cpu().numpy()
 
 
 def rows(env, obs):
@@ -100,7 +87,7 @@ def start(n, seed, rng_seed, envs, orcs, lo=3.0, hi=9.0):
     obs = [e.reset(joint_positions=jp, target_positions=tp) for e in envs]
     oobs = [o.reset(joint_pos=jp.astype(np.float64), target_pos=tp.astype(np.float64)) for o in orcs]
     for e, ob in zip(envs, obs):
-        assert np.abs(rows(e, ob) - oobs[0]).max() < 3e-5
+        assert np.abs(rows(e, ob) - oobs[0]).max() < POS_TOL
     return rng, jp, tp
 
 
@@ -150,10 +137,10 @@ def test_step_kernel_every_instantiation_both_phases(layout, act_layout, randomi
         for t in range(5):
             act = (rng.uniform(-0.3, 0.3, (n, 6)) * env.a_max).astype(np.float32)
             pre = words(env)
-            full.load_state_words(pre); full.load_dyn_words(dynw(env))
+            full.load_state_words(pre); full.load_dyn_words(dyn_words(env))
             obs, rew, done, trunc, info = env.vector_step(dev_actions(env, act), want_info=True)
             full.step(act)
-            w = dynw(env)
+            w = dyn_words(env)
             wq, wqd, out = phase_a(w[0:6].T.astype(np.float64), w[6:12].T.astype(np.float64), full, contact)
             merge_worst(fig, {"dq": wq, "dqd": wqd, "phase_a_outside_share": out})
             pb.load_state_words(pre); pb.load_dyn_words(w)
@@ -195,7 +182,7 @@ def test_done_is_exact_inside_float32_noise_of_the_threshold_while_the_arm_moves
         env.reset(joint_positions=jp, target_positions=tp)
         if kernel == "step":
             obs, rew, done, trunc, info = env.vector_step(dev_actions(env, acts[0]), want_info=True)
-            w = dynw(env)
+            w = dyn_words(env)
             o = rows(env, obs)[None]
             assert np.array_equal(o[0][:, 0:6], w[0:6].T.astype(np.float64)) and np.array_equal(o[0][:, 90:96], w[6:12].T.astype(np.float64))
             res = o, host(rew)[0][None], host(done)[0][None], host(trunc)[0][None], host(info)[0][:, 3].astype(np.float32)[None]
@@ -273,7 +260,7 @@ def test_rollout_kernel_every_instantiation_through_the_chain(layout, act_layout
                 assert err.max() <= ROLL_OBS_TOL and rerr.max() <= ROLL_REW_TOL, (t, err.max(), rerr.max())
                 merge_worst(fig, {"twin_row": float(err.max()), "twin_rew": float(rerr.max())})
         merge_worst(fig, {"state_pot": check_state_words(env, pb)})
-        w = dynw(env)
+        w = dyn_words(env)
         assert np.array_equal(w[0:6].T.astype(np.float64), o[-1][:, 0:6]) and np.array_equal(w[6:12].T.astype(np.float64), o[-1][:, 90:96])
         assert np.array_equal(words(env)[:21], words(twin)[:21]) and np.array_equal(words(env)[22:], words(twin)[22:])
         env.close(); twin.close()
@@ -303,7 +290,7 @@ def test_success_reset_in_the_step_kernel(n, act_layout):
     fig, exempt_steps, resets, successes = {}, 0, 0, 0
     for t in range(4):
         act = (rng.uniform(-0.3, 0.3, (n, 6)) * env.a_max).astype(np.float32)
-        pre, pre_dyn = words(env), dynw(env)
+        pre, pre_dyn = words(env), dyn_words(env)
         full.load_state_words(pre); full.load_dyn_words(pre_dyn)
         obs, rew, done, trunc, info = env.vector_step(dev_actions(env, act), want_info=True)
         oobs, orew, odone, otrunc, oinfo = full.step(act, want_info=True)
@@ -318,12 +305,12 @@ def test_success_reset_in_the_step_kernel(n, act_layout):
         if t == 0 and n >= 37:
             assert 0.2 <= odone.mean() <= 0.8
         # reset envs
-        w, wd, ow = words(env), dynw(env), full.state_words()
+        w, wd, ow = words(env), dyn_words(env), full.state_words()
         assert np.array_equal(w[:21, was_reset], ow[:21, was_reset]) and np.array_equal(w[22:, was_reset], ow[22:, was_reset])
         assert np.array_equal(wd[0:35, was_reset], full.dyn_words()[0:35, was_reset])
         if was_reset.any():
             fresh = float(np.abs(got[0][was_reset] - oobs[was_reset]).max())
-            assert fresh < 3e-5
+            assert fresh < POS_TOL
             merge_worst(fig, {"fresh_row": fresh})
         dn = keep & (odone != 0)
         assert np.array_equal(got[4][dn, 2], np.full(int(dn.sum()), AWARD_DONE)) and not got[4][keep & (odone == 0), 2].any()
@@ -376,7 +363,7 @@ def test_success_reset_in_the_rollout_kernel(n, act_layout):
     keep = ~exempt
     w, tw = words(env), words(twin)
     assert np.array_equal(w[:21, keep], tw[:21, keep]) and np.array_equal(w[22:, keep], tw[22:, keep])
-    assert np.array_equal(dynw(env)[12:35, keep], dynw(twin)[12:35, keep])
+    assert np.array_equal(dyn_words(env)[12:35, keep], dyn_words(twin)[12:35, keep])
     assert successes >= 0.2 * n
     env.close(); twin.close()
     record("success_reset/rollout/n%d/%s" % (n, act_layout),
@@ -426,7 +413,7 @@ def test_joint_stops(n, kernel):
     acts[1:] = (np.where(rng.rand(T - 1, n, 6) < 0.5, -0.3, 0.3) * env.a_max).astype(np.float32)
     if kernel == "rollout":
         full.load_state_words(words(env)); noisy.load_state_words(words(env))
-        first_dyn = dynw(env)
+        first_dyn = dyn_words(env)
         obs, _, _, _ = env.rollout(dev_actions(env, acts))
         o = rows(env, obs)
     fig = {"dq": 0.0, "dqd": 0.0, "ref_noise_dq": 0.0, "ref_noise_dqd": 0.0}
@@ -434,9 +421,9 @@ def test_joint_stops(n, kernel):
     for t in range(T):
         if kernel == "step":
             full.load_state_words(words(env)); noisy.load_state_words(words(env))
-            pre_dyn = dynw(env)
+            pre_dyn = dyn_words(env)
             env.vector_step(dev_actions(env, acts[t]))
-            post = dynw(env)
+            post = dyn_words(env)
             gq, gqd = post[0:6].T, post[6:12].T
         else:
             pre_dyn = first_dyn

@@ -1,8 +1,8 @@
 """GPU tests of pnr_world_step_wrenches (PioneerVectorEnv.world_step(link_wrenches=...), the facade's apply_force / apply_torque)
 against the float64 reference of tests/external_force_ref.py, on the inputs of tests/external_force_cases.py.
 
-Bars: the project's own for a world step re-synchronised with the float64 reference, Q_TOL / QD_TOL = 5e-5 / 2e-3
-(tests/test_gpu_dynamics.py).  tests/test_external_force_cpu.py asserts that on these inputs float32 rounding alone stays within a
+Bars: the project's own for a world step re-synchronised with the float64 reference, Q_TOL / QD_TOL
+(tests/bars.py).  tests/test_external_force_cpu.py asserts that on these inputs float32 rounding alone stays within a
 quarter of them and that the wrenches move qd by more than ten times QD_TOL.  Every test prints its figures before it asserts.
 MEASURED VALUES ON AN MI355X: see DESIGN.md 3l.
 """
@@ -14,43 +14,18 @@ import torch
 
 import external_force_cases as cases
 import external_force_ref as ref
+from bars import Q_TOL, QD_TOL
+from gpu_support import bits, dev, dyn_env, dyn_words, lib as _lib, load_joints, set_motors
 
 pytestmark = pytest.mark.gpu
 
-Q_TOL, QD_TOL = cases.Q_TOL, cases.QD_TOL
-
-
-def _lib():
-    from pioneer_amd import _lib
-    return _lib
-
-
-def T(x):
-    return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32, device="cuda:0")
-
 
 def make(family, n, frame_skip=cases.FRAME_SKIP):
-    """The family's env with its motors set, reset; and its motors' dictionaries"""
-    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig
+    """The family's env with its motors set, reset"""
     f = cases.FAMILIES[family]
-    env = PioneerVectorEnv(n, device="cuda:0", seed=f["seed"], simulation_config=SimulationConfig(gravity=f["gravity"], frame_skip=frame_skip),
-                           engine_config=EngineConfig(mode="dynamic", auto_reset=False, max_episode_steps=0, **f["engine"]))
-    env.reset()
-    for j, m in enumerate(f["motors"]):
-        if m is not None:
-            env.set_joint_motor(j, m["control_mode"], target_position=m.get("target_position", 0.0), target_velocity=m["target_velocity"],
-                                position_gain=m["position_gain"], velocity_gain=m["velocity_gain"], max_force=m["max_force"])
+    env = dyn_env(n, f["seed"], f["gravity"], frame_skip, **f["engine"])
+    set_motors(env, f["motors"])
     return env
-
-
-def dyn(env):
-    return env.get_dyn_state().cpu().numpy()
-
-
-def load(env, q, qd):
-    d = env.get_dyn_state()
-    d[0:6], d[6:12] = T(np.asarray(q).T), T(np.asarray(qd).T)
-    env.set_dyn_state(d)
 
 
 def command_r(env):
@@ -61,12 +36,8 @@ def command_r(env):
 def scenario(family, env):
     """(q, qd, wrenches, torques) of the family for this env's batch, loaded into the env"""
     q, qd = cases.states(family, command_r(env))
-    load(env, q, qd)
+    load_joints(env, q, qd)
     return q, qd, cases.wrenches(family, q), cases.joint_torques(family, env.num_envs)
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 # ---- 6. against the reference ---------------------------------------------------------------------------------------------------
@@ -82,13 +53,13 @@ def test_world_step_wrenches_against_the_reference(n, family):
     words = env.get_state().cpu().numpy().view(np.uint32)[:, idx]
     orc.load_state_words(words); plain.load_state_words(words)
     q, qd, w, tau = scenario(family, env)
-    wt, tq = T(w), T(tau)
+    wt, tq = dev(w), dev(tau)
     worst_q = worst_qd = 0.0
     for with_tau in (False, True):
         for hold in cases.HOLDS:
-            load(env, q, qd)
+            load_joints(env, q, qd)
             for step in range(cases.STEPS):
-                d = dyn(env)[:, idx]
+                d = dyn_words(env)[:, idx]
                 orc.load_dyn_words(d)
                 if step == 0 and cases.PHYS[family] & 1:
                     share = np.mean([orc.contact_wrenches(e)[0] for e in range(orc.n)])
@@ -101,7 +72,7 @@ def test_world_step_wrenches_against_the_reference(n, family):
                     effect = np.abs(orc.dstate["qd"] - plain.dstate["qd"]).max()
                     assert n < 37 or effect > 10 * QD_TOL, effect
                 env.world_step(joint_torques=tq if with_tau else None, link_wrenches=(f["specs"], wt), hold_substeps=hold)
-                e = dyn(env)[:, idx].astype(np.float64)
+                e = dyn_words(env)[:, idx].astype(np.float64)
                 dq, dqd = np.abs(e[0:6].T - orc.dstate["q"]).max(), np.abs(e[6:12].T - orc.dstate["qd"]).max()
                 worst_q, worst_qd = max(worst_q, dq), max(worst_qd, dqd)
                 print(f"family {family} n={n} torques={with_tau} hold={hold} step={step}: |dq| {dq:.3e} of {Q_TOL:.1e}, |dqd| {dqd:.3e} of {QD_TOL:.1e}")
@@ -124,15 +95,15 @@ def test_a_wrench_steps_like_its_jacobian_torques(frame):
     for link in range(0, 11):
         q, world, local = cases.same_wrench_both_frames(n, link, point=point, scale=cases.LINK_WRENCH_SCALE.get(link, 1.0))
         for env in (a, b, c):
-            load(env, q, qd)
+            load_joints(env, q, qd)
         J = a.jacobian(link=link, local_point=point).double()
-        wr = T(world if frame == "world" else local)
-        F, Tq = T(world[:, 0, 0:3]).double(), T(world[:, 0, 6:9]).double()   # the world force and torque
+        wr = dev(world if frame == "world" else local)
+        F, Tq = dev(world[:, 0, 0:3]).double(), dev(world[:, 0, 6:9]).double()   # the world force and torque
         tau = torch.einsum("nij,ni->nj", J[:, 0:3], F) + torch.einsum("nij,ni->nj", J[:, 3:6], Tq)
         a.world_step(link_wrenches=([(link, frame)], wr))
         b.world_step(joint_torques=tau.float())
         c.world_step(joint_torques=zero)
-        da, db, dc = (dyn(e).astype(np.float64) for e in (a, b, c))
+        da, db, dc = (dyn_words(e).astype(np.float64) for e in (a, b, c))
         effect = np.abs(db[6:12] - dc[6:12]).max(axis=0)
         dq, dqd = np.abs(da[0:6] - db[0:6]).max(), np.abs(da[6:12] - db[6:12]).max()
         print(f"wrench vs J^T [F; T] on the GPU, frame {frame}, link {link}: |dq| {dq:.3e} of {Q_TOL:.1e}, |dqd| {dqd:.3e} of {QD_TOL:.1e}; "
@@ -152,13 +123,13 @@ def test_zero_wrenches_step_like_zero_torques(family):
     f = cases.FAMILIES[family]
     a, b = make(family, n), make(family, n)
     q, qd, w, _ = scenario(family, a)
-    load(b, q, qd)
-    zero_w, zero_t = torch.zeros_like(T(w)), torch.zeros((n, 6), device="cuda:0")
+    load_joints(b, q, qd)
+    zero_w, zero_t = torch.zeros_like(dev(w)), torch.zeros((n, 6), device="cuda:0")
     for step in range(cases.STEPS):
         b.set_dyn_state(a.get_dyn_state())
         a.world_step(joint_torques=zero_t)
         b.world_step(link_wrenches=(f["specs"], zero_w))
-        da, db = dyn(a).astype(np.float64), dyn(b).astype(np.float64)
+        da, db = dyn_words(a).astype(np.float64), dyn_words(b).astype(np.float64)
         dq, dqd = np.abs(da[0:6] - db[0:6]).max(), np.abs(da[6:12] - db[6:12]).max()
         print(f"zero wrenches family {family} step={step}: |dq| {dq:.3e} |dqd| {dqd:.3e} bit-equal {np.array_equal(da, db)}")
         assert dq <= Q_TOL and dqd <= QD_TOL
@@ -172,7 +143,7 @@ def test_an_env_computes_the_same_bits_whatever_the_batch():
     env = make(family, n)
     q, qd, w, tau = scenario(family, env)
     words, d0 = env.get_state().clone(), env.get_dyn_state().clone()
-    wt, tq = T(w), T(tau)
+    wt, tq = dev(w), dev(tau)
     for _ in range(cases.STEPS):
         env.world_step(joint_torques=tq, link_wrenches=(f["specs"], wt), hold_substeps=4)
     got = env.get_dyn_state().clone()
@@ -197,7 +168,7 @@ def test_inputs_and_the_other_planes_are_left_alone():
     f = cases.FAMILIES[family]
     env = make(family, n)
     q, qd, w, tau = scenario(family, env)
-    wt, tq = T(w), T(tau)
+    wt, tq = dev(w), dev(tau)
     w0, t0 = wt.clone(), tq.clone()
     words, d0 = env.get_state().clone(), env.get_dyn_state().clone()
     env.world_step(joint_torques=tq, link_wrenches=(f["specs"], wt))
@@ -283,7 +254,7 @@ def test_graph_capture_replays_the_eager_result():
     env = make(family, n)
     q, qd, w, tau = scenario(family, env)
     d0 = env.get_dyn_state().clone()
-    wt, tq = T(w), T(tau)
+    wt, tq = dev(w), dev(tau)
     s = torch.cuda.Stream(device=env.device)
     s.wait_stream(torch.cuda.current_stream(env.device))
     g = torch.cuda.CUDAGraph()

@@ -20,7 +20,7 @@ import pytest
 import torch
 
 import ppo_loss_ref as ref
-from test_gpu_mlp import _unpack_flat, make
+from gpu_support import mlp_make as make, unpack_flat as _unpack_flat
 
 pytestmark = pytest.mark.gpu
 SENTINEL = -777.25

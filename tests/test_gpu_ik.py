@@ -10,12 +10,11 @@ import torch
 
 import ik_ref
 import link_kinematics_ref as lk
-from env_joints import dyn_joints, kin_joints
+from gpu_support import LIMITS, dyn_joints, kin_joints
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 37, 64, 1000]
-LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416], dtype=np.float32)
 LOCAL_POINT = (0.3, -0.2, 0.5)
 INNER_LO, INNER_HI = (15.0, -8.0, 2.0), (22.0, 8.0, 6.0)
 FK_TOL = 3e-5            # the existing forward-kinematics bound (test_gpu_link_states.py)

@@ -24,12 +24,12 @@ UP_LOW = ((18.0, 0.0, 4.0), (0.0, -1.0, 0.0, 1.0))        # the pointer straight
 FAR = ((40.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0))            # the links' lengths add up to 30.07
 
 
-def T(a):
+def host_tensor(a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a))
 
 
 def solve(env, quat, pos, start=None, **kw):
-    return [t.cpu().numpy() for t in env.solve_ik_pose(T(quat), T(pos), T(start), **kw)]
+    return [t.cpu().numpy() for t in env.solve_ik_pose(host_tensor(quat), host_tensor(pos), host_tensor(start), **kw)]
 
 
 def check_converged(env, q, res, ang, its, pos, quat, mode, want_its):
@@ -84,7 +84,7 @@ def test_every_near_pose_converges_with_the_defaults(n):
     from pioneer_amd import PioneerVectorEnv
     env = PioneerVectorEnv(n, device="cuda:0", seed=2)
     pos, quat, start, _ = ref.near_set(n, ref.NEAR_SEED(n))
-    out = env.solve_ik_pose(T(quat), T(pos), T(start))
+    out = env.solve_ik_pose(host_tensor(quat), host_tensor(pos), host_tensor(start))
     assert [tuple(t.shape) for t in out] == [(n, 6), (n,), (n,), (n,)]
     assert [t.dtype for t in out] == [torch.float32, torch.float32, torch.float32, torch.int32]
     q, res, ang, its = (t.cpu().numpy() for t in out)
@@ -103,7 +103,7 @@ def test_every_point_target_converges_in_axis_mode_from_the_rest_pose(n):
     want_its = ref.solve_ik_pose(pos, quat, None, mode=ref.AXIS)[3]
     check_converged(env, q, res, ang, its, pos, quat, ref.AXIS, want_its)
     # the same through the env's own targets (target=None) and an axis of another length
-    env.reset(target_positions=T(pos))
+    env.reset(target_positions=host_tensor(pos))
     q2, res2, ang2, its2 = solve(env, quat, None, align_axis=(2.5, 0.0, 0.0))
     assert np.array_equal(q, q2) and np.array_equal(res, res2) and np.array_equal(ang, ang2) and np.array_equal(its, its2)
     env.close()
@@ -153,10 +153,10 @@ def test_an_envs_result_does_not_depend_on_the_batch_around_it():
     quat[bad & (pos[:, 0] == 18.0)] = UP_LOW[1]
     start[rng.random(n) < 0.3] = 0.0                                            # and with rest-pose starts
     env = PioneerVectorEnv(n, device="cuda:0", seed=2)
-    base = [t.cpu() for t in env.solve_ik_pose(T(quat), T(pos), T(start))]
+    base = [t.cpu() for t in env.solve_ik_pose(host_tensor(quat), host_tensor(pos), host_tensor(start))]
     assert len(np.unique(base[3].numpy())) >= 4                                 # the lanes of a wave stop at different times
     perm = rng.permutation(n)
-    moved = [t.cpu() for t in env.solve_ik_pose(T(quat[perm]), T(pos[perm]), T(start[perm]))]
+    moved = [t.cpu() for t in env.solve_ik_pose(host_tensor(quat[perm]), host_tensor(pos[perm]), host_tensor(start[perm]))]
     for a, b in zip(base, moved):
         assert torch.equal(a[torch.from_numpy(perm)], b)
     env.close()
@@ -164,7 +164,7 @@ def test_an_envs_result_does_not_depend_on_the_batch_around_it():
     its = base[3].numpy()
     slow = int(np.argmax(np.where(its < 32, its, -1)))                          # the slowest env that did converge
     for k in (0, 63, 64, 517, 999, slow, int(np.argmax(its))):
-        alone = [t.cpu() for t in one.solve_ik_pose(T(quat[k:k + 1]), T(pos[k:k + 1]), T(start[k:k + 1]))]
+        alone = [t.cpu() for t in one.solve_ik_pose(host_tensor(quat[k:k + 1]), host_tensor(pos[k:k + 1]), host_tensor(start[k:k + 1]))]
         for a, b in zip(base, alone):
             assert torch.equal(a[k:k + 1], b), k
     one.close()
@@ -180,7 +180,7 @@ def test_bad_arguments_are_refused_and_leave_the_output_alone():
     ang = torch.full((n + 2,), -7.25, dtype=torch.float32, device=env.device)
     its = torch.full((n + 2,), -7, dtype=torch.int32, device=env.device)
     pos_np, quat_np, start_np, _ = ref.near_set(n, ref.NEAR_SEED(n))
-    tgt, quat, start = T(pos_np).cuda(), T(quat_np).cuda(), T(start_np).cuda()
+    tgt, quat, start = host_tensor(pos_np).cuda(), host_tensor(quat_np).cuda(), host_tensor(start_np).cuda()
     P = lambda t, off=0: C.c_void_p(t.data_ptr() + off)  # noqa: E731
 
     def params(**kw):
@@ -258,7 +258,7 @@ def test_graph_capture_replays_the_eager_result():
     n = 64
     env = PioneerVectorEnv(n, device="cuda:0", seed=6)
     pos, quat, start, _ = ref.near_set(n, 5)
-    pos, quat, start = T(pos).cuda(), T(quat).cuda(), T(start).cuda()
+    pos, quat, start = host_tensor(pos).cuda(), host_tensor(quat).cuda(), host_tensor(start).cuda()
     out = {"q": torch.empty((n, 6), device=env.device), "residual": torch.empty(n, device=env.device),
            "angle": torch.empty(n, device=env.device), "iterations": torch.empty(n, dtype=torch.int32, device=env.device)}
     s = torch.cuda.Stream(device=env.device)
@@ -271,7 +271,7 @@ def test_graph_capture_replays_the_eager_result():
             env.solve_ik_pose(quat, pos, start, out=out)
     torch.cuda.synchronize()
     pos2, quat2, start2, _ = ref.near_set(n, 6)
-    pos.copy_(T(pos2)); quat.copy_(T(quat2)); start.copy_(T(start2))
+    pos.copy_(host_tensor(pos2)); quat.copy_(host_tensor(quat2)); start.copy_(host_tensor(start2))
     for t in out.values():
         t.fill_(-1)
     g.replay()

@@ -2,7 +2,7 @@
 world_step(joint_torques=...) and the facade's Joint.control_torque) against the float64 reference of
 tests/inverse_dynamics_ref.py, on the inputs of tests/inverse_dynamics_cases.py.
 
-Bars.  HARD (the project's own, tests/test_gpu_dynamics.py): a world step re-synchronised with the float64 reference agrees to
+Bars.  HARD (the project's own, tests/bars.py): a world step re-synchronised with the float64 reference agrees to
 Q_TOL / QD_TOL; an acceleration error below QD_TOL / step_time = 0.048 rad/s^2 cannot move a world step outside QD_TOL, so the
 engine's torques, fed to the float64 forward dynamics, must give back qdd to that, and the mass matrix must satisfy
 |M_ref^-1 (M - M_ref)|_inf x 20 <= the same (20: the largest |qdd| here).  TIGHT: FLOOR_MARGIN = 8 times what float32 arithmetic
@@ -18,11 +18,12 @@ import torch
 
 import inverse_dynamics_cases as cases
 import inverse_dynamics_ref as ref
+from bars import Q_TOL, QD_TOL
+from gpu_support import dev, dyn_env, dyn_words, f64, kin_env, lib as _lib, load_joints
 from oracle import DynOracle
 
 pytestmark = pytest.mark.gpu
 
-Q_TOL, QD_TOL = 5e-5, 2e-3                                            # tests/test_gpu_dynamics.py
 HARD_ACC = QD_TOL / cases.STEP_TIME                                   # 0.048 rad/s^2
 SIZES = [1, 37, 64, 1000]
 SENTINEL = -7.25
@@ -30,41 +31,12 @@ TIGHT_TAU = cases.FLOOR_MARGIN * cases.TAU_FLOOR
 TIGHT_M = cases.FLOOR_MARGIN * cases.M_FLOOR
 
 
-def _lib():
-    from pioneer_amd import _lib
-    return _lib
-
-
-def T(x):
-    return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32, device="cuda:0")
-
-
 def make_dyn(n, gravity=9.81, frame_skip=10, seed=cases.SEED, **eng):
-    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig
-    env = PioneerVectorEnv(n, device="cuda:0", seed=seed, simulation_config=SimulationConfig(gravity=gravity, frame_skip=frame_skip),
-                           engine_config=EngineConfig(mode="dynamic", auto_reset=False, max_episode_steps=0, **eng))
-    env.reset()
-    return env
+    return dyn_env(n, seed, gravity, frame_skip, **eng)
 
 
 def make_kin(n, gravity=9.81, reset=True, **eng):
-    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig
-    env = PioneerVectorEnv(n, device="cuda:0", seed=cases.SEED, simulation_config=SimulationConfig(gravity=gravity),
-                           engine_config=EngineConfig(**eng))
-    if reset:
-        env.reset()
-    return env
-
-
-def load(env, q, qd=None):
-    d = env.get_dyn_state()
-    d[0:6] = T(np.asarray(q).T)
-    d[6:12] = 0.0 if qd is None else T(np.asarray(qd).T)
-    env.set_dyn_state(d)
-
-
-def dyn(env):
-    return env.get_dyn_state().cpu().numpy()
+    return kin_env(n, cases.SEED, reset, sim=dict(gravity=gravity), **eng)
 
 
 def free_joints(env):
@@ -77,14 +49,10 @@ def free_joints(env):
 def oracle_of(env, gravity, q=None, qd=None):
     """The float64 oracle with the env's own per-env parameters (and, unless given, its simulated joints)."""
     orc = DynOracle(env.num_envs, dyn=dict(gravity=gravity))
-    orc.load_dyn_words(dyn(env))
+    orc.load_dyn_words(dyn_words(env))
     if q is not None:
         ref.set_states(orc, np.asarray(q, dtype=np.float64), np.asarray(qd, dtype=np.float64))
     return orc
-
-
-def f64(t):
-    return t.double().cpu().numpy()
 
 
 # ---- 1. inverse dynamics against the reference ----------------------------------------------------------------------------------
@@ -96,14 +64,14 @@ def _source(kind, n, gravity):
         orc = cases.make_oracle(n, gravity, False, joint_damping=0.1, joint_friction=0.1)
         ref.set_states(orc, q.astype(np.float64), qd.astype(np.float64))
         assert np.all(orc.dstate["mass_scale"] == 1.0) and np.allclose(orc.dstate["damping"], 0.1, rtol=1e-7, atol=0)
-        return env, orc, T(np.concatenate([q, qd], axis=1)), qdd
+        return env, orc, dev(np.concatenate([q, qd], axis=1)), qdd
     env = make_dyn(n, gravity, randomize=True)
     if kind == "dynamic_buffer":                                      # the handle's per-env scales under a caller's joints
         orc = oracle_of(env, gravity, q, qd)
         assert orc.dstate["mass_scale"].min() < 0.75 or n < 8
-        return env, orc, T(np.concatenate([q, qd], axis=1)), qdd
+        return env, orc, dev(np.concatenate([q, qd], axis=1)), qdd
     assert kind == "dynamic_own"                                      # the handle's own simulated joints after two free world steps
-    load(env, q, qd)
+    load_joints(env, q, qd)
     free_joints(env)
     env.world_step(); env.world_step()
     return env, oracle_of(env, gravity), None, qdd
@@ -115,7 +83,7 @@ def _source(kind, n, gravity):
 def test_inverse_dynamics_against_the_reference(n, kind, gravity):
     env, orc, js, qdd = _source(kind, n, gravity)
     before = None if js is None else js.clone()
-    acc = T(qdd)
+    acc = dev(qdd)
     qdd64 = qdd.astype(np.float64)
     M, _, _ = ref.mass_and_bias(orc, 0.0)
     bias = {g: ref.mass_and_bias(orc, g)[2] for g in {0.0, gravity}}
@@ -167,7 +135,7 @@ def test_mass_matrix_against_the_reference(n, kind):
     assert np.all(tight <= TIGHT_M), tight / TIGHT_M
     # consistency on the device alone: inverse_dynamics(qdd) - inverse_dynamics(None) = M qdd.  Two torques within TIGHT_TAU each
     # and a matrix within TIGHT_M against |qdd| <= 20: the sum of the bars
-    acc = T(qdd)
+    acc = dev(qdd)
     lhs = f64(env.inverse_dynamics(acc, js)) - f64(env.inverse_dynamics(None, js))
     rhs = np.einsum("nij,nj->ni", M, qdd.astype(np.float64))
     bar = 2.0 * TIGHT_TAU + TIGHT_M @ np.full(6, 20.0)
@@ -184,7 +152,7 @@ def test_mass_matrix_against_the_reference(n, kind):
 def _hold_env(n):
     env = make_dyn(n, 9.81, seed=cases.HOLD_SEED, randomize=True, rand_friction=(0.0, 0.0), rand_damping=(0.0, 0.0))
     free_joints(env)
-    load(env, cases.hold_poses(n))
+    load_joints(env, cases.hold_poses(n))
     return env
 
 
@@ -194,14 +162,14 @@ def test_gravity_compensation_holds_the_pose():
     0.24 rad and float32-rounded reference torques drift 2.5e-7 rad: 1 % of the fall leaves four orders to a correct kernel."""
     n, steps = 64, 24
     hold, fall = _hold_env(n), _hold_env(n)
-    q0 = dyn(hold)[0:6].astype(np.float64)
-    assert np.array_equal(q0, dyn(fall)[0:6].astype(np.float64))
+    q0 = dyn_words(hold)[0:6].astype(np.float64)
+    assert np.array_equal(q0, dyn_words(fall)[0:6].astype(np.float64))
     drift, moved = np.zeros(n), np.zeros(n)
     for _ in range(steps):
         hold.world_step(joint_torques=hold.inverse_dynamics())
         fall.world_step(joint_torques=torch.zeros((n, 6), device="cuda:0"))
-        drift = np.maximum(drift, np.abs(dyn(hold)[0:6] - q0).max(axis=0))
-        moved = np.maximum(moved, np.abs(dyn(fall)[0:6] - q0).max(axis=0))
+        drift = np.maximum(drift, np.abs(dyn_words(hold)[0:6] - q0).max(axis=0))
+        moved = np.maximum(moved, np.abs(dyn_words(fall)[0:6] - q0).max(axis=0))
     print(f"gravity hold: smallest free-fall displacement {moved.min():.4f} rad, largest hold drift {drift.max():.3e} rad")
     assert moved.min() >= 0.1, "without the torque every arm must fall"
     assert drift.max() <= 0.01 * moved.min()
@@ -215,12 +183,12 @@ def test_computed_torque_realises_the_acceleration(n):
     env = make_dyn(n, 9.81, frame_skip=1, randomize=True, rand_damping=(0.5, 0.5), rand_friction=(0.2, 0.2))
     free_joints(env)
     q, qd, qdd = cases.joints(n, frac=0.8)                            # 0.2 x the limit (>= 0.26 rad) from a limit; two sub-steps move 0.025
-    load(env, q, qd)
-    d0 = dyn(env)
+    load_joints(env, q, qd)
+    d0 = dyn_words(env)
     assert np.all(d0[23:29] == np.float32(0.2)) and np.all(d0[29:35] == np.float32(0.5))
-    tau = env.inverse_dynamics(T(qdd), joint_losses=True)
+    tau = env.inverse_dynamics(dev(qdd), joint_losses=True)
     env.world_step(joint_torques=tau)
-    got = dyn(env)[6:12].T.astype(np.float64)
+    got = dyn_words(env)[6:12].T.astype(np.float64)
     want = qd.astype(np.float64) + cases.H * qdd.astype(np.float64)
     err = np.abs(got - want).max()
     print(f"computed torque n={n}: |qd+ - (qd + h qdd*)| {err:.3e} of {QD_TOL:.1e}; h |qdd*| max {cases.H * np.abs(qdd).max():.3f}")
@@ -248,15 +216,15 @@ def test_world_step_torques_against_the_reference(n):
     dynamics per env and sub-step) follows every 8th env and the whole partial last wave; the engine steps all of them."""
     env = _torque_env(n)
     q, qd, tau = cases.torque_scenario(n)
-    load(env, q, qd)
+    load_joints(env, q, qd)
     law = cases.PD_KP * (np.array(cases.PD_TARGETS) - q[:, :3]) - cases.PD_KD * qd[:, :3]
     assert (np.abs(law) > np.array(cases.PD_FORCES)).mean() > 0.5, "the motors' caps must be active"
     idx = np.arange(n) if n <= 64 else np.array([e for e in range(n) if e % 8 == 0 or e >= (n // 64) * 64])
     orc, plain = cases.torque_oracle(len(idx)), cases.torque_oracle(len(idx))
-    tq = T(tau)
+    tq = dev(tau)
     worst_q = worst_qd = 0.0
     for step in range(10):
-        d = dyn(env)[:, idx]
+        d = dyn_words(env)[:, idx]
         orc.load_dyn_words(d)
         ref.world_step_torques(orc, cases.TORQUE_MOTORS, tau[idx])
         if step == 0:                                                 # not vacuous: the torques matter at 10 x the bar
@@ -266,7 +234,7 @@ def test_world_step_torques_against_the_reference(n):
             print(f"torque step n={n}: the torques change qd by {effect:.3e}")
             assert effect > 10 * QD_TOL
         env.world_step(joint_torques=tq)
-        e = dyn(env)[:, idx].astype(np.float64)
+        e = dyn_words(env)[:, idx].astype(np.float64)
         dq, dqd = np.abs(e[0:6].T - orc.dstate["q"]).max(), np.abs(e[6:12].T - orc.dstate["qd"]).max()
         worst_q, worst_qd = max(worst_q, dq), max(worst_qd, dqd)
         print(f"torque step n={n} step={step}: |dq| {dq:.3e} of {Q_TOL:.1e}, |dqd| {dqd:.3e} of {QD_TOL:.1e}")
@@ -279,13 +247,13 @@ def test_world_step_torques_against_the_reference(n):
 def test_zero_torques_step_like_the_plain_world_step(n):
     a, b = _torque_env(n), _torque_env(n)
     q, qd, _ = cases.torque_scenario(n)
-    load(a, q, qd); load(b, q, qd)
+    load_joints(a, q, qd); load_joints(b, q, qd)
     zero = torch.zeros((n, 6), device="cuda:0")
     for step in range(5):
         b.set_dyn_state(a.get_dyn_state())
         a.world_step()
         b.world_step(joint_torques=zero)
-        da, db = dyn(a).astype(np.float64), dyn(b).astype(np.float64)
+        da, db = dyn_words(a).astype(np.float64), dyn_words(b).astype(np.float64)
         dq, dqd = np.abs(da[0:6] - db[0:6]).max(), np.abs(da[6:12] - db[6:12]).max()
         print(f"zero torques n={n} step={step}: |dq| {dq:.3e} |dqd| {dqd:.3e} bit-equal {np.array_equal(da, db)}")
         assert dq <= Q_TOL and dqd <= QD_TOL
@@ -298,9 +266,9 @@ def test_an_env_computes_the_same_bits_whatever_the_batch():
     env = _torque_env(n)
     q, qd, tau = cases.torque_scenario(n)
     _, _, qdd = cases.joints(n)
-    load(env, q, qd)
+    load_joints(env, q, qd)
     words, d0 = env.get_state().clone(), env.get_dyn_state().clone()
-    tq, acc = T(tau), T(qdd)
+    tq, acc = dev(tau), dev(qdd)
     idt = env.inverse_dynamics(acc, joint_losses=True).clone()
     M = env.mass_matrix().clone()
     for _ in range(3):
@@ -394,9 +362,9 @@ def test_graph_capture_replays_the_eager_result():
     env = _torque_env(n)
     q, qd, _ = cases.torque_scenario(n)
     _, _, qdd = cases.joints(n)
-    load(env, q, qd)
+    load_joints(env, q, qd)
     d0 = env.get_dyn_state().clone()
-    acc = T(0.1 * qdd)
+    acc = dev(0.1 * qdd)
     tau = torch.empty((n, 6), device="cuda:0")
     s = torch.cuda.Stream(device=env.device)
     s.wait_stream(torch.cuda.current_stream(env.device))

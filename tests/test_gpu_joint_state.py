@@ -14,6 +14,8 @@ import constraint_motor_cases as ccases
 import external_force_cases as xcases
 import joint_state_cases as cases
 import joint_state_ref as ref
+from bars import QD_TOL
+from gpu_support import bits, dev, dyn_env, dyn_words, lib as _lib, load_joints, set_motors, words
 
 pytestmark = pytest.mark.gpu
 
@@ -22,54 +24,11 @@ SENTINEL = -7.25
 FORMS = {"ext": (True, True), "wrench": (True, False), "torque": (False, True), "plain": (False, False)}
 
 
-def _lib():
-    from pioneer_amd import _lib
-    return _lib
-
-
-def T(x):
-    return torch.as_tensor(np.ascontiguousarray(x), dtype=torch.float32, device="cuda:0")
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def dyn(env):
-    return env.get_dyn_state().cpu().numpy()
-
-
-def load(env, q, qd):
-    d = env.get_dyn_state()
-    d[0:6], d[6:12] = T(np.asarray(q).T), T(np.asarray(qd).T)
-    env.set_dyn_state(d)
-
-
-def make_env(n, seed, gravity, frame_skip, **eng):
-    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig
-    env = PioneerVectorEnv(n, device="cuda:0", seed=seed, simulation_config=SimulationConfig(gravity=gravity, frame_skip=frame_skip),
-                           engine_config=EngineConfig(mode="dynamic", auto_reset=False, max_episode_steps=0, **eng))
-    env.reset()
-    return env
-
-
-def set_motors(env, motors):
-    L = _lib()
-    modes = {"velocity_constraint": L.CONTROL_VELOCITY_CONSTRAINT, "position_constraint": L.CONTROL_POSITION_CONSTRAINT}
-    for j, m in enumerate(motors):
-        if m is None:
-            continue
-        mode = modes.get(m["kind"])
-        if mode is None:
-            mode = L.CONTROL_VELOCITY if m["control_mode"] == 1 else L.CONTROL_POSITION
-        env.set_joint_motor(j, mode, **{k: v for k, v in m.items() if k not in ("kind", "control_mode")})
-
-
 def scenario(name, n, frame_skip=None):
     """(env, inputs for the whole batch as device tensors and arrays) of a family, `hold` or a constraint case, its states loaded"""
     if name in cases.CONSTRAINT:
         c = ccases.CASES[name]
-        env = make_env(n, c["seed"], ccases.GRAVITY, c["frame_skip"], **c["engine"])
+        env = dyn_env(n, c["seed"], ccases.GRAVITY, c["frame_skip"], **c["engine"])
         for act in ccases.command_actions(name, n, env.a_max):
             env.vector_step(torch.from_numpy(act).cuda())
         set_motors(env, c["motors"])
@@ -77,20 +36,20 @@ def scenario(name, n, frame_skip=None):
         I = dict(motors=c["motors"], specs=(), wrenches=None, tau=None)
     elif name == "hold":
         from inverse_dynamics_cases import HOLD_SEED
-        env = make_env(n, HOLD_SEED, 9.81, frame_skip or 10, randomize=True, rand_friction=(0.0, 0.0), rand_damping=(0.0, 0.0))
+        env = dyn_env(n, HOLD_SEED, 9.81, frame_skip or 10, randomize=True, rand_friction=(0.0, 0.0), rand_damping=(0.0, 0.0))
         orc = cases.hold_oracle(n)
-        assert np.array_equal(dyn(env)[12:35], orc.dyn_words()[12:35]), "the engine's link draws are the oracle's"
+        assert np.array_equal(dyn_words(env)[12:35], orc.dyn_words()[12:35]), "the engine's link draws are the oracle's"
         _, I = cases.hold_inputs(n, orc)
         set_motors(env, I["motors"])
         q, qd = I["q"], I["qd"]
     else:
         f = xcases.FAMILIES[name]
-        env = make_env(n, f["seed"], f["gravity"], frame_skip or xcases.FRAME_SKIP, **f["engine"])
+        env = dyn_env(n, f["seed"], f["gravity"], frame_skip or xcases.FRAME_SKIP, **f["engine"])
         set_motors(env, f["motors"])
         r_cmd = env.get_state().view(torch.float32)[12:18].T.cpu().numpy()
         q, qd = xcases.states(name, r_cmd)
         I = dict(motors=f["motors"], specs=f["specs"], wrenches=xcases.wrenches(name, q), tau=xcases.joint_torques(name, n))
-    load(env, q, qd)
+    load_joints(env, q, qd)
     I.update(q=q, qd=qd)
     return env, I
 
@@ -105,14 +64,14 @@ def reference(name, n, form, env, I):
         idx = cases.followed(n)
         if name in cases.CONSTRAINT:
             orc = ccases.make_oracle(name, n)
-            assert np.array_equal(env.get_state().cpu().numpy().view(np.uint32)[:21], orc.state_words()[:21])
+            assert np.array_equal(words(env)[:21], orc.state_words()[:21])
             assert n <= 64
         elif name == "hold":
             orc = cases.hold_oracle(len(idx))
         else:
             orc = xcases.make_oracle(name, len(idx), reset=False)
-        orc.load_state_words(env.get_state().cpu().numpy().view(np.uint32)[:, idx])
-        orc.load_dyn_words(dyn(env)[:, idx])
+        orc.load_state_words(words(env)[:, idx])
+        orc.load_dyn_words(dyn_words(env)[:, idx])
         sub = {k: (v[idx] if isinstance(v, np.ndarray) else v) for k, v in I.items()}
         R = cases.reference(orc, sub, *FORMS[form])
         R["room"] = cases.clamp_room(orc, sub, R["qdd"])
@@ -123,8 +82,8 @@ def reference(name, n, form, env, I):
 
 def query(env, I, form, **kw):
     with_w, with_t = FORMS[form]
-    return env.joint_states(joint_torques=T(I["tau"]) if with_t else None,
-                            link_wrenches=(I["specs"], T(I["wrenches"])) if with_w else None, **kw)
+    return env.joint_states(joint_torques=dev(I["tau"]) if with_t else None,
+                            link_wrenches=(I["specs"], dev(I["wrenches"])) if with_w else None, **kw)
 
 
 def against_the_reference(name, n, form):
@@ -185,7 +144,7 @@ def test_constraint_motors_velocities_and_the_sweep_at_the_kernels_own_accelerat
     dv = H * np.abs(joints[:, :, 2] - R["qdd"])
     dtau = joints[:, :, 3] - R["tau_motor"]
     dvt = H * np.abs(np.einsum("nij,nj->ni", R["Minv"], dtau))
-    print(f"{case} n={n}: h |dqdd| {dv.max():.3e}, h |M^-1 dtau| {dvt.max():.3e} of {cases.QD_TOL:.1e}; |dtau| {np.abs(dtau).max():.3e} at "
+    print(f"{case} n={n}: h |dqdd| {dv.max():.3e}, h |M^-1 dtau| {dvt.max():.3e} of {QD_TOL:.1e}; |dtau| {np.abs(dtau).max():.3e} at "
           f"torques up to {np.abs(R['tau_motor']).max():.3e}")
     at = ref.newton_euler_reaction(I["q"], I["qd"], joints[:, :, 2], R["scales"], R["gravity"], R["fext"])
     F = cases.REACTION_AT_QDD[case]["plain"]["free"]
@@ -193,7 +152,7 @@ def test_constraint_motors_velocities_and_the_sweep_at_the_kernels_own_accelerat
     ef, em = np.abs(gf - rf).max(axis=2), np.abs(gm - rm).max(axis=2)
     print(f"{case} n={n}: f(q, qd, the kernel's qdd): force error / bar {(ef / (cases.FLOOR_MARGIN * F['force'])).max():.3f}, "
           f"moment error / bar {(em / (cases.FLOOR_MARGIN * F['moment'])).max():.3f}")
-    assert dv.max() <= cases.QD_TOL and dvt.max() <= cases.QD_TOL
+    assert dv.max() <= QD_TOL and dvt.max() <= QD_TOL
     assert np.all(ef <= cases.FLOOR_MARGIN * F["force"]) and np.all(em <= cases.FLOOR_MARGIN * F["moment"])
     env.close()
 
@@ -210,8 +169,8 @@ def test_the_step_integrates_the_acceleration_the_query_showed(family):
     joints = query(env, I, "ext", reaction=False)["joints"].double().cpu().numpy()
     torch.cuda.synchronize()
     assert torch.equal(bits(env.get_state()), bits(before[0])) and torch.equal(bits(env.get_dyn_state()), bits(before[1]))
-    env.world_step(joint_torques=T(I["tau"]), link_wrenches=(I["specs"], T(I["wrenches"])))
-    qd0, qd1 = I["qd"].astype(np.float64), dyn(env)[6:12].T.astype(np.float64)
+    env.world_step(joint_torques=dev(I["tau"]), link_wrenches=(I["specs"], dev(I["wrenches"])))
+    qd0, qd1 = I["qd"].astype(np.float64), dyn_words(env)[6:12].T.astype(np.float64)
     hqdd = H * joints[:, :, 2]
     compared = R["room"] > cases.CLAMP_MARGIN
     ulp = np.spacing(np.maximum(np.abs(qd0), np.abs(hqdd)).astype(np.float32)).astype(np.float64)
@@ -231,7 +190,7 @@ def test_the_same_bits_without_the_reaction_and_from_the_callers_joints():
         full = query(env, I, "ext")
         lean = query(env, I, "ext", reaction=False)
         assert set(lean) == {"joints"} and torch.equal(bits(lean["joints"]), bits(full["joints"]))
-        own = torch.cat([T(I["q"]), T(I["qd"])], dim=1)
+        own = torch.cat([dev(I["q"]), dev(I["qd"])], dim=1)
         given = query(env, I, "ext", joint_state=own)
         assert torch.equal(bits(given["joints"]), bits(full["joints"])) and torch.equal(bits(given["reaction"]), bits(full["reaction"]))
         other = own.clone()
@@ -335,7 +294,7 @@ def test_refusals_launch_nothing_and_touch_no_output():
 def test_graph_capture_replays_the_eager_result():
     n = 64
     env, I = scenario("C", n)
-    wt, tq = T(I["wrenches"]), T(I["tau"])
+    wt, tq = dev(I["wrenches"]), dev(I["tau"])
     out = dict(joints=torch.zeros((n, 6, 4), device="cuda:0"), reaction=torch.zeros((n, 6, 6), device="cuda:0"))
     s = torch.cuda.Stream(device=env.device)
     s.wait_stream(torch.cuda.current_stream(env.device))
@@ -392,7 +351,7 @@ def test_facade_joint_state_sees_the_queued_shove_and_leaves_it_queued():
     assert len(env.world._wrenches) == 1 and env.world._torques == {1: 3.0}, "looked at, not consumed"
     env.world.step(); still.world.step()
     assert env.world._wrenches == [] and env.world._torques == {}
-    assert np.abs(qd(env) - qd(still)).max() > 10 * cases.QD_TOL, "the step still applied the shove"
+    assert np.abs(qd(env) - qd(still)).max() > 10 * QD_TOL, "the step still applied the shove"
     after = np.array(J[0].state().joint_reaction_forces)
     assert np.abs(after - pushed).max() > 1.0, "the next look carries no force"
     # kinematic mode: position and velocity as today, nothing simulated

@@ -8,12 +8,11 @@ import pytest
 import torch
 
 import link_kinematics_ref as ref
-from env_joints import dyn_joints, kin_joints
+from gpu_support import LIMITS, dyn_joints, kin_joints
 
 pytestmark = pytest.mark.gpu
 
 ROW = 11 * 13
-LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416], dtype=np.float32)
 
 
 def check_records(rec, q, qd):

@@ -9,6 +9,8 @@ the observation filter."""
 import pytest
 import torch
 
+from gpu_support import mlp_make as make, unpack_flat as _unpack_flat
+
 pytestmark = pytest.mark.gpu
 NAMES = ["w1", "b1", "w2", "b2", "w3", "b3"] * 2
 
@@ -20,31 +22,6 @@ def rel(a, b):
 
 def bf(x):
     return x.to(torch.bfloat16).double()
-
-
-def make(B, seed, rows=None, with_filter=False):
-    from pioneer_amd.ppo import ActorCritic, PPOConfig
-    from pioneer_amd.mlp import HipMLP
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(seed)
-    model = ActorCritic(PPOConfig()).to(dev)
-    with torch.no_grad():                                   # heads of visible size, non-zero biases
-        for net in (model.policy, model.value):
-            for l in net:
-                if isinstance(l, torch.nn.Linear):
-                    l.bias.normal_(0, 0.1)
-        model.policy[4].weight.mul_(30.0)
-    g = torch.Generator(device=dev).manual_seed(seed + 1)
-    rows = rows or B
-    obs = torch.randn(rows, 137, generator=g, device=dev) * 2.0 + 0.3
-    idx = torch.randperm(rows, generator=g, device=dev)[:B].contiguous() if rows != B else None
-    filt = None
-    if with_filter:
-        loc = torch.randn(137, generator=g, device=dev) * 0.5
-        inv = torch.rand(137, generator=g, device=dev) + 0.5
-        hi = torch.full((137,), 2.5, device=dev)
-        filt = (loc, inv, -hi, hi)
-    return model, HipMLP(model, B, dev), obs, idx, filt
 
 
 def net_input(obs, idx, filt):
@@ -189,19 +166,6 @@ def _record(B, dev, seed=9):
     R = lambda *s: torch.randn(*s, generator=g, device=dev)   # noqa: E731
     act, mean, ls = R(B, 6), 0.1 * R(B, 6), 0.1 * R(B, 6)
     return {"actions": act, "mean": mean, "log_std": ls, "logp": gaussian_logp(act, mean, ls), "values": R(B), "adv": R(B), "vtarg": R(B)}
-
-
-def _unpack_flat(flat):
-    """The padded gradient bucket [2][107 024] as the twelve parameter-shaped gradients (policy six, value six)."""
-    E = flat.numel() // 2
-    out = []
-    for n in range(2):
-        f = flat[n * E:(n + 1) * E]
-        n3 = 12 if n == 0 else 1
-        out += [f[:256 * 144].view(256, 144)[:, :137], f[102400 + 4096:102400 + 4096 + 256],
-                f[36864:36864 + 65536].view(256, 256), f[102400 + 4096 + 256:102400 + 4096 + 512],
-                f[102400:102400 + 4096].view(16, 256)[:n3], f[102400 + 4096 + 512:102400 + 4096 + 512 + 16][:n3]]
-    return out
 
 
 @pytest.mark.parametrize("B", [8192, 4099, 1])

@@ -7,7 +7,7 @@ batch.  Checked per env against the float64 oracle's world step under that env's
 tests/constraint_motor_ref.py run once per target set (constraint motors), against the engine's own pnr_world_step_torques on a
 second handle (joint torques in the same launch), and bit for bit against single-env handles and eager calls (batch
 independence, graph replay).  Inputs: tests/motor_target_cases.py; tests/test_motor_targets_cpu.py asserts on the oracle that
-they bite.  Tolerances: the project's Q_TOL / QD_TOL for re-synchronised world steps (tests/test_gpu_dynamics.py), the engine
+they bite.  Tolerances: the project's Q_TOL / QD_TOL for re-synchronised world steps (tests/bars.py), the engine
 state loaded into the reference before every step.  Every test prints its worst deviations before it asserts.
 MEASURED on an MI355X (worst |dq| rad, |dqd| rad/s over every env and step): PD laws 3.8e-7, 7.7e-6; inertia-scaled 4.1e-7, 2.7e-6;
 with ground, box and link contacts 3.3e-7, 1.8e-5; the partial mask 2.8e-7, 5.9e-6; constraint motors 1.2e-7, 2.1e-6; deadbeat
@@ -19,66 +19,31 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_support
 import motor_target_cases as cases
+from bars import Q_TOL, QD_TOL
+from gpu_support import dev, dyn_env, dyn_words, kin_env, lib as _lib, load_joints, words
 
 pytestmark = pytest.mark.gpu
 
-Q_TOL, QD_TOL, DOF = cases.Q_TOL, cases.QD_TOL, cases.DOF
+DOF = cases.DOF
 NAN = float("nan")
 AMPLE = 1e9                                                           # a force no sub-step here needs
 INVALID, UNSUPPORTED = -1, -5
 
 
-def _lib():
-    from pioneer_amd import _lib
-    return _lib
-
-
 def make(n, case, engine=None, mode="dynamic", reset=True, **over):
-    from pioneer_amd import EngineConfig, PioneerVectorEnv, SimulationConfig
-    eng = dict(case["engine"] if engine is None else engine)
+    gravity, frame_skip = over.get("gravity", case["gravity"]), over.get("frame_skip", case["frame_skip"])
     if mode != "dynamic":
-        eng = {}
-    sim = SimulationConfig(gravity=over.get("gravity", case["gravity"]), frame_skip=over.get("frame_skip", case["frame_skip"]))
-    env = PioneerVectorEnv(n, device="cuda:0", seed=case["seed"], simulation_config=sim,
-                           engine_config=EngineConfig(mode=mode, auto_reset=False, max_episode_steps=0, **eng))
-    if reset:
-        env.reset()
-    return env
+        return kin_env(n, case["seed"], reset, sim=dict(gravity=gravity, frame_skip=frame_skip), mode=mode, auto_reset=False, max_episode_steps=0)
+    return dyn_env(n, case["seed"], gravity, frame_skip, reset, **(case["engine"] if engine is None else engine))
 
 
 def set_motors(env, laws, tgt=None):
     """pnr_set_joint_motor for every law that is not None; tgt [12]: these targets instead of the laws' own"""
-    L = _lib()
-    modes = {"velocity_constraint": L.CONTROL_VELOCITY_CONSTRAINT, "position_constraint": L.CONTROL_POSITION_CONSTRAINT}
-    for j, m in enumerate(laws):
-        if m is None:
-            continue
-        if tgt is not None:
-            m = cases.law_for_env(m, tgt, j)
-        mode = modes.get(m["kind"])
-        if mode is None:
-            mode = L.CONTROL_VELOCITY if m["control_mode"] == 1 else L.CONTROL_POSITION
-        env.set_joint_motor(j, mode, **{k: v for k, v in m.items() if k not in ("kind", "control_mode")})
-
-
-def load(env, q, qd):
-    d = env.get_dyn_state()
-    d[0:6] = torch.as_tensor(np.ascontiguousarray(q.T), dtype=torch.float32, device=d.device)
-    d[6:12] = torch.as_tensor(np.ascontiguousarray(qd.T), dtype=torch.float32, device=d.device)
-    env.set_dyn_state(d)
-
-
-def dyn(env):
-    return env.get_dyn_state().cpu().numpy()
-
-
-def words(env):
-    return env.get_state().cpu().numpy().view(np.uint32)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    if tgt is not None:
+        laws = [m if m is None else cases.law_for_env(m, tgt, j) for j, m in enumerate(laws)]
+    gpu_support.set_motors(env, laws)
 
 
 def prepared(case, n, engine=None):
@@ -89,14 +54,14 @@ def prepared(case, n, engine=None):
         env.vector_step(dev(act))
     set_motors(env, case["laws"])
     w = words(env)
-    assert np.array_equal(w[:21], orc.state_words()[:21]) and np.array_equal(dyn(env)[12:35], orc.dyn_words()[12:35])
+    assert np.array_equal(w[:21], orc.state_words()[:21]) and np.array_equal(dyn_words(env)[12:35], orc.dyn_words()[12:35])
     orc.load_state_words(w)
     return env, orc
 
 
 def deviation(env, orc):
     """per env, the engine's q, qd against the oracle's: (|dq| [n], |dqd| [n])"""
-    d = dyn(env).astype(np.float64)
+    d = dyn_words(env).astype(np.float64)
     return np.abs(d[0:6].T - orc.dstate["q"]).max(axis=1), np.abs(d[6:12].T - orc.dstate["qd"]).max(axis=1)
 
 
@@ -118,8 +83,8 @@ def test_pd_motors_track_each_envs_own_targets_like_the_oracle(n, engine):
     eng = {"pd": c["engine"], "scaled": cases.PD_SCALED_ENGINE, "contacts": cases.PD_CONTACT_ENGINE}[engine]
     env, orc = prepared(c, n, eng)
     for step in range(c["steps"]):
-        load(env, *cases.states(c, n, step))
-        orc.load_dyn_words(dyn(env))
+        load_joints(env, *cases.states(c, n, step))
+        orc.load_dyn_words(dyn_words(env))
         tgt = cases.targets(c, n, step)
         env.world_step(motor_targets=dev(tgt))
         cases.oracle_world_step(orc, c["laws"], tgt, cases.FULL)
@@ -139,19 +104,19 @@ def test_partial_mask_next_to_commanded_and_uncommanded_joints_and_nothing_persi
     st = env.state_dict()
     assert np.all(st["v"][:, [2, 5]] != 0), "the command state the unmasked, uncommanded joints track must have moved"
     for step in range(c["steps"]):
-        load(env, *cases.states(c, n, step))
-        orc.load_dyn_words(dyn(env))
+        load_joints(env, *cases.states(c, n, step))
+        orc.load_dyn_words(dyn_words(env))
         tgt = cases.targets(c, n, step, mask, poison=True)
-        w0, d0 = words(env), dyn(env)
+        w0, d0 = words(env), dyn_words(env)
         env.world_step(motor_targets=dev(tgt), motor_joints=mask)
-        w1, d1 = words(env), dyn(env)
+        w1, d1 = words(env), dyn_words(env)
         assert np.array_equal(w0, w1), "the state words must be left bit for bit"
         assert np.array_equal(d0[12:36].view(np.uint32), d1[12:36].view(np.uint32)), "dyn words 12-35 must be left bit for bit"
         assert np.isfinite(d1[0:12]).all()
         cases.oracle_world_step(orc, c["laws"], tgt, mask)
         check(f"targets_partial step={step}", env, orc)
-    load(env, *cases.states(c, n, c["steps"]))
-    orc.load_dyn_words(dyn(env))
+    load_joints(env, *cases.states(c, n, c["steps"]))
+    orc.load_dyn_words(dyn_words(env))
     env.world_step()
     cases.oracle_world_step(orc, c["laws"])
     check("targets_partial, plain step afterwards", env, orc)
@@ -168,8 +133,8 @@ def test_constraint_motors_take_each_envs_own_targets(n, mask, steps):
     env, orc = prepared(c, n)
     for step in range(steps):
         q, qd = cases.states(c, n, step)
-        load(env, q, qd)
-        orc.load_dyn_words(dyn(env))
+        load_joints(env, q, qd)
+        orc.load_dyn_words(dyn_words(env))
         sets, pick = cases.target_sets(c, n, step, mask)
         tgt = sets[pick].copy()
         for j in range(DOF):
@@ -190,7 +155,7 @@ def test_velocity_constraint_motors_are_deadbeat_on_each_envs_own_target():
     c = dict(cases.PD, engine=dict(joint_damping=0.5, joint_friction=0.2))
     n = 1000
     env = make(n, c, gravity=0.0, frame_skip=1)
-    load(env, cases.states(c, n, 0)[0], np.zeros((n, DOF), np.float32))
+    load_joints(env, cases.states(c, n, 0)[0], np.zeros((n, DOF), np.float32))
     for j in range(DOF):
         env.set_joint_motor(j, L.CONTROL_VELOCITY_CONSTRAINT, target_velocity=0.0, max_force=AMPLE)
     rng = np.random.default_rng(40)
@@ -198,9 +163,9 @@ def test_velocity_constraint_motors_are_deadbeat_on_each_envs_own_target():
         vs = rng.uniform(-2.0, 2.0, size=(n, DOF)).astype(np.float32)
         assert len(np.unique(vs, axis=0)) == n, "every env's targets must be its own"
         tgt = np.concatenate([np.zeros((n, DOF), np.float32), vs], axis=1)
-        q0 = dyn(env)[0:6].T.astype(np.float64)
+        q0 = dyn_words(env)[0:6].T.astype(np.float64)
         env.world_step(motor_targets=dev(tgt))
-        d = dyn(env).astype(np.float64)
+        d = dyn_words(env).astype(np.float64)
         q, qd = d[0:6].T, d[6:12].T
         assert np.all((q > env.r_lo) & (q < env.r_hi)), "no joint may reach a limit here (the stop would zero its velocity)"
         err = np.abs(qd - vs) / np.maximum(1.0, np.abs(vs))
@@ -216,19 +181,19 @@ def test_joint_torques_in_the_same_launch_equal_world_step_torques_under_each_en
     n = 64
     env, ref = make(n, c), make(n, c)
     set_motors(env, c["laws"])
-    load(env, *cases.states(c, n, 0))
+    load_joints(env, *cases.states(c, n, 0))
     w0, d0 = env.get_state().clone(), env.get_dyn_state().clone()
     sets, pick = cases.target_sets(c, n, 0)
     rng = np.random.default_rng(50)
     tq = dev(rng.uniform(-500.0, 500.0, size=(n, DOF)).astype(np.float32))
     env.world_step(motor_targets=dev(sets[pick]), joint_torques=tq)
-    got = dyn(env).astype(np.float64)
+    got = dyn_words(env).astype(np.float64)
     runs = []
     for k in range(len(sets)):
         ref.set_state(w0); ref.set_dyn_state(d0)
         set_motors(ref, c["laws"], sets[k])
         ref.world_step(joint_torques=tq)
-        runs.append(dyn(ref).astype(np.float64))
+        runs.append(dyn_words(ref).astype(np.float64))
     want = np.stack(runs)[pick, :, np.arange(n)].T                  # [36, n]: env e from the run of its own set
     dq, dqd = np.abs(got[0:6] - want[0:6]).max(), np.abs(got[6:12] - want[6:12]).max()
     print(f"targets_torques: |dq| {dq:.3e} |dqd| {dqd:.3e}")
@@ -240,7 +205,7 @@ def test_joint_torques_in_the_same_launch_equal_world_step_torques_under_each_en
     # the torques act: without them the result differs
     env.set_state(w0); env.set_dyn_state(d0)
     env.world_step(motor_targets=dev(sets[pick]))
-    assert np.abs(dyn(env)[6:12] - got[6:12]).max() > 20 * QD_TOL
+    assert np.abs(dyn_words(env)[6:12] - got[6:12]).max() > 20 * QD_TOL
     env.close(); ref.close()
 
 
@@ -253,14 +218,14 @@ def test_batch_envs_equal_single_env_handles_bit_for_bit(table):
     n, steps = 1000, 3
     env = make(n, c, eng)
     set_motors(env, c["laws"])
-    load(env, *cases.states(c, n, 0))
+    load_joints(env, *cases.states(c, n, 0))
     w0, d0 = env.get_state().clone(), env.get_dyn_state().clone()
     rng = np.random.default_rng(60)
     tgts = [dev(cases.targets(c, n, s)) for s in range(steps)]
     tqs = [dev(rng.uniform(-300.0, 300.0, size=(n, DOF)).astype(np.float32)) if table == "pd" else None for s in range(steps)]
     for s in range(steps):
         env.world_step(motor_targets=tgts[s], joint_torques=tqs[s])
-    got = dyn(env)
+    got = dyn_words(env)
     assert np.isfinite(got).all()
     for e in (0, 36, 63, 64, 999):
         one = make(1, c, eng)
@@ -269,7 +234,7 @@ def test_batch_envs_equal_single_env_handles_bit_for_bit(table):
         set_motors(one, c["laws"])
         for s in range(steps):
             one.world_step(motor_targets=tgts[s][e:e + 1].clone(), joint_torques=None if tqs[s] is None else tqs[s][e:e + 1].clone())
-        assert np.array_equal(dyn(one)[:, 0].view(np.uint32), got[:, e].view(np.uint32)), e
+        assert np.array_equal(dyn_words(one)[:, 0].view(np.uint32), got[:, e].view(np.uint32)), e
         one.close()
     env.close()
 
@@ -281,7 +246,7 @@ def test_refusals_are_decided_before_any_launch_and_name_the_call():
     n = 8
     env = make(n, c)
     set_motors(env, c["laws"])
-    load(env, *cases.states(c, n, 0))
+    load_joints(env, *cases.states(c, n, 0))
     lib, st = env.lib, env._stream()
     buf = torch.zeros(n * 12 + 4, device="cuda")
     good, off4 = buf[:n * 12], buf[1:n * 12 + 1]                      # 16-byte aligned (the allocator's) and 4 bytes past it
@@ -291,14 +256,14 @@ def test_refusals_are_decided_before_any_launch_and_name_the_call():
 
     def refused(handle, code, call):
         w0 = words(handle) if handle is not None else None
-        d0 = dyn(handle) if handle is not None and handle.engine_config.mode == "dynamic" else None
+        d0 = dyn_words(handle) if handle is not None and handle.engine_config.mode == "dynamic" else None
         assert call() == code
         msg = lib.pnr_last_error(handle._h if handle is not None else None)
         assert b"pnr_world_step_targets" in msg, msg
         if w0 is not None:
             assert np.array_equal(w0, words(handle))
         if d0 is not None:
-            assert np.array_equal(d0.view(np.uint32), dyn(handle).view(np.uint32))
+            assert np.array_equal(d0.view(np.uint32), dyn_words(handle).view(np.uint32))
 
     refused(None, INVALID, lambda: lib.pnr_world_step_targets(None, 63, p(good), None, st))                  # a null handle
     refused(env, INVALID, lambda: lib.pnr_world_step_targets(env._h, 63, None, None, st))                    # NULL targets
@@ -340,7 +305,7 @@ def test_two_captured_calls_replay_with_rewritten_targets_bit_for_bit():
     n = 1000
     env = make(n, c)
     set_motors(env, c["laws"])
-    load(env, *cases.states(c, n, 0))
+    load_joints(env, *cases.states(c, n, 0))
     w0, d0 = env.get_state().clone(), env.get_dyn_state().clone()
     first, second = dev(cases.targets(c, n, 0)), dev(cases.targets(c, n, 1))
     tgt = second.clone()
@@ -350,7 +315,7 @@ def test_two_captured_calls_replay_with_rewritten_targets_bit_for_bit():
         env.world_step(motor_targets=tgt)
         env.world_step(motor_targets=tgt)
     s.synchronize()
-    want = dyn(env)
+    want = dyn_words(env)
     env.set_state(w0); env.set_dyn_state(d0)
     tgt.copy_(first)
     torch.cuda.synchronize()
@@ -358,12 +323,12 @@ def test_two_captured_calls_replay_with_rewritten_targets_bit_for_bit():
     with torch.cuda.graph(g, stream=s):
         env.world_step(motor_targets=tgt)
         env.world_step(motor_targets=tgt)
-    assert np.array_equal(dyn(env).view(np.uint32), d0.cpu().numpy().view(np.uint32)), "capturing must not run the calls"
+    assert np.array_equal(dyn_words(env).view(np.uint32), d0.cpu().numpy().view(np.uint32)), "capturing must not run the calls"
     tgt.copy_(second)
     torch.cuda.synchronize()
     g.replay()
     torch.cuda.synchronize()
-    got = dyn(env)
+    got = dyn_words(env)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
     assert not np.array_equal(got[0:12], d0.cpu().numpy()[0:12])
     env.close()

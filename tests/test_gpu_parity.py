@@ -1,92 +1,17 @@
 """GPU parity: the HIP path (through the C ABI) against the CPU oracle.
 
-Tolerances (float32 engine vs float64 oracle, ORC_DEV storage model):
-  * joint state a, v, r and target: BIT-EXACT (the integrator reproduces the
-    reference's mixed-precision arithmetic; reset draws share Philox4x32-10);
-  * cos/sin observation entries: 4e-7 absolute (<= ~2 float32 ulp at 1.0 on top
-    of the oracle's own float32 rounding);
-  * pointer xyz / diff / distance: 3e-5 absolute in a ~30-unit workspace
-    (relative 1e-6);
-  * potential 1e-4, reward 2e-4 absolute: potential = 95/(d/10+1) <= 95 is a float32
-    (ulp 7.6e-6 near 95) with |d pot / d dist| <= 9.5, so a 3e-5 distance error alone can
-    move it by ~3e-4 at dist -> 0 and by < 1e-4 in the target box; the reward is a
-    difference of two such potentials.
+Tolerances (float32 engine vs float64 oracle, ORC_DEV storage model): tests/bars.py, where each is derived.
 """
 import numpy as np
 import pytest
 import torch
 
+from bars import POS_IDX, REW_TOL, TRIG_IDX, check_obs
+from gpu_support import check_state_exact, make_pair, run_parity
 from oracle import COracle
 from oracle.binding import ORC_DEV
 
 pytestmark = pytest.mark.gpu
-
-TRIG_TOL = 4e-7
-POS_TOL = 3e-5
-POT_TOL = 1e-4
-REW_TOL = 2e-4
-
-TRIG_IDX = np.r_[6:18, 24:36, 42:54, 60:72, 78:90, 96:108, 114:126]
-LIN_IDX = np.r_[0:6, 18:24, 36:42, 90:96, 108:114, 129:132]      # exact float32 copies
-SUB_IDX = np.r_[54:60, 72:78]                                      # float32 subtractions (exact vs oracle)
-POS_IDX = np.r_[126:129, 132:136]
-
-
-def make_pair(n, seed=0, layout="env_major", act_layout="env_major", auto_reset=True, max_steps=500, **cfg):
-    from pioneer_amd import PioneerVectorEnv, EngineConfig, PioneerKinematicConfig
-    env = PioneerVectorEnv(n, device="cuda:0", seed=seed,
-                           pioneer_config=PioneerKinematicConfig(**cfg),
-                           engine_config=EngineConfig(auto_reset=auto_reset, obs_layout=layout,
-                                                      action_layout=act_layout, max_episode_steps=max_steps))
-    orc = COracle(n, seed=seed, precision=ORC_DEV, auto_reset=auto_reset, max_episode_steps=max_steps,
-                  nthreads=8, **cfg)
-    return env, orc
-
-
-def to_env_major(env, obs):
-    o = obs.double().cpu().numpy()
-    return o.T if env.feature_major_obs else o
-
-
-def check_obs(got, want):
-    """got/want [n,137] float64."""
-    g, w = got, want
-    assert np.array_equal(g[:, LIN_IDX], w[:, LIN_IDX]), "linear obs entries must be exact"
-    assert np.array_equal(g[:, SUB_IDX], w[:, SUB_IDX]), "r - r_lo / r_hi - r must be exact float32"
-    assert np.abs(g[:, TRIG_IDX] - w[:, TRIG_IDX]).max() <= TRIG_TOL
-    assert np.abs(g[:, POS_IDX] - w[:, POS_IDX]).max() <= POS_TOL
-    assert np.abs(g[:, 136] - w[:, 136]).max() <= POT_TOL
-
-
-def check_state_exact(env, orc):
-    w = env.get_state().cpu().numpy().view(np.uint32)
-    ow = orc.state_words()
-    assert np.array_equal(w[:21], ow[:21]), "a, v, r, target must be bit-exact"
-    assert np.array_equal(w[22:], ow[22:]), "step_index / episode must match"
-    pot = w[21].view(np.float32).astype(np.float64)
-    opot = ow[21].view(np.float32).astype(np.float64)
-    assert np.abs(pot - opot).max() <= POT_TOL
-
-
-def run_parity(n, steps, layout="env_major", act_layout="env_major", seed=3, action_scale=1.0, **kw):
-    env, orc = make_pair(n, seed=seed, layout=layout, act_layout=act_layout, **kw)
-    obs = env.reset()
-    check_obs(to_env_major(env, obs), orc.reset())
-    rng = np.random.RandomState(seed)
-    for t in range(steps):
-        act = (rng.uniform(-1, 1, size=(n, 6)) * env.a_max * action_scale).astype(np.float32)
-        a_dev = torch.from_numpy(act.T.copy() if env.feature_major_act else act).cuda()
-        obs, rew, done, trunc, info = env.vector_step(a_dev, want_info=True)
-        oobs, orew, odone, otrunc, oinfo = orc.step(act, want_info=True)
-        # done / truncated are bytes the caller branches on: identical for EVERY env (the engine re-evaluates the
-        # predicate in float64 wherever the float32 distance comes near done_distance, pnr_device.h done_predicate)
-        assert np.array_equal(done.cpu().numpy(), odone) and np.array_equal(trunc.cpu().numpy(), otrunc)
-        assert np.abs(rew.double().cpu().numpy() - orew).max() <= REW_TOL
-        assert np.abs(info.double().cpu().numpy()[:, :3] - oinfo[:, :3]).max() <= REW_TOL
-        assert np.abs(info.double().cpu().numpy()[:, 3] - oinfo[:, 3]).max() <= POS_TOL
-        check_obs(to_env_major(env, obs), oobs)
-    check_state_exact(env, orc)
-    env.close()
 
 
 @pytest.mark.parametrize("layout,act_layout", [("env_major", "env_major"), ("feature_major", "feature_major"),

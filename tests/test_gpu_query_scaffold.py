@@ -16,18 +16,15 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import LIMITS, dev
+
 pytestmark = pytest.mark.gpu
 
 SIZES = (130, 65, 1)                     # the largest first: the smaller envs take its words
 GUARD = 64
 SENTINEL = -7.25
-LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416], dtype=np.float32)
 LOCAL_POINT = (0.3, -0.2, 0.5)
 KINDS = ("buffer", "kinematic_own", "dynamic_own")
-
-
-def T(x, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype, device="cuda:0")
 
 
 def inputs():
@@ -61,16 +58,16 @@ def make_env(kind, n, q, qd, words):
         w = env.get_state()
         if kind == "kinematic_own":
             f = w.view(torch.float32)
-            f[6:12], f[12:18] = T(qd.T), T(q.T)
+            f[6:12], f[12:18] = dev(qd.T), dev(q.T)
         words["kin"] = w.clone()
         if dyn:
             d = env.get_dyn_state()
-            d[0:6], d[6:12] = T(q.T), T(qd.T)
+            d[0:6], d[6:12] = dev(q.T), dev(qd.T)
             words["dyn"] = d.clone()
     env.set_state(words["kin"][:, :n].contiguous())
     if dyn:
         env.set_dyn_state(words["dyn"][:, :n].contiguous())
-    return env, (T(np.concatenate([q[:n], qd[:n]], axis=1)) if kind == "buffer" else None)
+    return env, (dev(np.concatenate([q[:n], qd[:n]], axis=1)) if kind == "buffer" else None)
 
 
 class Guarded:
@@ -97,12 +94,12 @@ def run_queries(env, js, n, q, qdd, targets, body_pos, own_target):
     res = {"link_states": env.link_states(js, out=g.new("link_states", (n, 11, 13))),
            "jacobian": env.jacobian(10, LOCAL_POINT, js, out=g.new("jacobian", (n, 6, 6))),
            "mass_matrix": env.mass_matrix(js, out=g.new("mass_matrix", (n, 6, 6))),
-           "inverse_dynamics": env.inverse_dynamics(T(qdd[:n]), js, joint_losses=True, out=g.new("inverse_dynamics", (n, 6)))}
+           "inverse_dynamics": env.inverse_dynamics(dev(qdd[:n]), js, joint_losses=True, out=g.new("inverse_dynamics", (n, 6)))}
     out = {"points": g.new("points", (n, 23, 9)), "summary": g.new("summary", (n, 4)), "joint_torques": g.new("joint_torques", (n, 6))}
-    res.update(env.contacts(joint_state=js, bodies=bodies(), body_positions=T(body_pos[:n]), joint_torques=True, out=out))
+    res.update(env.contacts(joint_state=js, bodies=bodies(), body_positions=dev(body_pos[:n]), joint_torques=True, out=out))
     # solve_ik has no joint source; its own two sources are the caller's targets and the env's own (state words 18-20)
     out = {"q": g.new("ik_q", (n, 6)), "residual": g.new("ik_residual", (n,)), "iterations": g.new("ik_iterations", (n,), torch.int32)}
-    ik = env.solve_ik(None if own_target else T(targets[:n]), T(0.3 * q[:n]), max_iterations=6, out=out)
+    ik = env.solve_ik(None if own_target else dev(targets[:n]), dev(0.3 * q[:n]), max_iterations=6, out=out)
     res.update(zip(("ik_q", "ik_residual", "ik_iterations"), ik))
     torch.cuda.synchronize()
     g.check()

@@ -20,10 +20,10 @@ import torch
 import link_kinematics_ref as lk
 import ray_ref as ry
 import render_ref as rr
+from gpu_support import LIMITS, coloured_bodies, random_state
 
 pytestmark = pytest.mark.gpu
 
-LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416], dtype=np.float32)
 POS_TOL_REL = 4 * 9.42e-7          # x |to - from|; see the module docstring
 NORMAL_TOL = 4 * 1.43e-5
 MASKS = {"bodies": ry.HIT_BODIES, "arm_bodies": ry.HIT_ARM | ry.HIT_BODIES, "all": ry.HIT_ARM | ry.HIT_BODIES | ry.HIT_TARGET}
@@ -31,22 +31,12 @@ POINTER = 10
 
 
 def scene_bodies():
-    """The three bodies of tests/test_gpu_render.py: a rotated box, a sphere, the plane at z = -0.5."""
-    from pioneer_amd.config import scene_box, scene_plane, scene_sphere
-    return [scene_box((1.0, 1.5, 3.0), (10.0, 5.0, 0.0), (0.0, 0.0, 0.38268343, 0.92387953)),
-            scene_sphere(2.0, (-8.0, -6.0, 4.0)), scene_plane((0.0, 0.0, 1.0), (0.0, 0.0, -0.5))]
+    """The render tests' three bodies, without their colours."""
+    return [b for b, _ in coloured_bodies()]
 
 
 def ref_bodies(bodies, positions=None):
     return [(b.shape, b.position if positions is None else positions[i], b.orientation, b.size) for i, b in enumerate(bodies)]
-
-
-def random_state(n, seed):
-    """As tests/test_gpu_render.py's."""
-    rng = np.random.default_rng(seed)
-    q = (rng.uniform(-1.0, 1.0, size=(n, 6)) * LIMITS).astype(np.float32)
-    tgt = rng.uniform((15, -10, 2), (25, 10, 6), size=(n, 3)).astype(np.float32)
-    return q, tgt
 
 
 def fan(n=32):

@@ -9,30 +9,20 @@ import torch
 
 import link_kinematics_ref  # noqa: F401  (render_ref's chain)
 import render_ref as rr
+from gpu_support import LIMITS, coloured_bodies, random_state
 
 pytestmark = pytest.mark.gpu
 
-LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416], dtype=np.float32)
 CAMS = {"default": dict(), "close": dict(camera_distance=25.0), "axis": dict(camera_yaw=0.0, camera_pitch=0.0, camera_roll=0.0)}
 GREY = (0.3, 0.3, 0.3, 1.0)
 
 
 def scene_bodies():
-    from pioneer_amd.config import scene_box, scene_plane, scene_sphere
-    return [(scene_box((1.0, 1.5, 3.0), (10.0, 5.0, 0.0), (0.0, 0.0, 0.38268343, 0.92387953)), (0.8, 0.2, 0.6, 1.0)),
-            (scene_sphere(2.0, (-8.0, -6.0, 4.0)), (0.2, 0.7, 0.9, 1.0)),
-            (scene_plane((0.0, 0.0, 1.0), (0.0, 0.0, -0.5)), (0.4, 0.4, 0.4, 1.0))]
+    return coloured_bodies()
 
 
 def ref_bodies(bodies):
     return [(b.shape, b.position, b.orientation, b.size, rgba) for b, rgba in bodies]
-
-
-def random_state(n, seed):
-    rng = np.random.default_rng(seed)
-    q = (rng.uniform(-1.0, 1.0, size=(n, 6)) * LIMITS).astype(np.float32)
-    tgt = rng.uniform((15, -10, 2), (25, 10, 6), size=(n, 3)).astype(np.float32)
-    return q, tgt
 
 
 def check_env(frames, k, q, tgt, cfg, bodies, min_checked=0.9):

@@ -9,13 +9,14 @@ canonical [24][n] words of include/pioneer_amd.h do not change; these tests go t
 
 Sizes: 1, 31, 32, 33, 65 — one env, a ragged tile, a full tile, a tile and one env, two tiles and one env; 32 768 and 32 800, the
 last size of the one-pass form without the row pass and the first with it (step_row_pass, pnr_api.hip).  Equalities and
-tolerances are tests/test_gpu_parity.py's: a, v, r, target, step_index, episode bit-exact, potential within POT_TOL.
+tolerances are the kinematic suite's (tests/bars.py): a, v, r, target, step_index, episode bit-exact, potential within POT_TOL.
 """
 import numpy as np
 import pytest
 import torch
 
-import test_gpu_parity as parity
+from bars import POT_TOL
+from gpu_support import check_state_exact, dev, make_pair, words
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +30,8 @@ def _env(n, mode="kinematic", seed=3, auto_reset=False, max_steps=0, env_id_offs
                             engine_config=EngineConfig(mode=mode, auto_reset=auto_reset, max_episode_steps=max_steps))
 
 
-def _dev(w):
-    return torch.from_numpy(w.view(np.int32)).cuda()
-
-
-def _get(env):
-    return env.get_state().cpu().numpy().view(np.uint32)
+def _state_tensor(w):
+    return dev(w.view(np.int32), torch.int32)
 
 
 def _distinct_words(n):
@@ -50,7 +47,7 @@ def _distinct_words(n):
 def _state_with_odd_cold_words(env, n):
     """the env's own state after a reset (finite, inside the limits), with distinctive episode words everywhere and non-finite
     target and episode words in the first and the last env"""
-    w = _get(env).copy()
+    w = words(env).copy()
     w[23] = 0x00ABC000 + 3 * np.arange(n, dtype=np.uint32)
     for j, e in enumerate(sorted({0, n - 1})):
         w[18 + j, e] = (NAN1, NINF)[j]
@@ -64,8 +61,8 @@ def test_set_state_get_state_round_trip_is_bit_exact(n, mode):
     env = _env(n, mode)
     env.reset()
     w = _distinct_words(n)
-    env.set_state(_dev(w))
-    got = _get(env)
+    env.set_state(_state_tensor(w))
+    got = words(env)
     for k in range(24):
         assert np.array_equal(got[k], w[k]), f"word {k} did not come back"
     env.close()
@@ -79,14 +76,14 @@ def _check_hot_words(got, orc):
     assert np.array_equal(np.isnan(pot), np.isnan(opot))         # (a non-finite target makes the potential NaN in both)
     fin = ~np.isnan(opot)
     if fin.any():
-        assert np.abs(pot[fin] - opot[fin]).max() <= parity.POT_TOL
+        assert np.abs(pot[fin] - opot[fin]).max() <= POT_TOL
 
 
 def _survive(n, rollout):
-    env, orc = parity.make_pair(n, seed=5, auto_reset=False, max_steps=0)
+    env, orc = make_pair(n, seed=5, auto_reset=False, max_steps=0)
     env.reset()
     w = _state_with_odd_cold_words(env, n)
-    env.set_state(_dev(w))
+    env.set_state(_state_tensor(w))
     orc.load_state_words(w)
     rng = np.random.RandomState(n)
     acts = (rng.uniform(-1, 1, size=(3, n, 6)) * env.a_max).astype(np.float32)
@@ -96,7 +93,7 @@ def _survive(n, rollout):
         if not rollout:
             env.vector_step(torch.from_numpy(acts[t]).cuda())
         orc.step(acts[t], want_obs=False)
-    got = _get(env)
+    got = words(env)
     for k in (18, 19, 20, 23):
         assert np.array_equal(got[k], w[k]), f"cold word {k} changed"
     _check_hot_words(got, orc)
@@ -117,11 +114,11 @@ def test_cold_words_survive_three_steps_in_dynamics_mode(n):
     env = _env(n, "dynamic")
     env.reset()
     w = _state_with_odd_cold_words(env, n)
-    env.set_state(_dev(w))
+    env.set_state(_state_tensor(w))
     rng = np.random.RandomState(n)
     for t in range(3):
         env.vector_step(torch.from_numpy((rng.uniform(-1, 1, size=(n, 6)) * env.a_max).astype(np.float32)).cuda())
-    got = _get(env)
+    got = words(env)
     for k in (18, 19, 20, 23):
         assert np.array_equal(got[k], w[k]), f"cold word {k} changed"
     assert np.all(got[22] == w[22] + 3)
@@ -135,7 +132,7 @@ def test_cold_words_are_rewritten_by_the_reset_inside_a_step(n, offset):
     env = _env(n, seed=11, auto_reset=True, max_steps=2, env_id_offset=offset)
     orc = COracle(n, seed=11, precision=ORC_DEV, auto_reset=True, max_episode_steps=2, env_id_offset=offset, nthreads=8)
     env.reset(); orc.reset(want_obs=False)
-    before = _get(env).copy()
+    before = words(env).copy()
     assert np.all(before[23] == 1)
     rng = np.random.RandomState(n)
     cut, never_done = np.zeros(n, dtype=np.int64), np.ones(n, dtype=bool)
@@ -146,12 +143,12 @@ def test_cold_words_are_rewritten_by_the_reset_inside_a_step(n, offset):
         assert np.array_equal(done.cpu().numpy(), odone) and np.array_equal(trunc.cpu().numpy(), otrunc)
         cut += trunc.cpu().numpy()
         never_done &= odone == 0
-    got = _get(env)
+    got = words(env)
     # an env that never came within done_distance was truncated exactly once, by the second step: one new episode, a new target
     assert never_done.mean() > 0.99 and np.all(cut[never_done] == 1)
     assert np.all(got[23][never_done] == 2)
     assert np.all((got[18:21] != before[18:21]).any(axis=0)[never_done]), "a reset draws a new target"
-    parity.check_state_exact(env, orc)           # target, r (and a, v), step_index, episode: the oracle's bits; potential to POT_TOL
+    check_state_exact(env, orc)           # target, r (and a, v), step_index, episode: the oracle's bits; potential to POT_TOL
     env.close()
 
 
@@ -159,14 +156,14 @@ def test_link_state_ray_and_ik_kernels_read_joints_and_target_from_the_record():
     n = 65
     env = _env(n, seed=2)
     env.reset()
-    w = _get(env).copy()
+    w = words(env).copy()
     f = w.view(np.float32)
     rng = np.random.RandomState(4)
     q = (rng.uniform(-0.9, 0.9, size=(n, 6)) * env.r_hi).astype(np.float32)
     qd = rng.uniform(-0.5, 0.5, size=(n, 6)).astype(np.float32)
     tgt = (np.array((15.0, -8.0, 2.0)) + np.array((7.0, 16.0, 4.0)) * rng.random((n, 3))).astype(np.float32)
     f[12:18], f[6:12], f[18:21] = q.T, qd.T, tgt.T
-    env.set_state(_dev(w))
+    env.set_state(_state_tensor(w))
     js = torch.from_numpy(np.concatenate([q, qd], axis=1)).cuda()
     bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t  # noqa: E731
 

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_parity as parity
+from gpu_support import make_pair, run_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -63,8 +63,8 @@ def test_general_and_one_pass_kernels_agree_at_the_selection_boundary(layout):
 def test_ragged_sizes_through_the_one_pass_kernel_against_the_oracle(n):
     """A single pair, a tile one env short, one env over a tile, and the largest grid with a ragged last tile: two steps with
     an auto-reset of every env in between (max_episode_steps = 1), both layouts."""
-    parity.run_parity(n, 2, "env_major", "env_major", max_steps=1)
-    parity.run_parity(n, 2, "feature_major", "feature_major", max_steps=1)
+    run_parity(n, 2, "env_major", "env_major", max_steps=1)
+    run_parity(n, 2, "feature_major", "feature_major", max_steps=1)
 
 
 @pytest.mark.parametrize("layout", ["env_major", "feature_major"])
@@ -73,8 +73,8 @@ def test_rollout_in_one_general_launch_equals_one_pass_steps(layout):
     general form, two pnr_step calls (info requested) are two launches of the one-pass form; every env is truncated and
     re-drawn at each step."""
     n, T = 96 + 5, 2
-    env1, _ = parity.make_pair(n, seed=9, layout=layout, max_steps=1)
-    env2, _ = parity.make_pair(n, seed=9, layout=layout, max_steps=1)
+    env1, _ = make_pair(n, seed=9, layout=layout, max_steps=1)
+    env2, _ = make_pair(n, seed=9, layout=layout, max_steps=1)
     assert torch.equal(env1.reset(), env2.reset())
     g = torch.Generator(device="cpu").manual_seed(2)
     acts = ((torch.rand(T, n, 6, generator=g) * 2 - 1) * torch.from_numpy(env1.a_max)).cuda()

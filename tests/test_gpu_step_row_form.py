@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_parity as parity
+import bars
+from gpu_support import check_state_exact, make_pair, run_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -31,28 +32,28 @@ def _step_both(env, orc, act, check_obs=True):
     obs, rew, done, trunc = env.vector_step(torch.from_numpy(act).cuda())
     oobs, orew, odone, otrunc = orc.step(act, want_obs=check_obs)
     assert np.array_equal(done.cpu().numpy(), odone) and np.array_equal(trunc.cpu().numpy(), otrunc)
-    assert np.abs(rew.double().cpu().numpy() - orew).max() <= parity.REW_TOL
+    assert np.abs(rew.double().cpu().numpy() - orew).max() <= bars.REW_TOL
     if check_obs:
-        parity.check_obs(obs.double().cpu().numpy(), oobs)
+        bars.check_obs(obs.double().cpu().numpy(), oobs)
 
 
 @pytest.mark.parametrize("n", ROW_SIZES + ONE_PASS_SIZES + [GENERAL_SIZE])
 def test_random_actions_across_truncation_resets(n):
     """Eight steps of random actions with max_episode_steps = 5: the truncation resets land in the middle of the run; every
     step's outputs are checked and the state is bit-exact at the end."""
-    parity.run_parity(n, 8, max_steps=5)
+    run_parity(n, 8, max_steps=5)
 
 
 @pytest.mark.parametrize("n", ROW_SIZES + [GENERAL_SIZE])
 def test_unclipped_actions_at_five_times_a_max(n):
-    parity.run_parity(n, 8, action_scale=5.0, max_steps=0, auto_reset=False)
+    run_parity(n, 8, action_scale=5.0, max_steps=0, auto_reset=False)
 
 
 @pytest.mark.parametrize("n", ROW_SIZES + ONE_PASS_SIZES + [GENERAL_SIZE])
 def test_constant_sign_actions_saturate_every_joint_into_its_limit(n):
     """Thirty steps of +-a_max (the sign alternates from env to env, so the two halves of a wave saturate at opposite bounds): every
     lane takes the saturation block in every joint, then every joint is parked at a limit."""
-    env, orc = parity.make_pair(n, seed=1, auto_reset=False, max_steps=0)
+    env, orc = make_pair(n, seed=1, auto_reset=False, max_steps=0)
     env.reset(); orc.reset(want_obs=False)
     sign = np.where(np.arange(n)[:, None] % 2 == 0, 1.0, -1.0) * np.ones((1, 6))
     act = (sign * env.a_max).astype(np.float32)
@@ -60,7 +61,7 @@ def test_constant_sign_actions_saturate_every_joint_into_its_limit(n):
         _step_both(env, orc, act, check_obs=(t % 6 == 5 or t < 6))
     st = env.state_dict()
     assert np.all((st["r"] == env.r_hi) | (st["r"] == env.r_lo)), "every joint must be parked at a limit"
-    parity.check_state_exact(env, orc)
+    check_state_exact(env, orc)
     env.close()
 
 
@@ -70,7 +71,7 @@ def test_one_saturating_env_per_wave_and_none(n):
     action from rest: one pair of a wave takes the saturation block, the quotients of the other lanes are computed and dropped.
     Then the same with all-zero actions: no lane saturates and the block is skipped."""
     for some in (True, False):
-        env, orc = parity.make_pair(n, seed=2, auto_reset=False, max_steps=0)
+        env, orc = make_pair(n, seed=2, auto_reset=False, max_steps=0)
         env.reset(); orc.reset(want_obs=False)
         e = np.arange(n)
         pick = some & ((e % 32) == (e // 32) % 32)
@@ -81,7 +82,7 @@ def test_one_saturating_env_per_wave_and_none(n):
         # a picked env's joints run at v_max (or sit at the upper limit they ran into); nobody else has moved
         assert np.all((st["v"][pick] == env.v_max) | (st["r"][pick] == env.r_hi))
         assert np.all(st["v"][~pick] == 0.0)
-        parity.check_state_exact(env, orc)
+        check_state_exact(env, orc)
         env.close()
 
 
@@ -90,7 +91,7 @@ def test_non_finite_actions_propagate_as_in_the_oracle(n):
     """auto_reset = False; a few envs (in the first, a middle and the ragged last tile) are given NaN, +inf and -inf actions among
     random ones, in some joints or in all of them: a, v, r words equal the oracle's, so a NaN passes through the predictor, the
     clip and the limits exactly as NumPy lets it."""
-    env, orc = parity.make_pair(n, seed=4, auto_reset=False, max_steps=0)
+    env, orc = make_pair(n, seed=4, auto_reset=False, max_steps=0)
     env.reset(); orc.reset(want_obs=False)
     rng = np.random.RandomState(8)
     for t in range(4):
@@ -113,8 +114,8 @@ def test_rollout_of_two_steps_in_the_general_form():
     """pnr_rollout with T = 2 at 64 envs: the general form's t loop, against the oracle stepped twice; saturating actions on half
     of the envs."""
     n, T = 64, 2
-    env, orc = parity.make_pair(n, seed=6, auto_reset=True, max_steps=3)
-    parity.check_obs(env.reset().double().cpu().numpy(), orc.reset())
+    env, orc = make_pair(n, seed=6, auto_reset=True, max_steps=3)
+    bars.check_obs(env.reset().double().cpu().numpy(), orc.reset())
     rng = np.random.RandomState(1)
     for launch in range(3):
         acts = (rng.uniform(-1, 1, size=(T, n, 6)) * env.a_max).astype(np.float32)
@@ -123,7 +124,7 @@ def test_rollout_of_two_steps_in_the_general_form():
         for t in range(T):
             oobs, orew, odone, otrunc = orc.step(acts[t])
             assert np.array_equal(done[t].cpu().numpy(), odone) and np.array_equal(trunc[t].cpu().numpy(), otrunc)
-            assert np.abs(rew[t].double().cpu().numpy() - orew).max() <= parity.REW_TOL
-            parity.check_obs(obs[t].double().cpu().numpy(), oobs)
-    parity.check_state_exact(env, orc)
+            assert np.abs(rew[t].double().cpu().numpy() - orew).max() <= bars.REW_TOL
+            bars.check_obs(obs[t].double().cpu().numpy(), oobs)
+    check_state_exact(env, orc)
     env.close()
