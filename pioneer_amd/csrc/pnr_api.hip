@@ -30,6 +30,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <tuple>
 
 #include "../../include/pioneer_amd.h"
 
@@ -120,6 +121,14 @@ static int launch_reset(pnr_handle h, const KParams& P, int obs_kind, void* stre
     }); });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
+}
+
+// what the form's argument slot holds (pnr_env_kernels.h): the argument of the slot's role, or nothing
+template <int FORM, int SLOT, class Args>
+static WorldSlot<FORM, SLOT> slot_value(const Args& args)
+{
+    constexpr int role = world_role_at(FORM, SLOT);
+    if constexpr (role == kWorldRoles) return NoArg{}; else return std::get<role>(args);
 }
 
 static const char g_unit_fp[] = "pnr_build_fp:api=" PNR_UNIT_FINGERPRINT ";";
@@ -523,115 +532,112 @@ int pnr_set_joint_motor(pnr_handle h, int joint, int control_mode, double target
     return PNR_OK;
 }
 
+// The dynamics-mode world step's one launch, for the four calls below (their checks have passed): dyn_world_kernel<RAND, PHYS, form>
+// with the call's inputs, its motor table W and, for wrenches, its record table.  `form` is one of the six listed here; no other
+// is instantiated.  (Always the instantiation that reads the per-env link scales: without randomisation they are stored as 1.)
+struct WorldStepInputs {
+    const float* targets = nullptr; unsigned mask = 0;      // pnr_world_step_targets
+    const float* tau_ext = nullptr;
+    const float* wrenches = nullptr; LinkWrenchTable T = {};   // pnr_world_step_wrenches
+};
+
+static int launch_world_step(pnr_handle h, int form, const JointMotorTable& W, const WorldStepInputs& in, void* stream)
+{
+    DeviceGuard g(h->device);
+    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
+    bool launched = false;
+    // (forms outermost, in this order: the compiler emits the instantiations in the reverse of it)
+    const auto args = std::make_tuple(in.wrenches, in.targets, in.tau_ext, in.mask, h->dbase, W, in.T);      // by WorldRole
+    with_int<kWorldWrench | kWorldTorque, kWorldTargets | kWorldTorque, kWorldTargets | kWorldCMotor, kWorldTorque, 0, kWorldCMotor>(form, [&](auto F_) {
+        constexpr int F = decltype(F_)::value;
+        with_int<0, 1, 2, 3>(dyn_phys(h->dbase), [&](auto C) {
+            hipLaunchKernelGGL((dyn_world_kernel<true, C(), F>), grid, dim3(kWave), 0, (hipStream_t)stream, h->state, h->dyn, (long long)h->n,
+                               slot_value<F, 0>(args), slot_value<F, 1>(args), slot_value<F, 2>(args), slot_value<F, 3>(args), slot_value<F, 4>(args));
+            launched = true;
+        });
+    });
+    if (!launched) return fail(h, PNR_ERR_INVALID, "world step: form %d is not built", form);
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+// joint torques or wrenches (`input`) next to a constraint motor on `joint`
+static int refuse_constraint_motor(pnr_handle h, const char* call, int joint, const char* input)
+{
+    return fail(h, PNR_ERR_UNSUPPORTED, "%s: joint %d is on a constraint motor (%s input with the boxed solve is not built)", call, joint, input);
+}
+
 int pnr_world_step(pnr_handle h, float* joint_state, void* stream)
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_world_step before the first pnr_reset (or pnr_set_state)");
-    DeviceGuard g(h->device);
-    hipStream_t st = (hipStream_t)stream;
     if (h->cfg.mode != PNR_MODE_DYNAMIC) {
         if (!joint_state) return fail(h, PNR_ERR_INVALID, "pnr_world_step: a kinematic-mode handle steps the caller's joint_state [n][12]");
+        DeviceGuard g(h->device);
         const long long items = h->n * kDof;
-        hipLaunchKernelGGL(kin_world_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, joint_state, (long long)h->n, (float)h->k.dt);
+        hipLaunchKernelGGL(kin_world_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, joint_state, (long long)h->n, (float)h->k.dt);
         HIP_TRY(h, hipGetLastError());
         return PNR_OK;
     }
     if (joint_state) return fail(h, PNR_ERR_INVALID, "pnr_world_step: joint_state must be NULL in dynamics mode (the simulated joints are the handle's)");
-    const DynParams& D = h->dbase;
-    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
-    bool cm = false;                      // a constraint motor anywhere: the instantiation with motor_constraints
-    for (int i = 0; i < kDof; ++i) cm = cm || h->motors.kind[i] != kMotorPD;
-    // (always the instantiation that reads the per-env link scales: without randomisation they are stored as 1)
-    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) { with_bool(cm, [&](auto M) {
-        hipLaunchKernelGGL((dyn_world_kernel<true, C(), M()>), grid, dim3(kWave), 0, st, h->state, h->dyn, (long long)h->n, D, h->motors);
-    }); });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    return launch_world_step(h, has_constraint_motor(h) ? kWorldCMotor : 0, h->motors, {}, stream);
 }
 
 int pnr_world_step_torques(pnr_handle h, const float* joint_torques, void* stream)
 {
+    const char* call = "pnr_world_step_torques";
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (h->cfg.mode != PNR_MODE_DYNAMIC)
-        return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_torques: joint torques exist in dynamics mode only");
-    if (!joint_torques) return fail(h, PNR_ERR_INVALID, "pnr_world_step_torques: null joint_torques");
-    if (!aligned16(joint_torques)) return fail(h, PNR_ERR_INVALID, "pnr_world_step_torques: joint_torques must be 16-byte aligned");
-    if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_world_step_torques before the first pnr_reset (or pnr_set_state)");
-    for (int i = 0; i < kDof; ++i)
-        if (h->motors.kind[i] != kMotorPD)
-            return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_torques: joint %d is on a constraint motor (torque input with the boxed solve is not built)", i);
-    DeviceGuard g(h->device);
-    const DynParams& D = h->dbase;
-    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
-    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) {
-        hipLaunchKernelGGL((dyn_world_torque_kernel<true, C()>), grid, dim3(kWave), 0, (hipStream_t)stream, h->state, h->dyn,
-                           (long long)h->n, joint_torques, D, h->motors);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    if (h->cfg.mode != PNR_MODE_DYNAMIC) return fail(h, PNR_ERR_UNSUPPORTED, "%s: joint torques exist in dynamics mode only", call);
+    if (!joint_torques) return fail(h, PNR_ERR_INVALID, "%s: null joint_torques", call);
+    if (const int rc = check_aligned(h, call, {{joint_torques, "joint_torques", 16}})) return rc;
+    if (!h->ready) return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)", call);
+    int joint;
+    if (has_constraint_motor(h, &joint)) return refuse_constraint_motor(h, call, joint, "torque");
+    WorldStepInputs in;
+    in.tau_ext = joint_torques;
+    return launch_world_step(h, kWorldTorque, h->motors, in, stream);
 }
 
 int pnr_world_step_targets(pnr_handle h, uint32_t joint_mask, const float* targets, const float* joint_torques, void* stream)
 {
-    if (!h) return fail(nullptr, PNR_ERR_INVALID, "pnr_world_step_targets: null handle");
-    if (h->cfg.mode != PNR_MODE_DYNAMIC)
-        return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_targets: joint motors exist in dynamics mode only");
-    if (!targets) return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets: null targets");
-    if (!aligned16(targets)) return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets: targets must be 16-byte aligned");
-    if (joint_torques && !aligned16(joint_torques))
-        return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets: joint_torques must be 16-byte aligned");
+    const char* call = "pnr_world_step_targets";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "%s: null handle", call);
+    if (h->cfg.mode != PNR_MODE_DYNAMIC) return fail(h, PNR_ERR_UNSUPPORTED, "%s: joint motors exist in dynamics mode only", call);
+    if (!targets) return fail(h, PNR_ERR_INVALID, "%s: null targets", call);
+    if (const int rc = check_aligned(h, call, {{targets, "targets", 16}, {joint_torques, "joint_torques", 16}})) return rc;
     if (joint_mask == 0 || joint_mask >> kDof)
-        return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets: joint_mask 0x%x must name at least one of joints 0..5 and no other bit", joint_mask);
-    if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_world_step_targets before the first pnr_reset (or pnr_set_state)");
-    bool cm = false;                      // a constraint motor anywhere: the instantiation with motor_constraints
-    for (int i = 0; i < kDof; ++i) {
-        if (h->motors.kind[i] == kMotorPD) continue;
-        cm = true;
-        if (joint_torques)
-            return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_targets: joint %d is on a constraint motor (torque input with the boxed solve is not built)", i);
-    }
+        return fail(h, PNR_ERR_INVALID, "%s: joint_mask 0x%x must name at least one of joints 0..5 and no other bit", call, joint_mask);
+    if (!h->ready) return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)", call);
+    int joint;
+    const bool cm = has_constraint_motor(h, &joint);
+    if (cm && joint_torques) return refuse_constraint_motor(h, call, joint, "torque");
     // this call's table: the masked joints track the lane's r, v, where the kernel puts the env's targets; h->motors stays as it is
     JointMotorTable W = h->motors;
     for (int i = 0; i < kDof; ++i)
         if ((joint_mask >> i) & 1u) W.from_cmd[i] = 1;
-    DeviceGuard g(h->device);
-    const DynParams& D = h->dbase;
-    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
-    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) { with_bool(cm, [&](auto M) {
-        hipLaunchKernelGGL((dyn_world_target_kernel<true, C(), M()>), grid, dim3(kWave), 0, (hipStream_t)stream, h->state, h->dyn,
-                           (long long)h->n, targets, joint_torques, (unsigned)joint_mask, D, W);
-    }); });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    WorldStepInputs in;
+    in.targets = targets; in.mask = joint_mask; in.tau_ext = joint_torques;
+    return launch_world_step(h, kWorldTargets | (cm ? kWorldCMotor : kWorldTorque), W, in, stream);
 }
 
 int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int n_specs, const float* wrenches,
                             const float* joint_torques, int hold_substeps, void* stream)
 {
+    const char* call = "pnr_world_step_wrenches";
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
-    if (h->cfg.mode != PNR_MODE_DYNAMIC)
-        return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_wrenches: link wrenches exist in dynamics mode only");
-    if (!specs) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: null specs");
-    if (!wrenches) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: null wrenches");
-    if (!aligned16(wrenches)) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: wrenches must be 16-byte aligned");
-    if (joint_torques && !aligned16(joint_torques))
-        return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches: joint_torques must be 16-byte aligned");
-    LinkWrenchTable T;
-    if (const int rc = fill_wrench_table(h, "pnr_world_step_wrenches", specs, n_specs, T)) return rc;      // (pnr_env_host.h)
-    if (!h->ready) return fail(h, PNR_ERR_INVALID, "pnr_world_step_wrenches before the first pnr_reset (or pnr_set_state)");
-    for (int i = 0; i < kDof; ++i)
-        if (h->motors.kind[i] != kMotorPD)
-            return fail(h, PNR_ERR_UNSUPPORTED, "pnr_world_step_wrenches: joint %d is on a constraint motor (wrench input with the boxed solve is not built)", i);
-    DeviceGuard g(h->device);
-    const DynParams& D = h->dbase;
-    T.hold = (hold_substeps <= 0 || hold_substeps >= D.nsub) ? D.nsub : hold_substeps;
-    const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
-    with_int<0, 1, 2, 3>(dyn_phys(D), [&](auto C) {
-        hipLaunchKernelGGL((dyn_world_wrench_kernel<true, C()>), grid, dim3(kWave), 0, (hipStream_t)stream, h->state, h->dyn,
-                           (long long)h->n, wrenches, joint_torques, D, h->motors, T);
-    });
-    HIP_TRY(h, hipGetLastError());
-    return PNR_OK;
+    if (h->cfg.mode != PNR_MODE_DYNAMIC) return fail(h, PNR_ERR_UNSUPPORTED, "%s: link wrenches exist in dynamics mode only", call);
+    if (!specs) return fail(h, PNR_ERR_INVALID, "%s: null specs", call);
+    if (!wrenches) return fail(h, PNR_ERR_INVALID, "%s: null wrenches", call);
+    if (const int rc = check_aligned(h, call, {{wrenches, "wrenches", 16}, {joint_torques, "joint_torques", 16}})) return rc;
+    WorldStepInputs in;
+    if (const int rc = fill_wrench_table(h, call, specs, n_specs, in.T)) return rc;      // (pnr_env_host.h)
+    if (!h->ready) return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)", call);
+    int joint;
+    if (has_constraint_motor(h, &joint)) return refuse_constraint_motor(h, call, joint, "wrench");
+    const int nsub = h->dbase.nsub;
+    in.T.hold = (hold_substeps <= 0 || hold_substeps >= nsub) ? nsub : hold_substeps;
+    in.wrenches = wrenches; in.tau_ext = joint_torques;
+    return launch_world_step(h, kWorldWrench | kWorldTorque, h->motors, in, stream);
 }
 
 }  // extern "C"

@@ -634,6 +634,27 @@ struct LinkWrenchTable {
 // in body coordinates).
 struct WrenchLane { float w[kMaxWrench][9]; };
 
+// env e's records 0 .. T.n - 1 of wrenches [n][T.n][9] (env-major); the lane's other records stay as the caller set them
+__device__ __forceinline__ void load_wrench_records(const float* __restrict__ wrenches, const LinkWrenchTable& T, long long e, WrenchLane& L)
+{
+    const float* wr = wrenches + e * (9 * T.n);
+    static_for<kMaxWrench>([&](auto j_) {
+        constexpr int j = decltype(j_)::value;
+        if (j < T.n) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) L.w[j][i] = wr[9 * j + i];
+        }
+    });
+}
+
+// env e's six joint torques of tau_ext [n][6] (env-major, 24 B per env, 8-byte aligned since the buffer is 16-byte aligned)
+__device__ __forceinline__ void load_joint_torques(const float* __restrict__ tau_ext, long long e, float (&tx)[kDof])
+{
+    const float2* t2 = reinterpret_cast<const float2*>(tau_ext) + 3 * e;
+    const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
+    tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
+}
+
 // R <- R * R(axis_J, q_J): the rotation part of pose_outward
 template <int J>
 __device__ __forceinline__ M3 rot_outward(const M3& Rp, float c, float s)
@@ -985,24 +1006,55 @@ __device__ __forceinline__ void dyn_lane_load(const DynLead& in, long long base,
     for (int p = 0; p < 2; ++p) unpack_record(k[p], L.a + 3 * p, L.v + 3 * p, L.r + 3 * p, L.cw[p]);
 }
 
+// One joint's motor law, for the env step, the world step and pnr_get_joint_states alike: the torque before the caller's joint
+// torque, damping and friction.  SCALED (PHYS bit 1): the law is an acceleration request instead, handed out in ades and scaled
+// and capped inside the ABA; the torque is then 0.
+template <bool SCALED>
+__device__ __forceinline__ float motor_law(float rr, float vr, float q, float qd, float kp, float kd, float cpos, float vcap, float tcap,
+                                           float& ades)
+{
+    const float dq = rr - q;
+    const float v_ask = fminf(fmaxf(vr + cpos * dq, -vcap), vcap);
+    float tq = kp * dq + kd * (v_ask - qd);
+    if constexpr (SCALED) { ades = tq; tq = 0.f; }
+    else { ades = 0.f; tq = fminf(fmaxf(tq, -tcap), tcap); }
+    return tq;
+}
+
+// The world step's options (dyn_core's FORM, dyn_world_kernel's) ..
+enum : int {
+    kWorld = 1,
+    kWorldCMotor = 2,    // W holds constraint motors as well: motor_constraints adds their boxed solve to each sub-step's accelerations
+    kWorldTorque = 4,    // pnr_world_step_torques: tau_ext, the caller's joint torques of this call, are added to each joint's torque in
+                         // every sub-step, after the motor law's own cap and before damping and friction (PyBullet's TORQUE_CONTROL)
+    kWorldWrench = 8,    // pnr_world_step_wrenches: the lane's link wrench records XL under the table X; converted once at the call's
+                         // first pose, they give each of the first X.hold sub-steps its fext (a wave-uniform compare on the loop counter)
+    kWorldTargets = 16,  // pnr_world_step_targets: the caller has put the env's own targets into the lane's r, v for the from_cmd joints.
+                         // The PD law tracks those anyway; a constraint joint with from_cmd set does so only here
+};
+// .. and its operands: an option's are read only where the option is set.  The joint torques are an argument of their own (dyn_core's
+// tau_ext): with the array's address kept in a struct, the kernel's zero fill of it stops being promoted as one vector, the `0 + tau`
+// of the inertia-scaled law is folded into the null-pointer branch, and the targets form with PD motors and PHYS 3 goes from 256
+// VGPRs / 0 AGPRs / two waves per SIMD to 256 / 2 / one.
+struct WorldOperands {
+    const JointMotorTable& W;
+    const LinkWrenchTable* X;      // null without kWorldWrench
+    WrenchLane& XL;
+};
+
 // The arithmetic of phase A, shared by the single-step and the rollout kernels (one text, so that both produce
 // the same bits): command integration with the action latched for the next step, then nsub sub-steps of ABA + PD.
-// WORLD (pnr_world_step): the sub-steps alone — no command integration, no teleport — with the per-joint motor table W.
-// CMOTOR (WORLD only): W holds constraint motors as well; their joints get no torque of the table's law, and motor_constraints
-// adds their boxed solve to each sub-step's accelerations.
-// TORQUE (WORLD only, pnr_world_step_torques): tau_ext[6], the caller's joint torques of this call, are added to each joint's
-// torque in every sub-step, after the motor law's own cap and before damping and friction (PyBullet's TORQUE_CONTROL).
-// WRENCH (WORLD only, pnr_world_step_wrenches): the lane's link wrench records XL under the table X; converted once at the call's
-// first pose, they give each of the first X->hold sub-steps its fext (a wave-uniform compare on the loop counter).
-// LANE_REF (CMOTOR only, pnr_world_step_targets): a constraint joint with from_cmd set tracks the lane's r, v as well, as the PD
-// joints always did; the caller has put the env's own targets there.
-template <int PHYS, bool WORLD = false, bool CMOTOR = false, bool TORQUE = false, bool WRENCH = false, bool LANE_REF = false>
+// FORM: 0 as above (pnr_step, pnr_rollout), or kWorld with the world step's options (pnr_world_step*, World.step): the sub-steps
+// alone — no command integration, no teleport — with the operands `world` refers to.
+template <int PHYS, int FORM = 0>
 __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, float (&a)[kDof], float (&v)[kDof],
                                          float (&r)[kDof], float (&q)[kDof], float (&qd)[kDof], const float (&sc)[kNumLinks],
                                          const float (&fric_)[kDof], const float (&damp_)[kDof], const float (&act)[kDof],
-                                         const JointMotorTable* W = nullptr, const float* tau_ext = nullptr,
-                                         const LinkWrenchTable* X = nullptr, WrenchLane* XL = nullptr)
+                                         const WorldOperands* world = nullptr, const float* tau_ext = nullptr)
 {
+    constexpr bool WORLD = (FORM & kWorld) != 0, CMOTOR = (FORM & kWorldCMotor) != 0, TORQUE = (FORM & kWorldTorque) != 0,
+                   WRENCH = (FORM & kWorldWrench) != 0, TARGETS = (FORM & kWorldTargets) != 0;
+    static_assert(WORLD ? !(CMOTOR && (TORQUE || WRENCH)) : FORM == 0, "the options are the world step's; torque or wrench input with the boxed solve is not built");
     if constexpr (!WORLD) {
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
@@ -1042,26 +1094,22 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
         float c[kDof], s[kDof];
 #pragma unroll
         for (int i = 0; i < kDof; ++i) { c[i] = cs[i].x; s[i] = cs[i].y; }
-        wrench_prepare(*X, c, s, *XL);
+        wrench_prepare(*world->X, c, s, world->XL);
     }
     for (int k = 0; k < D.nsub; ++k) {
         float tau[kDof], qdd[kDof], ades[kDof], tc[kDof];
 #pragma unroll
         for (int i = 0; i < kDof; ++i) {
-            // one motor law; WORLD: the joint's own motor (wave-uniform table entries), which may track a reference of its own
-            // instead of the env's command state
-            const bool cmd = !WORLD || W->from_cmd[i];
-            const float rr = cmd ? r[i] : W->r_ref[i], vr = cmd ? v[i] : W->v_ref[i];
-            const float kpi = WORLD ? W->kp[i] : kp, kdi = WORLD ? W->kd[i] : kd;
-            const float cpi = WORLD ? W->cpos[i] : cpos, vci = WORLD ? W->vcap[i] : vcap;
-            tc[i] = WORLD ? W->tcap[i] : tcap;
-            const float dq = rr - q[i];
-            const float v_ask = fminf(fmaxf(vr + cpi * dq, -vci), vci);
-            float tq = kpi * dq + kdi * (v_ask - qd[i]);
-            if constexpr ((PHYS & 2) != 0) { ades[i] = tq; tq = 0.f; }        // an acceleration request: scaled and capped inside the ABA
-            else { ades[i] = 0.f; tq = fminf(fmaxf(tq, -tc[i]), tc[i]); }
+            // WORLD: the joint's own motor (wave-uniform table entries), which may track a reference of its own instead of the env's
+            // command state
+            const bool cmd = !WORLD || world->W.from_cmd[i];
+            const float rr = cmd ? r[i] : world->W.r_ref[i], vr = cmd ? v[i] : world->W.v_ref[i];
+            const float kpi = WORLD ? world->W.kp[i] : kp, kdi = WORLD ? world->W.kd[i] : kd;
+            const float cpi = WORLD ? world->W.cpos[i] : cpos, vci = WORLD ? world->W.vcap[i] : vcap;
+            tc[i] = WORLD ? world->W.tcap[i] : tcap;
+            float tq = motor_law<(PHYS & 2) != 0>(rr, vr, q[i], qd[i], kpi, kdi, cpi, vci, tc[i], ades[i]);
             if constexpr (CMOTOR) {
-                if (W->kind[i] != kMotorPD) { ades[i] = 0.f; tq = 0.f; }
+                if (world->W.kind[i] != kMotorPD) { ades[i] = 0.f; tq = 0.f; }
             }
             if constexpr (TORQUE) tq += tau_ext[i];
             tq -= damp[i] * qd[i];
@@ -1074,15 +1122,14 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
             for (int i = 0; i < kDof; ++i) { c[i] = cs[i].x; s[i] = cs[i].y; }
             if constexpr (WRENCH) {
                 P3 fx[kDof];
-                if (k < X->hold) wrench_forces(*X, c, s, *XL, fx);
+                if (k < world->X->hold) wrench_forces(*world->X, c, s, world->XL, fx);
                 else {
 #pragma unroll
                     for (int i = 0; i < kDof; ++i) fx[i] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
                 }
                 aba<PHYS, true>(D, M, c, s, qd, tau, ades, tc, qdd, fx);
             } else aba<PHYS>(D, M, c, s, qd, tau, ades, tc, qdd);
-            if constexpr (CMOTOR && LANE_REF) motor_constraints<true>(D, M, c, s, q, qd, *W, inv_h, qdd, r, v);
-            else if constexpr (CMOTOR) motor_constraints(D, M, c, s, q, qd, *W, inv_h, qdd);
+            if constexpr (CMOTOR) motor_constraints<TARGETS>(D, M, c, s, q, qd, world->W, inv_h, qdd, r, v);
         }
 #pragma unroll
         for (int i = 0; i < kDof; ++i) {   // semi-implicit Euler + inelastic joint limits (selects, no branches)

@@ -8,6 +8,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../include/pioneer_amd.h"
@@ -37,6 +38,23 @@ struct pnr_env_s {
 __attribute__((visibility("hidden"))) int fail(pnr_handle h, int code, const char* fmt, ...);
 
 static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+
+// a call's pointer arguments against their alignment, in the order given (a null pointer passes); `call` names it in the message
+struct AlignedArg { const void* p; const char* name; unsigned align; };
+static int check_aligned(pnr_handle h, const char* call, std::initializer_list<AlignedArg> args)
+{
+    for (const AlignedArg& a : args)
+        if (!aligned_to(a.p, a.align)) return fail(h, PNR_ERR_INVALID, "%s: %s must be %u-byte aligned", call, a.name, a.align);
+    return PNR_OK;
+}
+
+// a constraint motor anywhere in the handle's table (the kernels' instantiation with motor_constraints); *joint: the first such joint
+static inline bool has_constraint_motor(pnr_handle h, int* joint = nullptr)
+{
+    for (int i = 0; i < pnr::kDof; ++i)
+        if (h->motors.kind[i] != pnr::kMotorPD) { if (joint) *joint = i; return true; }
+    return false;
+}
 
 template <class T>
 static bool finite_all(const T* v, int k)

@@ -8,6 +8,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <tuple>
+
 #include "pnr_device.h"
 #include "pnr_dyn.h"
 
@@ -602,167 +604,120 @@ __global__ __launch_bounds__(kWave) void reset_kernel(const KParams P, const Dyn
 }
 
 // ---------------------------------------------------------------------------------
-// World.step (bullet_scene.py:273-275), pnr_world_step: frame_skip sub-steps of the simulator and NOTHING else — no command
-// integration, reward, TimeLimit, reset or observation.  One env per lane (the phase-A shape of dyn_step_kernel); the joints'
-// motors are the per-joint table W (Joint.control_position / control_velocity, bullet_scene.py:123-155).  CMOTOR: the table holds
-// at least one of Bullet's constraint motors (motor_constraints, pnr_dyn.h); launched only then.
+// World.step (bullet_scene.py:273-275), the four pnr_world_step* calls: frame_skip sub-steps of the simulator and NOTHING else — no
+// command integration, reward, TimeLimit, reset or observation.  One env per lane (the phase-A shape of dyn_step_kernel); the
+// joints' motors are the per-joint table W (Joint.control_position / control_velocity, bullet_scene.py:123-155).  FORM: the
+// call's options (kWorld*, pnr_dyn.h); the host launches six of their combinations (launch_world_step, pnr_api.hip) and no other
+// is instantiated.  Every load is issued before the sub-step loop, and every branch on an option's input is wave-uniform.
+//   kWorldCMotor   W holds at least one of Bullet's constraint motors (motor_constraints, pnr_dyn.h); launched only then.
+//   kWorldTorque   tau_ext [n][6], the lane's six joint torques.  PD motors only: the host refuses them next to a constraint
+//                  motor.  Next to wrenches or targets the pointer may be null: the branch loads zeros instead, so the call
+//                  without joint torques costs no second set of instantiations.
+//   kWorldWrench   up to four link wrench records per env (wrenches [n][T.n][9], env-major: force | position | torque) under the
+//                  by-value table T.  The records stay in registers over the loop (36 VGPRs; the kernel has no scratch).
+//   kWorldTargets  the env's OWN motor targets (targets [n][12], env-major: position[6] | velocity[6], 48 B per env, 16-byte
+//                  aligned) for the joints of `mask`.  The kernel holds the env's command state r, v in registers for the from_cmd
+//                  joints anyway; the masked joints' r, v are the lane's targets instead (a wave-uniform select per joint, before
+//                  the loop: the twelve loaded values die there and the loop carries what the plain form's carries), and the host
+//                  hands over a copy of the table with from_cmd set for the masked joints.  The row is loaded whole and the
+//                  unmasked joints' entries are dropped by the select, never used in arithmetic.
+// Behind `state, dyn, n` a form takes the arguments that it reads and no other, in the order wrenches | targets | tau_ext | mask |
+// D | W | T: the argument list, the kernarg offsets and the preloaded leading arguments of a kernel written for that form alone.
+// They matter: with D and W eight bytes further on (behind empty one-byte arguments) the plain step measured 0.2 us more per
+// launch at 65 536 envs, and without the targets forms' row, torque pointer and mask preloaded the PD form at PHYS 3 falls to one
+// wave per SIMD.  So the five parameters behind n are slots: slot i holds the form's i-th argument (WorldSlot; an empty struct behind
+// the last), and the body finds an argument by its role (world_arg).  The targets form with constraint motors keeps the torque
+// pointer (never read) between its row and its mask.
 // ---------------------------------------------------------------------------------
-template <bool RAND, int PHYS, bool CMOTOR = false>
-__global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
-                                                          const DynParams D, const JointMotorTable W)
+struct NoArg {};
+enum WorldRole : int { kArgWrenches, kArgTargets, kArgTau, kArgMask, kArgD, kArgW, kArgT, kWorldRoles };
+template <int ROLE> using WorldRoleType = std::tuple_element_t<ROLE, std::tuple<const float*, const float*, const float*, unsigned, DynParams,
+                                                                                  JointMotorTable, LinkWrenchTable>>;
+constexpr int kWorldSlots = 5;
+// (named functions of plain ints: an expression on the flag enum written into a parameter type is mangled into the kernel's name,
+// and for an unnamed enum the host and the device pass number it differently: the launch then finds no such symbol)
+constexpr bool world_has(int form, int role)
 {
+    const bool tg = (form & kWorldTargets) != 0, wr = (form & kWorldWrench) != 0;
+    return role == kArgD || role == kArgW || (role == kArgTau ? tg || (form & kWorldTorque) != 0 : (role == kArgWrenches || role == kArgT) ? wr : tg);
+}
+constexpr int world_slot(int form, int role)        // the role's slot in this form
+{
+    int slot = 0;
+    for (int r = 0; r < role; ++r) slot += world_has(form, r);
+    return slot;
+}
+constexpr int world_role_at(int form, int slot)     // .. and the slot's role; kWorldRoles: none
+{
+    for (int r = 0; r < kWorldRoles; ++r)
+        if (world_has(form, r) && world_slot(form, r) == slot) return r;
+    return kWorldRoles;
+}
+template <int FORM, int SLOT, int ROLE = world_role_at(FORM, SLOT)>
+using WorldSlot = std::conditional_t<ROLE == kWorldRoles, NoArg, WorldRoleType<ROLE == kWorldRoles ? 0 : ROLE>>;
+template <int I, class A, class... R>
+__host__ __device__ __forceinline__ const auto& world_nth(const A& a, const R&... r)
+{
+    if constexpr (I == 0) return a; else return world_nth<I - 1>(r...);
+}
+// the argument of `role` among the form's slots s...
+template <int FORM, int ROLE, class... S>
+__host__ __device__ __forceinline__ const WorldRoleType<ROLE>& world_arg(const S&... s) { return world_nth<world_slot(FORM, ROLE)>(s...); }
+
+template <bool RAND, int PHYS, int FORM>
+__global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
+                                                          const WorldSlot<FORM, 0> s0, const WorldSlot<FORM, 1> s1, const WorldSlot<FORM, 2> s2,
+                                                          const WorldSlot<FORM, 3> s3, const WorldSlot<FORM, 4> s4)
+{
+    const DynParams& D = world_arg<FORM, kArgD>(s0, s1, s2, s3, s4);
+    const JointMotorTable& W = world_arg<FORM, kArgW>(s0, s1, s2, s3, s4);
+    constexpr bool TORQUE = (FORM & kWorldTorque) != 0, WRENCH = (FORM & kWorldWrench) != 0, TARGETS = (FORM & kWorldTargets) != 0;
     const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
     if (e >= n) return;
-    float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof];
+    float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
     HalfRec k[2];                           // the env's command state r, v: what a joint without a command of its own tracks
     load_env_halves(state, n, e, 0, k);
-#pragma unroll
-    for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) {
-        q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
-        fric[i] = dyn[(long long)(kDynFric + i) * n + e]; damp[i] = dyn[(long long)(kDynDamp + i) * n + e];
-        act[i] = 0.f;
+    [[maybe_unused]] float4 g0, g1, g2;     // the env's targets row
+    if constexpr (TARGETS) {
+        const float4* g4 = reinterpret_cast<const float4*>(world_arg<FORM, kArgTargets>(s0, s1, s2, s3, s4)) + 3 * e;
+        g0 = g4[0]; g1 = g4[1]; g2 = g4[2];
     }
 #pragma unroll
-    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
-    const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
-    dyn_core<PHYS, true, CMOTOR>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &W);
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
-}
-
-// pnr_world_step_torques: the same step with the lane's six joint torques (tau_ext [n][6], env-major, 24 B per env, 8-byte
-// aligned since the buffer is 16-byte aligned) loaded with everything else, before the sub-step loop, and handed to
-// dyn_core<.., TORQUE = true>.  PD motors only: the host refuses a table that holds a constraint motor.  A kernel of its own,
-// with the load text repeated: with both kernels routed through one shared device function, dyn_world_kernel's scalar address
-// arithmetic came out two instructions shorter than before, and its instructions are required not to move.
-template <bool RAND, int PHYS>
-__global__ __launch_bounds__(kWave) void dyn_world_torque_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
-                                                                 const float* __restrict__ tau_ext, const DynParams D,
-                                                                 const JointMotorTable W)
-{
-    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
-    if (e >= n) return;
-    float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
-    HalfRec k[2];
-    load_env_halves(state, n, e, 0, k);
-#pragma unroll
     for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
         q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
         fric[i] = dyn[(long long)(kDynFric + i) * n + e]; damp[i] = dyn[(long long)(kDynDamp + i) * n + e];
-        act[i] = 0.f;
-    }
-#pragma unroll
-    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
-    const float2* t2 = reinterpret_cast<const float2*>(tau_ext) + 3 * e;
-    const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
-    tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
-    const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
-    dyn_core<PHYS, true, false, true>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &W, tx);
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
-}
-
-// pnr_world_step_wrenches: the torque step with up to four link wrench records per env (wrenches [n][T.n][9], env-major: force |
-// position | torque) under the by-value table T.  Everything is loaded before the sub-step loop and the records stay in registers
-// over it (36 VGPRs; the kernel has no scratch).  tau_ext may be null: a wave-uniform branch loads zeros, so the call without joint
-// torques costs no second set of instantiations.  A kernel of its own with the load text repeated, as dyn_world_torque_kernel.
-template <bool RAND, int PHYS>
-__global__ __launch_bounds__(kWave) void dyn_world_wrench_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
-                                                                 const float* __restrict__ wrenches, const float* __restrict__ tau_ext,
-                                                                 const DynParams D, const JointMotorTable W, const LinkWrenchTable T)
-{
-    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
-    if (e >= n) return;
-    float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
-    HalfRec k[2];
-    load_env_halves(state, n, e, 0, k);
-#pragma unroll
-    for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) {
-        q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
-        fric[i] = dyn[(long long)(kDynFric + i) * n + e]; damp[i] = dyn[(long long)(kDynDamp + i) * n + e];
-        act[i] = 0.f;
+        act[i] = 0.f; tx[i] = 0.f;
     }
 #pragma unroll
     for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
     WrenchLane XL;
-    const float* wr = wrenches + e * (9 * T.n);
-    static_for<kMaxWrench>([&](auto j_) {
-        constexpr int j = decltype(j_)::value;
+    if constexpr (WRENCH) {
+        static_for<kMaxWrench>([&](auto j_) {
 #pragma unroll
-        for (int i = 0; i < 9; ++i) XL.w[j][i] = 0.f;
-        if (j < T.n) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) XL.w[j][i] = wr[9 * j + i];
-        }
-    });
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) tx[i] = 0.f;
-    if (tau_ext) {
-        const float2* t2 = reinterpret_cast<const float2*>(tau_ext) + 3 * e;
-        const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
-        tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
+            for (int i = 0; i < 9; ++i) XL.w[decltype(j_)::value][i] = 0.f;
+        });
+        load_wrench_records(world_arg<FORM, kArgWrenches>(s0, s1, s2, s3, s4), world_arg<FORM, kArgT>(s0, s1, s2, s3, s4), e, XL);
     }
-    const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
-    dyn_core<PHYS, true, false, true, true>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &W, tx, &T, &XL);
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
-}
-
-// pnr_world_step_targets: the world step with the env's OWN motor targets (targets [n][12], env-major: position[6] | velocity[6],
-// 48 B per env, 16-byte aligned) for the joints of `mask`.  The world kernels hold the env's command state r, v in registers for the
-// from_cmd joints anyway; here the masked joints' r, v are the lane's targets instead (a wave-uniform select per joint, before the
-// sub-step loop: the twelve loaded values die there and the loop carries what dyn_world_kernel's carries), and the host hands over
-// a copy of the table with from_cmd set for the masked joints.  dyn_core's PD law needs nothing more; motor_constraints reads the
-// lane's values for such a joint under LANE_REF.  The row is loaded whole (three float4) and the unmasked joints' entries are
-// dropped by the select, never used in arithmetic.  tau_ext [n][6] may be null: a wave-uniform branch, as in
-// dyn_world_wrench_kernel; the CMOTOR instantiation never reads it (the host refuses torques next to a constraint motor).  A kernel of
-// its own with the load text repeated, as dyn_world_torque_kernel.
-template <bool RAND, int PHYS, bool CMOTOR>
-__global__ __launch_bounds__(kWave) void dyn_world_target_kernel(const float4* __restrict__ state, float* __restrict__ dyn, const long long n,
-                                                                 const float* __restrict__ targets, const float* __restrict__ tau_ext,
-                                                                 const unsigned mask, const DynParams D, const JointMotorTable W)
-{
-    const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
-    if (e >= n) return;
-    float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
-    HalfRec k[2];
-    load_env_halves(state, n, e, 0, k);
-    const float4* g4 = reinterpret_cast<const float4*>(targets) + 3 * e;
-    const float4 g0 = g4[0], g1 = g4[1], g2 = g4[2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) unpack_record(k[p], a + 3 * p, v + 3 * p, r + 3 * p);
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) {
-        q[i] = dyn[(long long)i * n + e]; qd[i] = dyn[(long long)(kDynQd + i) * n + e];
-        fric[i] = dyn[(long long)(kDynFric + i) * n + e]; damp[i] = dyn[(long long)(kDynDamp + i) * n + e];
-        act[i] = 0.f;
+    if constexpr (TORQUE) {
+        const float* tau_ext = world_arg<FORM, kArgTau>(s0, s1, s2, s3, s4);
+        if (!(WRENCH || TARGETS) || tau_ext) load_joint_torques(tau_ext, e, tx);
     }
+    if constexpr (TARGETS) {
+        const float tp[kDof] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y}, tv[kDof] = {g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
 #pragma unroll
-    for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) tx[i] = 0.f;
-    if constexpr (!CMOTOR) {
-        if (tau_ext) {
-            const float2* t2 = reinterpret_cast<const float2*>(tau_ext) + 3 * e;
-            const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
-            tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
+        for (int i = 0; i < kDof; ++i) {
+            const bool own = (world_arg<FORM, kArgMask>(s0, s1, s2, s3, s4) >> i) & 1u;
+            r[i] = own ? tp[i] : r[i];
+            v[i] = own ? tv[i] : v[i];
         }
     }
-    const float tp[kDof] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y}, tv[kDof] = {g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
-#pragma unroll
-    for (int i = 0; i < kDof; ++i) {
-        const bool own = (mask >> i) & 1u;
-        r[i] = own ? tp[i] : r[i];
-        v[i] = own ? tv[i] : v[i];
-    }
     const DynLead lead = {state, dyn, nullptr, n, 0.0, 0.0, 0.f};
-    dyn_core<PHYS, true, CMOTOR, !CMOTOR, false, CMOTOR>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &W, tx);
+    const LinkWrenchTable* X = nullptr;
+    if constexpr (WRENCH) X = &world_arg<FORM, kArgT>(s0, s1, s2, s3, s4);
+    const WorldOperands world = {W, X, XL};
+    dyn_core<PHYS, kWorld | FORM>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &world, tx);
 #pragma unroll
     for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
 }

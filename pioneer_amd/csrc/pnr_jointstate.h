@@ -6,7 +6,7 @@
 // Shape: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  Per lane
 //   1. joints (the caller's [n][12] or the handle's planes: a wave-uniform run-time branch, not a template argument, which
 //      halves the instantiations of a kernel that holds a whole ABA), link scales, friction, damping, the command state r, v;
-//   2. dyn_core's motor-law block for one sub-step, restated (dyn_core itself is the step kernels' and does not move);
+//   2. the motor law of one sub-step (motor_law, pnr_dyn.h: dyn_core's), keeping the law's own torque and the joint losses apart;
 //   3. the external body forces: the caller's records (wrench_prepare / wrench_forces at the current pose, which is that call's
 //      q0) and the penalty contacts (contact_wrenches), added into one fext[6] HERE and handed to aba<.., EXT = true> as external
 //      forces.  aba then runs without its own contact code: fext[b] is subtracted from body b's bias force either way, so the
@@ -125,21 +125,8 @@ __global__ __launch_bounds__(kWave) void joint_state_kernel(const JointStateArgs
 #pragma unroll
         for (int l = 0; l < kNumLinks; ++l) sc[l] = A.dyn[(long long)(kDynScale + l) * n + e];
         if constexpr (EXT) {
-            if (A.tau_ext) {
-                const float2* t2 = reinterpret_cast<const float2*>(A.tau_ext) + 3 * e;
-                const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
-                tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
-            }
-            if (A.wrenches) {
-                const float* wr = A.wrenches + e * (9 * T.n);
-                static_for<kMaxWrench>([&](auto j_) {
-                    constexpr int j = decltype(j_)::value;
-                    if (j < T.n) {
-#pragma unroll
-                        for (int i = 0; i < 9; ++i) XL.w[j][i] = wr[9 * j + i];
-                    }
-                });
-            }
+            if (A.tau_ext) load_joint_torques(A.tau_ext, e, tx);
+            if (A.wrenches) load_wrench_records(A.wrenches, T, e, XL);
         }
     }
 
@@ -149,18 +136,14 @@ __global__ __launch_bounds__(kWave) void joint_state_kernel(const JointStateArgs
 #pragma unroll
     for (int i = 0; i < kDof; ++i) sincos_any(q[i], s[i], c[i]);
 
-    // 2. the motor law of one sub-step (dyn_core's WORLD block): tau = what aba receives, law = the joint's own motor in it
+    // 2. the motor law of one sub-step: tau = what aba receives, law = the joint's own motor in it
     float tau[kDof], ades[kDof], tc[kDof], law[kDof], loss[kDof];
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
         const bool cmd = W.from_cmd[i];
         const float rr = cmd ? r[i] : W.r_ref[i], vr = cmd ? v[i] : W.v_ref[i];
         tc[i] = W.tcap[i];
-        const float dq = rr - q[i];
-        const float v_ask = fminf(fmaxf(vr + W.cpos[i] * dq, -W.vcap[i]), W.vcap[i]);
-        float tq = W.kp[i] * dq + W.kd[i] * (v_ask - qd[i]);
-        if constexpr (SCALED) { ades[i] = tq; tq = 0.f; }             // an acceleration request: scaled and capped inside the ABA
-        else { ades[i] = 0.f; tq = fminf(fmaxf(tq, -tc[i]), tc[i]); }
+        float tq = motor_law<SCALED>(rr, vr, q[i], qd[i], W.kp[i], W.kd[i], W.cpos[i], W.vcap[i], tc[i], ades[i]);
         if constexpr (CMOTOR) {
             if (W.kind[i] != kMotorPD) { ades[i] = 0.f; tq = 0.f; }
         }

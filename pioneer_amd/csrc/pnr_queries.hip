@@ -25,15 +25,6 @@ using namespace pnr;
 static const char g_unit_fp[] = "pnr_build_fp:queries=" PNR_UNIT_FINGERPRINT ";";
 extern "C" const char* pnr_unit_fingerprint_queries(void) { return g_unit_fp; }
 
-// a call's pointer arguments against their alignment, in the order given (a null pointer passes); `call` names it in the message
-struct AlignedArg { const void* p; const char* name; unsigned align; };
-static int check_aligned(pnr_handle h, const char* call, std::initializer_list<AlignedArg> args)
-{
-    for (const AlignedArg& a : args)
-        if (!aligned_to(a.p, a.align)) return fail(h, PNR_ERR_INVALID, "%s: %s must be %u-byte aligned", call, a.name, a.align);
-    return PNR_OK;
-}
-
 // One static body of the scene (pnr_env_host.h: checked, its frame) as the ray casters want it (pnr_render, pnr_ray_test): the
 // world -> primitive rotation rows rt, the half sizes h and the bounding radius (a plane: rows 0 and 1 zero, row 2 its unit world normal, no bound).  Returns the kVis* shape.
 static int scene_body_prim(const pnr_scene_body& S, double (&rt)[9], float (&h)[3], double& bound)
@@ -178,8 +169,7 @@ int pnr_get_joint_states(pnr_handle h, const float* joint_state, const float* jo
         if (const int rc = fill_wrench_table(h, call, specs, n_specs, T)) return rc;
     }
     if (!h->ready) return before_first_reset(h, call);
-    bool cm = false;                                   // a constraint motor anywhere: the instantiation with motor_constraints
-    for (int i = 0; i < kDof; ++i) cm = cm || h->motors.kind[i] != kMotorPD;
+    const bool cm = has_constraint_motor(h);
     const bool ext = joint_torques || n_specs > 0;
     if (cm && ext)
         return fail(h, PNR_ERR_UNSUPPORTED, "%s: a joint is on a constraint motor (torque or wrench input with the boxed solve is not built)", call);
