@@ -18,6 +18,9 @@
  *     and waits for that fill (hipStreamSynchronize(NULL)) before it returns,
  *     so that a first pnr_reset on ANY stream, blocking or not, finds them
  *     zero (pnr_destroy frees memory and synchronises as hipFree does);
+ *     and a SECOND, of the same kind: the first pnr_set_body_params of a
+ *     handle allocates the sphere buffer, zero-fills it on the NULL stream
+ *     and waits for that fill, so that every env is inert on every stream;
  *   - a handle is not thread-safe; distinct handles are independent;
  *   - there is NO CPU backend: pnr_create fails with PNR_ERR_NODEVICE when no
  *     gfx950 device is usable.
@@ -45,7 +48,8 @@ extern "C" {
  *      accepts g_head == NULL with w3_partials; later, additively: pnr_get_link_states, pnr_render,
  *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
  *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
- *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets */
+ *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets, pnr_body_params_default,
+ *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -54,6 +58,7 @@ extern "C" {
 #define PNR_INFO_DIM 4     /* r_pot, r_step, r_done, dist (numeric subset of   */
                            /* the info dict, pioneer_knm_env.py:167-179)      */
 #define PNR_DYN_STATE_WORDS 36 /* dynamics mode: q[6] qd[6] + 24 params       */
+#define PNR_BODY_STATE_WORDS 8 /* the moving sphere: position[3] velocity[3] mass radius */
 #define PNR_NUM_LINKS 11       /* pnr_get_link_states: links per env (URDF joint order) */
 #define PNR_LINK_STATE_DIM 13  /* floats per link record                      */
 #define PNR_JACOBIAN_DIM 36    /* pnr_get_jacobian: 6 rows x 6 joint columns per env */
@@ -595,6 +600,62 @@ int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int
  * float64 reference under that env's table.
  */
 int pnr_world_step_targets(pnr_handle h, uint32_t joint_mask, const float* targets, const float* joint_torques, void* stream);
+
+/*
+ * ONE MOVING SPHERE per env, in dynamics mode: createMultiBody(baseMass > 0) with a sphere collision shape (bullet_scene.py:230-246,
+ * Scene.create_body_sphere :193-204), and the base-item branch of Item.pose / velocity / reset_pose (getBasePositionAndOrientation,
+ * getBaseVelocity, resetBasePositionAndOrientation, bullet_scene.py:53-73).  The world step integrates the sphere together with
+ * the arm; it collides with the arm's contact samples and with everything static.  It is a POINT MASS WITH A RADIUS: position and
+ * linear velocity, no orientation, no spin — ROLLING IS NOT MODELLED.  Boxes and planes stay static.
+ *
+ * State: the handle owns a planar float32 buffer [PNR_BODY_STATE_WORDS][num_envs]: words 0-2 the world position of the centre,
+ * 3-5 the linear velocity, 6 the mass, 7 the radius.  Mass and radius are per env (they can be randomised).  AN ENV WHOSE MASS
+ * WORD IS <= 0 HAS NO SPHERE: it exerts and feels no force, and its eight words are never written.
+ *
+ * The law.  Per sub-step of length h = timestep, every force is evaluated at the state the sub-step starts from; kp, kd are the
+ * params' contact_kp, contact_kd; x, v, m, radius the env's words.
+ *   Sphere against the static world (ground_z, the obstacle box, the n_scene bodies), always surface to surface: with sdf the signed
+ *   distance of the centre to the body's surface (positive outside; the signed-distance forms of the arm's contacts) and n the
+ *   outward normal there, depth = radius - sdf, fn = kp depth - kd (v . n); where depth > 0 and fn > 0 the force is
+ *       fn n - friction fn v_t / sqrt(|v_t|^2 + slip_eps^2),    v_t = v - (v . n) n      (regularised sliding friction).
+ *   Sphere against the arm: the arm's samples are the pointer's sample sphere always and all 23 with link_contacts.  For a sample
+ *   with centre p_s, velocity v_s and radius r_s: d = x - p_s, len = |d|, depth = radius + r_s - len, n = d / len ((0, 0, 1) at
+ *   len == 0), fn = kp depth - kd ((v - v_s) . n); where depth > 0 and fn > 0, +fn n acts on the sphere and -fn n on the sample, where
+ *   it enters the sample's body exactly as a static contact force does.  There is no friction between arm and sphere.
+ *   Integration (semi-implicit Euler, as the joints'): v += h (F / m - linear_damping v - gravity z^), x += h v.
+ * Stability of the explicit penalty spring needs contact_kd timestep < mass and contact_kp timestep^2 < mass: with the defaults
+ * (50, 2000, 1/240) that is mass > 0.21.  Mass and radius are device data and cannot be validated on the host.
+ *
+ * pnr_body_params: contact_kp, contact_kd NaN = the handle's (pnr_config.contact_kp / contact_kd); friction 0.5; slip_eps 0.05;
+ * linear_damping 0 (pnr_body_params_default).
+ * pnr_set_body_params enables the sphere.  Its first call on a handle allocates the buffer and zero-fills it — every env inert
+ * until a state is set — and WAITS for that fill (Conventions: the second synchronising exception); later calls only replace the
+ * params.  params == NULL disables the sphere and keeps the buffer and its contents.  PNR_ERR_UNSUPPORTED: a kinematic-mode handle.
+ * PNR_ERR_INVALID: a null handle, a wrong struct_size, contact_kp <= 0, contact_kd / friction / linear_damping < 0, slip_eps <= 0,
+ * anything non-finite.
+ * pnr_set_body_state writes words [8][num_envs] (device memory, 16-byte aligned, read only) into the buffer with one small kernel;
+ * with mask ([num_envs] bytes, device memory) only the envs with a non-zero byte — the device-side "reset the sphere of the envs
+ * that just finished".  pnr_get_body_state copies the buffer to out [8][num_envs] (16-byte aligned).  Both are asynchronous on
+ * `stream`, never synchronise and allocate nothing; PNR_ERR_INVALID before the first pnr_set_body_params, for a null or misaligned
+ * pointer.  They work while the sphere is disabled.
+ *
+ * With a sphere enabled pnr_world_step, pnr_world_step_torques and pnr_world_step_targets move it (same signatures, same checks, one
+ * launch: the kernels' forms with the sphere, always with contact code).  Not built, and refused with PNR_ERR_UNSUPPORTED in a message
+ * that names the sphere: any of them with a constraint motor in the table, pnr_world_step_wrenches, pnr_get_joint_states.
+ * pnr_step, pnr_rollout and pnr_reset neither move nor see the sphere.  Parity unpinned; checked against a float64 restatement of
+ * this law on the float64 oracle's forward dynamics.
+ */
+typedef struct pnr_body_params {
+    uint32_t struct_size;
+    float contact_kp, contact_kd;
+    float friction;
+    float slip_eps;
+    float linear_damping;
+} pnr_body_params;
+int pnr_body_params_default(pnr_body_params* p);
+int pnr_set_body_params(pnr_handle h, const pnr_body_params* params);
+int pnr_set_body_state(pnr_handle h, const float* words, const uint8_t* mask, void* stream);
+int pnr_get_body_state(pnr_handle h, float* out, void* stream);
 
 /*
  * getJointState for every env of a dynamics-mode handle, one launch: per revolute joint its position, velocity, ACCELERATION and

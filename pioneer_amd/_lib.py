@@ -46,6 +46,7 @@ MAX_LINK_WRENCHES = 4   # pnr_world_step_wrenches: wrench records per env, at mo
 WRENCH_DIM = 9          # .. force[3], position[3], torque[3] per record
 JOINT_STATE_DIM = 4     # pnr_get_joint_states: q, qd, qdd, tau_motor per joint
 REACTION_DIM = 6        # .. Fx, Fy, Fz, Mx, My, Mz per joint
+BODY_STATE_WORDS = 8    # pnr_set_body_state: the moving sphere's position[3], velocity[3], mass, radius (PNR_BODY_STATE_WORDS)
 FRAME_LINK, FRAME_WORLD = 1, 2                     # .. a record's frame (PNR_FRAME_*; pybullet's LINK_FRAME / WORLD_FRAME)
 
 PNR_OK = 0
@@ -68,6 +69,12 @@ SHAPE_PLANE, SHAPE_BOX, SHAPE_SPHERE = 1, 2, 3
 class PnrLinkWrenchSpec(C.Structure):
     """pnr_link_wrench_spec of include/pioneer_amd.h (the call-uniform part of one wrench record of pnr_world_step_wrenches)."""
     _fields_ = [("link", C.c_int32), ("frame", C.c_int32)]
+
+
+class PnrBodyParams(C.Structure):
+    """pnr_body_params of include/pioneer_amd.h (the moving sphere's contact gains, friction and damping)."""
+    _fields_ = [("struct_size", C.c_uint32), ("contact_kp", C.c_float), ("contact_kd", C.c_float), ("friction", C.c_float),
+                ("slip_eps", C.c_float), ("linear_damping", C.c_float)]
 
 
 class PnrSceneBody(C.Structure):
@@ -205,6 +212,10 @@ SIGNATURES = {
     "pnr_set_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_get_dyn_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_dyn_state": (C.c_int, [_VP, _VP, _VP]),
+    "pnr_body_params_default": (C.c_int, [C.POINTER(PnrBodyParams)]),
+    "pnr_set_body_params": (C.c_int, [_VP, C.POINTER(PnrBodyParams)]),
+    "pnr_set_body_state": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "pnr_get_body_state": (C.c_int, [_VP, _VP, _VP]),
     "pnr_get_link_states": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_get_jacobian": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_double * 3), _VP, _VP]),
     "pnr_inverse_dynamics": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
@@ -250,7 +261,7 @@ SIGNATURES = {
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h"]      # what every env-engine unit includes
 UNITS = {
-    # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (116, 88 of them dynamics mode's)
+    # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (121, 92 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
     # the query entry points of the C ABI and their kernels (35)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",

@@ -367,6 +367,7 @@ int pnr_destroy(pnr_handle h)
     if (h->state) (void)hipFree(h->state);
     if (h->dyn) (void)hipFree(h->dyn);
     if (h->scene) (void)hipFree(h->scene);
+    if (h->sphere.words) (void)hipFree(h->sphere.words);
     delete h;
     return PNR_OK;
 }
@@ -533,8 +534,9 @@ int pnr_set_joint_motor(pnr_handle h, int joint, int control_mode, double target
 }
 
 // The dynamics-mode world step's one launch, for the four calls below (their checks have passed): dyn_world_kernel<RAND, PHYS, form>
-// with the call's inputs, its motor table W and, for wrenches, its record table.  `form` is one of the six listed here; no other
-// is instantiated.  (Always the instantiation that reads the per-env link scales: without randomisation they are stored as 1.)
+// with the call's inputs, its motor table W and, for wrenches, its record table.  `form` is one of the eight listed here; no other
+// is instantiated.  With the handle's sphere enabled the torque and the targets form are the ones with kWorldBody (PHYS 1 or 3 only:
+// always with contact code), which the plain call takes too, its joint torques null.  (Always the instantiation that reads the per-env link scales: without randomisation they are stored as 1.)
 struct WorldStepInputs {
     const float* targets = nullptr; unsigned mask = 0;      // pnr_world_step_targets
     const float* tau_ext = nullptr;
@@ -546,15 +548,20 @@ static int launch_world_step(pnr_handle h, int form, const JointMotorTable& W, c
     DeviceGuard g(h->device);
     const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
     bool launched = false;
+    int phys = dyn_phys(h->dbase);
+    WorldBody body = h->sphere;
+    if (h->sphere_on) { form |= kWorldBody | kWorldTorque; phys |= 1; body.joint_mask = in.mask; }
     // (forms outermost, in this order: the compiler emits the instantiations in the reverse of it)
-    const auto args = std::make_tuple(in.wrenches, in.targets, in.tau_ext, in.mask, h->dbase, W, in.T);      // by WorldRole
-    with_int<kWorldWrench | kWorldTorque, kWorldTargets | kWorldTorque, kWorldTargets | kWorldCMotor, kWorldTorque, 0, kWorldCMotor>(form, [&](auto F_) {
+    const auto args = std::make_tuple(in.wrenches, in.targets, in.tau_ext, in.mask, h->dbase, W, in.T, body);      // by WorldRole
+    with_int<kWorldBody | kWorldTargets | kWorldTorque, kWorldBody | kWorldTorque, kWorldWrench | kWorldTorque, kWorldTargets | kWorldTorque,
+             kWorldTargets | kWorldCMotor, kWorldTorque, 0, kWorldCMotor>(form, [&](auto F_) {
         constexpr int F = decltype(F_)::value;
-        with_int<0, 1, 2, 3>(dyn_phys(h->dbase), [&](auto C) {
+        const auto launch = [&](auto C) {
             hipLaunchKernelGGL((dyn_world_kernel<true, C(), F>), grid, dim3(kWave), 0, (hipStream_t)stream, h->state, h->dyn, (long long)h->n,
                                slot_value<F, 0>(args), slot_value<F, 1>(args), slot_value<F, 2>(args), slot_value<F, 3>(args), slot_value<F, 4>(args));
             launched = true;
-        });
+        };
+        if constexpr ((F & kWorldBody) != 0) with_int<1, 3>(phys, launch); else with_int<0, 1, 2, 3>(phys, launch);
     });
     if (!launched) return fail(h, PNR_ERR_INVALID, "world step: form %d is not built", form);
     HIP_TRY(h, hipGetLastError());
@@ -580,6 +587,7 @@ int pnr_world_step(pnr_handle h, float* joint_state, void* stream)
         return PNR_OK;
     }
     if (joint_state) return fail(h, PNR_ERR_INVALID, "pnr_world_step: joint_state must be NULL in dynamics mode (the simulated joints are the handle's)");
+    if (h->sphere_on && has_constraint_motor(h)) return refuse_sphere(h, "pnr_world_step", "a constraint motor");
     return launch_world_step(h, has_constraint_motor(h) ? kWorldCMotor : 0, h->motors, {}, stream);
 }
 
@@ -611,6 +619,7 @@ int pnr_world_step_targets(pnr_handle h, uint32_t joint_mask, const float* targe
     int joint;
     const bool cm = has_constraint_motor(h, &joint);
     if (cm && joint_torques) return refuse_constraint_motor(h, call, joint, "torque");
+    if (cm && h->sphere_on) return refuse_sphere(h, call, "a constraint motor");
     // this call's table: the masked joints track the lane's r, v, where the kernel puts the env's targets; h->motors stays as it is
     JointMotorTable W = h->motors;
     for (int i = 0; i < kDof; ++i)
@@ -634,10 +643,81 @@ int pnr_world_step_wrenches(pnr_handle h, const pnr_link_wrench_spec* specs, int
     if (!h->ready) return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)", call);
     int joint;
     if (has_constraint_motor(h, &joint)) return refuse_constraint_motor(h, call, joint, "wrench");
+    if (h->sphere_on) return refuse_sphere(h, call, "link wrenches");
     const int nsub = h->dbase.nsub;
     in.T.hold = (hold_substeps <= 0 || hold_substeps >= nsub) ? nsub : hold_substeps;
     in.wrenches = wrenches; in.tau_ext = joint_torques;
     return launch_world_step(h, kWorldWrench | kWorldTorque, h->motors, in, stream);
+}
+
+int pnr_body_params_default(pnr_body_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_body_params_default: null params");
+    *p = pnr_body_params{(uint32_t)sizeof(pnr_body_params), NAN, NAN, 0.5f, kFrictionEps, 0.f};
+    return PNR_OK;
+}
+
+int pnr_set_body_params(pnr_handle h, const pnr_body_params* p)
+{
+    const char* call = "pnr_set_body_params";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "%s: null handle", call);
+    if (h->cfg.mode != PNR_MODE_DYNAMIC) return fail(h, PNR_ERR_UNSUPPORTED, "%s: the moving sphere exists in dynamics mode only", call);
+    if (!p) { h->sphere_on = false; return PNR_OK; }
+    if (p->struct_size != sizeof(pnr_body_params))
+        return fail(h, PNR_ERR_INVALID, "%s: struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_body_params));
+    const float kp = p->contact_kp == p->contact_kp ? p->contact_kp : (float)h->cfg.contact_kp;
+    const float kd = p->contact_kd == p->contact_kd ? p->contact_kd : (float)h->cfg.contact_kd;
+    const float all[5] = {kp, kd, p->friction, p->slip_eps, p->linear_damping};
+    if (!finite_all(all, 5)) return fail(h, PNR_ERR_INVALID, "%s: non-finite parameter", call);
+    if (!(kp > 0) || kd < 0) return fail(h, PNR_ERR_INVALID, "%s: contact_kp must be > 0 and contact_kd >= 0 (%g, %g)", call, kp, kd);
+    if (p->friction < 0 || p->linear_damping < 0 || !(p->slip_eps > 0))
+        return fail(h, PNR_ERR_INVALID, "%s: friction and linear_damping must be >= 0 and slip_eps > 0 (%g, %g, %g)", call, p->friction,
+                    p->linear_damping, p->slip_eps);
+    if (!h->sphere.words) {
+        DeviceGuard g(h->device);
+        const size_t bytes = sizeof(float) * PNR_BODY_STATE_WORDS * (size_t)h->n;
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return fail(h, PNR_ERR_NOMEM, "%s: hipMalloc(sphere) failed: %s", call, hipGetErrorString(e));
+        // zero = mass 0 = no sphere in any env; waited for, as pnr_create waits for its fill (a set_body_state on a non-blocking
+        // stream is not ordered after NULL-stream work)
+        e = hipMemset(q, 0, bytes);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) { (void)hipFree(q); return fail(h, PNR_ERR_HIP, "%s: zero fill of the sphere buffer failed: %s", call, hipGetErrorString(e)); }
+        h->sphere.words = (float*)q;
+    }
+    h->sphere.kp = kp; h->sphere.kd = kd; h->sphere.friction = p->friction; h->sphere.slip_eps = p->slip_eps;
+    h->sphere.linear_damping = p->linear_damping;
+    h->sphere_on = true;
+    return PNR_OK;
+}
+
+// the argument checks of pnr_set_body_state / pnr_get_body_state
+static int check_body_state_call(pnr_handle h, const void* words, const char* name, const char* call)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "%s: null handle", call);
+    if (!h->sphere.words) return fail(h, PNR_ERR_INVALID, "%s before pnr_set_body_params (the handle has no sphere buffer)", call);
+    if (!words) return fail(h, PNR_ERR_INVALID, "%s: null %s", call, name);
+    return check_aligned(h, call, {{words, name, 16}});
+}
+
+int pnr_set_body_state(pnr_handle h, const float* words, const uint8_t* mask, void* stream)
+{
+    if (const int rc = check_body_state_call(h, words, "words", "pnr_set_body_state")) return rc;
+    DeviceGuard g(h->device);
+    hipLaunchKernelGGL(body_set_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->sphere.words, words, mask,
+                       (long long)h->n);
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+int pnr_get_body_state(pnr_handle h, float* out, void* stream)
+{
+    if (const int rc = check_body_state_call(h, out, "out", "pnr_get_body_state")) return rc;
+    DeviceGuard g(h->device);
+    const size_t bytes = sizeof(float) * PNR_BODY_STATE_WORDS * (size_t)h->n;      // (outside HIP_TRY, which quotes its argument in the message)
+    HIP_TRY(h, hipMemcpyAsync(out, h->sphere.words, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PNR_OK;
 }
 
 }  // extern "C"

@@ -501,11 +501,98 @@ __device__ __forceinline__ void pose_outward(const M3& Rp, V3 pp, float c, float
     R = {rot<AXJ>(Rp.r0, c, -s), rot<AXJ>(Rp.r1, c, -s), rot<AXJ>(Rp.r2, c, -s)};
 }
 
+// ---------------------------------------------------------------------------------
+// pnr_set_body_params: ONE MOVING SPHERE per env that the world step integrates with the arm (the law is stated in
+// include/pioneer_amd.h): a point mass with a radius — position and linear velocity, no orientation, no spin; rolling is not
+// modelled.  The buffer and the params are the kernel argument WorldBody (its own slot, pnr_env_kernels.h kArgBody); the lane keeps
+// the env's eight words and the sub-step's force in SphereLane.  An env with mass <= 0 has no sphere: it takes and gives no force.
+// ---------------------------------------------------------------------------------
+struct WorldBody {
+    float* words;                        // [PNR_BODY_STATE_WORDS][n]: x[3] v[3] mass radius
+    float kp, kd, friction, slip_eps, linear_damping;
+    unsigned joint_mask;                 // the targets form's joint mask rides here (that form has no slot left for kArgMask)
+};
+struct SphereLane { V3 x, v; float m, r; V3 F; };
+
+// signed distance of l (in the box's frame) to the box of half extents hx, hy, hz and the outward normal there (the forms of
+// sample_contact below: outside the nearest surface point's direction, inside out through the nearest face)
+__device__ __forceinline__ float box_sdf(V3 l, float hx, float hy, float hz, V3& nl)
+{
+    const V3 q = {fabsf(l.x) - hx, fabsf(l.y) - hy, fabsf(l.z) - hz};
+    const V3 o = {fmaxf(q.x, 0.f), fmaxf(q.y, 0.f), fmaxf(q.z, 0.f)};
+    const float out2 = dot(o, o);
+    if (out2 > 0.f) {
+        const float len = sqrtf(out2);
+        nl = {(l.x < 0.f ? -o.x : o.x) / len, (l.y < 0.f ? -o.y : o.y) / len, (l.z < 0.f ? -o.z : o.z) / len};
+        return len;
+    }
+    const int km = (q.x >= q.y && q.x >= q.z) ? 0 : (q.y >= q.z ? 1 : 2);
+    nl = {km == 0 ? (l.x < 0.f ? -1.f : 1.f) : 0.f, km == 1 ? (l.y < 0.f ? -1.f : 1.f) : 0.f, km == 2 ? (l.z < 0.f ? -1.f : 1.f) : 0.f};
+    return comp(q, km);
+}
+
+// one static contact of the sphere, surface to surface: the penalty force along n plus the regularised sliding friction
+__device__ __forceinline__ void sphere_touch(const WorldBody& B, SphereLane& S, float sdf, V3 n)
+{
+    const float depth = S.r - sdf, vn = dot(S.v, n);
+    const float fn = B.kp * depth - B.kd * vn;
+    if (depth > 0.f && fn > 0.f) {
+        const V3 vt = S.v - vn * n;
+        const float k = B.friction * fn * __builtin_amdgcn_rsqf(dot(vt, vt) + B.slip_eps * B.slip_eps);
+        S.F = S.F + fn * n - k * vt;
+    }
+}
+
+// S.F = the static world's force on the sphere at the sub-step's start: the ground plane, the axis-aligned box, the scene's bodies
+__device__ __forceinline__ void sphere_static(const DynParams& D, const WorldBody& B, SphereLane& S)
+{
+    S.F = {0.f, 0.f, 0.f};
+    if (D.has_ground) sphere_touch(B, S, S.x.z - D.ground_z, V3{0.f, 0.f, 1.f});
+    if (D.has_box) {
+        V3 nrm;
+        const float sdf = box_sdf(V3{S.x.x - D.box_c[0], S.x.y - D.box_c[1], S.x.z - D.box_c[2]}, D.box_h[0], D.box_h[1], D.box_h[2], nrm);
+        sphere_touch(B, S, sdf, nrm);
+    }
+#pragma unroll 1
+    for (int b = 0; b < D.n_scene; ++b) {
+        const SceneBody Sb = D.scene[b];
+        const V3 dd = {S.x.x - Sb.pos[0], S.x.y - Sb.pos[1], S.x.z - Sb.pos[2]};
+        V3 nrm; float sdf;
+        if (Sb.shape == 1) {
+            nrm = {Sb.rot[0], Sb.rot[1], Sb.rot[2]};
+            sdf = dot(nrm, dd);
+        } else if (Sb.shape == 3) {
+            const float len = sqrtf(dot(dd, dd));
+            sdf = len - Sb.size[0];
+            nrm = len > 0.f ? (1.f / len) * dd : V3{0.f, 0.f, 1.f};
+        } else {
+            const V3 l = {Sb.rot[0] * dd.x + Sb.rot[3] * dd.y + Sb.rot[6] * dd.z, Sb.rot[1] * dd.x + Sb.rot[4] * dd.y + Sb.rot[7] * dd.z,
+                          Sb.rot[2] * dd.x + Sb.rot[5] * dd.y + Sb.rot[8] * dd.z};
+            V3 nl;
+            sdf = box_sdf(l, Sb.size[0], Sb.size[1], Sb.size[2], nl);
+            nrm = {Sb.rot[0] * nl.x + Sb.rot[1] * nl.y + Sb.rot[2] * nl.z, Sb.rot[3] * nl.x + Sb.rot[4] * nl.y + Sb.rot[5] * nl.z,
+                   Sb.rot[6] * nl.x + Sb.rot[7] * nl.y + Sb.rot[8] * nl.z};
+        }
+        sphere_touch(B, S, sdf, nrm);
+    }
+}
+
+// the sphere's semi-implicit Euler step under S.F, linear damping and gravity (inv_m: 1 / mass)
+__device__ __forceinline__ void sphere_integrate(const DynParams& D, const WorldBody& B, float inv_m, SphereLane& S)
+{
+    const float h = D.dt_sub;
+    S.v = S.v + h * (inv_m * S.F - B.linear_damping * S.v - V3{0.f, 0.f, D.gravity});
+    S.x = S.x + h * S.v;
+}
+
 // Penalty contact of ONE sample sphere (centre c in the frame of the body whose world pose is R, p and whose spatial
 // velocity in body coordinates is vb) with the ground plane and the static axis-aligned box (the reference demo's scene
 // extras, pioneer_knm_env.py:249-261; create_body_plane / create_body_box, bullet_scene.py:206-228): the contact force
 // is added to the body's external spatial force in body coordinates.
-__device__ __forceinline__ void sample_contact(const DynParams& D, const M3& R, V3 p, const P3& vb, V3 c, float radius, P3& fext)
+// SPHERE (kWorldBody): the sample also meets the env's moving sphere S; the pair's force goes to S.F and, reversed, into F here.
+template <bool SPHERE = false>
+__device__ __forceinline__ void sample_contact(const DynParams& D, const M3& R, V3 p, const P3& vb, V3 c, float radius, P3& fext,
+                                               const WorldBody* B = nullptr, SphereLane* S = nullptr)
 {
     const V3 pos = p + mul(R, c);                           // world position of the sphere centre
     const V3 vw = mul(R, lin(vb) + cross(ang(vb), c));      // its world velocity
@@ -574,13 +661,22 @@ __device__ __forceinline__ void sample_contact(const DynParams& D, const M3& R, 
         const float fn = D.ckp * depth - D.ckd * dot(vw, nrm);
         if (depth > 0.f && fn > 0.f) F = F + fn * nrm;
     }
+    if constexpr (SPHERE) {
+        const V3 d = S->x - pos;
+        const float len = sqrtf(dot(d, d));
+        const V3 nrm = len > 0.f ? (1.f / len) * d : V3{0.f, 0.f, 1.f};
+        const float depth = S->r + radius - len;
+        const float fn = B->kp * depth - B->kd * dot(S->v - vw, nrm);
+        if (S->m > 0.f && depth > 0.f && fn > 0.f) { S->F = S->F + fn * nrm; F = F - fn * nrm; }
+    }
     const V3 fb = mulT(R, F);                             // R^T F
     fext = fext + pack(cross(c, fb), fb);
 }
 
 // every sample sphere of moving body BODY (compile-time table kCapsules); without link contacts only the pointer
-template <int BODY>
-__device__ __forceinline__ void body_contacts(const DynParams& D, const M3& R, V3 p, const P3& vb, P3& fext)
+template <int BODY, bool SPHERE = false>
+__device__ __forceinline__ void body_contacts(const DynParams& D, const M3& R, V3 p, const P3& vb, P3& fext, const WorldBody* B = nullptr,
+                                              SphereLane* S = nullptr)
 {
     static_for<kNumCapsules>([&](auto ci_) {
         constexpr int ci = decltype(ci_)::value;
@@ -592,24 +688,25 @@ __device__ __forceinline__ void body_contacts(const DynParams& D, const M3& R, V
                 constexpr bool tip = (ci == kNumCapsules - 1) && (i == K.n - 1);
                 const V3 c = tip ? V3{(float)kTipX, (float)kTipY, (float)kTipZ}
                                  : V3{K.ax + t * (K.bx - K.ax), K.ay + t * (K.by - K.ay), K.az + t * (K.bz - K.az)};
-                if (tip || D.link_contacts) sample_contact(D, R, p, vb, c, K.radius < 0.f ? D.ptr_radius : K.radius, fext);
+                if (tip || D.link_contacts) sample_contact<SPHERE>(D, R, p, vb, c, K.radius < 0.f ? D.ptr_radius : K.radius, fext, B, S);
             });
         }
     });
 }
 
 // the external spatial force of all active contacts on every body, in body coordinates
+template <bool SPHERE = false>
 __device__ __forceinline__ void contact_wrenches(const DynParams& D, const float (&c)[kDof], const float (&s)[kDof],
-                                                 const P3 (&v)[kDof], P3 (&fext)[kDof])
+                                                 const P3 (&v)[kDof], P3 (&fext)[kDof], const WorldBody* B = nullptr, SphereLane* S = nullptr)
 {
     M3 R = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}}, Rn;
     V3 p = {0.f, 0.f, 0.f}, pn;
     pose_outward<0>(R, p, c[0], s[0], Rn, pn); R = Rn; p = pn;          // body 0 (rotator1 + hinge1) carries no samples
-    pose_outward<1>(R, p, c[1], s[1], Rn, pn); R = Rn; p = pn; body_contacts<1>(D, R, p, v[1], fext[1]);
-    pose_outward<2>(R, p, c[2], s[2], Rn, pn); R = Rn; p = pn; body_contacts<2>(D, R, p, v[2], fext[2]);
-    pose_outward<3>(R, p, c[3], s[3], Rn, pn); R = Rn; p = pn; body_contacts<3>(D, R, p, v[3], fext[3]);
-    pose_outward<4>(R, p, c[4], s[4], Rn, pn); R = Rn; p = pn; body_contacts<4>(D, R, p, v[4], fext[4]);
-    pose_outward<5>(R, p, c[5], s[5], Rn, pn); R = Rn; p = pn; body_contacts<5>(D, R, p, v[5], fext[5]);
+    pose_outward<1>(R, p, c[1], s[1], Rn, pn); R = Rn; p = pn; body_contacts<1, SPHERE>(D, R, p, v[1], fext[1], B, S);
+    pose_outward<2>(R, p, c[2], s[2], Rn, pn); R = Rn; p = pn; body_contacts<2, SPHERE>(D, R, p, v[2], fext[2], B, S);
+    pose_outward<3>(R, p, c[3], s[3], Rn, pn); R = Rn; p = pn; body_contacts<3, SPHERE>(D, R, p, v[3], fext[3], B, S);
+    pose_outward<4>(R, p, c[4], s[4], Rn, pn); R = Rn; p = pn; body_contacts<4, SPHERE>(D, R, p, v[4], fext[4], B, S);
+    pose_outward<5>(R, p, c[5], s[5], Rn, pn); R = Rn; p = pn; body_contacts<5, SPHERE>(D, R, p, v[5], fext[5], B, S);
 }
 
 // ---------------------------------------------------------------------------------
@@ -737,10 +834,11 @@ __device__ __forceinline__ void wrench_forces(const LinkWrenchTable& T, const fl
 // PHYS: bit 0 = contacts, bit 1 = the inertia-scaled motor (its acceleration requests in ades, torque cap tcap)
 // EXT (pnr_world_step_wrenches): ext[6], the caller's wrenches of this sub-step in body coordinates; the contacts add into the same
 // fext, and body 0 (which carries no contact samples) has its bias force reduced as well
-template <int PHYS, bool EXT = false>
+// SPHERE (kWorldBody): the contact samples also meet the env's moving sphere, whose force accumulator sphere->F takes its share
+template <int PHYS, bool EXT = false, bool SPHERE = false>
 __device__ __forceinline__ void aba(const DynParams& D, const DynModel& M, const float (&c)[kDof], const float (&s)[kDof],
                                     const float (&qd)[kDof], const float (&tau)[kDof], const float (&ades)[kDof], const float (&tcap)[kDof],
-                                    float (&qdd)[kDof], const P3* ext = nullptr)
+                                    float (&qdd)[kDof], const P3* ext = nullptr, const WorldBody* sphere_p = nullptr, SphereLane* sphere = nullptr)
 {
     constexpr bool CONTACT = (PHYS & 1) != 0, SCALED = (PHYS & 2) != 0;
 
@@ -759,7 +857,7 @@ __device__ __forceinline__ void aba(const DynParams& D, const DynModel& M, const
 #pragma unroll
         for (int i = 0; i < kDof; ++i) fext[i] = EXT ? ext[i] : v0;
     }
-    if (CONTACT) contact_wrenches(D, c, s, v, fext);
+    if (CONTACT) contact_wrenches<SPHERE>(D, c, s, v, fext, sphere_p, sphere);
 
     // pass 2: tip -> base
     DynBody B[kDof];
@@ -1031,6 +1129,8 @@ enum : int {
                          // first pose, they give each of the first X.hold sub-steps its fext (a wave-uniform compare on the loop counter)
     kWorldTargets = 16,  // pnr_world_step_targets: the caller has put the env's own targets into the lane's r, v for the from_cmd joints.
                          // The PD law tracks those anyway; a constraint joint with from_cmd set does so only here
+    kWorldBody = 32,     // pnr_set_body_params: the env's moving sphere (SphereLane, under the params of WorldBody) is integrated with the
+                         // joints: in every sub-step the static world's and the arm samples' forces on it, the samples' reactions in fext
 };
 // .. and its operands: an option's are read only where the option is set.  The joint torques are an argument of their own (dyn_core's
 // tau_ext): with the array's address kept in a struct, the kernel's zero fill of it stops being promoted as one vector, the `0 + tau`
@@ -1050,11 +1150,13 @@ template <int PHYS, int FORM = 0>
 __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, float (&a)[kDof], float (&v)[kDof],
                                          float (&r)[kDof], float (&q)[kDof], float (&qd)[kDof], const float (&sc)[kNumLinks],
                                          const float (&fric_)[kDof], const float (&damp_)[kDof], const float (&act)[kDof],
-                                         const WorldOperands* world = nullptr, const float* tau_ext = nullptr)
+                                         const WorldOperands* world = nullptr, const float* tau_ext = nullptr,
+                                         const WorldBody* body = nullptr, SphereLane* sphere = nullptr)
 {
     constexpr bool WORLD = (FORM & kWorld) != 0, CMOTOR = (FORM & kWorldCMotor) != 0, TORQUE = (FORM & kWorldTorque) != 0,
-                   WRENCH = (FORM & kWorldWrench) != 0, TARGETS = (FORM & kWorldTargets) != 0;
+                   WRENCH = (FORM & kWorldWrench) != 0, TARGETS = (FORM & kWorldTargets) != 0, BODY = (FORM & kWorldBody) != 0;
     static_assert(WORLD ? !(CMOTOR && (TORQUE || WRENCH)) : FORM == 0, "the options are the world step's; torque or wrench input with the boxed solve is not built");
+    static_assert(!BODY || (TORQUE && !WRENCH && !CMOTOR && (PHYS & 1)), "the sphere is built into the torque forms, with contacts");
     if constexpr (!WORLD) {
 #pragma unroll
     for (int i = 0; i < kDof; ++i) {
@@ -1090,6 +1192,8 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
 #pragma unroll
     for (int i = 0; i < kDof; ++i) { float sn, cn; sincos_bounded(q[i], sn, cn); cs[i] = (f2){cn, sn}; }
     [[maybe_unused]] const float inv_h = CMOTOR ? 1.0f / D.dt_sub : 0.f;
+    [[maybe_unused]] float inv_m = 0.f;
+    if constexpr (BODY) inv_m = sphere->m > 0.f ? 1.0f / sphere->m : 0.f;
     if constexpr (WRENCH) {
         float c[kDof], s[kDof];
 #pragma unroll
@@ -1120,6 +1224,11 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
             float c[kDof], s[kDof];
 #pragma unroll
             for (int i = 0; i < kDof; ++i) { c[i] = cs[i].x; s[i] = cs[i].y; }
+            if constexpr (BODY) {      // every force at the state the sub-step starts from, then the sphere's own step
+                sphere_static(D, *body, *sphere);
+                aba<PHYS, false, true>(D, M, c, s, qd, tau, ades, tc, qdd, nullptr, body, sphere);
+                sphere_integrate(D, *body, inv_m, *sphere);
+            } else
             if constexpr (WRENCH) {
                 P3 fx[kDof];
                 if (k < world->X->hold) wrench_forces(*world->X, c, s, world->XL, fx);

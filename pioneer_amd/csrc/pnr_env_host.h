@@ -28,6 +28,8 @@ struct pnr_env_s {
     float4* state;
     float* dyn;          // dynamics-mode planar words [36][n] or null
     pnr::SceneBody* scene;    // dynamics-mode static scene bodies [kMaxScene] or null
+    pnr::WorldBody sphere;    // pnr_set_body_params: the moving sphere's buffer (words; null before the first call) and resolved params
+    bool sphere_on;           // .. and whether the world step moves it (the kWorldBody forms)
     int diag;            // -DPNR_DIAG_BUILD=1 variant only: the PNR_DIAG environment variable at create time; else 0
     bool ready;          // a full reset has happened, or the state was set explicitly
     bool kin_set, dyn_set;  // pnr_set_state / pnr_set_dyn_state seen (both needed in dynamics mode)
@@ -124,6 +126,12 @@ static pnr::SceneBody scene_body_device(const pnr_scene_body& B)
 
 // the dynamics kernels' PHYS template argument: bit 0 contacts (contact-free handles run instantiations without any contact
 // code), bit 1 the inertia-scaled motor
+// with the moving sphere enabled a world-step call with wrenches, a constraint motor, or pnr_get_joint_states is not built
+static inline int refuse_sphere(pnr_handle h, const char* call, const char* what)
+{
+    return fail(h, PNR_ERR_UNSUPPORTED, "%s: the moving sphere is enabled (pnr_set_body_params) and %s with the sphere is not built", call, what);
+}
+
 static inline int dyn_phys(const pnr::DynParams& D) { return ((D.has_ground || D.has_box || D.n_scene > 0) ? 1 : 0) | (D.inertia_scaled ? 2 : 0); }
 
 // pnr_world_step_wrenches' and pnr_get_joint_states' records: a table without records ..

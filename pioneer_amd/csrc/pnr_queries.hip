@@ -173,6 +173,7 @@ int pnr_get_joint_states(pnr_handle h, const float* joint_state, const float* jo
     const bool ext = joint_torques || n_specs > 0;
     if (cm && ext)
         return fail(h, PNR_ERR_UNSUPPORTED, "%s: a joint is on a constraint motor (torque or wrench input with the boxed solve is not built)", call);
+    if (h->sphere_on) return refuse_sphere(h, call, "the joint states");
     T.hold = 1;                                        // (one sub-step is looked at: the records act in it)
     JointStateArgs A;
     A.joints_in = joint_state; A.state = h->state; A.dyn = h->dyn;

@@ -94,6 +94,9 @@ class PioneerKinematicEnv(compat.GymEnv):
             self._vec.set_dyn_state(dyn)
             for args in self._motor_cmds.values():
                 self._vec.set_joint_motor(*args)
+            if old._body_on:                                               # the moving sphere: its params and its state
+                self._vec.set_body(old._body_params)
+                self._vec.set_body_state(old.body_state())
         old.close()
 
     # -- pickling: by constructor arguments, like gym.utils.EzPickle (pioneer_knm_env.py:38, :51) --

@@ -21,7 +21,12 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
 * bodies: ``create_body_box / plane / sphere`` with ``mass == 0``.  The reference's arm has no ``<collision>`` shapes, so there a
   created body never touches it: in kinematic mode a body is a record (``items_by_name``), as inert as in the reference.  In dynamics
   mode a body with a collision shape becomes a static scene body of the engine (``EngineConfig.scene``; the handle is rebuilt with the
-  env's state and the joints' motors carried over).  ``mass > 0`` asserts: moving bodies are not modelled (the reference never creates one).
+  env's state and the joints' motors carried over).  ``create_body_sphere(mass > 0, collision=True)`` on a dynamics-mode env creates
+  the engine's ONE moving sphere (``PioneerVectorEnv.set_body``: a point mass with a radius, no spin — rolling is not modelled):
+  ``world.step()`` moves it, its ``Item.pose() / velocity() / reset_pose()`` are engine calls (the base-item branch of
+  bullet_scene.py:53-73), ``render("rgb_array")`` draws it where it is; a second one, one in kinematic mode or without a collision
+  shape asserts, and so does a box or plane with ``mass > 0``.  The moving sphere is not among the bodies of ``contact_points`` /
+  ``ray_test_batch`` (the batched ``contacts(bodies=[scene_sphere(r)], body_positions=...)`` takes its position per env).
 * ``control_torque(torque)`` (setJointMotorControl2 with TORQUE_CONTROL; the reference's Joint has no such method, Bullet does):
   dynamics mode with the PD motors: the joint's torque for the next ``world.step()`` alone (``pnr_world_step_torques``), next to its
   motor; kinematic mode and ``joint_motor == "constraint"`` raise.
@@ -165,6 +170,30 @@ class Item:
 
     def __repr__(self) -> str:
         return f"Item(name={self.name}, shape={self.shape}, position={self._position}, collision={self.collision})"
+
+
+class BodyItem(Item):
+    """The scene's moving sphere (create_body_sphere with mass > 0): Item's base branch, getBasePositionAndOrientation /
+    getBaseVelocity / resetBasePositionAndOrientation (bullet_scene.py:53-73), on the engine's sphere state.  A point mass with a
+    radius: the orientation stays as created and the angular velocity is zero (rolling is not modelled)."""
+
+    def __init__(self, scene: "Scene", name, radius, position, orientation, rgba_color):
+        super().__init__(name, "sphere", position, orientation, True, (radius, 0.0, 0.0), rgba_color)
+        self._scene = scene
+
+    def _words(self) -> np.ndarray:
+        return self._scene._env._vec.body_state()[0].double().cpu().numpy()
+
+    def pose(self) -> Pose:
+        return Pose(tuple(map(float, self._words()[0:3])), self._orientation)
+
+    def velocity(self) -> Velocity:
+        return Velocity(tuple(map(float, self._words()[3:6])), _ZERO3)
+
+    def reset_pose(self, position, orientation):
+        """resetBasePositionAndOrientation: the sphere at ``position``, at rest (Bullet zeroes the velocities too)"""
+        self._orientation = tuple(map(float, orientation))
+        self._scene._env._vec.set_body(position=tuple(map(float, position)), velocity=_ZERO3)
 
 
 class LinkItem(Item):
@@ -352,13 +381,21 @@ class Scene:
             self.items_by_name[item.name] = item
 
     def _create(self, item: Item, mass: float, body):
-        assert float(mass) == 0.0, "only static bodies (mass 0) are modelled: the reference never creates a moving one"
+        assert float(mass) == 0.0, "only static bodies (mass 0) and one moving sphere are modelled: the reference never creates a moving one"
         self.add_item(item)
         vec = self._env._vec
         if item.collision and vec.engine_config.mode == "dynamic":
             self._env._rebuild_engine(dataclasses.replace(vec.engine_config, scene=tuple(vec.engine_config.scene) + (body,)))
 
     def create_body_sphere(self, name, collision, mass, radius, position, orientation, rgba_color=None):   # bullet_scene.py:193-204
+        if float(mass) > 0.0:                                                  # the engine's one moving sphere (module docstring)
+            vec = self._env._vec
+            assert vec.engine_config.mode == "dynamic", "a moving sphere (mass > 0) exists in dynamics mode only"
+            assert collision, "a moving sphere without a collision shape is not modelled"
+            assert not any(isinstance(i, BodyItem) for i in self.items), "the engine models one moving sphere per env: there is one already"
+            self.add_item(BodyItem(self, name, float(radius), position, orientation, rgba_color or OBSTACLE_RGBA))
+            vec.set_body(mass=float(mass), radius=float(radius), position=tuple(map(float, position)), velocity=_ZERO3)
+            return
         self._create(Item(name, "sphere", position, orientation, collision, (radius, 0.0, 0.0), rgba_color or OBSTACLE_RGBA), mass,
                      scene_sphere(radius, position, orientation))
 
@@ -371,14 +408,14 @@ class Scene:
 
     def render_bodies(self):
         """The created bodies as render_frames draws them: (SceneBody, rgba) of every item but the target."""
-        return [(SceneBody(i.shape, i._position, i._orientation, tuple(map(float, i.size))), i.rgba_color or OBSTACLE_RGBA)
-                for i in self.items if i.name != "target"]
+        return [(SceneBody(i.shape, i.pose().position, i._orientation, tuple(map(float, i.size))), i.rgba_color or OBSTACLE_RGBA)
+                for i in self.items if i.name != "target"]           # (the moving sphere where it is now)
 
     # -- contacts (pybullet.getContactPoints / getClosestPoints) ------------------------------------------------------------
     def collision_items(self) -> List[Item]:
         """The created bodies with a collision shape, in creation order: a body's place here is its body index in the engine's
         query and bodyUniqueIdB - 1."""
-        return [i for i in self.items if i.collision and i.name != "target" and not isinstance(i, LinkItem)]
+        return [i for i in self.items if i.collision and i.name != "target" and not isinstance(i, (LinkItem, BodyItem))]
 
     def _contact_records(self, item: Optional[Item], keep) -> List[ContactPoint]:
         bodies = self.collision_items()

@@ -75,6 +75,7 @@ class PioneerVectorEnv:
                                        C.c_uint64(seed & (2**64 - 1)), C.byref(h)))
         self._h = h
         self._seed = seed
+        self._body_on, self._body_params = False, None      # set_body: the moving sphere is enabled, under these params
 
         self.feature_major_obs = self.engine_config.obs_layout == "feature_major"
         self.feature_major_act = self.engine_config.action_layout == "feature_major"
@@ -243,7 +244,8 @@ class PioneerVectorEnv:
         law, gains, force cap and maxVelocity of each joint stay as ``set_joint_motor`` left them (a joint nobody commanded: the
         EngineConfig's law, the targets standing in for the env's command state).  The other joints' entries are ignored (NaN is
         fine); the position entry of a joint on a velocity law must be finite.  Combines with ``joint_torques`` (same launch), not
-        with ``joint_state`` or ``link_wrenches``.  Never synchronises."""
+        with ``joint_state`` or ``link_wrenches``.  With a moving sphere enabled (``set_body``) the same calls move it too;
+        ``link_wrenches`` and a constraint motor next to it are the engine's to refuse.  Never synchronises."""
         self._check_handle()
         if motor_targets is not None:
             if joint_state is not None:
@@ -286,6 +288,71 @@ class PioneerVectorEnv:
             return
         js = None if joint_state is None else self._out(joint_state, "joint_state", (self.num_envs, 12))
         self._chk(self.lib.pnr_world_step(self._h, _ptr(js), self._stream()))
+
+    # -- the moving sphere ----------------------------------------------------------------
+    def set_body(self, params=None, *, mass=None, radius=None, position=None, velocity=None, mask=None):
+        """One moving sphere per env that ``world_step`` integrates with the arm (pnr_set_body_params + pnr_set_body_state;
+        createMultiBody(baseMass > 0), bullet_scene.py:230-246): a point mass with a radius — position and linear velocity, no
+        orientation, no spin; rolling is not modelled.  It collides with the arm's contact samples (the pointer's; all 23 with
+        ``link_contacts``) and with everything static; include/pioneer_amd.h states the law.  ``params``: a dict of
+        ``contact_kp, contact_kd`` (default: the EngineConfig's), ``friction`` (0.5), ``slip_eps`` (0.05), ``linear_damping`` (0);
+        ``False`` disables the sphere (its state is kept).  ``mass`` / ``radius``: a number or ``[N]``; ``position`` /
+        ``velocity``: ``[3]`` or ``[N, 3]``; each left out keeps what the envs hold (all zero before the first call: mass 0 = no
+        sphere in that env, which takes and gives no force).  ``mask`` (``[N]`` bool / uint8): only these envs' words are written.
+        Stability of the explicit penalty spring needs ``contact_kd * timestep < mass`` and ``contact_kp * timestep**2 < mass``
+        (mass > 0.21 with the defaults).  ``vector_step`` / ``rollout`` / ``reset`` neither move nor see the sphere, and
+        ``render_frames`` / ``contacts`` / ``ray_test`` take it as any per-env body:
+        ``contacts(bodies=[scene_sphere(r)], body_positions=body_state()[:, None, 0:3])``.  The first call allocates and waits for
+        the buffer's zero fill."""
+        self._check_handle()
+        if params is False:
+            self._chk(self.lib.pnr_set_body_params(self._h, None))
+            self._body_on = False
+            return
+        if params is None and self._body_on:                   # a later call without params keeps them
+            params = self._body_params
+        p = _lib.PnrBodyParams()
+        _lib.check(self.lib.pnr_body_params_default(p))
+        for k, v in (params or {}).items():
+            if k not in ("contact_kp", "contact_kd", "friction", "slip_eps", "linear_damping"):
+                raise AssertionError(f"set_body: unknown parameter {k!r}")
+            setattr(p, k, float(v))
+        self._chk(self.lib.pnr_set_body_params(self._h, p))
+        self._body_on, self._body_params = True, dict(params or {})
+        given = dict(mass=mass, radius=radius, position=position, velocity=velocity)
+        if all(v is None for v in given.values()):
+            return
+        n = self.num_envs
+        w = self.body_state().T.contiguous()                                      # [8, N]
+        rows = dict(position=slice(0, 3), velocity=slice(3, 6), mass=slice(6, 7), radius=slice(7, 8))
+        for k, v in given.items():
+            if v is None:
+                continue
+            t = torch.as_tensor(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v), dtype=torch.float32).to(self.device)
+            width = rows[k].stop - rows[k].start
+            t = t.reshape(-1, width) if width == 3 else t.reshape(-1, 1)
+            if t.shape[0] not in (1, n):
+                raise AssertionError(f"set_body: {k} must be one value or one per env")
+            w[rows[k]] = t.expand(n, width).T
+        self.set_body_state(w.T, mask=mask)
+
+    def body_state(self):
+        """The spheres' state, float32 ``[N, 8]`` on the device: position[3] | velocity[3] | mass | radius (pnr_get_body_state; the
+        base-item branch of Item.pose / Item.velocity, bullet_scene.py:53-68)."""
+        self._check_handle()
+        w = self._new((_lib.BODY_STATE_WORDS, self.num_envs))
+        self._chk(self.lib.pnr_get_body_state(self._h, _ptr(w), self._stream()))
+        return w.T
+
+    def set_body_state(self, words, mask=None):
+        """``words`` ``[N, 8]`` (as ``body_state``) into the envs of ``mask`` (``[N]`` bool / uint8 on any device; None: all): the
+        device-side reset of a sphere (pnr_set_body_state; resetBasePositionAndOrientation, bullet_scene.py:70-73)."""
+        self._check_handle()
+        n = self.num_envs
+        w = self._in(words, (n, _lib.BODY_STATE_WORDS), torch.float32, "words").T.contiguous()
+        m = None if mask is None else self._in(torch.as_tensor(mask).to(torch.uint8), (n,), torch.uint8, "mask")
+        self._chk(self.lib.pnr_set_body_state(self._h, _ptr(w), _ptr(m), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()  # `w` and `m` are temporaries
 
     def inverse_dynamics(self, joint_accel=None, joint_state=None, gravity=True, joint_losses=False, out=None):
         """calculateInverseDynamics of every env, one launch (pnr_inverse_dynamics): float32 ``[N, 6]`` joint torques
@@ -633,11 +700,27 @@ class PioneerVectorEnv:
         torch.cuda.current_stream(self.device).synchronize()
 
     def state_dict(self):
-        """Decoded state (numpy, host): a, v, r [N,6]; target [N,3]; potential, step_index, episode [N]."""
+        """Decoded state (numpy, host): a, v, r [N,6]; target [N,3]; potential, step_index, episode [N]; with a moving sphere
+        enabled (``set_body``) also body [N,8]."""
         w = self.get_state().cpu().numpy().view(np.uint32)
         f = w.view(np.float32)
-        return dict(a=f[0:6].T.copy(), v=f[6:12].T.copy(), r=f[12:18].T.copy(), target=f[18:21].T.copy(),
-                    potential=f[21].copy(), step_index=w[22].copy(), episode=w[23].copy())
+        d = dict(a=f[0:6].T.copy(), v=f[6:12].T.copy(), r=f[12:18].T.copy(), target=f[18:21].T.copy(),
+                 potential=f[21].copy(), step_index=w[22].copy(), episode=w[23].copy())
+        if self._body_on:
+            d["body"] = self.body_state().cpu().numpy()
+        return d
+
+    def load_state_dict(self, d):
+        """``state_dict``'s inverse: the command state, and the spheres' where the dict carries a ``body`` key (which needs
+        ``set_body`` first: the params are not part of the state)."""
+        w = np.zeros((_lib.STATE_WORDS, self.num_envs), dtype=np.uint32)
+        f = w.view(np.float32)
+        f[0:6], f[6:12], f[12:18], f[18:21] = (np.asarray(d[k], dtype=np.float32).T for k in ("a", "v", "r", "target"))
+        f[21] = d["potential"]
+        w[22], w[23] = d["step_index"], d["episode"]
+        self.set_state(torch.from_numpy(w.view(np.int32)))
+        if "body" in d:
+            self.set_body_state(d["body"])
 
     def __reduce__(self):
         """Pickled by constructor arguments (a fresh batch, like the reference's EzPickle envs);

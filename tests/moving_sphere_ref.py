@@ -1,0 +1,193 @@
+"""Independent float64 reference of the moving sphere (pnr_set_body_params; one sphere per env that the world step integrates with
+the arm).  The law is the one stated in include/pioneer_amd.h: a point mass with a radius, no orientation, no spin (rolling is
+not modelled).  Per sub-step of length h, every force at the state the sub-step starts from:
+    static world   depth = radius - sdf, fn = kp depth - kd (v . n); where depth > 0 and fn > 0:
+                   F += fn n - friction fn v_t / sqrt(|v_t|^2 + slip_eps^2), v_t = v - (v . n) n
+    arm samples    d = x - p_s, depth = radius + r_s - |d|, n = d / |d| ((0, 0, 1) at |d| = 0), fn = kp depth - kd ((v - v_s) . n);
+                   where depth > 0 and fn > 0: +fn n on the sphere, -fn n on the sample's body at the sample's centre
+    integration    v += h (F / m - linear_damping v - g z^), x += h v; the joints as tests/external_force_ref.py integrates them
+An env with mass <= 0 has no sphere.
+
+Built on the float64 oracle's forward dynamics (DynOracle.contact_samples / contact_wrenches / aba_ext / aba_motor, through
+tests/external_force_ref.py's `accelerations`, which takes the sphere's reactions in its fext slot) and on the URDF chain's poses
+and velocities (tests/link_kinematics_ref.py).  The signed-distance forms are restated here in numpy.  It reads nothing of
+pioneer_amd.  `storage32` rounds the sphere's and the joints' state to float32 after every sub-step: the reference's own
+float32-storage deviation is what the GPU test's sphere bars are taken from.
+"""
+import numpy as np
+
+import external_force_ref as ext
+import link_kinematics_ref as lk
+
+DOF = 6
+DEFAULTS = dict(contact_kp=None, contact_kd=None, friction=0.5, slip_eps=0.05, linear_damping=0.0)      # None: the handle's
+
+
+def params_of(orc, params=None):
+    p = dict(DEFAULTS, **(params or {}))
+    if p["contact_kp"] is None:
+        p["contact_kp"] = float(orc.d.contact_kp)
+    if p["contact_kd"] is None:
+        p["contact_kd"] = float(orc.d.contact_kd)
+    return p
+
+
+def sphere(x, v, m, r):
+    """the spheres' state as this module carries it: float64 copies of x, v [n, 3], m, r [n]"""
+    return dict(x=np.array(x, dtype=np.float64), v=np.array(v, dtype=np.float64), m=np.array(m, dtype=np.float64), r=np.array(r, dtype=np.float64))
+
+
+def from_words(w):
+    """[8, n] planar words (pnr_get_body_state) -> the state dict"""
+    w = np.asarray(w, dtype=np.float64)
+    return sphere(w[0:3].T, w[3:6].T, w[6], w[7])
+
+
+# ---- signed distances of points x [n, 3] to the static bodies: (sdf [n], outward unit normal [n, 3]) ----------------------------
+def _box_sdf(l, half):
+    q = np.abs(l) - half
+    o = np.maximum(q, 0.0)
+    length = np.linalg.norm(o, axis=1)
+    sign = np.where(l < 0, -1.0, 1.0)
+    outside = length > 0
+    n_out = sign * o / np.where(outside, length, 1.0)[:, None]
+    km = np.where((q[:, 0] >= q[:, 1]) & (q[:, 0] >= q[:, 2]), 0, np.where(q[:, 1] >= q[:, 2], 1, 2))
+    n_in = np.zeros_like(l)
+    rows = np.arange(len(l))
+    n_in[rows, km] = sign[rows, km]
+    return np.where(outside, length, q[rows, km]), np.where(outside[:, None], n_out, n_in)
+
+
+def static_bodies(orc):
+    """[(kind, data)] of the oracle's static world: ("plane", (normal, point)), ("box", (R, centre, half)), ("sphere", (centre, radius))"""
+    d = orc.d
+    out = []
+    if d.ground_z == d.ground_z:
+        out.append(("plane", (np.array([0.0, 0.0, 1.0]), np.array([0.0, 0.0, d.ground_z]))))
+    half = np.array(d.obstacle_half_extents[:])
+    if np.all(half > 0):
+        out.append(("box", (np.eye(3), np.array(d.obstacle_position[:]), half)))
+    for i in range(d.n_scene):
+        b = d.scene[i]
+        quat = np.array(b.orientation[:])
+        R = lk.matrix_from_quat((quat / np.linalg.norm(quat))[None])[0]
+        pos, size = np.array(b.position[:]), np.array(b.size[:])
+        if b.shape == 1:
+            out.append(("plane", (R @ size / np.linalg.norm(size), pos)))
+        elif b.shape == 2:
+            out.append(("box", (R, pos, size)))
+        else:
+            out.append(("sphere", (pos, size[0])))
+    return out
+
+
+def body_sdf(kind, data, x):
+    if kind == "plane":
+        nrm, point = data
+        return (x - point) @ nrm, np.broadcast_to(nrm, x.shape)
+    if kind == "sphere":
+        centre, radius = data
+        dd = x - centre
+        length = np.linalg.norm(dd, axis=1)
+        nrm = np.where((length > 0)[:, None], dd / np.where(length > 0, length, 1.0)[:, None], np.array([0.0, 0.0, 1.0]))
+        return length - radius, nrm
+    R, centre, half = data
+    sdf, nl = _box_sdf((x - centre) @ R, half)                       # into the box's frame: R^T dd
+    return sdf, nl @ R.T
+
+
+def static_force(orc, s, p):
+    """F [n, 3] of the static world on the spheres, and whether each touches anything"""
+    x, v = s["x"], s["v"]
+    F = np.zeros_like(x)
+    touching = np.zeros(len(x), dtype=bool)
+    for kind, data in static_bodies(orc):
+        sdf, nrm = body_sdf(kind, data, x)
+        depth = s["r"] - sdf
+        vn = np.einsum("ni,ni->n", v, nrm)
+        fn = p["contact_kp"] * depth - p["contact_kd"] * vn
+        on = (depth > 0) & (fn > 0) & (s["m"] > 0)
+        vt = v - vn[:, None] * nrm
+        fr = p["friction"] * fn / np.sqrt(np.einsum("ni,ni->n", vt, vt) + p["slip_eps"] ** 2)
+        F += np.where(on[:, None], fn[:, None] * nrm - fr[:, None] * vt, 0.0)
+        touching |= on
+    return F, touching
+
+
+# ---- the arm's samples ----------------------------------------------------------------------------------------------------------
+def samples_world(orc):
+    """[(body, c, radius, position [n, 3], velocity [n, 3], R_b [n, 3, 3])] of the arm's active contact samples at the oracle's
+    joints: the pointer's sample always, all 23 with link_contacts (DynOracle.contact_samples)."""
+    q, qd = orc.dstate["q"], orc.dstate["qd"]
+    R, o, v, w = lk.link_frames(q, qd)
+    links = ext.body_links()
+    out = []
+    for body, c, radius in orc.contact_samples():
+        radius = radius if radius >= 0 else float(orc.d.pointer_radius)        # (the oracle's table marks the pointer's with -1)
+        k = links[body]
+        rc = np.einsum("nij,j->ni", R[:, k], c)
+        out.append((body, c, radius, o[:, k] + rc, v[:, k] + np.cross(w[:, k], rc), R[:, k]))
+    return out
+
+
+def arm_forces(orc, s, p):
+    """(F [n, 3] of the arm's samples on the spheres, fext [n, 6, 6] of the reactions on the arm's bodies (n_b | f_b, body
+    coordinates), touching [n])"""
+    n = orc.n
+    F, fext, touching = np.zeros((n, 3)), np.zeros((n, DOF, 6)), np.zeros(n, dtype=bool)
+    for body, c, radius, pos, vel, Rb in samples_world(orc):
+        d = s["x"] - pos
+        length = np.linalg.norm(d, axis=1)
+        nrm = np.where((length > 0)[:, None], d / np.where(length > 0, length, 1.0)[:, None], np.array([0.0, 0.0, 1.0]))
+        depth = s["r"] + radius - length
+        fn = p["contact_kp"] * depth - p["contact_kd"] * np.einsum("ni,ni->n", s["v"] - vel, nrm)
+        on = (depth > 0) & (fn > 0) & (s["m"] > 0)
+        f = np.where(on[:, None], fn[:, None] * nrm, 0.0)
+        F += f
+        fb = np.einsum("nji,nj->ni", Rb, -f)                           # R_b^T (-f): the reaction in body coordinates
+        fext[:, body, 0:3] += np.cross(c, fb)
+        fext[:, body, 3:6] += fb
+        touching |= on
+    return F, fext, touching
+
+
+def _f32(a):
+    return a.astype(np.float32).astype(np.float64)
+
+
+def world_step(orc, motors, s, params=None, tau_ext=None, targets=None, joints=(), storage32=False, frame_skip=None, h=1.0 / 240):
+    """One World.step of every env of the oracle's batch and its spheres `s`, in place on orc.dstate and s.  targets [n, 12]
+    (position[6] | velocity[6]) for the joints `joints`: they stand in for the env's command state r, v of those joints during the
+    call (joints on the env-wide law, motors[j] None).  Returns (the arm's force on the sphere in the first sub-step [n, 3],
+    touching the arm in the first sub-step [n], touching the static world in the first sub-step [n])."""
+    p = params_of(orc, params)
+    nsub = orc.d.frame_skip if frame_skip is None else frame_skip
+    g = float(orc.d.gravity)
+    tau = None if tau_ext is None else np.asarray(tau_ext, dtype=np.float64)
+    keep = None
+    if targets is not None:
+        assert all(motors[j] is None for j in joints)
+        keep = orc.state["r"].copy(), orc.state["v"].copy()
+        for j in joints:
+            orc.state["r"][:, j] = targets[:, j]
+            orc.state["v"][:, j] = targets[:, 6 + j]
+    first = None
+    live = s["m"] > 0
+    inv_m = np.where(live, 1.0 / np.where(live, s["m"], 1.0), 0.0)
+    for k in range(nsub):
+        Fs, on_static = static_force(orc, s, p)
+        Fa, fext, on_arm = arm_forces(orc, s, p)
+        qdd = ext.accelerations(orc, motors, fext, tau)
+        if first is None:
+            first = Fa.copy(), on_arm, on_static
+        ext.integrate(orc, qdd, h)
+        acc = (Fs + Fa) * inv_m[:, None] - p["linear_damping"] * s["v"] - np.array([0.0, 0.0, g])
+        vn = s["v"] + h * acc
+        s["v"] = np.where(live[:, None], vn, s["v"])
+        s["x"] = np.where(live[:, None], s["x"] + h * vn, s["x"])
+        if storage32:
+            orc.dstate["q"], orc.dstate["qd"] = _f32(orc.dstate["q"]), _f32(orc.dstate["qd"])
+            s["x"], s["v"] = _f32(s["x"]), _f32(s["v"])
+    if keep is not None:
+        orc.state["r"], orc.state["v"] = keep
+    return first

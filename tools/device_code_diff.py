@@ -12,7 +12,10 @@ Order is ignored: each listing is split at the kernel symbols into the function 
 .amdhsa_kernel descriptor block, compared as text.  For a body that differs the per-opcode count delta (after - before) is printed
 with it: "reordered only" when the instruction mix is the same.  Masked: the function's index in the listing, which numbers its local labels
 (.LBB<i>_<k>, .Lfunc_end<i>), and the assembler comments, which quote those labels.  A kernel that two listings of one side hold
-is an error (two units would compile, and the library would hold, the same kernel).  Exit status 0: no such kernel, same kernel
+is an error (two units would compile, and the library would hold, the same kernel).  --by-template-arguments pairs the kernels by
+their mangled name up to the end of the template argument list, without the parameter types (a kernel whose parameter types are
+written in terms of a role enum or a type list, dyn_world_kernel, is renamed by an addition to either; its code need not change),
+and masks the name inside body and descriptor.  Exit status 0: no such kernel, same kernel
 names, no body or descriptor differs; then the number of kernels each listing holds is printed too."""
 import argparse
 import collections
@@ -20,7 +23,13 @@ import re
 import sys
 
 
-def kernels(path):
+def short_name(name):
+    """the mangled name up to the end of its template argument list (the whole name of a kernel that is no template)"""
+    cut = name.find("EEv")
+    return name if cut < 0 else name[:cut + 2]
+
+
+def kernels(path, by_template_arguments=False):
     text = open(path).read()
     out = {}
     for m in re.finditer(r"^\t\.amdhsa_kernel (\S+)\n.*?^\t\.end_amdhsa_kernel\n", text, re.M | re.S):
@@ -28,15 +37,21 @@ def kernels(path):
         body = re.search(r"^%s:.*?^(\.Lfunc_end(\d+)):\n" % re.escape(name), text, re.M | re.S)
         idx = body.group(2)
         code = re.sub(r"[ \t]*;.*$", "", body.group(0), flags=re.M)
-        out[name] = (re.sub(r"(\.L[A-Za-z_]+)%s(?!\d)" % idx, r"\1#", code), m.group(0))
+        k = (re.sub(r"(\.L[A-Za-z_]+)%s(?!\d)" % idx, r"\1#", code), m.group(0))
+        if by_template_arguments:
+            short = short_name(name)
+            assert short not in out, f"{path}: two kernels shorten to {short}"
+            out[short] = tuple(t.replace(name, short) for t in k)
+        else:
+            out[name] = k
     return out
 
 
-def side(paths):
+def side(paths, by_template_arguments=False):
     """({kernel: (body, descriptor)}, {kernel: its listing}, [(kernel, listing, listing) held twice]) of one side's listings"""
     merged, where, twice = {}, {}, []
     for path in paths:
-        for name, k in kernels(path).items():
+        for name, k in kernels(path, by_template_arguments).items():
             if name in merged:
                 twice.append((name, where[name], path))
             merged[name], where[name] = k, path
@@ -50,8 +65,8 @@ def opcode_delta(x, y):
     return {o: cy[o] - cx[o] for o in sorted(set(cx) | set(cy)) if cx[o] != cy[o]}
 
 
-def main(before, after):
-    (a, a_where, a_twice), (b, b_where, b_twice) = side(before), side(after)
+def main(before, after, by_template_arguments=False, new_allowed=False):
+    (a, a_where, a_twice), (b, b_where, b_twice) = side(before, by_template_arguments), side(after, by_template_arguments)
     for when, twice in (("before", a_twice), ("after", b_twice)):
         for name, p, q in twice:
             print(f"twice {when}: {name}  ({p}, {q})")
@@ -62,7 +77,7 @@ def main(before, after):
         for k in names:
             delta = opcode_delta(a[k][0], b[k][0]) if names is bodies else None
             print(f"{what}: {k}" + ("" if delta is None else f"  {delta or 'reordered only'}"))
-    bad = bool(a_twice or b_twice or gone or new or bodies or descs)
+    bad = bool(a_twice or b_twice or gone or (new and not new_allowed) or bodies or descs)
     if not bad:
         for when, where in (("before", a_where), ("after", b_where)):
             for path, count in collections.Counter(where.values()).items():
@@ -76,5 +91,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--before", nargs="+", required=True, metavar="LISTING")
     ap.add_argument("--after", nargs="+", required=True, metavar="LISTING")
+    ap.add_argument("--by-template-arguments", action="store_true", help="pair kernels by name and template arguments, not parameter types")
+    ap.add_argument("--new-allowed", action="store_true", help="kernels only the after side holds are listed but are no failure (a feature adds kernels)")
     args = ap.parse_args()
-    sys.exit(main(args.before, args.after))
+    sys.exit(main(args.before, args.after, args.by_template_arguments, args.new_allowed))
