@@ -1,11 +1,12 @@
 """The input sets of the constraint-motor tests, shared by the CPU tests (which assert on the float64 reference that the inputs
 bite) and the GPU tests (which run the kernel on exactly these inputs), and deliberately WRONG solvers of the boxed problem that
-the CPU tests use to show what the inputs tell apart.  Nothing here is a reference: that is tests/constraint_motor_ref.py.
+the CPU tests use to show what the inputs tell apart.  Nothing here is a reference: that is tests/world_step_ref.py with
+tests/constraint_motor_ref.py.
 """
 import numpy as np
 
+import oracle_cases as ocases
 from oracle import DynOracle
-from oracle.binding import ORC_DEV
 
 DOF = 6
 H = 1.0 / 240
@@ -45,29 +46,9 @@ CASES = {
 GRAVITY = 9.81
 
 
-def oracle_dyn(case):
-    """the oracle's params for a case's EngineConfig arguments"""
-    e = CASES[case]["engine"]
-    d = dict(gravity=GRAVITY, randomize=int(e.get("randomize", False)), pd_inertia_scaled=int(e.get("pd_inertia_scaled", False)),
-             kp=e.get("pd_kp", 4000.0), kd=e.get("pd_kd", 400.0), torque_limit=e.get("torque_limit", 0.0))
-    return d
-
-
-def command_actions(case, n, a_max):
-    """the actions of the vector steps that move the command state off its reset values before the motors are set"""
-    rng = np.random.default_rng(1000 + CASES[case]["seed"])
-    return [(rng.uniform(-0.3, 0.3, (n, DOF)) * a_max).astype(np.float32) for _ in range(CASES[case].get("command_steps", 0))]
-
-
 def make_oracle(case, n):
-    """The float64 oracle of a case after its reset and command steps: per-env link scales, friction, damping and command state
-    as the engine draws them (tests/test_gpu_dynamics.py holds the two to the same bits)."""
     c = CASES[case]
-    orc = DynOracle(n, seed=c["seed"], precision=ORC_DEV, frame_skip=c["frame_skip"], dyn=oracle_dyn(case))
-    orc.reset()
-    for act in command_actions(case, n, orc.a_max):
-        orc.step(act)
-    return orc
+    return ocases.make_oracle(c["seed"], n, c["frame_skip"], GRAVITY, c["engine"], c.get("command_steps", 0))
 
 
 def states(case, n, step):
@@ -88,10 +69,6 @@ def _limits():
         orc = DynOracle(1)
         _LIMITS.append((orc.r_lo.astype(np.float64), orc.r_hi.astype(np.float64)))
     return _LIMITS[0]
-
-
-def load_oracle(orc, q, qd):
-    orc.dstate["q"], orc.dstate["qd"] = q.astype(np.float64), qd.astype(np.float64)
 
 
 # ---- wrong solvers of  v = b + A tau  (A = h M^-1 over S, SPD), each a mistake a kernel could make ----------------------------

@@ -30,12 +30,6 @@ def phase_b_oracle(n, seed=0, auto_reset=False, max_episode_steps=0, dyn=None, *
                        dyn=dict(dyn or {}, frame_skip=0), **tunables)
 
 
-def load_q_qd(orc, q, qd):
-    """q, qd [n, 6] (float32 values) into the oracle's simulated state; the per-env parameters stay."""
-    orc.dstate["q"] = np.asarray(q, dtype=np.float64)
-    orc.dstate["qd"] = np.asarray(qd, dtype=np.float64)
-
-
 def targets_near(orc, jp, lo, hi, rng):
     """float32 targets at distance U(lo, hi) from the pointer at joints jp [n, 6], in a random direction."""
     ptr = orc.fk(np.asarray(jp, dtype=np.float64))

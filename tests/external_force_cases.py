@@ -1,6 +1,6 @@
 """The inputs of the external-force tests, shared by the CPU tests (which assert on the float64 reference that the inputs are well
 conditioned and that the wrenches matter) and the GPU tests (which run the kernel on exactly these inputs).  Nothing here is a
-reference: that is tests/external_force_ref.py.
+reference: that is tests/world_step_ref.py with tests/external_force_ref.py.
 
 Every input is a float32 number (the engine's input format), held in float64 where the reference reads it, and comes from a
 generator of its own, so the inputs of n envs are the first n rows of the inputs of N_MAX envs: what the CPU tests establish on the
@@ -21,8 +21,7 @@ import numpy as np
 
 import bars
 import ik_ref
-from oracle import DynOracle
-from oracle.binding import ORC_DEV
+import oracle_cases as ocases
 
 DOF = 6
 N_MAX = 1000
@@ -57,25 +56,9 @@ def followed(n):
     return np.arange(n) if n <= 64 else np.array([e for e in range(n) if e % 8 == 0 or e >= (n // 64) * 64])
 
 
-def oracle_dyn(family):
-    """the oracle's params for a family's EngineConfig arguments"""
-    f = FAMILIES[family]
-    e = f["engine"]
-    d = dict(gravity=f["gravity"], randomize=int(e.get("randomize", False)), pd_inertia_scaled=int(e.get("pd_inertia_scaled", False)),
-             kp=e.get("pd_kp", 4000.0), kd=e.get("pd_kd", 400.0), torque_limit=e.get("torque_limit", 0.0),
-             link_contacts=int(e.get("link_contacts", False)))
-    if "ground_z" in e:
-        d["ground_z"] = e["ground_z"]
-    return d
-
-
 def make_oracle(family, n, reset=True):
-    """The float64 oracle of a family: after reset(), the per-env link scales, friction, damping and command state the engine
-    draws from the same seed (tests/test_gpu_dynamics.py holds the two to the same bits)."""
-    orc = DynOracle(n, seed=FAMILIES[family]["seed"], precision=ORC_DEV, frame_skip=FRAME_SKIP, dyn=oracle_dyn(family))
-    if reset:
-        orc.reset(want_obs=False)
-    return orc
+    f = FAMILIES[family]
+    return ocases.make_oracle(f["seed"], n, FRAME_SKIP, f["gravity"], f["engine"], reset=reset)
 
 
 def states(family, r_cmd, rounded=True):

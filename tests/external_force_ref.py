@@ -8,25 +8,18 @@ fixed joints merged) and to the link origin's fixed offset d in body coordinates
                     f_b = R_b(q_k)^T force,  n_b = p_b x f_b + R_b(q_k)^T torque
     fext[b] += (n_b, f_b) in the first `hold` sub-steps, on top of the contact wrenches; link 0 (the welded base) does nothing.
 
-Built on the float64 oracle's forward dynamics alone (DynOracle.aba_ext / aba_motor with their fext slot, orc_dyn_motor_torque,
-contact_wrenches), which tests/test_dyn_oracle.py validates, in the manner of tests/constraint_motor_ref.py, whose motor
-dictionaries and table law it uses; the poses R_b, o_b and the link offsets come from tests/link_kinematics_ref.py (the URDF chain
-of tests/golden/urdf_chain.json), not from the oracle or the engine.  The integrator is restated: semi-implicit Euler with the
-inelastic joint limits (orc_dyn_substep's).  It reads nothing of pioneer_amd.  Numbers are used as the engine stores them,
-rounded to float32.
+This module turns the records into fext (`prepare` once per call, `body_wrenches` per sub-step); the sub-step that takes fext is
+tests/world_step_ref.py's, whose world_step(wrenches=(specs, w), hold_substeps=...) is the reference of the call.  The poses R_b,
+o_b and the link offsets come from tests/link_kinematics_ref.py (the URDF chain of tests/golden/urdf_chain.json), not from the
+oracle or the engine.  It reads nothing of pioneer_amd.
 """
-import ctypes as C
-
 import numpy as np
 
-import constraint_motor_ref as cref
 import ik_ref
 import link_kinematics_ref as lk
-from oracle.binding import OrcDynParams
 
 DOF = 6
 NUM_LINKS = 11
-FRICTION_EPS = cref.FRICTION_EPS
 
 
 def body_links():
@@ -91,61 +84,3 @@ def body_wrenches(records, q):
         fext[:, b, 0:3] += nb
         fext[:, b, 3:6] += fb
     return fext
-
-
-def accelerations(orc, motors, fext, tau_ext=None):
-    """qdd [n, 6] at the oracle's current states: the joints' motors (constraint_motor_ref's dictionaries; PD kinds or None), the
-    joint losses, the caller's joint torques, the contacts' wrenches plus fext [n, 6, 6]."""
-    assert not cref.constraint_set(motors)
-    n, d = orc.n, orc.d
-    orc.lib.orc_dyn_motor_torque.restype = C.c_double
-    scaled = bool(d.pd_inertia_scaled)
-    contacts = d.ground_z == d.ground_z or d.obstacle_half_extents[0] > 0 or d.n_scene > 0
-    u = OrcDynParams()
-    qdd = np.empty((n, DOF))
-    for e in range(n):
-        q, qd = orc.dstate["q"][e], orc.dstate["qd"][e]
-        r_cmd, v_cmd = orc.state["r"][e], orc.state["v"][e].astype(np.float64)
-        law = np.array([cref._pd_torque(orc, motors[i], u, r_cmd[i], v_cmd[i], q[i], qd[i], scaled) for i in range(DOF)])
-        tau = -orc.dstate["damping"][e] * qd - orc.dstate["friction"][e] * qd / np.sqrt(qd * qd + FRICTION_EPS ** 2)
-        if tau_ext is not None:
-            tau = tau + tau_ext[e]
-        f = fext[e]
-        if contacts:
-            hit, fc = orc.contact_wrenches(e)
-            if hit:
-                f = f + fc
-        if scaled:
-            caps = {cref._f32(m.get("max_force", d.torque_limit)) for m in motors if m is not None and m["kind"] == "pd"}
-            assert caps <= {float(d.torque_limit)}, "orc_dyn_aba_motor takes one cap for all joints"
-            qdd[e] = orc.aba_motor(tau, law, d.torque_limit, d.gravity, f, e)
-        else:
-            qdd[e] = orc.aba_ext(tau + law, d.gravity, f, e)
-    return qdd
-
-
-def integrate(orc, qdd, h):
-    """semi-implicit Euler with the inelastic joint limits, in place on orc.dstate"""
-    q, qd = orc.dstate["q"], orc.dstate["qd"]
-    lo, hi = np.array(orc.p.r_lo[:], dtype=np.float64), np.array(orc.p.r_hi[:], dtype=np.float64)
-    qdn = qd + h * qdd
-    qn = q + h * qdn
-    qdn[(qn > hi) & (qdn > 0)] = 0.0
-    qdn[(qn < lo) & (qdn < 0)] = 0.0
-    orc.dstate["q"], orc.dstate["qd"] = np.clip(qn, lo, hi), qdn
-
-
-def world_step(orc, motors, specs=(), wrenches=None, tau_ext=None, hold_substeps=0, frame_skip=None, h=1.0 / 240):
-    """One World.step of every env of the oracle's batch, in place on orc.dstate.  Returns the sub-steps' qdd."""
-    nsub = orc.d.frame_skip if frame_skip is None else frame_skip
-    hold = nsub if hold_substeps <= 0 or hold_substeps >= nsub else hold_substeps
-    records = prepare(specs, wrenches, orc.dstate["q"].copy()) if len(specs) else []
-    tau = None if tau_ext is None else np.asarray(tau_ext, dtype=np.float64)
-    zero = np.zeros((orc.n, DOF, 6))
-    out = []
-    for k in range(nsub):
-        fext = body_wrenches(records, orc.dstate["q"]) if k < hold and records else zero
-        qdd = accelerations(orc, motors, fext, tau)
-        integrate(orc, qdd, h)
-        out.append(qdd)
-    return out

@@ -23,6 +23,8 @@ import numpy as np
 
 import ik_ref
 import inverse_dynamics_ref as ref
+import oracle_cases as ocases
+import world_step_ref as wref
 from oracle import DynOracle
 
 DOF = 6
@@ -56,9 +58,7 @@ def joints(n, frac=0.9, qd_max=3.0, qdd_max=20.0, seed=SEED):
 
 def make_oracle(n, gravity, randomize, seed=SEED, **dyn):
     """A reset oracle batch: unit link scales and the configured losses, or the per-env draws of `seed` (the engine's own)."""
-    orc = DynOracle(n, seed=seed, dyn=dict(gravity=gravity, randomize=int(randomize), **dyn))
-    orc.reset(want_obs=False)
-    return orc
+    return ocases.make_oracle(seed, n, 10, gravity, dict(dyn, randomize=randomize))
 
 
 def free_joints(orc):
@@ -72,7 +72,7 @@ FREE_MOTORS = [dict(kind="pd", control_mode=1, target_velocity=0.0, position_gai
 
 def losses32(qd, friction, damping):
     qd, friction, damping = (np.asarray(x, dtype=np.float32) for x in (qd, friction, damping))
-    return damping * qd + friction * qd / np.sqrt(qd * qd + np.float32(ref.FRICTION_EPS) ** 2)
+    return damping * qd + friction * qd / np.sqrt(qd * qd + np.float32(wref.FRICTION_EPS) ** 2)
 
 
 def tau_floor(q, qd, qdd, scales, gravity, friction=None, damping=None):
@@ -84,7 +84,7 @@ def tau_floor(q, qd, qdd, scales, gravity, friction=None, damping=None):
     if friction is not None:
         t32 = t32 + losses32(qd, friction, damping)
         qd64 = f32(qd).astype(np.float64)
-        t64 = t64 + f32(damping).astype(np.float64) * qd64 + f32(friction).astype(np.float64) * qd64 / np.sqrt(qd64 * qd64 + ref.FRICTION_EPS ** 2)
+        t64 = t64 + f32(damping).astype(np.float64) * qd64 + f32(friction).astype(np.float64) * qd64 / np.sqrt(qd64 * qd64 + wref.FRICTION_EPS ** 2)
     return np.abs(t32.astype(np.float64) - t64).max(axis=0), np.median(np.abs(t64), axis=0)
 
 

@@ -1,13 +1,11 @@
-"""Independent float64 reference of pnr_inverse_dynamics, pnr_mass_matrix and pnr_world_step_torques.
+"""Independent float64 reference of pnr_inverse_dynamics and pnr_mass_matrix.  (pnr_world_step_torques' is
+tests/world_step_ref.py's world_step(tau_ext=...): the forward dynamics of losses + motor law + tau_ext, directly.)
 
-Built on the float64 oracle's forward dynamics alone (DynOracle.aba_ext, which tests/test_dyn_oracle.py validates), in the style
-of tests/constraint_motor_ref.py, whose free_dynamics it uses for the torque world step; it reads nothing of pioneer_amd and
-restates neither a mass-matrix algorithm nor an inverse-dynamics recursion:
+Built on the float64 oracle's forward dynamics alone (DynOracle.aba_ext, which tests/test_dyn_oracle.py validates); it reads
+nothing of pioneer_amd and restates neither a mass-matrix algorithm nor an inverse-dynamics recursion:
   * M^-1 comes column by column from the ABA's affinity in tau (ABA(e_j) at qd = 0 without gravity), and M = inv(M^-1);
   * bias = C(q, qd) qd + G(q) = -M ABA(0, gravity);
-  * tau = M qdd + bias, plus the engine's joint losses damping qd + friction qd / sqrt(qd^2 + eps^2) when asked for;
-  * a torque world step is qdd = qdd_free + M^-1 tau_ext per sub-step, then the semi-implicit Euler and inelastic joint limits of
-    constraint_motor_ref.substep.
+  * tau = M qdd + bias, plus the engine's joint losses (world_step_ref.losses) when asked for.
 
 newton_euler() is a SECOND statement of the same torques, from tests/golden/urdf_chain.json alone: a world-frame Newton-Euler
 sweep over the 11 URDF links (mass s_l, inertia s_l 1 about the link frame origin), projected on the joint axes.  Every array
@@ -16,23 +14,11 @@ of it has the dtype it is called with: in float64 the CPU tests hold it against 
 """
 import numpy as np
 
-import constraint_motor_ref as cref
 import link_kinematics_ref as lk
+import world_step_ref as wref
 
 DOF = 6
 LINKS = 11
-FRICTION_EPS = cref.FRICTION_EPS
-
-
-def set_states(orc, q, qd, scales=None, friction=None, damping=None):
-    """Put q, qd [n, 6] (and optionally the per-env parameters) into the oracle's dynamics state."""
-    orc.dstate["q"], orc.dstate["qd"] = np.asarray(q, dtype=np.float64), np.asarray(qd, dtype=np.float64)
-    if scales is not None:
-        orc.dstate["mass_scale"] = np.asarray(scales, dtype=np.float64)
-    if friction is not None:
-        orc.dstate["friction"] = np.asarray(friction, dtype=np.float64)
-    if damping is not None:
-        orc.dstate["damping"] = np.asarray(damping, dtype=np.float64)
 
 
 def aba(orc, tau, gravity):
@@ -57,36 +43,11 @@ def mass_and_bias(orc, gravity):
     return M, Minv, -np.einsum("nij,nj->ni", M, qdd0)
 
 
-def losses(orc):
-    qd = orc.dstate["qd"]
-    return orc.dstate["damping"] * qd + orc.dstate["friction"] * qd / np.sqrt(qd * qd + FRICTION_EPS ** 2)
-
-
 def inverse_dynamics(orc, qdd=None, gravity=0.0, joint_losses=False):
     """tau [n, 6] = M qdd + C qd + G (+ the joint losses)."""
     M, _, bias = mass_and_bias(orc, gravity)
     tau = bias if qdd is None else bias + np.einsum("nij,nj->ni", M, np.asarray(qdd, dtype=np.float64))
-    return tau + losses(orc) if joint_losses else tau
-
-
-def torque_substep(orc, motors, tau_ext, h=1.0 / 240):
-    """One sub-step with the external joint torques tau_ext [n, 6], in place on orc.dstate (motors: PD kinds or None only)."""
-    assert not cref.constraint_set(motors)
-    qdd_free, Minv = cref.free_dynamics(orc, motors)
-    qdd = qdd_free + np.einsum("nij,nj->ni", Minv, np.asarray(tau_ext, dtype=np.float64))
-    q, qd = orc.dstate["q"], orc.dstate["qd"]
-    qd_plus = qd + h * qdd
-    lo, hi = np.array(orc.p.r_lo[:], dtype=np.float64), np.array(orc.p.r_hi[:], dtype=np.float64)
-    qn = q + h * qd_plus
-    qdn = qd_plus.copy()
-    qdn[(qn > hi) & (qdn > 0)] = 0.0
-    qdn[(qn < lo) & (qdn < 0)] = 0.0
-    orc.dstate["q"], orc.dstate["qd"] = np.clip(qn, lo, hi), qdn
-
-
-def world_step_torques(orc, motors, tau_ext, frame_skip=None, h=1.0 / 240):
-    for _ in range(orc.d.frame_skip if frame_skip is None else frame_skip):
-        torque_substep(orc, motors, tau_ext, h)
+    return tau + wref.losses(orc) if joint_losses else tau
 
 
 # ---- the second statement: world-frame Newton-Euler over the URDF links, in the caller's dtype -----------------------------------

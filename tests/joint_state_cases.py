@@ -168,6 +168,8 @@ import ik_ref
 import inverse_dynamics_cases as idcases
 import inverse_dynamics_ref as idref
 import joint_state_ref as ref
+import oracle_cases as ocases
+import world_step_ref as wref
 
 DOF = 6
 N_MAX = 1000
@@ -206,7 +208,7 @@ def family_inputs(family, n=N_MAX):
     """The oracle of a family's first n envs with the family's states loaded, and the call's inputs (float32 numbers)."""
     orc = xcases.make_oracle(family, n)
     q, qd = xcases.states(family, orc.state["r"][:n])
-    idref.set_states(orc, q, qd)
+    ocases.load_states(orc, q, qd)
     f = xcases.FAMILIES[family]
     return orc, dict(motors=f["motors"], specs=f["specs"], wrenches=xcases.wrenches(family, q), tau=xcases.joint_torques(family, n), q=q, qd=qd)
 
@@ -222,7 +224,7 @@ def hold_inputs(n=N_MAX, orc=None, rounded=True):
     """The gravity-hold scenario: (oracle, inputs).  rounded: the torques as the engine receives them, float32."""
     orc = orc or hold_oracle(n)
     q = idcases.hold_poses(n)
-    idref.set_states(orc, q, np.zeros_like(q))
+    ocases.load_states(orc, q, np.zeros_like(q))
     q64 = q.astype(np.float64)
     tip = ik_ref.point_position(q64, 10)
     J = ik_ref.jacobian(q64, 10)
@@ -238,7 +240,7 @@ def hold_inputs(n=N_MAX, orc=None, rounded=True):
 def constraint_inputs(case, n=N_MAX):
     orc = ccases.make_oracle(case, n)
     q, qd = ccases.states(case, n, 0)
-    ccases.load_oracle(orc, q, qd)
+    ocases.load_states(orc, q, qd)
     return orc, dict(motors=ccases.CASES[case]["motors"], specs=(), wrenches=None, tau=None, q=q, qd=qd)
 
 
@@ -313,14 +315,14 @@ def floors(name, n=N_MAX, seed=7):
     res = {}
     for with_w, with_t in forms(name):
         out = res.setdefault(form_name(with_w, with_t), {})
-        idref.set_states(orc, I["q"], I["qd"])
+        ocases.load_states(orc, I["q"], I["qd"])
         R = reference(orc, I, with_w, with_t)
         sc, g = orc.dstate["mass_scale"].copy(), orc.d.gravity
         tx = np.zeros((n, DOF)) if not with_t else np.asarray(I["tau"], dtype=np.float64)
         # (a) the float32 restatements on the same float32 inputs
         r32 = ref.newton_euler_reaction(f32(I["q"]), f32(I["qd"]), f32(R["qdd"]), f32(sc), g, f32(R["fext"]), np.float32).astype(np.float64)
         d_react = np.abs(r32 - R["reaction"])
-        rec32 = (ref.axis_moment(f32(r32)) - f32(tx) + f32(ref.losses(orc))).astype(np.float64)
+        rec32 = (ref.axis_moment(f32(r32)) - f32(tx) + f32(wref.losses(orc))).astype(np.float64)
         law32 = np.full((n, DOF), np.nan) if cm else pd_law32(orc, I["motors"]).astype(np.float64)
         d_tau = np.where(np.isnan(law32), np.abs(rec32 - R["tau_motor"]), np.abs(law32 - R["tau_motor"]))
         q32 = ref.forward32(f32(I["q"]), f32(I["qd"]), f32(sc), g, f32(R["fext"]), f32(R["total"]), np.float32).astype(np.float64)
@@ -329,10 +331,10 @@ def floors(name, n=N_MAX, seed=7):
         # (b) one float32 ulp on q and qd, random signs, through the whole float64 reference
         rng = np.random.default_rng(seed)
         qm, qdm = _ulp_moved(I["q"], rng), _ulp_moved(I["qd"], rng)
-        idref.set_states(orc, qm, qdm)
+        ocases.load_states(orc, qm, qdm)
         P = reference(orc, I, with_w, with_t)
         at = ref.newton_euler_reaction(qm.astype(np.float64), qdm.astype(np.float64), R["qdd"], sc, g, P["fext"], np.float64)
-        idref.set_states(orc, I["q"], I["qd"])
+        ocases.load_states(orc, I["q"], I["qd"])
         whole, fixed = np.maximum(d_react, np.abs(P["reaction"] - R["reaction"])), np.maximum(d_react, np.abs(at - R["reaction"]))
         cand = dict(qdd=np.maximum(d_qdd, np.abs(P["qdd"] - R["qdd"])), tau=np.maximum(d_tau, np.abs(P["tau_motor"] - R["tau_motor"])),
                     force=split(whole)[0].max(axis=2), moment=split(whole)[1].max(axis=2),

@@ -1,10 +1,10 @@
 """Independent float64 reference of pnr_get_joint_states: per joint q̈ and the motor torque of the world step's first sub-step, and
 the joints' reaction wrenches.
 
-  * q̈: external_force_ref.accelerations (the float64 oracle's forward dynamics with the motors' table law, the joint losses, the
-    caller's joint torques, the contacts' wrenches and the caller's) for PD and inertia-scaled motors; constraint_motor_ref.substep
+  * q̈: world_step_ref.accelerations (the float64 oracle's forward dynamics with the motors' table law, the joint losses, the
+    caller's joint torques, the contacts' wrenches and the caller's) for PD and inertia-scaled motors; constraint_motor_ref.constrain
     for constraint motors: (qd_plus - qd) / h, qd_plus before the joint limits act.
-  * the motor torque: the oracle's table law as constraint_motor_ref._pd_torque gives it; a constraint joint's is substep's tau.
+  * the motor torque: the oracle's table law as world_step_ref.table_law gives it; a constraint joint's is constrain's tau.
     The inertia-scaled law's torque is formed inside the oracle's ABA and not handed out: there the stated identity is used,
     tau_motor = (the reaction's moment along the joint axis) - joint_torque + damping + friction, evaluated in float64.
   * the reaction: a world-frame Newton-Euler sweep over the 11 URDF links (inverse_dynamics_ref._sweep: per link F = s acc,
@@ -16,36 +16,23 @@ newton_euler_reaction takes a dtype, as inverse_dynamics_ref.newton_euler does: 
 floor is measured with (tests/joint_state_cases.py); forward32 restates q̈ the same way, from the Newton-Euler mass matrix and bias.
 It reads nothing of pioneer_amd.
 """
-import ctypes as C
-
 import numpy as np
 
 import constraint_motor_ref as cref
 import external_force_ref as xref
 import inverse_dynamics_ref as idref
 import link_kinematics_ref as lk
-from oracle.binding import OrcDynParams
+import world_step_ref as wref
 
 DOF = 6
 LINKS = 11
-FRICTION_EPS = cref.FRICTION_EPS
-
-
-def losses(orc):
-    qd = orc.dstate["qd"]
-    return orc.dstate["damping"] * qd + orc.dstate["friction"] * qd / np.sqrt(qd * qd + FRICTION_EPS ** 2)
-
-
-def has_contacts(orc):
-    d = orc.d
-    return bool(d.ground_z == d.ground_z or d.obstacle_half_extents[0] > 0 or d.n_scene > 0)
 
 
 def contact_wrenches(orc):
     """[n, 6, 6] per body n_b | f_b (body coordinates) of the oracle's contacts at its current states, and who is in contact [n]"""
     f = np.zeros((orc.n, DOF, 6))
     hit = np.zeros(orc.n, dtype=bool)
-    if has_contacts(orc):
+    if wref.has_contacts(orc):
         for e in range(orc.n):
             hit[e], f[e] = orc.contact_wrenches(e)
     return f, hit
@@ -57,24 +44,6 @@ def external_wrenches(orc, specs=(), wrenches=None):
         return np.zeros((orc.n, DOF, 6))
     q = orc.dstate["q"].copy()
     return xref.body_wrenches(xref.prepare(specs, wrenches, q), q)
-
-
-def table_law(orc, motors):
-    """[n, 6]: the PD table law's torque after its cap (0 for a constraint joint; NaN where the inertia-scaled law applies)"""
-    orc.lib.orc_dyn_motor_torque.restype = C.c_double
-    scaled = bool(orc.d.pd_inertia_scaled)
-    u = OrcDynParams()
-    out = np.zeros((orc.n, DOF))
-    for e in range(orc.n):
-        q, qd = orc.dstate["q"][e], orc.dstate["qd"][e]
-        r_cmd, v_cmd = orc.state["r"][e], orc.state["v"][e].astype(np.float64)
-        for i in range(DOF):
-            m = motors[i]
-            if scaled and (m is None or m["kind"] == "pd"):
-                out[e, i] = np.nan
-            else:
-                out[e, i] = cref._pd_torque(orc, m, u, r_cmd[i], v_cmd[i], q[i], qd[i], False)
-    return out
 
 
 # ---- the Newton-Euler part, in the caller's dtype ------------------------------------------------------------------------------------
@@ -156,22 +125,21 @@ def joint_states(orc, motors, specs=(), wrenches=None, tau_ext=None, h=1.0 / 240
     tx = np.zeros((n, DOF)) if tau_ext is None else np.asarray(tau_ext, dtype=np.float64)
     fc, hit = contact_wrenches(orc)
     fx = external_wrenches(orc, specs, wrenches)
-    law = table_law(orc, motors)
+    law = wref.table_law(orc, motors)
     out = dict(hit=hit, fext=fc + fx)
     S = cref.constraint_set(motors)
     if S:
         assert tau_ext is None and not len(specs)
-        sub = cref.substep(orc, motors, h)
-        orc.dstate["q"], orc.dstate["qd"] = q.copy(), qd.copy()       # substep integrated: put the states back
+        sub = cref.constrain(orc, motors, *wref.free_dynamics(orc, motors), h)
         qdd = (sub["qd_plus"] - qd) / h
         law[:, S] = sub["tau"]
         out.update(Minv=sub["Minv"], S=S)
     else:
-        qdd = xref.accelerations(orc, motors, fc * 0 + fx, None if tau_ext is None else tx)      # (it adds the contacts itself)
+        qdd = wref.accelerations(orc, motors, fx, None if tau_ext is None else tx)      # (it adds the contacts itself)
     g = orc.d.gravity if gravity is None else gravity
     f_used = (fc if contacts else 0 * fc) + (fx if use_wrenches else 0 * fx)
     reaction = newton_euler_reaction(q, qd, qdd, orc.dstate["mass_scale"], g, f_used, np.float64, frame)
-    recovered = axis_moment(reaction) - (tx if use_torques else 0 * tx) + losses(orc)
+    recovered = axis_moment(reaction) - (tx if use_torques else 0 * tx) + wref.losses(orc)
     tau_motor = np.where(np.isnan(law), recovered, law)
-    out.update(qdd=qdd, tau_motor=tau_motor, reaction=reaction, total=tau_motor + tx - losses(orc))
+    out.update(qdd=qdd, tau_motor=tau_motor, reaction=reaction, total=tau_motor + tx - wref.losses(orc))
     return out

@@ -1,18 +1,18 @@
 """The input sets of the per-env motor-target tests (pnr_world_step_targets), shared by the CPU tests (which assert on the float64
 oracle that the inputs bite) and the GPU tests (which run the kernel on exactly these inputs), and the per-env form of the two
 references the project already has.  Nothing here restates a law: the PD reference is orc_dyn_world_step, called env by env with
-that env's own OrcJointMotor table (the oracle is per env already); the constraint reference is tests/constraint_motor_ref.py, which
+that env's own OrcJointMotor table (the oracle is per env already); the constraint reference is tests/world_step_ref.py, which
 takes one motor list for all envs and is therefore run once per TARGET SET, each env being compared with the run of its own set.
 
-A motor law is a dict in the form of tests/constraint_motor_ref.py (kind "pd" / "position_constraint" / "velocity_constraint") or
+A motor law is a dict in the form of tests/world_step_ref.py (kind "pd" / "position_constraint" / "velocity_constraint") or
 None (nobody commanded the joint: the handle's own law).  Its target_position / target_velocity are what pnr_set_joint_motor puts
 into the table; a masked joint's are replaced, per env, by that env's row of `targets` [n, 12] = position[6] | velocity[6].
 """
 import numpy as np
 
 import bars
+import oracle_cases as ocases
 from oracle import DynOracle
-from oracle.binding import ORC_DEV
 
 DOF = 6
 Q_TOL, QD_TOL = bars.Q_TOL, bars.QD_TOL                               # read through this module by tests/test_motor_targets_cpu.py
@@ -116,35 +116,9 @@ def target_sets(case, n, step, mask=FULL):
     return sets, pick
 
 
-def command_actions(case, n, a_max):
-    """the actions of the vector steps that move the command state off its reset values before the motors are set"""
-    rng = np.random.default_rng(1000 + case["seed"])
-    return [(rng.uniform(-0.3, 0.3, (n, DOF)) * a_max).astype(np.float32) for _ in range(case.get("command_steps", 0))]
-
-
-def oracle_dyn(engine, gravity):
-    """the oracle's params for EngineConfig arguments"""
-    e = dict(engine)
-    d = dict(gravity=gravity, kp=e.pop("pd_kp", 4000.0), kd=e.pop("pd_kd", 400.0), torque_limit=e.pop("torque_limit", 0.0),
-             randomize=int(e.pop("randomize", False)), pd_inertia_scaled=int(e.pop("pd_inertia_scaled", False)),
-             link_contacts=int(e.pop("link_contacts", False)))
-    d.update(e)                                                       # joint_damping, joint_friction, ground_z, the box: same names
-    return d
-
-
 def make_oracle(case, n, engine=None):
-    """The float64 oracle after its reset and the case's command steps: per-env link scales, friction, damping and command state
-    as the engine draws them (tests/test_gpu_dynamics.py holds the two to the same bits)."""
-    orc = DynOracle(n, seed=case["seed"], precision=ORC_DEV, frame_skip=case["frame_skip"],
-                    dyn=oracle_dyn(case["engine"] if engine is None else engine, case["gravity"]))
-    orc.reset()
-    for act in command_actions(case, n, orc.a_max):
-        orc.step(act)
-    return orc
-
-
-def load_oracle(orc, q, qd):
-    orc.dstate["q"], orc.dstate["qd"] = q.astype(np.float64), qd.astype(np.float64)
+    return ocases.make_oracle(case["seed"], n, case["frame_skip"], case["gravity"], case["engine"] if engine is None else engine,
+                              case.get("command_steps", 0))
 
 
 def law_for_env(law, tgt, j):
@@ -182,22 +156,17 @@ def constraint_reference_step(orc, laws, sets, pick, mask, frame_skip):
     """One world step of every env under the constraint-motor reference, env e with the targets sets[pick[e]] on the joints of
     `mask`: the reference runs once per set with that set's motors for everybody, and each env keeps the run of its own set.
     In place on orc.dstate; returns the last sub-step's info dicts, one per set."""
-    import constraint_motor_ref as ref
+    import world_step_ref as wref
     start = orc.dstate.copy()
-    state0 = orc.state.copy()
     out = start.copy()
     infos = []
+    uncommanded = [j for j in mask if laws[j] is None]                # the handle's law: the targets stand in for r, v
     for k in range(len(sets)):
         orc.dstate[:] = start
-        orc.state[:] = state0
-        motors = []
-        for j, m in enumerate(laws):
-            if j in mask and m is None:                               # the handle's law: the targets stand in for r, v
-                orc.state["r"][:, j], orc.state["v"][:, j] = sets[k, j], sets[k, DOF + j]
-            motors.append(law_for_env(m, sets[k], j) if (j in mask and m is not None) else m)
-        infos.append(ref.world_step(orc, motors, frame_skip)[-1])
+        motors = [law_for_env(m, sets[k], j) if (j in mask and m is not None) else m for j, m in enumerate(laws)]
+        infos.append(wref.world_step(orc, motors, targets=np.broadcast_to(sets[k], (orc.n, 2 * DOF)), joints=uncommanded,
+                                     frame_skip=frame_skip)[-1])
         mine = pick == k
         out[mine] = orc.dstate[mine]
     orc.dstate[:] = out
-    orc.state[:] = state0
     return infos

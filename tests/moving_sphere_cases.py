@@ -1,6 +1,7 @@
 """The inputs of the moving-sphere tests, shared by the CPU tests (which assert on the float64 reference that the inputs are well
 conditioned) and the GPU tests (which run the kernel on exactly these inputs), and the sphere's bars, which are taken from the
-reference's own float32-storage deviation on these inputs.  The reference itself is tests/moving_sphere_ref.py.
+reference's own float32-storage deviation on these inputs.  The reference itself is tests/world_step_ref.py's world_step(sphere=...)
+with the sphere's law of tests/moving_sphere_ref.py.
 
 Every input is a float32 number, held in float64 where the reference reads it, and comes from a generator of its own sized N_MAX,
 so the inputs of n envs are the first n rows of those of N_MAX envs.
@@ -23,8 +24,9 @@ import bars
 import ik_ref
 import link_kinematics_ref as lk
 import moving_sphere_ref as ref
+import oracle_cases as ocases
+import world_step_ref as wref
 from oracle import DynOracle
-from oracle.binding import ORC_DEV
 
 DOF = 6
 N_MAX = 1000
@@ -60,10 +62,7 @@ def followed(n):
 
 def make_oracle(family, n, reset=True):
     f = FAMILIES[family]
-    orc = DynOracle(n, seed=f["seed"], precision=ORC_DEV, frame_skip=FRAME_SKIP, dyn=dict(f["dyn"], gravity=f["gravity"]))
-    if reset:
-        orc.reset(want_obs=False)
-    return orc
+    return ocases.make_oracle(f["seed"], n, FRAME_SKIP, f["gravity"], f["dyn"], reset=reset)
 
 
 def states(family, r_cmd):
@@ -153,7 +152,7 @@ def scenario(family, orc, idx):
     r_all = np.zeros((n, DOF))
     r_all[idx] = orc.state["r"]
     q, qd = states(family, r_all)
-    orc.dstate["q"], orc.dstate["qd"] = q[idx].astype(np.float64), qd[idx].astype(np.float64)
+    ocases.load_states(orc, q[idx], qd[idx])
     w = spheres(family, q)
     return ref.from_words(w[:, idx]), joint_torques(family, n)[idx], targets(family, r_all.astype(np.float32))[idx]
 
@@ -173,8 +172,8 @@ def reference_margins(family):
         for _ in range(STEPS):
             b.dstate[:] = a.dstate
             sb = {k: v.copy() for k, v in s.items()}
-            ref.world_step(a, TRACK, s, tau_ext=te, targets=tt, joints=joints, storage32=True)
-            ref.world_step(b, TRACK, sb, tau_ext=te, targets=tt, joints=joints, storage32=False)
+            wref.world_step(a, TRACK, sphere=s, tau_ext=te, targets=tt, joints=joints, storage32=True)
+            wref.world_step(b, TRACK, sphere=sb, tau_ext=te, targets=tt, joints=joints, storage32=False)
             live = s["m"] > 0
             worst["x"] = max(worst["x"], float(np.abs(s["x"] - sb["x"])[live].max()))
             worst["v"] = max(worst["v"], float(np.abs(s["v"] - sb["v"])[live].max()))

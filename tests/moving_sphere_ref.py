@@ -5,14 +5,15 @@ not modelled).  Per sub-step of length h, every force at the state the sub-step 
                    F += fn n - friction fn v_t / sqrt(|v_t|^2 + slip_eps^2), v_t = v - (v . n) n
     arm samples    d = x - p_s, depth = radius + r_s - |d|, n = d / |d| ((0, 0, 1) at |d| = 0), fn = kp depth - kd ((v - v_s) . n);
                    where depth > 0 and fn > 0: +fn n on the sphere, -fn n on the sample's body at the sample's centre
-    integration    v += h (F / m - linear_damping v - g z^), x += h v; the joints as tests/external_force_ref.py integrates them
+    integration    v += h (F / m - linear_damping v - g z^), x += h v; the joints as tests/world_step_ref.py integrates them
 An env with mass <= 0 has no sphere.
 
-Built on the float64 oracle's forward dynamics (DynOracle.contact_samples / contact_wrenches / aba_ext / aba_motor, through
-tests/external_force_ref.py's `accelerations`, which takes the sphere's reactions in its fext slot) and on the URDF chain's poses
-and velocities (tests/link_kinematics_ref.py).  The signed-distance forms are restated here in numpy.  It reads nothing of
-pioneer_amd.  `storage32` rounds the sphere's and the joints' state to float32 after every sub-step: the reference's own
-float32-storage deviation is what the GPU test's sphere bars are taken from.
+This module is the sphere's own law: the forces (`static_force`, `arm_forces`) and `integrate`.  The reference of the call is
+tests/world_step_ref.py's world_step(sphere=...), whose forward dynamics take the sphere's reactions in their fext slot and whose
+`storage32` rounds the sphere's and the joints' state to float32 after every sub-step: the reference's own float32-storage
+deviation is what the GPU test's sphere bars are taken from.  Built on the oracle's sample table (DynOracle.contact_samples) and
+on the URDF chain's poses and velocities (tests/link_kinematics_ref.py).  The signed-distance forms are restated here in numpy.
+It reads nothing of pioneer_amd.
 """
 import numpy as np
 
@@ -151,43 +152,11 @@ def arm_forces(orc, s, p):
     return F, fext, touching
 
 
-def _f32(a):
-    return a.astype(np.float32).astype(np.float64)
-
-
-def world_step(orc, motors, s, params=None, tau_ext=None, targets=None, joints=(), storage32=False, frame_skip=None, h=1.0 / 240):
-    """One World.step of every env of the oracle's batch and its spheres `s`, in place on orc.dstate and s.  targets [n, 12]
-    (position[6] | velocity[6]) for the joints `joints`: they stand in for the env's command state r, v of those joints during the
-    call (joints on the env-wide law, motors[j] None).  Returns (the arm's force on the sphere in the first sub-step [n, 3],
-    touching the arm in the first sub-step [n], touching the static world in the first sub-step [n])."""
-    p = params_of(orc, params)
-    nsub = orc.d.frame_skip if frame_skip is None else frame_skip
-    g = float(orc.d.gravity)
-    tau = None if tau_ext is None else np.asarray(tau_ext, dtype=np.float64)
-    keep = None
-    if targets is not None:
-        assert all(motors[j] is None for j in joints)
-        keep = orc.state["r"].copy(), orc.state["v"].copy()
-        for j in joints:
-            orc.state["r"][:, j] = targets[:, j]
-            orc.state["v"][:, j] = targets[:, 6 + j]
-    first = None
+def integrate(s, F, p, g, h):
+    """the spheres' sub-step under the force F [n, 3] (static world plus arm), in place on s; an env without a sphere stays as it is"""
     live = s["m"] > 0
     inv_m = np.where(live, 1.0 / np.where(live, s["m"], 1.0), 0.0)
-    for k in range(nsub):
-        Fs, on_static = static_force(orc, s, p)
-        Fa, fext, on_arm = arm_forces(orc, s, p)
-        qdd = ext.accelerations(orc, motors, fext, tau)
-        if first is None:
-            first = Fa.copy(), on_arm, on_static
-        ext.integrate(orc, qdd, h)
-        acc = (Fs + Fa) * inv_m[:, None] - p["linear_damping"] * s["v"] - np.array([0.0, 0.0, g])
-        vn = s["v"] + h * acc
-        s["v"] = np.where(live[:, None], vn, s["v"])
-        s["x"] = np.where(live[:, None], s["x"] + h * vn, s["x"])
-        if storage32:
-            orc.dstate["q"], orc.dstate["qd"] = _f32(orc.dstate["q"]), _f32(orc.dstate["qd"])
-            s["x"], s["v"] = _f32(s["x"]), _f32(s["v"])
-    if keep is not None:
-        orc.state["r"], orc.state["v"] = keep
-    return first
+    acc = F * inv_m[:, None] - p["linear_damping"] * s["v"] - np.array([0.0, 0.0, g])
+    vn = s["v"] + h * acc
+    s["v"] = np.where(live[:, None], vn, s["v"])
+    s["x"] = np.where(live[:, None], s["x"] + h * vn, s["x"])

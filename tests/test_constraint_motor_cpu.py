@@ -10,6 +10,8 @@ import pytest
 
 import constraint_motor_cases as cases
 import constraint_motor_ref as ref
+import oracle_cases as ocases
+import world_step_ref as wref
 from bars import QD_TOL
 from oracle import DynOracle
 from oracle.binding import ORC_DEV
@@ -25,8 +27,8 @@ def solved(case, n):
     orc = cases.make_oracle(case, n)
     out = []
     for step in range(c["steps"]):
-        cases.load_oracle(orc, *cases.states(case, n, step))
-        out.append(ref.world_step(orc, c["motors"], c["frame_skip"]))
+        ocases.load_states(orc, *cases.states(case, n, step))
+        out.append(wref.world_step(orc, c["motors"], frame_skip=c["frame_skip"]))
     return out
 
 
@@ -66,8 +68,8 @@ def test_ample_forces_reach_every_target():
     n = 64
     motors = [dict(m, max_force=1e9) if m and m["kind"].endswith("_constraint") else m for m in cases.CASES["subset"]["motors"]]
     orc = cases.make_oracle("subset", n)
-    cases.load_oracle(orc, *cases.states("subset", n, 0))
-    info = ref.substep(orc, motors)
+    ocases.load_states(orc, *cases.states("subset", n, 0))
+    info = wref.world_step(orc, motors, frame_skip=1)[0]
     S = info["S"]
     assert S == [0, 2, 3, 5] and np.all(info["pattern"] == 0)
     assert np.abs(info["qd_plus"][:, S] - info["rhs"][:, S]).max() <= 1e-12
@@ -86,7 +88,7 @@ def _pair(n, seed):
     q = rng.uniform(0.6 * a.r_lo.astype(np.float64), 0.6 * a.r_hi.astype(np.float64), size=(n, 6)).astype(np.float32)
     qd = rng.uniform(-1.0, 1.0, size=(n, 6)).astype(np.float32)
     for o in (a, b):
-        cases.load_oracle(o, q, qd)
+        ocases.load_states(o, q, qd)
     assert sum(a.contact_wrenches(e)[0] for e in range(n)) >= n // 4, "the scenario must have contacts"
     return a, b
 
@@ -96,7 +98,7 @@ def test_zero_forces_are_the_oracles_world_step_without_motors():
     mine, orc = _pair(n, 21)
     for j in range(6):
         orc.set_joint_motor(j, 1, target_velocity=0.0, velocity_gain=0.0)
-    ref.world_step(mine, [cases.vel(0.7, 0.0)] * 6)
+    wref.world_step(mine, [cases.vel(0.7, 0.0)] * 6)
     orc.world_step()
     assert np.abs(mine.dstate["q"] - orc.dstate["q"]).max() <= 1e-12 and np.abs(mine.dstate["qd"] - orc.dstate["qd"]).max() <= 1e-10
 
@@ -113,7 +115,7 @@ def test_one_saturated_joint_is_the_oracles_constant_torque(k, F, side):
     for j in range(6):
         if j != k:
             orc.set_joint_motor(j, 1, target_velocity=0.0, velocity_gain=0.0)
-    infos = ref.world_step(mine, motors)
+    infos = wref.world_step(mine, motors)
     orc.world_step()
     assert len(infos) == 10 and all(np.all(i["pattern"] == side) and np.all(i["tau"] == side * F) for i in infos)
     assert np.abs(mine.dstate["q"] - orc.dstate["q"]).max() <= 1e-12 and np.abs(mine.dstate["qd"] - orc.dstate["qd"]).max() <= 1e-10

@@ -9,7 +9,8 @@
 import numpy as np
 import pytest
 
-from dyn_outputs_ref import TILE, check_outputs, full_oracle, load_q_qd, phase_b_oracle, targets_near
+from dyn_outputs_ref import TILE, check_outputs, full_oracle, phase_b_oracle, targets_near
+from oracle_cases import load_states
 
 N, STEPS = 256, 10
 
@@ -52,7 +53,7 @@ def test_zero_substep_oracle_chained_on_row_columns_is_the_full_oracles_phase_b(
     n_done = n_trunc = 0
     for t in range(STEPS - 1):
         want = full.step(acts[t], want_info=True)
-        load_q_qd(pb, want[0][:, 0:6], want[0][:, 90:96])        # never re-synced: only the row's q, qd
+        load_states(pb, want[0][:, 0:6], want[0][:, 90:96])        # never re-synced: only the row's q, qd
         got = pb.step(acts[t], want_info=True)
         assert _same(got, want), t
         n_done += int(want[2].sum()); n_trunc += int(want[3].sum())

@@ -1,5 +1,5 @@
-"""CPU tests of the float64 reference of pnr_world_step_wrenches (tests/external_force_ref.py) and of the inputs the GPU tests run
-(tests/external_force_cases.py): the reference is held against the oracle's own forward dynamics, against joint torques through
+"""CPU tests of the float64 reference of pnr_world_step_wrenches (tests/world_step_ref.py's world_step on the records of
+tests/external_force_ref.py) and of the inputs the GPU tests run (tests/external_force_cases.py): the reference is held against the oracle's own forward dynamics, against joint torques through
 an independent Jacobian and against the oracle's world step; the inputs are shown to be well conditioned at float32 and to
 matter at many times the bars.  Every test prints its figures before it asserts.
 """
@@ -10,6 +10,8 @@ import external_force_cases as cases
 import external_force_ref as ref
 import ik_ref
 import link_kinematics_ref as lk
+import oracle_cases as ocases
+import world_step_ref as wref
 from oracle import DynOracle
 
 DOF = 6
@@ -102,9 +104,9 @@ def test_zero_wrenches_reproduce_the_oracles_world_step(family):
     q, qd = cases.states(family, a.state["r"])
     worst = 0.0
     for orc in (a, b):
-        orc.dstate["q"], orc.dstate["qd"] = q.astype(np.float64), qd.astype(np.float64)
+        ocases.load_states(orc, q, qd)
     for step in range(cases.STEPS):
-        ref.world_step(a, f["motors"], f["specs"], np.zeros((n, len(f["specs"]), 9)))
+        wref.world_step(a, f["motors"], wrenches=(f["specs"], np.zeros((n, len(f["specs"]), 9))))
         b.world_step()
         worst = max(worst, np.abs(a.dstate["q"] - b.dstate["q"]).max(), np.abs(a.dstate["qd"] - b.dstate["qd"]).max())
     print(f"zero wrenches, family {family}: worst |reference - DynOracle.world_step| {worst:.3e}; |qd| reaches {np.abs(b.dstate['qd']).max():.3f}")
@@ -122,8 +124,8 @@ def test_frames_hold_and_the_welded_base():
         orc.dstate["q"], orc.dstate["qd"] = q.copy(), qd.copy()
         first = None
         for _ in range(steps):
-            out = ref.world_step(orc, cases.FREE, specs, w, hold_substeps=hold)
-            first = out[0] if first is None else first
+            out = wref.world_step(orc, cases.FREE, wrenches=(specs, w), hold_substeps=hold)
+            first = out[0]["qdd"] if first is None else first
         return first, orc.dstate["qd"].copy()
 
     a0, _ = run([(7, "world")], world, 1)
@@ -153,11 +155,11 @@ def _run(family, idx, rounded, with_tau, hold, with_wrench=True, steps=cases.STE
     if not with_wrench:
         w = np.zeros_like(w)
     tau = cases.joint_torques(family, cases.N_MAX)[idx].astype(np.float64) if with_tau else None
-    orc.dstate["q"], orc.dstate["qd"] = q[idx].astype(np.float64), qd[idx].astype(np.float64)
+    ocases.load_states(orc, q[idx], qd[idx])
     out = []
     share = np.mean([orc.contact_wrenches(e)[0] for e in range(orc.n)]) if cases.PHYS[family] & 1 else 0.0
     for _ in range(steps):
-        ref.world_step(orc, f["motors"], f["specs"], w, tau, hold)
+        wref.world_step(orc, f["motors"], wrenches=(f["specs"], w), tau_ext=tau, hold_substeps=hold)
         if rounded:
             orc.dstate["q"] = orc.dstate["q"].astype(np.float32).astype(np.float64)
             orc.dstate["qd"] = orc.dstate["qd"].astype(np.float32).astype(np.float64)

@@ -6,7 +6,7 @@ these tests check the law's own consequences — deadbeat velocities, the 0.9^m 
 a saturated motor as a constant torque against the unchanged oracle — and that a batch computes each env as alone.
 
 The boxed solve itself (mass matrix, Cholesky, active set, pass cap) is compared with the float64 reference of
-tests/constraint_motor_ref.py on the input sets of tests/constraint_motor_cases.py, every env, at Q_TOL / QD_TOL, plus the
+tests/world_step_ref.py (the boxed solve: tests/constraint_motor_ref.py) on the input sets of tests/constraint_motor_cases.py, every env, at Q_TOL / QD_TOL, plus the
 deadbeat bound on joints that are free with margin (second half of this file; tests/test_constraint_motor_cpu.py asserts that
 those inputs bite).  Each of these tests prints its worst |dq|, |dqd| and |qd - rhs| per step and writes the scenario's worst
 values through tests/test_gpu_dynamics.py's _record_margin (keys cmotor_mixed, cmotor_subset, cmotor_skip10, cmotor_scaled).
@@ -278,13 +278,14 @@ def _against_reference(case, n):
     """Runs an input set's re-randomised world steps on the engine and on the reference; asserts the project's bar on q and qd
     of every env and the deadbeat bound on the joints that are free with margin; records the worst deviations."""
     import constraint_motor_cases as cases
-    import constraint_motor_ref as ref
+    import oracle_cases as ocases
+    import world_step_ref as wref
     from test_gpu_dynamics import _record_margin
     c = cases.CASES[case]
     env = make(n, gravity=cases.GRAVITY, frame_skip=c["frame_skip"], seed=c["seed"], **c["engine"])
     orc = cases.make_oracle(case, n)
     assert np.array_equal(env.a_max, orc.a_max)
-    for act in cases.command_actions(case, n, env.a_max):
+    for act in ocases.command_actions(c["seed"], c.get("command_steps", 0), n, env.a_max):
         env.vector_step(torch.from_numpy(act).cuda())
     set_motors(env, c["motors"])
     # the engine's command state and per-env draws are the ones the CPU tests' conditions were asserted on
@@ -299,7 +300,7 @@ def _against_reference(case, n):
     for step in range(c["steps"]):
         load_joints(env, *cases.states(case, n, step))
         orc.load_dyn_words(dyn_words(env))
-        infos = ref.world_step(orc, c["motors"], c["frame_skip"])
+        infos = wref.world_step(orc, c["motors"], frame_skip=c["frame_skip"])
         env.world_step()
         d = dyn_words(env).astype(np.float64)
         q, qd = d[0:6].T, d[6:12].T

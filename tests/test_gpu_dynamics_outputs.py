@@ -30,8 +30,9 @@ import pytest
 import torch
 
 from bars import POS_TOL, POT_TOL, PTR_TOL, Q_TOL, QD_TOL, REW_TOL, ROLL_OBS_TOL, ROLL_REW_TOL, TRIG_TOL
-from dyn_outputs_ref import check_outputs, full_oracle, load_q_qd, merge_worst, phase_b_oracle, targets_near, worst_outputs
+from dyn_outputs_ref import check_outputs, full_oracle, merge_worst, phase_b_oracle, targets_near, worst_outputs
 from gpu_support import dyn_words, engine_config_from_oracle_names, words
+from oracle_cases import load_states
 from test_gpu_dynamics import _record_margin
 
 pytestmark = pytest.mark.gpu
@@ -203,7 +204,7 @@ def test_done_is_exact_inside_float32_noise_of_the_threshold_while_the_arm_moves
     pb.reset(joint_pos=jp.astype(np.float64), target_pos=tp.astype(np.float64))
     fig, flips, near_done = {}, 0, np.zeros(n, dtype=bool)
     for t in range(T):
-        load_q_qd(pb, two[0][t][:, 0:6], two[0][t][:, 90:96])
+        load_states(pb, two[0][t][:, 0:6], two[0][t][:, 90:96])
         want = pb.step(acts[t], want_info=True)
         sel = judged == t
         assert np.abs(want[4][sel, 3] - DONE_DISTANCE).max() < 3e-5                 # construction: every env within the noise
@@ -239,7 +240,7 @@ def test_rollout_kernel_every_instantiation_through_the_chain(layout, act_layout
         obs, rew, done, trunc = env.rollout(dev_actions(env, acts))
         o = rows(env, obs); rew, done, trunc = host(rew, done, trunc)
         for t in range(T):
-            load_q_qd(pb, o[t][:, 0:6], o[t][:, 90:96])
+            load_states(pb, o[t][:, 0:6], o[t][:, 90:96])
             want = pb.step(acts[t])
             got = (o[t], rew[t], done[t], trunc[t], None)
             merge_worst(fig, worst_outputs(got, want + (None,)))

@@ -1,5 +1,5 @@
 """GPU tests of pnr_world_step_wrenches (PioneerVectorEnv.world_step(link_wrenches=...), the facade's apply_force / apply_torque)
-against the float64 reference of tests/external_force_ref.py, on the inputs of tests/external_force_cases.py.
+against the float64 reference of tests/world_step_ref.py (the records: tests/external_force_ref.py), on the inputs of tests/external_force_cases.py.
 
 Bars: the project's own for a world step re-synchronised with the float64 reference, Q_TOL / QD_TOL
 (tests/bars.py).  tests/test_external_force_cpu.py asserts that on these inputs float32 rounding alone stays within a
@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import external_force_cases as cases
-import external_force_ref as ref
+import world_step_ref as wref
 from bars import Q_TOL, QD_TOL
 from gpu_support import bits, dev, dyn_env, dyn_words, lib as _lib, load_joints, set_motors
 
@@ -65,10 +65,11 @@ def test_world_step_wrenches_against_the_reference(n, family):
                     share = np.mean([orc.contact_wrenches(e)[0] for e in range(orc.n)])
                     print(f"family {family} n={n}: {share:.2%} of the followed envs in contact")
                     assert n < 37 or 0.05 <= share <= 0.95
-                ref.world_step(orc, f["motors"], f["specs"], w[idx], tau[idx] if with_tau else None, hold)
+                wref.world_step(orc, f["motors"], wrenches=(f["specs"], w[idx]), tau_ext=tau[idx] if with_tau else None, hold_substeps=hold)
                 if step == 0:                                         # not vacuous: the wrenches matter at 10 x the bar
                     plain.load_dyn_words(d)
-                    ref.world_step(plain, f["motors"], f["specs"], np.zeros_like(w[idx]), tau[idx] if with_tau else None, hold)
+                    wref.world_step(plain, f["motors"], wrenches=(f["specs"], np.zeros_like(w[idx])), tau_ext=tau[idx] if with_tau else None,
+                                    hold_substeps=hold)
                     effect = np.abs(orc.dstate["qd"] - plain.dstate["qd"]).max()
                     assert n < 37 or effect > 10 * QD_TOL, effect
                 env.world_step(joint_torques=tq if with_tau else None, link_wrenches=(f["specs"], wt), hold_substeps=hold)

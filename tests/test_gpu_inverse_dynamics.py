@@ -1,6 +1,6 @@
 """GPU tests of pnr_inverse_dynamics / pnr_mass_matrix / pnr_world_step_torques (PioneerVectorEnv.inverse_dynamics, mass_matrix,
 world_step(joint_torques=...) and the facade's Joint.control_torque) against the float64 reference of
-tests/inverse_dynamics_ref.py, on the inputs of tests/inverse_dynamics_cases.py.
+tests/inverse_dynamics_ref.py (the torque step: tests/world_step_ref.py), on the inputs of tests/inverse_dynamics_cases.py.
 
 Bars.  HARD (the project's own, tests/bars.py): a world step re-synchronised with the float64 reference agrees to
 Q_TOL / QD_TOL; an acceleration error below QD_TOL / step_time = 0.048 rad/s^2 cannot move a world step outside QD_TOL, so the
@@ -18,6 +18,8 @@ import torch
 
 import inverse_dynamics_cases as cases
 import inverse_dynamics_ref as ref
+import oracle_cases as ocases
+import world_step_ref as wref
 from bars import Q_TOL, QD_TOL
 from gpu_support import dev, dyn_env, dyn_words, f64, kin_env, lib as _lib, load_joints
 from oracle import DynOracle
@@ -51,7 +53,7 @@ def oracle_of(env, gravity, q=None, qd=None):
     orc = DynOracle(env.num_envs, dyn=dict(gravity=gravity))
     orc.load_dyn_words(dyn_words(env))
     if q is not None:
-        ref.set_states(orc, np.asarray(q, dtype=np.float64), np.asarray(qd, dtype=np.float64))
+        ocases.load_states(orc, np.asarray(q, dtype=np.float64), np.asarray(qd, dtype=np.float64))
     return orc
 
 
@@ -62,7 +64,7 @@ def _source(kind, n, gravity):
     if kind == "kinematic_buffer":                                    # unit scales, the config's losses
         env = make_kin(n, gravity, joint_damping=0.1, joint_friction=0.1)
         orc = cases.make_oracle(n, gravity, False, joint_damping=0.1, joint_friction=0.1)
-        ref.set_states(orc, q.astype(np.float64), qd.astype(np.float64))
+        ocases.load_states(orc, q.astype(np.float64), qd.astype(np.float64))
         assert np.all(orc.dstate["mass_scale"] == 1.0) and np.allclose(orc.dstate["damping"], 0.1, rtol=1e-7, atol=0)
         return env, orc, dev(np.concatenate([q, qd], axis=1)), qdd
     env = make_dyn(n, gravity, randomize=True)
@@ -87,7 +89,7 @@ def test_inverse_dynamics_against_the_reference(n, kind, gravity):
     qdd64 = qdd.astype(np.float64)
     M, _, _ = ref.mass_and_bias(orc, 0.0)
     bias = {g: ref.mass_and_bias(orc, g)[2] for g in {0.0, gravity}}
-    loss = ref.losses(orc)
+    loss = wref.losses(orc)
     assert np.abs(loss).max() > 1e-3                                  # the losses flag has something to add
     for with_gravity in (True, False):
         g = gravity if with_gravity else 0.0
@@ -226,10 +228,10 @@ def test_world_step_torques_against_the_reference(n):
     for step in range(10):
         d = dyn_words(env)[:, idx]
         orc.load_dyn_words(d)
-        ref.world_step_torques(orc, cases.TORQUE_MOTORS, tau[idx])
+        wref.world_step(orc, cases.TORQUE_MOTORS, tau_ext=tau[idx])
         if step == 0:                                                 # not vacuous: the torques matter at 10 x the bar
             plain.load_dyn_words(d)
-            ref.world_step_torques(plain, cases.TORQUE_MOTORS, np.zeros((len(idx), 6)))
+            wref.world_step(plain, cases.TORQUE_MOTORS, tau_ext=np.zeros((len(idx), 6)))
             effect = np.abs(orc.dstate["qd"] - plain.dstate["qd"]).max()
             print(f"torque step n={n}: the torques change qd by {effect:.3e}")
             assert effect > 10 * QD_TOL

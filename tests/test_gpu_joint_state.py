@@ -14,6 +14,7 @@ import constraint_motor_cases as ccases
 import external_force_cases as xcases
 import joint_state_cases as cases
 import joint_state_ref as ref
+import oracle_cases as ocases
 from bars import QD_TOL
 from gpu_support import bits, dev, dyn_env, dyn_words, lib as _lib, load_joints, set_motors, words
 
@@ -29,7 +30,7 @@ def scenario(name, n, frame_skip=None):
     if name in cases.CONSTRAINT:
         c = ccases.CASES[name]
         env = dyn_env(n, c["seed"], ccases.GRAVITY, c["frame_skip"], **c["engine"])
-        for act in ccases.command_actions(name, n, env.a_max):
+        for act in ocases.command_actions(c["seed"], c.get("command_steps", 0), n, env.a_max):
             env.vector_step(torch.from_numpy(act).cuda())
         set_motors(env, c["motors"])
         q, qd = ccases.states(name, n, 0)

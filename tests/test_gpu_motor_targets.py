@@ -4,7 +4,7 @@ motor targets for the joints of a mask — PyBullet's setJointMotorControlArray 
 The contract (include/pioneer_amd.h): env e gets what pnr_world_step gives it on a handle whose motor table holds env e's entries
 as the targets of the masked joints, to float32 rounding; nothing but q, qd is written; an env's result does not depend on the
 batch.  Checked per env against the float64 oracle's world step under that env's own table (PD laws), against
-tests/constraint_motor_ref.py run once per target set (constraint motors), against the engine's own pnr_world_step_torques on a
+tests/world_step_ref.py run once per target set (constraint motors), against the engine's own pnr_world_step_torques on a
 second handle (joint torques in the same launch), and bit for bit against single-env handles and eager calls (batch
 independence, graph replay).  Inputs: tests/motor_target_cases.py; tests/test_motor_targets_cpu.py asserts on the oracle that
 they bite.  Tolerances: the project's Q_TOL / QD_TOL for re-synchronised world steps (tests/bars.py), the engine
@@ -21,6 +21,7 @@ import torch
 
 import gpu_support
 import motor_target_cases as cases
+import oracle_cases as ocases
 from bars import Q_TOL, QD_TOL
 from gpu_support import dev, dyn_env, dyn_words, kin_env, lib as _lib, load_joints, words
 
@@ -50,7 +51,7 @@ def prepared(case, n, engine=None):
     """The engine and the oracle after reset, the case's command steps and its motors, held to the same command state and draws."""
     env = make(n, case, engine)
     orc = cases.make_oracle(case, n, engine)
-    for act in cases.command_actions(case, n, env.a_max):
+    for act in ocases.command_actions(case["seed"], case.get("command_steps", 0), n, env.a_max):
         env.vector_step(dev(act))
     set_motors(env, case["laws"])
     w = words(env)
@@ -123,7 +124,7 @@ def test_partial_mask_next_to_commanded_and_uncommanded_joints_and_nothing_persi
     env.close()
 
 
-# ---- 3. constraint motors, every env, against tests/constraint_motor_ref.py ---------------------------------------------
+# ---- 3. constraint motors, every env, against tests/world_step_ref.py ---------------------------------------------------
 @pytest.mark.parametrize("n,mask,steps", cases.CMOTOR_SETS)
 def test_constraint_motors_take_each_envs_own_targets(n, mask, steps):
     """Position constraint motors with maxVelocity, velocity constraint motors (one saturating), a PD joint and an uncommanded

@@ -1,6 +1,6 @@
 """GPU tests of the moving sphere (pnr_set_body_params / pnr_set_body_state / pnr_get_body_state and the world step's kWorldBody
 forms; PioneerVectorEnv.set_body, the facade's create_body_sphere(mass > 0)) against the float64 reference of
-tests/moving_sphere_ref.py, on the inputs of tests/moving_sphere_cases.py.
+tests/world_step_ref.py (the sphere's law: tests/moving_sphere_ref.py), on the inputs of tests/moving_sphere_cases.py.
 
 Bars.  Joints: Q_TOL / QD_TOL (tests/bars.py), the project's bars for a world step re-synchronised with the float64 reference.
 Sphere: 4 x the reference's own float32-storage deviation on the same inputs (cases.sphere_bars; the ratio the CPU tests hold the
@@ -20,6 +20,7 @@ import torch
 
 import moving_sphere_cases as cases
 import moving_sphere_ref as ref
+import world_step_ref as wref
 from bars import Q_TOL, QD_TOL
 from gpu_support import bits, dev, dyn_words, engine_config_from_oracle_names, kin_env, lib as _lib, load_joints
 
@@ -84,7 +85,8 @@ def test_world_step_with_a_sphere_against_the_reference(n, family, form):
         orc.load_dyn_words(dyn_words(env)[:, idx])
         before = body_words(env)
         s = ref.from_words(before[:, idx])
-        _, on_arm, on_static = ref.world_step(orc, cases.TRACK, s, tau_ext=te, targets=tt, joints=joints)
+        first = wref.world_step(orc, cases.TRACK, sphere=s, tau_ext=te, targets=tt, joints=joints)[0]
+        on_arm, on_static = first["on_arm"], first["on_static"]
         live = s["m"] > 0
         if step == 0:
             print(f"family {family} n={n} {form}: {on_arm.mean():.2%} of the followed envs' spheres touch the arm, "

@@ -13,6 +13,8 @@ import pytest
 import ik_ref
 import inverse_dynamics_cases as cases
 import inverse_dynamics_ref as ref
+import oracle_cases as ocases
+import world_step_ref as wref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _batch(n, gravity, randomize=True):
     q, qd, qdd = (x.astype(np.float64) for x in cases.joints(n))
     orc = cases.make_oracle(n, gravity, randomize)
-    ref.set_states(orc, q, qd)
+    ocases.load_states(orc, q, qd)
     return orc, q, qd, qdd
 
 
@@ -57,12 +59,15 @@ def test_reference_torques_invert_the_forward_dynamics(oracle_built, gravity):
     bias = ref.inverse_dynamics(orc, None, gravity)
     assert np.abs(ref.newton_euler(q, qd, 0 * qdd, orc.dstate["mass_scale"], gravity) - bias).max() <= 1e-9 * np.abs(tau).max()
     # the losses are the sub-step's own terms: with them the engine's free dynamics realise qdd
-    import constraint_motor_ref as cref
     orc.d.gravity = gravity
-    qdd_free, Minv = cref.free_dynamics(orc, cases.FREE_MOTORS)
+    qdd_free, Minv = wref.free_dynamics(orc, cases.FREE_MOTORS)
     tl = ref.inverse_dynamics(orc, qdd, gravity, joint_losses=True)
     # (1e-8: free_dynamics takes M^-1 from differences of accelerations of the size of qdd_free, which costs it a digit)
     assert np.abs(qdd_free + np.einsum("nij,nj->ni", Minv, tl) - qdd).max() <= 1e-8
+    # .. and so does the torque step's own path, the forward dynamics of losses + tau_ext directly (no difference: 1e-9)
+    direct = np.abs(wref.accelerations(orc, cases.FREE_MOTORS, tau_ext=tl) - qdd).max()
+    print("accelerations(tau_ext) - qdd", direct)
+    assert direct <= 1e-9
     assert np.abs(tl - tau).max() > 0.05                                  # the drawn friction and damping do something
 
 
@@ -74,7 +79,7 @@ def test_float32_floor_constants_hold_on_the_inputs(oracle_built):
     ones = np.ones((n, 11))
     orc = cases.make_oracle(n, 9.81, True)
     sc, fr, da = (orc.dstate[k].copy() for k in ("mass_scale", "friction", "damping"))
-    ref.set_states(orc, q, qd)
+    ocases.load_states(orc, q, qd)
     cases.free_joints(orc)
     orc.world_step(); orc.world_step()                                    # the "own simulated joints" source of the GPU test
     qs, qds = orc.dstate["q"].astype(np.float32), orc.dstate["qd"].astype(np.float32)
@@ -126,11 +131,11 @@ def hold_scenario(n, steps=24):
         orc = cases.make_oracle(n, 9.81, True, seed=cases.HOLD_SEED)
         orc.dstate["friction"] = 0.0
         orc.dstate["damping"] = 0.0
-        ref.set_states(orc, q0, np.zeros_like(q0))
+        ocases.load_states(orc, q0, np.zeros_like(q0))
         drift = np.zeros(n)
         for _ in range(steps):
             tau = ref.inverse_dynamics(orc, None, 9.81).astype(np.float32).astype(np.float64) if held else np.zeros((n, 6))
-            ref.world_step_torques(orc, cases.FREE_MOTORS, tau)
+            wref.world_step(orc, cases.FREE_MOTORS, tau_ext=tau)
             drift = np.maximum(drift, np.abs(orc.dstate["q"] - q0).max(axis=1))
         out.append(drift)
     return out[0], out[1]

@@ -10,6 +10,7 @@ import external_force_ref as xref
 import inverse_dynamics_ref as idref
 import joint_state_cases as cases
 import joint_state_ref as ref
+import world_step_ref as wref
 
 DOF = 6
 ALL = cases.FAMILIES + ["hold"] + cases.CONSTRAINT
@@ -37,7 +38,7 @@ def test_floor_constants_hold_on_the_inputs(name):
     free_fall = None
     if name == "hold":
         orc, I = cases.hold_inputs()
-        free_fall = np.median(np.abs(xref.accelerations(orc, I["motors"], np.zeros((orc.n, DOF, 6)))), axis=0)
+        free_fall = np.median(np.abs(wref.accelerations(orc, I["motors"])), axis=0)
         print(f"hold: free-fall median |qdd| {free_fall}")
     for form, by_class in measured.items():
         assert set(table[name][form]) == set(by_class)
@@ -102,10 +103,10 @@ def test_the_axis_moment_is_the_total_joint_torque(family):
         err = np.abs(axis - total).max() / np.abs(total).max()
         print(f"family {family} {form}: axis moment vs M (qdd - ABA(0)): relative {err:.2e} at torques up to {np.abs(total).max():.3e}")
         assert err <= 1e-9
-        law = ref.table_law(orc, I["motors"])
+        law = wref.table_law(orc, I["motors"])
         if not np.isnan(law).any():
             tx = I["tau"].astype(np.float64) if form in ("ext", "torque") else 0.0
-            stated = law + tx - ref.losses(orc)
+            stated = law + tx - wref.losses(orc)
             err = np.abs(ref.axis_moment(R["reaction"]) - stated).max() / max(np.abs(stated).max(), 1.0)
             print(f"family {family} {form}: axis moment vs tau_motor + joint_torque - losses: relative {err:.2e}")
             assert err <= 1e-9
@@ -114,7 +115,7 @@ def test_the_axis_moment_is_the_total_joint_torque(family):
 def test_the_held_arm_rests_and_joint_0_carries_its_weight_and_the_payload():
     orc, I = cases.hold_inputs(rounded=False)
     R = cases.reference(orc, I)
-    fall = xref.accelerations(orc, I["motors"], np.zeros((orc.n, DOF, 6)))
+    fall = wref.accelerations(orc, I["motors"])
     rel = np.abs(R["qdd"]).max() / np.abs(fall).max()
     print(f"hold: |qdd| {np.abs(R['qdd']).max():.3e} against a free fall of {np.abs(fall).max():.3e}: {rel:.2e}")
     assert rel <= 1e-9

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import motor_target_cases as cases
+import oracle_cases as ocases
 
 Q_TOL, QD_TOL, DOF = cases.Q_TOL, cases.QD_TOL, cases.DOF
 BITE = 20.0                                                           # tolerances
@@ -18,7 +19,7 @@ def _ratio(a, b):
 
 
 def _run(orc, case, n, step, laws, tgt, mask):
-    cases.load_oracle(orc, *cases.states(case, n, step))
+    ocases.load_states(orc, *cases.states(case, n, step))
     cases.oracle_world_step(orc, laws, tgt, mask)
     return orc.dstate.copy()
 
@@ -58,7 +59,7 @@ def test_the_per_env_helper_without_targets_is_the_oracles_world_step():
     n = c["n"]
     orc = cases.make_oracle(c, n)
     a = _run(orc, c, n, 0, c["laws"], None, ())
-    cases.load_oracle(orc, *cases.states(c, n, 0))
+    ocases.load_states(orc, *cases.states(c, n, 0))
     orc.world_step()                                                  # the motors are orc.motors, as the helper left them
     assert np.array_equal(a["q"], orc.dstate["q"]) and np.array_equal(a["qd"], orc.dstate["qd"])
 
@@ -95,7 +96,7 @@ def test_constraint_target_sets_bite(n, mask, step):
     sets, pick = cases.target_sets(c, n, step, mask)
     K = len(sets)
     assert sorted(set(pick.tolist())) == list(range(K)) and np.bincount(pick).max() < n
-    cases.load_oracle(orc, *cases.states(c, n, step))
+    ocases.load_states(orc, *cases.states(c, n, step))
     start = orc.dstate.copy()
     runs = []
     for k in range(K):

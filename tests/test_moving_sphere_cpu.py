@@ -1,4 +1,4 @@
-"""CPU tests of the moving sphere's float64 reference (tests/moving_sphere_ref.py) and of the inputs the GPU tests run on
+"""CPU tests of the moving sphere's float64 reference (tests/moving_sphere_ref.py, stepped by tests/world_step_ref.py) and of the inputs the GPU tests run on
 (tests/moving_sphere_cases.py): closed forms of the law, the conditions on the inputs, and the reference's own float32-storage
 deviation, which sets the sphere's bars in tests/test_gpu_moving_sphere.py (4 x) and is written to moving_sphere_margins.json."""
 import numpy as np
@@ -6,6 +6,7 @@ import pytest
 
 import moving_sphere_cases as cases
 import moving_sphere_ref as ref
+import world_step_ref as wref
 from bars import Q_TOL, QD_TOL
 
 
@@ -21,11 +22,11 @@ def test_a_sphere_at_rest_on_the_ground_sits_where_spring_and_weight_balance():
     m, r = np.array([0.5, 1.0, 2.0, 4.0]), np.array([0.3, 0.5, 1.0, 1.5])
     x = np.stack([np.full(4, 60.0), np.full(4, 30.0), gz + r - m * g / kp], axis=1)          # away from the box, beyond the pointer
     s = ref.sphere(x, np.zeros((4, 3)), m, r)
-    ref.world_step(orc, cases.TRACK, s)
+    wref.world_step(orc, cases.TRACK, sphere=s)
     assert np.abs(s["x"] - x).max() < 1e-12 and np.abs(s["v"]).max() < 1e-12
     s = ref.sphere(x + [0.0, 0.0, 0.01], np.zeros((4, 3)), m, r)
     for _ in range(100):
-        ref.world_step(orc, cases.TRACK, s)
+        wref.world_step(orc, cases.TRACK, sphere=s)
     assert np.abs(s["x"] - x).max() < 1e-9 and np.abs(s["v"]).max() < 1e-8
 
 
@@ -59,10 +60,11 @@ def test_the_inputs_are_well_conditioned(family, n):
         o.dstate[:] = full.dstate[idx]
     s, _, _ = cases.scenario(family, orc, idx)
     plain.dstate[:] = orc.dstate
-    _, on_arm, on_static = ref.world_step(orc, cases.TRACK, s)
+    first = wref.world_step(orc, cases.TRACK, sphere=s)[0]
+    on_arm, on_static = first["on_arm"], first["on_static"]
     gone = {k: v.copy() for k, v in s.items()}
     gone["m"][:] = 0.0
-    ref.world_step(plain, cases.TRACK, gone)
+    wref.world_step(plain, cases.TRACK, sphere=gone)
     effect = np.abs(orc.dstate["qd"] - plain.dstate["qd"]).max()
     live = s["m"] > 0
     print(f"family {family} n={n}: {on_arm.mean():.2%} touch the arm, {on_static[live].mean():.2%} of the spheres touch the static world, "
