@@ -4,8 +4,8 @@
 // getContactPoints / getClosestPoints.  Included by pnr_queries.hip only, whose code object holds no step kernel.
 //
 // Per env: q[6], qd[6] in (48-96 B), 23 records of 9 floats out (828 B) + one float4 + six floats.  The signed-distance forms
-// (plane, sphere, oriented box with the nearest-face rule inside) and the penalty law max(0, kp depth - kd v.n) are those of
-// pnr_dyn.h sample_contact's scene-body loop, restated here so that the step kernels' code does not move.  Every sample
+// (plane, sphere, oriented box with the nearest-face rule inside), the penalty law max(0, kp depth - kd v.n) and the walk over
+// the samples are the step's own: body_distance, penalty and for_body_samples of pnr_dyn.h, the one statement of each.  Every sample
 // touches with its SURFACE; the step's one quirk (link_contacts = 0: the pointer meets ground_z with its centre) is not part
 // of the query.
 //
@@ -30,7 +30,6 @@
 namespace pnr {
 
 constexpr int kContactDim = 9;
-constexpr int kContactSamples = kCapsules[0].n + kCapsules[1].n + kCapsules[2].n + kCapsules[3].n + kCapsules[4].n;
 constexpr int kContactRowFloats = kContactSamples * kContactDim;     // 207 floats = 828 B per env
 constexpr int kContactTileFloats = kWave * kContactRowFloats;         // 13 248 floats = 52 992 B per wave
 static_assert(kNumCapsules == 5 && kContactSamples == 23, "the sample table is pnr_model.h kCapsules");
@@ -87,39 +86,6 @@ __device__ __forceinline__ void contact_frame_outward(const ContactFrame& B, flo
     velocity_outward<J>(B, qd, C, axis);
 }
 
-// signed distance of the point `pos` to the body S placed at `o`, and the body's unit outward normal there (world frame)
-__device__ __forceinline__ void body_distance(const SceneBody& S, V3 o, V3 pos, float& sdf, V3& nrm)
-{
-    const V3 dd = pos - o;
-    if (S.shape == 1) {                                // plane: unit world normal in rot[0..2]
-        nrm = {S.rot[0], S.rot[1], S.rot[2]};
-        sdf = dot(nrm, dd);
-    } else if (S.shape == 3) {                         // sphere
-        const float len = sqrtf(dot(dd, dd));
-        sdf = len - S.size[0];
-        nrm = len > 0.f ? (1.f / len) * dd : V3{0.f, 0.f, 1.f};
-    } else {                                           // oriented box: into its frame, out again with the normal
-        const V3 l = {S.rot[0] * dd.x + S.rot[3] * dd.y + S.rot[6] * dd.z, S.rot[1] * dd.x + S.rot[4] * dd.y + S.rot[7] * dd.z,
-                      S.rot[2] * dd.x + S.rot[5] * dd.y + S.rot[8] * dd.z};
-        const V3 q = {fabsf(l.x) - S.size[0], fabsf(l.y) - S.size[1], fabsf(l.z) - S.size[2]};
-        const V3 out = {fmaxf(q.x, 0.f), fmaxf(q.y, 0.f), fmaxf(q.z, 0.f)};
-        const float out2 = dot(out, out);
-        V3 nl;
-        if (out2 > 0.f) {
-            const float len = sqrtf(out2);
-            sdf = len;
-            nl = {(l.x < 0.f ? -out.x : out.x) / len, (l.y < 0.f ? -out.y : out.y) / len, (l.z < 0.f ? -out.z : out.z) / len};
-        } else {                                       // inside: out through the nearest face
-            const int km = (q.x >= q.y && q.x >= q.z) ? 0 : (q.y >= q.z ? 1 : 2);
-            sdf = comp(q, km);
-            nl = {km == 0 ? (l.x < 0.f ? -1.f : 1.f) : 0.f, km == 1 ? (l.y < 0.f ? -1.f : 1.f) : 0.f,
-                  km == 2 ? (l.z < 0.f ? -1.f : 1.f) : 0.f};
-        }
-        nrm = {S.rot[0] * nl.x + S.rot[1] * nl.y + S.rot[2] * nl.z, S.rot[3] * nl.x + S.rot[4] * nl.y + S.rot[5] * nl.z,
-               S.rot[6] * nl.x + S.rot[7] * nl.y + S.rot[8] * nl.z};
-    }
-}
-
 // per-env running summary: smallest distance, its sample and body, number of penetrating samples
 struct ContactSummary { float dist, sample, body, count; };
 
@@ -147,8 +113,8 @@ __device__ __forceinline__ void contact_sample(const ContactArgs& A, ContactBody
         V3 nrm;
         body_distance(S, o, pos, sdf, nrm);
         const float depth = radius - sdf;              // surface to surface
-        const float fn = A.ckp * depth - A.ckd * dot(vel, nrm);
-        const float f = (depth > 0.f && fn > 0.f) ? fn : 0.f;
+        float fn;
+        const float f = penalty(A.ckp, A.ckd, depth, dot(vel, nrm), fn) ? fn : 0.f;
         F = F + f * nrm;
         if (-depth < best) { best = -depth; bestn = nrm; bestb = (float)b; bestf = f; }
     }
@@ -162,14 +128,6 @@ __device__ __forceinline__ void contact_sample(const ContactArgs& A, ContactBody
     }
     if (s == 0 || best < sm.dist) { sm.dist = best; sm.sample = (float)s; sm.body = bestb; }
     sm.count += best < 0.f ? 1.f : 0.f;
-}
-
-// first sample index of capsule ci (table order)
-__host__ __device__ constexpr int contact_sample_base(int ci)
-{
-    int k = 0;
-    for (int i = 0; i < ci; ++i) k += kCapsules[i].n;
-    return k;
 }
 
 // one env: the 23 records into `row` (207 floats, or null), the summary, tau_j = sum_s a_j . ((pos_s - o_j) x F_s)
@@ -190,26 +148,14 @@ __device__ __forceinline__ void contacts_env(const ContactArgs& A, const float* 
         contact_frame_outward<J>(b, q[J], qd[J], c, axis[J]);
         b = c;
         org[J] = b.p;
-        static_for<kNumCapsules>([&](auto ci_) {
-            constexpr int ci = decltype(ci_)::value;
-            if constexpr (kCapsules[ci].body == J) {
-                static_for<kCapsules[ci].n>([&](auto i_) {
-                    constexpr int i = decltype(i_)::value;
-                    constexpr CapsuleDef K = kCapsules[ci];
-                    constexpr int s = contact_sample_base(ci) + i;
-                    constexpr float t = K.n > 1 ? (float)((double)i / (double)(K.n - 1)) : 0.f;
-                    constexpr bool tip = (ci == kNumCapsules - 1) && (i == K.n - 1);
-                    const V3 cen = tip ? V3{(float)kTipX, (float)kTipY, (float)kTipZ}
-                                       : V3{K.ax + t * (K.bx - K.ax), K.ay + t * (K.by - K.ay), K.az + t * (K.bz - K.az)};
-                    V3 pos, F;
-                    contact_sample(A, bw, bp, b, cen, K.radius < 0.f ? A.ptr_radius : K.radius, s, row ? row + kContactDim * s : nullptr, sm,
-                                   pos, F);
-                    if (want_tau) {
-                        static_for<J + 1>([&](auto k_) {                // the joints between the base and this body
-                            constexpr int k = decltype(k_)::value;
-                            tau[k] += dot(axis[k], cross(pos - org[k], F));
-                        });
-                    }
+        for_body_samples<J>([&](auto s_, V3 cen, float radius, auto) {
+            constexpr int s = decltype(s_)::value;
+            V3 pos, F;
+            contact_sample(A, bw, bp, b, cen, radius < 0.f ? A.ptr_radius : radius, s, row ? row + kContactDim * s : nullptr, sm, pos, F);
+            if (want_tau) {
+                static_for<J + 1>([&](auto k_) {                        // the joints between the base and this body
+                    constexpr int k = decltype(k_)::value;
+                    tau[k] += dot(axis[k], cross(pos - org[k], F));
                 });
             }
         });

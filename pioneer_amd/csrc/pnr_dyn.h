@@ -490,15 +490,21 @@ __device__ __forceinline__ void acc_outward(const P3& ap, const P3& vJ, float c,
     pr<AXJ>(a).x += qdd;
 }
 
+// R = Rp * R(axis_J, q_J): each row of Rp times R, (row * R) = rot(row, c, -s)
+template <int J>
+__device__ __forceinline__ M3 rot_outward(const M3& Rp, float c, float s)
+{
+    constexpr int AXJ = (int)kJoints[J].axis;
+    return {rot<AXJ>(Rp.r0, c, -s), rot<AXJ>(Rp.r1, c, -s), rot<AXJ>(Rp.r2, c, -s)};
+}
+
 // world pose of body J from its parent's (for the pointer/ground contact)
 template <int J>
 __device__ __forceinline__ void pose_outward(const M3& Rp, V3 pp, float c, float s, M3& R, V3& p)
 {
-    constexpr int AXJ = (int)kJoints[J].axis;
     constexpr float ox = (float)kJoints[J].ox, oy = (float)kJoints[J].oy, oz = (float)kJoints[J].oz;
     p = pp + mul(Rp, V3{ox, oy, oz});
-    // R = Rp * R(axis, q): rows of Rp times R  -> row' = R^T-applied... (row * R) = rot(row, c, -s)
-    R = {rot<AXJ>(Rp.r0, c, -s), rot<AXJ>(Rp.r1, c, -s), rot<AXJ>(Rp.r2, c, -s)};
+    R = rot_outward<J>(Rp, c, s);
 }
 
 // ---------------------------------------------------------------------------------
@@ -514,29 +520,66 @@ struct WorldBody {
 };
 struct SphereLane { V3 x, v; float m, r; V3 F; };
 
-// signed distance of l (in the box's frame) to the box of half extents hx, hy, hz and the outward normal there (the forms of
-// sample_contact below: outside the nearest surface point's direction, inside out through the nearest face)
-__device__ __forceinline__ float box_sdf(V3 l, float hx, float hy, float hz, V3& nl)
+// ---------------------------------------------------------------------------------
+// The contact geometry of the static bodies and the penalty law, stated once for the step's arm samples (sample_contact), the
+// moving sphere (sphere_static) and pnr_get_contacts (pnr_contacts.h contact_sample): the nearest-face tie rule, the fallback of
+// a zero-length normal and the surface-to-surface convention are the same text for all three.
+// ---------------------------------------------------------------------------------
+// signed distance of l (in the box's frame) to the box of half extents h and the outward normal there: outside the direction of
+// the nearest surface point, inside out through the nearest face
+__device__ __forceinline__ void box_sdf(V3 l, const float (&h)[3], float& sdf, V3& nl)
 {
-    const V3 q = {fabsf(l.x) - hx, fabsf(l.y) - hy, fabsf(l.z) - hz};
+    const V3 q = {fabsf(l.x) - h[0], fabsf(l.y) - h[1], fabsf(l.z) - h[2]};
     const V3 o = {fmaxf(q.x, 0.f), fmaxf(q.y, 0.f), fmaxf(q.z, 0.f)};
     const float out2 = dot(o, o);
     if (out2 > 0.f) {
         const float len = sqrtf(out2);
+        sdf = len;
         nl = {(l.x < 0.f ? -o.x : o.x) / len, (l.y < 0.f ? -o.y : o.y) / len, (l.z < 0.f ? -o.z : o.z) / len};
-        return len;
+    } else {                                           // inside: out through the nearest face
+        const int km = (q.x >= q.y && q.x >= q.z) ? 0 : (q.y >= q.z ? 1 : 2);
+        sdf = comp(q, km);
+        nl = {km == 0 ? (l.x < 0.f ? -1.f : 1.f) : 0.f, km == 1 ? (l.y < 0.f ? -1.f : 1.f) : 0.f,
+              km == 2 ? (l.z < 0.f ? -1.f : 1.f) : 0.f};
     }
-    const int km = (q.x >= q.y && q.x >= q.z) ? 0 : (q.y >= q.z ? 1 : 2);
-    nl = {km == 0 ? (l.x < 0.f ? -1.f : 1.f) : 0.f, km == 1 ? (l.y < 0.f ? -1.f : 1.f) : 0.f, km == 2 ? (l.z < 0.f ? -1.f : 1.f) : 0.f};
-    return comp(q, km);
+}
+
+// signed distance of the point `pos` to the body S placed at `o`, and the body's unit outward normal there (world frame)
+__device__ __forceinline__ void body_distance(const SceneBody& S, V3 o, V3 pos, float& sdf, V3& nrm)
+{
+    const V3 dd = pos - o;
+    if (S.shape == 1) {                                // plane: unit world normal in rot[0..2]
+        nrm = {S.rot[0], S.rot[1], S.rot[2]};
+        sdf = dot(nrm, dd);
+    } else if (S.shape == 3) {                         // sphere
+        const float len = sqrtf(dot(dd, dd));
+        sdf = len - S.size[0];
+        nrm = len > 0.f ? (1.f / len) * dd : V3{0.f, 0.f, 1.f};
+    } else {                                           // oriented box: into its frame, out again with the normal
+        const V3 l = {S.rot[0] * dd.x + S.rot[3] * dd.y + S.rot[6] * dd.z, S.rot[1] * dd.x + S.rot[4] * dd.y + S.rot[7] * dd.z,
+                      S.rot[2] * dd.x + S.rot[5] * dd.y + S.rot[8] * dd.z};
+        V3 nl;
+        box_sdf(l, S.size, sdf, nl);
+        nrm = {S.rot[0] * nl.x + S.rot[1] * nl.y + S.rot[2] * nl.z, S.rot[3] * nl.x + S.rot[4] * nl.y + S.rot[5] * nl.z,
+               S.rot[6] * nl.x + S.rot[7] * nl.y + S.rot[8] * nl.z};
+    }
+}
+
+// The penalty law of every contact: fn = kp depth - kd vn for a contact of depth `depth` whose surfaces part at vn along the normal.
+// True while it acts, depth > 0 and fn > 0: the force is max(0, fn) gated on depth > 0.  The test and fn are handed out separately so
+// that a caller's `if` is the one the kernels were tuned with (the other forms tried: DESIGN.md 3s)
+__device__ __forceinline__ bool penalty(float kp, float kd, float depth, float vn, float& fn)
+{
+    fn = kp * depth - kd * vn;
+    return depth > 0.f && fn > 0.f;
 }
 
 // one static contact of the sphere, surface to surface: the penalty force along n plus the regularised sliding friction
 __device__ __forceinline__ void sphere_touch(const WorldBody& B, SphereLane& S, float sdf, V3 n)
 {
-    const float depth = S.r - sdf, vn = dot(S.v, n);
-    const float fn = B.kp * depth - B.kd * vn;
-    if (depth > 0.f && fn > 0.f) {
+    const float vn = dot(S.v, n);
+    float fn;
+    if (penalty(B.kp, B.kd, S.r - sdf, vn, fn)) {
         const V3 vt = S.v - vn * n;
         const float k = B.friction * fn * __builtin_amdgcn_rsqf(dot(vt, vt) + B.slip_eps * B.slip_eps);
         S.F = S.F + fn * n - k * vt;
@@ -549,30 +592,15 @@ __device__ __forceinline__ void sphere_static(const DynParams& D, const WorldBod
     S.F = {0.f, 0.f, 0.f};
     if (D.has_ground) sphere_touch(B, S, S.x.z - D.ground_z, V3{0.f, 0.f, 1.f});
     if (D.has_box) {
-        V3 nrm;
-        const float sdf = box_sdf(V3{S.x.x - D.box_c[0], S.x.y - D.box_c[1], S.x.z - D.box_c[2]}, D.box_h[0], D.box_h[1], D.box_h[2], nrm);
+        V3 nrm; float sdf;
+        box_sdf(S.x - V3{D.box_c[0], D.box_c[1], D.box_c[2]}, D.box_h, sdf, nrm);
         sphere_touch(B, S, sdf, nrm);
     }
 #pragma unroll 1
     for (int b = 0; b < D.n_scene; ++b) {
         const SceneBody Sb = D.scene[b];
-        const V3 dd = {S.x.x - Sb.pos[0], S.x.y - Sb.pos[1], S.x.z - Sb.pos[2]};
         V3 nrm; float sdf;
-        if (Sb.shape == 1) {
-            nrm = {Sb.rot[0], Sb.rot[1], Sb.rot[2]};
-            sdf = dot(nrm, dd);
-        } else if (Sb.shape == 3) {
-            const float len = sqrtf(dot(dd, dd));
-            sdf = len - Sb.size[0];
-            nrm = len > 0.f ? (1.f / len) * dd : V3{0.f, 0.f, 1.f};
-        } else {
-            const V3 l = {Sb.rot[0] * dd.x + Sb.rot[3] * dd.y + Sb.rot[6] * dd.z, Sb.rot[1] * dd.x + Sb.rot[4] * dd.y + Sb.rot[7] * dd.z,
-                          Sb.rot[2] * dd.x + Sb.rot[5] * dd.y + Sb.rot[8] * dd.z};
-            V3 nl;
-            sdf = box_sdf(l, Sb.size[0], Sb.size[1], Sb.size[2], nl);
-            nrm = {Sb.rot[0] * nl.x + Sb.rot[1] * nl.y + Sb.rot[2] * nl.z, Sb.rot[3] * nl.x + Sb.rot[4] * nl.y + Sb.rot[5] * nl.z,
-                   Sb.rot[6] * nl.x + Sb.rot[7] * nl.y + Sb.rot[8] * nl.z};
-        }
+        body_distance(Sb, V3{Sb.pos[0], Sb.pos[1], Sb.pos[2]}, S.x, sdf, nrm);
         sphere_touch(B, S, sdf, nrm);
     }
 }
@@ -586,9 +614,9 @@ __device__ __forceinline__ void sphere_integrate(const DynParams& D, const World
 }
 
 // Penalty contact of ONE sample sphere (centre c in the frame of the body whose world pose is R, p and whose spatial
-// velocity in body coordinates is vb) with the ground plane and the static axis-aligned box (the reference demo's scene
-// extras, pioneer_knm_env.py:249-261; create_body_plane / create_body_box, bullet_scene.py:206-228): the contact force
-// is added to the body's external spatial force in body coordinates.
+// velocity in body coordinates is vb) with the ground plane, the static axis-aligned box (the reference demo's scene
+// extras, pioneer_knm_env.py:249-261; create_body_plane / create_body_box, bullet_scene.py:206-228) and the scene's bodies: the
+// contact force is added to the body's external spatial force in body coordinates.
 // SPHERE (kWorldBody): the sample also meets the env's moving sphere S; the pair's force goes to S.F and, reversed, into F here.
 template <bool SPHERE = false>
 __device__ __forceinline__ void sample_contact(const DynParams& D, const M3& R, V3 p, const P3& vb, V3 c, float radius, P3& fext,
@@ -597,86 +625,53 @@ __device__ __forceinline__ void sample_contact(const DynParams& D, const M3& R, 
     const V3 pos = p + mul(R, c);                           // world position of the sphere centre
     const V3 vw = mul(R, lin(vb) + cross(ang(vb), c));      // its world velocity
     V3 F = {0.f, 0.f, 0.f};
+    // the ground: the pointer alone touches with its centre (the r01 form); with link contacts every sphere with its surface.
+    // F is zero still, so this is an assignment (why not `+=`: DESIGN.md 3s)
     if (D.has_ground) {
-        // the pointer alone touches with its centre (the r01 form); with link contacts every sphere with its surface
-        const float depth = D.ground_z - pos.z + (D.link_contacts ? radius : 0.f);
-        const float fz = D.ckp * depth - D.ckd * vw.z;
-        if (depth > 0.f && fz > 0.f) F.z += fz;
+        float fz;
+        F.z = penalty(D.ckp, D.ckd, D.ground_z - pos.z + (D.link_contacts ? radius : 0.f), vw.z, fz) ? fz : 0.f;
     }
     if (D.has_box) {
-        // signed distance of the centre to the axis-aligned box and its outward normal
-        const V3 dd = {pos.x - D.box_c[0], pos.y - D.box_c[1], pos.z - D.box_c[2]};
-        const V3 q = {fabsf(dd.x) - D.box_h[0], fabsf(dd.y) - D.box_h[1], fabsf(dd.z) - D.box_h[2]};
-        const V3 o = {fmaxf(q.x, 0.f), fmaxf(q.y, 0.f), fmaxf(q.z, 0.f)};
-        const float out2 = dot(o, o);
         V3 nrm; float sdf;
-        if (out2 > 0.f) {
-            const float len = sqrtf(out2);
-            sdf = len;
-            nrm = {(dd.x < 0.f ? -o.x : o.x) / len, (dd.y < 0.f ? -o.y : o.y) / len, (dd.z < 0.f ? -o.z : o.z) / len};
-        } else {                                          // inside: out through the nearest face
-            const int km = (q.x >= q.y && q.x >= q.z) ? 0 : (q.y >= q.z ? 1 : 2);
-            sdf = comp(q, km);
-            nrm = {km == 0 ? (dd.x < 0.f ? -1.f : 1.f) : 0.f, km == 1 ? (dd.y < 0.f ? -1.f : 1.f) : 0.f,
-                   km == 2 ? (dd.z < 0.f ? -1.f : 1.f) : 0.f};
-        }
-        const float depth = radius - sdf;
-        const float fn = D.ckp * depth - D.ckd * dot(vw, nrm);
-        if (depth > 0.f && fn > 0.f) F = F + fn * nrm;
+        box_sdf(pos - V3{D.box_c[0], D.box_c[1], D.box_c[2]}, D.box_h, sdf, nrm);
+        float fn;
+        if (penalty(D.ckp, D.ckd, radius - sdf, dot(vw, nrm), fn)) F = F + fn * nrm;
     }
-    // the scene's static bodies: wave-uniform loop over a small device array, the sample touches with its surface.  Same signed-distance forms as the oracle's contact_force_sphere.
+    // the scene's static bodies: wave-uniform loop over a small device array, the sample touches with its surface
 #pragma unroll 1
     for (int b = 0; b < D.n_scene; ++b) {
-        const SceneBody S = D.scene[b];
-        const V3 dd = {pos.x - S.pos[0], pos.y - S.pos[1], pos.z - S.pos[2]};
+        const SceneBody Sb = D.scene[b];
         V3 nrm; float sdf;
-        if (S.shape == 1) {                                // plane: unit world normal in rot[0..2]
-            nrm = {S.rot[0], S.rot[1], S.rot[2]};
-            sdf = dot(nrm, dd);
-        } else if (S.shape == 3) {                         // sphere
-            const float len = sqrtf(dot(dd, dd));
-            sdf = len - S.size[0];
-            nrm = len > 0.f ? (1.f / len) * dd : V3{0.f, 0.f, 1.f};
-        } else {                                           // oriented box: into its frame, out again with the normal
-            const V3 l = {S.rot[0] * dd.x + S.rot[3] * dd.y + S.rot[6] * dd.z, S.rot[1] * dd.x + S.rot[4] * dd.y + S.rot[7] * dd.z,
-                          S.rot[2] * dd.x + S.rot[5] * dd.y + S.rot[8] * dd.z};
-            const V3 q = {fabsf(l.x) - S.size[0], fabsf(l.y) - S.size[1], fabsf(l.z) - S.size[2]};
-            const V3 o = {fmaxf(q.x, 0.f), fmaxf(q.y, 0.f), fmaxf(q.z, 0.f)};
-            const float out2 = dot(o, o);
-            V3 nl;
-            if (out2 > 0.f) {
-                const float len = sqrtf(out2);
-                sdf = len;
-                nl = {(l.x < 0.f ? -o.x : o.x) / len, (l.y < 0.f ? -o.y : o.y) / len, (l.z < 0.f ? -o.z : o.z) / len};
-            } else {
-                const int km = (q.x >= q.y && q.x >= q.z) ? 0 : (q.y >= q.z ? 1 : 2);
-                sdf = comp(q, km);
-                nl = {km == 0 ? (l.x < 0.f ? -1.f : 1.f) : 0.f, km == 1 ? (l.y < 0.f ? -1.f : 1.f) : 0.f,
-                      km == 2 ? (l.z < 0.f ? -1.f : 1.f) : 0.f};
-            }
-            nrm = {S.rot[0] * nl.x + S.rot[1] * nl.y + S.rot[2] * nl.z, S.rot[3] * nl.x + S.rot[4] * nl.y + S.rot[5] * nl.z,
-                   S.rot[6] * nl.x + S.rot[7] * nl.y + S.rot[8] * nl.z};
-        }
-        const float depth = radius - sdf;
-        const float fn = D.ckp * depth - D.ckd * dot(vw, nrm);
-        if (depth > 0.f && fn > 0.f) F = F + fn * nrm;
+        body_distance(Sb, V3{Sb.pos[0], Sb.pos[1], Sb.pos[2]}, pos, sdf, nrm);
+        float fn;
+        if (penalty(D.ckp, D.ckd, radius - sdf, dot(vw, nrm), fn)) F = F + fn * nrm;
     }
     if constexpr (SPHERE) {
         const V3 d = S->x - pos;
         const float len = sqrtf(dot(d, d));
         const V3 nrm = len > 0.f ? (1.f / len) * d : V3{0.f, 0.f, 1.f};
-        const float depth = S->r + radius - len;
-        const float fn = B->kp * depth - B->kd * dot(S->v - vw, nrm);
-        if (S->m > 0.f && depth > 0.f && fn > 0.f) { S->F = S->F + fn * nrm; F = F - fn * nrm; }
+        float fn;
+        const bool hit = penalty(B->kp, B->kd, S->r + radius - len, dot(S->v - vw, nrm), fn);
+        if (S->m > 0.f && hit) { S->F = S->F + fn * nrm; F = F - fn * nrm; }
     }
     const V3 fb = mulT(R, F);                             // R^T F
     fext = fext + pack(cross(c, fb), fb);
 }
 
-// every sample sphere of moving body BODY (compile-time table kCapsules); without link contacts only the pointer
-template <int BODY, bool SPHERE = false>
-__device__ __forceinline__ void body_contacts(const DynParams& D, const M3& R, V3 p, const P3& vb, P3& fext, const WorldBody* B = nullptr,
-                                              SphereLane* S = nullptr)
+// first sample index of capsule ci in table order; of kNumCapsules: the number of samples
+__host__ __device__ constexpr int contact_sample_base(int ci)
+{
+    int k = 0;
+    for (int i = 0; i < ci; ++i) k += kCapsules[i].n;
+    return k;
+}
+constexpr int kContactSamples = contact_sample_base(kNumCapsules);
+
+// The sample spheres of moving body BODY, in the order of the compile-time table kCapsules: f(s, c, radius, tip) with the sample's
+// table index s (an integral_constant), its centre c in the body's frame, its radius (< 0: the pointer's, a run-time parameter)
+// and whether it is the pointer itself, the last sample of the last capsule (a bool_constant); every one a constant in the callee.
+template <int BODY, class F>
+__device__ __forceinline__ void for_body_samples(F&& f)
 {
     static_for<kNumCapsules>([&](auto ci_) {
         constexpr int ci = decltype(ci_)::value;
@@ -688,9 +683,19 @@ __device__ __forceinline__ void body_contacts(const DynParams& D, const M3& R, V
                 constexpr bool tip = (ci == kNumCapsules - 1) && (i == K.n - 1);
                 const V3 c = tip ? V3{(float)kTipX, (float)kTipY, (float)kTipZ}
                                  : V3{K.ax + t * (K.bx - K.ax), K.ay + t * (K.by - K.ay), K.az + t * (K.bz - K.az)};
-                if (tip || D.link_contacts) sample_contact<SPHERE>(D, R, p, vb, c, K.radius < 0.f ? D.ptr_radius : K.radius, fext, B, S);
+                f(std::integral_constant<int, contact_sample_base(ci) + i>{}, c, K.radius, std::bool_constant<tip>{});
             });
         }
+    });
+}
+
+// every sample sphere of moving body BODY; without link contacts only the pointer
+template <int BODY, bool SPHERE = false>
+__device__ __forceinline__ void body_contacts(const DynParams& D, const M3& R, V3 p, const P3& vb, P3& fext, const WorldBody* B = nullptr,
+                                              SphereLane* S = nullptr)
+{
+    for_body_samples<BODY>([&](auto, V3 c, float radius, auto tip) {
+        if (tip || D.link_contacts) sample_contact<SPHERE>(D, R, p, vb, c, radius < 0.f ? D.ptr_radius : radius, fext, B, S);
     });
 }
 
@@ -750,14 +755,6 @@ __device__ __forceinline__ void load_joint_torques(const float* __restrict__ tau
     const float2* t2 = reinterpret_cast<const float2*>(tau_ext) + 3 * e;
     const float2 x0 = t2[0], x1 = t2[1], x2 = t2[2];
     tx[0] = x0.x; tx[1] = x0.y; tx[2] = x1.x; tx[3] = x1.y; tx[4] = x2.x; tx[5] = x2.y;
-}
-
-// R <- R * R(axis_J, q_J): the rotation part of pose_outward
-template <int J>
-__device__ __forceinline__ M3 rot_outward(const M3& Rp, float c, float s)
-{
-    constexpr int AXJ = (int)kJoints[J].axis;
-    return {rot<AXJ>(Rp.r0, c, -s), rot<AXJ>(Rp.r1, c, -s), rot<AXJ>(Rp.r2, c, -s)};
 }
 
 // before the sub-steps, at the pose q0 of the call's start (c, s = cos / sin q0)

@@ -9,12 +9,11 @@
 // nvalid is written.  Two flushes, on purpose: a dense tile (stride = row length: 143, 207) is copied as it lies, a short last
 // tile's tail float by float; the 6 x 6 tile (36 floats at stride 37) is gathered row by row, which the dense kernels do not want.
 //
-// Deliberately NOT shared: flush_tile of pnr_device.h (its alignment branch) and the contact signed-distance code, which stays
-// twice (pnr_contacts.h body_distance, pnr_dyn.h sample_contact): the step kernels' four headers are the fingerprint of the
-// counter values under profiles/ and do not move.  The outward sweep is pose_outward (pnr_dyn.h), then velocity_outward, as two
-// calls: link_body_outward's quaternion product sits between them, and on either side of one fused call it changes
-// link_state_kernel's register allocation.  chain_jacobian (pnr_ik.h) keeps its own walk over pose_outward: it skips the joints
-// beyond the body on a scalar branch and carries no velocity.
+// Deliberately NOT shared: flush_tile of pnr_device.h (its alignment branch).  The contact geometry (box_sdf, body_distance, the
+// penalty law, the walk over the sample spheres) is stated once, in pnr_dyn.h, for the step and for pnr_contacts.h alike.  The
+// outward sweep is pose_outward (pnr_dyn.h), then velocity_outward, as two calls: link_body_outward's quaternion product sits
+// between them, and on either side of one fused call it changes link_state_kernel's register allocation.  chain_jacobian
+// (pnr_ik.h) keeps its own walk over pose_outward: it skips the joints beyond the body on a scalar branch and carries no velocity.
 #pragma once
 
 #include <hip/hip_runtime.h>
