@@ -1,7 +1,8 @@
 """Independent reference of pnr_get_contacts: the arm's 23 contact sample spheres against static planes, boxes and spheres.
 
 Built from tests/golden/urdf_chain.json (through link_kinematics_ref.link_frames) and its own copy of the sample table; it
-imports nothing of pioneer_amd.  The law it restates (include/pioneer_amd.h):
+imports nothing of pioneer_amd.  `body_distance` is the one statement under tests/ of the plane / sphere / box signed distance
+(tests/moving_sphere_ref.py takes its static world from it).  The law it restates (include/pioneer_amd.h):
 
 * sample s is a sphere (centre c_s in the frame of URDF link L_s, radius r_s; the needle's three samples take the pointer's
   radius) and touches every body with its surface: distance = sdf_body(centre) - r_s;
@@ -11,8 +12,9 @@ imports nothing of pioneer_amd.  The law it restates (include/pioneer_amd.h):
 * record of sample s: the nearest body's (distance, n, centre - r n, b, f); summary: the smallest distance, its sample, its body,
   the number of samples with distance < 0; tau_j = sum_s a_j . ((x_s - o_j) x F_s), F_s the sum over all bodies.
 
-`query(..., dtype=np.float32)` runs the same arithmetic in float32 (its own sweep over the chain, `frames`): the difference to
-float64 on the same inputs is what float32 alone costs, whatever the order of operations.
+`query(..., dtype=np.float32)` runs the same arithmetic in float32 (link_frames in float32, the joints' rotations written entry
+by entry: link_kinematics_ref.coordinate_rotation): the difference to float64 on the same inputs is what float32 alone costs,
+whatever the order of operations.
 """
 import numpy as np
 
@@ -70,41 +72,9 @@ def sphere(radius, position):
     return dict(shape="sphere", position=tuple(map(float, position)), quat=(0.0, 0.0, 0.0, 1.0), size=(float(radius), 0.0, 0.0))
 
 
-def frames(q, qd, dtype=np.float64, chain=None):
-    """The sweep of link_kinematics_ref.link_frames in `dtype` (every fixed joint of the chain has rpy 0, asserted)."""
-    chain = chain or lk.load_chain()
-    q = np.atleast_2d(np.asarray(q, dtype=dtype)); qd = np.atleast_2d(np.asarray(qd, dtype=dtype))
-    n = q.shape[0]
-    eye = np.broadcast_to(np.eye(3, dtype=dtype), (n, 3, 3))
-    zero = np.zeros((n, 3), dtype=dtype)
-    fr = {"world": (eye, zero, zero, zero)}
-    out, qi = [], 0
-    for j in chain:
-        assert tuple(j["rpy"]) == (0, 0, 0)
-        Rp, pp, vp, wp = fr[j["parent"]]
-        p = pp + Rp @ np.asarray(j["xyz"], dtype=dtype)
-        R, w = Rp, wp
-        if j["type"] == "revolute":
-            axis = np.asarray(j["axis"], dtype=dtype)
-            k = int(np.argmax(np.abs(axis)))
-            assert abs(axis[k]) == 1.0 and np.count_nonzero(axis) == 1
-            a, b = (k + 1) % 3, (k + 2) % 3
-            c, s = np.cos(q[:, qi]), np.sin(q[:, qi]) * dtype(axis[k])
-            Rq = np.zeros((n, 3, 3), dtype=dtype)
-            Rq[:, k, k] = 1
-            Rq[:, a, a] = c; Rq[:, a, b] = -s; Rq[:, b, a] = s; Rq[:, b, b] = c
-            w = wp + qd[:, qi:qi + 1] * (Rp @ axis)
-            R = Rp @ Rq
-            qi += 1
-        v = vp + np.cross(wp, p - pp)
-        fr[j["child"]] = (R, p, v, w)
-        out.append((R, p, v, w))
-    return tuple(np.stack([o[i] for o in out], axis=1) for i in range(4))
-
-
 def body_frame(b):
     """float64: the body's rotation from its quaternion (x, y, z, w), normalised; a plane's unit world normal"""
-    R = lk.matrix_from_quat(np.asarray(b["quat"], dtype=np.float64)[None] / np.linalg.norm(b["quat"]))[0]
+    R = lk.matrix_from_quat(b["quat"])
     normal = None
     if b["shape"] == "plane":
         nrm = np.asarray(b["size"], dtype=np.float64)
@@ -152,10 +122,7 @@ def query(q, qd, bodies, body_positions=None, kp=2000.0, kd=50.0, pointer_radius
     force [N, 23, 3] (F_s over all bodies); box_gap [N, 23] (the smallest nearest-face gap over the boxes the centre is inside);
     lever [N] (the longest |x_s - o_j| over the samples and their inboard joints)."""
     dtype = np.dtype(dtype).type
-    if dtype is np.float64:
-        R, p, v, w = lk.link_frames(q, qd)
-    else:
-        R, p, v, w = frames(q, qd, dtype)
+    R, p, v, w = lk.link_frames(q, qd, dtype=dtype, rotation=lk.axis_rotation if dtype is np.float64 else lk.coordinate_rotation)
     n, nb = p.shape[0], len(bodies)
     kp, kd = dtype(kp), dtype(kd)
     bp = None if body_positions is None else np.asarray(body_positions, dtype=dtype).reshape(n, nb, 3)

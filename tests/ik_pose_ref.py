@@ -21,10 +21,10 @@ axis cannot be formed (half a turn, opposite vectors: |s| = 0, c < 0) the max() 
 `angle` stays pi.
 
 `dtype=np.float32` gives the float32 emulation of the law: a second correct float32 implementation, whose distance from the
-float64 law measures what float32 rounding alone does to the joints.  Its chain walk (kinematics_f32) rounds every link's
-rotation and position, the sines and cosines, the Jacobian and the error to float32, the target's rotation is formed in float32
-from the float32 quaternion (rotation_from_quat_f32); the system, its solve and the update run in float32 (numpy's float32 matmul
-and LAPACK's sgesv).  The float64 law itself uses ik_ref.jacobian and lk.link_frames only.
+float64 law measures what float32 rounding alone does to the joints.  kinematics_f32 (lk.link_frames in float32) rounds every
+link's rotation and position, the sines and cosines, the Jacobian and the error to float32, the target's rotation is formed in
+float32 from the float32 quaternion (lk.matrix_from_quat in float32); the system, its solve and the update run in float32 (numpy's
+float32 matmul and LAPACK's sgesv).  The float64 law itself uses ik_ref.jacobian and lk.link_frames only.
 """
 import numpy as np
 
@@ -37,27 +37,6 @@ DEFAULTS = dict(max_iterations=32, damping=0.03, error_damping=0.01, orientation
 LIMITS = np.array([3.1416, 1.309, 1.309, 3.1416, 1.5708, 3.1416])
 INNER_LO, INNER_HI = np.array([15.0, -8.0, 2.0]), np.array([22.0, 8.0, 6.0])
 S_FLOOR = 1e-12
-
-
-def rotation_from_quat(quat):
-    """[N, 3, 3] of quaternions (x, y, z, w) [N, 4], normalised here; the sign of w does not matter."""
-    quat = np.atleast_2d(np.asarray(quat, dtype=np.float64))
-    return lk.matrix_from_quat(quat / np.linalg.norm(quat, axis=1, keepdims=True))
-
-
-def rotation_from_quat_f32(quat):
-    """rotation_from_quat with every operation in float32: what a float32 implementation makes of its float32 input."""
-    f = np.float32
-    quat = np.atleast_2d(np.asarray(quat, dtype=f))
-    quat = quat / np.sqrt((quat * quat).sum(axis=1, keepdims=True, dtype=f))
-    x, y, z, w = (quat[:, i] for i in range(4))
-    one, two = f(1), f(2)
-    R = np.stack([
-        np.stack([one - two * (y * y + z * z), two * (x * y - z * w), two * (x * z + y * w)], axis=1),
-        np.stack([two * (x * y + z * w), one - two * (x * x + z * z), two * (y * z - x * w)], axis=1),
-        np.stack([two * (x * z - y * w), two * (y * z + x * w), one - two * (x * x + y * y)], axis=1)], axis=1)
-    assert R.dtype == f
-    return R
 
 
 def link_pose(q, link=10, local_point=None, chain=None):
@@ -85,38 +64,23 @@ def orientation_error(R, R_target, mode=FULL, local_axis=(1.0, 0.0, 0.0)):
 def pose_error(q, target_pos, target_quat, mode=FULL, local_axis=(1.0, 0.0, 0.0), link=10, local_point=None, chain=None):
     """(distance [N], angle [N]) of the joints q [N, 6] from the target pose, by the float64 chain."""
     p, R = link_pose(np.asarray(q, dtype=np.float64), link, local_point, chain)
-    _, angle = orientation_error(R, rotation_from_quat(target_quat), mode, local_axis)
+    _, angle = orientation_error(R, lk.matrix_from_quat(np.atleast_2d(target_quat)), mode, local_axis)
     return np.linalg.norm(np.asarray(target_pos, dtype=np.float64) - p, axis=1), angle
 
 
 def kinematics_f32(q, link=10, local_point=None, chain=None):
-    """The chain walked with float32 results at every step: (point [N, 3], R of the link [N, 3, 3], J [N, 6, 6]) in float32."""
+    """From the chain walked with float32 results at every step: (point [N, 3], R of the link [N, 3, 3], J [N, 6, 6]) in float32."""
     f = np.float32
-    chain = chain or lk.load_chain()
     q = np.atleast_2d(np.asarray(q, dtype=f))
-    n = q.shape[0]
-    frames = {"world": (np.broadcast_to(np.eye(3, dtype=f), (n, 3, 3)), np.zeros((n, 3), dtype=f))}
-    axes, qi = [], 0
-    for j in chain[:link + 1]:
-        Rp, pp = frames[j["parent"]]
-        p = (pp + Rp @ np.asarray(j["xyz"], dtype=f)).astype(f)
-        R = (Rp @ lk.rpy_rotation(j["rpy"]).astype(f)).astype(f)
-        if j["type"] == "revolute":
-            axis = np.asarray(j["axis"], dtype=np.float64)
-            K = np.array([[0.0, -axis[2], axis[1]], [axis[2], 0.0, -axis[0]], [-axis[1], axis[0], 0.0]]).astype(f)
-            sn, cs = np.sin(q[:, qi]).astype(f)[:, None, None], np.cos(q[:, qi]).astype(f)[:, None, None]
-            rot = (np.eye(3, dtype=f)[None] + sn * K[None] + (f(1) - cs) * (K @ K)[None]).astype(f)
-            axes.append((qi, (R @ axis.astype(f)).astype(f), p))
-            R = (R @ rot).astype(f)
-            qi += 1
-        frames[j["child"]] = (R, p)
+    # (with qdd the walk hands out the joints' world axes as it forms them, before the joint's own rotation)
+    R, p, _, _, _, _, axes, origins = lk.link_frames(q, chain=chain, qdd=np.zeros_like(q), dtype=f, upto=link)
     local = np.zeros(3, dtype=f) if local_point is None else np.asarray(local_point, dtype=f)
-    point = (p + R @ local).astype(f)
-    J = np.zeros((n, 6, 6), dtype=f)
-    for col, a, o in axes:
-        J[:, 0:3, col] = np.cross(a, (point - o).astype(f)).astype(f)
-        J[:, 3:6, col] = a
-    return point, R, J
+    point = p[:, link] + R[:, link] @ local
+    J = np.zeros((q.shape[0], 6, 6), dtype=f)
+    J[:, 0:3, :axes.shape[1]] = np.cross(axes, point[:, None] - origins).transpose(0, 2, 1)
+    J[:, 3:6, :axes.shape[1]] = axes.transpose(0, 2, 1)
+    assert point.dtype == R.dtype == J.dtype == f
+    return point, R[:, link], J
 
 
 def solve_ik_pose(target_pos, target_quat, q_init=None, link=10, local_point=None, mode=FULL, local_axis=(1.0, 0.0, 0.0),
@@ -125,7 +89,7 @@ def solve_ik_pose(target_pos, target_quat, q_init=None, link=10, local_point=Non
     """Returns (q [N, 6], residual [N], angle [N], iterations [N] int).  Limits: the float32 limits of the engine."""
     chain = chain or lk.load_chain()
     target_pos = np.atleast_2d(np.asarray(target_pos, dtype=np.float64))
-    Rt = rotation_from_quat_f32(target_quat).astype(np.float64) if dtype is np.float32 else rotation_from_quat(target_quat)
+    Rt = lk.matrix_from_quat(np.atleast_2d(target_quat), dtype).astype(np.float64)
     n = target_pos.shape[0]
     lo, hi = (v.astype(dtype) for v in ik_ref.limits_f32(chain))
     q = np.zeros((n, 6)) if q_init is None else np.array(np.broadcast_to(np.asarray(q_init, dtype=np.float64), (n, 6)))

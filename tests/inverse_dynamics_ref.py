@@ -14,6 +14,7 @@ of it has the dtype it is called with: in float64 the CPU tests hold it against 
 """
 import numpy as np
 
+import ik_ref
 import link_kinematics_ref as lk
 import world_step_ref as wref
 
@@ -51,40 +52,10 @@ def inverse_dynamics(orc, qdd=None, gravity=0.0, joint_losses=False):
 
 
 # ---- the second statement: world-frame Newton-Euler over the URDF links, in the caller's dtype -----------------------------------
-def _axis_rotation(axis, q, T):
-    a = np.asarray(axis, dtype=T)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]], dtype=T)
-    s, c = np.sin(q)[:, None, None], np.cos(q)[:, None, None]
-    return (np.eye(3, dtype=T)[None] + s * K[None] + (T(1) - c) * (K @ K)[None]).astype(T)
-
-
-def _sweep(q, qd, qdd, gravity, T, chain):
-    """Per link: origin p, angular acceleration, linear acceleration of the origin (gravity as the base's +g z), the number of
-    revolute joints up to it; per revolute joint: world axis and origin."""
-    n = q.shape[0]
-    z = np.zeros((n, 3), dtype=T)
-    g0 = z.copy()
-    g0[:, 2] = T(gravity)
-    frames = {"world": (np.broadcast_to(np.eye(3, dtype=T), (n, 3, 3)), z, z, z, g0)}
-    links, joints, qi = [], [], 0
-    for j in chain:
-        Rp, pp, wp, alp, accp = frames[j["parent"]]
-        d = (Rp @ np.asarray(j["xyz"], dtype=T)).astype(T)
-        p = pp + d
-        R = (Rp @ lk.rpy_rotation(j["rpy"]).astype(T)).astype(T)
-        w, al = wp, alp
-        acc = accp + np.cross(alp, d) + np.cross(wp, np.cross(wp, d))
-        if j["type"] == "revolute":
-            axis = np.asarray(j["axis"], dtype=T)
-            a = (R @ axis).astype(T)
-            w = wp + qd[:, qi:qi + 1] * a
-            al = alp + qdd[:, qi:qi + 1] * a + qd[:, qi:qi + 1] * np.cross(wp, a)
-            R = (R @ _axis_rotation(axis, q[:, qi], T)).astype(T)
-            joints.append((a, p))
-            qi += 1
-        frames[j["child"]] = (R, p, w, al, acc)
-        links.append((p, al.astype(T), acc.astype(T), len(joints)))
-    return links, joints
+def joints_upstream(chain):
+    """per link, the number of revolute joints up to it"""
+    idx = ik_ref.revolute_links(chain)[0]
+    return [sum(k <= l for k in idx) for l in range(len(chain))]
 
 
 def newton_euler(q, qd, qdd, scales, gravity, dtype=np.float64, chain=None):
@@ -93,14 +64,14 @@ def newton_euler(q, qd, qdd, scales, gravity, dtype=np.float64, chain=None):
     T = np.dtype(dtype).type
     chain = chain or lk.load_chain()
     q, qd, qdd, scales = (np.atleast_2d(np.asarray(x, dtype=T)) for x in (q, qd, qdd, scales))
-    links, joints = _sweep(q, qd, qdd, gravity, T, chain)
+    _, p, _, _, al, acc, axes, origins = lk.link_frames(q, qd, chain, qdd=qdd, gravity=gravity, dtype=T)
     tau = np.zeros((q.shape[0], DOF), dtype=T)
-    for l, (p, al, acc, nj) in enumerate(links):
+    for l, nj in enumerate(joints_upstream(chain)):
         s = scales[:, l:l + 1]
-        F, N = s * acc, s * al
+        F, N = s * acc[:, l], s * al[:, l]
         for j in range(nj):
-            a, o = joints[j]
-            tau[:, j] += (np.cross(a, p - o) * F).sum(axis=1) + (a * N).sum(axis=1)
+            a, o = axes[:, j], origins[:, j]
+            tau[:, j] += (np.cross(a, p[:, l] - o) * F).sum(axis=1) + (a * N).sum(axis=1)
     assert tau.dtype == np.dtype(dtype)
     return tau
 

@@ -7,8 +7,8 @@ the joints' reaction wrenches.
   * the motor torque: the oracle's table law as world_step_ref.table_law gives it; a constraint joint's is constrain's tau.
     The inertia-scaled law's torque is formed inside the oracle's ABA and not handed out: there the stated identity is used,
     tau_motor = (the reaction's moment along the joint axis) - joint_torque + damping + friction, evaluated in float64.
-  * the reaction: a world-frame Newton-Euler sweep over the 11 URDF links (inverse_dynamics_ref._sweep: per link F = s acc,
-    N = s alpha, mass s and inertia s 1 about the link's origin) at that q̈, with the oracle's per-body contact wrenches and
+  * the reaction: a world-frame Newton-Euler sweep over the 11 URDF links (link_kinematics_ref.link_frames with q̈: per link
+    F = s acc, N = s alpha, mass s and inertia s 1 about the link's origin) at that q̈, with the oracle's per-body contact wrenches and
     external_force_ref.body_wrenches subtracted: everything distal to joint b summed, shifted to body b's origin and rotated into
     body b's frame.  A different statement of the mechanics from the kernel's body-frame recursion on six merged bodies.
 
@@ -20,6 +20,7 @@ import numpy as np
 
 import constraint_motor_ref as cref
 import external_force_ref as xref
+import ik_ref
 import inverse_dynamics_ref as idref
 import link_kinematics_ref as lk
 import world_step_ref as wref
@@ -47,21 +48,6 @@ def external_wrenches(orc, specs=(), wrenches=None):
 
 
 # ---- the Newton-Euler part, in the caller's dtype ------------------------------------------------------------------------------------
-def _body_rotations(q, T, chain):
-    """R [n, 6, 3, 3] in dtype T: the six bodies' world rotations (the chain's rpy and the joints' rotations, composed in T)"""
-    n = q.shape[0]
-    frames = {"world": np.broadcast_to(np.eye(3, dtype=T), (n, 3, 3))}
-    out, qi = [], 0
-    for j in chain:
-        R = (frames[j["parent"]] @ lk.rpy_rotation(j["rpy"]).astype(T)).astype(T)
-        if j["type"] == "revolute":
-            R = (R @ idref._axis_rotation(np.asarray(j["axis"], dtype=T), q[:, qi], T)).astype(T)
-            out.append(R)
-            qi += 1
-        frames[j["child"]] = R
-    return np.stack(out, axis=1)
-
-
 def newton_euler_reaction(q, qd, qdd, scales, gravity, fext=None, dtype=np.float64, frame="child", chain=None):
     """[n, 6, 6] in `dtype`: per joint b (Fx, Fy, Fz, Mx, My, Mz), the wrench the parent exerts on body b at body b's origin in body
     b's coordinates (frame="parent": in the parent body's, the mistake the tests tell apart).  fext [n, 6, 6]: per body n_b | f_b in
@@ -70,25 +56,26 @@ def newton_euler_reaction(q, qd, qdd, scales, gravity, fext=None, dtype=np.float
     chain = chain or lk.load_chain()
     q, qd, qdd, scales = (np.atleast_2d(np.asarray(x, dtype=T)) for x in (q, qd, qdd, scales))
     n = q.shape[0]
-    links, joints = idref._sweep(q, qd, qdd, gravity, T, chain)
-    R = _body_rotations(q, T, chain)
+    R, p, _, _, al, acc, _, origins = lk.link_frames(q, qd, chain, qdd=qdd, gravity=gravity, dtype=T)
+    upstream = idref.joints_upstream(chain)
+    R = R[:, ik_ref.revolute_links(chain)[0]]                                 # the six bodies' world rotations
     fe = None if fext is None else np.asarray(fext, dtype=T)
     out = np.zeros((n, DOF, 6), dtype=T)
     for b in range(DOF):
-        o = joints[b][1]
+        o = origins[:, b]
         F, N = np.zeros((n, 3), dtype=T), np.zeros((n, 3), dtype=T)
-        for l, (p, al, acc, nj) in enumerate(links):
+        for l, nj in enumerate(upstream):
             if nj > b:                                                # the link hangs on joint b
                 s = scales[:, l:l + 1]
-                f = s * acc
+                f = s * acc[:, l]
                 F = F + f
-                N = N + np.cross(p - o, f) + s * al
+                N = N + np.cross(p[:, l] - o, f) + s * al[:, l]
         if fe is not None:
             for c in range(b, DOF):
                 fw = np.einsum("nij,nj->ni", R[:, c], fe[:, c, 3:6])
                 nw = np.einsum("nij,nj->ni", R[:, c], fe[:, c, 0:3])
                 F = F - fw
-                N = N - nw - np.cross(joints[c][1] - o, fw)
+                N = N - nw - np.cross(origins[:, c] - o, fw)
         Rb = R[:, b] if frame == "child" else (R[:, b - 1] if b > 0 else np.broadcast_to(np.eye(3, dtype=T), (n, 3, 3)))
         out[:, b, 0:3] = np.einsum("nji,nj->ni", Rb, F)
         out[:, b, 3:6] = np.einsum("nji,nj->ni", Rb, N)

@@ -12,11 +12,12 @@ This module is the sphere's own law: the forces (`static_force`, `arm_forces`) a
 tests/world_step_ref.py's world_step(sphere=...), whose forward dynamics take the sphere's reactions in their fext slot and whose
 `storage32` rounds the sphere's and the joints' state to float32 after every sub-step: the reference's own float32-storage
 deviation is what the GPU test's sphere bars are taken from.  Built on the oracle's sample table (DynOracle.contact_samples) and
-on the URDF chain's poses and velocities (tests/link_kinematics_ref.py).  The signed-distance forms are restated here in numpy.
-It reads nothing of pioneer_amd.
+on the URDF chain's poses and velocities (tests/link_kinematics_ref.py); the static world's signed distances and normals are
+tests/contact_query_ref.py's body_distance.  It reads nothing of pioneer_amd.
 """
 import numpy as np
 
+import contact_query_ref as cq
 import external_force_ref as ext
 import link_kinematics_ref as lk
 
@@ -44,57 +45,24 @@ def from_words(w):
     return sphere(w[0:3].T, w[3:6].T, w[6], w[7])
 
 
-# ---- signed distances of points x [n, 3] to the static bodies: (sdf [n], outward unit normal [n, 3]) ----------------------------
-def _box_sdf(l, half):
-    q = np.abs(l) - half
-    o = np.maximum(q, 0.0)
-    length = np.linalg.norm(o, axis=1)
-    sign = np.where(l < 0, -1.0, 1.0)
-    outside = length > 0
-    n_out = sign * o / np.where(outside, length, 1.0)[:, None]
-    km = np.where((q[:, 0] >= q[:, 1]) & (q[:, 0] >= q[:, 2]), 0, np.where(q[:, 1] >= q[:, 2], 1, 2))
-    n_in = np.zeros_like(l)
-    rows = np.arange(len(l))
-    n_in[rows, km] = sign[rows, km]
-    return np.where(outside, length, q[rows, km]), np.where(outside[:, None], n_out, n_in)
-
-
+# ---- the static world ----------------------------------------------------------------------------------------------------------
 def static_bodies(orc):
-    """[(kind, data)] of the oracle's static world: ("plane", (normal, point)), ("box", (R, centre, half)), ("sphere", (centre, radius))"""
+    """the oracle's static world as contact_query_ref's body records: the ground, the obstacle box, then the scene's bodies"""
     d = orc.d
     out = []
     if d.ground_z == d.ground_z:
-        out.append(("plane", (np.array([0.0, 0.0, 1.0]), np.array([0.0, 0.0, d.ground_z]))))
-    half = np.array(d.obstacle_half_extents[:])
-    if np.all(half > 0):
-        out.append(("box", (np.eye(3), np.array(d.obstacle_position[:]), half)))
+        out.append(cq.plane((0.0, 0.0, 1.0), (0.0, 0.0, d.ground_z)))
+    if np.all(np.array(d.obstacle_half_extents[:]) > 0):
+        out.append(cq.box(d.obstacle_half_extents[:], d.obstacle_position[:]))
     for i in range(d.n_scene):
         b = d.scene[i]
-        quat = np.array(b.orientation[:])
-        R = lk.matrix_from_quat((quat / np.linalg.norm(quat))[None])[0]
-        pos, size = np.array(b.position[:]), np.array(b.size[:])
         if b.shape == 1:
-            out.append(("plane", (R @ size / np.linalg.norm(size), pos)))
+            out.append(cq.plane(b.size[:], b.position[:], b.orientation[:]))
         elif b.shape == 2:
-            out.append(("box", (R, pos, size)))
+            out.append(cq.box(b.size[:], b.position[:], b.orientation[:]))
         else:
-            out.append(("sphere", (pos, size[0])))
+            out.append(cq.sphere(b.size[0], b.position[:]))
     return out
-
-
-def body_sdf(kind, data, x):
-    if kind == "plane":
-        nrm, point = data
-        return (x - point) @ nrm, np.broadcast_to(nrm, x.shape)
-    if kind == "sphere":
-        centre, radius = data
-        dd = x - centre
-        length = np.linalg.norm(dd, axis=1)
-        nrm = np.where((length > 0)[:, None], dd / np.where(length > 0, length, 1.0)[:, None], np.array([0.0, 0.0, 1.0]))
-        return length - radius, nrm
-    R, centre, half = data
-    sdf, nl = _box_sdf((x - centre) @ R, half)                       # into the box's frame: R^T dd
-    return sdf, nl @ R.T
 
 
 def static_force(orc, s, p):
@@ -102,8 +70,8 @@ def static_force(orc, s, p):
     x, v = s["x"], s["v"]
     F = np.zeros_like(x)
     touching = np.zeros(len(x), dtype=bool)
-    for kind, data in static_bodies(orc):
-        sdf, nrm = body_sdf(kind, data, x)
+    for b in static_bodies(orc):
+        sdf, nrm, _ = cq.body_distance(b, b["position"], x, np.float64)
         depth = s["r"] - sdf
         vn = np.einsum("ni,ni->n", v, nrm)
         fn = p["contact_kp"] * depth - p["contact_kd"] * vn

@@ -1,8 +1,8 @@
 """Independent float64 reference of pnr_ray_test: segments against the URDF's visual shapes, the target and static bodies.
 
-Built from render_ref.scene_prims (tests/golden/urdf_visuals.json posed by link_kinematics_ref.link_frames), render_ref's slab
-helper and normal_at; it does not read the engine, its tables or pioneer_amd.  Rules (include/pioneer_amd.h, pnr_ray_test): ray r
-is from + t (to - from), t in [0, 1]; every shape is a solid (a plane: the half-space below its surface); a ray hits a solid at
+Built from render_ref.scene_prims (tests/golden/urdf_visuals.json posed by link_kinematics_ref.link_frames), render_ref's
+solid_interval (the line against a sphere, box or capped cylinder) and normal_at; it does not read the engine, its tables or
+pioneer_amd.  Rules (include/pioneer_amd.h, pnr_ray_test): ray r is from + t (to - from), t in [0, 1]; every shape is a solid (a plane: the half-space below its surface); a ray hits a solid at
 its entering parameter t_n if it starts outside it and 0 <= t_n <= 1; the smallest t_n wins, on a tie the order is arm visuals
 (table order), the target, bodies by index; a zero-length ray misses.  With parent_link >= 0 the rays are given in that URDF
 link's frame of the env.
@@ -38,44 +38,18 @@ def enabled(prims, mask):
             | ((lab >= rr.SEG_BODY0) & bool(mask & HIT_BODIES)))
 
 
-def _local(P, O, D):
-    """Origins and directions [M, 3] in the primitive's frame."""
-    return (O - P["c"][None]) @ P["R"], D @ P["R"]
-
-
 def intersect(P, O, D):
     """(tn, tf) of the lines O[m] + t D[m] against the solid P; tn > tf where the line misses it."""
-    if P["kind"] == rr.PLANE:                                        # the half-space n . (x - c) <= 0
-        on, dn = (O - P["c"][None]) @ P["n"], D @ P["n"]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t = -on / dn
-        # { t : on + t dn <= 0 }: [t0, inf) going down, (-inf, t0] going up, all or nothing along the surface
-        tn = np.where(dn < 0, t, np.where((dn > 0) | (on <= 0), -np.inf, np.inf))
-        tf = np.where(dn > 0, t, np.where((dn < 0) | (on <= 0), np.inf, -np.inf))
-        return tn, tf
-    o, dl = _local(P, O, D)
-    if P["kind"] == rr.SPHERE:
-        a = np.einsum("ij,ij->i", dl, dl)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            tc = -np.einsum("ij,ij->i", o, dl) / a
-            v = o + tc[:, None] * dl
-            disc = P["half"][0] ** 2 - np.einsum("ij,ij->i", v, v)
-            half = np.sqrt(np.maximum(disc, 0) / a)
-        ok = (a > 0) & (disc >= 0)
-        return np.where(ok, tc - half, np.inf), np.where(ok, tc + half, -np.inf)
-    if P["kind"] == rr.BOX:
-        los, his = zip(*[rr._slab(o[:, k], dl[:, k], P["half"][k]) for k in range(3)])
-        return np.max(los, axis=0), np.min(his, axis=0)
-    r, hl = P["half"][0], P["half"][2]                                # capped cylinder along local z
-    a = dl[:, 0] ** 2 + dl[:, 1] ** 2
-    par = a == 0
+    if P["kind"] != rr.PLANE:
+        return rr.solid_interval(P, O, D)
+    # pnr_ray_test's plane is the half-space n . (x - c) <= 0 below it (pnr_render's is the surface alone, render_ref.intersect):
+    # { t : on + t dn <= 0 } is [t0, inf) going down, (-inf, t0] going up, all or nothing along the surface
+    on, dn = (O - P["c"][None]) @ P["n"], D @ P["n"]
     with np.errstate(divide="ignore", invalid="ignore"):
-        tc = np.where(par, 0.0, -(o[:, 0] * dl[:, 0] + o[:, 1] * dl[:, 1]) / np.where(par, 1.0, a))
-        vx, vy = o[:, 0] + tc * dl[:, 0], o[:, 1] + tc * dl[:, 1]
-        disc = r * r - (vx * vx + vy * vy)
-        half = np.where(par, np.inf, np.sqrt(np.maximum(disc, 0) / np.where(par, 1.0, a)))
-    zlo, zhi = rr._slab(o[:, 2], dl[:, 2], hl)
-    return (np.where(disc >= 0, np.maximum(tc - half, zlo), np.inf), np.where(disc >= 0, np.minimum(tc + half, zhi), -np.inf))
+        t = -on / dn
+    tn = np.where(dn < 0, t, np.where((dn > 0) | (on <= 0), -np.inf, np.inf))
+    tf = np.where(dn > 0, t, np.where((dn < 0) | (on <= 0), np.inf, -np.inf))
+    return tn, tf
 
 
 def surface_distance(P, X):

@@ -29,13 +29,6 @@ def load_visuals(path=GOLDEN):
         return json.load(f)
 
 
-def quat_matrix(q):
-    x, y, z, w = np.asarray(q, dtype=np.float64) / np.linalg.norm(np.asarray(q, dtype=np.float64))
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-
-
 def scene_prims(q, target, target_radius=0.2, target_rgba=(1.0, 0.0, 0.0, 0.5), bodies=(), data=None):
     """Primitives of one env: dicts with kind, R (shape frame -> world), c (centre), half, rgb, label, alpha (None = opaque).
     q: the env's 6 joints; bodies: (shape, position, orientation (x, y, z, w), size, rgba) per static body."""
@@ -60,7 +53,7 @@ def scene_prims(q, target, target_radius=0.2, target_rgba=(1.0, 0.0, 0.0, 0.5), 
         prims.append(dict(kind=g["type"], R=Rw, c=c, half=half, rgb=np.asarray(rgba[:3], dtype=np.float64), label=SEG_LINK0 + k,
                           alpha=None))
     for b, (shape, pos, orn, size, rgba) in enumerate(bodies):
-        Rb = quat_matrix(orn)
+        Rb = lk.matrix_from_quat(orn)
         size = np.asarray(size, dtype=np.float64)
         if shape == PLANE:
             n = Rb @ size / np.linalg.norm(size)
@@ -87,52 +80,54 @@ def rays(view, fov, W, H, px, py):
     return eye, d_eye @ Rv
 
 
-def _slab(o, d, h):
-    """Interval of t with |o + t d| <= h (one axis, arrays)."""
+def solid_interval(P, O, D):
+    """(tn, tf) of the lines O + t D[m] (O [3] or [M, 3], D [M, 3]) against the solid P, a sphere, box or capped cylinder;
+    tn > tf where the line misses it."""
+    def slab(o, d, h):
+        """Interval of t with |o + t d| <= h (one axis)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a, b = (-h - o) / d, (h - o) / d
+        inside = np.abs(o) <= h
+        lo = np.where(d == 0, np.where(inside, -np.inf, np.inf), np.minimum(a, b))
+        hi = np.where(d == 0, np.where(inside, np.inf, -np.inf), np.maximum(a, b))
+        return lo, hi
+
+    dl = D @ P["R"]                                                    # into the solid's frame
+    o = np.broadcast_to((O - P["c"]) @ P["R"], dl.shape)
+    if P["kind"] == SPHERE:
+        a = np.einsum("ij,ij->i", dl, dl)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tc = -np.einsum("ij,ij->i", o, dl) / a
+            v = o + tc[:, None] * dl
+            disc = P["half"][0] ** 2 - np.einsum("ij,ij->i", v, v)
+            half = np.sqrt(np.maximum(disc, 0) / a)
+        ok = (a > 0) & (disc >= 0)                                     # (a = 0: a zero-length ray; a camera's rays have none)
+        return np.where(ok, tc - half, np.inf), np.where(ok, tc + half, -np.inf)
+    if P["kind"] == BOX:
+        los, his = zip(*[slab(o[:, k], dl[:, k], P["half"][k]) for k in range(3)])
+        return np.max(los, axis=0), np.min(his, axis=0)
+    r, hl = P["half"][0], P["half"][2]                                # capped cylinder along local z
+    a = dl[:, 0] ** 2 + dl[:, 1] ** 2
+    par = a == 0
     with np.errstate(divide="ignore", invalid="ignore"):
-        a, b = (-h - o) / d, (h - o) / d
-    lo, hi = np.minimum(a, b), np.maximum(a, b)
-    par = d == 0
-    inside = np.abs(o) <= h
-    lo = np.where(par, np.where(inside, -np.inf, np.inf), lo)
-    hi = np.where(par, np.where(inside, np.inf, -np.inf), hi)
-    return lo, hi
+        tc = np.where(par, 0.0, -(o[:, 0] * dl[:, 0] + o[:, 1] * dl[:, 1]) / np.where(par, 1.0, a))
+        vx, vy = o[:, 0] + tc * dl[:, 0], o[:, 1] + tc * dl[:, 1]
+        disc = r * r - (vx * vx + vy * vy)
+        half = np.where(par, np.inf, np.sqrt(np.maximum(disc, 0) / np.where(par, 1.0, a)))
+    zlo, zhi = slab(o[:, 2], dl[:, 2], hl)
+    return np.where(disc >= 0, np.maximum(tc - half, zlo), np.inf), np.where(disc >= 0, np.minimum(tc + half, zhi), -np.inf)
 
 
 def intersect(P, eye, d):
     """(tn, tf) of every ray against primitive P; tn > tf where it misses."""
-    if P["kind"] == PLANE:
-        n = P["n"]
-        dn = d @ n
-        on = (eye - P["c"]) @ n
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t = np.where(dn != 0, -on / np.where(dn != 0, dn, 1.0), np.inf)
-        return t, np.where(dn != 0, t, -np.inf)
-    o = P["R"].T @ (eye - P["c"])
-    dl = d @ P["R"]
-    if P["kind"] == SPHERE:
-        a = np.einsum("ij,ij->i", dl, dl)
-        tc = -(dl @ o) / a
-        v = o[None] + tc[:, None] * dl
-        disc = P["half"][0] ** 2 - np.einsum("ij,ij->i", v, v)
-        half = np.sqrt(np.maximum(disc, 0) / a)
-        return np.where(disc >= 0, tc - half, np.inf), np.where(disc >= 0, tc + half, -np.inf)
-    if P["kind"] == BOX:
-        los, his = zip(*[_slab(o[k], dl[:, k], P["half"][k]) for k in range(3)])
-        return np.max(los, axis=0), np.min(his, axis=0)
-    # capped cylinder along local z
-    r, hl = P["half"][0], P["half"][2]
-    a = dl[:, 0] ** 2 + dl[:, 1] ** 2
-    par = a == 0
+    if P["kind"] != PLANE:
+        return solid_interval(P, eye, d)
+    # pnr_render sees a plane as a surface, from both sides: tn = tf = t (pnr_ray_test's is the half-space below it, ray_ref.intersect)
+    dn = d @ P["n"]
+    on = (eye - P["c"]) @ P["n"]
     with np.errstate(divide="ignore", invalid="ignore"):
-        tc = np.where(par, 0.0, -(o[0] * dl[:, 0] + o[1] * dl[:, 1]) / np.where(par, 1.0, a))
-        vx, vy = o[0] + tc * dl[:, 0], o[1] + tc * dl[:, 1]
-        disc = r * r - (vx * vx + vy * vy)
-        half = np.where(par, np.inf, np.sqrt(np.maximum(disc, 0) / np.where(par, 1.0, a)))
-    zlo, zhi = _slab(o[2], dl[:, 2], hl)
-    tn = np.maximum(tc - half, zlo)
-    tf = np.minimum(tc + half, zhi)
-    return np.where(disc >= 0, tn, np.inf), np.where(disc >= 0, tf, -np.inf)
+        t = np.where(dn != 0, -on / np.where(dn != 0, dn, 1.0), np.inf)
+    return t, np.where(dn != 0, t, -np.inf)
 
 
 def normal_at(P, eye, d, t):

@@ -4,6 +4,7 @@ float64 C oracle (oracle/pnr_dyn_oracle.c), whose contact model the query restat
 import ctypes as C
 
 import numpy as np
+import pytest
 
 import contact_query_cases as cases
 import contact_query_ref as ref
@@ -53,9 +54,13 @@ def test_the_sample_table_is_the_oracles(oracle_built):
 
 
 def test_the_sweep_in_float64_is_link_frames():
+    """the two forms of the joint rotation, through the one walk: entry by entry (the float32 query's) against Rodrigues"""
     q, qd = cases.joints(50)
-    for a, b in zip(ref.frames(q.astype(np.float64), qd.astype(np.float64)), lk.link_frames(q, qd)):
-        assert np.abs(a - b).max() < 1e-12
+    for a, b in zip(lk.link_frames(q, qd, rotation=lk.coordinate_rotation), lk.link_frames(q, qd)):
+        assert a.dtype == b.dtype == np.float64 and np.abs(a - b).max() < 1e-12
+    with pytest.raises(AssertionError):                              # the entry-wise form is for +- a coordinate axis only
+        lk.coordinate_rotation((0.6, 0.8, 0.0), q[:, 0])
+    assert np.abs(lk.coordinate_rotation((0, -1, 0), q[:, 0], np.float32) - lk.axis_rotation((0, -1, 0), q[:, 0])).max() < 1e-7
 
 
 def test_forces_as_body_wrenches_equal_the_oracles(oracle_built):

@@ -294,7 +294,7 @@ def test_facade_solve_ik_pose_puts_the_pointer_on_the_target_with_the_orientatio
     env.reset_world(joint_positions=q, target_position=target)
     rec = env._vec.link_states()[0, 10].double().cpu().numpy()                   # position[3], quaternion (x, y, z, w)
     assert np.linalg.norm(rec[0:3] - np.array(target)) <= TOL + 2 * FK_TOL
-    x_axis = ref.rotation_from_quat(rec[3:7][None])[0, :, 0]
+    x_axis = ref.lk.matrix_from_quat(rec[3:7])[:, 0]
     assert np.arccos(min(1.0, x_axis[0])) <= ANGLE_TOL + ANGLE_EVAL_TOL
     # a full pose: that of known joints, asked at its position; the link's quaternion comes back (either sign)
     q_t = np.array([[0.4, 0.5, -0.3, 0.2, 0.8, -0.1]])

@@ -45,7 +45,7 @@ def test_reference_orientation_error_against_scipy():
     # quaternions: normalised by the reference, the sign does not matter, consistent with scipy (x, y, z, w)
     qt = Rb.as_quat()
     for scaled in (qt, -qt, 3.0 * qt):
-        assert np.abs(ref.rotation_from_quat(scaled) - Rb.as_matrix()).max() <= 1e-12
+        assert np.abs(ref.lk.matrix_from_quat(scaled) - Rb.as_matrix()).max() <= 1e-12
 
 
 @pytest.mark.parametrize("n", ref.SIZES + [4096])
@@ -60,7 +60,7 @@ def test_reference_converges_for_every_env_of_the_shared_sets(n):
     assert (dist <= TOL).all() and (angle <= ANGLE_TOL).all() and (its <= 8).all()
     assert (q >= lo).all() and (q <= hi).all()
     pos, quat = ref.point_set(n, ref.POINT_SEED(n))
-    assert np.abs(ref.rotation_from_quat(quat)[:, :, 0] - np.array([1.0, 0.0, 0.0])).max() <= 1e-6    # local x along world +x
+    assert np.abs(ref.lk.matrix_from_quat(quat)[:, :, 0] - np.array([1.0, 0.0, 0.0])).max() <= 1e-6    # local x along world +x
     q, dist, angle, its = ref.solve_ik_pose(pos, quat, None, mode=ref.AXIS)
     print(f"POINT n {n}: iterations {np.bincount(its)} mean {its.mean():.2f}, max distance {dist.max():.3g}, max angle {angle.max():.3g}")
     assert (dist <= TOL).all() and (angle <= ANGLE_TOL).all() and (its <= 8).all()
