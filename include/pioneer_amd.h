@@ -49,7 +49,7 @@ extern "C" {
  *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
  *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
  *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets, pnr_body_params_default,
- *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state */
+ *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state, pnr_render_bodies, pnr_set_body_queries */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -658,6 +658,26 @@ int pnr_set_body_state(pnr_handle h, const float* words, const uint8_t* mask, vo
 int pnr_get_body_state(pnr_handle h, float* out, void* stream);
 
 /*
+ * Which of the batched scene queries SEE the moving sphere: pnr_render / pnr_render_bodies, pnr_ray_test, pnr_get_contacts.
+ *   queries  PNR_BODY_IN_RENDER | PNR_BODY_IN_RAYS | PNR_BODY_IN_CONTACTS; 0, the state after pnr_create, is every query as it was
+ *            before this call existed (the sphere is invisible to all three).
+ *   rgba     4 host floats, the colour pnr_render draws the sphere in (rgb used, alpha ignored: opaque), or NULL = keep the current
+ *            colour; initially the URDF's obstacle_mat, (0.3, 0.3, 0.3, 1).
+ * A host-side switch stored in the handle: no launch, no allocation, no synchronisation; it holds for every later call on the
+ * handle.  A query whose bit is set reads the handle's body-state buffer when it runs (so it sees what pnr_world_step and
+ * pnr_set_body_state last wrote, in stream order): env k has a sphere where its mass word is > 0 (the step's own rule), centre words
+ * 0-2, velocity 3-5, radius 7.  Whether pnr_set_body_params(NULL) has disabled the sphere for the step does not matter, and the
+ * caller's joint_state combines freely with the handle's sphere.  What a set bit means is stated with each query below; in short:
+ *   render    one more opaque sphere per env, segmentation label PNR_SEG_MOVING_BODY (21), shaded and depth-tested like a body
+ *   rays      one more solid among the bodies (PNR_RAY_HIT_BODIES), label 21, after the caller's bodies on a tie
+ *   contacts  one more body, index PNR_MAX_SCENE (8), with the step's arm-sphere law on the RELATIVE velocity
+ * PNR_ERR_UNSUPPORTED: a kinematic-mode handle.  PNR_ERR_INVALID: a null handle, a call before the first pnr_set_body_params (there
+ * is no buffer), unknown bits, a non-finite colour.  A refused call changes nothing.
+ */
+enum pnr_body_query { PNR_BODY_IN_RENDER = 1, PNR_BODY_IN_RAYS = 2, PNR_BODY_IN_CONTACTS = 4 };
+int pnr_set_body_queries(pnr_handle h, uint32_t queries, const float* rgba);
+
+/*
  * getJointState for every env of a dynamics-mode handle, one launch: per revolute joint its position, velocity, ACCELERATION and
  * MOTOR TORQUE, and optionally the joint's REACTION WRENCH.  The call evaluates exactly what the FIRST SUB-STEP of
  * pnr_world_step, pnr_world_step_torques or pnr_world_step_wrenches would evaluate if called with the same arguments, and takes
@@ -726,6 +746,14 @@ int pnr_get_joint_states(pnr_handle h, const float* joint_state, const float* jo
  *   joint_torques   [num_envs][6] float32 or NULL: tau_c = sum_s J_s(q)^T F_s, F_s the sum over ALL bodies of the force above
  *                   on sample s (what the step accumulates): joint j's entry is a_j . ((pos_s - o_j) x F_s) over the samples
  *                   outboard of it.  pnr_world_step_torques with these on a contact-free handle is a step with contacts.
+ *   The moving sphere (a handle with PNR_BODY_IN_CONTACTS set, pnr_set_body_queries): in every env whose mass word is > 0 the
+ *   sphere is one more body, index PNR_MAX_SCENE (8) in points[..][7] and summary[2].  With x, v, radius the env's words and p_s,
+ *   v_s, r_s the sample's centre, velocity and radius: distance = |p_s - x| - radius - r_s (surface to surface), the normal on
+ *   the sphere towards the sample n = (p_s - x) / |p_s - x|, (0, 0, -1) at zero distance (the mirror of the step's (0, 0, 1)), and
+ *   the force max(0, kp depth - kd ((v_s - v) . n)) where depth = -distance > 0: the step's arm-sphere law, with this call's
+ *   contact_kp, contact_kd and the RELATIVE velocity.  F_s, and so joint_torques, include it.  The sphere competes for "nearest
+ *   body" with the caller's bodies and, having the highest index, loses a tie.  With n_bodies == 0 an env with a sphere reports
+ *   the sphere; an env without one reports what it reports without the bit.
  * At least one output must be non-NULL; nothing is written past num_envs rows of any output; outputs 16-byte aligned,
  * body_positions 4-byte.  An env's results do not depend on the batch around it, bit for bit.
  * PNR_ERR_INVALID, nothing launched and no output touched, for: a null handle or params, a wrong struct_size, n_bodies outside
@@ -776,12 +804,23 @@ int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_p
  * tiles of 256 to 1 024 pixels, and a call before the first pnr_reset or pnr_set_state (the target comes from the state).
  * float32 arithmetic.  Parity unpinned: Bullet's TinyRenderer / OpenGL pixels are not reproduced (no shadows, textures or
  * anti-aliasing; the shading rule above is the engine's own).
+ *
+ * pnr_render_bodies is pnr_render with a world of its own per env: body_positions, with pnr_get_contacts' layout and meaning
+ * ([num_envs][n_bodies][3] float32, 4-byte aligned, read only, or NULL): row [k][b] replaces bodies[b].position in env k;
+ * orientation, size and colour stay shared; for a plane it is the point the plane passes through; ignored when n_bodies == 0.
+ * Checks and refusals are pnr_render's (its messages name pnr_render), plus the alignment of body_positions.  With
+ * body_positions == NULL it is pnr_render, byte for byte.
+ * The moving sphere (a handle with PNR_BODY_IN_RENDER set, pnr_set_body_queries), in both calls: every env whose mass word is > 0
+ * shows one more opaque sphere of the env's radius at the env's centre, in the colour pnr_set_body_queries holds, labelled
+ * PNR_SEG_MOVING_BODY and shaded and depth-tested like a body.  Without per-env positions and without a shown sphere both calls
+ * launch the kernel pnr_render always launched.
  */
 enum pnr_seg {
     PNR_SEG_BACKGROUND = 0,
     PNR_SEG_LINK0 = 1,       /* + link_index: the URDF link of the visual (2 .. 11: robot:rotator1 .. robot:pointer) */
     PNR_SEG_TARGET = 12,
-    PNR_SEG_BODY0 = 13       /* + body index (13 .. 20) */
+    PNR_SEG_BODY0 = 13,      /* + body index (13 .. 20) */
+    PNR_SEG_MOVING_BODY = 21 /* the env's moving sphere: PNR_SEG_BODY0 + PNR_MAX_SCENE */
 };
 typedef struct pnr_render_params {
     uint32_t struct_size;              /* sizeof(pnr_render_params) */
@@ -799,6 +838,8 @@ typedef struct pnr_render_params {
 } pnr_render_params;
 int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* p, uint8_t* rgb, float* depth, uint8_t* seg,
                void* stream);
+int pnr_render_bodies(pnr_handle h, const float* joint_state, const pnr_render_params* p, const float* body_positions, uint8_t* rgb,
+                      float* depth, uint8_t* seg, void* stream);
 
 /*
  * rayTest / rayTestBatch for every env, one launch: n_rays segments per env against that env's solids.
@@ -819,12 +860,16 @@ int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* 
  *   starts inside a solid does not hit that solid (Bullet's rule for convex shapes; it makes a sensor inside the pointer's
  *   sphere usable).  The smallest t_n over the enabled solids wins; on a tie the order is arm visuals in table order, then the
  *   target, then bodies by index.  A zero-length ray misses.
+ *   The moving sphere (a handle with PNR_BODY_IN_RAYS set, pnr_set_body_queries): where hit_mask has PNR_RAY_HIT_BODIES, every env
+ *   whose mass word is > 0 has one more solid, a sphere of the env's radius at the env's centre, under the same rule (the
+ *   entering parameter counts; a ray that starts inside does not hit it), label PNR_SEG_MOVING_BODY (21), after the caller's
+ *   bodies on a tie.  hit_mask keeps its three bits.
  *   Outputs (at least one non-NULL, each 16-byte aligned; nothing past the last row is written):
  *     hits      [num_envs][n_rays][PNR_RAY_DIM] float32:
  *                 [0]   hit fraction t_n; 1 on a miss (PyBullet's convention)
  *                 [1:4] world hit position; `to` in the world frame on a miss
  *                 [4:7] unit outward world normal; 0 on a miss
- *                 [7]   the enum pnr_seg label as a float: 0 miss, 1 + link, 12 the target, 13 + body
+ *                 [7]   the enum pnr_seg label as a float: 0 miss, 1 + link, 12 the target, 13 + body, 21 the moving sphere
  *     fractions [num_envs][n_rays] float32: [0] alone (the tensor that goes into an observation)
  * PNR_ERR_INVALID, nothing launched and no output touched, for: a null handle or params, a wrong struct_size, n_rays outside
  * 1..PNR_MAX_RAYS, parent_link outside -1..10, n_bodies outside 0..PNR_MAX_SCENE, a hit_mask that is 0 or has unknown bits,

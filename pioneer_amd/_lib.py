@@ -82,8 +82,11 @@ class PnrSceneBody(C.Structure):
                 ("size", C.c_double * 3)]
 
 
-# pnr_render's segmentation labels (enum pnr_seg): background, 1 + URDF link index, the target, 13 + static body index
+# pnr_render's segmentation labels (enum pnr_seg): background, 1 + URDF link index, the target, 13 + static body index, the moving sphere
 SEG_BACKGROUND, SEG_LINK0, SEG_TARGET, SEG_BODY0 = 0, 1, 12, 13
+SEG_MOVING_BODY = SEG_BODY0 + MAX_SCENE      # 21; pnr_get_contacts reports the sphere as body MAX_SCENE
+# pnr_set_body_queries' bits (enum pnr_body_query): which scene queries see the moving sphere
+BODY_IN_RENDER, BODY_IN_RAYS, BODY_IN_CONTACTS = 1, 2, 4
 
 
 class PnrRenderParams(C.Structure):
@@ -216,6 +219,7 @@ SIGNATURES = {
     "pnr_set_body_params": (C.c_int, [_VP, C.POINTER(PnrBodyParams)]),
     "pnr_set_body_state": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_get_body_state": (C.c_int, [_VP, _VP, _VP]),
+    "pnr_set_body_queries": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_float * 4)]),
     "pnr_get_link_states": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_get_jacobian": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_double * 3), _VP, _VP]),
     "pnr_inverse_dynamics": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP]),
@@ -226,6 +230,7 @@ SIGNATURES = {
     "pnr_ik_pose_params_default": (C.c_int, [C.POINTER(PnrIkPoseParams)]),
     "pnr_solve_ik_pose": (C.c_int, [_VP, C.POINTER(PnrIkPoseParams)] + [_VP] * 8),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
+    "pnr_render_bodies": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_contact_params_default": (C.c_int, [C.POINTER(PnrContactParams)]),
     "pnr_get_contacts": (C.c_int, [_VP, _VP, C.POINTER(PnrContactParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_ray_params_default": (C.c_int, [C.POINTER(PnrRayParams)]),
@@ -263,7 +268,7 @@ _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr
 UNITS = {
     # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (121, 92 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
-    # the query entry points of the C ABI and their kernels (35)
+    # the query entry points of the C ABI and their kernels (44: the three scene queries have a per-env-world form each, pnr_query.h)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",
                         "pnr_jointstate.h", "pnr_contacts.h", "pnr_rays.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",

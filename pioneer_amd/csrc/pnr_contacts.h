@@ -14,6 +14,9 @@
 // argument (scalar loads).  Each output is a wave-uniform branch on its pointer.  The records go to a dense LDS tile of
 // [64][207] floats (52 992 B); summary and joint_torques are 16 + 24 B per lane and go out as plain per-lane stores.  No
 // cross-lane arithmetic: an env's results do not depend on the batch around it.
+//
+// The scene form (contacts_kernel<SRC | kQueryScene>, pnr_query.h; a handle whose moving sphere the query reports): the lane loads
+// its env's eight sphere words once, and every sample meets the sphere after the body loop, as body kMaxScene.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -89,10 +92,16 @@ __device__ __forceinline__ void contact_frame_outward(const ContactFrame& B, flo
 // per-env running summary: smallest distance, its sample and body, number of penetrating samples
 struct ContactSummary { float dist, sample, body, count; };
 
+// The scene form's argument: ContactArgs first (contact_body_words), then the handle's moving-sphere words
+struct ContactSceneArgs : ContactArgs { const float* sphere; };   // [PNR_BODY_STATE_WORDS][n] (pnr_dyn.h WorldBody::words)
+
 // One sample sphere (centre c in the frame B, radius) against every body: its record into rec (9 floats of this lane's LDS
 // row, or null), the summary, and F = the sum over ALL bodies of the penalty force on it; pos = its centre in the world.
+// SPHERE: after the caller's bodies the env's moving sphere sp (mass <= 0: none), as body kMaxScene: the step's arm-sphere pair
+// (pnr_dyn.h sample_contact) seen from the sample, with the relative velocity in the law; it loses a tie to a caller's body.
+template <bool SPHERE>
 __device__ __forceinline__ void contact_sample(const ContactArgs& A, ContactBodyWords bw, const float* __restrict__ bp, const ContactFrame& B, V3 c,
-                                               float radius, int s, float* rec, ContactSummary& sm, V3& pos, V3& F)
+                                               float radius, int s, float* rec, ContactSummary& sm, V3& pos, V3& F, const SphereLane& sp)
 {
     const V3 rel = mul(B.R, c);
     pos = B.p + rel;
@@ -118,6 +127,23 @@ __device__ __forceinline__ void contact_sample(const ContactArgs& A, ContactBody
         F = F + f * nrm;
         if (-depth < best) { best = -depth; bestn = nrm; bestb = (float)b; bestf = f; }
     }
+    if constexpr (SPHERE) {
+        // body_distance's sphere, asked from the sample's side: the unit vector towards the sphere's centre, (0, 0, 1) at zero
+        // distance, is the step's n; the normal on the sphere towards the sample is its mirror
+        SceneBody S = SceneBody{};
+        S.shape = 3;
+        S.size[0] = sp.r;
+        float sdf;
+        V3 towards;
+        body_distance(S, pos, sp.x, sdf, towards);
+        const V3 nrm = -1.f * towards;
+        const float depth = radius - sdf;                  // surface to surface: radius + r - |x - pos|
+        const bool there = sp.m > 0.f;
+        float fn;
+        const float f = (penalty(A.ckp, A.ckd, depth, dot(vel - sp.v, nrm), fn) && there) ? fn : 0.f;
+        F = F + f * nrm;
+        if (there && -depth < best) { best = -depth; bestn = nrm; bestb = (float)kMaxScene; bestf = f; }
+    }
     if (rec) {
         const V3 on = pos - radius * bestn;
         rec[0] = best;
@@ -131,8 +157,9 @@ __device__ __forceinline__ void contact_sample(const ContactArgs& A, ContactBody
 }
 
 // one env: the 23 records into `row` (207 floats, or null), the summary, tau_j = sum_s a_j . ((pos_s - o_j) x F_s)
+template <bool SPHERE>
 __device__ __forceinline__ void contacts_env(const ContactArgs& A, const float* __restrict__ bp, const float (&q)[kDof],
-                                             const float (&qd)[kDof], float* row, ContactSummary& sm, float (&tau)[kDof])
+                                             const float (&qd)[kDof], float* row, ContactSummary& sm, float (&tau)[kDof], const SphereLane& sp)
 {
     const bool want_tau = A.torques != nullptr;
     const ContactBodyWords bw = contact_body_words();
@@ -151,7 +178,7 @@ __device__ __forceinline__ void contacts_env(const ContactArgs& A, const float* 
         for_body_samples<J>([&](auto s_, V3 cen, float radius, auto) {
             constexpr int s = decltype(s_)::value;
             V3 pos, F;
-            contact_sample(A, bw, bp, b, cen, radius < 0.f ? A.ptr_radius : radius, s, row ? row + kContactDim * s : nullptr, sm, pos, F);
+            contact_sample<SPHERE>(A, bw, bp, b, cen, radius < 0.f ? A.ptr_radius : radius, s, row ? row + kContactDim * s : nullptr, sm, pos, F, sp);
             if (want_tau) {
                 static_for<J + 1>([&](auto k_) {                        // the joints between the base and this body
                     constexpr int k = decltype(k_)::value;
@@ -163,17 +190,26 @@ __device__ __forceinline__ void contacts_env(const ContactArgs& A, const float* 
 }
 
 template <int SRC>
-__global__ __launch_bounds__(kWave) void contacts_kernel(const ContactArgs A)
+__global__ __launch_bounds__(kWave) void contacts_kernel(const QueryArgs<SRC, ContactArgs, ContactSceneArgs> A)
 {
+    constexpr bool SCENE = (SRC & kQueryScene) != 0;
     __shared__ __attribute__((aligned(16))) float tile[kContactTileFloats];
     const EnvLane L = env_lane(A.n);
     float q[kDof], qd[kDof];
-    load_lane_joints<SRC>(A.src, A.state, A.n, L, q, qd);
+    load_lane_joints<(SRC & kJointSrcMask)>(A.src, A.state, A.n, L, q, qd);
     // a lane past the batch computes on the last env's body positions and stores nothing
     const float* bp = A.body_pos ? A.body_pos + (L.live ? L.e : A.n - 1) * (3 * A.n_bodies) : nullptr;
     ContactSummary sm;
     float tau[kDof];
-    contacts_env(A, bp, q, qd, A.points ? tile + L.lane * kContactRowFloats : nullptr, sm, tau);
+    SphereLane sp = {};                                 // (a lane past the batch: mass 0, no sphere)
+    if constexpr (SCENE) {
+        if (L.live) {                                   // the env's eight words, once per env
+            const float* w = A.sphere + L.e;
+            sp.x = {w[0], w[A.n], w[2 * A.n]}; sp.v = {w[3 * A.n], w[4 * A.n], w[5 * A.n]};
+            sp.m = w[6 * A.n]; sp.r = w[7 * A.n];
+        }
+    }
+    contacts_env<SCENE>(A, bp, q, qd, A.points ? tile + L.lane * kContactRowFloats : nullptr, sm, tau, sp);
     if (L.live) {
         if (A.summary) reinterpret_cast<float4*>(A.summary)[L.e] = make_float4(sm.dist, sm.sample, sm.body, sm.count);
         if (A.torques) {

@@ -30,6 +30,9 @@ struct pnr_env_s {
     pnr::SceneBody* scene;    // dynamics-mode static scene bodies [kMaxScene] or null
     pnr::WorldBody sphere;    // pnr_set_body_params: the moving sphere's buffer (words; null before the first call) and resolved params
     bool sphere_on;           // .. and whether the world step moves it (the kWorldBody forms)
+    unsigned body_queries;    // pnr_set_body_queries: which scene queries see the sphere (0: none), a host-side switch
+    bool body_rgb_set;        // .. and its drawn colour, once the caller gave one (else the obstacle material's grey)
+    float body_rgb[3];
     int diag;            // -DPNR_DIAG_BUILD=1 variant only: the PNR_DIAG environment variable at create time; else 0
     bool ready;          // a full reset has happened, or the state was set explicitly
     bool kin_set, dyn_set;  // pnr_set_state / pnr_set_dyn_state seen (both needed in dynamics mode)

@@ -80,7 +80,27 @@ static inline bool has_link_scales(pnr_handle h) { return h->ready || h->dyn_set
 static inline bool has_own_target(pnr_handle h) { return h->ready || h->kin_set; }                 // pnr_solve_ik, pnr_render
 static int before_first_reset(pnr_handle h, const char* call, const char* why = "") { return fail(h, PNR_ERR_INVALID, "%s before the first pnr_reset (or pnr_set_state)%s", call, why); }
 
+// the handle's moving-sphere words where the query `bit` (pnr_set_body_queries) sees the sphere, else null
+static inline const float* shown_sphere(pnr_handle h, unsigned bit) { return (h->body_queries & bit) ? h->sphere.words : nullptr; }
+
 extern "C" {
+
+int pnr_set_body_queries(pnr_handle h, uint32_t queries, const float* rgba)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (h->cfg.mode != PNR_MODE_DYNAMIC)
+        return fail(h, PNR_ERR_UNSUPPORTED, "pnr_set_body_queries: the moving sphere exists in dynamics mode only");
+    if (!h->sphere.words) return fail(h, PNR_ERR_INVALID, "pnr_set_body_queries before pnr_set_body_params (the handle has no sphere buffer)");
+    if (queries & ~(uint32_t)(PNR_BODY_IN_RENDER | PNR_BODY_IN_RAYS | PNR_BODY_IN_CONTACTS))
+        return fail(h, PNR_ERR_INVALID, "pnr_set_body_queries: unknown bits in 0x%x", (unsigned)queries);
+    if (rgba && !finite_all(rgba, 4)) return fail(h, PNR_ERR_INVALID, "pnr_set_body_queries: non-finite colour");
+    h->body_queries = queries;
+    if (rgba) {
+        for (int k = 0; k < 3; ++k) h->body_rgb[k] = rgba[k];
+        h->body_rgb_set = true;
+    }
+    return PNR_OK;
+}
 
 int pnr_get_link_states(pnr_handle h, const float* joint_state, float* out, void* stream)
 {
@@ -329,6 +349,12 @@ int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_p
     A.ckp = (float)p->contact_kp; A.ckd = (float)p->contact_kd; A.ptr_radius = (float)h->cfg.pointer_radius;
     A.n_bodies = p->n_bodies;
     for (int b = 0; b < p->n_bodies; ++b) A.bodies[b] = scene_body_device(p->bodies[b]);
+    if (const float* sphere = shown_sphere(h, PNR_BODY_IN_CONTACTS)) {
+        ContactSceneArgs X;
+        static_cast<ContactArgs&>(X) = A;
+        X.sphere = sphere;
+        return launch_env_waves(h, stream, J.kind, [](auto S) { return contacts_kernel<S() | kQueryScene>; }, X);
+    }
     return launch_env_waves(h, stream, J.kind, [](auto S) { return contacts_kernel<S()>; }, A);
 }
 
@@ -417,15 +443,19 @@ static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& 
     return PNR_OK;
 }
 
-extern "C" {
+// the moving sphere's colour where the caller never set one: the URDF's obstacle_mat (render.OBSTACLE_RGBA)
+static const float kObstacleRgb[3] = {0.3f, 0.3f, 0.3f};
 
-int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* p, uint8_t* rgb, float* depth, uint8_t* seg,
-               void* stream)
+// pnr_render and pnr_render_bodies: render_kernel where every env sees the caller's bodies where they are and no moving sphere
+// (what pnr_render always launched), else its scene form
+static int render_call(pnr_handle h, const float* joint_state, const pnr_render_params* p, const float* body_positions, uint8_t* rgb,
+                       float* depth, uint8_t* seg, void* stream)
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!p) return fail(h, PNR_ERR_INVALID, "pnr_render: null params");
     if (!rgb && !depth && !seg) return fail(h, PNR_ERR_INVALID, "pnr_render: every output is NULL");
-    if (const int rc = check_aligned(h, "pnr_render", {{rgb, "rgb", 16}, {depth, "depth", 16}, {seg, "seg", 16}, {joint_state, "joint_state", 16}})) return rc;
+    if (const int rc = check_aligned(h, "pnr_render", {{rgb, "rgb", 16}, {depth, "depth", 16}, {seg, "seg", 16}, {joint_state, "joint_state", 16},
+                                                        {body_positions, "body_positions", 4}})) return rc;
     if (!has_own_target(h)) return before_first_reset(h, "pnr_render", ": the target comes from the state");
     RenderParams P;
     const int rc = render_setup(h, p, P);
@@ -434,11 +464,33 @@ int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* 
     const dim3 grid((unsigned)(h->n * P.tiles)), block(kRenderThreads);
     hipStream_t st = (hipStream_t)stream;
     const JointSource J = joint_source(h, joint_state);       // (the kernel reads the target from h->state whatever the source)
+    RenderSceneParams X;
+    static_cast<RenderParams&>(X) = P;
+    X.body_pos = p->n_bodies > 0 ? body_positions : nullptr;
+    X.sphere = shown_sphere(h, PNR_BODY_IN_RENDER);
+    for (int k = 0; k < 3; ++k) X.sphere_rgb[k] = h->body_rgb_set ? h->body_rgb[k] : kObstacleRgb[k];
     with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(J.kind, [&](auto S) {
-        hipLaunchKernelGGL(render_kernel<S()>, grid, block, 0, st, J.src, h->state, (long long)h->n, P, rgb, depth, seg);
+        if (X.body_pos || X.sphere)
+            hipLaunchKernelGGL(render_kernel<S() | kQueryScene>, grid, block, 0, st, J.src, h->state, (long long)h->n, X, rgb, depth, seg);
+        else
+            hipLaunchKernelGGL(render_kernel<S()>, grid, block, 0, st, J.src, h->state, (long long)h->n, P, rgb, depth, seg);
     });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
+}
+
+extern "C" {
+
+int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* p, uint8_t* rgb, float* depth, uint8_t* seg,
+               void* stream)
+{
+    return render_call(h, joint_state, p, nullptr, rgb, depth, seg, stream);
+}
+
+int pnr_render_bodies(pnr_handle h, const float* joint_state, const pnr_render_params* p, const float* body_positions, uint8_t* rgb,
+                      float* depth, uint8_t* seg, void* stream)
+{
+    return render_call(h, joint_state, p, body_positions, rgb, depth, seg, stream);
 }
 
 }  // extern "C"
@@ -514,9 +566,15 @@ int pnr_ray_test(pnr_handle h, const float* joint_state, const pnr_ray_params* p
     if (groups > 0x7fffffffLL) return fail(h, PNR_ERR_INVALID, "pnr_ray_test: %lld envs x %d rays exceed one launch", h->n, p->n_rays);
     DeviceGuard g(h->device);
     const dim3 grid((unsigned)groups), block((unsigned)((span + kWave - 1) / kWave * kWave));
-    const size_t lds = sizeof(float) * (size_t)ray_lds_words(A.max_envs);
+    // the moving sphere is one of the bodies: seen with the bodies bit of the mask
+    const float* sphere = (p->hit_mask & PNR_RAY_HIT_BODIES) ? shown_sphere(h, PNR_BODY_IN_RAYS) : nullptr;
+    const size_t lds = sizeof(float) * (size_t)(sphere ? ray_scene_lds_words(A.max_envs) : ray_lds_words(A.max_envs));
+    RaySceneArgs X;
+    static_cast<RayArgs&>(X) = A;
+    X.sphere = sphere;
     with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(J.kind, [&](auto S) {
-        hipLaunchKernelGGL(ray_kernel<S()>, grid, block, lds, (hipStream_t)stream, A);
+        if (sphere) hipLaunchKernelGGL(ray_kernel<S() | kQueryScene>, grid, block, lds, (hipStream_t)stream, X);
+        else hipLaunchKernelGGL(ray_kernel<S()>, grid, block, lds, (hipStream_t)stream, A);
     });
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;

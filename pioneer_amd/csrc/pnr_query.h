@@ -33,6 +33,15 @@ enum : int {
     kJointSrcKin = 2,      // kinematic-mode state records (load_env_halves, pnr_device.h): q = r (words 12-17), qd = v (6-11)
 };
 
+// The scene queries (pnr_render.h, pnr_rays.h, pnr_contacts.h) have a second form each, for a per-env world: the handle's moving
+// sphere and, in the renderer, per-env body positions.  It is the same kernel template at SRC | kQueryScene, so that the forms
+// every earlier call launches keep their names (<0>, <1>, <2>) and, their `if constexpr`s being false, their code; the scene
+// form's argument struct is the plain one with the per-env world appended (QueryArgs), so the plain forms keep their argument too.
+constexpr int kQueryScene = 4;
+constexpr int kJointSrcMask = 3;
+template <int SRC, class Plain, class Scene>
+using QueryArgs = std::conditional_t<(SRC & kQueryScene) != 0, Scene, Plain>;
+
 // env e's joints from the source SRC
 template <int SRC>
 __device__ __forceinline__ void load_joints(const float* __restrict__ src, const float4* __restrict__ state, const long long n,

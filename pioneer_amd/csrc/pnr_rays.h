@@ -22,6 +22,9 @@
 // selected branch-free, one hit_normal_at from the winner.  No cross-lane arithmetic: an env's results do not depend on the
 // batch around it.  hits leaves as two 16-byte non-temporal stores per lane (a lane's row is 32 contiguous bytes, a wave's 2 KB:
 // staging through LDS would add a barrier and 8 KB of LDS for the same bytes), fractions as one coalesced dword store.
+//
+// The scene form (ray_kernel<SRC | kQueryScene>, pnr_query.h; a handle whose moving sphere the rays see): one more record per
+// staged env, built from the sphere's words, tested after the caller's bodies.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -116,9 +119,16 @@ __device__ __forceinline__ void ray_against(const RayPrim& Q, V3 c, int shape, i
     }
 }
 
+// The scene form's argument and dynamic LDS: one more record per staged env, behind the poses
+struct RaySceneArgs : RayArgs { const float* sphere; };          // [PNR_BODY_STATE_WORDS][n] (pnr_dyn.h WorldBody::words)
+__host__ __device__ constexpr int ray_scene_lds_words(int E) { return ray_lds_words(E) + E * kRayPrimWords; }
+static_assert(ray_scene_lds_words(kRayMaxEnvs) * 4 <= 48 * 1024, "three workgroups fit a CU's 160 KB of LDS");
+constexpr int kRayIdxSphere = kRayEnvPrims + kMaxScene;           // the moving sphere's place in the tie order: after the bodies
+
 template <int SRC>
-__global__ __launch_bounds__(kRayThreads) void ray_kernel(const RayArgs A)
+__global__ __launch_bounds__(kRayThreads) void ray_kernel(const QueryArgs<SRC, RayArgs, RaySceneArgs> A)
 {
+    constexpr bool SCENE = (SRC & kQueryScene) != 0;
     extern __shared__ __attribute__((aligned(16))) float ray_lds[];
     RayPrim* const bodies = reinterpret_cast<RayPrim*>(ray_lds);                        // [kMaxScene], shared by the envs
     RayPrim* const recs = bodies + kMaxScene;                                           // [max_envs][kRayEnvPrims]
@@ -138,7 +148,7 @@ __global__ __launch_bounds__(kRayThreads) void ray_kernel(const RayArgs A)
     if (arm || A.parent_body >= 0) {
         if (tid < nenv) {
             float q[kDof], qd[kDof];
-            load_joints<SRC>(A.src, A.state, A.n, e0 + tid, q, qd);
+            load_joints<(SRC & kJointSrcMask)>(A.src, A.state, A.n, e0 + tid, q, qd);
             LinkBody b = link_base();
             static_for<kDof>([&](auto jc) {
                 constexpr int J = decltype(jc)::value;
@@ -193,6 +203,19 @@ __global__ __launch_bounds__(kRayThreads) void ray_kernel(const RayArgs A)
             }
         }
     }
+    if constexpr (SCENE) {
+        // the env's moving sphere (words 0-2 centre, 6 mass, 7 radius), label kSegMovingBody; an env without one (mass <= 0) gets a
+        // negative bound2: no segment comes that close, so every ray's early-out skips it
+        RayPrim* const spheres = reinterpret_cast<RayPrim*>(poses + A.max_envs * (12 * kDof));   // [max_envs]
+        for (int slot = tid; slot < nenv; slot += nthreads) {
+            const float* w = A.sphere + (e0 + slot);
+            const float m = w[6 * A.n], r = w[7 * A.n];
+            const float half[3] = {r, r, r};
+            RayPrim& Q = spheres[slot];
+            put_ray_prim(Q, diag3(1.f), V3{w[0], w[A.n], w[2 * A.n]}, kVisSphere, half, r, kSegMovingBody);
+            if (!(m > 0.f)) Q.bound2 = -1.f;
+        }
+    }
     __syncthreads();
 
     // ---- per ray ----
@@ -231,12 +254,18 @@ __global__ __launch_bounds__(kRayThreads) void ray_kernel(const RayArgs A)
         ray_against(Q, V3{cen[3 * b], cen[3 * b + 1], cen[3 * b + 2]}, __builtin_amdgcn_readfirstlane(Q.shape), kRayEnvPrims + b, from, d,
                     inv_dd, best);
     }
+    const RayPrim* sphere_rec = nullptr;
+    if constexpr (SCENE) {
+        sphere_rec = reinterpret_cast<const RayPrim*>(poses + A.max_envs * (12 * kDof)) + slot;
+        ray_against(*sphere_rec, V3{sphere_rec->c[0], sphere_rec->c[1], sphere_rec->c[2]}, kVisSphere, kRayIdxSphere, from, d, inv_dd, best);
+    }
     const bool hit = best.idx >= 0 && dd > 0.f;                       // a zero-length ray misses
     float frac = 1.f, label = 0.f;
     V3 pos = to, nrm = {0.f, 0.f, 0.f};
     if (hit) {
-        const bool own = best.idx < kRayEnvPrims;
-        const RayPrim& Q = own ? mine[best.idx] : bodies[best.idx - kRayEnvPrims];
+        const bool sph = SCENE && best.idx == kRayIdxSphere;
+        const bool own = best.idx < kRayEnvPrims || sph;               // a record that carries its own centre
+        const RayPrim& Q = sph ? *sphere_rec : own ? mine[best.idx] : bodies[best.idx - kRayEnvPrims];
         const int b = own ? 0 : best.idx - kRayEnvPrims;
         const V3 c = own ? V3{Q.c[0], Q.c[1], Q.c[2]} : V3{cen[3 * b], cen[3 * b + 1], cen[3 * b + 2]};
         const V3 w = from - c;

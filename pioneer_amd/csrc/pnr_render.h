@@ -14,6 +14,10 @@
 // skipped where the primitive's rectangle misses the wave's 64 pixels (a scalar branch), a branch-free nearest hit, one shading
 // from the winner's record.  The tile's bytes are staged in LDS and leave as lane-linear 16-byte non-temporal stores; only the
 // partial 16-byte chunks at a span's two ends are written byte by byte.
+//
+// The scene form (render_kernel<SRC | kQueryScene>, pnr_query.h; pnr_render_bodies, and pnr_render where the handle shows its moving
+// sphere): each body's lane re-places the host's record at the env's own position, and one more lane builds the env's moving
+// sphere as one more primitive in one more slot.  The per-pixel loop is the same text.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,7 +32,7 @@
 namespace pnr {
 
 enum : int { kVisBox = 0, kVisCylinder = 1, kVisSphere = 2, kVisPlane = 3 };
-enum : int { kSegBackground = 0, kSegLink0 = 1, kSegTarget = 12, kSegBody0 = 13 };
+enum : int { kSegBackground = 0, kSegLink0 = 1, kSegTarget = 12, kSegBody0 = 13, kSegMovingBody = kSegBody0 + kMaxScene };
 
 // One <visual> of the URDF (pioneer_knm_6dof.urdf:36-202), in the frame of moving body `body` (pnr_model.h: kLinkBody of its
 // link; every fixed joint is the identity except effector_to_pointer, so the pointer's sphere sits at kTip).  rot: visual
@@ -241,12 +245,20 @@ __device__ __forceinline__ void flush_span(const uint8_t* __restrict__ lds, uint
     }
 }
 
+// The scene form's argument: RenderParams (render_kernel<0..2>'s as it was) and the per-env world, either pointer may be null.
+struct RenderSceneParams : RenderParams {
+    const float* body_pos;     // [n][n_static][3] world positions that replace the bodies', or null
+    const float* sphere;       // [PNR_BODY_STATE_WORDS][n] (pnr_dyn.h WorldBody::words) where the sphere is drawn, or null
+    float sphere_rgb[3];
+};
+
 template <int SRC>
 __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __restrict__ src, const float4* __restrict__ state,
-                                                                const long long n, const RenderParams P, uint8_t* __restrict__ rgb,
-                                                                float* __restrict__ depth, uint8_t* __restrict__ seg)
+                                                                const long long n, const QueryArgs<SRC, RenderParams, RenderSceneParams> P,
+                                                                uint8_t* __restrict__ rgb, float* __restrict__ depth, uint8_t* __restrict__ seg)
 {
-    __shared__ RenderPrim prims[kRenderPrims];
+    constexpr bool SCENE = (SRC & kQueryScene) != 0;
+    __shared__ RenderPrim prims[kRenderPrims + (SCENE ? 1 : 0)];    // (the scene form: one more slot, the moving sphere's)
     __shared__ float pose[kDof][12];                                  // R (rows), p of the six moving bodies
     __shared__ __attribute__((aligned(16))) uint8_t st_rgb[16 + 3 * kRenderMaxTile];
     __shared__ __attribute__((aligned(16))) uint8_t st_seg[16 + kRenderMaxTile];
@@ -262,7 +274,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
     // ---- prologue: body poses (wave 0), then one record per primitive ----
     if (tid < kWave) {
         float q[kDof], qd[kDof];
-        load_joints<SRC>(src, state, n, e, q, qd);
+        load_joints<(SRC & kJointSrcMask)>(src, state, n, e, q, qd);
         LinkBody b = link_base();
         static_for<kDof>([&](auto jc) {
             constexpr int J = decltype(jc)::value;
@@ -277,7 +289,33 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
         });
     }
     __syncthreads();
-    const int nprim = 1 + kNumVisuals + P.n_static;
+    int nprim = 1 + kNumVisuals + P.n_static;
+    if constexpr (SCENE) {
+        if (tid > kNumVisuals && tid < nprim) {                      // a static body: the host's record, re-placed at the env's position
+            RenderPrim& Q = prims[tid];
+            Q = P.bodies[tid - 1 - kNumVisuals];
+            if (P.body_pos) {
+                const float* bp = P.body_pos + (e * P.n_static + (tid - 1 - kNumVisuals)) * 3;
+                const V3 c = {bp[0], bp[1], bp[2]};
+                if (Q.shape == kVisPlane) {                          // the host's form: o[2] = n . (eye - point), the whole screen
+                    Q.o[2] = dot(V3{Q.rt[6], Q.rt[7], Q.rt[8]}, V3{P.eye[0], P.eye[1], P.eye[2]} - c);
+                } else {
+                    const M3 R = {{Q.rt[0], Q.rt[3], Q.rt[6]}, {Q.rt[1], Q.rt[4], Q.rt[7]}, {Q.rt[2], Q.rt[5], Q.rt[8]}};   // (rt is R^T)
+                    const float half[3] = {Q.h[0], Q.h[1], Q.h[2]}, colour[3] = {Q.rgb[0], Q.rgb[1], Q.rgb[2]};
+                    const float bound = Q.shape == kVisBox ? sqrtf(half[0] * half[0] + half[1] * half[1] + half[2] * half[2]) : half[0];
+                    put_prim(Q, P, R, c, Q.shape, half, bound, colour, Q.label);
+                }
+            }
+        } else if (tid == nprim && P.sphere) {                       // the env's moving sphere (words 0-2 centre, 6 mass, 7 radius)
+            const float* w = P.sphere + e;
+            const float m = w[6 * n], r = w[7 * n];
+            const float half[3] = {r, r, r};
+            RenderPrim& Q = prims[tid];
+            put_prim(Q, P, diag3(1.f), V3{w[0], w[n], w[2 * n]}, kVisSphere, half, r, P.sphere_rgb, kSegMovingBody);
+            if (!(m > 0.f)) { Q.x0 = 0x7fffffff; Q.x1 = -1; Q.y0 = 0x7fffffff; Q.y1 = -1; }      // no sphere: a rectangle no wave meets
+        }
+        nprim += P.sphere ? 1 : 0;
+    }
     if (tid == 0) {                                                  // the target (state words 18-20)
         const float4 w = state_cold(state, n)[e];
         const float half[3] = {P.target_radius, P.target_radius, P.target_radius};
@@ -293,7 +331,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
         const float bound = sqrtf(D.half[0] * D.half[0] + D.half[1] * D.half[1] + D.half[2] * D.half[2]);
         put_prim(prims[tid], P, R, c, D.shape, D.half, D.shape == kVisBox ? bound : (D.shape == kVisSphere ? D.half[0] :
                  sqrtf(D.half[0] * D.half[0] + D.half[2] * D.half[2])), D.rgba, kSegLink0 + D.link);
-    } else if (tid < nprim) {
+    } else if (!SCENE && tid < nprim) {
         prims[tid] = P.bodies[tid - 1 - kNumVisuals];
     }
     __syncthreads();

@@ -97,6 +97,8 @@ class PioneerKinematicEnv(compat.GymEnv):
             if old._body_on:                                               # the moving sphere: its params and its state
                 self._vec.set_body(old._body_params)
                 self._vec.set_body_state(old.body_state())
+                if old._body_queries is not None:                          # .. and which queries see it
+                    self._vec.set_body_queries(**old._body_queries)
         old.close()
 
     # -- pickling: by constructor arguments, like gym.utils.EzPickle (pioneer_knm_env.py:38, :51) --

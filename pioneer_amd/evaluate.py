@@ -37,7 +37,8 @@ def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, g
     reset) — what tells "did not reach" from "could not reach".  When the env has at least one collision body
     (PioneerVectorEnv.collision_bodies: the engine_config's ground_z, obstacle box or scene) the result also holds collision_steps,
     the share of the evaluated steps with any penetrating contact sample, and min_clearance, the smallest sample-to-body distance
-    seen (one PioneerVectorEnv.contacts launch per step); without a body the result is unchanged."""
+    seen (one PioneerVectorEnv.contacts launch per step; a moving sphere that ``contacts`` reports counts as a body); without a body
+    the result is unchanged."""
     device = torch.device(device)
     model, filt, cfg = load_policy(checkpoint, device)
     env = TimeLimit(PioneerKinematicEnv(device=device, mode=mode, engine_config=engine_config), max_episode_steps=max_episode_steps)
@@ -47,7 +48,7 @@ def evaluate(checkpoint: str, episodes: int = 3, max_episode_steps: int = 500, g
     gen = torch.Generator(device=device).manual_seed(0 if seed is None else seed)
     frames: List[np.ndarray] = []
     rewards, lengths, successes, reachable = [], [], [], []
-    has_bodies = len(env.env._vec.collision_bodies()) > 0
+    has_bodies = len(env.env._vec.collision_bodies()) > 0 or bool((env.env._vec._body_queries or {}).get("contacts"))   # (a moving sphere the query reports)
     touching, clearance = 0, float("inf")
     for _ in range(episodes):
         obs = env.reset()

@@ -25,8 +25,9 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   the engine's ONE moving sphere (``PioneerVectorEnv.set_body``: a point mass with a radius, no spin — rolling is not modelled):
   ``world.step()`` moves it, its ``Item.pose() / velocity() / reset_pose()`` are engine calls (the base-item branch of
   bullet_scene.py:53-73), ``render("rgb_array")`` draws it where it is; a second one, one in kinematic mode or without a collision
-  shape asserts, and so does a box or plane with ``mass > 0``.  The moving sphere is not among the bodies of ``contact_points`` /
-  ``ray_test_batch`` (the batched ``contacts(bodies=[scene_sphere(r)], body_positions=...)`` takes its position per env).
+  shape asserts, and so does a box or plane with ``mass > 0``.  The moving sphere is among the bodies of ``contact_points`` /
+  ``closest_points`` / ``ray_test`` / ``ray_test_batch`` (``PioneerVectorEnv.set_body_queries``: the engine's queries read its state
+  where it is, with its velocity in the contact force); its body id is ``body_id(item)``, one past the created static bodies'.
 * ``control_torque(torque)`` (setJointMotorControl2 with TORQUE_CONTROL; the reference's Joint has no such method, Bullet does):
   dynamics mode with the PD motors: the joint's torque for the next ``world.step()`` alone (``pnr_world_step_torques``), next to its
   motor; kinematic mode and ``joint_motor == "constraint"`` raise.
@@ -395,6 +396,7 @@ class Scene:
             assert not any(isinstance(i, BodyItem) for i in self.items), "the engine models one moving sphere per env: there is one already"
             self.add_item(BodyItem(self, name, float(radius), position, orientation, rgba_color or OBSTACLE_RGBA))
             vec.set_body(mass=float(mass), radius=float(radius), position=tuple(map(float, position)), velocity=_ZERO3)
+            vec.set_body_queries(rays=True, contacts=True)                     # (render_bodies draws it: not a second time)
             return
         self._create(Item(name, "sphere", position, orientation, collision, (radius, 0.0, 0.0), rgba_color or OBSTACLE_RGBA), mass,
                      scene_sphere(radius, position, orientation))
@@ -417,6 +419,16 @@ class Scene:
         query and bodyUniqueIdB - 1."""
         return [i for i in self.items if i.collision and i.name != "target" and not isinstance(i, (LinkItem, BodyItem))]
 
+    def moving_body(self) -> Optional["BodyItem"]:
+        """The scene's moving sphere, if one was created."""
+        return next((i for i in self.items if isinstance(i, BodyItem)), None)
+
+    def body_id(self, item: Item) -> int:
+        """bodyUniqueIdB / objectUniqueId of a created collision body: 1 + its place in ``collision_items()``; the moving sphere's
+        is one past the last of them (the engine reports it after the static bodies)."""
+        bodies = self.collision_items()
+        return 1 + (len(bodies) if isinstance(item, BodyItem) else bodies.index(item))
+
     def _contact_records(self, item: Optional[Item], keep) -> List[ContactPoint]:
         bodies = self.collision_items()
         if len(bodies) > _lib.MAX_SCENE:
@@ -432,10 +444,11 @@ class Scene:
                 continue
             if isinstance(item, LinkItem) and CONTACT_SAMPLE_LINKS[s] != item.link_index:
                 continue
-            if item is not None and not isinstance(item, LinkItem) and bodies[b] is not item:
+            hit = self.moving_body() if b == _lib.MAX_SCENE else bodies[b]   # (body MAX_SCENE: the moving sphere)
+            if item is not None and not isinstance(item, LinkItem) and hit is not item:
                 continue
             n, on_a = r[1:4], r[4:7]
-            out.append(ContactPoint(0, 0, 1 + b, CONTACT_SAMPLE_LINKS[s], -1, tuple(map(float, on_a)), tuple(map(float, on_a - r[0] * n)),
+            out.append(ContactPoint(0, 0, self.body_id(hit), CONTACT_SAMPLE_LINKS[s], -1, tuple(map(float, on_a)), tuple(map(float, on_a - r[0] * n)),
                                     tuple(map(float, n)), float(r[0]), float(r[8])))
         return out
 
@@ -450,16 +463,20 @@ class Scene:
 
     # -- ray casts (pybullet.rayTest / rayTestBatch) ---------------------------------------------------------------------------
     @staticmethod
-    def _ray_hits(hits: np.ndarray) -> List[RayHit]:
+    def _ray_hits(hits: np.ndarray, moving_id: int = -1) -> List[RayHit]:
         """pnr_ray_test's ``[R, 8]`` rows as RayHit tuples: the arm is body 0 with linkIndex the URDF link, a created body
-        1 + its place in ``collision_items()`` with linkIndex -1, a miss PyBullet's (-1, -1, 1.0, (0, 0, 0), (0, 0, 0))."""
+        1 + its place in ``collision_items()`` with linkIndex -1 (the moving sphere: ``moving_id``, its item's ``body_id``), a miss PyBullet's
+        (-1, -1, 1.0, (0, 0, 0), (0, 0, 0))."""
         out = []
         for r in np.asarray(hits, dtype=np.float64):
             label = int(r[7])
             if label == _lib.SEG_BACKGROUND or label == _lib.SEG_TARGET:       # (the façade never enables the target)
                 out.append(RayHit(-1, -1, 1.0, _ZERO3, _ZERO3))
                 continue
-            body, link = (1 + label - _lib.SEG_BODY0, -1) if label >= _lib.SEG_BODY0 else (0, label - _lib.SEG_LINK0)
+            if label == _lib.SEG_MOVING_BODY:
+                body, link = moving_id, -1
+            else:
+                body, link = (1 + label - _lib.SEG_BODY0, -1) if label >= _lib.SEG_BODY0 else (0, label - _lib.SEG_LINK0)
             out.append(RayHit(body, link, float(r[0]), tuple(map(float, r[1:4])), tuple(map(float, r[4:7]))))
         return out
 
@@ -479,7 +496,8 @@ class Scene:
         sb = [SceneBody(i.shape, i._position, i._orientation, tuple(map(float, i.size))) for i in bodies]
         hits = vec.ray_test(rays, parent_link=-1 if parent_item is None else parent_item.link_index, hit_arm=True, bodies=sb,
                             joint_state=js)["hits"][0].cpu().numpy()
-        return self._ray_hits(hits)
+        sphere = self.moving_body()
+        return self._ray_hits(hits, -1 if sphere is None else self.body_id(sphere))
 
     def ray_test(self, ray_from, ray_to) -> RayHit:
         """rayTest: the first hit of the segment ray_from -> ray_to (world frame); see ``ray_test_batch``."""

@@ -76,6 +76,7 @@ class PioneerVectorEnv:
         self._h = h
         self._seed = seed
         self._body_on, self._body_params = False, None      # set_body: the moving sphere is enabled, under these params
+        self._body_queries = None                           # set_body_queries' arguments, once called (render: render_frames asks pnr_render_bodies)
 
         self.feature_major_obs = self.engine_config.obs_layout == "feature_major"
         self.feature_major_act = self.engine_config.action_layout == "feature_major"
@@ -300,10 +301,9 @@ class PioneerVectorEnv:
         ``velocity``: ``[3]`` or ``[N, 3]``; each left out keeps what the envs hold (all zero before the first call: mass 0 = no
         sphere in that env, which takes and gives no force).  ``mask`` (``[N]`` bool / uint8): only these envs' words are written.
         Stability of the explicit penalty spring needs ``contact_kd * timestep < mass`` and ``contact_kp * timestep**2 < mass``
-        (mass > 0.21 with the defaults).  ``vector_step`` / ``rollout`` / ``reset`` neither move nor see the sphere, and
-        ``render_frames`` / ``contacts`` / ``ray_test`` take it as any per-env body:
-        ``contacts(bodies=[scene_sphere(r)], body_positions=body_state()[:, None, 0:3])``.  The first call allocates and waits for
-        the buffer's zero fill."""
+        (mass > 0.21 with the defaults).  ``vector_step`` / ``rollout`` / ``reset`` neither move nor see the sphere;
+        ``render_frames`` / ``ray_test`` / ``contacts`` see it once ``set_body_queries`` says so.  The first call allocates and
+        waits for the buffer's zero fill."""
         self._check_handle()
         if params is False:
             self._chk(self.lib.pnr_set_body_params(self._h, None))
@@ -335,6 +335,21 @@ class PioneerVectorEnv:
                 raise AssertionError(f"set_body: {k} must be one value or one per env")
             w[rows[k]] = t.expand(n, width).T
         self.set_body_state(w.T, mask=mask)
+
+    def set_body_queries(self, render=False, rays=False, contacts=False, rgba=None):
+        """Which batched scene queries see the moving sphere (pnr_set_body_queries; all off after construction, which is every
+        query as it always was): ``render`` draws it in ``render_frames`` (label ``_lib.SEG_MOVING_BODY`` = 21, colour ``rgba``,
+        initially the obstacle material's grey; None keeps the current colour), ``rays`` lets ``ray_test`` hit it with
+        ``hit_bodies`` (label 21, after the caller's bodies on a tie), ``contacts`` makes ``contacts`` report it as body
+        ``_lib.MAX_SCENE`` (8) with the step's arm-sphere law on the relative velocity.  Each query reads the spheres' state of the
+        moment it runs, per env: mass > 0 = a sphere, its own centre, velocity and radius.  A host-side switch: no launch.  Needs a
+        first ``set_body`` (the buffer)."""
+        self._check_handle()
+        bits = (_lib.BODY_IN_RENDER if render else 0) | (_lib.BODY_IN_RAYS if rays else 0) | (_lib.BODY_IN_CONTACTS if contacts else 0)
+        col = None if rgba is None else (C.c_float * 4)(*(float(v) for v in rgba))
+        self._chk(self.lib.pnr_set_body_queries(self._h, bits, col))
+        rgba = rgba if rgba is not None or self._body_queries is None else self._body_queries["rgba"]
+        self._body_queries = dict(render=bool(render), rays=bool(rays), contacts=bool(contacts), rgba=rgba)
 
     def body_state(self):
         """The spheres' state, float32 ``[N, 8]`` on the device: position[3] | velocity[3] | mass | radius (pnr_get_body_state; the
@@ -518,15 +533,18 @@ class PioneerVectorEnv:
         return self.solve_ik()[1] <= within
 
     def render_frames(self, render_config=None, joint_state=None, bodies=None, rgb=True, depth=False, segmentation=False, out=None,
-                      light_direction=(0.4, 0.2, 1.0), ambient=0.45, diffuse=0.55, background=(1.0, 1.0, 1.0), target_rgba=None):
+                      light_direction=(0.4, 0.2, 1.0), ambient=0.45, diffuse=0.55, background=(1.0, 1.0, 1.0), target_rgba=None,
+                      body_positions=None):
         """render('rgb_array') of every env in one launch (bullet_env.py:156-185 -> getCameraImage; pnr_render): the URDF's 14
         visual shapes in their materials' colours, posed by each env's joints, the translucent target sphere and static bodies,
         seen by the camera of ``render_config`` (a RenderConfig, default RenderConfig(); render.view_matrix, its fov, near, far).
 
         Returns a dict of device tensors, those asked for: ``rgb`` uint8 [N, H, W, 3], ``depth`` float32 [N, H, W] (eye depth
         along the view axis, +inf where nothing is hit), ``seg`` uint8 [N, H, W] (``_lib.SEG_*``: 0 background, 1 + link index,
-        12 the target, 13 + body index).  ``joint_state``: as ``link_states`` (None = the handle's own joints).  ``bodies``: None
-        draws ``engine_config.scene`` in the URDF's obstacle_mat colour; else a sequence of (SceneBody, rgba) pairs.
+        12 the target, 13 + body index, 21 the moving sphere).  ``joint_state``: as ``link_states`` (None = the handle's own
+        joints).  ``bodies``: None draws ``engine_config.scene`` in the URDF's obstacle_mat colour; else a sequence of (SceneBody,
+        rgba) pairs.  ``body_positions`` (float32 ``[N, len(bodies), 3]``): a world position per env in place of each body's own, as
+        in ``contacts`` (pnr_render_bodies); after ``set_body_queries(render=True)`` every env with a moving sphere shows it.
         Shading: c = clamp(rgb (ambient + diffuse max(0, n . l)), 0, 1) with the defaults light_direction (0.4, 0.2, 1.0) (towards
         the light, world frame: from above, on the default camera's side), ambient 0.45, diffuse 0.55, a white background;
         ``target_rgba`` defaults to the env's PioneerKinematicConfig.target_rgba.  ``out`` may carry preallocated ``rgb`` /
@@ -562,8 +580,13 @@ class PioneerVectorEnv:
         js = self._joints(joint_state)
         res = self._asked(out, (("rgb", rgb, (n, H, W, 3), torch.uint8), ("depth", depth, (n, H, W), torch.float32),
                                 ("seg", segmentation, (n, H, W), torch.uint8)), "render_frames: ask for at least one of rgb, depth, segmentation")
-        self._chk(self.lib.pnr_render(self._h, _ptr(js), p, _ptr(res.get("rgb")), _ptr(res.get("depth")), _ptr(res.get("seg")),
-                                      self._stream()))
+        if body_positions is None and not (self._body_queries or {}).get("render"):
+            self._chk(self.lib.pnr_render(self._h, _ptr(js), p, _ptr(res.get("rgb")), _ptr(res.get("depth")), _ptr(res.get("seg")),
+                                          self._stream()))
+            return res
+        bp = None if body_positions is None else self._in(body_positions, (n, len(bodies), 3), torch.float32, "body_positions")
+        self._chk(self.lib.pnr_render_bodies(self._h, _ptr(js), p, _ptr(bp), _ptr(res.get("rgb")), _ptr(res.get("depth")),
+                                             _ptr(res.get("seg")), self._stream()))
         return res
 
     def collision_bodies(self):
@@ -597,7 +620,9 @@ class PioneerVectorEnv:
         obstacle box if set, then ``engine_config.scene``.  ``body_positions`` (float32 ``[N, len(bodies), 3]``): a world position
         per env in place of each body's own (orientation and size stay shared): the per-env obstacle.  ``joint_state``: as
         ``link_states`` (None = the handle's own joints).  The gains are the config's ``contact_kp`` / ``contact_kd``; the
-        pointer's radius its ``pointer_radius``.  ``out`` may carry preallocated ``points`` / ``summary`` / ``joint_torques``
+        pointer's radius its ``pointer_radius``.  After ``set_body_queries(contacts=True)`` every env with a moving sphere reports
+        it as one more body, index ``_lib.MAX_SCENE`` (8), under the step's arm-sphere law with the sphere's own velocity and
+        radius (it loses a distance tie to a body of ``bodies``; with no ``bodies`` it is the nearest body of its env).  ``out`` may carry preallocated ``points`` / ``summary`` / ``joint_torques``
         tensors, written in place.  Never synchronises."""
         self._check_handle()
         n = self.num_envs
@@ -634,7 +659,8 @@ class PioneerVectorEnv:
         What a ray can hit: ``hit_bodies`` the static ``bodies`` (a sequence of SceneBody, at most 8, planes as half-spaces below
         their surface; None = ``collision_bodies()``, as in ``contacts()``; ``body_positions`` ``[N, len(bodies), 3]`` a world
         position per env), ``hit_arm`` the URDF's 14 visual shapes posed by the env's joints (what ``render_frames`` draws),
-        ``hit_target`` the target sphere.  Every shape is a solid; a ray that starts inside one does not hit it.  The default is
+        ``hit_target`` the target sphere; after ``set_body_queries(rays=True)`` ``hit_bodies`` includes every env's moving sphere
+        (label ``_lib.SEG_MOVING_BODY`` = 21).  Every shape is a solid; a ray that starts inside one does not hit it.  The default is
         what Bullet would hit: the reference URDF has no collision shapes.  ``joint_state``: as ``link_states`` (None = the
         handle's own joints).  ``out`` may carry preallocated ``hits`` / ``fractions`` tensors, written in place.  Never
         synchronises."""
