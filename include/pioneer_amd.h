@@ -49,7 +49,8 @@ extern "C" {
  *      pnr_get_jacobian, pnr_ik_params_default, pnr_solve_ik, pnr_inverse_dynamics, pnr_mass_matrix, pnr_world_step_torques,
  *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
  *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets, pnr_body_params_default,
- *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state, pnr_render_bodies, pnr_set_body_queries */
+ *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state, pnr_render_bodies, pnr_set_body_queries,
+ *      pnr_render_cameras */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -840,6 +841,36 @@ int pnr_render(pnr_handle h, const float* joint_state, const pnr_render_params* 
                void* stream);
 int pnr_render_bodies(pnr_handle h, const float* joint_state, const pnr_render_params* p, const float* body_positions, uint8_t* rgb,
                       float* depth, uint8_t* seg, void* stream);
+
+/*
+ * pnr_render_bodies through a camera of its own per env, one launch: getCameraImage with a view matrix computed per env, from
+ * getLinkState for a camera on the arm (bullet_env.py:156-185 -> getCameraImage; bullet_scene.py:53-59 -> getLinkState).
+ *   cameras      device float32 [7] (cameras_per_env = 0: one row for all envs) or [num_envs][7] (cameras_per_env = 1), 4-byte
+ *                aligned, read only.  A row is position[3] | quaternion (x, y, z, w): the camera frame expressed in the parent
+ *                frame.  The camera's axes are x right, y up, z towards the viewer; it looks along -z, the convention of
+ *                p->view.  The kernel normalises the quaternion.  NULL: the camera pose is the inverse of p->view, which is then
+ *                the transform parent frame -> eye frame (cameras_per_env is still checked).  With a non-NULL cameras p->view is
+ *                not read.
+ *   camera_link  the parent frame: -1 the world; 0 .. 10 that URDF link's frame of EACH env (pnr_get_link_states' link index;
+ *                link 0 is the base, the world frame; link 10, robot:pointer, carries the fixed effector_to_pointer offset, as
+ *                pnr_ray_test's parent_link does): an eye-in-hand camera.  The link's pose comes from the joints the arm is
+ *                drawn from: joint_state, else the handle's own (dynamics mode the simulated q, kinematic mode the env's r).
+ * Everything else is pnr_render_bodies': fov_y, near_clip, far_clip, the light (world frame), the hit rule, shading, labels,
+ * the outputs, body_positions and the moving sphere where the handle shows it.  A camera inside a shape sees that shape's far
+ * face (the hit rule's leaving candidate), so a wrist camera sits outside its link's shapes: on the pointer, whose sphere has
+ * radius 0.2 about the link's origin, at a distance > 0.2 + near_clip from it, or it looks at the inside of that sphere.
+ * Unlike Bullet's getCameraImage, depth is the eye depth along the view axis, not the depth buffer's value in [0, 1].
+ * PNR_ERR_INVALID, nothing launched and no output touched, for: everything pnr_render_bodies refuses (p->view where it is
+ * read: with cameras == NULL), camera_link outside -1..10, cameras_per_env outside {0, 1}, a cameras pointer that is not
+ * 4-byte aligned.  The camera rows are device data and are not checked: a non-finite row or a zero quaternion may give THAT env
+ * any bytes, inside that env's own spans of the outputs; nothing else is written and no other env changes.  An env's image does
+ * not depend on the batch around it, bit for bit.  With camera_link == -1 and cameras == NULL the call is pnr_render_bodies: the
+ * same launch, the same bytes.  float32 arithmetic: the camera, every shape's record and its pixel rectangle are built per env
+ * on the device, where pnr_render builds the shared camera's static bodies on the host in double.
+ */
+int pnr_render_cameras(pnr_handle h, const float* joint_state, const pnr_render_params* p, const float* body_positions,
+                       int32_t camera_link, const float* cameras, int32_t cameras_per_env, uint8_t* rgb, float* depth,
+                       uint8_t* seg, void* stream);
 
 /*
  * rayTest / rayTestBatch for every env, one launch: n_rays segments per env against that env's solids.

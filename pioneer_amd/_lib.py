@@ -231,6 +231,7 @@ SIGNATURES = {
     "pnr_solve_ik_pose": (C.c_int, [_VP, C.POINTER(PnrIkPoseParams)] + [_VP] * 8),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
     "pnr_render_bodies": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP, _VP]),
+    "pnr_render_cameras": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
     "pnr_contact_params_default": (C.c_int, [C.POINTER(PnrContactParams)]),
     "pnr_get_contacts": (C.c_int, [_VP, _VP, C.POINTER(PnrContactParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_ray_params_default": (C.c_int, [C.POINTER(PnrRayParams)]),
@@ -268,7 +269,7 @@ _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr
 UNITS = {
     # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (121, 92 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
-    # the query entry points of the C ABI and their kernels (44: the three scene queries have a per-env-world form each, pnr_query.h)
+    # the query entry points of the C ABI and their kernels (47: the three scene queries have a per-env-world form each, pnr_query.h; the renderer a per-env-camera form too)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",
                         "pnr_jointstate.h", "pnr_contacts.h", "pnr_rays.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",

@@ -360,8 +360,9 @@ int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_p
 
 }  // extern "C"
 
-// pnr_render's checks of its params (nothing launched, nothing written on failure) and the kernel's constants built from them
-static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& P)
+// pnr_render's checks of its params (nothing launched, nothing written on failure) and the kernel's constants built from them;
+// use_view false (pnr_render_cameras with camera rows): p->view is neither checked nor read, the camera is the identity
+static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& P, bool use_view = true)
 {
     if (p->struct_size != sizeof(pnr_render_params))
         return fail(h, PNR_ERR_INVALID, "pnr_render: params struct_size %u, want %zu", p->struct_size, sizeof(pnr_render_params));
@@ -371,8 +372,9 @@ static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& 
     if (!(std::isfinite(p->near_clip) && std::isfinite(p->far_clip) && p->near_clip > 0 && p->far_clip > 0))
         return fail(h, PNR_ERR_INVALID, "pnr_render: near_clip and far_clip must be finite and > 0");
     if (!(p->near_clip < p->far_clip)) return fail(h, PNR_ERR_INVALID, "pnr_render: near_clip must be < far_clip");
-    if (!finite_all(p->view, 16)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite view matrix");
-    const double* V = p->view;
+    static const double kIdentityView[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const double* V = use_view ? p->view : kIdentityView;
+    if (!finite_all(V, 16)) return fail(h, PNR_ERR_INVALID, "pnr_render: non-finite view matrix");
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) {
             const double d = V[4 * a] * V[4 * b] + V[4 * a + 1] * V[4 * b + 1] + V[4 * a + 2] * V[4 * b + 2];
@@ -446,19 +448,30 @@ static int render_setup(pnr_handle h, const pnr_render_params* p, RenderParams& 
 // the moving sphere's colour where the caller never set one: the URDF's obstacle_mat (render.OBSTACLE_RGBA)
 static const float kObstacleRgb[3] = {0.3f, 0.3f, 0.3f};
 
+// pnr_render_cameras' mount: the parent link (-1 or 0: the world), the camera rows (null: the inverse of the params' view)
+struct CameraMount { int link; const float* cameras; int per_env; };
+
 // pnr_render and pnr_render_bodies: render_kernel where every env sees the caller's bodies where they are and no moving sphere
-// (what pnr_render always launched), else its scene form
+// (what pnr_render always launched), else its scene form; pnr_render_cameras (mount non-null): the same two through the world
+// camera of the params' view, else the camera form
 static int render_call(pnr_handle h, const float* joint_state, const pnr_render_params* p, const float* body_positions, uint8_t* rgb,
-                       float* depth, uint8_t* seg, void* stream)
+                       float* depth, uint8_t* seg, void* stream, const CameraMount* mount = nullptr)
 {
     if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
     if (!p) return fail(h, PNR_ERR_INVALID, "pnr_render: null params");
     if (!rgb && !depth && !seg) return fail(h, PNR_ERR_INVALID, "pnr_render: every output is NULL");
     if (const int rc = check_aligned(h, "pnr_render", {{rgb, "rgb", 16}, {depth, "depth", 16}, {seg, "seg", 16}, {joint_state, "joint_state", 16},
                                                         {body_positions, "body_positions", 4}})) return rc;
+    if (mount) {
+        if (mount->link < -1 || mount->link >= kNumLinks)
+            return fail(h, PNR_ERR_INVALID, "pnr_render_cameras: camera_link %d outside -1..%d", mount->link, kNumLinks - 1);
+        if (mount->per_env != 0 && mount->per_env != 1) return fail(h, PNR_ERR_INVALID, "pnr_render_cameras: cameras_per_env must be 0 or 1");
+        if (const int rc = check_aligned(h, "pnr_render_cameras", {{mount->cameras, "cameras", 4}})) return rc;
+    }
     if (!has_own_target(h)) return before_first_reset(h, "pnr_render", ": the target comes from the state");
+    const bool own_camera = mount && (mount->cameras || mount->link >= 1);      // (link 0 is the base: the world frame)
     RenderParams P;
-    const int rc = render_setup(h, p, P);
+    const int rc = render_setup(h, p, P, !(mount && mount->cameras));
     if (rc) return rc;
     DeviceGuard g(h->device);
     const dim3 grid((unsigned)(h->n * P.tiles)), block(kRenderThreads);
@@ -469,8 +482,20 @@ static int render_call(pnr_handle h, const float* joint_state, const pnr_render_
     X.body_pos = p->n_bodies > 0 ? body_positions : nullptr;
     X.sphere = shown_sphere(h, PNR_BODY_IN_RENDER);
     for (int k = 0; k < 3; ++k) X.sphere_rgb[k] = h->body_rgb_set ? h->body_rgb[k] : kObstacleRgb[k];
+    RenderCameraParams Y;
+    if (own_camera) {                                   // P's camera is the mount's, in the parent frame; the kernel composes each env's
+        static_cast<RenderSceneParams&>(Y) = X;
+        Y.cameras = mount->cameras; Y.cam_per_env = mount->per_env;
+        Y.cam_body = mount->link >= 1 ? kLinkBody[mount->link] : -1;
+        Y.cam_tip = mount->link == kNumLinks - 1;
+        memset(Y.body_centre, 0, sizeof(Y.body_centre));
+        for (int b = 0; b < p->n_bodies; ++b)
+            for (int k = 0; k < 3; ++k) Y.body_centre[b][k] = (float)p->bodies[b].position[k];
+    }
     with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(J.kind, [&](auto S) {
-        if (X.body_pos || X.sphere)
+        if (own_camera)
+            hipLaunchKernelGGL(render_kernel<S() | kQueryScene | kQueryCamera>, grid, block, 0, st, J.src, h->state, (long long)h->n, Y, rgb, depth, seg);
+        else if (X.body_pos || X.sphere)
             hipLaunchKernelGGL(render_kernel<S() | kQueryScene>, grid, block, 0, st, J.src, h->state, (long long)h->n, X, rgb, depth, seg);
         else
             hipLaunchKernelGGL(render_kernel<S()>, grid, block, 0, st, J.src, h->state, (long long)h->n, P, rgb, depth, seg);
@@ -491,6 +516,14 @@ int pnr_render_bodies(pnr_handle h, const float* joint_state, const pnr_render_p
                       float* depth, uint8_t* seg, void* stream)
 {
     return render_call(h, joint_state, p, body_positions, rgb, depth, seg, stream);
+}
+
+int pnr_render_cameras(pnr_handle h, const float* joint_state, const pnr_render_params* p, const float* body_positions,
+                       int32_t camera_link, const float* cameras, int32_t cameras_per_env, uint8_t* rgb, float* depth,
+                       uint8_t* seg, void* stream)
+{
+    const CameraMount mount = {camera_link, cameras, cameras_per_env};
+    return render_call(h, joint_state, p, body_positions, rgb, depth, seg, stream, &mount);
 }
 
 }  // extern "C"

@@ -38,6 +38,7 @@ enum : int {
 // every earlier call launches keep their names (<0>, <1>, <2>) and, their `if constexpr`s being false, their code; the scene
 // form's argument struct is the plain one with the per-env world appended (QueryArgs), so the plain forms keep their argument too.
 constexpr int kQueryScene = 4;
+constexpr int kQueryCamera = 8;        // the renderer's third form (pnr_render.h): SRC | kQueryScene | kQueryCamera, a camera per env
 constexpr int kJointSrcMask = 3;
 template <int SRC, class Plain, class Scene>
 using QueryArgs = std::conditional_t<(SRC & kQueryScene) != 0, Scene, Plain>;

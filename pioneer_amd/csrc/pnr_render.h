@@ -18,6 +18,12 @@
 // The scene form (render_kernel<SRC | kQueryScene>, pnr_query.h; pnr_render_bodies, and pnr_render where the handle shows its moving
 // sphere): each body's lane re-places the host's record at the env's own position, and one more lane builds the env's moving
 // sphere as one more primitive in one more slot.  The per-pixel loop is the same text.
+//
+// The camera form (render_kernel<SRC | kQueryScene | kQueryCamera>; pnr_render_cameras): a camera per env, in the world or on a
+// link of the env's arm.  Lane 0, once its sweep has filled pose[][], reads the env's camera row (position | quaternion in the
+// parent frame), composes it with the parent link's body pose and writes eye, right, up, back as one more 12-word row behind
+// the poses; the prologue's barrier covers it.  Every record is then built from that row (the static bodies too: their centres
+// travel in the argument, as the host's records hold none), and the per-pixel loop takes right, up, back from it into SGPRs.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -115,20 +121,26 @@ __host__ __device__ inline void sphere_rect(float cx, float cy, float depth, flo
 
 __device__ __forceinline__ float nonzero(float d) { return fabsf(d) < 1e-20f ? (d < 0.f ? -1e-20f : 1e-20f) : d; }
 
-// the eye-space centre of a world point
-__device__ __forceinline__ void eye_space(const RenderParams& P, V3 c, float& cx, float& cy, float& depth)
+// A camera as the prologue reads it: the eye and the eye axes in the world frame.  RenderParams holds the shared one under these
+// names (the plain and the scene form pass P itself for it); the camera form builds one per env in LDS.
+struct RenderCamera { float eye[3]; float right[3], up[3], back[3]; };
+
+// the eye-space centre of a world point seen by camera C
+template <class Cam>
+__device__ __forceinline__ void eye_space(const Cam& C, V3 c, float& cx, float& cy, float& depth)
 {
-    const V3 d = c - V3{P.eye[0], P.eye[1], P.eye[2]};
-    cx = dot(V3{P.right[0], P.right[1], P.right[2]}, d);
-    cy = dot(V3{P.up[0], P.up[1], P.up[2]}, d);
-    depth = -dot(V3{P.back[0], P.back[1], P.back[2]}, d);
+    const V3 d = c - V3{C.eye[0], C.eye[1], C.eye[2]};
+    cx = dot(V3{C.right[0], C.right[1], C.right[2]}, d);
+    cy = dot(V3{C.up[0], C.up[1], C.up[2]}, d);
+    depth = -dot(V3{C.back[0], C.back[1], C.back[2]}, d);
 }
 
-// record of a shape whose world rotation is R (shape frame -> world) and centre c
-__device__ __forceinline__ void put_prim(RenderPrim& Q, const RenderParams& P, const M3& R, V3 c, int shape, const float* half,
-                                         float bound, const float* rgb, int label)
+// record of a shape whose world rotation is R (shape frame -> world) and centre c, seen by camera C
+template <class Cam>
+__device__ __forceinline__ void put_prim(RenderPrim& Q, const RenderParams& P, const Cam& C, const M3& R, V3 c, int shape,
+                                         const float* half, float bound, const float* rgb, int label)
 {
-    const V3 e = V3{P.eye[0], P.eye[1], P.eye[2]} - c;
+    const V3 e = V3{C.eye[0], C.eye[1], C.eye[2]} - c;
     const V3 c0 = col(R, 0), c1 = col(R, 1), c2 = col(R, 2);          // rows of R^T
     Q.rt[0] = c0.x; Q.rt[1] = c0.y; Q.rt[2] = c0.z;
     Q.rt[3] = c1.x; Q.rt[4] = c1.y; Q.rt[5] = c1.z;
@@ -138,7 +150,7 @@ __device__ __forceinline__ void put_prim(RenderPrim& Q, const RenderParams& P, c
     Q.rgb[0] = rgb[0]; Q.rgb[1] = rgb[1]; Q.rgb[2] = rgb[2];
     Q.shape = shape; Q.label = label;
     float cx, cy, depth;
-    eye_space(P, c, cx, cy, depth);
+    eye_space(C, c, cx, cy, depth);
     sphere_rect(cx, cy, depth, bound, P, Q.x0, Q.x1, Q.y0, Q.y1);
 }
 
@@ -252,14 +264,76 @@ struct RenderSceneParams : RenderParams {
     float sphere_rgb[3];
 };
 
+// The camera form's argument: the scene form's and the camera mount.  P's eye / right / up / back hold the camera in the PARENT
+// frame where `cameras` is null (the inverse of the caller's view); body_centre is what the host's records lack.
+struct RenderCameraParams : RenderSceneParams {
+    const float* cameras;      // [7] or [n][7]: position | quaternion (x, y, z, w) in the parent frame, or null
+    int cam_per_env;           // 1: a row per env
+    int cam_body;              // the moving body that carries the parent link; -1: the world
+    int cam_tip;               // the parent is the pointer: the body's frame moved by kTip
+    float body_centre[kMaxScene][3];   // the static bodies' world centres (a plane: the point it passes through)
+};
+template <int SRC>
+using RenderArgs = std::conditional_t<(SRC & kQueryCamera) != 0, RenderCameraParams, QueryArgs<SRC, RenderParams, RenderSceneParams>>;
+
+// the camera the prologue builds its records from: the launch's (P itself) or, in the camera form, the env's 12-word row in LDS
+template <bool CAMERA, class Args>
+__device__ __forceinline__ const auto& render_camera(const Args& P, const float* row)
+{
+    if constexpr (CAMERA) return *reinterpret_cast<const RenderCamera*>(row);
+    else return P;
+}
+
+// an eye axis for the per-pixel loop: the launch's lies in SGPRs as it is; the env's is an LDS broadcast, made provably uniform
+template <bool CAMERA>
+__device__ __forceinline__ V3 eye_axis(const float* a)
+{
+    if constexpr (CAMERA)
+        return {__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a[0]))), __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a[1]))),
+                __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a[2])))};
+    else
+        return {a[0], a[1], a[2]};
+}
+
+// env e's camera: its row composed with the parent link's body pose (pose[][], filled by this lane), into `cam`
+__device__ __forceinline__ void build_camera(const RenderCameraParams& P, const long long e, const float (*pose)[12], RenderCamera& cam)
+{
+    V3 le = {P.eye[0], P.eye[1], P.eye[2]};                          // the camera in the parent frame: eye, then its x, y, z axes
+    V3 lr = {P.right[0], P.right[1], P.right[2]}, lu = {P.up[0], P.up[1], P.up[2]}, lb = {P.back[0], P.back[1], P.back[2]};
+    if (P.cameras) {
+        const float* c = P.cameras + (P.cam_per_env ? e * 7 : 0);
+        le = {c[0], c[1], c[2]};
+        const float s = 1.f / sqrtf(c[3] * c[3] + c[4] * c[4] + c[5] * c[5] + c[6] * c[6]);
+        const float x = s * c[3], y = s * c[4], z = s * c[5], w = s * c[6];
+        lr = {1.f - 2.f * (y * y + z * z), 2.f * (x * y + z * w), 2.f * (x * z - y * w)};       // the rotation's columns
+        lu = {2.f * (x * y - z * w), 1.f - 2.f * (x * x + z * z), 2.f * (y * z + x * w)};
+        lb = {2.f * (x * z + y * w), 2.f * (y * z - x * w), 1.f - 2.f * (x * x + y * y)};
+    }
+    if (P.cam_body >= 0) {
+        const float* w = pose[P.cam_body];
+        const M3 Rb = {{w[0], w[1], w[2]}, {w[3], w[4], w[5]}, {w[6], w[7], w[8]}};
+        V3 pb = {w[9], w[10], w[11]};
+        if (P.cam_tip) pb = pb + mul(Rb, V3{(float)kTipX, (float)kTipY, (float)kTipZ});
+        le = pb + mul(Rb, le);
+        lr = mul(Rb, lr); lu = mul(Rb, lu); lb = mul(Rb, lb);
+    }
+    cam.eye[0] = le.x; cam.eye[1] = le.y; cam.eye[2] = le.z;
+    cam.right[0] = lr.x; cam.right[1] = lr.y; cam.right[2] = lr.z;
+    cam.up[0] = lu.x; cam.up[1] = lu.y; cam.up[2] = lu.z;
+    cam.back[0] = lb.x; cam.back[1] = lb.y; cam.back[2] = lb.z;
+}
+
 template <int SRC>
 __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __restrict__ src, const float4* __restrict__ state,
-                                                                const long long n, const QueryArgs<SRC, RenderParams, RenderSceneParams> P,
+                                                                const long long n, const RenderArgs<SRC> P,
                                                                 uint8_t* __restrict__ rgb, float* __restrict__ depth, uint8_t* __restrict__ seg)
 {
-    constexpr bool SCENE = (SRC & kQueryScene) != 0;
+    constexpr bool SCENE = (SRC & kQueryScene) != 0, CAMERA = (SRC & kQueryCamera) != 0;
+    static_assert(SCENE || !CAMERA, "the camera form is a scene form");
+    static_assert(sizeof(RenderCamera) == 12 * sizeof(float), "the env's camera is one more row behind the poses");
     __shared__ RenderPrim prims[kRenderPrims + (SCENE ? 1 : 0)];    // (the scene form: one more slot, the moving sphere's)
-    __shared__ float pose[kDof][12];                                  // R (rows), p of the six moving bodies
+    __shared__ float pose[kDof + (CAMERA ? 1 : 0)][12];               // R (rows), p of the six moving bodies (the camera form: the env's camera behind them)
+    const auto& C = render_camera<CAMERA>(P, pose[kDof - 1] + 12);
     __shared__ __attribute__((aligned(16))) uint8_t st_rgb[16 + 3 * kRenderMaxTile];
     __shared__ __attribute__((aligned(16))) uint8_t st_seg[16 + kRenderMaxTile];
     __shared__ __attribute__((aligned(16))) float st_depth[4 + kRenderMaxTile];
@@ -287,6 +361,8 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
                 w[6] = b.R.r2.x; w[7] = b.R.r2.y; w[8] = b.R.r2.z; w[9] = b.p.x; w[10] = b.p.y; w[11] = b.p.z;
             }
         });
+        if constexpr (CAMERA)
+            if (tid == 0) build_camera(P, e, pose, *reinterpret_cast<RenderCamera*>(pose[kDof]));    // (behind this lane's own pose writes)
     }
     __syncthreads();
     int nprim = 1 + kNumVisuals + P.n_static;
@@ -294,16 +370,18 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
         if (tid > kNumVisuals && tid < nprim) {                      // a static body: the host's record, re-placed at the env's position
             RenderPrim& Q = prims[tid];
             Q = P.bodies[tid - 1 - kNumVisuals];
-            if (P.body_pos) {
-                const float* bp = P.body_pos + (e * P.n_static + (tid - 1 - kNumVisuals)) * 3;
+            if (CAMERA || P.body_pos) {                              // (the camera form: always, the host's record is no env's camera's)
+                const float* bp;
+                if constexpr (CAMERA) bp = P.body_pos ? P.body_pos + (e * P.n_static + (tid - 1 - kNumVisuals)) * 3 : P.body_centre[tid - 1 - kNumVisuals];
+                else bp = P.body_pos + (e * P.n_static + (tid - 1 - kNumVisuals)) * 3;
                 const V3 c = {bp[0], bp[1], bp[2]};
                 if (Q.shape == kVisPlane) {                          // the host's form: o[2] = n . (eye - point), the whole screen
-                    Q.o[2] = dot(V3{Q.rt[6], Q.rt[7], Q.rt[8]}, V3{P.eye[0], P.eye[1], P.eye[2]} - c);
+                    Q.o[2] = dot(V3{Q.rt[6], Q.rt[7], Q.rt[8]}, V3{C.eye[0], C.eye[1], C.eye[2]} - c);
                 } else {
                     const M3 R = {{Q.rt[0], Q.rt[3], Q.rt[6]}, {Q.rt[1], Q.rt[4], Q.rt[7]}, {Q.rt[2], Q.rt[5], Q.rt[8]}};   // (rt is R^T)
                     const float half[3] = {Q.h[0], Q.h[1], Q.h[2]}, colour[3] = {Q.rgb[0], Q.rgb[1], Q.rgb[2]};
                     const float bound = Q.shape == kVisBox ? sqrtf(half[0] * half[0] + half[1] * half[1] + half[2] * half[2]) : half[0];
-                    put_prim(Q, P, R, c, Q.shape, half, bound, colour, Q.label);
+                    put_prim(Q, P, C, R, c, Q.shape, half, bound, colour, Q.label);
                 }
             }
         } else if (tid == nprim && P.sphere) {                       // the env's moving sphere (words 0-2 centre, 6 mass, 7 radius)
@@ -311,7 +389,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
             const float m = w[6 * n], r = w[7 * n];
             const float half[3] = {r, r, r};
             RenderPrim& Q = prims[tid];
-            put_prim(Q, P, diag3(1.f), V3{w[0], w[n], w[2 * n]}, kVisSphere, half, r, P.sphere_rgb, kSegMovingBody);
+            put_prim(Q, P, C, diag3(1.f), V3{w[0], w[n], w[2 * n]}, kVisSphere, half, r, P.sphere_rgb, kSegMovingBody);
             if (!(m > 0.f)) { Q.x0 = 0x7fffffff; Q.x1 = -1; Q.y0 = 0x7fffffff; Q.y1 = -1; }      // no sphere: a rectangle no wave meets
         }
         nprim += P.sphere ? 1 : 0;
@@ -319,7 +397,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
     if (tid == 0) {                                                  // the target (state words 18-20)
         const float4 w = state_cold(state, n)[e];
         const float half[3] = {P.target_radius, P.target_radius, P.target_radius};
-        put_prim(prims[0], P, diag3(1.f), V3{w.x, w.y, w.z}, kVisSphere, half, P.target_radius, P.target_rgb, kSegTarget);
+        put_prim(prims[0], P, C, diag3(1.f), V3{w.x, w.y, w.z}, kVisSphere, half, P.target_radius, P.target_rgb, kSegTarget);
     } else if (tid <= kNumVisuals) {
         const VisualDef& D = kVisuals[tid - 1];
         const float* w = pose[D.body];
@@ -329,7 +407,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
         const M3 R = D.shape == kVisSphere ? diag3(1.f) : M3{mulT(Rv, Rb.r0), mulT(Rv, Rb.r1), mulT(Rv, Rb.r2)};
         const V3 c = V3{w[9], w[10], w[11]} + mul(Rb, V3{D.t[0], D.t[1], D.t[2]});
         const float bound = sqrtf(D.half[0] * D.half[0] + D.half[1] * D.half[1] + D.half[2] * D.half[2]);
-        put_prim(prims[tid], P, R, c, D.shape, D.half, D.shape == kVisBox ? bound : (D.shape == kVisSphere ? D.half[0] :
+        put_prim(prims[tid], P, C, R, c, D.shape, D.half, D.shape == kVisBox ? bound : (D.shape == kVisSphere ? D.half[0] :
                  sqrtf(D.half[0] * D.half[0] + D.half[2] * D.half[2])), D.rgba, kSegLink0 + D.link);
     } else if (!SCENE && tid < nprim) {
         prims[tid] = P.bodies[tid - 1 - kNumVisuals];
@@ -338,7 +416,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_kernel(const float* __r
 
     // ---- per pixel ----
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const V3 right = {P.right[0], P.right[1], P.right[2]}, up = {P.up[0], P.up[1], P.up[2]}, back = {P.back[0], P.back[1], P.back[2]};
+    const V3 right = eye_axis<CAMERA>(C.right), up = eye_axis<CAMERA>(C.up), back = eye_axis<CAMERA>(C.back);
     const float invW = 2.f / (float)P.W, invH = 2.f / (float)P.H;
     const int hrgb = (int)((3 * ((unsigned long long)e * P.HW + px0)) & 15);
     const int hdep = (int)(((unsigned long long)e * P.HW + px0) & 3);

@@ -54,6 +54,68 @@ def view_matrix(cfg: RenderConfig) -> np.ndarray:
     return V
 
 
+def camera_pose(view) -> np.ndarray:
+    """The camera row ``[7]`` (position | quaternion x, y, z, w; float64) whose view matrix is ``view`` (4 x 4, parent frame -> eye
+    frame, as ``view_matrix`` makes it): the camera frame expressed in the parent frame, x right, y up, looking along -z.  What
+    ``PioneerVectorEnv.render_frames(cameras=...)`` (pnr_render_cameras) takes."""
+    V = np.asarray(view, dtype=np.float64).reshape(4, 4)
+    R = V[:3, :3].T                                          # camera -> parent: the eye axes as columns
+    t = [R[0, 0] + R[1, 1] + R[2, 2], R[0, 0], R[1, 1], R[2, 2]]
+    k = int(np.argmax(t))                                    # Shepperd: the largest of w, x, y, z from the diagonal
+    if k == 0:
+        s = 2.0 * np.sqrt(1.0 + t[0])
+        q = [(R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, 0.25 * s]
+    else:
+        a, b, c = k - 1, k % 3, (k + 1) % 3
+        s = 2.0 * np.sqrt(1.0 + R[a, a] - R[b, b] - R[c, c])
+        q = [0.0, 0.0, 0.0, (R[c, b] - R[b, c]) / s]
+        q[a], q[b], q[c] = 0.25 * s, (R[a, b] + R[b, a]) / s, (R[a, c] + R[c, a]) / s
+    q = np.asarray(q) / np.linalg.norm(q)
+    return np.concatenate([-R @ V[:3, 3], q])
+
+
+def look_at_cameras(eye, target, up=(0.0, 0.0, 1.0)):
+    """The batched look-at: camera rows ``[N, 7]`` (position | quaternion x, y, z, w) at ``eye`` looking at ``target`` with ``up``
+    upwards in the image, for ``PioneerVectorEnv.render_frames(cameras=...)``.  ``eye`` / ``target`` / ``up``: ``[N, 3]`` or
+    ``[3]`` tensors or array-likes, on any device; the result is a float32 torch tensor on the inputs' device and never leaves
+    it, so a tracking camera (``target`` = each env's target or pointer) costs no host round trip.  Host inputs whose view
+    direction is zero or parallel to ``up`` raise ValueError; device inputs are NOT checked (that would synchronise): such a row
+    comes out non-finite and its env's image is undefined."""
+    import torch
+    tensors = [x for x in (eye, target, up) if isinstance(x, torch.Tensor)]
+    device = tensors[0].device if tensors else torch.device("cpu")
+    e, t, u = (torch.atleast_2d(torch.as_tensor(x, dtype=torch.float32, device=device) if not isinstance(x, torch.Tensor)
+                                else x.to(device=device, dtype=torch.float32)) for x in (eye, target, up))
+    n = max(e.shape[0], t.shape[0], u.shape[0])
+    e, t, u = (x.expand(n, 3) for x in (e, t, u))
+    f = t - e
+    f = f / f.norm(dim=1, keepdim=True)
+    r = torch.linalg.cross(f, u)
+    rn = r.norm(dim=1, keepdim=True)
+    if device.type == "cpu" and not bool((torch.isfinite(f).all(dim=1, keepdim=True) & (rn > 1e-6 * u.norm(dim=1, keepdim=True))).all()):
+        raise ValueError("look_at_cameras: a view direction is zero or parallel to up")
+    r = r / rn
+    v = torch.linalg.cross(r, f)
+    b = -f
+    # the rotation's columns are right, up, back; Shepperd's four forms, the one with the largest pivot picked per row
+    m = lambda i, j: (r, v, b)[j][:, i]  # noqa: E731
+    tr = m(0, 0) + m(1, 1) + m(2, 2)
+    piv = torch.stack([tr, m(0, 0), m(1, 1), m(2, 2)], dim=1)
+    forms = []
+    s = 2.0 * torch.sqrt(torch.clamp(1.0 + tr, min=1e-30))
+    forms.append(torch.stack([(m(2, 1) - m(1, 2)) / s, (m(0, 2) - m(2, 0)) / s, (m(1, 0) - m(0, 1)) / s, 0.25 * s], dim=1))
+    for a in range(3):
+        bb, c = (a + 1) % 3, (a + 2) % 3
+        s = 2.0 * torch.sqrt(torch.clamp(1.0 + m(a, a) - m(bb, bb) - m(c, c), min=1e-30))
+        q = [None] * 4
+        q[a], q[bb], q[c], q[3] = 0.25 * s, (m(a, bb) + m(bb, a)) / s, (m(a, c) + m(c, a)) / s, (m(c, bb) - m(bb, c)) / s
+        forms.append(torch.stack(q, dim=1))
+    k = piv.argmax(dim=1)
+    quat = torch.stack(forms, dim=0)[k, torch.arange(n, device=device)]
+    quat = quat / quat.norm(dim=1, keepdim=True)
+    return torch.cat([e, quat], dim=1).contiguous()
+
+
 def project(points, cfg: RenderConfig):
     """World points [k,3] -> pixel coords [k,2], depth [k] (NaN where behind the near plane)."""
     V = view_matrix(cfg)

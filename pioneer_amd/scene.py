@@ -134,6 +134,16 @@ class RayHit(NamedTuple):
     hitNormal: Tuple[float, float, float]
 
 
+class CameraImage(NamedTuple):
+    """pybullet.getCameraImage's result, numpy arrays: rgb uint8 [height, width, 3], depth float32 [height, width] (the eye depth
+    along the view axis, +inf where nothing is hit: not Bullet's depth buffer), seg uint8 [height, width] (``_lib.SEG_*``)."""
+    width: int
+    height: int
+    rgb: np.ndarray
+    depth: np.ndarray
+    seg: np.ndarray
+
+
 def ray_fan(n: int, length: float, start: float = 0.0) -> np.ndarray:
     """A range sensor's rays as a float32 ``[n, 6]`` array (from | to): ``n`` directions spread over the sphere (the Fibonacci
     lattice), each ray from ``start`` to ``length`` along its direction, in the frame the rays are cast in (for a sensor mounted
@@ -220,6 +230,28 @@ class LinkItem(Item):
 
     def reset_pose(self, position, orientation):
         raise AssertionError("Position can be reset only for base items: to control linked items use joint methods")   # :69-71
+
+    def camera_image(self, width: int, height: int, position=_ZERO3, orientation=(0.0, 0.0, 0.0, 1.0), fov: float = 60.0,
+                     near: float = 0.05, far: float = 200.0) -> "CameraImage":
+        """getCameraImage from a camera mounted on this link (the view matrix from getLinkState, bullet_scene.py:53-59): the camera
+        frame (x right, y up, looking along -z) sits at ``position`` / ``orientation`` (quaternion x, y, z, w) of the link's frame.
+        One engine launch (``PioneerVectorEnv.render_frames(camera_link=..., cameras=...)``) drawing the arm, the target and the
+        scene's ``render_bodies()``, on the joints ``render("rgb_array")`` draws: dynamics mode the simulated ones, kinematic
+        mode the simulator's.  ``depth`` is the eye depth along the view axis (+inf where nothing is hit), not Bullet's depth
+        buffer; ``seg`` holds the engine's labels (``_lib.SEG_*``).  Keep the camera outside the link's own shapes: from inside
+        one it sees that shape's far face."""
+        from .config import RenderConfig
+        scene = self._scene
+        vec = scene._env._vec
+        bodies = scene.render_bodies()
+        if len(bodies) > _lib.MAX_SCENE:
+            raise AssertionError(f"the engine renderer draws at most {_lib.MAX_SCENE} created bodies, the scene has {len(bodies)}")
+        cfg = RenderConfig(render_width=int(width), render_height=int(height), projection_fov=float(fov), projection_near=float(near),
+                           projection_far=float(far))
+        js = None if vec.engine_config.mode == "dynamic" else scene._bullet
+        cam = np.asarray(tuple(position) + tuple(orientation), dtype=np.float32)
+        fr = vec.render_frames(cfg, joint_state=js, bodies=bodies, depth=True, segmentation=True, camera_link=self.link_index, cameras=cam)
+        return CameraImage(int(width), int(height), *(fr[k][0].cpu().numpy() for k in ("rgb", "depth", "seg")))
 
     def _queue_wrench(self, what: str, frame: str, force, position, torque):
         env = self._scene._env

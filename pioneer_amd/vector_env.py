@@ -534,7 +534,7 @@ class PioneerVectorEnv:
 
     def render_frames(self, render_config=None, joint_state=None, bodies=None, rgb=True, depth=False, segmentation=False, out=None,
                       light_direction=(0.4, 0.2, 1.0), ambient=0.45, diffuse=0.55, background=(1.0, 1.0, 1.0), target_rgba=None,
-                      body_positions=None):
+                      body_positions=None, camera_link=None, cameras=None):
         """render('rgb_array') of every env in one launch (bullet_env.py:156-185 -> getCameraImage; pnr_render): the URDF's 14
         visual shapes in their materials' colours, posed by each env's joints, the translucent target sphere and static bodies,
         seen by the camera of ``render_config`` (a RenderConfig, default RenderConfig(); render.view_matrix, its fov, near, far).
@@ -548,7 +548,16 @@ class PioneerVectorEnv:
         Shading: c = clamp(rgb (ambient + diffuse max(0, n . l)), 0, 1) with the defaults light_direction (0.4, 0.2, 1.0) (towards
         the light, world frame: from above, on the default camera's side), ambient 0.45, diffuse 0.55, a white background;
         ``target_rgba`` defaults to the env's PioneerKinematicConfig.target_rgba.  ``out`` may carry preallocated ``rgb`` /
-        ``depth`` / ``seg`` tensors, written in place.  Never synchronises."""
+        ``depth`` / ``seg`` tensors, written in place.  Never synchronises.
+
+        A camera per env (pnr_render_cameras; getCameraImage with a view matrix per env): ``cameras``, a float32 tensor ``[7]``
+        (one row for all envs) or ``[N, 7]`` on the env's device (host values are copied), each row position | quaternion
+        (x, y, z, w) of the camera frame (x right, y up, looking along -z) in its parent frame (``render.camera_pose``,
+        ``render.look_at_cameras``); ``camera_link``, the parent frame: None the world, else an int 0 .. 10 or a name of
+        ``LINK_NAMES``, that link of EACH env (an eye-in-hand camera; the link's pose follows the joints the arm is drawn from).
+        ``camera_link`` alone mounts ``render_config``'s camera pose on the link; its fov, near, far and size hold in every case.
+        A camera inside a shape sees that shape's far face: keep a wrist camera outside its link's shapes.  With both left out
+        the call is the shared-camera call above."""
         from . import render as _render
         from .config import RenderConfig
         self._check_handle()
@@ -580,6 +589,21 @@ class PioneerVectorEnv:
         js = self._joints(joint_state)
         res = self._asked(out, (("rgb", rgb, (n, H, W, 3), torch.uint8), ("depth", depth, (n, H, W), torch.float32),
                                 ("seg", segmentation, (n, H, W), torch.uint8)), "render_frames: ask for at least one of rgb, depth, segmentation")
+        if camera_link is not None or cameras is not None:
+            if isinstance(camera_link, str) and camera_link not in LINK_NAMES:
+                raise AssertionError(f"render_frames: no link named {camera_link!r}")
+            link = -1 if camera_link is None else (LINK_NAMES.index(camera_link) if isinstance(camera_link, str) else int(camera_link))
+            cams = None
+            if cameras is not None:
+                if not isinstance(cameras, torch.Tensor):
+                    cameras = torch.as_tensor(np.asarray(cameras), dtype=torch.float32)
+                if tuple(cameras.shape) not in ((7,), (n, 7)):
+                    raise AssertionError(f"cameras must have shape (7,) or ({n}, 7), got {tuple(cameras.shape)}")
+                cams = self._in(cameras, tuple(cameras.shape), torch.float32, "cameras")
+            bp = None if body_positions is None else self._in(body_positions, (n, len(bodies), 3), torch.float32, "body_positions")
+            self._chk(self.lib.pnr_render_cameras(self._h, _ptr(js), p, _ptr(bp), link, _ptr(cams), int(cams is not None and cams.dim() == 2),
+                                                  _ptr(res.get("rgb")), _ptr(res.get("depth")), _ptr(res.get("seg")), self._stream()))
+            return res
         if body_positions is None and not (self._body_queries or {}).get("render"):
             self._chk(self.lib.pnr_render(self._h, _ptr(js), p, _ptr(res.get("rgb")), _ptr(res.get("depth")), _ptr(res.get("seg")),
                                           self._stream()))

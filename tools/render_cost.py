@@ -5,6 +5,8 @@ median of alternated rounds, for
   b  65 536 envs x 64 x 64 RGB + segmentation, same scene
   c  one env at 1280 x 800 through the façade (render("rgb_array") with EngineConfig.renderer = "engine", copy to the host
      included) next to the host stick figure (render_rgb) on the same box.
+--cameras times the per-env cameras instead (pnr_render_cameras): case a through the shared camera, through the same
+camera given as a row per env, and through a camera on each env's pointer, alternated in the same rounds.
 Prints one JSON line per case: us per call, G pixels / s, output bytes / s and their share of the 8 TB/s HBM peak.
 Kernel-only times: run the same cases under `rocprofv3 --kernel-trace --stats -- python tools/render_cost.py --rounds 5`."""
 import argparse
@@ -40,6 +42,30 @@ def batch_setup(name, n, W, H, seg):
     for _ in range(3):
         run()
     return dict(name=name, env=env, run=run, n=n, W=W, H=H, seg=seg, times=[])
+
+
+def camera_setups(n=4096, W=84, H=84):
+    """--cameras: case a's batch three times over, one env batch and one output: the shared world camera (pnr_render), the same
+    camera as a row per env through the camera form (pnr_render_cameras: the same picture, so the difference is the form's own
+    cost), and a camera mounted on each env's pointer (another picture: near geometry fills the screen, the rectangles cull less)."""
+    from pioneer_amd import PioneerVectorEnv, RenderConfig, render
+    env = PioneerVectorEnv(n, device="cuda:0", seed=0)
+    env.reset()
+    cfg = RenderConfig(render_width=W, render_height=H, camera_distance=60.0)
+    wrist = RenderConfig(render_width=W, render_height=H, projection_fov=60.0, projection_near=0.05)
+    out = {"rgb": torch.empty((n, H, W, 3), dtype=torch.uint8, device="cuda:0")}
+    bodies = scene()
+    rows = torch.as_tensor(render.camera_pose(render.view_matrix(cfg)), dtype=torch.float32, device="cuda:0").repeat(n, 1).contiguous()
+    mount = torch.tensor([0.0, 0.0, 0.3, 1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device="cuda:0")
+    runs = {"a_shared_camera": lambda: env.render_frames(cfg, bodies=bodies, out=out),
+            "a_same_camera_per_env_rows": lambda: env.render_frames(cfg, bodies=bodies, out=out, cameras=rows),
+            "a_pointer_mount": lambda: env.render_frames(wrist, bodies=bodies, out=out, camera_link=10, cameras=mount)}
+    cases = []
+    for name, run in runs.items():
+        for _ in range(3):
+            run()
+        cases.append(dict(name=name, env=env, run=run, n=n, W=W, H=H, seg=False, times=[]))
+    return cases
 
 
 def time_round(c, calls):
@@ -87,7 +113,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--calls", type=int, default=20, help="launches per timed round (cases a, b)")
     ap.add_argument("--cases", default="abc")
+    ap.add_argument("--cameras", action="store_true", help="the per-env camera leg alone: case a through the shared camera, the same camera "
+                    "as per-env rows, and a pointer mount")
     args = ap.parse_args()
+    if args.cameras:
+        cases = camera_setups()
+        for _ in range(args.rounds):                        # alternated rounds
+            for c in cases:
+                time_round(c, args.calls)
+        results = [batch_result(c) for c in cases]
+        for r in results:
+            r["vs_shared_camera"] = round(r["us_per_call"] / results[0]["us_per_call"], 3)
+            print(json.dumps(r), flush=True)
+        return
     cases = []
     if "a" in args.cases:
         cases.append(batch_setup("a", 4096, 84, 84, False))
