@@ -50,7 +50,7 @@ extern "C" {
  *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
  *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets, pnr_body_params_default,
  *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state, pnr_render_bodies, pnr_set_body_queries,
- *      pnr_render_cameras */
+ *      pnr_render_cameras, pnr_body_grip_params_default, pnr_set_body_grip_params, pnr_set_body_grip, pnr_get_body_grip */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -60,6 +60,7 @@ extern "C" {
                            /* the info dict, pioneer_knm_env.py:167-179)      */
 #define PNR_DYN_STATE_WORDS 36 /* dynamics mode: q[6] qd[6] + 24 params       */
 #define PNR_BODY_STATE_WORDS 8 /* the moving sphere: position[3] velocity[3] mass radius */
+#define PNR_BODY_GRIP_WORDS 4  /* the grip on the moving sphere: max_force, last force on the sphere[3] */
 #define PNR_NUM_LINKS 11       /* pnr_get_link_states: links per env (URDF joint order) */
 #define PNR_LINK_STATE_DIM 13  /* floats per link record                      */
 #define PNR_JACOBIAN_DIM 36    /* pnr_get_jacobian: 6 rows x 6 joint columns per env */
@@ -657,6 +658,63 @@ int pnr_body_params_default(pnr_body_params* p);
 int pnr_set_body_params(pnr_handle h, const pnr_body_params* params);
 int pnr_set_body_state(pnr_handle h, const float* words, const uint8_t* mask, void* stream);
 int pnr_get_body_state(pnr_handle h, float* out, void* stream);
+
+/*
+ * THE GRIP: each env's moving sphere held at a point of link robot:pointer, PyBullet's createConstraint(arm, pointerLink, body, -1,
+ * JOINT_POINT2POINT, ...) with changeConstraint(maxForce) — how suction and magnet grippers are modelled — removeConstraint and
+ * getConstraintState.  Dynamics mode, on a handle with a sphere buffer (pnr_set_body_params first).
+ *
+ * State: the handle owns a planar float32 buffer [PNR_BODY_GRIP_WORDS][num_envs]: word 0 the env's max_force (<= 0: released, the
+ * state after allocation), words 1-3 the world-frame force on the sphere in the last sub-step of the last world step.
+ *
+ * The law: a soft point-to-point constraint with a force cap between a point of the pointer link and the sphere's centre,
+ * evaluated in every sub-step at the state the sub-step starts from, as every other force of the world step is, in every env whose
+ * max_force word is > 0 and whose mass word is > 0.  With R_5, p_5 the world pose of moving body 5 (the last one, which carries
+ * the pointer), (omega, v_lin) its spatial velocity in its own coordinates, kTip = (3.6, 0, 1.9) the pointer's origin in that body,
+ * radius_e the env's radius word and x, v the sphere's centre and velocity:
+ *     c_a = kTip + anchor + (radius_e + pointer_radius) direction      (body 5's frame; anchor and direction are the params')
+ *     p_a = p_5 + R_5 c_a,   v_a = R_5 (v_lin + omega x c_a)           (as a contact sample's position and velocity)
+ *     e   = x - p_a,   e'  = v - v_a
+ *     F_r = - grip_kp e - grip_kd e'
+ *     F   = F_r min(1, max_force / |F_r|)        (F = F_r where |F_r| <= max_force, in particular at F_r = 0)
+ * +F acts on the sphere, next to the static world's force, before the sphere's integration; -F acts on body 5 at c_a and enters it
+ * exactly as a contact reaction does.  The force is continuous in the state everywhere (no normalised direction, no threshold).
+ * WHILE AN ENV IS GRIPPED ITS SPHERE TAKES NO ARM-SPHERE CONTACT FROM ANY SAMPLE: the held sphere may overlap the pointer.  Its
+ * contacts with the static world stay, so it can be lifted off the ground and set down on a box.  A released env (max_force <= 0)
+ * follows the sphere's law above exactly, arm contacts included.
+ * Stability of the explicit spring needs grip_kp timestep^2 < m and grip_kd timestep < m, with m the smaller of the sphere's mass
+ * and the arm's effective mass at the pointer: with the defaults (2000, 50, 1/240) that is m > 0.21, as for the contacts.
+ *
+ * pnr_body_grip_params (pnr_body_grip_params_default): anchor (0, 0, 0); direction the unit vector along the tip offset
+ * (3.6, 0, 1.9) in the pointer's frame, with which the held sphere sits tangent to the pointer's own sample sphere for any per-env
+ * radius, so that a release does not start from a deep penetration; direction (0, 0, 0) makes the anchor a plain point of the link;
+ * any other direction is normalised.  grip_kp, grip_kd NaN = the sphere's resolved contact_kp, contact_kd at the time of the call.
+ * pnr_set_body_grip_params enables the grip.  Its first call on a handle allocates the buffer and zero-fills it — every env
+ * released — and WAITS for that fill, as the first pnr_set_body_params does; later calls only replace the params.  params == NULL
+ * disables the grip and keeps the buffer: the world step then launches the kernels of a handle that never knew a grip.
+ * pnr_set_body_grip writes max_force [num_envs] (device memory, read only) into word 0 and zeros into words 1-3, for every env or,
+ * with mask ([num_envs] bytes, device memory), the envs with a non-zero byte: the device-side "grip the envs that just came within
+ * reach" or "drop the envs that just finished".  pnr_get_body_grip copies the buffer to out [4][num_envs] (16-byte aligned): words
+ * 1-3 are PyBullet's getConstraintState.  The world step writes words 1-3 of gripped envs with mass > 0 and of no other.  Both
+ * calls are asynchronous on `stream`, never synchronise and allocate nothing, and work while the grip is disabled.
+ * PNR_ERR_UNSUPPORTED: a kinematic-mode handle.  PNR_ERR_INVALID: a null handle, a call before the first pnr_set_body_params, a
+ * wrong struct_size, anything non-finite, grip_kp <= 0, grip_kd < 0, a direction that is neither zero nor normalisable, a null or
+ * misaligned pointer, pnr_set_body_grip / pnr_get_body_grip before the first pnr_set_body_grip_params.  Every refusal is decided
+ * before any launch and changes nothing.  max_force is device data and cannot be validated on the host (NaN counts as released).
+ * What the sphere refuses stays refused, in the sphere's messages: constraint motors, pnr_world_step_wrenches, pnr_get_joint_states.
+ * THE SCENE QUERIES DO NOT KNOW THE GRIP: pnr_get_contacts keeps reporting (and pricing) the overlap of a held sphere with the arm's
+ * samples that the step ignores; pnr_render and pnr_ray_test see the sphere where it is, as before.  pnr_step, pnr_rollout and
+ * pnr_reset neither move nor see the sphere, gripped or not.  Parity unpinned; checked against a float64 restatement of this law.
+ */
+typedef struct pnr_body_grip_params {
+    uint32_t struct_size;
+    float anchor[3], direction[3];
+    float grip_kp, grip_kd;
+} pnr_body_grip_params;
+int pnr_body_grip_params_default(pnr_body_grip_params* p);
+int pnr_set_body_grip_params(pnr_handle h, const pnr_body_grip_params* params);
+int pnr_set_body_grip(pnr_handle h, const float* max_force, const uint8_t* mask, void* stream);
+int pnr_get_body_grip(pnr_handle h, float* out, void* stream);
 
 /*
  * Which of the batched scene queries SEE the moving sphere: pnr_render / pnr_render_bodies, pnr_ray_test, pnr_get_contacts.

@@ -47,6 +47,7 @@ WRENCH_DIM = 9          # .. force[3], position[3], torque[3] per record
 JOINT_STATE_DIM = 4     # pnr_get_joint_states: q, qd, qdd, tau_motor per joint
 REACTION_DIM = 6        # .. Fx, Fy, Fz, Mx, My, Mz per joint
 BODY_STATE_WORDS = 8    # pnr_set_body_state: the moving sphere's position[3], velocity[3], mass, radius (PNR_BODY_STATE_WORDS)
+BODY_GRIP_WORDS = 4     # pnr_get_body_grip: the grip's max_force, then the last sub-step's force on the sphere[3] (PNR_BODY_GRIP_WORDS)
 FRAME_LINK, FRAME_WORLD = 1, 2                     # .. a record's frame (PNR_FRAME_*; pybullet's LINK_FRAME / WORLD_FRAME)
 
 PNR_OK = 0
@@ -75,6 +76,12 @@ class PnrBodyParams(C.Structure):
     """pnr_body_params of include/pioneer_amd.h (the moving sphere's contact gains, friction and damping)."""
     _fields_ = [("struct_size", C.c_uint32), ("contact_kp", C.c_float), ("contact_kd", C.c_float), ("friction", C.c_float),
                 ("slip_eps", C.c_float), ("linear_damping", C.c_float)]
+
+
+class PnrBodyGripParams(C.Structure):
+    """pnr_body_grip_params of include/pioneer_amd.h (the grip's anchor point on the pointer link and its spring)."""
+    _fields_ = [("struct_size", C.c_uint32), ("anchor", C.c_float * 3), ("direction", C.c_float * 3), ("grip_kp", C.c_float),
+                ("grip_kd", C.c_float)]
 
 
 class PnrSceneBody(C.Structure):
@@ -219,6 +226,10 @@ SIGNATURES = {
     "pnr_set_body_params": (C.c_int, [_VP, C.POINTER(PnrBodyParams)]),
     "pnr_set_body_state": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_get_body_state": (C.c_int, [_VP, _VP, _VP]),
+    "pnr_body_grip_params_default": (C.c_int, [C.POINTER(PnrBodyGripParams)]),
+    "pnr_set_body_grip_params": (C.c_int, [_VP, C.POINTER(PnrBodyGripParams)]),
+    "pnr_set_body_grip": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "pnr_get_body_grip": (C.c_int, [_VP, _VP, _VP]),
     "pnr_set_body_queries": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_float * 4)]),
     "pnr_get_link_states": (C.c_int, [_VP, _VP, _VP, _VP]),
     "pnr_get_jacobian": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_double * 3), _VP, _VP]),
@@ -267,7 +278,7 @@ SIGNATURES = {
 # the library's translation units and what each includes: a unit is recompiled when one of its files is newer than its object
 _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_dyn.h"]      # what every env-engine unit includes
 UNITS = {
-    # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (121, 92 of them dynamics mode's)
+    # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (126, 96 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
     # the query entry points of the C ABI and their kernels (47: the three scene queries have a per-env-world form each, pnr_query.h; the renderer a per-env-camera form too)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",

@@ -368,6 +368,7 @@ int pnr_destroy(pnr_handle h)
     if (h->dyn) (void)hipFree(h->dyn);
     if (h->scene) (void)hipFree(h->scene);
     if (h->sphere.words) (void)hipFree(h->sphere.words);
+    if (h->sphere.grip) (void)hipFree(h->sphere.grip);
     delete h;
     return PNR_OK;
 }
@@ -534,9 +535,11 @@ int pnr_set_joint_motor(pnr_handle h, int joint, int control_mode, double target
 }
 
 // The dynamics-mode world step's one launch, for the four calls below (their checks have passed): dyn_world_kernel<RAND, PHYS, form>
-// with the call's inputs, its motor table W and, for wrenches, its record table.  `form` is one of the eight listed here; no other
+// with the call's inputs, its motor table W and, for wrenches, its record table.  `form` is one of the ten listed here; no other
 // is instantiated.  With the handle's sphere enabled the torque and the targets form are the ones with kWorldBody (PHYS 1 or 3 only:
-// always with contact code), which the plain call takes too, its joint torques null.  (Always the instantiation that reads the per-env link scales: without randomisation they are stored as 1.)
+// always with contact code), which the plain call takes too, its joint torques null; with the grip enabled as well
+// (pnr_set_body_grip_params) those two with kWorldGrip, and with it disabled or never enabled the two without: the kernels of a handle
+// that knows no grip.  (Always the instantiation that reads the per-env link scales: without randomisation they are stored as 1.)
 struct WorldStepInputs {
     const float* targets = nullptr; unsigned mask = 0;      // pnr_world_step_targets
     const float* tau_ext = nullptr;
@@ -549,11 +552,12 @@ static int launch_world_step(pnr_handle h, int form, const JointMotorTable& W, c
     const dim3 grid((unsigned)((h->n + kWave - 1) / kWave));
     bool launched = false;
     int phys = dyn_phys(h->dbase);
-    WorldBody body = h->sphere;
-    if (h->sphere_on) { form |= kWorldBody | kWorldTorque; phys |= 1; body.joint_mask = in.mask; }
+    WorldGrip body = h->sphere;
+    if (h->sphere_on) { form |= kWorldBody | kWorldTorque | (h->grip_on ? kWorldGrip : 0); phys |= 1; body.joint_mask = in.mask; }
     // (forms outermost, in this order: the compiler emits the instantiations in the reverse of it)
-    const auto args = std::make_tuple(in.wrenches, in.targets, in.tau_ext, in.mask, h->dbase, W, in.T, body);      // by WorldRole
-    with_int<kWorldBody | kWorldTargets | kWorldTorque, kWorldBody | kWorldTorque, kWorldWrench | kWorldTorque, kWorldTargets | kWorldTorque,
+    const auto args = std::make_tuple(in.wrenches, in.targets, in.tau_ext, in.mask, h->dbase, W, in.T, static_cast<const WorldBody&>(body), body);      // by WorldRole
+    with_int<kWorldGrip | kWorldBody | kWorldTargets | kWorldTorque, kWorldGrip | kWorldBody | kWorldTorque,
+             kWorldBody | kWorldTargets | kWorldTorque, kWorldBody | kWorldTorque, kWorldWrench | kWorldTorque, kWorldTargets | kWorldTorque,
              kWorldTargets | kWorldCMotor, kWorldTorque, 0, kWorldCMotor>(form, [&](auto F_) {
         constexpr int F = decltype(F_)::value;
         const auto launch = [&](auto C) {
@@ -717,6 +721,85 @@ int pnr_get_body_state(pnr_handle h, float* out, void* stream)
     DeviceGuard g(h->device);
     const size_t bytes = sizeof(float) * PNR_BODY_STATE_WORDS * (size_t)h->n;      // (outside HIP_TRY, which quotes its argument in the message)
     HIP_TRY(h, hipMemcpyAsync(out, h->sphere.words, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PNR_OK;
+}
+
+int pnr_body_grip_params_default(pnr_body_grip_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_body_grip_params_default: null params");
+    // direction: the unit vector along the tip offset, so that the held sphere sits tangent to the pointer's own sample sphere
+    const double tl = std::sqrt(kTipX * kTipX + kTipY * kTipY + kTipZ * kTipZ);
+    *p = pnr_body_grip_params{(uint32_t)sizeof(pnr_body_grip_params), {0.f, 0.f, 0.f},
+                              {(float)(kTipX / tl), (float)(kTipY / tl), (float)(kTipZ / tl)}, NAN, NAN};
+    return PNR_OK;
+}
+
+int pnr_set_body_grip_params(pnr_handle h, const pnr_body_grip_params* p)
+{
+    const char* call = "pnr_set_body_grip_params";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "%s: null handle", call);
+    if (h->cfg.mode != PNR_MODE_DYNAMIC) return fail(h, PNR_ERR_UNSUPPORTED, "%s: the moving sphere exists in dynamics mode only", call);
+    if (!h->sphere.words) return fail(h, PNR_ERR_INVALID, "%s before pnr_set_body_params (the handle has no sphere buffer)", call);
+    if (!p) { h->grip_on = false; return PNR_OK; }
+    if (p->struct_size != sizeof(pnr_body_grip_params))
+        return fail(h, PNR_ERR_INVALID, "%s: struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_body_grip_params));
+    const float kp = p->grip_kp == p->grip_kp ? p->grip_kp : h->sphere.kp;
+    const float kd = p->grip_kd == p->grip_kd ? p->grip_kd : h->sphere.kd;
+    const float all[8] = {kp, kd, p->anchor[0], p->anchor[1], p->anchor[2], p->direction[0], p->direction[1], p->direction[2]};
+    if (!finite_all(all, 8)) return fail(h, PNR_ERR_INVALID, "%s: non-finite parameter", call);
+    if (!(kp > 0) || kd < 0) return fail(h, PNR_ERR_INVALID, "%s: grip_kp must be > 0 and grip_kd >= 0 (%g, %g)", call, kp, kd);
+    // the direction: zero (the anchor is a plain point of the link) or normalised here, in double
+    const double dv[3] = {p->direction[0], p->direction[1], p->direction[2]};
+    const double dl = std::sqrt(sum_sq(dv, 3));
+    const bool zero = dv[0] == 0 && dv[1] == 0 && dv[2] == 0;
+    if (!zero && !(dl > 1e-6 && std::isfinite(dl)))
+        return fail(h, PNR_ERR_INVALID, "%s: direction (%g, %g, %g) is neither zero nor normalisable", call, dv[0], dv[1], dv[2]);
+    if (!h->sphere.grip) {
+        DeviceGuard g(h->device);
+        const size_t bytes = sizeof(float) * PNR_BODY_GRIP_WORDS * (size_t)h->n;
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return fail(h, PNR_ERR_NOMEM, "%s: hipMalloc(grip) failed: %s", call, hipGetErrorString(e));
+        // zero = max_force 0 = every env released; waited for, as the sphere buffer's fill is
+        e = hipMemset(q, 0, bytes);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) { (void)hipFree(q); return fail(h, PNR_ERR_HIP, "%s: zero fill of the grip buffer failed: %s", call, hipGetErrorString(e)); }
+        h->sphere.grip = (float*)q;
+    }
+    h->sphere.grip_kp = kp; h->sphere.grip_kd = kd;
+    for (int k = 0; k < 3; ++k) {
+        h->sphere.anchor[k] = p->anchor[k];
+        h->sphere.direction[k] = zero ? 0.f : (float)(dv[k] / dl);
+    }
+    h->grip_on = true;
+    return PNR_OK;
+}
+
+// the argument checks of pnr_set_body_grip / pnr_get_body_grip
+static int check_body_grip_call(pnr_handle h, const void* p, const char* name, unsigned align, const char* call)
+{
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "%s: null handle", call);
+    if (!h->sphere.grip) return fail(h, PNR_ERR_INVALID, "%s before pnr_set_body_grip_params (the handle has no grip buffer)", call);
+    if (!p) return fail(h, PNR_ERR_INVALID, "%s: null %s", call, name);
+    return check_aligned(h, call, {{p, name, align}});
+}
+
+int pnr_set_body_grip(pnr_handle h, const float* max_force, const uint8_t* mask, void* stream)
+{
+    if (const int rc = check_body_grip_call(h, max_force, "max_force", 4, "pnr_set_body_grip")) return rc;
+    DeviceGuard g(h->device);
+    hipLaunchKernelGGL(grip_set_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->sphere.grip, max_force, mask,
+                       (long long)h->n);
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+int pnr_get_body_grip(pnr_handle h, float* out, void* stream)
+{
+    if (const int rc = check_body_grip_call(h, out, "out", 16, "pnr_get_body_grip")) return rc;
+    DeviceGuard g(h->device);
+    const size_t bytes = sizeof(float) * PNR_BODY_GRIP_WORDS * (size_t)h->n;
+    HIP_TRY(h, hipMemcpyAsync(out, h->sphere.grip, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PNR_OK;
 }
 

@@ -519,6 +519,18 @@ struct WorldBody {
     unsigned joint_mask;                 // the targets form's joint mask rides here (that form has no slot left for kArgMask)
 };
 struct SphereLane { V3 x, v; float m, r; V3 F; };
+// pnr_set_body_grip_params (kWorldGrip): the forms with the grip take this argument in WorldBody's place (kArgGripBody) and carry this
+// lane; every other form's argument and lane are the ones above, untouched.  Where a kWorldGrip instantiation holds a WorldBody or a
+// SphereLane pointer, the object is one of these.
+struct WorldGrip : WorldBody {
+    float* grip;                         // [PNR_BODY_GRIP_WORDS][n]: max_force, then the last sub-step's force on the sphere[3]
+    float grip_kp, grip_kd;
+    float anchor[3], direction[3];       // c_a = kTip + anchor + (radius + pointer_radius) direction, in moving body 5's frame; wave-uniform
+};
+struct GripLane : SphereLane {
+    float g;                             // the env's grip word max_force (> 0: held)
+    V3 G;                                // the grip's force on the sphere in this sub-step
+};
 
 // ---------------------------------------------------------------------------------
 // The contact geometry of the static bodies and the penalty law, stated once for the step's arm samples (sample_contact), the
@@ -618,7 +630,9 @@ __device__ __forceinline__ void sphere_integrate(const DynParams& D, const World
 // extras, pioneer_knm_env.py:249-261; create_body_plane / create_body_box, bullet_scene.py:206-228) and the scene's bodies: the
 // contact force is added to the body's external spatial force in body coordinates.
 // SPHERE (kWorldBody): the sample also meets the env's moving sphere S; the pair's force goes to S.F and, reversed, into F here.
-template <bool SPHERE = false>
+// kSphereGrip (kWorldGrip): .. unless the env's sphere is held (S.g > 0), which takes no arm contact from any sample.
+enum : int { kSphereNone = 0, kSphereFree = 1, kSphereGrip = 2 };
+template <int SPHERE = kSphereNone>
 __device__ __forceinline__ void sample_contact(const DynParams& D, const M3& R, V3 p, const P3& vb, V3 c, float radius, P3& fext,
                                                const WorldBody* B = nullptr, SphereLane* S = nullptr)
 {
@@ -646,13 +660,15 @@ __device__ __forceinline__ void sample_contact(const DynParams& D, const M3& R, 
         float fn;
         if (penalty(D.ckp, D.ckd, radius - sdf, dot(vw, nrm), fn)) F = F + fn * nrm;
     }
-    if constexpr (SPHERE) {
+    if constexpr (SPHERE != kSphereNone) {
         const V3 d = S->x - pos;
         const float len = sqrtf(dot(d, d));
         const V3 nrm = len > 0.f ? (1.f / len) * d : V3{0.f, 0.f, 1.f};
         float fn;
         const bool hit = penalty(B->kp, B->kd, S->r + radius - len, dot(S->v - vw, nrm), fn);
-        if (S->m > 0.f && hit) { S->F = S->F + fn * nrm; F = F - fn * nrm; }
+        bool on = S->m > 0.f && hit;
+        if constexpr (SPHERE == kSphereGrip) on = on && !(static_cast<const GripLane*>(S)->g > 0.f);
+        if (on) { S->F = S->F + fn * nrm; F = F - fn * nrm; }
     }
     const V3 fb = mulT(R, F);                             // R^T F
     fext = fext + pack(cross(c, fb), fb);
@@ -690,7 +706,7 @@ __device__ __forceinline__ void for_body_samples(F&& f)
 }
 
 // every sample sphere of moving body BODY; without link contacts only the pointer
-template <int BODY, bool SPHERE = false>
+template <int BODY, int SPHERE = kSphereNone>
 __device__ __forceinline__ void body_contacts(const DynParams& D, const M3& R, V3 p, const P3& vb, P3& fext, const WorldBody* B = nullptr,
                                               SphereLane* S = nullptr)
 {
@@ -699,8 +715,29 @@ __device__ __forceinline__ void body_contacts(const DynParams& D, const M3& R, V
     });
 }
 
+// pnr_set_body_grip_params (the law is stated in include/pioneer_amd.h): the soft point-to-point constraint between the anchor point
+// c_a of moving body 5 (world pose R, p; spatial velocity vb in body coordinates) and the sphere's centre, capped at the lane's
+// max_force S.g.  +F goes to S.F (and to S.G, for the report), -F enters fext at c_a as a contact reaction does.  A lane that is
+// not held (S.g <= 0 or no sphere) adds exact zeros: selects, no branch.
+__device__ __forceinline__ void grip_force(const DynParams& D, const WorldGrip& B, const M3& R, V3 p, const P3& vb, P3& fext, GripLane& S)
+{
+    const float reach = S.r + D.ptr_radius;
+    const V3 c = {(float)kTipX + B.anchor[0] + reach * B.direction[0], (float)kTipY + B.anchor[1] + reach * B.direction[1],
+                  (float)kTipZ + B.anchor[2] + reach * B.direction[2]};
+    const V3 pos = p + mul(R, c);                           // exactly how sample_contact gets pos, vw
+    const V3 vw = mul(R, lin(vb) + cross(ang(vb), c));
+    const V3 Fr = (-B.grip_kp) * (S.x - pos) - B.grip_kd * (S.v - vw);
+    const bool held = S.g > 0.f && S.m > 0.f;
+    const float k = fminf(1.f, S.g / sqrtf(dot(Fr, Fr)));   // |Fr| = 0: max_force / 0 = +inf, k = 1
+    const V3 F = {held ? k * Fr.x : 0.f, held ? k * Fr.y : 0.f, held ? k * Fr.z : 0.f};
+    S.F = S.F + F;
+    S.G = F;
+    const V3 fb = mulT(R, V3{-F.x, -F.y, -F.z});
+    fext = fext + pack(cross(c, fb), fb);
+}
+
 // the external spatial force of all active contacts on every body, in body coordinates
-template <bool SPHERE = false>
+template <int SPHERE = kSphereNone>
 __device__ __forceinline__ void contact_wrenches(const DynParams& D, const float (&c)[kDof], const float (&s)[kDof],
                                                  const P3 (&v)[kDof], P3 (&fext)[kDof], const WorldBody* B = nullptr, SphereLane* S = nullptr)
 {
@@ -712,6 +749,7 @@ __device__ __forceinline__ void contact_wrenches(const DynParams& D, const float
     pose_outward<3>(R, p, c[3], s[3], Rn, pn); R = Rn; p = pn; body_contacts<3, SPHERE>(D, R, p, v[3], fext[3], B, S);
     pose_outward<4>(R, p, c[4], s[4], Rn, pn); R = Rn; p = pn; body_contacts<4, SPHERE>(D, R, p, v[4], fext[4], B, S);
     pose_outward<5>(R, p, c[5], s[5], Rn, pn); R = Rn; p = pn; body_contacts<5, SPHERE>(D, R, p, v[5], fext[5], B, S);
+    if constexpr (SPHERE == kSphereGrip) grip_force(D, *static_cast<const WorldGrip*>(B), R, p, v[5], fext[5], *static_cast<GripLane*>(S));
 }
 
 // ---------------------------------------------------------------------------------
@@ -831,8 +869,9 @@ __device__ __forceinline__ void wrench_forces(const LinkWrenchTable& T, const fl
 // PHYS: bit 0 = contacts, bit 1 = the inertia-scaled motor (its acceleration requests in ades, torque cap tcap)
 // EXT (pnr_world_step_wrenches): ext[6], the caller's wrenches of this sub-step in body coordinates; the contacts add into the same
 // fext, and body 0 (which carries no contact samples) has its bias force reduced as well
-// SPHERE (kWorldBody): the contact samples also meet the env's moving sphere, whose force accumulator sphere->F takes its share
-template <int PHYS, bool EXT = false, bool SPHERE = false>
+// SPHERE (kWorldBody): the contact samples also meet the env's moving sphere, whose force accumulator sphere->F takes its share;
+// kSphereGrip (kWorldGrip): and the grip holds it at body 5's anchor point
+template <int PHYS, bool EXT = false, int SPHERE = kSphereNone>
 __device__ __forceinline__ void aba(const DynParams& D, const DynModel& M, const float (&c)[kDof], const float (&s)[kDof],
                                     const float (&qd)[kDof], const float (&tau)[kDof], const float (&ades)[kDof], const float (&tcap)[kDof],
                                     float (&qdd)[kDof], const P3* ext = nullptr, const WorldBody* sphere_p = nullptr, SphereLane* sphere = nullptr)
@@ -1128,6 +1167,9 @@ enum : int {
                          // The PD law tracks those anyway; a constraint joint with from_cmd set does so only here
     kWorldBody = 32,     // pnr_set_body_params: the env's moving sphere (SphereLane, under the params of WorldBody) is integrated with the
                          // joints: in every sub-step the static world's and the arm samples' forces on it, the samples' reactions in fext
+    kWorldGrip = 64,     // pnr_set_body_grip_params, with kWorldBody only: the lane's max_force (GripLane::g) > 0 holds the sphere at the
+                         // pointer's anchor point (grip_force) and switches the arm samples' contact with it off; the last sub-step's
+                         // force is stored inside that sub-step (a wave-uniform compare on the loop counter)
 };
 // .. and its operands: an option's are read only where the option is set.  The joint torques are an argument of their own (dyn_core's
 // tau_ext): with the array's address kept in a struct, the kernel's zero fill of it stops being promoted as one vector, the `0 + tau`
@@ -1143,15 +1185,18 @@ struct WorldOperands {
 // the same bits): command integration with the action latched for the next step, then nsub sub-steps of ABA + PD.
 // FORM: 0 as above (pnr_step, pnr_rollout), or kWorld with the world step's options (pnr_world_step*, World.step): the sub-steps
 // alone — no command integration, no teleport — with the operands `world` refers to.
+// `env`: the lane's env index, read by the kWorldGrip forms alone (the address of the grip's report).
 template <int PHYS, int FORM = 0>
 __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, float (&a)[kDof], float (&v)[kDof],
                                          float (&r)[kDof], float (&q)[kDof], float (&qd)[kDof], const float (&sc)[kNumLinks],
                                          const float (&fric_)[kDof], const float (&damp_)[kDof], const float (&act)[kDof],
                                          const WorldOperands* world = nullptr, const float* tau_ext = nullptr,
-                                         const WorldBody* body = nullptr, SphereLane* sphere = nullptr)
+                                         const WorldBody* body = nullptr, SphereLane* sphere = nullptr, long long env = 0)
 {
     constexpr bool WORLD = (FORM & kWorld) != 0, CMOTOR = (FORM & kWorldCMotor) != 0, TORQUE = (FORM & kWorldTorque) != 0,
-                   WRENCH = (FORM & kWorldWrench) != 0, TARGETS = (FORM & kWorldTargets) != 0, BODY = (FORM & kWorldBody) != 0;
+                   WRENCH = (FORM & kWorldWrench) != 0, TARGETS = (FORM & kWorldTargets) != 0, BODY = (FORM & kWorldBody) != 0,
+                   GRIP = (FORM & kWorldGrip) != 0;
+    static_assert(!GRIP || BODY, "the grip holds the moving sphere");
     static_assert(WORLD ? !(CMOTOR && (TORQUE || WRENCH)) : FORM == 0, "the options are the world step's; torque or wrench input with the boxed solve is not built");
     static_assert(!BODY || (TORQUE && !WRENCH && !CMOTOR && (PHYS & 1)), "the sphere is built into the torque forms, with contacts");
     if constexpr (!WORLD) {
@@ -1223,7 +1268,14 @@ __device__ __forceinline__ void dyn_core(const DynLead& in, const DynParams& D, 
             for (int i = 0; i < kDof; ++i) { c[i] = cs[i].x; s[i] = cs[i].y; }
             if constexpr (BODY) {      // every force at the state the sub-step starts from, then the sphere's own step
                 sphere_static(D, *body, *sphere);
-                aba<PHYS, false, true>(D, M, c, s, qd, tau, ades, tc, qdd, nullptr, body, sphere);
+                aba<PHYS, false, GRIP ? kSphereGrip : kSphereFree>(D, M, c, s, qd, tau, ades, tc, qdd, nullptr, body, sphere);
+                if constexpr (GRIP) {  // the report (getConstraintState): the call's last sub-step's force, by held lanes
+                    const GripLane& GL = *static_cast<const GripLane*>(sphere);
+                    if (k == D.nsub - 1 && GL.g > 0.f && GL.m > 0.f) {
+                        float* gw = static_cast<const WorldGrip*>(body)->grip + env;
+                        gw[in.n] = GL.G.x; gw[2 * in.n] = GL.G.y; gw[3 * in.n] = GL.G.z;
+                    }
+                }
                 sphere_integrate(D, *body, inv_m, *sphere);
             } else
             if constexpr (WRENCH) {

@@ -28,8 +28,10 @@ struct pnr_env_s {
     float4* state;
     float* dyn;          // dynamics-mode planar words [36][n] or null
     pnr::SceneBody* scene;    // dynamics-mode static scene bodies [kMaxScene] or null
-    pnr::WorldBody sphere;    // pnr_set_body_params: the moving sphere's buffer (words; null before the first call) and resolved params
+    pnr::WorldGrip sphere;    // pnr_set_body_params: the moving sphere's buffer (words; null before the first call) and resolved params;
+                              // pnr_set_body_grip_params: the grip's buffer (grip; null before the first call) and resolved params
     bool sphere_on;           // .. and whether the world step moves it (the kWorldBody forms)
+    bool grip_on;             // pnr_set_body_grip_params: the grip is enabled (the kWorldGrip forms; its buffer and operands are in `sphere`)
     unsigned body_queries;    // pnr_set_body_queries: which scene queries see the sphere (0: none), a host-side switch
     bool body_rgb_set;        // .. and its drawn colour, once the caller gave one (else the obstacle material's grey)
     float body_rgb[3];

@@ -607,7 +607,7 @@ __global__ __launch_bounds__(kWave) void reset_kernel(const KParams P, const Dyn
 // World.step (bullet_scene.py:273-275), the four pnr_world_step* calls: frame_skip sub-steps of the simulator and NOTHING else — no
 // command integration, reward, TimeLimit, reset or observation.  One env per lane (the phase-A shape of dyn_step_kernel); the
 // joints' motors are the per-joint table W (Joint.control_position / control_velocity, bullet_scene.py:123-155).  FORM: the
-// call's options (kWorld*, pnr_dyn.h); the host launches eight of their combinations (launch_world_step, pnr_api.hip) and no other
+// call's options (kWorld*, pnr_dyn.h); the host launches ten of their combinations (launch_world_step, pnr_api.hip) and no other
 // is instantiated.  Every load is issued before the sub-step loop, and every branch on an option's input is wave-uniform.
 //   kWorldCMotor   W holds at least one of Bullet's constraint motors (motor_constraints, pnr_dyn.h); launched only then.
 //   kWorldTorque   tau_ext [n][6], the lane's six joint torques.  PD motors only: the host refuses them next to a constraint
@@ -632,18 +632,24 @@ __global__ __launch_bounds__(kWave) void reset_kernel(const KParams P, const Dyn
 //                  behind W.  Built into two forms, both with kWorldTorque (tau_ext may be null) and PHYS 1 or 3: the plain one and
 //                  the targets one, whose joint mask rides in WorldBody (five slots: targets | tau_ext | D | W | body).  The eight
 //                  words are loaded with the other first loads; words 0-5 are stored at the end, by lanes with mass > 0 only.
+//   kWorldGrip     the grip on the sphere (pnr_set_body_grip_params; pnr_dyn.h grip_force), with kWorldBody only: two more forms x PHYS 1
+//                  and 3.  No slot of its own: the grip buffer [4][n] and the wave-uniform operands ride in the sphere's argument,
+//                  which these forms take as WorldGrip (role kArgGripBody in kArgBody's place; the forms without the grip keep the
+//                  argument list they had).  The lane's max_force is loaded with the sphere's words; words 1-3 are stored inside
+//                  the last sub-step, by held lanes only.
 // ---------------------------------------------------------------------------------
 struct NoArg {};
-enum WorldRole : int { kArgWrenches, kArgTargets, kArgTau, kArgMask, kArgD, kArgW, kArgT, kArgBody, kWorldRoles };
+enum WorldRole : int { kArgWrenches, kArgTargets, kArgTau, kArgMask, kArgD, kArgW, kArgT, kArgBody, kArgGripBody, kWorldRoles };
 template <int ROLE> using WorldRoleType = std::tuple_element_t<ROLE, std::tuple<const float*, const float*, const float*, unsigned, DynParams,
-                                                                                  JointMotorTable, LinkWrenchTable, WorldBody>>;
+                                                                                  JointMotorTable, LinkWrenchTable, WorldBody, WorldGrip>>;
 constexpr int kWorldSlots = 5;
 // (named functions of plain ints: an expression on the flag enum written into a parameter type is mangled into the kernel's name,
 // and for an unnamed enum the host and the device pass number it differently: the launch then finds no such symbol)
 constexpr bool world_has(int form, int role)
 {
     const bool tg = (form & kWorldTargets) != 0, wr = (form & kWorldWrench) != 0, bd = (form & kWorldBody) != 0;
-    if (role == kArgBody) return bd;
+    if (role == kArgBody) return bd && (form & kWorldGrip) == 0;
+    if (role == kArgGripBody) return bd && (form & kWorldGrip) != 0;
     if (role == kArgMask) return tg && !bd;
     return role == kArgD || role == kArgW || (role == kArgTau ? tg || (form & kWorldTorque) != 0 : (role == kArgWrenches || role == kArgT) ? wr : tg);
 }
@@ -678,7 +684,7 @@ __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restri
     const DynParams& D = world_arg<FORM, kArgD>(s0, s1, s2, s3, s4);
     const JointMotorTable& W = world_arg<FORM, kArgW>(s0, s1, s2, s3, s4);
     constexpr bool TORQUE = (FORM & kWorldTorque) != 0, WRENCH = (FORM & kWorldWrench) != 0, TARGETS = (FORM & kWorldTargets) != 0,
-                   BODY = (FORM & kWorldBody) != 0;
+                   BODY = (FORM & kWorldBody) != 0, GRIP = (FORM & kWorldGrip) != 0;
     const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
     if (e >= n) return;
     float a[kDof], v[kDof], r[kDof], q[kDof], qd[kDof], sc[kNumLinks], fric[kDof], damp[kDof], act[kDof], tx[kDof];
@@ -699,11 +705,13 @@ __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restri
     }
 #pragma unroll
     for (int l = 0; l < kNumLinks; ++l) sc[l] = RAND ? dyn[(long long)(kDynScale + l) * n + e] : 1.0f;
-    [[maybe_unused]] SphereLane S;
+    constexpr int kBodyRole = GRIP ? kArgGripBody : kArgBody;      // the sphere's argument: WorldGrip with the grip, else WorldBody
+    [[maybe_unused]] std::conditional_t<GRIP, GripLane, SphereLane> S;
     if constexpr (BODY) {
-        const float* bw = world_arg<FORM, kArgBody>(s0, s1, s2, s3, s4).words + e;
+        const float* bw = world_arg<FORM, kBodyRole>(s0, s1, s2, s3, s4).words + e;
         S.x = {bw[0], bw[n], bw[2 * n]}; S.v = {bw[3 * n], bw[4 * n], bw[5 * n]};
         S.m = bw[6 * n]; S.r = bw[7 * n];
+        if constexpr (GRIP) S.g = world_arg<FORM, kBodyRole>(s0, s1, s2, s3, s4).grip[e];
     }
     WrenchLane XL;
     if constexpr (WRENCH) {
@@ -720,7 +728,7 @@ __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restri
     if constexpr (TARGETS) {
         const float tp[kDof] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y}, tv[kDof] = {g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
         unsigned mask;
-        if constexpr (BODY) mask = world_arg<FORM, kArgBody>(s0, s1, s2, s3, s4).joint_mask;
+        if constexpr (BODY) mask = world_arg<FORM, kBodyRole>(s0, s1, s2, s3, s4).joint_mask;
         else mask = world_arg<FORM, kArgMask>(s0, s1, s2, s3, s4);
 #pragma unroll
         for (int i = 0; i < kDof; ++i) {
@@ -733,16 +741,27 @@ __global__ __launch_bounds__(kWave) void dyn_world_kernel(const float4* __restri
     const LinkWrenchTable* X = nullptr;
     if constexpr (WRENCH) X = &world_arg<FORM, kArgT>(s0, s1, s2, s3, s4);
     const WorldOperands world = {W, X, XL};
-    if constexpr (BODY) dyn_core<PHYS, kWorld | FORM>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &world, tx, &world_arg<FORM, kArgBody>(s0, s1, s2, s3, s4), &S);
+    if constexpr (BODY) dyn_core<PHYS, kWorld | FORM>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &world, tx, &world_arg<FORM, kBodyRole>(s0, s1, s2, s3, s4), &S, e);
     else dyn_core<PHYS, kWorld | FORM>(lead, D, a, v, r, q, qd, sc, fric, damp, act, &world, tx);
 #pragma unroll
     for (int i = 0; i < kDof; ++i) { dyn[(long long)i * n + e] = q[i]; dyn[(long long)(kDynQd + i) * n + e] = qd[i]; }
     if constexpr (BODY) {
         if (S.m > 0.f) {               // an env without a sphere keeps its eight words as they are
-            float* bw = world_arg<FORM, kArgBody>(s0, s1, s2, s3, s4).words + e;
+            float* bw = world_arg<FORM, kBodyRole>(s0, s1, s2, s3, s4).words + e;
             bw[0] = S.x.x; bw[n] = S.x.y; bw[2 * n] = S.x.z; bw[3 * n] = S.v.x; bw[4 * n] = S.v.y; bw[5 * n] = S.v.z;
         }
     }
+}
+
+// pnr_set_body_grip: the caller's max_force into word 0 of the handle's grip buffer and zeros into the reported force (words 1-3),
+// for every env or the masked ones (the device-side "grip the envs that just came within reach")
+__global__ void grip_set_kernel(float* __restrict__ dst, const float* __restrict__ max_force, const uint8_t* __restrict__ mask, long long n)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n || (mask && !mask[e])) return;
+    dst[e] = max_force[e];
+#pragma unroll
+    for (int w = 1; w < PNR_BODY_GRIP_WORDS; ++w) dst[(long long)w * n + e] = 0.f;
 }
 
 // pnr_set_body_state: the caller's eight words per env into the handle's sphere buffer, for every env or the masked ones (the

@@ -99,6 +99,8 @@ class PioneerKinematicEnv(compat.GymEnv):
                 self._vec.set_body_state(old.body_state())
                 if old._body_queries is not None:                          # .. and which queries see it
                     self._vec.set_body_queries(**old._body_queries)
+                if old._grip_on:                                           # .. and the grip: its params and each env's max_force
+                    self._vec.set_body_grip(old._grip_params, max_force=old.body_grip()[:, 0])
         old.close()
 
     # -- pickling: by constructor arguments, like gym.utils.EzPickle (pioneer_knm_env.py:38, :51) --

@@ -378,6 +378,7 @@ class Scene:
             j.item = self.links_by_name[jd.child]                              # the joint's child link (bullet_env.py:120-126)
         # kinematic mode: the simulator's joints (q | qd) as act() leaves them in Bullet; see the module docstring
         self._bullet = torch.zeros((1, 12), dtype=torch.float32, device=env._vec.device)
+        self._grip: Optional[int] = None                                       # create_constraint's id while the grip exists
 
     def sync_from_env(self):
         """What act() does to the Bullet client on every step (pioneer_knm_env.py:148): joints at the env's r, velocity 0."""
@@ -439,6 +440,43 @@ class Scene:
 
     def create_body_plane(self, name, mass, normal, position, orientation):                                   # :219-227
         self._create(Item(name, "plane", position, orientation, True, normal, GROUND_RGBA), mass, scene_plane(normal, position, orientation))
+
+    # -- the grip (pybullet.createConstraint JOINT_POINT2POINT / changeConstraint / removeConstraint / getConstraintState) ----
+    _GRIP_ID = 1                                                               # the one constraint's userConstraintUniqueId
+
+    def create_constraint(self, parent, child, max_force: float, anchor=None, direction=None) -> int:
+        """createConstraint(arm, pointerLink, body, -1, JOINT_POINT2POINT, ...) + changeConstraint(maxForce): the moving sphere
+        held at a point of ``robot:pointer`` (``PioneerVectorEnv.set_body_grip``; a suction or magnet gripper).  ``parent`` is
+        ``links_by_name["robot:pointer"]`` and ``child`` the created moving sphere: nothing else is modelled.  ``anchor`` /
+        ``direction``: the grip's params (None: the defaults, the sphere tangent to the pointer's own sphere)."""
+        assert parent is self.links_by_name["robot:pointer"], "the grip is modelled on link robot:pointer only"
+        assert isinstance(child, BodyItem) and child is self.moving_body(), "the grip holds the created moving sphere (create_body_sphere with mass > 0) only"
+        assert self._grip is None, "the engine models one grip per env: there is one already"
+        assert float(max_force) > 0.0, "a constraint with max_force <= 0 holds nothing"
+        params = {k: tuple(map(float, v)) for k, v in (("anchor", anchor), ("direction", direction)) if v is not None}
+        self._env._vec.set_body_grip(params, max_force=float(max_force))
+        self._grip = self._GRIP_ID
+        return self._grip
+
+    def _check_constraint(self, constraint_id: int):
+        assert self._grip is not None and constraint_id == self._grip, f"no such constraint: {constraint_id}"
+
+    def remove_constraint(self, constraint_id: int):
+        """removeConstraint: the sphere is released (max_force 0) and follows the sphere's own law again, arm contacts included."""
+        self._check_constraint(constraint_id)
+        self._env._vec.set_body_grip(max_force=0.0)
+        self._grip = None
+
+    def change_constraint(self, constraint_id: int, max_force: float):
+        """changeConstraint(maxForce)"""
+        self._check_constraint(constraint_id)
+        assert float(max_force) > 0.0, "a constraint with max_force <= 0 holds nothing: remove_constraint releases"
+        self._env._vec.set_body_grip(max_force=float(max_force))
+
+    def constraint_state(self, constraint_id: int) -> Tuple[float, float, float]:
+        """getConstraintState: the world-frame force on the sphere in the last sub-step of the last ``world.step()``"""
+        self._check_constraint(constraint_id)
+        return tuple(map(float, self._env._vec.body_grip()[0, 1:4].double().cpu().numpy()))
 
     def render_bodies(self):
         """The created bodies as render_frames draws them: (SceneBody, rgba) of every item but the target."""

@@ -76,6 +76,7 @@ class PioneerVectorEnv:
         self._h = h
         self._seed = seed
         self._body_on, self._body_params = False, None      # set_body: the moving sphere is enabled, under these params
+        self._grip_on, self._grip_params = False, None      # set_body_grip: the grip is enabled, under these params
         self._body_queries = None                           # set_body_queries' arguments, once called (render: render_frames asks pnr_render_bodies)
 
         self.feature_major_obs = self.engine_config.obs_layout == "feature_major"
@@ -368,6 +369,82 @@ class PioneerVectorEnv:
         m = None if mask is None else self._in(torch.as_tensor(mask).to(torch.uint8), (n,), torch.uint8, "mask")
         self._chk(self.lib.pnr_set_body_state(self._h, _ptr(w), _ptr(m), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()  # `w` and `m` are temporaries
+
+    # -- the grip on the moving sphere ----------------------------------------------------
+    _GRIP_FIELDS = ("anchor", "direction", "grip_kp", "grip_kd")
+
+    def _grip_params_struct(self, params):
+        p = _lib.PnrBodyGripParams()
+        _lib.check(self.lib.pnr_body_grip_params_default(p))
+        for k, v in (params or {}).items():
+            if k not in self._GRIP_FIELDS:
+                raise AssertionError(f"set_body_grip: unknown parameter {k!r}")
+            if k in ("anchor", "direction"):
+                v = tuple(float(c) for c in v)
+                assert len(v) == 3, f"set_body_grip: {k} is a 3-vector"
+                setattr(p, k, (C.c_float * 3)(*v))
+            else:
+                setattr(p, k, float(v))
+        return p
+
+    def set_body_grip(self, params=None, *, max_force=None, mask=None):
+        """The grip: each env's moving sphere held at a point of link ``robot:pointer`` by a soft point-to-point constraint with a
+        force cap (pnr_set_body_grip_params + pnr_set_body_grip; PyBullet's createConstraint(JOINT_POINT2POINT) /
+        changeConstraint(maxForce) / removeConstraint; include/pioneer_amd.h states the law).  ``params``: a dict of ``anchor``
+        (0, 0, 0), ``direction`` (the unit vector along the tip offset: the held sphere sits tangent to the pointer's sample
+        sphere; (0, 0, 0): the anchor is a plain point of the link), ``grip_kp``, ``grip_kd`` (default: the sphere's contact
+        gains); ``False`` disables the grip (the buffer is kept and ``world_step`` runs the kernels without it).  ``max_force``: a
+        number or ``[N]``, each env's force cap; <= 0 releases.  ``mask`` (``[N]`` bool / uint8 on any device): only these envs'
+        words are written — "grip the envs that just came within reach".  A gripped env's sphere takes no contact from the arm;
+        the static world still holds it.  Needs ``set_body`` first; the first call allocates and waits for the buffer's zero
+        fill.  ``contacts()`` does not know the grip and keeps reporting the overlap of a held sphere."""
+        self._check_handle()
+        if params is False:
+            self._chk(self.lib.pnr_set_body_grip_params(self._h, None))
+            self._grip_on = False
+            return
+        if params is None and self._grip_on:                   # a later call without params keeps them
+            params = self._grip_params
+        p = self._grip_params_struct(params)
+        self._chk(self.lib.pnr_set_body_grip_params(self._h, p))
+        self._grip_on, self._grip_params = True, dict(params or {})
+        if max_force is None:
+            return
+        n = self.num_envs
+        f = torch.as_tensor(np.asarray(max_force.detach().cpu() if isinstance(max_force, torch.Tensor) else max_force), dtype=torch.float32)
+        if f.numel() not in (1, n):
+            raise AssertionError("set_body_grip: max_force must be one value or one per env")
+        f = f.reshape(-1).expand(n).contiguous().to(self.device)
+        m = None if mask is None else self._in(torch.as_tensor(mask).to(torch.uint8), (n,), torch.uint8, "mask")
+        self._chk(self.lib.pnr_set_body_grip(self._h, _ptr(f), _ptr(m), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()  # `f` and `m` are temporaries
+
+    def body_grip(self):
+        """The grips' state, float32 ``[N, 4]`` on the device: max_force | the world-frame force on the sphere in the last sub-step
+        of the last ``world_step`` [3] (pnr_get_body_grip; getConstraintState).  Zero force for an env that was not gripped."""
+        self._check_handle()
+        w = self._new((_lib.BODY_GRIP_WORDS, self.num_envs))
+        self._chk(self.lib.pnr_get_body_grip(self._h, _ptr(w), self._stream()))
+        return w.T
+
+    def grip_anchor(self):
+        """The world position ``[N, 3]`` (float32, on the device) of each env's anchor point, where the grip holds the sphere's
+        centre: the pointer link's pose (``link_states``) applied to ``anchor + (radius + pointer_radius) * direction`` with the
+        env's radius (``body_state``) and the grip's params (the defaults before ``set_body_grip``).  Plain torch: it lets a caller
+        write ``mask = (body_state()[:, :3] - grip_anchor()).norm(dim=1) < reach`` without restating the geometry."""
+        self._check_handle()
+        p = self._grip_params_struct(self._grip_params if self._grip_on else None)
+        anchor = torch.tensor(p.anchor[:], dtype=torch.float32, device=self.device)
+        direction = torch.tensor(p.direction[:], dtype=torch.float32, device=self.device)
+        if float(direction.norm()) > 0:
+            direction = direction / direction.norm()
+        link = self.link_states()[:, _lib.NUM_LINKS - 1]                              # robot:pointer
+        pos, (x, y, z, w) = link[:, 0:3], link[:, 3:7].unbind(dim=1)
+        R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                         2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                         2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+        reach = self.body_state()[:, 7:8] + float(self.engine_config.pointer_radius)
+        return pos + torch.einsum("nij,nj->ni", R, anchor[None, :] + reach * direction[None, :])
 
     def inverse_dynamics(self, joint_accel=None, joint_state=None, gravity=True, joint_losses=False, out=None):
         """calculateInverseDynamics of every env, one launch (pnr_inverse_dynamics): float32 ``[N, 6]`` joint torques
@@ -751,18 +828,21 @@ class PioneerVectorEnv:
 
     def state_dict(self):
         """Decoded state (numpy, host): a, v, r [N,6]; target [N,3]; potential, step_index, episode [N]; with a moving sphere
-        enabled (``set_body``) also body [N,8]."""
+        enabled (``set_body``) also body [N,8], with the grip enabled (``set_body_grip``) also grip [N,4]."""
         w = self.get_state().cpu().numpy().view(np.uint32)
         f = w.view(np.float32)
         d = dict(a=f[0:6].T.copy(), v=f[6:12].T.copy(), r=f[12:18].T.copy(), target=f[18:21].T.copy(),
                  potential=f[21].copy(), step_index=w[22].copy(), episode=w[23].copy())
         if self._body_on:
             d["body"] = self.body_state().cpu().numpy()
+        if self._grip_on:
+            d["grip"] = self.body_grip().cpu().numpy()
         return d
 
     def load_state_dict(self, d):
         """``state_dict``'s inverse: the command state, and the spheres' where the dict carries a ``body`` key (which needs
-        ``set_body`` first: the params are not part of the state)."""
+        ``set_body`` first: the params are not part of the state), and every env's grip word ``max_force`` where it carries a
+        ``grip`` key (``set_body_grip`` first; the reported force restarts at zero)."""
         w = np.zeros((_lib.STATE_WORDS, self.num_envs), dtype=np.uint32)
         f = w.view(np.float32)
         f[0:6], f[6:12], f[12:18], f[18:21] = (np.asarray(d[k], dtype=np.float32).T for k in ("a", "v", "r", "target"))
@@ -771,6 +851,8 @@ class PioneerVectorEnv:
         self.set_state(torch.from_numpy(w.view(np.int32)))
         if "body" in d:
             self.set_body_state(d["body"])
+        if "grip" in d:
+            self.set_body_grip(max_force=np.asarray(d["grip"])[:, 0])
 
     def __reduce__(self):
         """Pickled by constructor arguments (a fresh batch, like the reference's EzPickle envs);
