@@ -50,7 +50,8 @@ extern "C" {
  *      pnr_contact_params_default, pnr_get_contacts, pnr_ik_pose_params_default, pnr_solve_ik_pose, pnr_ray_params_default,
  *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets, pnr_body_params_default,
  *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state, pnr_render_bodies, pnr_set_body_queries,
- *      pnr_render_cameras, pnr_body_grip_params_default, pnr_set_body_grip_params, pnr_set_body_grip, pnr_get_body_grip */
+ *      pnr_render_cameras, pnr_body_grip_params_default, pnr_set_body_grip_params, pnr_set_body_grip, pnr_get_body_grip,
+ *      pnr_ik_multi_params_default, pnr_solve_ik_multi */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -445,7 +446,7 @@ int pnr_solve_ik(pnr_handle h, const pnr_ik_params* p, const float* target_pos, 
  * of a solution whose |q5| >= 0.4 converge 100 % in <= 8 iterations (99 % in <= 4); AXIS-mode pointing along world +x anywhere
  * in the box (15, -8, 2) .. (22, 8, 6) converges 100 % from the rest pose in <= 6 iterations.  From the rest pose to the full
  * pose of random joints at 0.8-0.9 of the limits 88 % converge (the rest stop in local minima at joint limits or on the other
- * wrist branch; multi-start search is the caller's); with lambda = 1 and no error term (pnr_solve_ik's damping) only 74-76 % do,
+ * wrist branch; pnr_solve_ik_multi searches from several starts); with lambda = 1 and no error term (pnr_solve_ik's damping) only 74-76 % do,
  * and 98 % of the near starts.  orientation_weight 1, 3, 10, 30 give 94, 91, 88, 89 % from the rest pose and 100 % near.
  *
  * PNR_ERR_INVALID, nothing launched and no output touched, for: a null handle, params, q_out or target_quat, a wrong
@@ -476,6 +477,93 @@ typedef struct pnr_ik_pose_params {
 int pnr_ik_pose_params_default(pnr_ik_pose_params* p);
 int pnr_solve_ik_pose(pnr_handle h, const pnr_ik_pose_params* p, const float* target_pos, const float* target_quat, const float* q_init,
                       float* q_out, float* residual_out, float* angle_out, int32_t* iterations_out, void* stream);
+
+/*
+ * Multi-start inverse kinematics for every env, one launch: S descents per env from S starts, and of the solutions found the one
+ * nearest to a posture.  Each start runs the law of pnr_solve_ik (task PNR_IK_TASK_POSITION) or of pnr_solve_ik_pose (task
+ * PNR_IK_TASK_POSE: its FULL mode; PNR_IK_TASK_AXIS: its AXIS mode) exactly as stated above, with the one damping
+ *
+ *     lambda^2 = damping^2 + error_damping (|e_p|^2 + w^2 angle^2)                 (the position task has no orientation rows:
+ *                                                                                  angle = 0, and its default error_damping is 0)
+ *
+ * A start's iterates do not depend on S, on the env's other starts (policy BEST) or on any other env, bit for bit: start k of
+ * an S-start call ends where a one-start call from the same joints ends.
+ *
+ *   starts       num_starts = S in {1, 2, 4, 8, 16, 32, 64}.  `starts` is [S][6] float32, one table for all envs, or, with
+ *                starts_per_env != 0, [num_envs][S][6]; NULL only with S = 1 (start 0 is then q_init, else the rest pose).
+ *                q_init [num_envs][6] or NULL: where given it replaces start 0 of every env.  Every start is clamped into the
+ *                joint limits before the first iteration.
+ *   converged    a start is converged when the pose it ends at is within the tolerances (float32; the position task: the distance)
+ *   selection    per env, over its S starts when the env stops: the smallest (not converged, cost, start index),
+ *                lexicographically.  cost of a converged start: sum_j (q_j - q_ref_j)^2, q_ref [num_envs][6] or NULL = the env's
+ *                clamped start 0; of a start that is not converged: |e_p| + w angle (the position task: |e_p|).  A cost that is
+ *                not finite counts as +inf, so the order is total: a NaN target selects start 0, with non-finite residuals.
+ *   policy       PNR_IK_MULTI_BEST: every start runs until it converges or max_iterations is reached; the winner is the converged
+ *                start nearest to q_ref.  PNR_IK_MULTI_FIRST: at the convergence check in which any start of an env converges
+ *                all of that env's starts freeze; the winner is the nearest of the starts that converged in that check (no start
+ *                converges: as BEST).  FIRST is there for the time of a wave, which under BEST nearly always holds a lane that
+ *                runs max_iterations.
+ *   outputs      of the winner: q_out [num_envs][6] (8-byte aligned, required), and optionally residual_out, angle_out (0 in the
+ *                position task), iterations_out, start_out (int32: the winner's start index), each [num_envs];
+ *                converged_out [num_envs] int32 or NULL: how many of the env's starts are converged when it stops (0: none).
+ *                Per start, each optional: all_q [num_envs][S][6] (8-byte aligned), all_residual, all_angle, all_iterations
+ *                [num_envs][S] — every branch found.  Under FIRST a start frozen by another's convergence reports the
+ *                iterations it made.  Nothing past these extents is written.
+ *
+ * PNR_ERR_INVALID, nothing launched and no output touched (the message names the field), for: everything pnr_solve_ik (position
+ * task) or pnr_solve_ik_pose (pose and axis tasks) refuses, a negative or non-finite error_damping in any task, an unknown task
+ * or policy, a num_starts outside the seven values, NULL starts with num_starts > 1, NULL target_quat in a pose or axis task, a
+ * NULL or wrongly sized buffers struct, misaligned pointers (q_out and all_q 8 bytes, the others 4).  float32 arithmetic,
+ * asynchronous on `stream`, no allocation, no synchronisation: capturable into a graph.
+ */
+enum pnr_ik_task {
+    PNR_IK_TASK_POSITION = 0,   /* pnr_solve_ik's 3 x 3 law */
+    PNR_IK_TASK_POSE = 1,       /* pnr_solve_ik_pose, PNR_IK_ORIENT_FULL */
+    PNR_IK_TASK_AXIS = 2        /* pnr_solve_ik_pose, PNR_IK_ORIENT_AXIS */
+};
+enum pnr_ik_multi_policy {
+    PNR_IK_MULTI_BEST = 0,      /* the nearest of all converged starts */
+    PNR_IK_MULTI_FIRST = 1      /* the nearest of the starts that converge first */
+};
+typedef struct pnr_ik_multi_params {
+    uint32_t struct_size;       /* sizeof(pnr_ik_multi_params) */
+    int32_t  task;              /* pnr_ik_task */
+    int32_t  policy;            /* pnr_ik_multi_policy; default PNR_IK_MULTI_BEST */
+    int32_t  num_starts;        /* S: 1, 2, 4, 8, 16, 32 or 64; default 8 */
+    int32_t  starts_per_env;    /* 0 (default): `starts` is [S][6]; else [num_envs][S][6] */
+    int32_t  link;              /* 0..10; default 10 (robot:pointer) */
+    double   local_point[3];    /* a point in the link's frame; default 0 */
+    int32_t  max_iterations;    /* 1..1024; default 32 */
+    int32_t  reserved;
+    double   local_axis[3];     /* axis task: as pnr_ik_pose_params.local_axis; default (1, 0, 0) */
+    double   damping;           /* > 0; default 1.0 (position), 0.03 (pose, axis) */
+    double   error_damping;     /* >= 0; default 0 (position), 0.01 (pose, axis) */
+    double   orientation_weight; /* w > 0, pose and axis tasks; default 10 */
+    double   max_step;          /* > 0, rad; default 0.5 */
+    double   tolerance;         /* >= 0, length; default 1e-3 */
+    double   angle_tolerance;   /* >= 0, rad, pose and axis tasks; default 1e-3 */
+} pnr_ik_multi_params;
+typedef struct pnr_ik_multi_buffers {
+    uint32_t struct_size;       /* sizeof(pnr_ik_multi_buffers) */
+    uint32_t reserved;
+    const float* target_pos;    /* [num_envs][3], or NULL = each env's own target (as pnr_solve_ik) */
+    const float* target_quat;   /* [num_envs][4] (x, y, z, w); pose and axis tasks, not read in the position task */
+    const float* starts;        /* [S][6] or [num_envs][S][6]; NULL only with num_starts 1 */
+    const float* q_init;        /* [num_envs][6] or NULL */
+    const float* q_ref;         /* [num_envs][6] or NULL */
+    float*   q_out;             /* [num_envs][6], 8-byte aligned */
+    float*   residual_out;      /* [num_envs] or NULL */
+    float*   angle_out;         /* [num_envs] or NULL */
+    int32_t* iterations_out;    /* [num_envs] or NULL */
+    int32_t* start_out;         /* [num_envs] or NULL */
+    int32_t* converged_out;     /* [num_envs] or NULL */
+    float*   all_q;             /* [num_envs][S][6], 8-byte aligned, or NULL */
+    float*   all_residual;      /* [num_envs][S] or NULL */
+    float*   all_angle;         /* [num_envs][S] or NULL */
+    int32_t* all_iterations;    /* [num_envs][S] or NULL */
+} pnr_ik_multi_buffers;
+int pnr_ik_multi_params_default(pnr_ik_multi_params* p, int32_t task);
+int pnr_solve_ik_multi(pnr_handle h, const pnr_ik_multi_params* p, const pnr_ik_multi_buffers* b, void* stream);
 
 /*
  * calculateInverseDynamics for every env, one launch: the joint torques of

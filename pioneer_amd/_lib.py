@@ -136,6 +136,27 @@ class PnrIkPoseParams(C.Structure):
                 ("angle_tolerance", C.c_double)]
 
 
+IK_TASK_POSITION, IK_TASK_POSE, IK_TASK_AXIS = 0, 1, 2      # pnr_ik_multi_params.task
+IK_MULTI_BEST, IK_MULTI_FIRST = 0, 1                         # pnr_ik_multi_params.policy
+IK_MULTI_STARTS = (1, 2, 4, 8, 16, 32, 64)                   # pnr_ik_multi_params.num_starts
+
+
+class PnrIkMultiParams(C.Structure):
+    """pnr_ik_multi_params of include/pioneer_amd.h (pnr_solve_ik_multi's task, policy, starts and the per-start law's parameters)."""
+    _fields_ = [("struct_size", C.c_uint32), ("task", C.c_int32), ("policy", C.c_int32), ("num_starts", C.c_int32),
+                ("starts_per_env", C.c_int32), ("link", C.c_int32), ("local_point", C.c_double * 3), ("max_iterations", C.c_int32),
+                ("reserved", C.c_int32), ("local_axis", C.c_double * 3), ("damping", C.c_double), ("error_damping", C.c_double),
+                ("orientation_weight", C.c_double), ("max_step", C.c_double), ("tolerance", C.c_double),
+                ("angle_tolerance", C.c_double)]
+
+
+class PnrIkMultiBuffers(C.Structure):
+    """pnr_ik_multi_buffers of include/pioneer_amd.h (pnr_solve_ik_multi's device pointers: inputs, the winner's and the per-start outputs)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(name, C.c_void_p) for name in (
+        "target_pos", "target_quat", "starts", "q_init", "q_ref", "q_out", "residual_out", "angle_out", "iterations_out", "start_out",
+        "converged_out", "all_q", "all_residual", "all_angle", "all_iterations")]
+
+
 class PnrConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
@@ -240,6 +261,8 @@ SIGNATURES = {
     "pnr_solve_ik": (C.c_int, [_VP, C.POINTER(PnrIkParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pnr_ik_pose_params_default": (C.c_int, [C.POINTER(PnrIkPoseParams)]),
     "pnr_solve_ik_pose": (C.c_int, [_VP, C.POINTER(PnrIkPoseParams)] + [_VP] * 8),
+    "pnr_ik_multi_params_default": (C.c_int, [C.POINTER(PnrIkMultiParams), C.c_int32]),
+    "pnr_solve_ik_multi": (C.c_int, [_VP, C.POINTER(PnrIkMultiParams), C.POINTER(PnrIkMultiBuffers), _VP]),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
     "pnr_render_bodies": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_render_cameras": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
@@ -280,7 +303,7 @@ _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr
 UNITS = {
     # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (126, 96 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
-    # the query entry points of the C ABI and their kernels (47: the three scene queries have a per-env-world form each, pnr_query.h; the renderer a per-env-camera form too)
+    # the query entry points of the C ABI and their kernels (49: the three scene queries have a per-env-world form each, pnr_query.h; the renderer a per-env-camera form too)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",
                         "pnr_jointstate.h", "pnr_contacts.h", "pnr_rays.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",

@@ -1,9 +1,10 @@
-// pnr_ik.h — pnr_get_jacobian, pnr_solve_ik and pnr_solve_ik_pose: the Jacobian of a point of a URDF link (PyBullet's
+// pnr_ik.h — pnr_get_jacobian, pnr_solve_ik, pnr_solve_ik_pose and pnr_solve_ik_multi: the Jacobian of a point of a URDF link (PyBullet's
 // calculateJacobian), position-only damped-least-squares inverse kinematics (calculateInverseKinematics without an orientation)
-// and pose inverse kinematics (with targetOrientation: a full orientation or one axis to point) for every env, one launch each.
+// and pose inverse kinematics (with targetOrientation: a full orientation or one axis to point) for every env, one launch each;
+// multi-start inverse kinematics (either law from S starts per env, the nearest solution found) at the end of the file.
 // Included by pnr_queries.hip only, whose code object holds no step kernel.
 //
-// Shape of all: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  The host resolves (link,
+// Shape of all but the multi-start kernels: one env per lane, one 64-lane wave per workgroup (pnr_query.h).  The host resolves (link,
 // local_point) into the moving body that carries the link and the point's offset in that body's frame; both arrive as
 // kernel arguments, so every `J <= body` test below is a scalar branch.
 //
@@ -336,6 +337,274 @@ __global__ __launch_bounds__(kWave) void ik_pose_kernel(const IkPoseArgs A)
     if (A.residual) A.residual[e] = dist;
     if (A.angle) A.angle[e] = angle;
     if (A.iterations) A.iterations[e] = iters;
+}
+
+// ---- multi-start inverse kinematics (pnr_solve_ik_multi) ---------------------------------------------------------------------
+// One START per lane: lane = g S + s is start s of the wave's env g, S = 1 << log2s a wave-uniform runtime argument (one kernel
+// per system size, none per S: a start's arithmetic is the same code whatever S is, so start k of an S-start call ends bit for bit
+// where a one-start call from the same joints ends).  A workgroup is one wave of 64 / S envs; thread t of the grid is start
+// t & (S - 1) of env t >> log2s, which is also its place in the per-start outputs.  The per-iteration steps below are the two
+// solves of ik_kernel / ik_pose_kernel restated as functions (those two kernels keep their own text: calling the functions from
+// them changed their device code), with the one damping lambda^2 = damping^2 + error_damping (|e_p|^2 +
+// w^2 angle^2).  Lanes freeze by selects; policy FIRST freezes a whole env from the ballot of the lanes still running, masked to the
+// lane's group.  After the loop the env's winner is the smallest (not converged, cost, start) of a butterfly of log2s
+// __shfl_xor exchanges (ds_bpermute: no LDS is allocated), which leaves every lane of the group with the same winner; the
+// winner's lane stores the env's record.
+struct IkMultiArgs {
+    const float* target;       // [n][3], or null: the env's own target (state words 18-20)
+    const float4* state;       // the handle's state planes (read only when target is null)
+    const float* quat;         // [n][4] x, y, z, w (the pose kernel only)
+    const float* starts;       // [S][6], per_env: [n][S][6]; null (S = 1 only): start 0 is q_init or the rest pose
+    const float* q_init;       // [n][6] or null: replaces start 0
+    const float* q_ref;        // [n][6] or null: the env's clamped start 0
+    float* q_out;              // [n][6], 8-byte aligned: the winner's
+    float* residual;           // [n] or null
+    float* angle;              // [n] or null
+    int* iterations;           // [n] or null
+    int* start_out;            // [n] or null: the winner's start
+    int* converged;            // [n] or null: converged starts of the env
+    float* all_q;              // [n][S][6], 8-byte aligned, or null
+    float* all_residual;       // [n][S] or null
+    float* all_angle;          // [n][S] or null
+    int* all_iterations;       // [n][S] or null
+    long long n;
+    ChainPoint point;
+    int log2s, per_env, first; // first: policy FIRST
+    int max_iter, axis_mode;
+    V3 axis;
+    float damping2, error_damping, weight, max_step, tol, angle_tol;
+};
+
+// start s of env e, clamped into the limits (s = 0: q_init where given; no table: the rest pose)
+__device__ __forceinline__ void ik_multi_start(const IkMultiArgs& A, const long long e, const int s, float (&q)[kDof])
+{
+    const float* row = nullptr;
+    if (s == 0 && A.q_init) row = A.q_init + kDof * e;
+    else if (A.starts) row = A.starts + kDof * ((A.per_env ? (e << A.log2s) : 0ll) + s);
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) q[i] = row ? row[i] : 0.f;
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        q[J] = fminf(fmaxf(q[J], limit_lo(J)), limit_hi(J));
+    });
+}
+
+// dq = J^T (J J^T + lambda^2 I)^-1 err for the three linear rows (ik_kernel's solve); big = max_j |dq_j|
+__device__ __forceinline__ void ik_position_step(const V3 (&lin)[kDof], const V3& err, const float lambda2, float (&dq)[kDof], float& big)
+{
+    float a00 = lambda2, a01 = 0.f, a02 = 0.f, a11 = lambda2, a12 = 0.f, a22 = lambda2;
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        const V3 g = lin[J];
+        a00 += g.x * g.x; a01 += g.x * g.y; a02 += g.x * g.z;
+        a11 += g.y * g.y; a12 += g.y * g.z; a22 += g.z * g.z;
+    });
+    const float i0 = fast_rcp(a00);
+    const float l10 = a01 * i0, l20 = a02 * i0;
+    const float d1 = a11 - l10 * a01, u12 = a12 - l20 * a01;
+    const float i1 = fast_rcp(d1);
+    const float l21 = u12 * i1;
+    const float d2 = a22 - l20 * a02 - l21 * u12;
+    const float i2 = fast_rcp(d2);
+    const float z0 = err.x, z1 = err.y - l10 * z0, z2 = err.z - l20 * z0 - l21 * z1;
+    const float y2 = z2 * i2, y1 = z1 * i1 - l21 * y2, y0 = z0 * i0 - l10 * y1 - l20 * y2;
+    const V3 y = {y0, y1, y2};
+    big = 0.f;
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        dq[J] = dot(lin[J], y);
+        big = fmaxf(big, fabsf(dq[J]));
+    });
+}
+
+// the same for the 6 x 6 system e = [err ; w e_o], J = [lin ; w ang] (ik_pose_kernel's solve: L D L^T, pivots held at >= lambda^2);
+// sv, sn, angle: the sine vector of the rotation still to make, its length and the angle
+__device__ __forceinline__ void ik_pose_step(const V3 (&lin)[kDof], const V3 (&ang)[kDof], const V3& err, const float dist2, const V3& sv,
+                                             const float sn, const float angle, const float weight, const float damping2,
+                                             const float error_damping, float (&dq)[kDof], float& big)
+{
+    constexpr int kPose = 6, kTriN = kPose * (kPose + 1) / 2;
+    const float wa = weight * angle;
+    const float ko = wa * fast_rcp(fmaxf(sn, kIkSineFloor));
+    const float er[kPose] = {err.x, err.y, err.z, ko * sv.x, ko * sv.y, ko * sv.z};
+    const float lambda2 = damping2 + error_damping * (dist2 + wa * wa);
+    float g[kDof][kPose];
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        g[J][0] = lin[J].x; g[J][1] = lin[J].y; g[J][2] = lin[J].z;
+        g[J][3] = weight * ang[J].x; g[J][4] = weight * ang[J].y; g[J][5] = weight * ang[J].z;
+    });
+    float a[kTriN];
+    static_for<kPose>([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        static_for<I + 1>([&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            float sum = I == K ? lambda2 : 0.f;
+            static_for<kDof>([&](auto jc) { constexpr int J = decltype(jc)::value; sum += g[J][I] * g[J][K]; });
+            a[kLow<I, K>] = sum;
+        });
+    });
+    float u[kTriN], l[kTriN], inv[kPose];                                // u_ik = l_ik d_k
+    static_for<kPose>([&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        float d = a[kLow<K, K>];
+        static_for<K>([&](auto mc_) { constexpr int M = decltype(mc_)::value; d -= l[kLow<K, M>] * u[kLow<K, M>]; });
+        inv[K] = fast_rcp(fmaxf(d, lambda2));
+        static_for<kPose>([&](auto ic) {
+            constexpr int I = decltype(ic)::value;
+            if constexpr (I > K) {
+                float t = a[kLow<I, K>];
+                static_for<K>([&](auto mc_) { constexpr int M = decltype(mc_)::value; t -= l[kLow<I, M>] * u[kLow<K, M>]; });
+                u[kLow<I, K>] = t;
+                l[kLow<I, K>] = t * inv[K];
+            }
+        });
+    });
+    float z[kPose], y[kPose];
+    static_for<kPose>([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        z[I] = er[I];
+        static_for<I>([&](auto mc_) { constexpr int M = decltype(mc_)::value; z[I] -= l[kLow<I, M>] * z[M]; });
+    });
+    static_for<kPose>([&](auto ic) {
+        constexpr int I = kPose - 1 - decltype(ic)::value;
+        y[I] = z[I] * inv[I];
+        static_for<kPose>([&](auto mc_) {
+            constexpr int M = decltype(mc_)::value;
+            if constexpr (M > I) y[I] -= l[kLow<M, I>] * y[M];
+        });
+    });
+    big = 0.f;
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        dq[J] = 0.f;
+        static_for<kPose>([&](auto ic) { constexpr int I = decltype(ic)::value; dq[J] += g[J][I] * y[I]; });
+        big = fmaxf(big, fabsf(dq[J]));
+    });
+}
+
+// POSE: the 6 x 6 system (FULL, or AXIS by the wave-uniform axis_mode), else the 3 x 3 one
+template <bool POSE>
+__global__ __launch_bounds__(kWave) void ik_multi_kernel(const IkMultiArgs A)
+{
+    const int lane = threadIdx.x;
+    const int S = 1 << A.log2s;
+    const int s = lane & (S - 1);
+    const long long t = (long long)blockIdx.x * kWave + lane;                  // = e S + s
+    const long long e = t >> A.log2s;
+    const bool live = e < A.n;                                                 // (a group is live or not as a whole)
+    const unsigned long long group = (~0ull >> (kWave - S)) << (lane - s);     // the env's lanes in a ballot (S = 64: no shift by 64)
+    float q[kDof];
+    V3 tgt = {0.f, 0.f, 0.f};
+    float qx = 0.f, qy = 0.f, qz = 0.f, qw = 1.f;
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) q[i] = 0.f;
+    if (live) {
+        if (A.target) { const float* tp = A.target + 3 * e; tgt = {tp[0], tp[1], tp[2]}; }
+        else { const float4 w = state_cold(A.state, A.n)[e]; tgt = {w.x, w.y, w.z}; }
+        if constexpr (POSE) {
+            const float* tq = A.quat + 4 * e;
+            qx = tq[0]; qy = tq[1]; qz = tq[2]; qw = tq[3];
+        }
+        ik_multi_start(A, e, s, q);
+    }
+    // the target's rotation as ik_pose_kernel forms it
+    const float qinv = 1.0f / sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
+    qx *= qinv; qy *= qinv; qz *= qinv; qw *= qinv;
+    const V3 t0 = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy + qz * qw), 2.f * (qx * qz - qy * qw)};
+    const V3 t1 = {2.f * (qx * qy - qz * qw), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz + qx * qw)};
+    const V3 t2 = {2.f * (qx * qz + qy * qw), 2.f * (qy * qz - qx * qw), 1.f - 2.f * (qx * qx + qy * qy)};
+    const V3 tv = A.axis.x * t0 + A.axis.y * t1 + A.axis.z * t2;
+    bool frozen = !live, conv = false;
+    int iters = 0;
+    float dist = 0.f, angle = 0.f;
+    for (int it = 0; ; ++it) {
+        float c[kDof], sj[kDof];
+#pragma unroll
+        for (int i = 0; i < kDof; ++i) sincos_bounded(q[i], sj[i], c[i]);    // q is inside the limits
+        V3 lin[kDof], ang[kDof], point;
+        M3 R;
+        chain_jacobian(c, sj, A.point, lin, ang, point, POSE ? &R : nullptr);
+        const V3 err = tgt - point;
+        const float dist2 = dot(err, err);
+        dist = sqrtf(dist2);
+        V3 sv = {0.f, 0.f, 0.f};
+        float sn = 0.f;
+        if constexpr (POSE) {
+            float cs;
+            if (A.axis_mode) {
+                const V3 u = mul(R, A.axis);
+                sv = cross(u, tv); cs = dot(u, tv);
+            } else {
+                const V3 r0 = col(R, 0), r1 = col(R, 1), r2 = col(R, 2);
+                sv = 0.5f * (cross(r0, t0) + cross(r1, t1) + cross(r2, t2));
+                cs = 0.5f * (dot(r0, t0) + dot(r1, t1) + dot(r2, t2) - 1.f);
+            }
+            sn = sqrtf(dot(sv, sv));
+            angle = atan2f(sn, cs);
+        }
+        conv = POSE ? (dist <= A.tol && angle <= A.angle_tol) : dist <= A.tol;   // of the pose q is at: a frozen lane's stays
+        if (it == A.max_iter) break;                                         // the pose of the result: its residuals
+        frozen = frozen || conv;
+        unsigned long long running = __builtin_amdgcn_ballot_w64(!frozen);
+        if (A.first) {                                                       // a lane of the env has converged: the env stops
+            frozen = frozen || (~running & group) != 0;
+            running = __builtin_amdgcn_ballot_w64(!frozen);
+        }
+        if (running == 0) break;
+        float dq[kDof], big;
+        if constexpr (POSE) ik_pose_step(lin, ang, err, dist2, sv, sn, angle, A.weight, A.damping2, A.error_damping, dq, big);
+        else ik_position_step(lin, err, A.damping2 + A.error_damping * dist2, dq, big);
+        const float scale = big > A.max_step ? A.max_step * fast_rcp(big) : 1.f;
+        static_for<kDof>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            const float qn = fminf(fmaxf(q[J] + scale * dq[J], limit_lo(J)), limit_hi(J));
+            q[J] = frozen ? q[J] : qn;
+        });
+        iters += frozen ? 0 : 1;
+    }
+    // the env's winner: the smallest (not converged, cost, start); a cost that is not finite is +inf (costs are >= 0, so their
+    // bit patterns order as they do, and the top bit is free for "not converged")
+    const unsigned long long conv_mask = __builtin_amdgcn_ballot_w64(conv && live);
+    float cost = dist + A.weight * angle;
+    if (conv) {
+        float ref[kDof];
+        if (live && A.q_ref) {
+#pragma unroll
+            for (int i = 0; i < kDof; ++i) ref[i] = A.q_ref[kDof * e + i];
+        } else {
+            ik_multi_start(A, live ? e : 0ll, 0, ref);
+        }
+        cost = 0.f;
+#pragma unroll
+        for (int i = 0; i < kDof; ++i) cost += (q[i] - ref[i]) * (q[i] - ref[i]);
+    }
+    cost = cost < __builtin_inff() ? cost : __builtin_inff();
+    unsigned key = __float_as_uint(cost) | (conv ? 0u : 0x80000000u);
+    int win = s;
+    for (int m = 1; m < S; m <<= 1) {
+        const unsigned okey = (unsigned)__shfl_xor((int)key, m);
+        const int owin = __shfl_xor(win, m);
+        const bool take = okey < key || (okey == key && owin < win);
+        key = take ? okey : key;
+        win = take ? owin : win;
+    }
+    if (!live) return;
+    if (A.all_q) {
+        float2* qa = reinterpret_cast<float2*>(A.all_q) + 3 * t;
+        qa[0] = make_float2(q[0], q[1]); qa[1] = make_float2(q[2], q[3]); qa[2] = make_float2(q[4], q[5]);
+    }
+    if (A.all_residual) A.all_residual[t] = dist;
+    if (A.all_angle) A.all_angle[t] = angle;
+    if (A.all_iterations) A.all_iterations[t] = iters;
+    if (s != win) return;
+    float2* qo = reinterpret_cast<float2*>(A.q_out) + 3 * e;
+    qo[0] = make_float2(q[0], q[1]); qo[1] = make_float2(q[2], q[3]); qo[2] = make_float2(q[4], q[5]);
+    if (A.residual) A.residual[e] = dist;
+    if (A.angle) A.angle[e] = angle;
+    if (A.iterations) A.iterations[e] = iters;
+    if (A.start_out) A.start_out[e] = s;
+    if (A.converged) A.converged[e] = __builtin_popcountll(conv_mask & group);
 }
 
 }  // namespace pnr

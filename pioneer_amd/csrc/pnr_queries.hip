@@ -1,5 +1,5 @@
 // pnr_queries.hip — the query entry points of the C ABI (include/pioneer_amd.h) and their kernels: link states, Jacobian,
-// inverse dynamics and mass matrix, joint states, the two IK solvers, contacts, render, ray casts.  A query reads the handle (or the
+// inverse dynamics and mass matrix, joint states, the IK solvers, contacts, render, ray casts.  A query reads the handle (or the
 // caller's joints) and writes the caller's buffers; it never changes an env.  The kernels are the query headers' (pnr_query.h:
 // their shared scaffold); the handle and the host helpers shared with the core unit pnr_api.hip are pnr_env_host.h's.  A unit
 // of its own so that a query's code object holds no step kernel and a change to one recompiles neither.
@@ -311,6 +311,93 @@ int pnr_solve_ik_pose(pnr_handle h, const pnr_ik_pose_params* p, const float* ta
     A.damping2 = (float)(p->damping * p->damping); A.error_damping = (float)p->error_damping; A.weight = (float)p->orientation_weight;
     A.max_step = (float)p->max_step; A.tol = (float)p->tolerance; A.angle_tol = (float)p->angle_tolerance;
     return launch_env_waves(h, stream, kJointSrcBuffer, [](auto) { return ik_pose_kernel; }, A);  // (no joint source: one form)
+}
+
+int pnr_ik_multi_params_default(pnr_ik_multi_params* p, int32_t task)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_ik_multi_params_default: null params");
+    if (task != PNR_IK_TASK_POSITION && task != PNR_IK_TASK_POSE && task != PNR_IK_TASK_AXIS)
+        return fail(nullptr, PNR_ERR_INVALID, "pnr_ik_multi_params_default: task %d outside {0, 1, 2} (position, pose, axis)", task);
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_ik_multi_params);
+    p->task = task;
+    p->policy = PNR_IK_MULTI_BEST;
+    p->num_starts = 8;
+    p->link = kNumLinks - 1;
+    p->max_iterations = 32;
+    p->local_axis[0] = 1.0;
+    const bool pose = task != PNR_IK_TASK_POSITION;           // each task's own defaults (pnr_ik_params_default, pnr_ik_pose_params_default)
+    p->damping = pose ? 0.03 : 1.0;
+    p->error_damping = pose ? 0.01 : 0.0;
+    p->orientation_weight = 10.0;
+    p->max_step = 0.5;
+    p->tolerance = 1e-3;
+    p->angle_tolerance = 1e-3;
+    return PNR_OK;
+}
+
+int pnr_solve_ik_multi(pnr_handle h, const pnr_ik_multi_params* p, const pnr_ik_multi_buffers* b, void* stream)
+{
+    const char* call = "pnr_solve_ik_multi";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "%s: null params", call);
+    if (!b) return fail(h, PNR_ERR_INVALID, "%s: null buffers", call);
+    if (p->struct_size != sizeof(pnr_ik_multi_params))
+        return fail(h, PNR_ERR_INVALID, "%s: params struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_ik_multi_params));
+    if (b->struct_size != sizeof(pnr_ik_multi_buffers))
+        return fail(h, PNR_ERR_INVALID, "%s: buffers struct_size %u, want %zu", call, b->struct_size, sizeof(pnr_ik_multi_buffers));
+    if (p->task != PNR_IK_TASK_POSITION && p->task != PNR_IK_TASK_POSE && p->task != PNR_IK_TASK_AXIS)
+        return fail(h, PNR_ERR_INVALID, "%s: task %d outside {0, 1, 2} (position, pose, axis)", call, p->task);
+    if (p->policy != PNR_IK_MULTI_BEST && p->policy != PNR_IK_MULTI_FIRST)
+        return fail(h, PNR_ERR_INVALID, "%s: policy %d outside {0, 1} (best, first)", call, p->policy);
+    const bool pose = p->task != PNR_IK_TASK_POSITION;
+    if (!b->q_out) return fail(h, PNR_ERR_INVALID, "%s: null q_out", call);
+    if (pose && !b->target_quat) return fail(h, PNR_ERR_INVALID, "%s: null target_quat", call);
+    int log2s = -1;
+    for (int k = 0; k <= 6; ++k) if (p->num_starts == (1 << k)) log2s = k;
+    if (log2s < 0) return fail(h, PNR_ERR_INVALID, "%s: num_starts %d is not one of 1, 2, 4, 8, 16, 32, 64", call, p->num_starts);
+    if (!b->starts && p->num_starts > 1) return fail(h, PNR_ERR_INVALID, "%s: null starts with num_starts %d", call, p->num_starts);
+    if (p->link < 0 || p->link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "%s: link %d outside 0..%d", call, p->link, kNumLinks - 1);
+    if (p->max_iterations < 1 || p->max_iterations > 1024)
+        return fail(h, PNR_ERR_INVALID, "%s: max_iterations %d outside 1..1024", call, p->max_iterations);
+    const struct { double v; const char* name; bool zero_ok, pose_only; } scalars[] = {
+        {p->damping, "damping", false, false}, {p->max_step, "max_step", false, false}, {p->orientation_weight, "orientation_weight", false, true},
+        {p->error_damping, "error_damping", true, false}, {p->tolerance, "tolerance", true, false}, {p->angle_tolerance, "angle_tolerance", true, true}};
+    for (const auto& s : scalars)
+        if ((pose || !s.pose_only) && !(std::isfinite(s.v) && (s.zero_ok ? s.v >= 0 : s.v > 0)))
+            return fail(h, PNR_ERR_INVALID, "%s: %s must be finite and %s 0", call, s.name, s.zero_ok ? ">=" : ">");
+    if (!finite_all(p->local_point, 3)) return fail(h, PNR_ERR_INVALID, "%s: non-finite local_point", call);
+    const double* ax = p->local_axis;
+    const double axis_len = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+    if (pose && (!finite_all(ax, 3) || !std::isfinite(axis_len) || !(axis_len > 0)))
+        return fail(h, PNR_ERR_INVALID, "%s: local_axis must be finite and not zero", call);
+    if (const int rc = check_aligned(h, call, {{b->q_out, "q_out", 8}, {b->all_q, "all_q", 8}, {b->target_pos, "target_pos", 4},
+                                               {b->target_quat, "target_quat", 4}, {b->starts, "starts", 4}, {b->q_init, "q_init", 4},
+                                               {b->q_ref, "q_ref", 4}, {b->residual_out, "residual_out", 4}, {b->angle_out, "angle_out", 4},
+                                               {b->iterations_out, "iterations_out", 4}, {b->start_out, "start_out", 4},
+                                               {b->converged_out, "converged_out", 4}, {b->all_residual, "all_residual", 4},
+                                               {b->all_angle, "all_angle", 4}, {b->all_iterations, "all_iterations", 4}})) return rc;
+    if (!b->target_pos && !has_own_target(h)) return before_first_reset(h, call, ": the target comes from the state");
+    IkMultiArgs A;
+    A.target = b->target_pos; A.state = h->state; A.quat = b->target_quat; A.starts = b->starts; A.q_init = b->q_init; A.q_ref = b->q_ref;
+    A.q_out = b->q_out; A.residual = b->residual_out; A.angle = b->angle_out; A.iterations = b->iterations_out;
+    A.start_out = b->start_out; A.converged = b->converged_out;
+    A.all_q = b->all_q; A.all_residual = b->all_residual; A.all_angle = b->all_angle; A.all_iterations = b->all_iterations;
+    A.n = h->n;
+    A.point = chain_point(p->link, p->local_point);
+    A.log2s = log2s; A.per_env = p->starts_per_env != 0; A.first = p->policy == PNR_IK_MULTI_FIRST;
+    A.max_iter = p->max_iterations; A.axis_mode = p->task == PNR_IK_TASK_AXIS;
+    A.axis = pose ? V3{(float)(ax[0] / axis_len), (float)(ax[1] / axis_len), (float)(ax[2] / axis_len)} : V3{1.f, 0.f, 0.f};
+    A.damping2 = (float)(p->damping * p->damping); A.error_damping = (float)p->error_damping;
+    A.weight = pose ? (float)p->orientation_weight : 0.f;                      // (the position task: no orientation rows, angle 0)
+    A.max_step = (float)p->max_step; A.tol = (float)p->tolerance; A.angle_tol = pose ? (float)p->angle_tolerance : 0.f;
+    DeviceGuard g(h->device);
+    const long long lanes = h->n << log2s;                                     // one start per lane, 64 >> log2s envs per wave
+    const dim3 grid((unsigned)((lanes + kWave - 1) / kWave));
+    if (pose) hipLaunchKernelGGL(ik_multi_kernel<true>, grid, dim3(kWave), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(ik_multi_kernel<false>, grid, dim3(kWave), 0, (hipStream_t)stream, A);
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
 }
 
 int pnr_contact_params_default(pnr_contact_params* p)

@@ -201,24 +201,46 @@ class PioneerKinematicEnv(compat.GymEnv):
     def observe(self) -> Observation:                                      # :184-211
         return self._vec.observe()[0].double().cpu().numpy()
 
-    def solve_ik(self, target_position: Optional[Tuple[float, float, float]] = None) -> Tuple[np.ndarray, float]:
+    def solve_ik(self, target_position: Optional[Tuple[float, float, float]] = None, starts=None,
+                 q_ref=None) -> Tuple[np.ndarray, float]:
         """calculateInverseKinematics for robot:pointer (position only, PioneerVectorEnv.solve_ik from the rest pose): the
         joint positions (float64 [6], inside the joint limits) that put the pointer on ``target_position`` (default: the
-        env's target) and the distance left; ``reset_world(joint_positions=...)`` takes them as they are."""
+        env's target) and the distance left; ``reset_world(joint_positions=...)`` takes them as they are.  ``starts`` (an int S or
+        an ``[S, 6]`` table) asks for the best of S starts instead (PioneerVectorEnv.solve_ik_multi): of the solutions found the
+        one nearest to the joint positions ``q_ref`` (default: start 0, the rest pose)."""
         tgt = None if target_position is None else np.asarray(target_position, dtype=np.float32).reshape(1, 3)
-        q, residual, _ = self._vec.solve_ik(target=tgt)
+        if starts is None and q_ref is None:
+            q, residual, _ = self._vec.solve_ik(target=tgt)
+        else:
+            res = self._vec.solve_ik_multi(target=tgt, starts=1 if starts is None else starts, q_ref=self._q_ref(q_ref))
+            q, residual = res["q"], res["residual"]
         return q[0].double().cpu().numpy(), float(residual[0].item())
 
     def solve_ik_pose(self, target_orientation, target_position: Optional[Tuple[float, float, float]] = None,
-                      align_axis: Optional[Tuple[float, float, float]] = None) -> Tuple[np.ndarray, float, float]:
+                      align_axis: Optional[Tuple[float, float, float]] = None, starts=None,
+                      q_ref=None) -> Tuple[np.ndarray, float, float]:
         """calculateInverseKinematics with a targetOrientation for robot:pointer (PioneerVectorEnv.solve_ik_pose from the rest
         pose): the joint positions (float64 [6], inside the joint limits) that put the pointer on ``target_position`` (default:
         the env's target) with the orientation ``target_orientation`` (quaternion x, y, z, w), or with only its local
-        ``align_axis`` along the target's; the distance and the angle (rad) left."""
+        ``align_axis`` along the target's; the distance and the angle (rad) left.  ``starts`` / ``q_ref``: as ``solve_ik``
+        (from the rest pose alone one full pose in nine ends in a local minimum)."""
         quat = np.asarray(target_orientation, dtype=np.float32).reshape(1, 4)
         tgt = None if target_position is None else np.asarray(target_position, dtype=np.float32).reshape(1, 3)
-        q, residual, angle, _ = self._vec.solve_ik_pose(quat, target=tgt, align_axis=align_axis)
+        if starts is None and q_ref is None:
+            q, residual, angle, _ = self._vec.solve_ik_pose(quat, target=tgt, align_axis=align_axis)
+        else:
+            res = self._vec.solve_ik_multi(quat, target=tgt, starts=1 if starts is None else starts, q_ref=self._q_ref(q_ref),
+                                           align_axis=align_axis)
+            q, residual, angle = res["q"], res["residual"], res["angle"]
         return q[0].double().cpu().numpy(), float(residual[0].item()), float(angle[0].item())
+
+    def target_reachable(self, within=None, starts=None) -> bool:
+        """Can the pointer get within ``within`` (default ``done_distance``) of the env's target inside the joint limits
+        (PioneerVectorEnv.target_reachable)?  ``starts`` None: from the rest pose alone; else the best of that many starts."""
+        return bool(self._vec.target_reachable(within, starts)[0].item())
+
+    def _q_ref(self, q_ref):
+        return None if q_ref is None else np.asarray(q_ref, dtype=np.float32).reshape(1, self.dof)
 
     def render(self, mode="human"):                                        # bullet_env.py:156-185
         if mode == "human":

@@ -156,6 +156,16 @@ def ray_fan(n: int, length: float, start: float = 0.0) -> np.ndarray:
     return np.concatenate([float(start) * d, float(length) * d], axis=1).astype(np.float32)
 
 
+def ik_start_table(S: int, seed: int = 0) -> np.ndarray:
+    """The default starts of multi-start inverse kinematics (``PioneerVectorEnv.solve_ik_multi(starts=S)``) as a float32 ``[S, 6]``
+    array: row 0 the rest pose q = 0, the others uniform in ±0.8 of the joint limits from ``np.random.default_rng(seed)``.  The
+    draws go row by row, so the table of S starts is the first S rows of every larger table of the same seed."""
+    limits = np.array([j.limit for j in model.revolute_joints()], dtype=np.float64)
+    table = np.random.default_rng(int(seed)).uniform(-0.8, 0.8, size=(int(S), len(limits))) * limits
+    table[0] = 0.0
+    return table.astype(np.float32)
+
+
 # the URDF link (Bullet's link_index) of each of the engine's 23 contact sample spheres, in the engine's order: 8 on arm1, 7 on
 # arm2, 2 on rotator2 (+ hinge2), 3 on arm3, 2 on the effector's needle, and the pointer's own sphere
 CONTACT_SAMPLE_LINKS = (3,) * 8 + (4,) * 7 + (5,) * 2 + (7,) * 3 + (9,) * 2 + (10,)

@@ -601,12 +601,92 @@ class PioneerVectorEnv:
                                              self._stream()))
         return q, res, ang, its
 
-    def target_reachable(self, within=None):
+    def solve_ik_multi(self, target_orientation=None, target=None, starts=8, q_init=None, q_ref=None, policy="best", align_axis=None,
+                       link=10, local_point=None, max_iterations=32, damping=None, error_damping=None, orientation_weight=10.0,
+                       max_step=0.5, tolerance=1e-3, angle_tolerance=1e-3, seed=0, return_all=False, out=None):
+        """Multi-start inverse kinematics for every env, one launch (pnr_solve_ik_multi): S descents per env, and of the solutions
+        found the one nearest to ``q_ref``.  ``target_orientation`` None solves for the position alone (``solve_ik``'s law and
+        defaults: damping 1.0, error_damping 0); ``[N, 4]`` quaternions ask for the pose (``solve_ik_pose``'s law and defaults:
+        damping 0.03, error_damping 0.01), ``align_axis`` as there.  ``starts``: an int S in 1, 2, 4, 8, 16, 32, 64 (the table
+        ``scene.ik_start_table(S, seed)``, kept on the device per (S, seed)), a ``[S, 6]`` tensor shared by all envs or an
+        ``[N, S, 6]`` tensor of each env's own; ``q_init`` (``[N, 6]``) replaces start 0 of every env.  The winner of an env is the
+        smallest (not converged, cost, start index): cost = |q - q_ref|² for a converged start (``q_ref`` ``[N, 6]``; None = the
+        env's start 0), the error left for the others.  ``policy`` "best": every start runs to its end; "first": an env stops at
+        the first convergence check in which one of its starts converges (the shorter wave time).
+        Returns a dict of device tensors, the winner's: ``q`` [N, 6], ``residual`` [N], ``angle`` [N] (0 for the position task),
+        ``iterations`` [N] int32, ``start`` [N] int32 (its start index), ``converged`` [N] int32 (how many of the env's starts
+        converged; 0: none did); with ``return_all`` also every start's ``all_q`` [N, S, 6], ``all_residual``, ``all_angle`` and
+        ``all_iterations`` [N, S].  ``out`` may carry preallocated tensors under the same keys.  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        pose = target_orientation is not None
+        if align_axis is not None and not pose:
+            raise AssertionError("align_axis goes with a target_orientation")
+        task = _lib.IK_TASK_POSITION if not pose else (_lib.IK_TASK_POSE if align_axis is None else _lib.IK_TASK_AXIS)
+        p = _lib.PnrIkMultiParams()
+        self._chk(self.lib.pnr_ik_multi_params_default(p, task))
+        if policy not in ("best", "first"):
+            raise AssertionError(f'policy must be "best" or "first", got {policy!r}')
+        p.policy = _lib.IK_MULTI_FIRST if policy == "first" else _lib.IK_MULTI_BEST
+        if isinstance(starts, (int, np.integer)):
+            S = int(starts)
+            if S not in _lib.IK_MULTI_STARTS:
+                raise AssertionError(f"starts must be one of {_lib.IK_MULTI_STARTS}, got {S}")
+            tables = self.__dict__.setdefault("_ik_start_tables", {})
+            if (S, int(seed)) not in tables:
+                from .scene import ik_start_table
+                tables[(S, int(seed))] = torch.from_numpy(ik_start_table(S, seed)).to(self.device)
+            table = tables[(S, int(seed))]
+        else:
+            shape = tuple(starts.shape)
+            S = int(shape[-2]) if len(shape) in (2, 3) else 0
+            if S not in _lib.IK_MULTI_STARTS:
+                raise AssertionError(f"starts must be [S, 6] or [N, S, 6] with S one of {_lib.IK_MULTI_STARTS}, got {shape}")
+            table = self._in(starts, (S, 6) if len(shape) == 2 else (n, S, 6), torch.float32, "starts")
+            p.starts_per_env = int(len(shape) == 3)
+        p.num_starts, p.link, p.max_iterations = S, int(link), int(max_iterations)
+        if local_point is not None:
+            for k in range(3):
+                p.local_point[k] = float(local_point[k])
+        if align_axis is not None:
+            for k in range(3):
+                p.local_axis[k] = float(align_axis[k])
+        if damping is not None:
+            p.damping = float(damping)
+        if error_damping is not None:
+            p.error_damping = float(error_damping)
+        p.orientation_weight, p.max_step = float(orientation_weight), float(max_step)
+        p.tolerance, p.angle_tolerance = float(tolerance), float(angle_tolerance)
+        quat = None if not pose else self._in(target_orientation, (n, 4), torch.float32, "target_orientation")
+        tgt = None if target is None else self._in(target, (n, 3), torch.float32, "target")
+        qi = None if q_init is None else self._in(q_init, (n, 6), torch.float32, "q_init")
+        qr = None if q_ref is None else self._in(q_ref, (n, 6), torch.float32, "q_ref")
+        i32 = torch.int32
+        res = self._asked(out, (("q", True, (n, 6), torch.float32), ("residual", True, (n,), torch.float32),
+                                ("angle", True, (n,), torch.float32), ("iterations", True, (n,), i32), ("start", True, (n,), i32),
+                                ("converged", True, (n,), i32), ("all_q", return_all, (n, S, 6), torch.float32),
+                                ("all_residual", return_all, (n, S), torch.float32), ("all_angle", return_all, (n, S), torch.float32),
+                                ("all_iterations", return_all, (n, S), i32)), "")
+        b = _lib.PnrIkMultiBuffers()
+        b.struct_size = C.sizeof(_lib.PnrIkMultiBuffers)
+        for name, t in (("target_pos", tgt), ("target_quat", quat), ("starts", table), ("q_init", qi), ("q_ref", qr), ("q_out", res["q"]),
+                        ("residual_out", res["residual"]), ("angle_out", res["angle"]), ("iterations_out", res["iterations"]),
+                        ("start_out", res["start"]), ("converged_out", res["converged"]), ("all_q", res.get("all_q")),
+                        ("all_residual", res.get("all_residual")), ("all_angle", res.get("all_angle")),
+                        ("all_iterations", res.get("all_iterations"))):
+            setattr(b, name, None if t is None else t.data_ptr())
+        self._chk(self.lib.pnr_solve_ik_multi(self._h, p, b, self._stream()))
+        return res
+
+    def target_reachable(self, within=None, starts=None):
         """bool ``[N]``: can the pointer get within ``within`` (default the config's ``done_distance``) of the env's own target
         without leaving the joint limits?  ``solve_ik()`` from the rest pose with all defaults; about 3 % of the reference's
         target box (its far corners) cannot be reached, and such an episode can only end at the time limit.  True is exact; False
-        means "not reached from the rest pose", which for about one target in a hundred is a local minimum of that start."""
+        means "not reached from the rest pose", which for about one target in a hundred is a local minimum of that start.
+        ``starts`` (as ``solve_ik_multi``'s): the best of that many starts instead; False then means "from none of them"."""
         within = float(self.config.done_distance if within is None else within)
+        if starts is not None:
+            return self.solve_ik_multi(starts=starts, policy="first")["residual"] <= within
         return self.solve_ik()[1] <= within
 
     def render_frames(self, render_config=None, joint_state=None, bodies=None, rgb=True, depth=False, segmentation=False, out=None,
