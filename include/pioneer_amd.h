@@ -51,7 +51,7 @@ extern "C" {
  *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets, pnr_body_params_default,
  *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state, pnr_render_bodies, pnr_set_body_queries,
  *      pnr_render_cameras, pnr_body_grip_params_default, pnr_set_body_grip_params, pnr_set_body_grip, pnr_get_body_grip,
- *      pnr_ik_multi_params_default, pnr_solve_ik_multi */
+ *      pnr_ik_multi_params_default, pnr_solve_ik_multi, pnr_path_params_default, pnr_path_clearance */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -922,6 +922,65 @@ int pnr_contact_params_default(pnr_contact_params* p);
 int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_params* p,
                      const float* body_positions, float* points, float* summary,
                      float* joint_torques, void* stream);
+
+/*
+ * Path clearance for every env, one launch: the arm swept along a piecewise-linear joint path, each configuration's clearance
+ * to the bodies of the call (pnr_get_contacts' distances, without its velocities, normals and forces) and the path's summary.
+ * The edge check of a sampling planner, the shield of a joint-target action, the score of a set of IK candidates.
+ * THIS IS A SAMPLED CHECK: only the C configurations below are looked at.  Something thinner than the samples' travel between
+ * two neighbouring configurations can be missed; choose substeps for the joint step the scene needs.
+ *   The path.  waypoints is [num_envs][K][6] float32 (waypoints_per_env != 0) or [K][6], shared by all envs (== 0), K =
+ *   n_waypoints, 8-byte aligned.  With from_current != 0 the env's own joints are waypoint 0 in front of the K given ones
+ *   (dynamics mode the simulated q, kinematic mode the env's r, as pnr_get_contacts reads them with a NULL joint_state).  W, the
+ *   number of waypoints so obtained, must be >= 1; K = 0 (waypoints NULL) with from_current is the env where it stands.
+ *   The configurations.  C = 1 + (W - 1) M, M = substeps.  Configuration 0 is waypoint 0; configuration 1 + i M + (j - 1),
+ *   j = 1..M, lies on segment i from waypoint a to waypoint b: a + (j / M) (b - a) in float32 for j < M and EXACTLY b for j = M,
+ *   so a waypoint's clearance is pnr_get_contacts' distance at that configuration.  Its path coordinate is t = i + j / M (0 for
+ *   configuration 0).  M = 1 looks at the waypoints alone: a candidate set.
+ *   The clearance of a configuration: the smallest signed surface-to-surface distance over the samples in sample_mask (bit s =
+ *   sample s of pnr_get_contacts; the pointer, sample 22, at pnr_config.pointer_radius) and over all bodies, in
+ *   pnr_get_contacts' forms; body_positions [num_envs][n_bodies][3] as there.  On a handle with PNR_BODY_IN_CONTACTS set
+ *   (pnr_set_body_queries) the env's moving sphere is body PNR_MAX_SCENE (8), standing still where it is now; it loses a tie.
+ *   A (sample, body) distance that is not finite counts as -inf: the order is total, and a NaN waypoint or body position makes
+ *   the path not free.
+ *   summary  [num_envs][PNR_PATH_SUMMARY_DIM] float32 or NULL, 16-byte aligned:
+ *              [0] the smallest clearance over the path; [1] its path coordinate t (the lowest configuration on a tie);
+ *              [2], [3] the sample and the body that attain it (within a configuration the lowest sample, then the lowest
+ *              body, as in pnr_get_contacts); [4] t of the first configuration with clearance < margin, -1 if there is none;
+ *              [5] the number of such configurations; [6] 1 if there is none, else 0; [7] 0.
+ *            With n_bodies == 0 and no sphere: +inf, 0, 0, -1, -1, 0, 1, 0.
+ *   clearance  [num_envs][C] float32 or NULL: every configuration's clearance, the profile.
+ * At least one output must be non-NULL; nothing is written past num_envs rows of either.
+ * lanes_per_env: how many lanes of a 64-lane wave share an env's configurations: 1, 2, 4, .. 64, or 0 = auto: the smallest
+ * power of two >= C, at most 32 (at C = 81 and 65 536 envs 32 lanes measured 537 us against 64 lanes' 725 us: three trips of
+ * 32 leave 15 lane-trips idle, two of 64 leave 47).  The outputs are bit-identical for every value, and an env's do not depend
+ * on the batch around it.
+ * PNR_ERR_INVALID, nothing launched and no output touched, for: everything pnr_get_contacts refuses about the handle, the
+ * params' struct_size, n_bodies, the bodies and the pointers' alignment; n_waypoints outside 0..PNR_MAX_PATH_WAYPOINTS; substeps
+ * outside 1..PNR_MAX_PATH_SUBSTEPS; a lanes_per_env that is none of the above; from_current or waypoints_per_env other than 0
+ * or 1; n_waypoints 0 without from_current; NULL waypoints with n_waypoints > 0; a sample_mask with no bit among the 23 samples
+ * or with a bit above them; a non-finite margin; every output NULL; from_current before the first pnr_reset (or
+ * pnr_set_state).  Device data is not inspected.  float32 arithmetic, asynchronous on `stream`, no allocation, no
+ * synchronisation: capturable into a graph.  Parity unpinned, as pnr_get_contacts.
+ */
+#define PNR_MAX_PATH_WAYPOINTS 256
+#define PNR_MAX_PATH_SUBSTEPS 64
+#define PNR_PATH_SUMMARY_DIM 8
+typedef struct pnr_path_params {
+    uint32_t struct_size;                    /* sizeof(pnr_path_params) */
+    int32_t  n_waypoints;                    /* K: the given waypoints, 0 .. PNR_MAX_PATH_WAYPOINTS; default 1 */
+    int32_t  substeps;                       /* M: configurations per segment, 1 .. PNR_MAX_PATH_SUBSTEPS; default 8 */
+    int32_t  from_current;                   /* != 0: the env's own joints are waypoint 0 */
+    int32_t  waypoints_per_env;              /* != 0: waypoints is [num_envs][K][6], else [K][6] */
+    int32_t  lanes_per_env;                  /* 0 (auto), 1, 2, 4, 8, 16, 32, 64 */
+    uint32_t sample_mask;                    /* bit s = sample s; default all 23 (0x7fffff) */
+    int32_t  n_bodies;                       /* 0 .. PNR_MAX_SCENE */
+    double   margin;                         /* a configuration with clearance < margin violates; finite; default 0 */
+    pnr_scene_body bodies[PNR_MAX_SCENE];    /* as pnr_contact_params.bodies */
+} pnr_path_params;
+int pnr_path_params_default(pnr_path_params* p);
+int pnr_path_clearance(pnr_handle h, const pnr_path_params* p, const float* waypoints, const float* body_positions,
+                       float* summary, float* clearance, void* stream);
 
 /*
  * render('rgb_array') for every env in one launch (bullet_env.py:156-185 -> getCameraImage): one camera shared by all envs,

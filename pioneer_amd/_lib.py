@@ -113,6 +113,18 @@ class PnrContactParams(C.Structure):
                 ("bodies", PnrSceneBody * MAX_SCENE)]
 
 
+PATH_SUMMARY_DIM = 8            # pnr_path_clearance: min clearance, its t, sample, body, first violating t, violations, free, 0
+MAX_PATH_WAYPOINTS, MAX_PATH_SUBSTEPS = 256, 64
+PATH_LANES = (0, 1, 2, 4, 8, 16, 32, 64)                     # pnr_path_params.lanes_per_env (0: auto)
+
+
+class PnrPathParams(C.Structure):
+    """pnr_path_params of include/pioneer_amd.h (pnr_path_clearance's path layout, sample mask, margin and bodies)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_waypoints", C.c_int32), ("substeps", C.c_int32), ("from_current", C.c_int32),
+                ("waypoints_per_env", C.c_int32), ("lanes_per_env", C.c_int32), ("sample_mask", C.c_uint32), ("n_bodies", C.c_int32),
+                ("margin", C.c_double), ("bodies", PnrSceneBody * MAX_SCENE)]
+
+
 class PnrRayParams(C.Structure):
     """pnr_ray_params of include/pioneer_amd.h (pnr_ray_test's ray layout, parent link, hit mask and bodies)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_rays", C.c_int32), ("rays_per_env", C.c_int32), ("parent_link", C.c_int32),
@@ -268,6 +280,8 @@ SIGNATURES = {
     "pnr_render_cameras": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
     "pnr_contact_params_default": (C.c_int, [C.POINTER(PnrContactParams)]),
     "pnr_get_contacts": (C.c_int, [_VP, _VP, C.POINTER(PnrContactParams), _VP, _VP, _VP, _VP, _VP]),
+    "pnr_path_params_default": (C.c_int, [C.POINTER(PnrPathParams)]),
+    "pnr_path_clearance": (C.c_int, [_VP, C.POINTER(PnrPathParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_ray_params_default": (C.c_int, [C.POINTER(PnrRayParams)]),
     "pnr_ray_test": (C.c_int, [_VP, _VP, C.POINTER(PnrRayParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_diag_sincos": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, _VP]),
@@ -303,9 +317,9 @@ _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr
 UNITS = {
     # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (126, 96 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
-    # the query entry points of the C ABI and their kernels (49: the three scene queries have a per-env-world form each, pnr_query.h; the renderer a per-env-camera form too)
+    # the query entry points of the C ABI and their kernels (55: the three scene queries have a per-env-world form each, pnr_query.h; the renderer a per-env-camera form too; six of pnr_path.h)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",
-                        "pnr_jointstate.h", "pnr_contacts.h", "pnr_rays.h"],
+                        "pnr_jointstate.h", "pnr_contacts.h", "pnr_rays.h", "pnr_path.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",
                       "pnr_mlp_gather.h", "pnr_mlp_backward.h", "pnr_mlp_wgrad.h", "pnr_mlp_adam.h", "pnr_sampler.h"],
 }

@@ -1,5 +1,5 @@
 // pnr_queries.hip — the query entry points of the C ABI (include/pioneer_amd.h) and their kernels: link states, Jacobian,
-// inverse dynamics and mass matrix, joint states, the IK solvers, contacts, render, ray casts.  A query reads the handle (or the
+// inverse dynamics and mass matrix, joint states, the IK solvers, contacts, path clearance, render, ray casts.  A query reads the handle (or the
 // caller's joints) and writes the caller's buffers; it never changes an env.  The kernels are the query headers' (pnr_query.h:
 // their shared scaffold); the handle and the host helpers shared with the core unit pnr_api.hip are pnr_env_host.h's.  A unit
 // of its own so that a query's code object holds no step kernel and a change to one recompiles neither.
@@ -19,6 +19,7 @@
 #include "pnr_jointstate.h"
 #include "pnr_contacts.h"
 #include "pnr_rays.h"
+#include "pnr_path.h"
 
 using namespace pnr;
 
@@ -443,6 +444,84 @@ int pnr_get_contacts(pnr_handle h, const float* joint_state, const pnr_contact_p
         return launch_env_waves(h, stream, J.kind, [](auto S) { return contacts_kernel<S() | kQueryScene>; }, X);
     }
     return launch_env_waves(h, stream, J.kind, [](auto S) { return contacts_kernel<S()>; }, A);
+}
+
+int pnr_path_params_default(pnr_path_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_path_params_default: null params");
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_path_params);
+    p->n_waypoints = 1; p->substeps = 8;
+    p->sample_mask = kPathAllSamples;
+    return PNR_OK;
+}
+
+int pnr_path_clearance(pnr_handle h, const pnr_path_params* p, const float* waypoints, const float* body_positions, float* summary,
+                       float* clearance, void* stream)
+{
+    const char* call = "pnr_path_clearance";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "%s: null params", call);
+    if (p->struct_size != sizeof(pnr_path_params))
+        return fail(h, PNR_ERR_INVALID, "%s: params struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_path_params));
+    if (!summary && !clearance) return fail(h, PNR_ERR_INVALID, "%s: every output is NULL", call);
+    if (const int rc = check_aligned(h, call, {{summary, "summary", 16}, {clearance, "clearance", 4}, {waypoints, "waypoints", 8},
+                                               {body_positions, "body_positions", 4}})) return rc;
+    if (p->n_waypoints < 0 || p->n_waypoints > PNR_MAX_PATH_WAYPOINTS)
+        return fail(h, PNR_ERR_INVALID, "%s: n_waypoints %d outside 0..%d", call, p->n_waypoints, PNR_MAX_PATH_WAYPOINTS);
+    if (p->substeps < 1 || p->substeps > PNR_MAX_PATH_SUBSTEPS)
+        return fail(h, PNR_ERR_INVALID, "%s: substeps %d outside 1..%d", call, p->substeps, PNR_MAX_PATH_SUBSTEPS);
+    if (p->from_current != 0 && p->from_current != 1) return fail(h, PNR_ERR_INVALID, "%s: from_current must be 0 or 1", call);
+    if (p->waypoints_per_env != 0 && p->waypoints_per_env != 1) return fail(h, PNR_ERR_INVALID, "%s: waypoints_per_env must be 0 or 1", call);
+    int log2p = -1;
+    for (int k = 0; k <= 6; ++k) if (p->lanes_per_env == (1 << k)) log2p = k;
+    if (log2p < 0 && p->lanes_per_env != 0)
+        return fail(h, PNR_ERR_INVALID, "%s: lanes_per_env %d is not one of 0 (auto), 1, 2, 4, 8, 16, 32, 64", call, p->lanes_per_env);
+    const int W = p->n_waypoints + p->from_current;
+    if (W < 1) return fail(h, PNR_ERR_INVALID, "%s: n_waypoints 0 without from_current: the path has no waypoint", call);
+    if (!waypoints && p->n_waypoints > 0) return fail(h, PNR_ERR_INVALID, "%s: null waypoints with n_waypoints %d", call, p->n_waypoints);
+    if ((p->sample_mask & kPathAllSamples) == 0 || (p->sample_mask & ~kPathAllSamples))
+        return fail(h, PNR_ERR_INVALID, "%s: sample_mask 0x%x has no bit among the %d samples or a bit above them", call, (unsigned)p->sample_mask, kContactSamples);
+    if (!std::isfinite(p->margin)) return fail(h, PNR_ERR_INVALID, "%s: non-finite margin", call);
+    if (p->n_bodies < 0 || p->n_bodies > PNR_MAX_SCENE)
+        return fail(h, PNR_ERR_INVALID, "%s: n_bodies %d outside 0..%d", call, p->n_bodies, PNR_MAX_SCENE);
+    for (int b = 0; b < p->n_bodies; ++b)
+        if (const int rc = check_scene_body(h, "pnr_path_clearance: body", b, p->bodies[b], true)) return rc;
+    if (p->from_current && !has_own_joints(h)) return before_first_reset(h, call, ": from_current reads the env's joints");
+    PathArgs A;
+    memset(&A, 0, sizeof(A));
+    int kind = kJointSrcBuffer;                         // (no from_current: no joint source)
+    if (p->from_current) {
+        const JointSource J = joint_source(h, nullptr);
+        kind = J.kind; A.src = J.src; A.state = J.state;
+    }
+    A.waypoints = p->n_waypoints > 0 ? waypoints : nullptr;
+    A.body_pos = p->n_bodies > 0 ? body_positions : nullptr;
+    A.summary = summary; A.clearance = clearance;
+    A.n = h->n;
+    A.ptr_radius = (float)h->cfg.pointer_radius; A.margin = (float)p->margin;
+    A.n_bodies = p->n_bodies;
+    A.K = p->n_waypoints; A.M = p->substeps; A.C = 1 + (W - 1) * p->substeps;
+    if (log2p < 0)                                      // auto: the smallest power of two >= C, at most 32 (measured: DESIGN.md 3y)
+        for (log2p = 0; log2p < 5 && (1 << log2p) < A.C; ++log2p) {}
+    A.log2p = log2p;
+    A.per_env = p->waypoints_per_env;
+    A.mask = p->sample_mask;
+    for (int b = 0; b < p->n_bodies; ++b) A.bodies[b] = scene_body_device(p->bodies[b]);
+    const long long groups = ((h->n << log2p) + kWave - 1) / kWave;       // one configuration per lane, 64 >> log2p envs per wave
+    if (groups > 0x7fffffffLL) return fail(h, PNR_ERR_INVALID, "%s: %lld envs x %d lanes exceed one launch", call, h->n, 1 << log2p);
+    DeviceGuard g(h->device);
+    const dim3 grid((unsigned)groups);
+    const float* sphere = shown_sphere(h, PNR_BODY_IN_CONTACTS);
+    PathSceneArgs X;
+    static_cast<PathArgs&>(X) = A;
+    X.sphere = sphere;
+    with_int<kJointSrcBuffer, kJointSrcDyn, kJointSrcKin>(kind, [&](auto S) {
+        if (sphere) hipLaunchKernelGGL(path_clearance_kernel<S() | kQueryScene>, grid, dim3(kWave), 0, (hipStream_t)stream, X);
+        else hipLaunchKernelGGL(path_clearance_kernel<S()>, grid, dim3(kWave), 0, (hipStream_t)stream, A);
+    });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
 }
 
 }  // extern "C"

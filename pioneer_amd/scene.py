@@ -62,6 +62,10 @@ one-env engine batch of ``PioneerKinematicEnv``.  What maps and how:
   (``CONTACT_SAMPLE_LINKS`` gives each one's URDF link): one entry per sample, against its nearest body.  bodyUniqueIdA is 0 (the
   arm), bodyUniqueIdB 1 + the body's place among the created collision bodies, linkIndexB -1 (a base).  Deviation: PyBullet's
   manifolds (several points per pair) are not reproduced.
+* ``scene.path_clearance(waypoints, substeps=8, margin=0.0)``: no single PyBullet call — getClosestPoints at every interpolated
+  configuration of the joint path ``waypoints`` against the created collision bodies, one engine launch (``pnr_path_clearance``),
+  either mode, as a ``PathClearance`` (free, the smallest clearance, where on the path, the link and the body id that attain it, the
+  first configuration under the margin).  A sampled check; ``path_substeps(waypoints, max_step)`` sizes ``substeps``.
 * ``scene.ray_test(ray_from, ray_to)`` / ``scene.ray_test_batch(ray_froms, ray_tos, parent_item=None)``: pybullet.rayTest /
   rayTestBatch against the created collision bodies and the arm's visual shapes, as ``RayHit`` tuples (PyBullet's field names),
   one engine launch (``pnr_ray_test``), either mode; ``parent_item`` a link item in whose frame the rays are given.  Ids as in
@@ -164,6 +168,41 @@ def ik_start_table(S: int, seed: int = 0) -> np.ndarray:
     table = np.random.default_rng(int(seed)).uniform(-0.8, 0.8, size=(int(S), len(limits))) * limits
     table[0] = 0.0
     return table.astype(np.float32)
+
+
+class PathClearance(NamedTuple):
+    """``Scene.path_clearance``'s answer for the one env: is the sampled path free, the smallest clearance on it, the path
+    coordinate t where it is attained (segment index + fraction), the URDF link and the created body (``Scene.body_id``; 0 where
+    there is no body) that attain it, and t of the first configuration with clearance < margin (-1.0: none)."""
+    free: bool
+    min_distance: float
+    at: float
+    link_name: str
+    body_id: int
+    first_hit: float
+
+
+def path_substeps(waypoints, max_step: float) -> int:
+    """The smallest ``substeps`` M of ``path_clearance`` for which no joint moves more than ``max_step`` rad between two
+    neighbouring configurations of the path ``waypoints`` (``[K, 6]`` or ``[N, K, 6]``; a CPU tensor or anything numpy takes), at
+    least 1.  On the host: the result sizes the launch.  More than 64 (``_lib.MAX_PATH_SUBSTEPS``) raises: add waypoints."""
+    w = waypoints.detach().cpu().numpy() if isinstance(waypoints, torch.Tensor) else np.asarray(waypoints)
+    w = w.astype(np.float64)
+    if w.ndim not in (2, 3) or w.shape[-1] != 6:
+        raise AssertionError(f"waypoints must have shape (K, 6) or (N, K, 6), got {w.shape}")
+    if not max_step > 0:
+        raise AssertionError("max_step must be > 0")
+    if not np.isfinite(w).all():
+        raise AssertionError("non-finite waypoints")
+    longest = float(np.abs(np.diff(w, axis=-2)).max()) if w.shape[-2] > 1 else 0.0
+    m = max(1, int(math.ceil(longest / float(max_step))))
+    while m > 1 and longest / (m - 1) <= max_step:      # (ceil of a quotient that rounded up)
+        m -= 1
+    while longest / m > max_step:
+        m += 1
+    if m > _lib.MAX_PATH_SUBSTEPS:
+        raise AssertionError(f"{m} sub-steps per segment exceed {_lib.MAX_PATH_SUBSTEPS}: add waypoints")
+    return m
 
 
 # the URDF link (Bullet's link_index) of each of the engine's 23 contact sample spheres, in the engine's order: 8 on arm1, 7 on
@@ -540,6 +579,21 @@ class Scene:
     def closest_points(self, distance: float, item: Optional[Item] = None) -> List[ContactPoint]:
         """getClosestPoints: the samples within ``distance`` of their nearest created body (contactDistance <= distance)."""
         return self._contact_records(item, lambda d: d <= float(distance))
+
+    def path_clearance(self, waypoints, substeps: int = 8, margin: float = 0.0) -> PathClearance:
+        """Sweeps the arm along the joint path ``waypoints`` (``[K, 6]``) against the created collision bodies (and the moving
+        sphere where it stands), ``substeps`` configurations per segment, one engine launch (``PioneerVectorEnv.path_clearance``:
+        a sampled check).  Body ids as in ``contact_points``."""
+        bodies = self.collision_items()
+        if len(bodies) > _lib.MAX_SCENE:
+            raise AssertionError(f"the engine queries at most {_lib.MAX_SCENE} created bodies, the scene has {len(bodies)}")
+        sb = [SceneBody(i.shape, i._position, i._orientation, tuple(map(float, i.size))) for i in bodies]
+        wp = torch.as_tensor(np.asarray(waypoints, dtype=np.float32)).reshape(-1, 6)
+        sm = self._env._vec.path_clearance(wp, substeps=substeps, bodies=sb, margin=margin)["summary"][0].double().cpu().numpy()
+        b = int(sm[3])
+        hit = None if b < 0 else (self.moving_body() if b == _lib.MAX_SCENE else bodies[b])
+        return PathClearance(bool(sm[6] > 0), float(sm[0]), float(sm[1]), model.LINK_NAMES[CONTACT_SAMPLE_LINKS[int(sm[2])]],
+                             0 if hit is None else self.body_id(hit), float(sm[4]))
 
     # -- ray casts (pybullet.rayTest / rayTestBatch) ---------------------------------------------------------------------------
     @staticmethod

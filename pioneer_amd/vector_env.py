@@ -824,6 +824,113 @@ class PioneerVectorEnv:
                                             _ptr(res.get("joint_torques")), self._stream()))
         return res
 
+    def path_clearance(self, waypoints, substeps=8, from_current=False, bodies=None, body_positions=None, margin=0.0, samples=None,
+                       profile=False, lanes_per_env=0, out=None):
+        """Sweeps every env's arm along a joint path, one launch (pnr_path_clearance): can env k move from waypoint to waypoint
+        without touching its bodies?  A SAMPLED check: only the configurations below are looked at (``scene.path_substeps``
+        chooses ``substeps`` for a joint step).
+
+        ``waypoints``: float32 ``[K, 6]`` (one path for all envs) or ``[N, K, 6]`` (a path per env), K <= 256; None with
+        ``from_current`` (the env where it stands).  ``from_current``: the env's own joints (dynamics mode the simulated q,
+        kinematic mode r) are waypoint 0 in front of them.  With W waypoints and M = ``substeps`` (1 .. 64) there are
+        C = 1 + (W - 1) M configurations: waypoint 0, then on segment i from a to b the configurations a + (j / M)(b - a),
+        j = 1 .. M (j = M: b itself), at the path coordinate t = i + j / M.  ``substeps=1`` looks at the waypoints alone: a set
+        of candidates.  A configuration's clearance is the smallest ``contacts()`` distance over the sample spheres (``samples``:
+        a sequence of sample indices 0 .. 22, None = all 23) and the bodies; ``bodies`` / ``body_positions`` as in ``contacts``
+        (None = ``collision_bodies()``), and after ``set_body_queries(contacts=True)`` the env's moving sphere, standing still, is
+        body ``_lib.MAX_SCENE``.  A distance that is not finite counts as -inf (a NaN waypoint makes the path not free).
+
+        Returns a dict of device tensors, views or cheap casts of the ``[N, 8]`` ``summary`` (also returned): ``min_distance``
+        (the smallest clearance over the path), ``at`` (its t; the lowest configuration on a tie), ``sample``, ``body`` (int64:
+        who attains it; body -1 without bodies), ``first_hit`` (t of the first configuration with clearance < ``margin``, -1 if
+        none), ``violations`` (int64: how many such), ``free`` (bool: none); with ``profile`` also ``clearance`` ``[N, C]``.
+        ``lanes_per_env``: 0 (auto) or 1, 2, .. 64 lanes of a wave per env; the results are the same bits for every value.
+        ``out`` may carry preallocated ``summary`` / ``clearance`` tensors, written in place.  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        bodies = self.collision_bodies() if bodies is None else list(bodies)
+        if len(bodies) > _lib.MAX_SCENE:
+            raise AssertionError(f"at most {_lib.MAX_SCENE} bodies can be queried, got {len(bodies)}")
+        p = _lib.PnrPathParams()
+        self._chk(self.lib.pnr_path_params_default(p))
+        wp = None
+        p.n_waypoints = 0
+        if waypoints is not None:
+            if not isinstance(waypoints, torch.Tensor):
+                waypoints = torch.as_tensor(np.asarray(waypoints), dtype=torch.float32)
+            if waypoints.dim() not in (2, 3) or waypoints.shape[-1] != 6 or (waypoints.dim() == 3 and waypoints.shape[0] != n):
+                raise AssertionError(f"waypoints must have shape (K, 6) or ({n}, K, 6), got {tuple(waypoints.shape)}")
+            wp = self._in(waypoints, tuple(waypoints.shape), torch.float32, "waypoints")
+            p.n_waypoints, p.waypoints_per_env = int(wp.shape[-2]), int(wp.dim() == 3)
+        p.substeps, p.from_current, p.lanes_per_env, p.margin = int(substeps), int(bool(from_current)), int(lanes_per_env), float(margin)
+        if samples is not None:
+            mask = 0
+            for s in samples:
+                if not 0 <= int(s) < _lib.CONTACT_SAMPLES:
+                    raise AssertionError(f"samples are indices 0 .. {_lib.CONTACT_SAMPLES - 1}, got {s}")
+                mask |= 1 << int(s)
+            p.sample_mask = mask
+        p.n_bodies = len(bodies)
+        for i, b in enumerate(bodies):
+            fill_scene_body(p.bodies[i], b, f"body {i}")
+        bp = None if body_positions is None else self._in(body_positions, (n, len(bodies), 3), torch.float32, "body_positions")
+        configs = 1 + (p.n_waypoints + p.from_current - 1) * p.substeps
+        res = self._asked(out, (("summary", True, (n, _lib.PATH_SUMMARY_DIM), torch.float32),
+                                ("clearance", profile, (n, max(configs, 1)), torch.float32)), "")
+        self._chk(self.lib.pnr_path_clearance(self._h, p, _ptr(wp), _ptr(bp), _ptr(res["summary"]), _ptr(res.get("clearance")), self._stream()))
+        sm = res["summary"]
+        res.update(min_distance=sm[:, 0], at=sm[:, 1], sample=sm[:, 2].long(), body=sm[:, 3].long(), first_hit=sm[:, 4],
+                   violations=sm[:, 5].long(), free=sm[:, 6] > 0)
+        return res
+
+    def solve_ik_free(self, target_orientation=None, target=None, margin=0.0, bodies=None, body_positions=None, **ik_multi_args):
+        """Collision-aware inverse kinematics, two launches: ``solve_ik_multi(return_all=True, policy="best")`` and ONE
+        ``path_clearance`` over every start's solution as the env's waypoints with ``substeps=1``, then a small selection on the
+        device.  Per env the result is the CONVERGED start nearest to ``q_ref`` (``solve_ik_multi``'s cost, |q - q_ref|^2; None =
+        the env's start 0; the lowest start on a tie) whose clearance is >= ``margin``; ``free`` (bool ``[N]``) tells whether there
+        was one, and where there was none the row is ``solve_ik_multi``'s own winner.  ``bodies`` / ``body_positions`` as in
+        ``contacts``; every other argument goes to ``solve_ik_multi``.
+        Returns ``solve_ik_multi``'s dict with ``q``, ``residual``, ``angle``, ``iterations``, ``start`` of the chosen start, and
+        ``free``, ``clearance`` ``[N]`` (the chosen configuration's) and ``all_clearance`` ``[N, S]``.  Never synchronises."""
+        for key in ("return_all", "policy"):
+            if key in ik_multi_args:
+                raise AssertionError(f"solve_ik_free sets {key} itself")
+        q_ref = ik_multi_args.get("q_ref")
+        res = self.solve_ik_multi(target_orientation=target_orientation, target=target, return_all=True, policy="best", **ik_multi_args)
+        n, S = res["all_residual"].shape
+        clr = self.path_clearance(res["all_q"], substeps=1, bodies=bodies, body_positions=body_positions, margin=margin, profile=True)["clearance"]
+        tol = float(ik_multi_args.get("tolerance", 1e-3))
+        conv = res["all_residual"] <= tol
+        if target_orientation is not None:
+            conv = conv & (res["all_angle"] <= float(ik_multi_args.get("angle_tolerance", 1e-3)))
+        allq = res["all_q"]
+        if q_ref is not None:
+            ref = self._in(q_ref, (n, 6), torch.float32, "q_ref")
+        elif ik_multi_args.get("q_init") is not None:
+            ref = self._in(ik_multi_args["q_init"], (n, 6), torch.float32, "q_init")
+        else:
+            starts = ik_multi_args.get("starts", 8)
+            if isinstance(starts, (int, np.integer)):
+                ref = self._ik_start_tables[(int(starts), int(ik_multi_args.get("seed", 0)))][0].expand(n, 6)
+            else:
+                st = self._in(starts, tuple(starts.shape), torch.float32, "starts")
+                ref = st[0].expand(n, 6) if st.dim() == 2 else st[:, 0]
+        cost = ((allq - ref[:, None, :]) ** 2).sum(dim=2)
+        ok = conv & (clr >= float(margin))
+        cost = torch.where(ok, cost, torch.full_like(cost, float("inf")))
+        pick = cost.argmin(dim=1)                       # (the first of equal costs: the lowest start)
+        free = ok.any(dim=1)
+        pick = torch.where(free, pick, res["start"].long())
+        rows = torch.arange(n, device=self.device)
+        res["q"] = torch.where(free[:, None], allq[rows, pick], res["q"])
+        for key, every in (("residual", "all_residual"), ("angle", "all_angle"), ("iterations", "all_iterations")):
+            res[key] = torch.where(free, res[every][rows, pick], res[key])
+        res["start"] = pick.to(torch.int32)
+        res["free"] = free
+        res["all_clearance"] = clr
+        res["clearance"] = clr[rows, pick]
+        return res
+
     def ray_test(self, rays, parent_link=-1, hit_arm=False, hit_target=False, hit_bodies=True, bodies=None, body_positions=None,
                  joint_state=None, hits=True, fractions=False, out=None):
         """rayTest / rayTestBatch of every env, one launch (pnr_ray_test): range sensors and line-of-sight checks.  ``rays``: a
