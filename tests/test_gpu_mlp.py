@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from gpu_support import mlp_make as make, unpack_flat as _unpack_flat
+from mlp_grad_ref import emulate      # the float64 restatement with the kernels' bf16 rounding points
 
 pytestmark = pytest.mark.gpu
 NAMES = ["w1", "b1", "w2", "b2", "w3", "b3"] * 2
@@ -18,10 +19,6 @@ NAMES = ["w1", "b1", "w2", "b2", "w3", "b3"] * 2
 def rel(a, b):
     a, b = a.double(), b.double()
     return float((a - b).norm() / (b.norm() + 1e-30))
-
-
-def bf(x):
-    return x.to(torch.bfloat16).double()
 
 
 def net_input(obs, idx, filt):
@@ -37,25 +34,6 @@ def head_grads(B, dev, seed=5):
     g_head[0, :, 12:] = 0
     g_head[1, :, 1:] = 0                                    # the loss kernel never puts gradient on the padding rows
     return g_head
-
-
-def emulate(model, x, g_head):
-    """float64 restatement with the kernels' bf16 rounding points.  Returns heads [2][B][16] and 12 gradients."""
-    heads, grads = [], []
-    xb = bf(x)
-    for n, net in enumerate((model.policy, model.value)):
-        W1, b1, W2, b2, W3, b3 = [t.detach() for l in net if isinstance(l, torch.nn.Linear) for t in (l.weight, l.bias)]
-        h1 = bf(torch.tanh(xb @ bf(W1).t() + b1.double()))
-        h2 = bf(torch.tanh(h1 @ bf(W2).t() + b2.double()))
-        n3 = W3.shape[0]
-        head = torch.zeros(x.shape[0], 16, dtype=torch.float64, device=x.device)
-        head[:, :n3] = h2 @ bf(W3).t() + b3.double()
-        heads.append(head)
-        gb = bf(g_head[n])[:, :n3]
-        dz2 = bf((gb @ bf(W3)) * (1 - h2 * h2))
-        dz1 = bf((dz2 @ bf(W2)) * (1 - h1 * h1))
-        grads += [dz1.t() @ xb, dz1.sum(0), dz2.t() @ h1, dz2.sum(0), gb.t() @ h2, gb.sum(0)]
-    return torch.stack(heads), grads
 
 
 @pytest.mark.parametrize("B,rows,with_filter", [(1, None, False), (4099, 6000, True), (131072, None, False), (32768, 40000, True)])
