@@ -51,7 +51,8 @@ extern "C" {
  *      pnr_ray_test, pnr_world_step_wrenches, pnr_get_joint_states, pnr_world_step_targets, pnr_body_params_default,
  *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state, pnr_render_bodies, pnr_set_body_queries,
  *      pnr_render_cameras, pnr_body_grip_params_default, pnr_set_body_grip_params, pnr_set_body_grip, pnr_get_body_grip,
- *      pnr_ik_multi_params_default, pnr_solve_ik_multi, pnr_path_params_default, pnr_path_clearance */
+ *      pnr_ik_multi_params_default, pnr_solve_ik_multi, pnr_path_params_default, pnr_path_clearance,
+ *      pnr_ik_path_params_default, pnr_solve_ik_path */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -981,6 +982,103 @@ typedef struct pnr_path_params {
 int pnr_path_params_default(pnr_path_params* p);
 int pnr_path_clearance(pnr_handle h, const pnr_path_params* p, const float* waypoints, const float* body_positions,
                        float* summary, float* clearance, void* stream);
+
+/*
+ * Cartesian path inverse kinematics for every env, one call: the pointer (any link point) follows a piecewise-linear path of
+ * poses in the WORLD, and the answer is the joint path that does it — PyBullet users' loop of calculateInverseKinematics(...,
+ * currentPositions = previous) over interpolated targets.  Its q_path is what pnr_path_clearance (waypoints, C <= 256) and
+ * pnr_world_step_targets (row by row) take.
+ *   inputs     waypoint_pos is [num_envs][K][3] float32 (waypoints_per_env != 0) or [K][3], shared by all envs (== 0), K =
+ *              n_waypoints in 1 .. PNR_MAX_PATH_WAYPOINTS.  Pose and axis tasks: waypoint_quat [num_envs][K][4] or [K][4], x, y, z,
+ *              w.  M = substeps in 1 .. PNR_MAX_PATH_SUBSTEPS; C = 1 + (K - 1) M configurations.  task: pnr_ik_task, as in
+ *              pnr_solve_ik_multi.  There is no "env's own target" form.
+ *   targets    Configuration 0 is waypoint 0.  Configuration 1 + i M + (j - 1), j = 1 .. M, lies on segment i from waypoint a to
+ *              waypoint b, u = (float)j / (float)M: position a + u (b - a) in float32 (each operation rounded once); orientation
+ *              the normalised (1 - u) q_a + u h q_b, h = -1 if q_a . q_b < 0 else +1 (the dot product summed x, y, z, w; the
+ *              shortest-arc nlerp: its squared norm is >= 1/2 for unit inputs, and the kernel normalises every target quaternion
+ *              as pnr_solve_ik_multi does).  At j = M the target is EXACTLY waypoint b, by a select.
+ *   starts     num_starts = S in {1, 2, 4, 8, 16, 32, 64}; starts, starts_per_env and q_init (replacing start 0) exactly as in
+ *              pnr_solve_ik_multi, clamped into the limits.  S = 1 with q_init the env's own joints: "follow the line from where
+ *              the arm stands".
+ *   tracking   per start, independent of S, of the env's other starts and of every other env, bit for bit.  Configuration c
+ *              runs the task's unchanged iteration (pnr_solve_ik_multi's, with lambda^2 = damping^2 + error_damping (|e_p|^2 +
+ *              w^2 angle^2), max_step and the limit clamp) from the joints configuration c - 1 ended at; configuration 0 from
+ *              the start.  The cap is max_iterations for configuration 0 and track_iterations for every later one.  A
+ *              configuration is REACHED when the pose it ends at is within tolerance (and angle_tolerance in the pose and axis
+ *              tasks).  A start STOPS at its first configuration that is not reached, c_fail, and makes no further iteration:
+ *              its rows for c > c_fail are copies of row c_fail (joints, residual, angle) with iterations 0.  A start is TRACKED
+ *              when every configuration is reached; then c_fail = -1.
+ *   per start  travel = sum_j |q_0j - q_ref_j| (only with q_ref, [num_envs][6]) + sum_{c >= 1} sum_j |q_cj - q_(c-1)j|, float32,
+ *              accumulated one term at a time with c ascending, then j ascending, over the configurations up to c_fail;
+ *              max_jump = max over those c >= 1 of max_j |q_cj - q_(c-1)j| (0 for C = 1): a branch flip shows here.
+ *   selection  per env the smallest (not tracked, cost, start index), lexicographically: a tracked start's cost is its travel,
+ *              an untracked start's (float)(C - c_fail) — the start that got farthest wins.  A cost that is not finite counts as
+ *              +inf, so the order is total.  A NaN waypoint makes its env untracked (c_fail: the first configuration whose target
+ *              holds it) and leaves every other env's bits alone.
+ *   outputs    summary [num_envs][PNR_IK_PATH_SUMMARY_DIM] float32, 16-byte aligned, required, of the winner: [0] tracked (1 / 0);
+ *              [1] c_fail (-1: none); [2] the largest residual over configurations 0 .. c_fail (all when tracked; a residual
+ *              that is not a number is the largest); [3] the largest angle over the same (0 in the position task); [4] travel;
+ *              [5] max_jump; [6] the winner's start index; [7] the number of the env's tracked starts.
+ *              q_path [num_envs][C][6] (8-byte aligned) or NULL: the winner's joints.  residual_path, angle_path [num_envs][C]
+ *              float32, iterations_path [num_envs][C] int32, each or NULL: the winner's profile.
+ *              all_summary [num_envs][S][4] float32 (16-byte aligned) or NULL, per start: tracked, c_fail, travel, max_jump.
+ *              Nothing past these extents is written.  Every start's path is not an output.
+ *   the winner's rows under S > 1 are written by tracking the winner's start a second time with the same code: THE WINNER'S ROWS
+ *              OF AN S-START CALL EQUAL, BIT FOR BIT, THE ROWS OF A ONE-START CALL WHOSE q_init IS THAT START.  winner_rows
+ *              chooses how: PNR_IK_PATH_ROWS_SECOND_PASS runs the configurations again inside the launch with only the winners'
+ *              lanes live; PNR_IK_PATH_ROWS_SECOND_LAUNCH is a second launch of the same kernel at one lane per env, which reads
+ *              the start index from `summary`; PNR_IK_PATH_ROWS_AUTO (default) is the second launch.  The same bits either way.
+ * PNR_ERR_INVALID, nothing launched and no output touched (the message names the field), for: everything pnr_solve_ik_multi
+ * refuses for the task (a NULL or wrongly sized params or buffers struct, task, num_starts, NULL starts with num_starts > 1,
+ * link, the scalars, local_axis, misaligned pointers: summary and all_summary 16 bytes, q_path 8, the others 4); n_waypoints,
+ * substeps, track_iterations or winner_rows out of range; NULL waypoint_pos or summary; NULL waypoint_quat in a pose or axis
+ * task.  float32 arithmetic, asynchronous on `stream`, no allocation, no synchronisation: capturable into a graph.
+ */
+#define PNR_IK_PATH_SUMMARY_DIM 8
+enum pnr_ik_path_rows {
+    PNR_IK_PATH_ROWS_AUTO = 0,
+    PNR_IK_PATH_ROWS_SECOND_PASS = 1,
+    PNR_IK_PATH_ROWS_SECOND_LAUNCH = 2
+};
+typedef struct pnr_ik_path_params {
+    uint32_t struct_size;       /* sizeof(pnr_ik_path_params) */
+    int32_t  task;              /* pnr_ik_task */
+    int32_t  num_starts;        /* S: 1, 2, 4, 8, 16, 32 or 64; default 1 */
+    int32_t  starts_per_env;    /* 0 (default): `starts` is [S][6]; else [num_envs][S][6] */
+    int32_t  n_waypoints;       /* K: 1 .. PNR_MAX_PATH_WAYPOINTS; default 1 */
+    int32_t  waypoints_per_env; /* != 0: the waypoints are [num_envs][K][..], else [K][..] (default) */
+    int32_t  substeps;          /* M: 1 .. PNR_MAX_PATH_SUBSTEPS; default 8 */
+    int32_t  link;              /* 0..10; default 10 (robot:pointer) */
+    int32_t  max_iterations;    /* configuration 0's cap, 1..1024; default 32 */
+    int32_t  track_iterations;  /* every later configuration's cap, 1..1024; default 8 */
+    int32_t  winner_rows;       /* pnr_ik_path_rows; default PNR_IK_PATH_ROWS_AUTO */
+    int32_t  reserved;
+    double   local_point[3];    /* a point in the link's frame; default 0 */
+    double   local_axis[3];     /* axis task: as pnr_ik_pose_params.local_axis; default (1, 0, 0) */
+    double   damping;           /* > 0; default 1.0 (position), 0.03 (pose, axis) */
+    double   error_damping;     /* >= 0; default 0 (position), 0.01 (pose, axis) */
+    double   orientation_weight; /* w > 0, pose and axis tasks; default 10 */
+    double   max_step;          /* > 0, rad; default 0.5 */
+    double   tolerance;         /* >= 0, length; default 1e-3 */
+    double   angle_tolerance;   /* >= 0, rad, pose and axis tasks; default 1e-3 */
+} pnr_ik_path_params;
+typedef struct pnr_ik_path_buffers {
+    uint32_t struct_size;       /* sizeof(pnr_ik_path_buffers) */
+    uint32_t reserved;
+    const float* waypoint_pos;  /* [K][3] or [num_envs][K][3] */
+    const float* waypoint_quat; /* [K][4] or [num_envs][K][4] (x, y, z, w); pose and axis tasks, not read in the position task */
+    const float* starts;        /* [S][6] or [num_envs][S][6]; NULL only with num_starts 1 */
+    const float* q_init;        /* [num_envs][6] or NULL */
+    const float* q_ref;         /* [num_envs][6] or NULL */
+    float*   summary;           /* [num_envs][8], 16-byte aligned */
+    float*   q_path;            /* [num_envs][C][6], 8-byte aligned, or NULL */
+    float*   residual_path;     /* [num_envs][C] or NULL */
+    float*   angle_path;        /* [num_envs][C] or NULL */
+    int32_t* iterations_path;   /* [num_envs][C] or NULL */
+    float*   all_summary;       /* [num_envs][S][4], 16-byte aligned, or NULL */
+} pnr_ik_path_buffers;
+int pnr_ik_path_params_default(pnr_ik_path_params* p, int32_t task);
+int pnr_solve_ik_path(pnr_handle h, const pnr_ik_path_params* p, const pnr_ik_path_buffers* b, void* stream);
 
 /*
  * render('rgb_array') for every env in one launch (bullet_env.py:156-185 -> getCameraImage): one camera shared by all envs,

@@ -169,6 +169,27 @@ class PnrIkMultiBuffers(C.Structure):
         "converged_out", "all_q", "all_residual", "all_angle", "all_iterations")]
 
 
+IK_PATH_SUMMARY_DIM = 8         # pnr_solve_ik_path: tracked, c_fail, max residual, max angle, travel, max jump, start, tracked starts
+IK_PATH_ROWS_AUTO, IK_PATH_ROWS_SECOND_PASS, IK_PATH_ROWS_SECOND_LAUNCH = 0, 1, 2      # pnr_ik_path_params.winner_rows
+
+
+class PnrIkPathParams(C.Structure):
+    """pnr_ik_path_params of include/pioneer_amd.h (pnr_solve_ik_path's task, starts, path layout, the two caps and the law's parameters)."""
+    _fields_ = [("struct_size", C.c_uint32), ("task", C.c_int32), ("num_starts", C.c_int32), ("starts_per_env", C.c_int32),
+                ("n_waypoints", C.c_int32), ("waypoints_per_env", C.c_int32), ("substeps", C.c_int32), ("link", C.c_int32),
+                ("max_iterations", C.c_int32), ("track_iterations", C.c_int32), ("winner_rows", C.c_int32), ("reserved", C.c_int32),
+                ("local_point", C.c_double * 3), ("local_axis", C.c_double * 3), ("damping", C.c_double), ("error_damping", C.c_double),
+                ("orientation_weight", C.c_double), ("max_step", C.c_double), ("tolerance", C.c_double),
+                ("angle_tolerance", C.c_double)]
+
+
+class PnrIkPathBuffers(C.Structure):
+    """pnr_ik_path_buffers of include/pioneer_amd.h (pnr_solve_ik_path's device pointers: waypoints, starts, the summary, the winner's rows)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(name, C.c_void_p) for name in (
+        "waypoint_pos", "waypoint_quat", "starts", "q_init", "q_ref", "summary", "q_path", "residual_path", "angle_path",
+        "iterations_path", "all_summary")]
+
+
 class PnrConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
@@ -275,6 +296,8 @@ SIGNATURES = {
     "pnr_solve_ik_pose": (C.c_int, [_VP, C.POINTER(PnrIkPoseParams)] + [_VP] * 8),
     "pnr_ik_multi_params_default": (C.c_int, [C.POINTER(PnrIkMultiParams), C.c_int32]),
     "pnr_solve_ik_multi": (C.c_int, [_VP, C.POINTER(PnrIkMultiParams), C.POINTER(PnrIkMultiBuffers), _VP]),
+    "pnr_ik_path_params_default": (C.c_int, [C.POINTER(PnrIkPathParams), C.c_int32]),
+    "pnr_solve_ik_path": (C.c_int, [_VP, C.POINTER(PnrIkPathParams), C.POINTER(PnrIkPathBuffers), _VP]),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
     "pnr_render_bodies": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_render_cameras": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP]),

@@ -607,6 +607,225 @@ __global__ __launch_bounds__(kWave) void ik_multi_kernel(const IkMultiArgs A)
     if (A.converged) A.converged[e] = __builtin_popcountll(conv_mask & group);
 }
 
+// ---- Cartesian path inverse kinematics (pnr_solve_ik_path) -------------------------------------------------------------------
+// ik_multi_kernel's layout (lane = g S + s, a workgroup is one wave of 64 / S envs) around a loop over the C configurations of a
+// pointer path: configuration c is one solve of the task's law from the joints configuration c - 1 ended at, towards the target
+// interpolated between two waypoints (ik_path_target, contraction off: its roundings are the stated ones), under the cap
+// max_iter (configuration 0) or track_iter.  A start that does not reach a configuration stops there by selects: its joints and
+// its recorded residuals stay, so the rows after it are copies; once a ballot finds every lane of the wave stopped the remaining
+// configurations only store.  After the loop the env's winner is the smallest (not tracked, cost, start) of the same butterfly.
+// The winner's rows under S > 1 come from tracking its start again with the same code: `passes` 2 runs the configuration loop a
+// second time in the launch with only the winners' lanes live; `replay` is a second launch at one lane per env that takes the
+// start index from the summary the first launch wrote (DESIGN.md 3z has the measurement that chose).  No LDS, no scratch.
+constexpr int kIkPathSummary = 8;                                // floats per env of the summary
+
+struct IkPathArgs {
+    const float* wp_pos;       // [K][3], wp_per_env: [n][K][3]
+    const float* wp_quat;      // [K][4], wp_per_env: [n][K][4]: x, y, z, w (the pose kernel only)
+    const float* starts;       // [S][6], starts_per_env: [n][S][6]; null (S = 1 only)
+    const float* q_init;       // [n][6] or null: replaces start 0
+    const float* q_ref;        // [n][6] or null: travel starts with |q_0 - q_ref|
+    float* summary;            // [n][8], 16-byte aligned (replay: read, column 6 is the start to track)
+    float* q_path;             // [n][C][6], 8-byte aligned, or null
+    float* residual;           // [n][C] or null
+    float* angle;              // [n][C] or null
+    int* iterations;           // [n][C] or null
+    float* all_summary;        // [n][S][4], 16-byte aligned, or null
+    long long n;
+    ChainPoint point;
+    int log2s;                 // lanes per env of this launch (replay: 0)
+    int log2t;                 // starts per env of the table
+    int starts_per_env, wp_per_env;
+    int passes, store, replay; // store: the last pass writes the rows; replay: no selection, no summary
+    int K, M, C;
+    int max_iter, track_iter, axis_mode;
+    V3 axis;
+    float damping2, error_damping, weight, max_step, tol, angle_tol;
+};
+
+// start s of env e as ik_multi_start gives it (the table's stride is its own S, whatever the launch's lanes per env)
+__device__ __forceinline__ void ik_path_start(const IkPathArgs& A, const long long e, const int s, float (&q)[kDof])
+{
+    const float* row = nullptr;
+    if (s == 0 && A.q_init) row = A.q_init + kDof * e;
+    else if (A.starts) row = A.starts + kDof * ((A.starts_per_env ? (e << A.log2t) : 0ll) + s);
+#pragma unroll
+    for (int i = 0; i < kDof; ++i) q[i] = row ? row[i] : 0.f;
+    static_for<kDof>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        q[J] = fminf(fmaxf(q[J], limit_lo(J)), limit_hi(J));
+    });
+}
+
+// The target of the configuration j of segment i (j = 0: waypoint i itself, only configuration 0; j = M: waypoint i + 1 itself):
+// a + u (b - a), u = (float)j / (float)M, each operation rounded once; the quaternion (1 - u) q_a + u h q_b, h = -1 where
+// q_a . q_b < 0, NOT normalised here (the kernel normalises every target quaternion).
+template <bool POSE>
+__device__ __forceinline__ void ik_path_target(const IkPathArgs& A, const long long wp0, const int i, const int j, V3& tgt, float (&tq)[4])
+{
+#pragma clang fp contract(off)
+    const int ib = i + 1 < A.K ? i + 1 : A.K - 1;
+    const float* pa = A.wp_pos + 3 * (wp0 + i);
+    const float* pb = A.wp_pos + 3 * (wp0 + ib);
+    const float u = (float)j / (float)A.M;
+    const V3 a = {pa[0], pa[1], pa[2]}, b = {pb[0], pb[1], pb[2]};
+    const V3 mid = {a.x + u * (b.x - a.x), a.y + u * (b.y - a.y), a.z + u * (b.z - a.z)};
+    tgt = j == 0 ? a : (j == A.M ? b : mid);
+    if constexpr (POSE) {
+        const float* qa = A.wp_quat + 4 * (wp0 + i);
+        const float* qb = A.wp_quat + 4 * (wp0 + ib);
+        float d = qa[0] * qb[0];
+        d = d + qa[1] * qb[1]; d = d + qa[2] * qb[2]; d = d + qa[3] * qb[3];
+        const float v = 1.f - u, w = d < 0.f ? -u : u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float m = v * qa[k] + w * qb[k];
+            tq[k] = j == 0 ? qa[k] : (j == A.M ? qb[k] : m);
+        }
+    }
+}
+
+// POSE: the 6 x 6 system (FULL, or AXIS by the wave-uniform axis_mode), else the 3 x 3 one
+template <bool POSE>
+__global__ __launch_bounds__(kWave) void ik_path_kernel(const IkPathArgs A)
+{
+    const int lane = threadIdx.x;
+    const int S = 1 << A.log2s;
+    const int sl = lane & (S - 1);
+    const long long t = (long long)blockIdx.x * kWave + lane;                  // = e S + s
+    const long long e = t >> A.log2s;
+    const bool live = e < A.n;                                                 // (a group is live or not as a whole)
+    const long long er = live ? e : 0ll;                                       // (a lane past the batch reads env 0's inputs and stores nothing)
+    const unsigned long long group = (~0ull >> (kWave - S)) << (lane - sl);
+    int s = sl;
+    if (A.replay) s = min(max((int)A.summary[kIkPathSummary * er + 6], 0), (1 << A.log2t) - 1);
+    const long long wp0 = A.wp_per_env ? er * A.K : 0ll;
+    const long long row0 = er * A.C;
+    int win = s;
+    for (int pass = 0; pass < A.passes; ++pass) {
+        const bool store = A.store && pass == A.passes - 1;                    // wave-uniform
+        const bool mine = live && s == win;                                    // (pass 0: every live lane)
+        bool stopped = !mine;
+        float q[kDof];
+        ik_path_start(A, er, s, q);
+        int cfail = -1, seg = 0, j = 0;
+        float max_res = 0.f, max_ang = 0.f, travel = 0.f, max_jump = 0.f, rdist = 0.f, rang = 0.f;
+        for (int cfg = 0; cfg < A.C; ++cfg) {
+            const bool was = stopped;
+            int iters = 0;
+            if (__builtin_amdgcn_ballot_w64(!stopped) != 0) {
+                float prev[kDof];
+#pragma unroll
+                for (int i = 0; i < kDof; ++i) prev[i] = q[i];
+                V3 tgt;
+                float tq[4] = {0.f, 0.f, 0.f, 1.f};
+                ik_path_target<POSE>(A, wp0, seg, j, tgt, tq);
+                // the target's rotation as ik_multi_kernel forms it
+                float qx = tq[0], qy = tq[1], qz = tq[2], qw = tq[3];
+                const float qinv = 1.0f / sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
+                qx *= qinv; qy *= qinv; qz *= qinv; qw *= qinv;
+                const V3 t0 = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy + qz * qw), 2.f * (qx * qz - qy * qw)};
+                const V3 t1 = {2.f * (qx * qy - qz * qw), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz + qx * qw)};
+                const V3 t2 = {2.f * (qx * qz + qy * qw), 2.f * (qy * qz - qx * qw), 1.f - 2.f * (qx * qx + qy * qy)};
+                const V3 tv = A.axis.x * t0 + A.axis.y * t1 + A.axis.z * t2;
+                const int cap = cfg == 0 ? A.max_iter : A.track_iter;
+                bool frozen = stopped, conv = false;
+                float dist = 0.f, angle = 0.f;
+                for (int it = 0; ; ++it) {
+                    float c[kDof], sj[kDof];
+#pragma unroll
+                    for (int i = 0; i < kDof; ++i) sincos_bounded(q[i], sj[i], c[i]);    // q is inside the limits
+                    V3 lin[kDof], ang[kDof], point;
+                    M3 R;
+                    chain_jacobian(c, sj, A.point, lin, ang, point, POSE ? &R : nullptr);
+                    const V3 err = tgt - point;
+                    const float dist2 = dot(err, err);
+                    dist = sqrtf(dist2);
+                    V3 sv = {0.f, 0.f, 0.f};
+                    float sn = 0.f;
+                    if constexpr (POSE) {
+                        float cs;
+                        if (A.axis_mode) {
+                            const V3 u = mul(R, A.axis);
+                            sv = cross(u, tv); cs = dot(u, tv);
+                        } else {
+                            const V3 r0 = col(R, 0), r1 = col(R, 1), r2 = col(R, 2);
+                            sv = 0.5f * (cross(r0, t0) + cross(r1, t1) + cross(r2, t2));
+                            cs = 0.5f * (dot(r0, t0) + dot(r1, t1) + dot(r2, t2) - 1.f);
+                        }
+                        sn = sqrtf(dot(sv, sv));
+                        angle = atan2f(sn, cs);
+                    }
+                    conv = POSE ? (dist <= A.tol && angle <= A.angle_tol) : dist <= A.tol;
+                    if (it == cap) break;                                        // the pose of the row: its residuals
+                    frozen = frozen || conv;
+                    if (__builtin_amdgcn_ballot_w64(!frozen) == 0) break;
+                    float dq[kDof], big;
+                    if constexpr (POSE) ik_pose_step(lin, ang, err, dist2, sv, sn, angle, A.weight, A.damping2, A.error_damping, dq, big);
+                    else ik_position_step(lin, err, A.damping2 + A.error_damping * dist2, dq, big);
+                    const float scale = big > A.max_step ? A.max_step * fast_rcp(big) : 1.f;
+                    static_for<kDof>([&](auto jc) {
+                        constexpr int J = decltype(jc)::value;
+                        const float qn = fminf(fmaxf(q[J] + scale * dq[J], limit_lo(J)), limit_hi(J));
+                        q[J] = frozen ? q[J] : qn;
+                    });
+                    iters += frozen ? 0 : 1;
+                }
+                // the bookkeeping of the lanes still tracking; a stopped lane keeps what it recorded at its last configuration
+                rdist = was ? rdist : dist;
+                rang = was ? rang : angle;
+                max_res = was || rdist <= max_res ? max_res : rdist;             // (a residual that is not a number is the largest)
+                max_ang = was || rang <= max_ang ? max_ang : rang;
+                const float* refp = A.q_ref ? A.q_ref + kDof * er : nullptr;
+#pragma unroll
+                for (int i = 0; i < kDof; ++i) {
+                    const float base = cfg > 0 ? prev[i] : (refp ? refp[i] : q[i]);
+                    const float d = fabsf(q[i] - base);
+                    travel = was ? travel : travel + d;
+                    max_jump = was || cfg == 0 ? max_jump : fmaxf(max_jump, d);
+                }
+                cfail = !was && !conv ? cfg : cfail;
+                stopped = was || !conv;
+            } else if (!store) {
+                break;                                                           // every lane of the wave has stopped: nothing left to do
+            }
+            if (store && mine) {
+                const long long r = row0 + cfg;
+                if (A.q_path) {
+                    float2* qo = reinterpret_cast<float2*>(A.q_path) + 3 * r;
+                    qo[0] = make_float2(q[0], q[1]); qo[1] = make_float2(q[2], q[3]); qo[2] = make_float2(q[4], q[5]);
+                }
+                if (A.residual) A.residual[r] = rdist;
+                if (A.angle) A.angle[r] = rang;
+                if (A.iterations) A.iterations[r] = iters;
+            }
+            if (++j > A.M) { j = 1; ++seg; }
+        }
+        if (pass > 0 || A.replay) continue;
+        // the env's winner: the smallest (not tracked, cost, start); a cost that is not finite is +inf (costs are >= 0, so their
+        // bit patterns order as they do, and the top bit is free for "not tracked")
+        const bool tracked = live && cfail < 0;
+        const unsigned long long tracked_mask = __builtin_amdgcn_ballot_w64(tracked);
+        float cost = tracked ? travel : (float)(A.C - cfail);
+        cost = cost < __builtin_inff() ? cost : __builtin_inff();
+        unsigned key = __float_as_uint(cost) | (tracked ? 0u : 0x80000000u);
+        for (int m = 1; m < S; m <<= 1) {
+            const unsigned okey = (unsigned)__shfl_xor((int)key, m);
+            const int owin = __shfl_xor(win, m);
+            const bool take = okey < key || (okey == key && owin < win);
+            key = take ? okey : key;
+            win = take ? owin : win;
+        }
+        if (!live) continue;
+        if (A.all_summary)
+            reinterpret_cast<float4*>(A.all_summary)[t] = make_float4(tracked ? 1.f : 0.f, (float)cfail, travel, max_jump);
+        if (s != win) continue;
+        float4* sm = reinterpret_cast<float4*>(A.summary) + 2 * e;
+        sm[0] = make_float4(tracked ? 1.f : 0.f, (float)cfail, max_res, max_ang);
+        sm[1] = make_float4(travel, max_jump, (float)s, (float)__builtin_popcountll(tracked_mask & group));
+    }
+}
+
 }  // namespace pnr
 
 #pragma clang fp contract(off)

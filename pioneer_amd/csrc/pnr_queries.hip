@@ -401,6 +401,115 @@ int pnr_solve_ik_multi(pnr_handle h, const pnr_ik_multi_params* p, const pnr_ik_
     return PNR_OK;
 }
 
+int pnr_ik_path_params_default(pnr_ik_path_params* p, int32_t task)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_ik_path_params_default: null params");
+    if (task != PNR_IK_TASK_POSITION && task != PNR_IK_TASK_POSE && task != PNR_IK_TASK_AXIS)
+        return fail(nullptr, PNR_ERR_INVALID, "pnr_ik_path_params_default: task %d outside {0, 1, 2} (position, pose, axis)", task);
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_ik_path_params);
+    p->task = task;
+    p->num_starts = 1;
+    p->n_waypoints = 1; p->substeps = 8;
+    p->link = kNumLinks - 1;
+    p->max_iterations = 32; p->track_iterations = 8;
+    p->local_axis[0] = 1.0;
+    const bool pose = task != PNR_IK_TASK_POSITION;           // each task's own defaults, as pnr_ik_multi_params_default
+    p->damping = pose ? 0.03 : 1.0;
+    p->error_damping = pose ? 0.01 : 0.0;
+    p->orientation_weight = 10.0;
+    p->max_step = 0.5;
+    p->tolerance = 1e-3;
+    p->angle_tolerance = 1e-3;
+    return PNR_OK;
+}
+
+int pnr_solve_ik_path(pnr_handle h, const pnr_ik_path_params* p, const pnr_ik_path_buffers* b, void* stream)
+{
+    const char* call = "pnr_solve_ik_path";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "%s: null params", call);
+    if (!b) return fail(h, PNR_ERR_INVALID, "%s: null buffers", call);
+    if (p->struct_size != sizeof(pnr_ik_path_params))
+        return fail(h, PNR_ERR_INVALID, "%s: params struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_ik_path_params));
+    if (b->struct_size != sizeof(pnr_ik_path_buffers))
+        return fail(h, PNR_ERR_INVALID, "%s: buffers struct_size %u, want %zu", call, b->struct_size, sizeof(pnr_ik_path_buffers));
+    if (p->task != PNR_IK_TASK_POSITION && p->task != PNR_IK_TASK_POSE && p->task != PNR_IK_TASK_AXIS)
+        return fail(h, PNR_ERR_INVALID, "%s: task %d outside {0, 1, 2} (position, pose, axis)", call, p->task);
+    const bool pose = p->task != PNR_IK_TASK_POSITION;
+    if (!b->waypoint_pos) return fail(h, PNR_ERR_INVALID, "%s: null waypoint_pos", call);
+    if (!b->summary) return fail(h, PNR_ERR_INVALID, "%s: null summary", call);
+    if (pose && !b->waypoint_quat) return fail(h, PNR_ERR_INVALID, "%s: null waypoint_quat", call);
+    int log2s = -1;
+    for (int k = 0; k <= 6; ++k) if (p->num_starts == (1 << k)) log2s = k;
+    if (log2s < 0) return fail(h, PNR_ERR_INVALID, "%s: num_starts %d is not one of 1, 2, 4, 8, 16, 32, 64", call, p->num_starts);
+    if (!b->starts && p->num_starts > 1) return fail(h, PNR_ERR_INVALID, "%s: null starts with num_starts %d", call, p->num_starts);
+    if (p->n_waypoints < 1 || p->n_waypoints > PNR_MAX_PATH_WAYPOINTS)
+        return fail(h, PNR_ERR_INVALID, "%s: n_waypoints %d outside 1..%d", call, p->n_waypoints, PNR_MAX_PATH_WAYPOINTS);
+    if (p->substeps < 1 || p->substeps > PNR_MAX_PATH_SUBSTEPS)
+        return fail(h, PNR_ERR_INVALID, "%s: substeps %d outside 1..%d", call, p->substeps, PNR_MAX_PATH_SUBSTEPS);
+    if (p->winner_rows != PNR_IK_PATH_ROWS_AUTO && p->winner_rows != PNR_IK_PATH_ROWS_SECOND_PASS && p->winner_rows != PNR_IK_PATH_ROWS_SECOND_LAUNCH)
+        return fail(h, PNR_ERR_INVALID, "%s: winner_rows %d outside {0, 1, 2} (auto, second pass, second launch)", call, p->winner_rows);
+    if (p->link < 0 || p->link >= kNumLinks) return fail(h, PNR_ERR_INVALID, "%s: link %d outside 0..%d", call, p->link, kNumLinks - 1);
+    if (p->max_iterations < 1 || p->max_iterations > 1024)
+        return fail(h, PNR_ERR_INVALID, "%s: max_iterations %d outside 1..1024", call, p->max_iterations);
+    if (p->track_iterations < 1 || p->track_iterations > 1024)
+        return fail(h, PNR_ERR_INVALID, "%s: track_iterations %d outside 1..1024", call, p->track_iterations);
+    const struct { double v; const char* name; bool zero_ok, pose_only; } scalars[] = {
+        {p->damping, "damping", false, false}, {p->max_step, "max_step", false, false}, {p->orientation_weight, "orientation_weight", false, true},
+        {p->error_damping, "error_damping", true, false}, {p->tolerance, "tolerance", true, false}, {p->angle_tolerance, "angle_tolerance", true, true}};
+    for (const auto& s : scalars)
+        if ((pose || !s.pose_only) && !(std::isfinite(s.v) && (s.zero_ok ? s.v >= 0 : s.v > 0)))
+            return fail(h, PNR_ERR_INVALID, "%s: %s must be finite and %s 0", call, s.name, s.zero_ok ? ">=" : ">");
+    if (!finite_all(p->local_point, 3)) return fail(h, PNR_ERR_INVALID, "%s: non-finite local_point", call);
+    const double* ax = p->local_axis;
+    const double axis_len = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+    if (pose && (!finite_all(ax, 3) || !std::isfinite(axis_len) || !(axis_len > 0)))
+        return fail(h, PNR_ERR_INVALID, "%s: local_axis must be finite and not zero", call);
+    if (const int rc = check_aligned(h, call, {{b->summary, "summary", 16}, {b->all_summary, "all_summary", 16}, {b->q_path, "q_path", 8},
+                                               {b->waypoint_pos, "waypoint_pos", 4}, {b->waypoint_quat, "waypoint_quat", 4},
+                                               {b->starts, "starts", 4}, {b->q_init, "q_init", 4}, {b->q_ref, "q_ref", 4},
+                                               {b->residual_path, "residual_path", 4}, {b->angle_path, "angle_path", 4},
+                                               {b->iterations_path, "iterations_path", 4}})) return rc;
+    const long long groups = ((h->n << log2s) + kWave - 1) / kWave;           // one start per lane, 64 >> log2s envs per wave
+    if (groups > 0x7fffffffLL) return fail(h, PNR_ERR_INVALID, "%s: %lld envs x %d starts exceed one launch", call, h->n, p->num_starts);
+    IkPathArgs A;
+    A.wp_pos = b->waypoint_pos; A.wp_quat = b->waypoint_quat; A.starts = b->starts; A.q_init = b->q_init; A.q_ref = b->q_ref;
+    A.summary = b->summary; A.q_path = b->q_path; A.residual = b->residual_path; A.angle = b->angle_path;
+    A.iterations = b->iterations_path; A.all_summary = b->all_summary;
+    A.n = h->n;
+    A.point = chain_point(p->link, p->local_point);
+    A.log2s = log2s; A.log2t = log2s; A.starts_per_env = p->starts_per_env != 0; A.wp_per_env = p->waypoints_per_env != 0;
+    A.K = p->n_waypoints; A.M = p->substeps; A.C = 1 + (p->n_waypoints - 1) * p->substeps;
+    A.max_iter = p->max_iterations; A.track_iter = p->track_iterations; A.axis_mode = p->task == PNR_IK_TASK_AXIS;
+    A.axis = pose ? V3{(float)(ax[0] / axis_len), (float)(ax[1] / axis_len), (float)(ax[2] / axis_len)} : V3{1.f, 0.f, 0.f};
+    A.damping2 = (float)(p->damping * p->damping); A.error_damping = (float)p->error_damping;
+    A.weight = pose ? (float)p->orientation_weight : 0.f;                      // (the position task: no orientation rows, angle 0)
+    A.max_step = (float)p->max_step; A.tol = (float)p->tolerance; A.angle_tol = pose ? (float)p->angle_tolerance : 0.f;
+    // the winner's rows: a one-start call writes them as it tracks; under S > 1 the winner's start is tracked a second time,
+    // in the launch (two passes) or by a second launch at one lane per env (auto: kIkPathAutoRows, measured: DESIGN.md 3z)
+    const bool rows = b->q_path || b->residual_path || b->angle_path || b->iterations_path;
+    constexpr int kIkPathAutoRows = PNR_IK_PATH_ROWS_SECOND_LAUNCH;
+    const int how = p->winner_rows == PNR_IK_PATH_ROWS_AUTO ? kIkPathAutoRows : p->winner_rows;
+    const bool again = rows && log2s > 0;
+    const bool relaunch = again && how == PNR_IK_PATH_ROWS_SECOND_LAUNCH;
+    A.replay = 0; A.passes = again && !relaunch ? 2 : 1; A.store = rows && !relaunch;
+    DeviceGuard g(h->device);
+    const auto launch = [&](const IkPathArgs& X, const long long waves) {
+        if (pose) hipLaunchKernelGGL(ik_path_kernel<true>, dim3((unsigned)waves), dim3(kWave), 0, (hipStream_t)stream, X);
+        else hipLaunchKernelGGL(ik_path_kernel<false>, dim3((unsigned)waves), dim3(kWave), 0, (hipStream_t)stream, X);
+    };
+    launch(A, groups);
+    HIP_TRY(h, hipGetLastError());
+    if (relaunch) {
+        IkPathArgs B = A;
+        B.log2s = 0; B.replay = 1; B.passes = 1; B.store = 1; B.all_summary = nullptr;
+        launch(B, (h->n + kWave - 1) / kWave);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return PNR_OK;
+}
+
 int pnr_contact_params_default(pnr_contact_params* p)
 {
     if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_contact_params_default: null params");

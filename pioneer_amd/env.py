@@ -234,6 +234,22 @@ class PioneerKinematicEnv(compat.GymEnv):
             q, residual, angle = res["q"], res["residual"], res["angle"]
         return q[0].double().cpu().numpy(), float(residual[0].item()), float(angle[0].item())
 
+    def solve_ik_path(self, waypoints, orientations=None, substeps: int = 8, **kw):
+        """The joint path on which robot:pointer follows the piecewise-linear world path ``waypoints`` (``[K, 3]``; with
+        ``orientations`` ``[K, 4]``, quaternions x, y, z, w, the pointer's pose), ``substeps`` targets per segment, each solved from
+        the joints the one before ended at (PioneerVectorEnv.solve_ik_path, whose other arguments ``kw`` takes: ``starts``,
+        ``from_current``, ``q_init``, ``q_ref``, ``align_axis``, the iteration caps and tolerances).  Returns an ``IkPath``."""
+        from .scene import IkPath
+        wp = np.asarray(waypoints, dtype=np.float32).reshape(-1, 3)
+        wq = None if orientations is None else np.asarray(orientations, dtype=np.float32).reshape(-1, 4)
+        for key in ("q_init", "q_ref"):
+            if kw.get(key) is not None:
+                kw[key] = self._q_ref(kw[key])
+        res = self._vec.solve_ik_path(wp, wq, substeps=substeps, path=True, **kw)
+        sm = res["summary"][0].double().cpu().numpy()
+        return IkPath(bool(sm[0] > 0), int(sm[1]), res["q_path"][0].double().cpu().numpy(), float(sm[2]), float(sm[3]), float(sm[4]),
+                      float(sm[5]))
+
     def target_reachable(self, within=None, starts=None) -> bool:
         """Can the pointer get within ``within`` (default ``done_distance``) of the env's target inside the joint limits
         (PioneerVectorEnv.target_reachable)?  ``starts`` None: from the rest pose alone; else the best of that many starts."""

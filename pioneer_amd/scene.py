@@ -170,6 +170,20 @@ def ik_start_table(S: int, seed: int = 0) -> np.ndarray:
     return table.astype(np.float32)
 
 
+class IkPath(NamedTuple):
+    """``PioneerKinematicEnv.solve_ik_path``'s answer for the one env: was every configuration of the pointer path reached, the
+    first configuration that was not (-1: none), the joint path (float64 ``[C, 6]``; the rows after ``fail_at`` repeat that row), the
+    largest distance and angle (rad) left over the configurations up to ``fail_at``, the joint travel sum |dq_j| over the path and
+    the largest single joint move between two neighbouring configurations (a branch flip shows there)."""
+    tracked: bool
+    fail_at: int
+    q_path: np.ndarray
+    max_residual: float
+    max_angle: float
+    travel: float
+    max_jump: float
+
+
 class PathClearance(NamedTuple):
     """``Scene.path_clearance``'s answer for the one env: is the sampled path free, the smallest clearance on it, the path
     coordinate t where it is attained (segment index + fraction), the URDF link and the created body (``Scene.body_id``; 0 where

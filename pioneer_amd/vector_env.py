@@ -628,22 +628,7 @@ class PioneerVectorEnv:
         if policy not in ("best", "first"):
             raise AssertionError(f'policy must be "best" or "first", got {policy!r}')
         p.policy = _lib.IK_MULTI_FIRST if policy == "first" else _lib.IK_MULTI_BEST
-        if isinstance(starts, (int, np.integer)):
-            S = int(starts)
-            if S not in _lib.IK_MULTI_STARTS:
-                raise AssertionError(f"starts must be one of {_lib.IK_MULTI_STARTS}, got {S}")
-            tables = self.__dict__.setdefault("_ik_start_tables", {})
-            if (S, int(seed)) not in tables:
-                from .scene import ik_start_table
-                tables[(S, int(seed))] = torch.from_numpy(ik_start_table(S, seed)).to(self.device)
-            table = tables[(S, int(seed))]
-        else:
-            shape = tuple(starts.shape)
-            S = int(shape[-2]) if len(shape) in (2, 3) else 0
-            if S not in _lib.IK_MULTI_STARTS:
-                raise AssertionError(f"starts must be [S, 6] or [N, S, 6] with S one of {_lib.IK_MULTI_STARTS}, got {shape}")
-            table = self._in(starts, (S, 6) if len(shape) == 2 else (n, S, 6), torch.float32, "starts")
-            p.starts_per_env = int(len(shape) == 3)
+        S, table, p.starts_per_env = self._ik_starts(starts, seed)
         p.num_starts, p.link, p.max_iterations = S, int(link), int(max_iterations)
         if local_point is not None:
             for k in range(3):
@@ -676,6 +661,123 @@ class PioneerVectorEnv:
                         ("all_iterations", res.get("all_iterations"))):
             setattr(b, name, None if t is None else t.data_ptr())
         self._chk(self.lib.pnr_solve_ik_multi(self._h, p, b, self._stream()))
+        return res
+
+    def _ik_starts(self, starts, seed):
+        """``solve_ik_multi``'s ``starts`` argument as (S, the table on the device, is it per env)."""
+        n = self.num_envs
+        if isinstance(starts, (int, np.integer)):
+            S = int(starts)
+            if S not in _lib.IK_MULTI_STARTS:
+                raise AssertionError(f"starts must be one of {_lib.IK_MULTI_STARTS}, got {S}")
+            tables = self.__dict__.setdefault("_ik_start_tables", {})
+            if (S, int(seed)) not in tables:
+                from .scene import ik_start_table
+                tables[(S, int(seed))] = torch.from_numpy(ik_start_table(S, seed)).to(self.device)
+            return S, tables[(S, int(seed))], 0
+        shape = tuple(starts.shape)
+        S = int(shape[-2]) if len(shape) in (2, 3) else 0
+        if S not in _lib.IK_MULTI_STARTS:
+            raise AssertionError(f"starts must be [S, 6] or [N, S, 6] with S one of {_lib.IK_MULTI_STARTS}, got {shape}")
+        return S, self._in(starts, (S, 6) if len(shape) == 2 else (n, S, 6), torch.float32, "starts"), int(len(shape) == 3)
+
+    def own_joints(self):
+        """The env's own joint positions as a new float32 ``[N, 6]`` device tensor, read from the state on the device: dynamics
+        mode the simulated q, kinematic mode r.  Never synchronises."""
+        if self.engine_config.mode == "dynamic":
+            return self.get_dyn_state()[0:6].t().contiguous()
+        return self.get_state()[12:18].view(torch.float32).t().contiguous()
+
+    def solve_ik_path(self, waypoints, orientations=None, substeps=8, starts=1, q_init=None, from_current=False, q_ref=None,
+                      align_axis=None, link=10, local_point=None, max_iterations=32, track_iterations=8, damping=None,
+                      error_damping=None, orientation_weight=10.0, max_step=0.5, tolerance=1e-3, angle_tolerance=1e-3, seed=0,
+                      path=True, profile=False, return_all=False, winner_rows=0, out=None):
+        """Cartesian path inverse kinematics for every env (pnr_solve_ik_path): the joint path on which ``local_point`` of ``link``
+        follows a piecewise-linear path in the WORLD — PyBullet users' loop of ``calculateInverseKinematics(...,
+        currentPositions=previous)`` over interpolated targets, in one call.
+
+        ``waypoints``: float32 ``[K, 3]`` (one path for all envs) or ``[N, K, 3]``, K <= 256; ``orientations`` None (the position
+        task, ``solve_ik``'s law and defaults) or ``[K, 4]`` / ``[N, K, 4]`` quaternions x, y, z, w (the pose task, ``solve_ik_pose``'s
+        law and defaults; ``align_axis`` as there).  With M = ``substeps`` (1 .. 64) there are C = 1 + (K - 1) M configurations:
+        waypoint 0, then on segment i from a to b the targets a + (j / M)(b - a), j = 1 .. M (j = M: b itself), the orientation by the
+        shortest-arc normalised lerp.  Configuration c is one solve from the joints configuration c - 1 ended at, with at most
+        ``track_iterations`` iterations (configuration 0: from the start, ``max_iterations``).  A configuration is reached when
+        its pose is within ``tolerance`` (and ``angle_tolerance``); a start stops at the first that is not (``fail_at``), and
+        its later rows are copies of that row.  ``starts`` as in ``solve_ik_multi`` (an int S, ``[S, 6]``, ``[N, S, 6]``); ``q_init``
+        ``[N, 6]`` replaces start 0; ``from_current=True`` puts the env's own joints there (``own_joints()``; an error together
+        with ``q_init``).  Per env the winner is the tracked start of the least travel (sum over the path of |dq_j|, plus
+        |q_0 - q_ref| with ``q_ref`` ``[N, 6]``), else the start that got farthest.
+
+        Returns a dict of device tensors: ``summary`` ``[N, 8]`` and its columns as views or small casts: ``tracked`` (bool),
+        ``fail_at`` (int64, -1: none), ``max_residual``, ``max_angle`` (the largest over the configurations up to ``fail_at``),
+        ``travel``, ``max_jump`` (the largest single joint move between two configurations: a branch flip shows here), ``start``
+        (int64: the winner's), ``tracked_starts`` (int64); ``q_path`` ``[N, C, 6]`` unless ``path=False``; with ``profile``
+        ``residual``, ``angle`` ``[N, C]`` and ``iterations`` ``[N, C]`` int32; with ``return_all`` ``all_summary`` ``[N, S, 4]`` (per start:
+        tracked, fail_at, travel, max_jump).  ``winner_rows``: how the winner's rows are written under S > 1 (``_lib.IK_PATH_ROWS_*``;
+        the same bits for every value).  ``out`` may carry preallocated ``summary`` / ``q_path`` / ``residual`` / ``angle`` /
+        ``iterations`` / ``all_summary`` tensors, written in place.  Never synchronises.
+
+        The two follow-ups::
+
+            res = env.solve_ik_path(line, substeps=8, from_current=True)
+            free = env.path_clearance(res["q_path"], substeps=1)["free"]        # C <= 256: is the joint path clear of the bodies?
+            for c in range(res["q_path"].shape[1]):                             # .. and the motors follow it row by row
+                env.world_step(motor_targets=res["q_path"][:, c])
+        """
+        self._check_handle()
+        n = self.num_envs
+        pose = orientations is not None
+        if align_axis is not None and not pose:
+            raise AssertionError("align_axis goes with orientations")
+        if from_current and q_init is not None:
+            raise AssertionError("from_current puts the env's own joints in as q_init: give one of the two")
+        task = _lib.IK_TASK_POSITION if not pose else (_lib.IK_TASK_POSE if align_axis is None else _lib.IK_TASK_AXIS)
+        p = _lib.PnrIkPathParams()
+        self._chk(self.lib.pnr_ik_path_params_default(p, task))
+
+        def way(t, width, name):
+            if not isinstance(t, torch.Tensor):
+                t = torch.as_tensor(np.asarray(t), dtype=torch.float32)
+            if t.dim() not in (2, 3) or t.shape[-1] != width or (t.dim() == 3 and t.shape[0] != n):
+                raise AssertionError(f"{name} must have shape (K, {width}) or ({n}, K, {width}), got {tuple(t.shape)}")
+            return self._in(t, tuple(t.shape), torch.float32, name)
+
+        wp = way(waypoints, 3, "waypoints")
+        wq = way(orientations, 4, "orientations") if pose else None
+        if pose and tuple(wq.shape[:-1]) != tuple(wp.shape[:-1]):
+            raise AssertionError(f"orientations {tuple(wq.shape)} do not go with waypoints {tuple(wp.shape)}")
+        S, table, p.starts_per_env = self._ik_starts(starts, seed)
+        p.num_starts, p.n_waypoints, p.waypoints_per_env, p.substeps = S, int(wp.shape[-2]), int(wp.dim() == 3), int(substeps)
+        p.link, p.max_iterations, p.track_iterations, p.winner_rows = int(link), int(max_iterations), int(track_iterations), int(winner_rows)
+        if local_point is not None:
+            for k in range(3):
+                p.local_point[k] = float(local_point[k])
+        if align_axis is not None:
+            for k in range(3):
+                p.local_axis[k] = float(align_axis[k])
+        if damping is not None:
+            p.damping = float(damping)
+        if error_damping is not None:
+            p.error_damping = float(error_damping)
+        p.orientation_weight, p.max_step = float(orientation_weight), float(max_step)
+        p.tolerance, p.angle_tolerance = float(tolerance), float(angle_tolerance)
+        qi = self.own_joints() if from_current else (None if q_init is None else self._in(q_init, (n, 6), torch.float32, "q_init"))
+        qr = None if q_ref is None else self._in(q_ref, (n, 6), torch.float32, "q_ref")
+        configs = 1 + (p.n_waypoints - 1) * p.substeps
+        i32 = torch.int32
+        res = self._asked(out, (("summary", True, (n, _lib.IK_PATH_SUMMARY_DIM), torch.float32), ("q_path", path, (n, max(configs, 1), 6), torch.float32),
+                                ("residual", profile, (n, max(configs, 1)), torch.float32), ("angle", profile, (n, max(configs, 1)), torch.float32),
+                                ("iterations", profile, (n, max(configs, 1)), i32), ("all_summary", return_all, (n, S, 4), torch.float32)), "")
+        b = _lib.PnrIkPathBuffers()
+        b.struct_size = C.sizeof(_lib.PnrIkPathBuffers)
+        for name, t in (("waypoint_pos", wp), ("waypoint_quat", wq), ("starts", table), ("q_init", qi), ("q_ref", qr),
+                        ("summary", res["summary"]), ("q_path", res.get("q_path")), ("residual_path", res.get("residual")),
+                        ("angle_path", res.get("angle")), ("iterations_path", res.get("iterations")), ("all_summary", res.get("all_summary"))):
+            setattr(b, name, None if t is None else t.data_ptr())
+        self._chk(self.lib.pnr_solve_ik_path(self._h, p, b, self._stream()))
+        sm = res["summary"]
+        res.update(tracked=sm[:, 0] > 0, fail_at=sm[:, 1].long(), max_residual=sm[:, 2], max_angle=sm[:, 3], travel=sm[:, 4],
+                   max_jump=sm[:, 5], start=sm[:, 6].long(), tracked_starts=sm[:, 7].long())
         return res
 
     def target_reachable(self, within=None, starts=None):
