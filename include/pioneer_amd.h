@@ -52,7 +52,8 @@ extern "C" {
  *      pnr_set_body_params, pnr_set_body_state, pnr_get_body_state, pnr_render_bodies, pnr_set_body_queries,
  *      pnr_render_cameras, pnr_body_grip_params_default, pnr_set_body_grip_params, pnr_set_body_grip, pnr_get_body_grip,
  *      pnr_ik_multi_params_default, pnr_solve_ik_multi, pnr_path_params_default, pnr_path_clearance,
- *      pnr_ik_path_params_default, pnr_solve_ik_path */
+ *      pnr_ik_path_params_default, pnr_solve_ik_path, pnr_retime_params_default, pnr_retime_workspace_bytes, pnr_retime_path,
+ *      pnr_traj_sample_params_default, pnr_sample_trajectory */
 #define PNR_ABI_VERSION 5
 
 #define PNR_DOF 6          /* revolute joints of pioneer_knm_6dof.urdf:209-264 */
@@ -1079,6 +1080,116 @@ typedef struct pnr_ik_path_buffers {
 } pnr_ik_path_buffers;
 int pnr_ik_path_params_default(pnr_ik_path_params* p, int32_t task);
 int pnr_solve_ik_path(pnr_handle h, const pnr_ik_path_params* p, const pnr_ik_path_buffers* b, void* stream);
+
+/*
+ * Time parameterisation of every env's joint path, one call: WHEN the arm should be at which row of a q_path, rest to rest,
+ * as fast as the joints' velocity, acceleration and (PNR_RETIME_TORQUE) torque limits allow.  The reachability-analysis form of
+ * time-optimal path parameterisation: a backward pass of controllable sets, then a greedy forward pass.  pnr_sample_trajectory
+ * turns the result into the [n][T][12] rows of q | qd that pnr_world_step_targets takes, one row per world step.
+ *   path       points p_k in R^6, k = 0 .. C - 1, C = n_points in 3 .. PNR_MAX_TRAJ_POINTS: q_path [num_envs][C][6]
+ *              (path_per_env != 0) or [C][6], shared; float32, 8-byte aligned — what pnr_solve_ik_path writes and
+ *              pnr_path_clearance reads.  The path coordinate s has grid spacing 1 and q(s) is the linear interpolation between
+ *              grid points.  C = 2 is refused: with x_0 = x_1 = 0 it cannot move under this discretisation.
+ *   differences, one float32 operation each: d_0 = p_1 - p_0, d_(C-1) = p_(C-1) - p_(C-2), else d_k = (p_(k+1) - p_(k-1)) / 2;
+ *              e_0 = e_(C-1) = 0, else e_k = (p_(k+1) - 2 p_k) + p_(k-1).
+ *   unknowns   x_k = sdot^2 at grid point k; u_k = sddot, constant on interval k (k to k + 1): x_(k+1) = x_k + 2 u_k; rest to
+ *              rest, x_0 = x_(C-1) = 0.
+ *   rows       at grid point k = 0 .. C - 2, each |A u + B x + c| <= LIM.  Acceleration, joint j: A = d_kj, B = e_kj, c = 0,
+ *              LIM = a_max[j].  Torque, joint j (PNR_RETIME_TORQUE): A = ID(p_k, 0, d_k) and B = ID(p_k, d_k, e_k) without
+ *              gravity, c = ID(p_k, 0, 0) with the handle's gravity, LIM = tau_max[j]; ID(q, qd, qdd) is pnr_inverse_dynamics
+ *              without joint losses (a dynamics-mode handle: the env's link scales; a kinematic one: the nominal model).
+ *              Velocity: x <= X_k = min over the joints with d_kj != 0 of (v_max[j] / |d_kj|)^2 (the quotient, then its
+ *              square); DECIDED HERE: a grid point where no joint moves (d_k = 0) has X_k = 0 — the path has no speed there.
+ *   backward   K_(C-1) = 0; for k = C - 2 .. 0: K_k = max { x in [0, X_k] : a u exists with every row at k and
+ *              0 <= x + 2u <= K_(k+1) }, evaluated without a division by A: each row's sign is turned so that A >= 0 (A, B, c
+ *              negated where A < 0) and gives a lower line A u >= L - B x, L = -LIM - c, and an upper line A u <= H - B x,
+ *              H = LIM - c; the next state adds the line A = 2, B = 1, L = 0, H = K_(k+1).  Every ordered pair (lower line i,
+ *              upper line j), i != j (a line with itself says 0 <= 2 A LIM), gives slope x <= rhs with slope = A_i B_j - A_j B_i,
+ *              rhs = A_i H_j - A_j L_i (each two products and a difference): slope > 0 bounds x above by rhs / slope, slope < 0
+ *              below, slope == 0 with rhs < 0 makes the set empty.  K_k = the smallest upper bound and X_k; the set is empty
+ *              too when the largest lower bound, or 0, exceeds K_k, and at k = 0 when a lower bound is > 0 (x_0 = 0 must lie in
+ *              it).  7 lines without torque rows, 13 with them.
+ *   forward    x_0 = 0; u = min over the rows with A > 0 of ((LIM - c) - B x_k) / A (none: +inf); x_(k+1) = min(max(x_k + 2u, 0),
+ *              K_(k+1)); the reported u_k = (x_(k+1) - x_k) / 2.
+ *   times      t_0 = 0, t_(k+1) = t_k + 2 / (sqrt(x_k) + sqrt(x_(k+1))), float32, k ascending.
+ *   infeasible an env is infeasible, with k_fail and a pnr_retime_reason, when: a K_k is empty (PNR_RETIME_EMPTY; e.g. |G|
+ *              exceeds tau_max where the arm must be held or lifted: the limits cannot even hold it there) or a coefficient or
+ *              K_k at k is not finite (PNR_RETIME_NONFINITE) — the backward pass reports the first such k it meets, which is
+ *              the LARGEST; or an interval has sqrt(x_k) + sqrt(x_(k+1)) = 0 (PNR_RETIME_STUCK, the smallest such k): three or
+ *              more equal rows in a run, such as the tail pnr_solve_ik_path repeats after c_fail, or an interior stop that
+ *              lasts an interval.  A NaN point makes its own env infeasible and leaves every other env's bits alone; an env's
+ *              result never depends on the batch around it, nor on path_per_env, bit for bit.
+ *   outputs    summary [num_envs][PNR_RETIME_SUMMARY_DIM] float32, 16-byte aligned, required: [0] feasible (1 / 0); [1] the
+ *              duration t_(C-1), +inf when infeasible; [2] k_fail (-1 when feasible); [3] the reason; [4] sqrt of the largest
+ *              x_k; [5] the largest row utilisation |(A u_k + B x_k) + c| / LIM over the rows and k = 0 .. C - 2; [6], [7] 0.
+ *              times, sdot2 [num_envs][C] float32, each or NULL: t_k and x_k.  Rows of an infeasible env: after a backward
+ *              failure (EMPTY, NONFINITE) no forward pass counts — sdot2 is 0 everywhere, times is 0 at k = 0 and +inf after,
+ *              [4] = [5] = 0; when STUCK the whole forward profile is in sdot2 (and in [4], [5]) and times holds t_k for
+ *              k <= k_fail and +inf after.
+ *   workspace  only with PNR_RETIME_TORQUE: pnr_retime_workspace_bytes bytes (n_points x 18 x num_envs floats; 0 without the
+ *              flag), 4-byte aligned, the caller's; it holds the torque rows A[6] | B[6] | c[6] planar, [C][18][num_envs].
+ *   what it is first-order collocation: the rows hold at the grid points for (x_k, u_k).  The result is feasible by
+ *              construction and time-optimal only as the grid is refined.  ON A COARSE GRID THE GREEDY PASS CAN BRING x TO 0 AT
+ *              AN INTERIOR POINT — a stop; a float64 prototype did so on about a third of 17- and 33-point sinusoid paths and on
+ *              none of 256 points.  Not built: boundary speeds other than rest, jerk limits, corner blending, per-env limit
+ *              vectors, C > PNR_MAX_TRAJ_POINTS.
+ * pnr_sample_trajectory: targets [num_envs][n_samples][12] float32, 16-byte aligned, n_samples in 1 .. PNR_MAX_TRAJ_SAMPLES.
+ * Sample i is at tau = t0 + (float)(i + 1) dt (float32: the product, then the sum); k is the interval with t_k <= tau < t_(k+1),
+ * delta = tau - t_k, sigma = sqrt(x_k) delta + (u_k delta^2) / 2 clamped to [0, 1], q = p_k + sigma (p_(k+1) - p_k),
+ * qd = (p_(k+1) - p_k)(sqrt(x_k) + u_k delta), u_k = (x_(k+1) - x_k) / 2.  At and past the duration (summary[1]) the row is
+ * p_(C-1) | 0: it holds.  For an infeasible env (summary[0] == 0) every row is p_0 | 0.  t0 >= 0, dt > 0.  A row is exactly what
+ * pnr_world_step_targets takes for all six joints; windows t0 = 0, T dt, 2 T dt, .. tile a trajectory.
+ * Both calls: PNR_ERR_INVALID, nothing launched and no output touched (the message names the field), for a NULL or wrongly sized
+ * struct, n_points, path_per_env, flags, a limit in use that is not finite and > 0 (also as float32), n_samples, t0, dt, a NULL
+ * required pointer (q_path, summary; workspace with the flag; every pointer of pnr_sample_trajectory) or a misaligned one
+ * (summary, targets 16 bytes; q_path 8; the others 4); with PNR_RETIME_TORQUE on a dynamics-mode handle before its first reset.
+ * float32 arithmetic, asynchronous on `stream`, no allocation, no synchronisation: capturable into a graph.  Both kinds of handle.
+ */
+#define PNR_MAX_TRAJ_POINTS 256
+#define PNR_MAX_TRAJ_SAMPLES 65536
+#define PNR_RETIME_SUMMARY_DIM 8
+#define PNR_RETIME_ROW_DIM 18
+enum pnr_retime_flags {
+    PNR_RETIME_TORQUE = 1
+};
+enum pnr_retime_reason {
+    PNR_RETIME_FEASIBLE = 0,
+    PNR_RETIME_EMPTY = 1,
+    PNR_RETIME_STUCK = 2,
+    PNR_RETIME_NONFINITE = 3
+};
+typedef struct pnr_retime_params {
+    uint32_t struct_size;       /* sizeof(pnr_retime_params) */
+    int32_t  n_points;          /* C: 3 .. PNR_MAX_TRAJ_POINTS; default 3 */
+    int32_t  path_per_env;      /* 1: q_path is [num_envs][C][6]; 0 (default): [C][6], shared */
+    int32_t  flags;             /* pnr_retime_flags; default 0 */
+    double   v_max[6];          /* rad/s, > 0; default 2 */
+    double   a_max[6];          /* rad/s^2, > 0; default 10 */
+    double   tau_max[6];        /* joint torque, > 0 with PNR_RETIME_TORQUE (not read without); default 0: to be set */
+} pnr_retime_params;
+typedef struct pnr_retime_buffers {
+    uint32_t struct_size;       /* sizeof(pnr_retime_buffers) */
+    uint32_t reserved;
+    const float* q_path;        /* [C][6] or [num_envs][C][6], 8-byte aligned */
+    void*    workspace;         /* pnr_retime_workspace_bytes bytes with PNR_RETIME_TORQUE, else not read (NULL is fine) */
+    float*   summary;           /* [num_envs][8], 16-byte aligned */
+    float*   times;             /* [num_envs][C] or NULL */
+    float*   sdot2;             /* [num_envs][C] or NULL */
+} pnr_retime_buffers;
+typedef struct pnr_traj_sample_params {
+    uint32_t struct_size;       /* sizeof(pnr_traj_sample_params) */
+    int32_t  n_points;          /* C of the timed path */
+    int32_t  path_per_env;      /* as pnr_retime_params */
+    int32_t  n_samples;         /* T: 1 .. PNR_MAX_TRAJ_SAMPLES; default 1 */
+    double   t0;                /* >= 0; default 0 */
+    double   dt;                /* > 0; default 10 / 240 (pnr_config_default's timestep x frame_skip: one world step) */
+} pnr_traj_sample_params;
+int pnr_retime_params_default(pnr_retime_params* p);
+int pnr_retime_workspace_bytes(pnr_handle h, const pnr_retime_params* p, uint64_t* bytes);
+int pnr_retime_path(pnr_handle h, const pnr_retime_params* p, const pnr_retime_buffers* b, void* stream);
+int pnr_traj_sample_params_default(pnr_traj_sample_params* p);
+int pnr_sample_trajectory(pnr_handle h, const pnr_traj_sample_params* p, const float* q_path, const float* times, const float* sdot2,
+                          const float* summary, float* targets, void* stream);
 
 /*
  * render('rgb_array') for every env in one launch (bullet_env.py:156-185 -> getCameraImage): one camera shared by all envs,

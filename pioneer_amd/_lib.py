@@ -190,6 +190,31 @@ class PnrIkPathBuffers(C.Structure):
         "iterations_path", "all_summary")]
 
 
+MAX_TRAJ_POINTS, MAX_TRAJ_SAMPLES = 256, 65536      # pnr_retime_path: points of a path; pnr_sample_trajectory: samples of a call
+RETIME_SUMMARY_DIM = 8          # pnr_retime_path: feasible, duration, k_fail, reason, largest sdot, largest row utilisation, 0, 0
+RETIME_ROW_DIM = 18             # .. the torque rows of one (env, grid point) in the workspace: A[6] | B[6] | c[6]
+RETIME_TORQUE = 1               # pnr_retime_params.flags (PNR_RETIME_TORQUE)
+RETIME_FEASIBLE, RETIME_EMPTY, RETIME_STUCK, RETIME_NONFINITE = 0, 1, 2, 3      # summary[3] (enum pnr_retime_reason)
+
+
+class PnrRetimeParams(C.Structure):
+    """pnr_retime_params of include/pioneer_amd.h (pnr_retime_path's path layout, flags and the joints' limits)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_points", C.c_int32), ("path_per_env", C.c_int32), ("flags", C.c_int32),
+                ("v_max", C.c_double * 6), ("a_max", C.c_double * 6), ("tau_max", C.c_double * 6)]
+
+
+class PnrRetimeBuffers(C.Structure):
+    """pnr_retime_buffers of include/pioneer_amd.h (pnr_retime_path's device pointers)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(name, C.c_void_p) for name in (
+        "q_path", "workspace", "summary", "times", "sdot2")]
+
+
+class PnrTrajSampleParams(C.Structure):
+    """pnr_traj_sample_params of include/pioneer_amd.h (pnr_sample_trajectory's path layout and sampling window)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_points", C.c_int32), ("path_per_env", C.c_int32), ("n_samples", C.c_int32),
+                ("t0", C.c_double), ("dt", C.c_double)]
+
+
 class PnrConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
@@ -298,6 +323,11 @@ SIGNATURES = {
     "pnr_solve_ik_multi": (C.c_int, [_VP, C.POINTER(PnrIkMultiParams), C.POINTER(PnrIkMultiBuffers), _VP]),
     "pnr_ik_path_params_default": (C.c_int, [C.POINTER(PnrIkPathParams), C.c_int32]),
     "pnr_solve_ik_path": (C.c_int, [_VP, C.POINTER(PnrIkPathParams), C.POINTER(PnrIkPathBuffers), _VP]),
+    "pnr_retime_params_default": (C.c_int, [C.POINTER(PnrRetimeParams)]),
+    "pnr_retime_workspace_bytes": (C.c_int, [_VP, C.POINTER(PnrRetimeParams), C.POINTER(C.c_uint64)]),
+    "pnr_retime_path": (C.c_int, [_VP, C.POINTER(PnrRetimeParams), C.POINTER(PnrRetimeBuffers), _VP]),
+    "pnr_traj_sample_params_default": (C.c_int, [C.POINTER(PnrTrajSampleParams)]),
+    "pnr_sample_trajectory": (C.c_int, [_VP, C.POINTER(PnrTrajSampleParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "pnr_render": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP]),
     "pnr_render_bodies": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, _VP, _VP, _VP, _VP]),
     "pnr_render_cameras": (C.c_int, [_VP, _VP, C.POINTER(PnrRenderParams), _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
@@ -340,9 +370,9 @@ _ENV_HOST = ["pnr_env_host.h", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr
 UNITS = {
     # the env engine's core: its C ABI but for the queries, and every kernel of pnr_env_kernels.h (126, 96 of them dynamics mode's)
     "pnr_api.hip": ["pnr_api.hip", *_ENV_HOST, "pnr_env_kernels.h"],
-    # the query entry points of the C ABI and their kernels (55: the three scene queries have a per-env-world form each, pnr_query.h; the renderer a per-env-camera form too; six of pnr_path.h)
+    # the query entry points of the C ABI and their kernels (61: the three scene queries have a per-env-world form each, pnr_query.h; the renderer a per-env-camera form too; six of pnr_path.h, four of pnr_retime.h)
     "pnr_queries.hip": ["pnr_queries.hip", *_ENV_HOST, "pnr_query.h", "pnr_links.h", "pnr_render.h", "pnr_ik.h", "pnr_invdyn.h",
-                        "pnr_jointstate.h", "pnr_contacts.h", "pnr_rays.h", "pnr_path.h"],
+                        "pnr_jointstate.h", "pnr_contacts.h", "pnr_rays.h", "pnr_path.h", "pnr_retime.h"],
     "pnr_learn.hip": ["pnr_learn.hip", "pnr_host.h", "pnr_device.h", "pnr_model.h", "pnr_ppo.h", "pnr_mlp.h", "pnr_mlp_forward.h",
                       "pnr_mlp_gather.h", "pnr_mlp_backward.h", "pnr_mlp_wgrad.h", "pnr_mlp_adam.h", "pnr_sampler.h"],
 }

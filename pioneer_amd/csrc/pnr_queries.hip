@@ -1,5 +1,5 @@
 // pnr_queries.hip — the query entry points of the C ABI (include/pioneer_amd.h) and their kernels: link states, Jacobian,
-// inverse dynamics and mass matrix, joint states, the IK solvers, contacts, path clearance, render, ray casts.  A query reads the handle (or the
+// inverse dynamics and mass matrix, joint states, the IK solvers, contacts, path clearance, time parameterisation, render, ray casts.  A query reads the handle (or the
 // caller's joints) and writes the caller's buffers; it never changes an env.  The kernels are the query headers' (pnr_query.h:
 // their shared scaffold); the handle and the host helpers shared with the core unit pnr_api.hip are pnr_env_host.h's.  A unit
 // of its own so that a query's code object holds no step kernel and a change to one recompiles neither.
@@ -20,6 +20,7 @@
 #include "pnr_contacts.h"
 #include "pnr_rays.h"
 #include "pnr_path.h"
+#include "pnr_retime.h"
 
 using namespace pnr;
 
@@ -629,6 +630,126 @@ int pnr_path_clearance(pnr_handle h, const pnr_path_params* p, const float* wayp
         if (sphere) hipLaunchKernelGGL(path_clearance_kernel<S() | kQueryScene>, grid, dim3(kWave), 0, (hipStream_t)stream, X);
         else hipLaunchKernelGGL(path_clearance_kernel<S()>, grid, dim3(kWave), 0, (hipStream_t)stream, A);
     });
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+int pnr_retime_params_default(pnr_retime_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_retime_params_default: null params");
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_retime_params);
+    p->n_points = 3;
+    for (int j = 0; j < kDof; ++j) { p->v_max[j] = 2.0; p->a_max[j] = 10.0; }     // (tau_max: 0, to be set with the torque flag)
+    return PNR_OK;
+}
+
+// the checks of pnr_retime_params that pnr_retime_workspace_bytes and pnr_retime_path share
+static int check_retime_params(pnr_handle h, const char* call, const pnr_retime_params* p)
+{
+    if (!p) return fail(h, PNR_ERR_INVALID, "%s: null params", call);
+    if (p->struct_size != sizeof(pnr_retime_params))
+        return fail(h, PNR_ERR_INVALID, "%s: params struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_retime_params));
+    if (p->n_points < 3 || p->n_points > PNR_MAX_TRAJ_POINTS)
+        return fail(h, PNR_ERR_INVALID, "%s: n_points %d outside 3..%d (two points cannot move under this discretisation)", call, p->n_points,
+                    PNR_MAX_TRAJ_POINTS);
+    if (p->path_per_env != 0 && p->path_per_env != 1) return fail(h, PNR_ERR_INVALID, "%s: path_per_env must be 0 or 1", call);
+    if (p->flags & ~PNR_RETIME_TORQUE) return fail(h, PNR_ERR_INVALID, "%s: unknown flags 0x%x", call, (unsigned)p->flags);
+    const struct { const double* v; const char* name; bool used; } limits[] = {
+        {p->v_max, "v_max", true}, {p->a_max, "a_max", true}, {p->tau_max, "tau_max", (p->flags & PNR_RETIME_TORQUE) != 0}};
+    for (const auto& l : limits)
+        for (int j = 0; l.used && j < kDof; ++j)
+            if (!(std::isfinite(l.v[j]) && l.v[j] > 0 && std::isfinite((float)l.v[j]) && (float)l.v[j] > 0.f))
+                return fail(h, PNR_ERR_INVALID, "%s: %s[%d] must be finite and > 0", call, l.name, j);
+    return PNR_OK;
+}
+
+int pnr_retime_workspace_bytes(pnr_handle h, const pnr_retime_params* p, uint64_t* bytes)
+{
+    const char* call = "pnr_retime_workspace_bytes";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!bytes) return fail(h, PNR_ERR_INVALID, "%s: null bytes", call);
+    if (const int rc = check_retime_params(h, call, p)) return rc;
+    *bytes = (p->flags & PNR_RETIME_TORQUE) ? (uint64_t)p->n_points * kRetimeRowFloats * (uint64_t)h->n * sizeof(float) : 0;
+    return PNR_OK;
+}
+
+int pnr_retime_path(pnr_handle h, const pnr_retime_params* p, const pnr_retime_buffers* b, void* stream)
+{
+    const char* call = "pnr_retime_path";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (const int rc = check_retime_params(h, call, p)) return rc;
+    if (!b) return fail(h, PNR_ERR_INVALID, "%s: null buffers", call);
+    if (b->struct_size != sizeof(pnr_retime_buffers))
+        return fail(h, PNR_ERR_INVALID, "%s: buffers struct_size %u, want %zu", call, b->struct_size, sizeof(pnr_retime_buffers));
+    const bool torque = (p->flags & PNR_RETIME_TORQUE) != 0;
+    if (!b->q_path) return fail(h, PNR_ERR_INVALID, "%s: null q_path", call);
+    if (!b->summary) return fail(h, PNR_ERR_INVALID, "%s: null summary", call);
+    if (torque && !b->workspace) return fail(h, PNR_ERR_INVALID, "%s: null workspace with torque rows", call);
+    if (const int rc = check_aligned(h, call, {{b->summary, "summary", 16}, {b->q_path, "q_path", 8}, {b->workspace, "workspace", 4},
+                                               {b->times, "times", 4}, {b->sdot2, "sdot2", 4}})) return rc;
+    // a dynamics-mode handle's link scales are drawn by the first reset: no model for the torque rows before it
+    if (torque && h->dyn && !has_link_scales(h)) return before_first_reset(h, call, ": the torque rows use the env's link scales");
+    RetimeArgs A;
+    A.q_path = b->q_path; A.dyn = h->dyn; A.rows = torque ? (float*)b->workspace : nullptr;
+    A.summary = b->summary; A.times = b->times; A.sdot2 = b->sdot2;
+    A.n = h->n; A.C = p->n_points; A.per_env = p->path_per_env;
+    A.gravity = (float)h->cfg.gravity;
+    for (int j = 0; j < kDof; ++j) { A.v_max[j] = (float)p->v_max[j]; A.a_max[j] = (float)p->a_max[j]; A.tau_max[j] = torque ? (float)p->tau_max[j] : 1.f; }
+    DeviceGuard g(h->device);
+    const unsigned waves = (unsigned)((h->n + kWave - 1) / kWave);
+    const size_t lds = (size_t)A.C * kWave * sizeof(float);            // K_k per lane: 64 KB at C = 256
+    if (torque) {
+        hipLaunchKernelGGL(retime_rows_kernel, dim3(waves, (unsigned)A.C), dim3(kWave), 0, (hipStream_t)stream, A);
+        HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(retime_pass_kernel<true>, dim3(waves), dim3(kWave), lds, (hipStream_t)stream, A);
+    } else {
+        hipLaunchKernelGGL(retime_pass_kernel<false>, dim3(waves), dim3(kWave), lds, (hipStream_t)stream, A);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return PNR_OK;
+}
+
+int pnr_traj_sample_params_default(pnr_traj_sample_params* p)
+{
+    if (!p) return fail(nullptr, PNR_ERR_INVALID, "pnr_traj_sample_params_default: null params");
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(pnr_traj_sample_params);
+    p->n_points = 3;
+    p->n_samples = 1;
+    p->dt = 10.0 / 240.0;                               // pnr_config_default's timestep x frame_skip: one world step
+    return PNR_OK;
+}
+
+int pnr_sample_trajectory(pnr_handle h, const pnr_traj_sample_params* p, const float* q_path, const float* times, const float* sdot2,
+                          const float* summary, float* targets, void* stream)
+{
+    const char* call = "pnr_sample_trajectory";
+    if (!h) return fail(nullptr, PNR_ERR_INVALID, "null handle");
+    if (!p) return fail(h, PNR_ERR_INVALID, "%s: null params", call);
+    if (p->struct_size != sizeof(pnr_traj_sample_params))
+        return fail(h, PNR_ERR_INVALID, "%s: params struct_size %u, want %zu", call, p->struct_size, sizeof(pnr_traj_sample_params));
+    if (p->n_points < 3 || p->n_points > PNR_MAX_TRAJ_POINTS)
+        return fail(h, PNR_ERR_INVALID, "%s: n_points %d outside 3..%d", call, p->n_points, PNR_MAX_TRAJ_POINTS);
+    if (p->path_per_env != 0 && p->path_per_env != 1) return fail(h, PNR_ERR_INVALID, "%s: path_per_env must be 0 or 1", call);
+    if (p->n_samples < 1 || p->n_samples > PNR_MAX_TRAJ_SAMPLES)
+        return fail(h, PNR_ERR_INVALID, "%s: n_samples %d outside 1..%d", call, p->n_samples, PNR_MAX_TRAJ_SAMPLES);
+    if (!(std::isfinite(p->t0) && p->t0 >= 0)) return fail(h, PNR_ERR_INVALID, "%s: t0 must be finite and >= 0", call);
+    if (!(std::isfinite(p->dt) && (float)p->dt > 0.f && std::isfinite((float)p->dt))) return fail(h, PNR_ERR_INVALID, "%s: dt must be finite and > 0", call);
+    const struct { const void* ptr; const char* name; } need[] = {{q_path, "q_path"}, {times, "times"}, {sdot2, "sdot2"}, {summary, "summary"},
+                                                                  {targets, "targets"}};
+    for (const auto& a : need)
+        if (!a.ptr) return fail(h, PNR_ERR_INVALID, "%s: null %s", call, a.name);
+    if (const int rc = check_aligned(h, call, {{targets, "targets", 16}, {summary, "summary", 16}, {q_path, "q_path", 8}, {times, "times", 4},
+                                               {sdot2, "sdot2", 4}})) return rc;
+    const long long groups = (h->n * (long long)p->n_samples + kWave - 1) / kWave;     // one (env, sample) per lane
+    if (groups > 0x7fffffffLL) return fail(h, PNR_ERR_INVALID, "%s: %lld envs x %d samples exceed one launch", call, h->n, p->n_samples);
+    TrajSampleArgs A;
+    A.q_path = q_path; A.times = times; A.sdot2 = sdot2; A.summary = summary; A.targets = targets;
+    A.n = h->n; A.C = p->n_points; A.per_env = p->path_per_env; A.T = p->n_samples;
+    A.t0 = (float)p->t0; A.dt = (float)p->dt;
+    DeviceGuard g(h->device);
+    hipLaunchKernelGGL(traj_sample_kernel, dim3((unsigned)groups), dim3(kWave), 0, (hipStream_t)stream, A);
     HIP_TRY(h, hipGetLastError());
     return PNR_OK;
 }

@@ -250,6 +250,20 @@ class PioneerKinematicEnv(compat.GymEnv):
         return IkPath(bool(sm[0] > 0), int(sm[1]), res["q_path"][0].double().cpu().numpy(), float(sm[2]), float(sm[3]), float(sm[4]),
                       float(sm[5]))
 
+    def retime_path(self, q_path, v_max, a_max, tau_max=None, dt=None, steps=None):
+        """When the arm should be at which row of the joint path ``q_path`` (``[C, 6]``, or an ``IkPath``), rest to rest, as fast as
+        the joints' velocity, acceleration and (``tau_max``) torque limits allow (PioneerVectorEnv.retime_path).  ``steps`` None:
+        as many world steps of ``dt`` (default timestep x frame_skip) as the duration needs (``scene.steps_for``; this reads the
+        duration back from the device).  Returns a ``Trajectory``."""
+        from .scene import Trajectory, steps_for
+        qp = np.asarray(getattr(q_path, "q_path", q_path), dtype=np.float32).reshape(-1, self.dof)
+        res = self._vec.retime_path(qp, v_max, a_max, tau_max)
+        feasible, duration = bool(res["feasible"][0].item()), float(res["duration"][0].item())
+        step = float(self._vec._c_cfg.timestep * self._vec._c_cfg.frame_skip if dt is None else dt)
+        count = steps_for(duration, step) if steps is None else int(steps)
+        targets = self._vec.sample_trajectory(qp, res["times"], res["sdot2"], res["summary"], count, dt=step)
+        return Trajectory(feasible, duration, res["times"][0].double().cpu().numpy(), targets[0].double().cpu().numpy())
+
     def target_reachable(self, within=None, starts=None) -> bool:
         """Can the pointer get within ``within`` (default ``done_distance``) of the env's target inside the joint limits
         (PioneerVectorEnv.target_reachable)?  ``starts`` None: from the rest pose alone; else the best of that many starts."""

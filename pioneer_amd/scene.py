@@ -184,6 +184,26 @@ class IkPath(NamedTuple):
     max_jump: float
 
 
+class Trajectory(NamedTuple):
+    """``PioneerKinematicEnv.retime_path``'s answer for the one env: do the limits admit the path at all, the time it takes (s; inf
+    when not), the time at every row of the joint path (float64 ``[C]``) and the motor-target rows q | q̇ (float64 ``[steps, 12]``,
+    one per world step; past the end they hold the last point, an infeasible path's hold the first)."""
+    feasible: bool
+    duration: float
+    times: np.ndarray
+    targets: np.ndarray
+
+
+def steps_for(duration: float, dt: float) -> int:
+    """How many samples at dt, 2 dt, .. cover a trajectory of ``duration``: the smallest count whose last sample is at or past the
+    end, and so the trajectory's last point (at least 1).  A duration that is not finite (an infeasible path) gives 1."""
+    if not (dt > 0):
+        raise AssertionError(f"dt must be > 0, got {dt}")
+    if not np.isfinite(duration) or duration <= 0:
+        return 1
+    return max(1, int(np.ceil(float(duration) / float(dt))))
+
+
 class PathClearance(NamedTuple):
     """``Scene.path_clearance``'s answer for the one env: is the sampled path free, the smallest clearance on it, the path
     coordinate t where it is attained (segment index + fraction), the URDF link and the created body (``Scene.body_id``; 0 where

@@ -780,6 +780,107 @@ class PioneerVectorEnv:
                    max_jump=sm[:, 5], start=sm[:, 6].long(), tracked_starts=sm[:, 7].long())
         return res
 
+    @staticmethod
+    def _limits(p_field, value, name):
+        """a scalar or six numbers into a params struct's double[6]"""
+        v = np.asarray(value.detach().cpu().numpy() if isinstance(value, torch.Tensor) else value, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.full(6, float(v))
+        if v.shape != (6,):
+            raise AssertionError(f"{name} must be a number or six of them, got shape {v.shape}")
+        for j in range(6):
+            p_field[j] = float(v[j])
+
+    def _timed_path(self, q_path):
+        n = self.num_envs
+        if not isinstance(q_path, torch.Tensor):
+            q_path = torch.as_tensor(np.asarray(q_path), dtype=torch.float32)
+        if q_path.dim() not in (2, 3) or q_path.shape[-1] != 6 or (q_path.dim() == 3 and q_path.shape[0] != n):
+            raise AssertionError(f"q_path must have shape (C, 6) or ({n}, C, 6), got {tuple(q_path.shape)}")
+        return self._in(q_path, tuple(q_path.shape), torch.float32, "q_path")
+
+    def retime_path(self, q_path, v_max, a_max, tau_max=None, dt=None, steps=None, t0=0.0, profile=True, out=None):
+        """Time parameterisation of every env's joint path, one call (pnr_retime_path): when the arm should be at which row of
+        ``q_path``, rest to rest, as fast as the limits allow — time-optimal path parameterisation by reachability analysis (a
+        backward pass of controllable sets, a greedy forward pass) on the path's own grid; the law is include/pioneer_amd.h's.
+
+        ``q_path``: float32 ``[C, 6]`` (one path for all envs) or ``[N, C, 6]``, 3 <= C <= 256 — what ``solve_ik_path`` returns and
+        ``path_clearance`` takes.  ``v_max``, ``a_max``: the joints' velocity and acceleration limits, a number or six; ``tau_max``
+        (None: no torque rows) the joint-torque limits: the rows ``|M(q) q̈ + C q̇ + G| <= tau_max`` on the model ``inverse_dynamics``
+        evaluates (dynamics mode: each env's link scales and the config's gravity), so the answer differs per env and payload.
+
+        Returns a dict of device tensors: ``summary`` ``[N, 8]`` and its columns as views or small casts — ``feasible`` (bool),
+        ``duration`` (+inf when infeasible), ``fail_at`` (int64 grid index, -1), ``reason`` (int64, ``_lib.RETIME_*``: empty
+        controllable set, stuck, not finite), ``max_sdot``, ``utilisation`` (the largest row value over its limit: 1 up to float32
+        where a limit is active) — and with ``profile`` ``times`` and ``sdot2`` ``[N, C]`` (t_k and ṡ² at the grid points).  With
+        ``steps`` (an int, see ``scene.steps_for``) also ``targets`` ``[N, steps, 12]``: the rows q | q̇ at t0 + (i + 1) dt,
+        ``dt`` defaulting to the handle's timestep x frame_skip (one world step), each what ``world_step(motor_targets=…)``
+        takes; past the end they hold the last point, and an infeasible env's rows hold the first.  ``out`` may carry
+        preallocated ``summary`` / ``times`` / ``sdot2`` / ``targets`` tensors, written in place.  The torque rows' workspace is
+        cached per (C, N).  Never synchronises.  A coarse grid can make the arm stop inside the path (DESIGN 3aa)::
+
+            res = env.solve_ik_path(line, substeps=8, from_current=True)
+            timed = env.retime_path(res["q_path"], 2.0, 10.0, tau_max=700.0, steps=240)
+            for i in range(240):
+                env.world_step(motor_targets=timed["targets"][:, i])
+        """
+        self._check_handle()
+        n = self.num_envs
+        qp = self._timed_path(q_path)
+        p = _lib.PnrRetimeParams()
+        self._chk(self.lib.pnr_retime_params_default(p))
+        p.n_points, p.path_per_env = int(qp.shape[-2]), int(qp.dim() == 3)
+        self._limits(p.v_max, v_max, "v_max")
+        self._limits(p.a_max, a_max, "a_max")
+        if tau_max is not None:
+            p.flags = _lib.RETIME_TORQUE
+            self._limits(p.tau_max, tau_max, "tau_max")
+        Cn = p.n_points
+        need = profile or steps is not None
+        res = self._asked(out, (("summary", True, (n, _lib.RETIME_SUMMARY_DIM), torch.float32), ("times", need, (n, Cn), torch.float32),
+                                ("sdot2", need, (n, Cn), torch.float32)), "")
+        b = _lib.PnrRetimeBuffers()
+        b.struct_size = C.sizeof(_lib.PnrRetimeBuffers)
+        ws = None
+        if tau_max is not None:
+            nbytes = C.c_uint64(0)
+            self._chk(self.lib.pnr_retime_workspace_bytes(self._h, p, C.byref(nbytes)))
+            cache = self.__dict__.setdefault("_retime_workspaces", {})
+            if (Cn, n) not in cache:
+                cache[(Cn, n)] = self._new((int(nbytes.value) // 4,))
+            ws = cache[(Cn, n)]
+        for name, t in (("q_path", qp), ("workspace", ws), ("summary", res["summary"]), ("times", res.get("times")), ("sdot2", res.get("sdot2"))):
+            setattr(b, name, None if t is None else t.data_ptr())
+        self._chk(self.lib.pnr_retime_path(self._h, p, b, self._stream()))
+        sm = res["summary"]
+        res.update(feasible=sm[:, 0] > 0, duration=sm[:, 1], fail_at=sm[:, 2].long(), reason=sm[:, 3].long(), max_sdot=sm[:, 4],
+                   utilisation=sm[:, 5])
+        if steps is not None:
+            res["targets"] = self.sample_trajectory(qp, res["times"], res["sdot2"], sm, steps, dt=dt, t0=t0,
+                                                    out=None if out is None else out.get("targets"))
+        return res
+
+    def sample_trajectory(self, q_path, times, sdot2, summary, steps, dt=None, t0=0.0, out=None):
+        """Another window of an already timed path (pnr_sample_trajectory): float32 ``[N, steps, 12]`` rows q | q̇ at
+        t0 + (i + 1) dt, i = 0 .. steps - 1, from ``retime_path``'s ``times``, ``sdot2`` and ``summary`` of the same ``q_path``.
+        ``dt`` None: the handle's timestep x frame_skip.  Windows t0 = 0, steps dt, 2 steps dt, .. tile the trajectory.  Past
+        the duration a row is the last point at rest; an infeasible env's rows are the first point at rest.  Never synchronises."""
+        self._check_handle()
+        n = self.num_envs
+        qp = self._timed_path(q_path)
+        Cn = int(qp.shape[-2])
+        p = _lib.PnrTrajSampleParams()
+        self._chk(self.lib.pnr_traj_sample_params_default(p))
+        p.n_points, p.path_per_env, p.n_samples = Cn, int(qp.dim() == 3), int(steps)
+        p.t0 = float(t0)
+        p.dt = float(self._c_cfg.timestep * self._c_cfg.frame_skip if dt is None else dt)
+        tm = self._in(times, (n, Cn), torch.float32, "times")
+        xs = self._in(sdot2, (n, Cn), torch.float32, "sdot2")
+        sm = self._in(summary, (n, _lib.RETIME_SUMMARY_DIM), torch.float32, "summary")
+        res = self._out(out, "targets", (n, max(int(steps), 1), 12))
+        self._chk(self.lib.pnr_sample_trajectory(self._h, p, _ptr(qp), _ptr(tm), _ptr(xs), _ptr(sm), _ptr(res), self._stream()))
+        return res
+
     def target_reachable(self, within=None, starts=None):
         """bool ``[N]``: can the pointer get within ``within`` (default the config's ``done_distance``) of the env's own target
         without leaving the joint limits?  ``solve_ik()`` from the rest pose with all defaults; about 3 % of the reference's
