@@ -15,8 +15,8 @@ import ppo_loss_ref as lref
 
 IN, IN_PAD, HID, HEAD = 137, 144, 256, 16
 WG_CHUNK, MAX_SLICES = 64, 32
-# the power-of-two scales of the fp16 planes (planes = 2): activations, net inputs; gradients: grad_scale(B)
-SCALE_ACT, SCALE_INPUT = 2.0 ** 8, 2.0 ** 4
+# the power-of-two scales of the fp16 planes (planes = 2): activations, net inputs, weights (Fmt<2>::kSW); gradients: grad_scale(B)
+SCALE_ACT, SCALE_INPUT, SCALE_WEIGHT = 2.0 ** 8, 2.0 ** 4, 2.0 ** 8
 
 
 def bf(x):
@@ -93,11 +93,11 @@ def gemm_ref(a, b):
 def planes_to_f64(buf, planes, kind, B):
     """The float64 value a stored 16-bit operand buffer [planes, ...] (bf16 element type) stands for: planes = 1 the bf16 value,
     3 the sum of the three bf16 planes, 2 the sum of the two fp16 planes over the tensor's power-of-two scale — kind "act"
-    (2^8), "input" (2^4) or "grad" (grad_scale(B))."""
+    (2^8), "input" (2^4), "weight" (2^8) or "grad" (grad_scale(B))."""
     assert buf.dtype == torch.bfloat16 and buf.shape[0] == planes and planes in (1, 2, 3)
     if planes != 2:
         return buf.double().sum(0)                     # (a sum of at most three bf16 numbers is exact in float64)
-    scale = {"act": SCALE_ACT, "input": SCALE_INPUT, "grad": grad_scale(B)}[kind]
+    scale = {"act": SCALE_ACT, "input": SCALE_INPUT, "weight": SCALE_WEIGHT, "grad": grad_scale(B)}[kind]
     return buf.view(torch.float16).double().sum(0) / scale
 
 
@@ -105,7 +105,7 @@ def split_planes(v, planes, kind, B):
     """The CPU statement of the kernels' split of float32 values into [planes, ...] 16-bit planes (bf16 element type)."""
     v = v.float()
     if planes == 2:
-        scale = {"act": SCALE_ACT, "input": SCALE_INPUT, "grad": grad_scale(B)}[kind]
+        scale = {"act": SCALE_ACT, "input": SCALE_INPUT, "weight": SCALE_WEIGHT, "grad": grad_scale(B)}[kind]
         s = torch.clamp(v * scale, -65504.0, 65504.0)
         p0 = s.to(torch.float16)
         p1 = (s - p0.float()).to(torch.float16)
